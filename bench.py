@@ -15,15 +15,18 @@ region (it is host Tier-2 + PCIe work, like the single-GPU finish()).
 
 `python bench.py --gpus N` with N > 1 and no launcher around it starts its N ranks itself (self_launch: the driver's own
 torch.distributed.run line on 127.0.0.1) and fails loudly when the node has fewer GPUs; under a launcher --gpus must equal
-WORLD_SIZE.  Every default run (any N) also carries `strong_scaling_c4`: the 16K x 16K frame in 256 tiles sharded over
+WORLD_SIZE.  Every --full run (any N) also carries `strong_scaling_c4`: the 16K x 16K frame in 256 tiles sharded over
 the ranks, with the RCCL gatherv of the tile-parts timed on its own -- one 1/2/4/8 sweep answers both the replica
 (weak) and the tile-sharded (strong) question of north_star.
 
-Prints ONE JSON line (rank 0).  Extra objects on that line:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline figure
+(`value`, `ms_per_step`); --dump-outputs DIR also writes what the last timed step computed.  --full adds everything that
+takes runs or checks of its own: the timed region verified after it ran, per-kernel timings, the two-stream and no-overlap
+runs, the frame pipelines, strong_scaling_c4, and these objects:
   roofline     -- the dominant kernel of the step against the HBM roofline, from live HIP-event
                   timings on the codec's own stream (algorithmic bytes: SURVEY.md section 8(d))
-  cpu_baseline -- the reference library itself (oracle/_ref, built from /root/reference) timed
-                  on this box's host CPU, single thread (the library is single-threaded)
+  cpu_baseline -- the reference library itself (oracle/_ref, built by oracle/Makefile) timed
+                  on the host CPU, single thread (the library is single-threaded)
 """
 import argparse
 import json
@@ -59,6 +62,30 @@ WORKLOAD_EXTRA = {          # what a workload needs beyond the tuple: make_param
     "c6_4k_gray_32b_rev53": dict(container=32),
     "c7_4k_444_12b_atk97": dict(params=dict(atk=ATK97, wavelet=2)),
 }
+
+DUMP_MAX_ENTRIES = 1 << 22     # per array of --dump-outputs: 16 MiB as float32, 32 MiB as float64 (48 MiB in all at most)
+
+
+def dump_outputs(out_dir, arrays, seed=1234):
+    """--dump-outputs: {name: (1-D array or device tensor, dtype)} -> out_dir/<name>.npy.  An array of more than
+    DUMP_MAX_ENTRIES entries is replaced by a stratified sample of that many: entry i comes from the i-th of DUMP_MAX_ENTRIES
+    equal slices, at an offset drawn from a generator seeded with `seed` -- the same positions in every run, for every array
+    of the same length."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (a, dtype) in arrays.items():
+        n = int(a.shape[0])
+        idx = None
+        if n > DUMP_MAX_ENTRIES:
+            stride = n // DUMP_MAX_ENTRIES
+            idx = np.arange(DUMP_MAX_ENTRIES, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, DUMP_MAX_ENTRIES)
+        if hasattr(a, "cpu"):                    # a device tensor: sampled where it lies, then fetched
+            if idx is not None:
+                import torch
+                a = a[torch.from_numpy(idx).to(a.device)]
+            a = a.cpu().numpy()
+        elif idx is not None:
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
 
 
 def workload_image(name, seed_offset=0, frame=0):
@@ -136,12 +163,23 @@ def main():
     ap.add_argument("--calibrate", action="store_true",
                     help="also launch one elementwise kernel of known traffic (PMC unit calibration)")
     ap.add_argument("--plain", action="store_true",
-                    help="only the timed steps and their per-launch event timings (no two-stream / no-overlap objects, pipelines, "
-                         "strong-scaling part): what the rocprofv3 passes run, so that a trace holds ONE schedule of every launch")
+                    help="with --full: only the timed steps and their per-launch event timings (no two-stream / no-overlap objects, "
+                         "pipelines, strong-scaling part), so that a trace holds ONE schedule of every launch")
     ap.add_argument("--no-strong", action="store_true",
                     help="skip the strong-scaling sub-measurement (the 16K x 16K frame in 256 tiles sharded over the ranks)")
     ap.add_argument("--strong-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel timings and the roofline objects, the checks of the timed "
+                         "region (last step against the first encode and the reference's digests), the two-stream and no-overlap runs, "
+                         "the frame pipelines, the strong-scaling part and the CPU baselines.  Without it a run sets up, warms up, times "
+                         "the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: decoded.npy (the decoded "
+                         "samples) and codestream.npy (the codestream's bytes), float32 (float64 for 32-bit containers); an array "
+                         "of more than %d entries is replaced by a fixed, seeded sample of that many" % DUMP_MAX_ENTRIES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.plain:
         args.no_strong = True; args.e2e_frames = 0
 
@@ -158,7 +196,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # the all-core CPU figure forks worker processes: done first, before this process owns a GPU context
     cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:          # (the CPU figures belong to the N = 1 line)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:          # (the CPU figures belong to the N = 1 line)
         w_, h_, nc_, bd_, rev_, ct_, qstep_, _tile = WORKLOADS[args.workload]
         try:
             cpu_all = cpu_baseline_all_cores(workload_image(args.workload), bd_, rev_, ct_, qstep_, _tile)
@@ -283,7 +321,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     d_out.zero_()                                # the timed steps must produce the frame again (checked after the loop)
-    _, epoch0 = dec.giveup_epoch()               # (synchronises)
+    if args.full:
+        _, epoch0 = dec.giveup_epoch()           # (synchronises)
     torch.cuda.synchronize(dev)
     step_events = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if os.environ.get("OJPH_BENCH_STEP_EVENTS") else None
     t0 = time.perf_counter()
@@ -302,44 +341,60 @@ def main():
     if step_events:
         sys.stderr.write("timed region %.3f ms, enqueued after %.3f ms; per step (ms): %s\n" % (elapsed * 1e3, t_enq * 1e3, " ".join(
             "%.3f" % step_events[i].elapsed_time(step_events[i + 1]) for i in range(min(args.steps, 40)))))
-    # What the timed steps produced, checked AFTER them: the last step's decode is collected (block verdicts; a one-launch
-    # block decoder whose wait ran out would be repeated here and counted), no timed run gave up un-noticed (the give-up epoch
-    # of the decoder object, bracketing the loop), the samples of the LAST timed step against the input, and the coded size.
-    giveup1, epoch1 = dec.giveup_epoch()
-    failed_after = dec.failed_blocks()
-    retries_after = dec.fused_retries()
-    err_after = roundtrip_err()
-    assert failed_after == 0 or os.environ.get("OJPH_BENCH_NOCHECK"), "timed region: decode failed for %d code-blocks" % failed_after
-    assert err_after == err or os.environ.get("OJPH_BENCH_NOCHECK"), "timed region: round-trip error %d, was %d before it" % (err_after, err)
-    assert enc.coded_bytes() == coded_bytes, "timed region: the encoder's coded size changed"
-    # ... and the codestream (tiled: this rank's tile-parts) the LAST timed encode produced: the bytes of the first one,
-    # which the decoder above decodes and which the parity tests compare with the reference's
-    import hashlib
-    if tiled:
-        last_part, _ = enc.finish_tiles()
-        first_part = part.cpu().numpy().tobytes() if hasattr(part, "cpu") else bytes(part)
-        cs_same = bytes(last_part) == first_part
-        cs_digest = hashlib.sha256(bytes(last_part)).hexdigest()
-    else:
-        last_cs = enc.finish() if frames == 1 else [enc.finish(f) for f in range(frames)]
-        cs_same = last_cs == cs
-        cs_digest = hashlib.sha256(last_cs if frames == 1 else b"".join(last_cs)).hexdigest()
-    assert cs_same, "timed region: the last timed encode's codestream differs from the first encode's"
-    # rank 0's frame of C2 / C3 is the survey's known-answer frame: the reference's own codestream and decoded samples
-    # (digests in tests/golden/survey_ka.json, made by tests/golden/make_survey_ka.py from the reference built here)
-    ref_cs = ref_dec = None
-    if rank == 0 and frames == 1 and not tiled and args.workload[:2] in ("c2", "c3"):
-        gold = json.load(open(os.path.join(ROOT, "tests", "golden", "survey_ka.json")))[args.workload[:2]]
-        gold = gold.get("generic", gold)
-        ref_cs = bool(len(last_cs) == gold["bytes"] and cs_digest == gold["sha256"])
-        if "decoded_sha256" in gold:
-            ref_dec = bool(hashlib.sha256(np.ascontiguousarray(d_out.cpu().numpy().astype(np.int32)).tobytes()).hexdigest() == gold["decoded_sha256"])
-        assert ref_cs and ref_dec is not False, "timed region: codestream / decoded samples are not the reference's (tests/golden/survey_ka.json)"
-    verified = {"verified_after_timing": True, "failed_blocks": int(failed_after), "fused_retries": int(retries_after),
-                "fused_runs_timed": int(epoch1 - epoch0), "fused_giveups_in_timed_region": bool(giveup1 > epoch0),
-                "roundtrip_max_abs_err_last_step": int(err_after), "coded_bytes_last_step": int(coded_bytes),
-                "codestream_last_step_equals_first": bool(cs_same), "codestream_last_step_sha256": cs_digest,
-                "codestream_last_step_equals_reference_digest": ref_cs, "decoded_last_step_equals_reference_digest": ref_dec}
+
+    def last_codestream():
+        """what the LAST timed encode produced: the codestream (a batch: one per frame; tiled: this rank's tile-parts)"""
+        if tiled:
+            return bytes(enc.finish_tiles()[0])
+        return enc.finish() if frames == 1 else [enc.finish(f) for f in range(frames)]
+    last_cs = None
+    verified = {}
+    if args.full:
+        # What the timed steps produced, checked AFTER them: the last step's decode is collected (block verdicts; a one-launch
+        # block decoder whose wait ran out would be repeated here and counted), no timed run gave up un-noticed (the give-up epoch
+        # of the decoder object, bracketing the loop), the samples of the LAST timed step against the input, and the coded size.
+        giveup1, epoch1 = dec.giveup_epoch()
+        failed_after = dec.failed_blocks()
+        retries_after = dec.fused_retries()
+        err_after = roundtrip_err()
+        assert failed_after == 0 or os.environ.get("OJPH_BENCH_NOCHECK"), "timed region: decode failed for %d code-blocks" % failed_after
+        assert err_after == err or os.environ.get("OJPH_BENCH_NOCHECK"), "timed region: round-trip error %d, was %d before it" % (err_after, err)
+        assert enc.coded_bytes() == coded_bytes, "timed region: the encoder's coded size changed"
+        # ... and the codestream (tiled: this rank's tile-parts) the LAST timed encode produced: the bytes of the first one,
+        # which the decoder above decodes and which the parity tests compare with the reference's
+        import hashlib
+        last_cs = last_codestream()
+        if tiled:
+            first_part = part.cpu().numpy().tobytes() if hasattr(part, "cpu") else bytes(part)
+            cs_same = last_cs == first_part
+            cs_digest = hashlib.sha256(last_cs).hexdigest()
+        else:
+            cs_same = last_cs == cs
+            cs_digest = hashlib.sha256(last_cs if frames == 1 else b"".join(last_cs)).hexdigest()
+        assert cs_same, "timed region: the last timed encode's codestream differs from the first encode's"
+        # rank 0's frame of C2 / C3 is the survey's known-answer frame: the reference's own codestream and decoded samples
+        # (digests in tests/golden/survey_ka.json, made by tests/golden/make_survey_ka.py from the reference)
+        ref_cs = ref_dec = None
+        if rank == 0 and frames == 1 and not tiled and args.workload[:2] in ("c2", "c3"):
+            gold = json.load(open(os.path.join(ROOT, "tests", "golden", "survey_ka.json")))[args.workload[:2]]
+            gold = gold.get("generic", gold)
+            ref_cs = bool(len(last_cs) == gold["bytes"] and cs_digest == gold["sha256"])
+            if "decoded_sha256" in gold:
+                ref_dec = bool(hashlib.sha256(np.ascontiguousarray(d_out.cpu().numpy().astype(np.int32)).tobytes()).hexdigest() == gold["decoded_sha256"])
+            assert ref_cs and ref_dec is not False, "timed region: codestream / decoded samples are not the reference's (tests/golden/survey_ka.json)"
+        verified = {"verified_after_timing": True, "failed_blocks": int(failed_after), "fused_retries": int(retries_after),
+                    "fused_runs_timed": int(epoch1 - epoch0), "fused_giveups_in_timed_region": bool(giveup1 > epoch0),
+                    "roundtrip_max_abs_err_last_step": int(err_after), "coded_bytes_last_step": int(coded_bytes),
+                    "codestream_last_step_equals_first": bool(cs_same), "codestream_last_step_sha256": cs_digest,
+                    "codestream_last_step_equals_reference_digest": ref_cs, "decoded_last_step_equals_reference_digest": ref_dec}
+    if args.dump_outputs and rank == 0:
+        if last_cs is None:                      # (no --full) the last run is collected first, as a caller does before reading it
+            failed_after = dec.failed_blocks()
+            assert failed_after == 0 or os.environ.get("OJPH_BENCH_NOCHECK"), "timed region: decode failed for %d code-blocks" % failed_after
+            last_cs = last_codestream()
+        dump_outputs(args.dump_outputs, {
+            "decoded": (d_out.reshape(-1), np.float64 if args.container == 32 else np.float32),
+            "codestream": (np.frombuffer(last_cs if isinstance(last_cs, bytes) else b"".join(last_cs), dtype=np.uint8), np.float32)})
     per_rank_ms = [round(elapsed * 1e3 / args.steps, 4)]
     if world > 1:                                # every rank's own time travels: a straggler shows; value uses the maximum
         t = torch.zeros(world, dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -355,6 +410,43 @@ def main():
             torch.add(a, 1.0, out=b)
         torch.cuda.synchronize(dev)
         del a, b
+    # bytes of a working sample: 4 (int32 / float planes); 8 on the reference's 64-bit sample path (components of more than
+    # 32 bits of precision: int64 planes, SURVEY.md section 8(f) N4) -- the algorithmic bytes of 8(d) with that element size
+    elem = 8.0 if any(plan.comp_style(c)["wide"] for c in range(nc)) else 4.0
+    result = {
+        "metric": "Msamples/s encode+decode, 8K 12-bit 4:4:4; achieved HBM GB/s vs roofline",
+        "value": round(nsamples * (1 if tiled else world) / (ms_per_step * 1e-3) / 1e6, 2),
+        "unit": "Msamples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": settle,
+        "ms_per_step": round(ms_per_step, 4),
+        "per_rank_ms_per_step": per_rank_ms,
+        "higher_is_better": True, "scaling": "strong" if tiled else "weak", "vs_baseline": None,
+        "dtype": ("i64" if elem == 8 else "i32") if rev else "f32", "data": "synthetic",
+        "value_covers": "device-resident step: samples in HBM -> convert + DWT + quantise + HT block encode -> coded block bytes in HBM, "
+                        "then those bytes -> HT block decode + inverse DWT + convert -> samples in HBM; PCIe and host Tier-2 are "
+                        "outside (e2e_steady_Msamples_s has them inside)",
+        "config": {"workload": args.workload, "width": w, "height": h, "components": nc, "bit_depth": bd,
+                   "wavelet": ("5/3 reversible" if rev else "9/7 irreversible") + (" as an ATK marker segment (general lifting kernels)" if "params" in extra else "")
+                              + (", 64-bit sample path" if elem == 8 else ""), "qstep": qstep if not rev else None,
+                   "decomps": levels, "block": [int(params.block_w), int(params.block_h)],
+                   "tile": list(tile), "frames_per_step": frames * (1 if tiled else world),
+                   "sharding": ("%d tiles per GPU of one frame" % my_tiles[1]) if tiled else "one frame per GPU (replicas)",
+                   "hip_streams": args.streams, "sample_container_bits": args.container,
+                   "coded_bytes_per_sample": round(c_rate, 4),
+                   "e2e_first_encode_s_incl_pcie_tier2": round(t_e2e_enc, 3),
+                   "roundtrip_max_abs_err": int(err)},
+    }
+    result["dist"] = {"backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
+                      "world_size": dist.get_world_size() if world > 1 else 1,
+                      "devices": torch.cuda.device_count(), "one_gpu_smoke": bool(os.environ.get("OJPH_BENCH_ONE_GPU"))}
+    if dist_info:
+        result["dist"].update(dist_info)
+    if not args.full:                            # the headline figure is all a plain run measures
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # per-kernel timings: HIP events on the codec's own stream, averaged over a second run of the
     # same steps (reading the events synchronises, so it is kept out of the timed region above)
@@ -374,9 +466,6 @@ def main():
         for k, v in acc.items():
             acc[k] = [x / reps for x in v] if isinstance(v, list) else v / reps
     ns = nsamples_rank
-    # bytes of a working sample: 4 (int32 / float planes); 8 on the reference's 64-bit sample path (components of more than
-    # 32 bits of precision: int64 planes, SURVEY.md section 8(f) N4) -- the algorithmic bytes of 8(d) with that element size
-    elem = 8.0 if any(plan.comp_style(c)["wide"] for c in range(nc)) else 4.0
     kernels = {
         "dwt_forward(all levels)": (dwt_alg_bytes(ns, levels, args.container, elem), te["dwt_ms"]),
         "dwt_forward(level 1)": ((elem + args.container / 8.0) * ns, te["dwt_levels_ms"][0] if te["dwt_levels_ms"] else 0.0),
@@ -556,53 +645,26 @@ def main():
             else:
                 strong = box.get("r")
 
-    result = {
-        "metric": "Msamples/s encode+decode, 8K 12-bit 4:4:4; achieved HBM GB/s vs roofline",
-        "value": round(nsamples * (1 if tiled else world) / (ms_per_step * 1e-3) / 1e6, 2),
-        "unit": "Msamples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": settle,
-        "ms_per_step": round(ms_per_step, 4),
-        "per_rank_ms_per_step": per_rank_ms,
-        "higher_is_better": True, "scaling": "strong" if tiled else "weak", "vs_baseline": None,
-        "dtype": ("i64" if elem == 8 else "i32") if rev else "f32", "data": "synthetic",
-        "value_covers": "device-resident step: samples in HBM -> convert + DWT + quantise + HT block encode -> coded block bytes in HBM, "
-                        "then those bytes -> HT block decode + inverse DWT + convert -> samples in HBM; PCIe and host Tier-2 are "
-                        "outside (e2e_steady_Msamples_s has them inside)",
-        "e2e_steady_Msamples_s": ({k: v["Msamples_s"] for k, v in e2e.items() if isinstance(v, dict) and "Msamples_s" in v} if e2e and "error" not in e2e else None),
-        "config": {"workload": args.workload, "width": w, "height": h, "components": nc, "bit_depth": bd,
-                   "wavelet": ("5/3 reversible" if rev else "9/7 irreversible") + (" as an ATK marker segment (general lifting kernels)" if "params" in extra else "")
-                              + (", 64-bit sample path" if elem == 8 else ""), "qstep": qstep if not rev else None,
-                   "decomps": levels, "block": [int(params.block_w), int(params.block_h)],
-                   "tile": list(tile), "frames_per_step": frames * (1 if tiled else world),
-                   "sharding": ("%d tiles per GPU of one frame" % my_tiles[1]) if tiled else "one frame per GPU (replicas)",
-                   "hip_streams": args.streams, "sample_container_bits": args.container,
-                   "coded_bytes_per_sample": round(c_rate, 4),
-                   "encode_ms": round(te["total_ms"], 4), "decode_ms": round(td["total_ms"], 4),
-                   "encode_Msamples_s": round(ns / te["total_ms"] / 1e3, 1),
-                   "decode_Msamples_s": round(ns / td["total_ms"] / 1e3, 1),
-                   "e2e_first_encode_s_incl_pcie_tier2": round(t_e2e_enc, 3),
-                   "roundtrip_max_abs_err": int(err),
-                   "two_streams_ms_per_step": round(two_stream_ms, 4) if two_stream_ms else None,
-                   "two_streams_Msamples_s": round(nsamples / two_stream_ms / 1e3, 2) if two_stream_ms else None},
-        # achieved = SURVEY.md section 8(d)'s algorithmic bytes of the launch / its measured duration; what the launch moves
-        # beyond them (records handed from step 1 to step 2, halo re-reads) shows in `traffic` and `traffic_ratio`
-        "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "algorithmic_bytes": int(dom_b), "intermediate_bytes": int(intermediate.get(dom, 0)),
-                     "traffic_ratio": round(traffic / dom_b, 3) if traffic and dom_b else None,
-                     "traffic_source": "profiles/pmc_traffic.json (%s)" % pmc_state},
-        "kernels": kinfo,
-    }
+    result["e2e_steady_Msamples_s"] = ({k: v["Msamples_s"] for k, v in e2e.items() if isinstance(v, dict) and "Msamples_s" in v}
+                                       if e2e and "error" not in e2e else None)
+    result["config"].update({"encode_ms": round(te["total_ms"], 4), "decode_ms": round(td["total_ms"], 4),
+                             "encode_Msamples_s": round(ns / te["total_ms"] / 1e3, 1),
+                             "decode_Msamples_s": round(ns / td["total_ms"] / 1e3, 1),
+                             "two_streams_ms_per_step": round(two_stream_ms, 4) if two_stream_ms else None,
+                             "two_streams_Msamples_s": round(nsamples / two_stream_ms / 1e3, 2) if two_stream_ms else None})
+    # achieved = SURVEY.md section 8(d)'s algorithmic bytes of the launch / its measured duration; what the launch moves
+    # beyond them (records handed from step 1 to step 2, halo re-reads) shows in `traffic` and `traffic_ratio`
+    result["roofline"] = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                          "algorithmic_bytes": int(dom_b), "intermediate_bytes": int(intermediate.get(dom, 0)),
+                          "traffic_ratio": round(traffic / dom_b, 3) if traffic and dom_b else None,
+                          "traffic_source": "profiles/pmc_traffic.json (%s)" % pmc_state}
+    result["kernels"] = kinfo
     result.update(verified)
     if e2e:
         result["e2e"] = e2e
     if strong:
         result["strong_scaling_c4"] = strong
-    result["dist"] = {"backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
-                      "world_size": dist.get_world_size() if world > 1 else 1,
-                      "devices": torch.cuda.device_count(), "one_gpu_smoke": bool(os.environ.get("OJPH_BENCH_ONE_GPU"))}
-    if dist_info:
-        result["dist"].update(dist_info)
     rv = roofline_valu(args.workload, kinfo)
     if rv:
         result["roofline_valu"] = rv

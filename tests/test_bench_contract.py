@@ -93,6 +93,24 @@ def test_stale_counter_files_are_refused(tmp_path, monkeypatch):
 
 
 
+def test_dump_outputs_writes_small_arrays_whole_and_samples_large_ones_alike(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): an array of at most DUMP_MAX_ENTRIES entries as it is, a larger one as one entry
+    from each of DUMP_MAX_ENTRIES equal slices, at seeded offsets: the same positions in every run"""
+    import bench
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 1000)
+    small = np.arange(-500, 500, dtype=np.int16)
+    big = np.arange(12345, dtype=np.int64)                   # entry = its position
+    bench.dump_outputs(str(tmp_path / "a"), {"small": (small, np.float32), "big": (big, np.float64)})
+    bench.dump_outputs(str(tmp_path / "b"), {"big": (big.copy(), np.float64)})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (1000,) and np.array_equal(a, b)
+    stride = 12345 // 1000
+    assert np.array_equal(a.astype(np.int64) // stride, np.arange(1000)) and len(set(a.astype(np.int64) % stride)) > 1
+
+
 @pytest.mark.parametrize("frac_hbm,kd,want", [
     (0.19, {"frac": 0.66, "frac_at_2p4_cycles": 0.38, "wait_share": 0.60}, "latency"),
     (0.19, {"frac": 0.66, "frac_at_2p4_cycles": 0.38, "wait_share": 0.31}, "valu-issue"),

@@ -9,7 +9,7 @@ for wl in $WLS; do
   w=${wl%%:*}; c=${wl##*:}
   for round in 1 2 3; do
     for v in $A $B; do
-      env $VAR=$v timeout 300 python bench.py --workload $w --container $c --steps 300 --warmup 5 --no-cpu-baseline --plain 2>/dev/null | tail -1 | \
+      env $VAR=$v timeout 300 python bench.py --workload $w --container $c --steps 300 --warmup 5 --full --no-cpu-baseline --plain 2>/dev/null | tail -1 | \
         python -c "import sys,json; d=json.loads(sys.stdin.read()); c=d['config']; print('$w $VAR=$v step %.4f enc %.4f dec %.4f' % (d['ms_per_step'], c['encode_ms'], c['decode_ms']), {k: v['ms'] for k, v in d['kernels'].items()})" >> $O 2>&1
     done
   done

@@ -12,7 +12,7 @@ for wl in $WLS; do
   for rep in 1 2 3; do
     for v in $VARS; do
       if [ $v = orig ]; then cp /tmp/lib_orig.so openjph_amd/libojphgpu.so; else cp openjph_amd/variants/lib_$v.so openjph_amd/libojphgpu.so; fi
-      timeout 300 python bench.py --workload $w --container $c --steps 300 --warmup 5 --no-cpu-baseline --plain 2>/tmp/err.txt | tail -1 > /tmp/out.txt
+      timeout 300 python bench.py --workload $w --container $c --steps 300 --warmup 5 --full --no-cpu-baseline --plain 2>/tmp/err.txt | tail -1 > /tmp/out.txt
       python -c "
 import json; d=json.loads(open('/tmp/out.txt').read()); c=d['config']
 print('%-28s %-8s step %.4f enc %.4f dec %.4f' % ('$w', '$v', d['ms_per_step'], c['encode_ms'], c['decode_ms']), {k: v['ms'] for k, v in d['kernels'].items() if 'level 1' not in k}, 'verified' if d.get('verified_after_timing') else '')" >> $O 2>&1 || tail -3 /tmp/err.txt >> $O

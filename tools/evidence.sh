@@ -42,17 +42,17 @@ timeout 400 bash tools/sq_round.sh > $R/sq_counters.txt 2>&1
 cp gpurun_out/sq_counters.json $R/sq_counters.json 2>/dev/null
 cp $R/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null; cp gpurun_out/sq_counters.json profiles/sq_counters.json 2>/dev/null
 # 2. the bench lines, with the counter files of THIS build in place (bench.py quotes nothing from a stale file)
-( timeout 900 python bench.py 2> $R/bench.err | tail -1 ) > $R/bench_c3.json
+( timeout 900 python bench.py --full 2> $R/bench.err | tail -1 ) > $R/bench_c3.json
 if [ -z "$QUICK" ]; then
   for wl in c2_4k_rgb_8b_rev53:8 c4_16k_gray_16b_rev53_tiled:16 c5_4k_444_10b_irv97_batch:16; do
     w=${wl%%:*}; c=${wl##*:}
-    ( timeout 400 python bench.py --workload $w --container $c --steps 200 --no-cpu-baseline 2>> $R/bench2.err | tail -1 ) > $R/bench_$w.json
+    ( timeout 400 python bench.py --workload $w --container $c --steps 200 --full --no-cpu-baseline 2>> $R/bench2.err | tail -1 ) > $R/bench_$w.json
   done
   for wl in c6_4k_gray_32b_rev53:32 c7_4k_444_12b_atk97:16; do
     w=${wl%%:*}; c=${wl##*:}
-    ( timeout 500 python bench.py --workload $w --container $c --steps 200 2>> $R/bench2.err | tail -1 ) > $R/bench_$w.json
+    ( timeout 500 python bench.py --workload $w --container $c --steps 200 --full 2>> $R/bench2.err | tail -1 ) > $R/bench_$w.json
   done
-  ( OJPH_BENCH_BACKEND=gloo OJPH_BENCH_ONE_GPU=1 timeout 400 python bench.py --gpus 2 --steps 20 --no-cpu-baseline 2>> $R/bench2.err | tail -1 ) > $R/bench_2ranks_one_gpu.json
+  ( OJPH_BENCH_BACKEND=gloo OJPH_BENCH_ONE_GPU=1 timeout 400 python bench.py --gpus 2 --steps 20 --full --no-cpu-baseline 2>> $R/bench2.err | tail -1 ) > $R/bench_2ranks_one_gpu.json
   ( timeout 300 python tools/block_sizes.py 2>&1 | grep "^block" ) > $R/block_sizes.txt
   ( SWEEP_STAGES=1 timeout 300 python tools/qstep_sweep.py 2>&1 | grep "qstep\|stages\|alone" ) > $R/rate_sweep.txt
   ( timeout 100 python tools/fuzz_blocks_gpu.py 45 5 2>&1 | tail -2 ) > $R/fuzz_blocks.txt
