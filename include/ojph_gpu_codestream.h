@@ -265,6 +265,10 @@ public:
   void enable_resilience();
   void read_headers(infile_base* file);
   void restrict_input_resolution(ui32 skipped_res_for_data, ui32 skipped_res_for_recon);
+  // GPU-side addition, like set_devices: decode only the rectangle (x0, y0, w, h) of the reference grid, relative to the
+  // image origin (ojphgpu_plan_restrict_region); call it between read_headers (and restrict_input_resolution) and create.
+  // param_siz::get_recon_width / _height and the lines pull() returns then describe the region.
+  void restrict_input_region(ui32 x0, ui32 y0, ui32 w, ui32 h);
   void create();
   line_buf* pull(ui32& comp_num);
 

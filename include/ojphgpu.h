@@ -268,6 +268,23 @@ int  ojphgpu_plan_padded_blocks(const ojphgpu_plan* plan, ojphgpu_padded_block* 
  * what ojphgpu_plan_comp_info reports -- shrinks to ceil(size / 2^skipped_res_for_recon). */
 int  ojphgpu_plan_restrict_resolution(ojphgpu_plan* plan, uint32_t skipped_res_for_data,
                                       uint32_t skipped_res_for_recon);
+/* Region decoding (opj_set_decode_area, Kakadu -region): a decoder created from the plan afterwards does only the work the
+ * samples of the rectangle depend on -- it decodes those code-blocks, uploads their bytes and synthesises those rows and
+ * columns at every level -- and writes a frame that holds the region alone, bit for bit the crop of the whole frame.
+ * (x0, y0, w, h) is a rectangle on the reference grid relative to the image origin: columns [image_x0 + x0, image_x0 + x0 + w),
+ * also after restrict_resolution.  Component c, fx = XRsiz * 2^skipped_res_for_recon, gets the columns
+ * [ceil(A0 / fx), ceil(A1 / fx)) of its own grid (A0, A1: the region's absolute bounds; rows alike); ojphgpu_plan_comp_info and
+ * the frame size then describe the region frame, laid out as any frame.  A sub-sampled component may get an empty plane.
+ * After ojphgpu_t2_parse (and after ojphgpu_plan_restrict_resolution, if at all; restrict_resolution on a region plan is
+ * refused); once per plan.  OJPHGPU_E_INVALID, the plan unchanged: w or h 0, a rectangle not inside the image, a second call,
+ * or a component of the general lifting kernels (an ATK wavelet, a DFS decomposition, 64-bit samples).
+ * A region decoder takes ojphgpu_decoder_upload / run_device* / decode* / failed_blocks and the timing calls as any;
+ * ojphgpu_decoder_create_batch when every plan carries the same region; ojphgpu_decoder_create_tiles only over all tiles.
+ * failed_blocks counts the blocks the region needs, so a region decode fails only when one of those fails. */
+int  ojphgpu_plan_restrict_region(ojphgpu_plan* plan, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
+/* per block of the plan (plan order, n = the plan's block count): 1 = decoded for the region; blocks of resolutions that
+ * are not read are 0.  A plan without a region: the blocks a whole-frame decoder decodes. */
+int  ojphgpu_plan_region_blocks(const ojphgpu_plan* plan, uint8_t* mask, size_t n);
 
 /* ------------------------------------------------------------------------------------------ *
  * 4. Batched device stages.  Descriptor arrays live in device memory.
@@ -336,6 +353,22 @@ int ojphgpu_dwt_forward_image_ex(void* stream, const ojphgpu_params* params, con
                                  uint32_t max_w, uint32_t max_h, const void* d_image, void* d_base, int container_bits, int colour);
 int ojphgpu_dwt_inverse_image_ex(void* stream, const ojphgpu_params* params, const ojphgpu_dwt_desc* d_descs, uint32_t n,
                                  uint32_t max_w, uint32_t max_h, void* d_image, void* d_base, int container_bits, int colour);
+/* Region synthesis: regions[i] (device memory, parallel to the descriptors) is the range of descriptor i's plane whose samples
+ * are wanted exactly, in plane coordinates; the launch covers the strips and row pairs over it.  d_image == NULL: a lower level,
+ * written into the plane in the arena (whole strips, inside the plane).  d_image set: the top level, plane sample (x, y) of the
+ * range written to element out_off + (y - ry0) * out_pitch + (x - rx0) of d_image in `container` (32 | 16 | 8)-bit samples,
+ * converted with the descriptor's `reserved` = bit depth | is_signed << 8.  5/3 and 9/7 only.  Reads the descriptors and
+ * regions back to size the grid (synchronises the stream); the decoders size it from their own copies.  _ex: colour != 0 =
+ * descriptor triples of the three colour planes, the inverse component transform in the stores (as _image_ex). */
+typedef struct ojphgpu_dwt_region {
+  uint32_t rx0, ry0, rx1, ry1;       /* exact range [rx0, rx1) x [ry0, ry1) in plane coordinates (empty: nothing to do) */
+  uint64_t out_off;                  /* top level: element offset of sample (rx0, ry0) in d_image */
+  uint32_t out_pitch, reserved;      /* top level: elements per row of d_image */
+} ojphgpu_dwt_region;
+int ojphgpu_dwt_inverse_region(void* stream, int reversible, const ojphgpu_dwt_desc* d_descs, const ojphgpu_dwt_region* d_regions,
+                               uint32_t n, void* d_base, void* d_image, int container);
+int ojphgpu_dwt_inverse_region_ex(void* stream, int reversible, const ojphgpu_dwt_desc* d_descs, const ojphgpu_dwt_region* d_regions,
+                                  uint32_t n, void* d_base, void* d_image, int container, int colour);
 /* the same with the image samples in 16-bit containers: int16 (two's complement) for signed
  * components, uint16 otherwise; bit depths up to 16.  Halves the HBM traffic of the image side of
  * the top level (and the PCIe traffic of whoever fills / drains the image buffer). */
@@ -540,6 +573,11 @@ int  ojphgpu_decode16(ojphgpu_decoder* dec, const uint8_t* h_codestream, size_t 
 int  ojphgpu_decoder_failed_blocks(ojphgpu_decoder* dec, uint32_t* count);
 /* how many runs of this decoder were repeated that way (0 in any normal process) */
 int  ojphgpu_decoder_fused_retries(ojphgpu_decoder* dec, uint32_t* count);
+/* out[0] = code-blocks decoded per frame, out[1] = blocks of the plan, out[2] = codestream bytes uploaded per frame (the
+ * first frame), out[3] = tiles touched.  A region decoder (ojphgpu_plan_restrict_region) uploads only the bytes of the
+ * blocks it decodes, runs of them that are adjacent in the codestream gathered in one pinned buffer and copied at once; its
+ * upload waits (on the host) until the copy of the previous upload has left that buffer, not for the decoder's runs. */
+int  ojphgpu_decoder_region_info(ojphgpu_decoder* dec, uint64_t out[4]);
 /* synchronises the decoder's stream; *current = the number of one-launch (fused) block-decoder runs enqueued so far,
  * *last_giveup = the number of the newest of them whose wait ran out (0 = none ever did).  A caller that times or pipelines
  * uncollected runs brackets them with two calls: no run in between gave up iff last_giveup <= the first call's *current. */

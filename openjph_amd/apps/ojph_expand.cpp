@@ -1,6 +1,7 @@
 // openjph_amd/apps/ojph_expand.cpp -- command-line decoder on the GPU path, option-compatible with
 // the reference's ojph_expand (src/apps/ojph_expand/ojph_expand.cpp:75-438): -i, -o, -skip_res
-// ({n} or {for_data,for_recon}), -resilient.  Output: .pgm (1 component), .ppm (3 components), .yuv /
+// ({n} or {for_data,for_recon}), -resilient; -region x0,y0,w,h (a GPU-side addition: decode that rectangle of the reference
+// grid, relative to the image origin, only; combines with -skip_res).  Output: .pgm (1 component), .ppm (3 components), .yuv /
 // .raw (planar).  Prints "Elapsed time = ..." (:204).
 #include <chrono>
 #include "ojph_app_common.h"
@@ -9,7 +10,7 @@
 int main(int argc, char** argv) {
   Args a(argc, argv);
   const char* in = a.get("-i"); const char* out = a.get("-o");
-  if (!in || !out) { printf("ojph_expand (GPU path) -i in.j2c -o out.{pgm,ppm,yuv,raw} [-skip_res n] [-resilient true] [-device n | -devices n,n,...]\n"); return -1; }
+  if (!in || !out) { printf("ojph_expand (GPU path) -i in.j2c -o out.{pgm,ppm,yuv,raw} [-skip_res n] [-region x0,y0,w,h] [-resilient true] [-device n | -devices n,n,...]\n"); return -1; }
   try {
     const auto t0 = std::chrono::steady_clock::now();
     const bool verbose = getenv("OJPH_APP_TIMING") != nullptr;       // phase times on stderr
@@ -30,6 +31,11 @@ int main(int argc, char** argv) {
     lap("file read + headers parsed");
     auto sk = Args::numbers(a.get("-skip_res"));
     if (!sk.empty()) cs.restrict_input_resolution((ojph::ui32)sk[0], (ojph::ui32)(sk.size() > 1 ? sk[1] : sk[0]));
+    if (a.get("-region")) {
+      auto rg = Args::numbers(a.get("-region"));
+      if (rg.size() != 4 || rg[0] < 0 || rg[1] < 0 || rg[2] <= 0 || rg[3] <= 0) throw std::runtime_error("-region takes x0,y0,w,h");
+      cs.restrict_input_region((ojph::ui32)rg[0], (ojph::ui32)rg[1], (ojph::ui32)rg[2], (ojph::ui32)rg[3]);
+    }
     ojph::param_siz siz = cs.access_siz();
     Image img;
     img.num_comps = siz.get_num_components();

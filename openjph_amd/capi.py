@@ -115,6 +115,13 @@ class DwtDesc(C.Structure):
     ]
 
 
+class DwtRegion(C.Structure):             # ojphgpu_dwt_region
+    _fields_ = [
+        ("rx0", C.c_uint32), ("ry0", C.c_uint32), ("rx1", C.c_uint32), ("ry1", C.c_uint32),
+        ("out_off", C.c_uint64), ("out_pitch", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
 class CbDesc(C.Structure):
     _fields_ = [
         ("coef_off", C.c_uint64), ("pitch", C.c_uint32), ("w", C.c_uint16), ("h", C.c_uint16),
@@ -173,6 +180,12 @@ SIGNATURES = {
     "ojphgpu_plan_set_comments": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16),
                                             C.c_uint32]),
     "ojphgpu_plan_restrict_resolution": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "ojphgpu_plan_restrict_region": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ojphgpu_plan_region_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ojphgpu_decoder_region_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ojphgpu_dwt_inverse_region": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]),
+    "ojphgpu_dwt_inverse_region_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_int]),
     "ojphgpu_plan_bands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "ojphgpu_plan_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "ojphgpu_plan_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -8,10 +8,11 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import check, Params, DwtDesc, CbDesc, CbResult, ConvertDesc
+from .capi import check, Params, DwtDesc, DwtRegion, CbDesc, CbResult, ConvertDesc
 from .plan import Plan, make_params, parse_codestream
 
 dwt_desc_dtype = np.dtype(DwtDesc)
+dwt_region_dtype = np.dtype(DwtRegion)
 cb_desc_dtype = np.dtype(CbDesc)
 cb_result_dtype = np.dtype(CbResult)
 convert_desc_dtype = np.dtype(ConvertDesc)
@@ -175,10 +176,12 @@ class Encoder:
 class Decoder:
     """Whole-frame decoder bound to one parsed codestream layout (ojphgpu_decoder)."""
 
-    def __init__(self, codestream, device=0, resilient=False, tiles=None, skip_res=None):
+    def __init__(self, codestream, device=0, resilient=False, tiles=None, skip_res=None, region=None):
         """codestream: bytes, or a list of codestreams of same-shaped frames (batch decoder, output
         [B,C,H,W]).  tiles=(first, count) restricts the decoder to a run of tiles (multi-GPU sharding).
-        skip_res=n or (for_data, for_recon): reduced-resolution decoding (codestream::restrict_input_resolution)."""
+        skip_res=n or (for_data, for_recon): reduced-resolution decoding (codestream::restrict_input_resolution).
+        region=(x0, y0, w, h): decode that rectangle of the reference grid (relative to the image origin) only, applied after
+        skip_res (Plan.restrict_region); the frame is the region's."""
         torch = _torch()
         self.device = device
         self.resilient = resilient
@@ -189,6 +192,9 @@ class Decoder:
             a, b = (skip_res, skip_res) if isinstance(skip_res, int) else skip_res
             for pl in self.plans:
                 pl.restrict_resolution(a, b)
+        if region is not None:
+            for pl in self.plans:
+                pl.restrict_region(*region)
         self.plan = self.plans[0]
         self.tiles = (0, self.plan.num_tiles) if tiles is None else (int(tiles[0]), int(tiles[1]))
         self._lib = capi.lib()
@@ -247,6 +253,12 @@ class Decoder:
         n = C.c_uint32()
         check(self._lib.ojphgpu_decoder_failed_blocks(self._h, C.byref(n)), "decoder_failed_blocks")
         return int(n.value)
+
+    def region_info(self):
+        """-> dict(blocks decoded, blocks of the plan, codestream bytes uploaded per frame, tiles touched)"""
+        out = (C.c_uint64 * 4)()
+        check(self._lib.ojphgpu_decoder_region_info(self._h, out), "decoder_region_info")
+        return dict(blocks=int(out[0]), plan_blocks=int(out[1]), upload_bytes=int(out[2]), tiles=int(out[3]))
 
     def fused_retries(self):
         """runs of this decoder that were repeated through the separate launches (see ojphgpu_decoder_failed_blocks)"""
@@ -372,8 +384,8 @@ def encode(image: np.ndarray, device=0, **kw) -> bytes:
     return Encoder(make_params(w, h, nc, **kw), device=device).encode(image)
 
 
-def decode(codestream: bytes, device=0, resilient=False, skip_res=None) -> np.ndarray:
-    return Decoder(codestream, device=device, resilient=resilient, skip_res=skip_res).decode()
+def decode(codestream: bytes, device=0, resilient=False, skip_res=None, region=None) -> np.ndarray:
+    return Decoder(codestream, device=device, resilient=resilient, skip_res=skip_res, region=region).decode()
 
 
 # -------------------------------------------------------------------------------------------------
@@ -387,6 +399,19 @@ def dwt(direction, reversible, descs: np.ndarray, arena, max_w, max_h):
     f = capi.lib().ojphgpu_dwt_forward if direction == "forward" else capi.lib().ojphgpu_dwt_inverse
     check(f(_stream_ptr(torch, dev), int(reversible), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
             C.c_void_p(arena.data_ptr())), "dwt_" + direction)
+    torch.cuda.synchronize(dev)
+
+
+def dwt_inverse_region(reversible, descs: np.ndarray, regions: np.ndarray, arena, image=None, container=32, colour=False):
+    """region synthesis (ojphgpu_dwt_inverse_region_ex): descs dwt_desc_dtype, regions dwt_region_dtype (host, parallel);
+    image None = lower levels into the arena, else a device tensor the top level writes into"""
+    torch = _torch()
+    dev = arena.device.index
+    d, r = to_device(descs, dev), to_device(regions, dev)
+    check(capi.lib().ojphgpu_dwt_inverse_region_ex(_stream_ptr(torch, dev), int(reversible), C.c_void_p(d.data_ptr()), C.c_void_p(r.data_ptr()),
+                                                    len(descs), C.c_void_p(arena.data_ptr()),
+                                                    None if image is None else C.c_void_p(image.data_ptr()), int(container), int(colour)),
+          "dwt_inverse_region")
     torch.cuda.synchronize(dev)
 
 

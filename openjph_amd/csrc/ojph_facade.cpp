@@ -144,7 +144,8 @@ struct codestream_state {
   struct Pending { outfile_base* file; bool close_after; };
   std::vector<Pending> pending;
   ui32 pipelining = 0;                // 0: flush() returns with the codestream written (the reference's contract)
-  bool restricted = false;            // restrict_input_resolution was called for this frame
+  bool restricted = false;            // restrict_input_resolution or restrict_input_region was called for this frame
+  bool region = false; ui32 reg[4] = { 0, 0, 0, 0 };   // restrict_input_region: x0, y0, w, h from the image origin
   si32* frame = nullptr; bool frame_pinned = false; size_t frame_elems = 0;
   std::vector<ui32> cw, ch; std::vector<size_t> coff;   // component planes inside the frame (ojphgpu_plan_comp_info)
   std::vector<si32> spare;                              // a line nobody reads (interleaved exchange past a short component)
@@ -177,7 +178,7 @@ struct codestream_state {
     if (plan && plan != epipe_plan) ojphgpu_plan_destroy(plan);
     plan = nullptr;
     if (frame && !frame_of_pipe) { if (frame_pinned) (void)hipHostFree(frame); else free(frame); }
-    frame = nullptr; frame_of_pipe = false; restricted = false; slot = nullptr;
+    frame = nullptr; frame_of_pipe = false; restricted = false; region = false; slot = nullptr;
     frame_elems = 0; stream.clear(); lines.clear();
     headers_written = headers_read = decoded = false; exhausted = false; cur_comp = cur_line = 0;
     outfile = nullptr; infile = nullptr;
@@ -273,14 +274,14 @@ struct codestream_state {
   ui32 recon_w(ui32 c) const
   {
     const ui64 d = (ui64)(c < comps.size() && comps[c].ds.x ? comps[c].ds.x : 1) << skip_recon;
-    const ui64 x1 = (ui64)image_offset.x + p.width;
-    return (ui32)((x1 + d - 1) / d - ((ui64)image_offset.x + d - 1) / d);
+    const ui64 x0 = (ui64)image_offset.x + (region ? reg[0] : 0), x1 = region ? x0 + reg[2] : (ui64)image_offset.x + p.width;
+    return (ui32)((x1 + d - 1) / d - (x0 + d - 1) / d);
   }
   ui32 recon_h(ui32 c) const
   {
     const ui64 d = (ui64)(c < comps.size() && comps[c].ds.y ? comps[c].ds.y : 1) << skip_recon;
-    const ui64 y1 = (ui64)image_offset.y + p.height;
-    return (ui32)((y1 + d - 1) / d - ((ui64)image_offset.y + d - 1) / d);
+    const ui64 y0 = (ui64)image_offset.y + (region ? reg[1] : 0), y1 = region ? y0 + reg[3] : (ui64)image_offset.y + p.height;
+    return (ui32)((y1 + d - 1) / d - (y0 + d - 1) / d);
   }
 };
 
@@ -811,6 +812,18 @@ void codestream::restrict_input_resolution(ui32 skipped_res_for_data, ui32 skipp
   S.skip_recon = skipped_res_for_recon; S.skip_data = skipped_res_for_data; S.restricted = true;
 }
 
+// GPU-side addition (opj_set_decode_area): only the rectangle (x0, y0, w, h) of the reference grid, from the image origin, is
+// decoded; get_recon_width / _height and the lines pulled describe it.  Between read_headers (and restrict_input_resolution,
+// if at all) and create.
+void codestream::restrict_input_region(ui32 x0, ui32 y0, ui32 w, ui32 h)
+{
+  codestream_state& S = *state;
+  if (!S.headers_read) ojph_error(0x00030F0D, "restrict_input_region called before read_headers");
+  if (ojphgpu_plan_restrict_region(S.plan, x0, y0, w, h) != OJPHGPU_OK)
+    ojph_error(0x00030F0D, "the GPU path rejected the region (empty, outside the image, given twice, or a Part-2 / 64-bit component)");
+  S.region = true; S.reg[0] = x0; S.reg[1] = y0; S.reg[2] = w; S.reg[3] = h; S.restricted = true;
+}
+
 void codestream::create()
 {
   codestream_state& S = *state;
@@ -840,7 +853,7 @@ void codestream::create()
     return;
   }
   int rc;
-  if (S.devices.size() > 1)
+  if (S.devices.size() > 1 && !S.region)         // (a region frame: the plan decoder on the first device)
     rc = ojphgpu_multi_decoder_create(S.stream.data(), S.stream.size(), S.resilient ? 1 : 0, S.restricted ? S.skip_data : 0,
                                       S.restricted ? S.skip_recon : 0, S.devices.data(), (uint32_t)S.devices.size(), &S.mdec);
   else

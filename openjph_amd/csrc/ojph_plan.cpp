@@ -1044,6 +1044,7 @@ extern "C" int ojphgpu_plan_restrict_resolution(ojphgpu_plan* plan, uint32_t ski
   if (!plan) return OJPHGPU_E_INVALID;
   Plan& P = plan->plan;
   if (P.coded.size() != P.blocks.size()) return OJPHGPU_E_INVALID;           // a parsed codestream only
+  if (P.has_region) return OJPHGPU_E_INVALID;                                 // (the region's frame is taken at the resolution it found)
   if (skipped_res_for_data < skipped_res_for_recon) return OJPHGPU_E_INVALID; // ojph_codestream_local.cpp:886-890
   if (skipped_res_for_data > P.p.num_decomps) return OJPHGPU_E_INVALID;       // :891-895 (the COD's count)
   for (uint32_t c = 0; c < P.p.num_comps; ++c)                                // a component with fewer decompositions than are
@@ -1066,6 +1067,85 @@ extern "C" int ojphgpu_plan_restrict_resolution(ojphgpu_plan* plan, uint32_t ski
     g.w = (uint32_t)((X1 + fx - 1) / fx) - g.x0; g.h = (uint32_t)((Y1 + fy - 1) / fy) - g.y0;
     g.frame_off = P.frame_elems;
     P.frame_elems += (uint64_t)g.w * g.h;
+  }
+  return OJPHGPU_OK;
+}
+
+// Region decoding.  Per tile-component the region meets, from the reconstructed top level down: the output of a level has to
+// be exact over [a, b) (per direction, absolute coordinates of its resolution); it reads both of its bands over
+// [floor(a / 2) - m, ceil(b / 2) + m), clipped to the band, m = 2 for the 5/3 (3- and 5-tap synthesis filters), 3 for the 9/7
+// (7 and 9 taps) -- wider than the filters need; the low x low part of that is the exact range of the level below.  The
+// blocks that meet those ranges are the ones decoded.  (A mirrored neighbour at a band edge lies inside the clipped range.)
+extern "C" int ojphgpu_plan_restrict_region(ojphgpu_plan* plan, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
+{
+  if (!plan) return OJPHGPU_E_INVALID;
+  Plan& P = plan->plan;
+  if (P.coded.size() != P.blocks.size() || P.has_region) return OJPHGPU_E_INVALID;   // a parsed codestream, once
+  if (w == 0 || h == 0 || (uint64_t)x0 + w > P.p.width || (uint64_t)y0 + h > P.p.height) return OJPHGPU_E_INVALID;
+  for (uint32_t c = 0; c < P.p.num_comps; ++c)
+    if (P.general(c)) return OJPHGPU_E_INVALID;            // kernels_lift.hip and the 64-bit planes have no region form
+  return no_throw([&] {
+    const uint64_t ax0 = (uint64_t)P.p.image_x0 + x0, ax1 = ax0 + w, ay0 = (uint64_t)P.p.image_y0 + y0, ay1 = ay0 + h;
+    std::vector<CompGeo> comps = P.comps;
+    uint64_t frame_elems = 0;
+    for (CompGeo& g : comps) {                               // CompGeo's own rule with the image extent replaced by the region
+      const uint64_t fx = (uint64_t)g.dx << P.skip_recon, fy = (uint64_t)g.dy << P.skip_recon;
+      g.x0 = (uint32_t)((ax0 + fx - 1) / fx); g.y0 = (uint32_t)((ay0 + fy - 1) / fy);
+      g.w = (uint32_t)((ax1 + fx - 1) / fx) - g.x0; g.h = (uint32_t)((ay1 + fy - 1) / fy) - g.y0;
+      g.frame_off = frame_elems;
+      frame_elems += (uint64_t)g.w * g.h;
+    }
+    std::vector<uint8_t> sel(P.blocks.size(), 0), tiles(P.tiles.size(), 0);
+    std::vector<Rect> exact(P.ress.size(), Rect{ 0, 0, 0, 0 });
+    auto meet = [](int64_t a0, int64_t a1, int64_t b0, int64_t b1, int64_t& o0, int64_t& o1) { o0 = std::max(a0, b0); o1 = std::min(a1, b1); return o0 < o1; };
+    auto select = [&](const Band& B, int64_t nx0, int64_t nx1, int64_t ny0, int64_t ny1) {
+      int64_t bx0, bx1, by0, by1;
+      if (B.empty || !meet(nx0, nx1, B.r.x0, (int64_t)B.r.x0 + B.r.w, bx0, bx1) || !meet(ny0, ny1, B.r.y0, (int64_t)B.r.y0 + B.r.h, by0, by1)) return;
+      for (uint32_t i = 0; i < B.nbx * B.nby; ++i) {
+        const Block& k = P.blocks[B.first_block + i];
+        const int64_t kx0 = (int64_t)B.r.x0 + k.r.x0, ky0 = (int64_t)B.r.y0 + k.r.y0;
+        if (kx0 < bx1 && kx0 + k.r.w > bx0 && ky0 < by1 && ky0 + k.r.h > by0) sel[B.first_block + i] = 1;
+      }
+    };
+    for (const Tile& t : P.tiles)
+      for (uint32_t c = 0; c < P.p.num_comps; ++c) {
+        const TileComp& tc = P.tcomps[t.comps[c]];
+        const CompGeo& g = comps[c];
+        const uint32_t L = P.recon_decomps(c), top_read = P.top_read_res(c);
+        const int64_t m = P.style(c).rev ? 2 : 3;
+        const Rect& top = P.ress[tc.res[L]].r;
+        int64_t cx0, cx1, cy0, cy1;                          // the exact range of the current level's output
+        if (!meet(top.x0, (int64_t)top.x0 + top.w, g.x0, (int64_t)g.x0 + g.w, cx0, cx1) ||
+            !meet(top.y0, (int64_t)top.y0 + top.h, g.y0, (int64_t)g.y0 + g.h, cy0, cy1)) continue;
+        tiles[t.idx] = 1;
+        for (uint32_t r = L;; --r) {
+          const Resolution& R = P.ress[tc.res[r]];
+          exact[tc.res[r]] = Rect{ (uint32_t)cx0, (uint32_t)cy0, (uint32_t)(cx1 - cx0), (uint32_t)(cy1 - cy0) };
+          if (r == 0) { select(P.bands[(size_t)R.band[0]], cx0, cx1, cy0, cy1); break; }
+          const int64_t nx0 = std::max<int64_t>((cx0 >> 1) - m, 0), nx1 = ((cx1 + 1) >> 1) + m;
+          const int64_t ny0 = std::max<int64_t>((cy0 >> 1) - m, 0), ny1 = ((cy1 + 1) >> 1) + m;
+          if (r <= top_read)
+            for (int b = 1; b < 4; ++b) if (R.band[b] >= 0) select(P.bands[(size_t)R.band[b]], nx0, nx1, ny0, ny1);
+          const Rect& lo = P.ress[tc.res[r - 1]].r;
+          if (!meet(nx0, nx1, lo.x0, (int64_t)lo.x0 + lo.w, cx0, cx1) || !meet(ny0, ny1, lo.y0, (int64_t)lo.y0 + lo.h, cy0, cy1)) break;
+        }
+      }
+    P.comps.swap(comps); P.frame_elems = frame_elems;
+    P.reg_blocks.swap(sel); P.reg_exact.swap(exact); P.reg_tiles.swap(tiles);
+    P.has_region = true;
+    P.region[0] = x0; P.region[1] = y0; P.region[2] = w; P.region[3] = h;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_plan_region_blocks(const ojphgpu_plan* plan, uint8_t* mask, size_t n)
+{
+  if (!plan || !mask) return OJPHGPU_E_INVALID;
+  const Plan& P = plan->plan;
+  if (n < P.blocks.size()) return OJPHGPU_E_INVALID;
+  for (size_t i = 0; i < P.blocks.size(); ++i) {
+    const Band& B = P.bands[P.blocks[i].band];
+    mask[i] = P.has_region ? P.reg_blocks[i] : (uint8_t)(B.res <= P.top_read_res(B.comp) ? 1 : 0);
   }
   return OJPHGPU_OK;
 }

@@ -185,6 +185,13 @@ struct Plan {
   ojphgpu_lift lift_of(uint32_t comp, uint32_t d) const;
   uint32_t max_block_bytes;
   std::string error;
+  // region decoding (ojphgpu_plan_restrict_region): comps / frame_elems then describe the region frame
+  bool has_region = false;
+  uint32_t region[4] = { 0, 0, 0, 0 };      // x0, y0, w, h as asked: reference grid, from the image origin
+  std::vector<uint8_t> reg_blocks;          // per block: decoded for the region
+  std::vector<Rect> reg_exact;              // per resolution (ress index): the range synthesised exactly, in that resolution's
+                                            // absolute coordinates (w or h 0: none)
+  std::vector<uint8_t> reg_tiles;           // per tile: the region touches one of its tile-components
 };
 
 // builds everything from p (p.tile_w/h == 0 -> single tile). Returns 0 or OJPHGPU_E_INVALID.

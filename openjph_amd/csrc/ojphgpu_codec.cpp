@@ -518,9 +518,11 @@ extern "C" void ojphgpu_decoder_destroy(ojphgpu_decoder* d)
   if (!d) return;
   (void)hipSetDevice(d->device);
   for (DeviceBuf* b : { &d->arena, &d->image, &d->dwt_descs, &d->img_descs, &d->cb_descs, &d->conv_descs, &d->data, &d->status, &d->quads, &d->aux,
-                       &d->fstate })
+                       &d->fstate, &d->dwt_regs, &d->img_regs })
     b->release();
   if (d->h_retry) (void)hipHostFree(d->h_retry);
+  if (d->h_stage) (void)hipHostFree(d->h_stage);
+  if (d->ev_stage) (void)hipEventDestroy(d->ev_stage);
   if (d->side) (void)hipStreamDestroy(d->side);
   if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
   if (d->ev_join) (void)hipEventDestroy(d->ev_join);
@@ -556,6 +558,7 @@ int ojphgpu_same_frame_geometry(const Plan& P, const Plan& Q, bool compare_block
 {
   if (Q.coded.size() != Q.blocks.size()) return OJPHGPU_E_INVALID;    // plans must come from ojphgpu_t2_parse
   if (Q.skip_read != P.skip_read || Q.skip_recon != P.skip_recon) return OJPHGPU_E_INVALID;
+  if (Q.has_region != P.has_region || memcmp(Q.region, P.region, sizeof(P.region)) != 0) return OJPHGPU_E_INVALID;   // one region
   if (Q.blocks.size() != P.blocks.size() || Q.arena_elems != P.arena_elems || Q.p.width != P.p.width ||
       Q.p.height != P.p.height || Q.p.num_comps != P.p.num_comps || Q.p.bit_depth != P.p.bit_depth ||
       Q.p.is_signed != P.p.is_signed || Q.p.reversible != P.p.reversible || Q.p.num_decomps != P.p.num_decomps ||
@@ -621,11 +624,43 @@ void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<
   }
   if (min_off > max_off) min_off = max_off = 0;
   min_off &= ~(uint64_t)15;                                             // only this byte range of the codestream is uploaded
-  for (size_t i = 0; i < ids.size(); ++i) {
-    ojphgpu_cb_desc& o = bd[i];
-    if (o.len1 + o.len2) o.data_off = o.data_off - min_off + data_base; else o.data_off = 0;
+  fi.runs.clear();
+  if (P.has_region) {
+    // a region decoder's blocks are scattered over the codestream (progression orders interleave them): the runs of blocks
+    // adjacent in the codestream are placed one after another, 64 zero bytes on either side of each
+    std::vector<std::pair<uint64_t, uint64_t>> spans;                    // (offset, end) of every block with bytes here
+    for (size_t i = 0; i < ids.size(); ++i) {
+      const ojphgpu_cb_desc& o = bd[i];
+      if ((o.len1 + o.len2) && (padded_at.empty() || std::none_of(padded_at.begin(), padded_at.end(), [&](const auto& pp) { return pp.first == i; })))
+        spans.emplace_back(o.data_off, o.data_off + o.len1 + o.len2);
+    }
+    std::sort(spans.begin(), spans.end());
+    uint64_t at = 0;
+    for (const auto& sp : spans) {
+      if (!fi.runs.empty() && sp.first <= fi.runs.back().src + fi.runs.back().n) {
+        DecRun& r = fi.runs.back();
+        r.n = std::max(r.n, sp.second - r.src);
+        continue;
+      }
+      if (!fi.runs.empty()) at = ((fi.runs.back().dst + fi.runs.back().n + 63) & ~(uint64_t)63);
+      at += 64;
+      fi.runs.push_back(DecRun{ sp.first, at, sp.second - sp.first });
+    }
+    const uint64_t staged = fi.runs.empty() ? 0 : ((fi.runs.back().dst + fi.runs.back().n + 63) & ~(uint64_t)63) + 64;
+    for (size_t i = 0; i < ids.size(); ++i) {
+      ojphgpu_cb_desc& o = bd[i];
+      if (!(o.len1 + o.len2)) { o.data_off = 0; continue; }
+      auto it = std::upper_bound(fi.runs.begin(), fi.runs.end(), o.data_off, [](uint64_t v, const DecRun& r) { return v < r.src; });
+      if (it != fi.runs.begin()) { --it; o.data_off = data_base + it->dst + (o.data_off - it->src); }
+    }
+    fi.first = 0; fi.len = staged;
+  } else {
+    for (size_t i = 0; i < ids.size(); ++i) {
+      ojphgpu_cb_desc& o = bd[i];
+      if (o.len1 + o.len2) o.data_off = o.data_off - min_off + data_base; else o.data_off = 0;
+    }
+    fi.first = min_off; fi.len = max_off - min_off;
   }
-  fi.first = min_off; fi.len = max_off - min_off;
   uint64_t at = (fi.len + 63) & ~(uint64_t)63;                          // padded blocks: behind the range, 64 bytes apart at least
   for (const auto& pp : padded_at) {
     ojphgpu_cb_desc& o = bd[pp.first]; const Plan::PaddedBlock& pb = *pp.second;
@@ -658,6 +693,7 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
   const ojphgpu_plan* plan = plans[0];
   const Plan& P = plan->plan;
   if ((uint64_t)tile_first + tile_count > P.tiles.size()) return OJPHGPU_E_INVALID;
+  if (P.has_region && (tile_first != 0 || tile_count != P.tiles.size())) return OJPHGPU_E_INVALID;   // a region decoder decodes whole frames
   for (uint32_t f = 0; f < nframes; ++f) {                              // every frame of a batch has the same geometry
     if (!plans[f]) return OJPHGPU_E_INVALID;
     const int rc = ojphgpu_same_frame_geometry(P, plans[f]->plan, f != 0);
@@ -679,9 +715,20 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
   std::vector<ojphgpu_dwt_desc> dd; build_level_batches(P, tr, dd, d->batches);
   std::vector<ojphgpu_dwt_desc> idd;
   build_image_level_descs(P, tr, dd, d->batches, idd);
+  std::vector<ojphgpu_dwt_region> rg, irg;
+  d->region = P.has_region;
+  if (d->region) {                                          // region synthesis: the levels the region needs, each with its exact range
+    restrict_levels_to_region(P, tr, dd, idd, d->batches, rg, irg);
+    replicate_regions(rg, irg, d->batches, nframes, frame_elems);
+  }
   replicate_levels(dd, idd, d->batches, nframes, P.arena_elems, frame_elems);
   std::reverse(d->batches.begin(), d->batches.end());                 // synthesis: lowest resolution first
   std::vector<ojphgpu_convert_desc> cd; d->need_convert = build_convert_descs(P, tr, cd, d->conv_max_w, d->conv_max_h);
+  d->conv_tiles = tile_count; d->tiles_touched = tile_count;
+  if (d->region) {
+    d->conv_tiles = d->tiles_touched = restrict_converts_to_region(P, tr, cd, d->conv_max_w, d->conv_max_h);
+    d->need_convert = d->need_convert && d->conv_max_w && d->conv_max_h;
+  }
   replicate_converts(cd, nframes, P.arena_elems, P.frame_elems);
   std::vector<uint32_t> ids = blocks_of_tiles(P, tr);
   // Overlap of the lower synthesis levels with the block decoder: the blocks below the top
@@ -707,12 +754,15 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
   std::vector<ojphgpu_cb_desc> bd(ids.size() * nframes);
   uint64_t nquads = 0, naux = 0, data_total = 0;
   d->f_first.assign(nframes, 0); d->f_len.assign(nframes, 0); d->f_base.assign(nframes, 0); d->f_pads.assign(nframes, {});
+  d->f_runs.assign(nframes, {});
   for (uint32_t f = 0; f < nframes; ++f) {
     DecFrameInfo fi;
     ojphgpu_decoder_fill_descs(P, plans[f]->plan, ids, (uint64_t)f * P.arena_elems, data_total, bd.data() + (size_t)f * ids.size(), fi);
     d->any_refine |= fi.any_refine; d->kinds |= fi.kinds; d->max_len1 = std::max(d->max_len1, fi.max_len1);
     d->f_first[f] = (size_t)fi.first; d->f_len[f] = (size_t)fi.len; d->f_base[f] = (size_t)data_total;
     d->f_pads[f] = fi.pads;
+    d->f_runs[f] = fi.runs;
+    d->stage_cap = std::max(d->stage_cap, (size_t)fi.len);
     data_total += fi.data_bytes();
   }
   d->data_first = d->f_first[0];
@@ -743,6 +793,15 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
   if (!idd.empty() && hipMemcpy(d->img_descs.p, idd.data(), idd.size() * sizeof(idd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!bd.empty() && hipMemcpy(d->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!cd.empty() && hipMemcpy(d->conv_descs.p, cd.data(), cd.size() * sizeof(cd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
+  if (d->region) {
+    if (d->dwt_regs.alloc(rg.size() * sizeof(ojphgpu_dwt_region)) || d->img_regs.alloc(irg.size() * sizeof(ojphgpu_dwt_region))) return bail(OJPHGPU_E_NOMEM);
+    if (!rg.empty() && hipMemcpy(d->dwt_regs.p, rg.data(), rg.size() * sizeof(rg[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
+    if (!irg.empty() && hipMemcpy(d->img_regs.p, irg.data(), irg.size() * sizeof(irg[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
+    void* hp = nullptr;                                     // the staging buffer of the uploads
+    if (d->stage_cap && hipHostMalloc(&hp, d->stage_cap, hipHostMallocDefault) != hipSuccess) return bail(OJPHGPU_E_NOMEM);
+    d->h_stage = (uint8_t*)hp;
+    if (hipEventCreateWithFlags(&d->ev_stage, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
+  }
   if (d->timer.init() != 0) return bail(OJPHGPU_E_HIP);
   owner.p = nullptr;
   *out = d;
@@ -756,7 +815,26 @@ extern "C" int ojphgpu_decoder_upload(ojphgpu_decoder* d, const uint8_t* h_codes
 
 extern "C" int ojphgpu_decoder_upload_frame(ojphgpu_decoder* d, uint32_t frame, const uint8_t* h_codestream, size_t len)
 {
-  if (!d || !h_codestream || frame >= d->nframes || len < d->f_first[frame] + d->f_len[frame]) return OJPHGPU_E_INVALID;
+  if (!d || !h_codestream || frame >= d->nframes) return OJPHGPU_E_INVALID;
+  if (d->region) {                                          // the runs of the decoded blocks, gathered, then one copy
+    const std::vector<DecRun>& runs = d->f_runs[frame];
+    for (const DecRun& r : runs) if (r.src + r.n > len) return OJPHGPU_E_INVALID;
+    if (d->f_len[frame]) {
+      if (d->ev_stage) HIPCHK(hipEventSynchronize(d->ev_stage));   // the copy of the previous upload has left the staging buffer
+      uint8_t* st = d->h_stage;
+      uint64_t at = 0;
+      for (const DecRun& r : runs) {
+        memset(st + at, 0, r.dst - at);
+        memcpy(st + r.dst, h_codestream + r.src, r.n);
+        at = r.dst + r.n;
+      }
+      memset(st + at, 0, d->f_len[frame] - at);
+      HIPCHK(hipMemcpyAsync((uint8_t*)d->data.p + d->f_base[frame], st, d->f_len[frame], hipMemcpyHostToDevice, d->stream));
+      HIPCHK(hipEventRecord(d->ev_stage, d->stream));
+    }
+    return ojphgpu_decoder_upload_pads(d->stream, (uint8_t*)d->data.p + d->f_base[frame], h_codestream, len, d->f_pads[frame]);
+  }
+  if (len < d->f_first[frame] + d->f_len[frame]) return OJPHGPU_E_INVALID;
   if (d->f_len[frame])
     HIPCHK(hipMemcpyAsync((uint8_t*)d->data.p + d->f_base[frame], h_codestream + d->f_first[frame], d->f_len[frame],
                           hipMemcpyHostToDevice, d->stream));
@@ -816,7 +894,7 @@ extern "C" int ojphgpu_decoder_run_device8(ojphgpu_decoder* d, uint8_t* d_image)
 
 int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int container)
 {
-  if (!d || !d_image) return OJPHGPU_E_INVALID;
+  if (!d || (!d_image && !(d->region && d->P->frame_elems == 0))) return OJPHGPU_E_INVALID;   // (a region may hold no sample at a reduced resolution)
   const Plan& P = *d->P;
   if (container != 32 && container != 16 && container != 8) return OJPHGPU_E_INVALID;
   if (container != 32) for (const CompGeo& g : P.comps) if (g.bit_depth > (uint32_t)container) return OJPHGPU_E_INVALID;
@@ -877,7 +955,12 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
     hipStream_t ls = (n_low && !top) ? d->side : s;
     if (top && n_low && !joined && (rc = finish_blocks()) != 0) return rc;
     const int sp = T.begin(SP_DWT, ls);
-    if (b.img_first >= 0) {                                 // float->int / level shift applied in the stores
+    if (d->region) {                                        // region synthesis (the Part-1 wavelets only: plan_restrict_region)
+      const ojphgpu_dwt_region* regs = (const ojphgpu_dwt_region*)(b.img_first >= 0 ? d->img_regs.p : d->dwt_regs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
+      const ojphgpu_dwt_desc* descs = (const ojphgpu_dwt_desc*)(b.img_first >= 0 ? d->img_descs.p : d->dwt_descs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
+      rc = ojphgpu::dwt_inverse_region_launch(ls, b.rev ? 1 : 0, descs, regs, b.count, b.rgrid, d->arena.p, b.img_first >= 0 ? d_image : nullptr,
+                                              container, b.img_first >= 0 ? b.nc : 1);
+    } else if (b.img_first >= 0) {                          // float->int / level shift applied in the stores
       ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0;
       const ojphgpu_dwt_desc* idesc = (const ojphgpu_dwt_desc*)d->img_descs.p + b.img_first;
       rc = b.general ? ojphgpu_dwt_inverse_general_image(ls, &b.k, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container)
@@ -893,7 +976,7 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
   if (n_low && !joined && (rc = finish_blocks()) != 0) return rc;
   if (d->need_convert) {
     const int sp = T.begin(SP_CONVERT, s);
-    rc = ojphgpu_convert_inverse_ex(s, &P.p, (const ojphgpu_convert_desc*)d->conv_descs.p, d->tiles.count * d->nframes,
+    rc = ojphgpu_convert_inverse_ex(s, &P.p, (const ojphgpu_convert_desc*)d->conv_descs.p, d->conv_tiles * d->nframes,
                                     d->conv_max_w, d->conv_max_h, d_image, d->arena.p, container);
     if (rc) return rc;
     T.end(sp, s);
@@ -959,6 +1042,15 @@ extern "C" int ojphgpu_decoder_giveup_epoch(ojphgpu_decoder* d, uint32_t* last_g
   HIPCHK(hipStreamSynchronize(d->stream));
   *last_giveup = d->h_retry ? *(volatile uint32_t*)d->h_retry : 0u;
   *current = d->fused_epoch;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_decoder_region_info(ojphgpu_decoder* d, uint64_t out[4])
+{
+  if (!d || !out) return OJPHGPU_E_INVALID;
+  uint64_t bytes = d->f_len.empty() ? 0 : d->f_len[0];
+  if (!d->f_pads.empty()) for (const PadCopy& c : d->f_pads[0]) bytes += c.got;
+  out[0] = d->block_ids.size(); out[1] = d->P->blocks.size(); out[2] = bytes; out[3] = d->tiles_touched;
   return OJPHGPU_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "dwt_region.h"
 #include "ht_tables.h"
 #include "ojph_plan.h"
 
@@ -54,7 +55,8 @@ struct HostBuf {
 // general: levels of components that need the general lifting kernels (a Part-2 wavelet or decomposition, or 64-bit samples;
 // kernels_dwt.hip's WvGen pipeline or kernels_lift.hip) -- k describes the level; components with equal k share a batch
 struct LevelBatch { uint32_t first, count, max_w, max_h, depth; bool rev; int img_first; int nc; int group; bool general; ojphgpu_lift k;
-                    std::vector<uint32_t> comps; };        // comps: the components of a general-lifting batch, in descriptor order
+                    std::vector<uint32_t> comps;           // comps: the components of a general-lifting batch, in descriptor order
+                    ojphgpu::DwtRegionGrid rgrid; };       // region decoders: what sizes the batch's region launch
 
 // DWT descriptors grouped so that one launch handles every tile-component
 struct TileRange { uint32_t first, count; bool has(uint32_t t) const { return t >= first && t - first < count; } };
@@ -243,6 +245,96 @@ bool build_convert_descs(const Plan& P, TileRange tr, std::vector<ojphgpu_conver
   return any;
 }
 
+// Region decoders (Plan::has_region): the exact range of a level's output plane, in plane coordinates; the top level writes it
+// into the region frame (out_off, out_pitch)
+inline ojphgpu_dwt_region region_of_level(const Plan& P, const ojphgpu_level_info& lv, bool top)
+{
+  const TileComp& tc = P.tcomps[P.tiles[lv.tile].comps[lv.comp]];
+  const uint32_t rid = tc.res[lv.res];
+  const Rect& E = P.reg_exact[rid]; const Rect& R = P.ress[rid].r;
+  ojphgpu_dwt_region r; memset(&r, 0, sizeof(r));
+  if (E.w == 0 || E.h == 0) return r;
+  r.rx0 = E.x0 - R.x0; r.ry0 = E.y0 - R.y0; r.rx1 = r.rx0 + E.w; r.ry1 = r.ry0 + E.h;
+  if (top) {
+    const CompGeo& g = P.comps[lv.comp];
+    r.out_off = g.frame_off + (uint64_t)(E.y0 - g.y0) * g.w + (E.x0 - g.x0); r.out_pitch = g.w;
+  }
+  return r;
+}
+
+// Keeps the descriptors of the levels whose exact range is not empty and gives each its region; the batches follow (a batch
+// left empty goes).  descs / img_descs as build_level_batches / build_image_level_descs made them.
+void restrict_levels_to_region(const Plan& P, TileRange tr, std::vector<ojphgpu_dwt_desc>& descs, std::vector<ojphgpu_dwt_desc>& img_descs,
+                               std::vector<LevelBatch>& batches, std::vector<ojphgpu_dwt_region>& regs, std::vector<ojphgpu_dwt_region>& img_regs)
+{
+  std::vector<ojphgpu_dwt_desc> od, oi; std::vector<LevelBatch> ob;
+  regs.clear(); img_regs.clear();
+  for (const LevelBatch& b : batches) {
+    LevelBatch n = b;
+    n.first = (uint32_t)od.size(); n.count = 0; n.img_first = b.img_first >= 0 ? (int)oi.size() : -1;
+    n.rgrid = ojphgpu::DwtRegionGrid();
+    size_t k = 0;
+    for_levels_of(P, tr, b.depth, b.rev, b.group, -1, [&](const ojphgpu_level_info& lv) {
+      const size_t i = k++;
+      const ojphgpu_dwt_region r = region_of_level(P, lv, b.img_first >= 0);
+      if (r.rx1 <= r.rx0) return;
+      od.push_back(descs[b.first + i]); regs.push_back(r);
+      if (b.img_first >= 0) { oi.push_back(img_descs[(size_t)b.img_first + i]); img_regs.push_back(r); }
+      ojphgpu::dwt_region_grid_add(n.rgrid, descs[b.first + i], r);
+      n.count++;
+    });
+    if (n.count) ob.push_back(n);
+  }
+  descs.swap(od); img_descs.swap(oi); batches.swap(ob);
+}
+
+// the same regions for every frame of a batch decoder (call before replicate_levels, on the batches it is given)
+void replicate_regions(std::vector<ojphgpu_dwt_region>& regs, std::vector<ojphgpu_dwt_region>& img_regs, const std::vector<LevelBatch>& batches,
+                       uint32_t nframes, uint64_t frame_elems)
+{
+  if (nframes <= 1) return;
+  std::vector<ojphgpu_dwt_region> out, iout;
+  for (const LevelBatch& b : batches)
+    for (uint32_t f = 0; f < nframes; ++f)
+      for (uint32_t i = 0; i < b.count; ++i) {
+        out.push_back(regs[b.first + i]);
+        if (b.img_first >= 0) { ojphgpu_dwt_region r = img_regs[(size_t)b.img_first + i]; r.out_off += (uint64_t)f * frame_elems; iout.push_back(r); }
+      }
+  regs.swap(out); img_regs.swap(iout);
+}
+
+// Region decoders: the conversion descriptors of the tiles the region touches (one per component, in that order), each
+// moved to the corner of its tile-component's region part and writing into the region frame.  Returns the tiles kept.
+uint32_t restrict_converts_to_region(const Plan& P, TileRange tr, std::vector<ojphgpu_convert_desc>& descs, uint32_t& max_w, uint32_t& max_h)
+{
+  std::vector<ojphgpu_convert_desc> out;
+  max_w = max_h = 0;
+  uint32_t kept = 0, ti = 0;
+  for (const Tile& t : P.tiles) {
+    if (!tr.has(t.idx)) continue;
+    const size_t base = (size_t)(ti++) * P.p.num_comps;
+    if (!P.reg_tiles[t.idx]) continue;
+    ++kept;
+    for (uint32_t c = 0; c < P.p.num_comps; ++c) {
+      ojphgpu_convert_desc d = descs[base + c];
+      const TileComp& tc = P.tcomps[t.comps[c]];
+      const uint32_t rid = tc.res[P.recon_decomps(c)];
+      const Rect& E = P.reg_exact[rid]; const Rect& R = P.ress[rid].r;
+      const CompGeo& g = P.comps[c];
+      if (d.w && d.h && E.w && E.h) {
+        d.plane_off += (uint64_t)(E.y0 - R.y0) * d.pitch + (E.x0 - R.x0);
+        d.w = E.w; d.h = E.h;
+        d.src_x0 = E.x0 - g.x0; d.src_y0 = E.y0 - g.y0;
+        d.img_pitch = g.w; d.img_off = g.frame_off;
+      } else d.w = d.h = 0;
+      max_w = std::max(max_w, d.w); max_h = std::max(max_h, d.h);
+      out.push_back(d);
+    }
+  }
+  descs.swap(out);
+  return kept;
+}
+
 // Frame batches: the same plan applied to `nframes` independent frames in one set of launches
 // (config C5: a batch of independent 4K frames).  Frame f lives f * arena_elems further in the arena
 // and f * frame_elems further in the image buffer; descriptors are simply replicated, batch by batch.
@@ -290,6 +382,7 @@ std::vector<uint32_t> blocks_of_tiles(const Plan& P, TileRange tr)
   std::vector<uint32_t> ids;
   for (size_t i = 0; i < P.blocks.size(); ++i) {
     const Band& B = P.bands[P.blocks[i].band];
+    if (P.has_region && !P.reg_blocks[i]) continue;          // a region decoder: the blocks the region depends on
     if (tr.has(B.tile) && B.res <= P.top_read_res(B.comp)) ids.push_back((uint32_t)i);   // resolutions above are not decoded: their bands stay zero
   }
   return ids;
@@ -392,6 +485,9 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
 // then zeros up to `total`, placed at `dst` -- an offset into the frame's part of the device data buffer, BEHIND the byte
 // range that is uploaded as it is.
 struct PadCopy { uint64_t src, dst; uint32_t got, total; };
+// a run of decoded blocks adjacent in the codestream: n bytes at src, placed at dst of the frame's staged bytes (64 zero bytes
+// on either side: the VLC partner's 16-byte loads)
+struct DecRun { uint64_t src, dst, n; };
 struct ojphgpu_decoder {
   const Plan* P = nullptr;
   int device = 0; hipStream_t stream = nullptr;
@@ -426,6 +522,15 @@ struct ojphgpu_decoder {
   int kinds = 0;                                   // block kinds of the frame(s), for ht_decode_step2_launch
   std::vector<size_t> f_first, f_len, f_base;      // per frame: codestream byte range uploaded, its place in `data`
   std::vector<std::vector<PadCopy>> f_pads;        // per frame: blocks uploaded with zeros behind their bytes (PadCopy)
+  // region decoders (Plan::has_region): the frame's bytes are the runs of its decoded blocks (DecRun), gathered into the pinned
+  // h_stage and copied at once; f_len = the bytes staged.  DWT descriptors get their regions (dwt_regs, img_regs) and the
+  // conversion kernels take conv_tiles tiles per frame
+  bool region = false;
+  std::vector<std::vector<DecRun>> f_runs;
+  uint8_t* h_stage = nullptr; size_t stage_cap = 0;
+  hipEvent_t ev_stage = nullptr;                   // recorded behind the copy out of h_stage: an upload waits for it, not for runs
+  DeviceBuf dwt_regs, img_regs;
+  uint32_t conv_tiles = 0, tiles_touched = 0;
   uint32_t nblocks = 0;                            // code-blocks of the tile range (all frames)
   std::vector<LevelBatch> batches;
   uint32_t conv_max_w = 0, conv_max_h = 0, max_len1 = 0;
@@ -437,6 +542,7 @@ struct ojphgpu_decoder {
   const void* o_cb_descs = nullptr; const void* o_data = nullptr; void* o_status = nullptr;
 };
 struct DecFrameInfo {
+  std::vector<DecRun> runs;                                  // region decoders: the runs; first = 0, len = the bytes staged
   uint64_t first = 0, len = 0; bool any_refine = false; uint32_t max_len1 = 0; int kinds = 0;   // kinds: see ht_decode_step2_launch; bit 5: blocks on the 64-bit sample path
   std::vector<PadCopy> pads; uint64_t pad_len = 0;         // padded blocks: their copies, the bytes they take behind `len` (rounded up to 64)
   uint64_t data_bytes() const { return ((len + 63) & ~(uint64_t)63) + pad_len; }

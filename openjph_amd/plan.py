@@ -130,6 +130,7 @@ class Plan:
             handle = h
         self.handle = handle
         self.skip = (0, 0)
+        self.region = None
         cnt = (C.c_uint64 * 8)()
         check(self._lib.ojphgpu_plan_counts(self.handle, cnt))
         (self.num_tiles, self.num_bands, self.num_blocks, self.num_levels, self.arena_elems,
@@ -173,6 +174,20 @@ class Plan:
         check(self._lib.ojphgpu_plan_restrict_resolution(self.handle, int(skipped_res_for_data), int(skipped_res_for_recon)),
               "plan_restrict_resolution")
         self.skip = (int(skipped_res_for_data), int(skipped_res_for_recon))
+
+    def restrict_region(self, x0, y0, w, h):
+        """region decoding (ojphgpu_plan_restrict_region) on a parsed plan, after restrict_resolution if at all: a Decoder made
+        from the plan decodes the rectangle (x0, y0, w, h) of the reference grid, relative to the image origin, and nothing
+        else; comp_info / frame_shape then describe the region frame"""
+        check(self._lib.ojphgpu_plan_restrict_region(self.handle, int(x0), int(y0), int(w), int(h)), "plan_restrict_region")
+        self.region = (int(x0), int(y0), int(w), int(h))
+
+    def region_blocks(self):
+        """-> bool per block of the plan: decoded for the region (without a region: by a whole-frame decoder)"""
+        out = np.zeros(self.num_blocks, np.uint8)
+        if self.num_blocks:
+            check(self._lib.ojphgpu_plan_region_blocks(self.handle, out.ctypes.data, self.num_blocks), "plan_region_blocks")
+        return out.astype(bool)
 
     def comp_info(self, comp):
         """-> dict(x0, y0, w, h, frame_off, dx, dy) of component `comp` (see ojphgpu_plan_comp_info)"""
