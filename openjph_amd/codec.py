@@ -415,6 +415,44 @@ def dwt_inverse_region(reversible, descs: np.ndarray, regions: np.ndarray, arena
     torch.cuda.synchronize(dev)
 
 
+def convert(direction, params: Params, descs: np.ndarray, image, arena, max_w, max_h, container=32):
+    """ojphgpu_convert_forward_ex / _inverse_ex: descs convert_desc_dtype (host; n_tiles * params.num_comps of them, each with
+    its own fmt), image a device tensor of `container`-bit samples, arena a device tensor of 32-bit elements"""
+    torch = _torch()
+    dev = arena.device.index
+    d = to_device(descs, dev)
+    n_tiles = len(descs) // max(int(params.num_comps), 1)
+    f = capi.lib().ojphgpu_convert_forward_ex if direction == "forward" else capi.lib().ojphgpu_convert_inverse_ex
+    check(f(_stream_ptr(torch, dev), C.byref(params), C.c_void_p(d.data_ptr()), n_tiles, max_w, max_h,
+            C.c_void_p(image.data_ptr()), C.c_void_p(arena.data_ptr()), int(container)), "convert_" + direction)
+    torch.cuda.synchronize(dev)
+
+
+def dwt_image(direction, params: Params, descs: np.ndarray, image, arena, max_w, max_h, container=32, colour=False):
+    """ojphgpu_dwt_forward_image_ex / _inverse_image_ex: one level with the sample conversion fused in; descs dwt_desc_dtype
+    (host) with src_off / src_pitch inside `image` and reserved = the plane's bit depth | signed << 8"""
+    torch = _torch()
+    dev = arena.device.index
+    d = to_device(descs, dev)
+    f = capi.lib().ojphgpu_dwt_forward_image_ex if direction == "forward" else capi.lib().ojphgpu_dwt_inverse_image_ex
+    check(f(_stream_ptr(torch, dev), C.byref(params), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
+            C.c_void_p(image.data_ptr()), C.c_void_p(arena.data_ptr()), int(container), int(bool(colour))), "dwt_image_" + direction)
+    torch.cuda.synchronize(dev)
+
+
+def dwt_general_image(direction, steps, elem, params: Params, descs: np.ndarray, image, arena, max_w, max_h, K=1.0, container=32):
+    """ojphgpu_dwt_forward_general_image / _inverse_general_image: the general lifting kernels' top level with the conversion
+    fused in (steps as for dwt_general; elem 0 = int32, 2 = float); descs as for dwt_image"""
+    torch = _torch()
+    dev = arena.device.index
+    d = to_device(descs, dev)
+    k = _lift(steps, elem, K, True, True)
+    f = capi.lib().ojphgpu_dwt_forward_general_image if direction == "forward" else capi.lib().ojphgpu_dwt_inverse_general_image
+    check(f(_stream_ptr(torch, dev), C.byref(k), C.byref(params), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
+            C.c_void_p(image.data_ptr()), C.c_void_p(arena.data_ptr()), int(container)), "dwt_general_image_" + direction)
+    torch.cuda.synchronize(dev)
+
+
 class _LiftStep(C.Structure):
     _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("e", C.c_int32), ("A", C.c_float)]
 
@@ -424,12 +462,7 @@ class _Lift(C.Structure):
                 ("steps", _LiftStep * 16)]
 
 
-def dwt_general(direction, steps, elem, descs: np.ndarray, arena, max_w, max_h, K=1.0, horz=True, vert=True):
-    """ojphgpu_dwt_forward_general / _inverse_general: steps in synthesis order -- (a, b, e) tuples for a reversible
-    kernel, floats for an irreversible one; elem 0 = int32, 1 = int64, 2 = float planes in `arena`."""
-    torch = _torch()
-    dev = arena.device.index
-    d = to_device(descs, dev)
+def _lift(steps, elem, K, horz, vert):
     k = _Lift()
     k.num_steps, k.elem, k.horz, k.vert, k.K = len(steps), int(elem), int(bool(horz)), int(bool(vert)), float(K)
     for i, st in enumerate(steps):
@@ -437,6 +470,16 @@ def dwt_general(direction, steps, elem, descs: np.ndarray, arena, max_w, max_h, 
             k.steps[i].a, k.steps[i].b, k.steps[i].e = st
         else:
             k.steps[i].A = float(st)
+    return k
+
+
+def dwt_general(direction, steps, elem, descs: np.ndarray, arena, max_w, max_h, K=1.0, horz=True, vert=True):
+    """ojphgpu_dwt_forward_general / _inverse_general: steps in synthesis order -- (a, b, e) tuples for a reversible
+    kernel, floats for an irreversible one; elem 0 = int32, 1 = int64, 2 = float planes in `arena`."""
+    torch = _torch()
+    dev = arena.device.index
+    d = to_device(descs, dev)
+    k = _lift(steps, elem, K, horz, vert)
     f = capi.lib().ojphgpu_dwt_forward_general if direction == "forward" else capi.lib().ojphgpu_dwt_inverse_general
     check(f(_stream_ptr(torch, dev), C.byref(k), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h, C.c_void_p(arena.data_ptr())),
           "dwt_general_" + direction)

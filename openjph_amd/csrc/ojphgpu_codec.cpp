@@ -285,7 +285,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     const LevelBatch& b = e->batches[i];
     const int sp = T.begin(SP_DWT, s);
     if (b.img_first >= 0) {                                 // level shift / int->float applied in the loads
-      ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0;
+      ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0; pp.bit_depth = b.img_depth; pp.is_signed = b.img_signed;
       const ojphgpu_dwt_desc* idesc = (const ojphgpu_dwt_desc*)e->img_descs.p + b.img_first;
       rc = b.general ? ojphgpu_dwt_forward_general_image(s, &b.k, &pp, idesc, b.count, b.max_w, b.max_h, d_image, e->arena.p, container)
                      : ojphgpu_dwt_forward_image_ex(s, &pp, idesc, b.count, b.max_w, b.max_h, d_image, e->arena.p, container, b.nc == 3);
@@ -961,7 +961,7 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
       rc = ojphgpu::dwt_inverse_region_launch(ls, b.rev ? 1 : 0, descs, regs, b.count, b.rgrid, d->arena.p, b.img_first >= 0 ? d_image : nullptr,
                                               container, b.img_first >= 0 ? b.nc : 1);
     } else if (b.img_first >= 0) {                          // float->int / level shift applied in the stores
-      ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0;
+      ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0; pp.bit_depth = b.img_depth; pp.is_signed = b.img_signed;
       const ojphgpu_dwt_desc* idesc = (const ojphgpu_dwt_desc*)d->img_descs.p + b.img_first;
       rc = b.general ? ojphgpu_dwt_inverse_general_image(ls, &b.k, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container)
                      : ojphgpu_dwt_inverse_image_ex(ls, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container, b.nc == 3);

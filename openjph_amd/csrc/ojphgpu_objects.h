@@ -56,7 +56,8 @@ struct HostBuf {
 // kernels_dwt.hip's WvGen pipeline or kernels_lift.hip) -- k describes the level; components with equal k share a batch
 struct LevelBatch { uint32_t first, count, max_w, max_h, depth; bool rev; int img_first; int nc; int group; bool general; ojphgpu_lift k;
                     std::vector<uint32_t> comps;           // comps: the components of a general-lifting batch, in descriptor order
-                    ojphgpu::DwtRegionGrid rgrid; };       // region decoders: what sizes the batch's region launch
+                    ojphgpu::DwtRegionGrid rgrid;          // region decoders: what sizes the batch's region launch
+                    uint32_t img_depth = 0, img_signed = 0; }; // img_first >= 0: the deepest sample format among the batch's image planes
 
 // DWT descriptors grouped so that one launch handles every tile-component
 struct TileRange { uint32_t first, count; bool has(uint32_t t) const { return t >= first && t - first < count; } };
@@ -174,6 +175,11 @@ void build_image_level_descs(const Plan& P, TileRange tr, const std::vector<ojph
   out.clear();
   if (P.any_nlt3 || (P.p.color_transform && !colour_fused(P))) return;   // those conversions live in the conversion kernels
   const bool gfused = general_fused(P);
+  // each plane is converted in its own format (desc.reserved); the launch is validated against the deepest of them, not
+  // against component 0's, which may not be in the batch at all
+  auto note_format = [&](LevelBatch& b, const CompGeo& g) {
+    if (g.bit_depth > b.img_depth) { b.img_depth = g.bit_depth; b.img_signed = g.is_signed ? 1 : 0; }
+  };
   auto image_desc = [&](const ojphgpu_level_info& lv, ojphgpu_dwt_desc d) {
     const TileComp& tc = P.tcomps[P.tiles[lv.tile].comps[lv.comp]];
     const CompGeo& g = P.comps[lv.comp];
@@ -188,7 +194,10 @@ void build_image_level_descs(const Plan& P, TileRange tr, const std::vector<ojph
       b.img_first = (int)out.size();
       size_t k = 0;
       for (uint32_t c : b.comps)
-        for_levels_of(P, tr, 0, P.style(c).rev, 0, (int)c, [&](const ojphgpu_level_info& lv) { out.push_back(image_desc(lv, descs[b.first + k++])); });
+        for_levels_of(P, tr, 0, P.style(c).rev, 0, (int)c, [&](const ojphgpu_level_info& lv) {
+          note_format(b, P.comps[lv.comp]);
+          out.push_back(image_desc(lv, descs[b.first + k++]));
+        });
       continue;
     }
     if (b.depth != 0 || b.count == 0 || b.general) continue;
@@ -205,6 +214,7 @@ void build_image_level_descs(const Plan& P, TileRange tr, const std::vector<ojph
       d.src_off = g.frame_off + (uint64_t)(rr.y0 - g.y0) * g.w + (rr.x0 - g.x0);
       d.src_pitch = g.w;
       d.reserved = g.bit_depth | (g.is_signed ? 0x100u : 0u);   // the component's sample format for the fused conversion
+      note_format(b, g);
       out.push_back(d);
     });
   }
