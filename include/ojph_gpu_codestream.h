@@ -300,6 +300,15 @@ public:
   // frame an outfile object of its own and close() it after drain().
   void enable_frame_pipelining(ui32 frames_in_flight = 4);
   void drain();
+  // GPU-side addition: flush() codes the frame to at most max_bytes bytes, SOC to EOC (include/ojphgpu.h section 5b: the
+  // finest base step of a fixed grid whose codestream fits; the step set with param_qcd::set_irrev_quant is then not
+  // used).  Call it before write_headers; 0 switches it off.  Irreversible coding without quality factors, one frame on
+  // one device (no restart()ed sequence, no set_devices): anything else is reported by write_headers, a budget below the
+  // codestream of the coarsest step by flush() -- like every OJPH_ERROR, a message and std::runtime_error.
+  void set_byte_budget(size_t max_bytes);
+  // after such a flush(): the step it chose (its index in the grid and its value), the codestream's length and the number
+  // of block-coder runs the search made; false when there was none
+  bool get_byte_budget_result(ui32& grid_index, float& qstep, ui64& bytes, ui32& passes);
 
 private:
   codestream(const codestream&) = delete;

@@ -37,6 +37,7 @@ extern "C" {
 #define OJPHGPU_E_AGAIN        -7   /* a frame pipeline has no free slot: collect a result first */
 #define OJPHGPU_E_UNCOLLECTED  -8   /* ojphgpu_decoder_run_device*: the run BEFORE this one asked to be decoded again (see
                                      * ojphgpu_decoder_failed_blocks) and was never collected -- its frame was incomplete */
+#define OJPHGPU_E_BUDGET       -9   /* a byte budget that not even the coarsest step of the rate grid meets (section 5b) */
 
 /* ------------------------------------------------------------------------------------------ *
  * 1. Codestream parameters: what ojph::param_siz / param_cod / param_qcd setters carry
@@ -494,6 +495,18 @@ int ojphgpu_convert_inverse16(void* stream, const ojphgpu_params* params,
                               const ojphgpu_convert_desc* d_descs, uint32_t n_tiles,
                               uint32_t max_w, uint32_t max_h, uint16_t* d_image, const void* d_arena);
 
+/* Band statistics (section 5b builds on them): one pass over sub-band planes of fp32 coefficients, an 80-bin histogram of
+ * the magnitudes in half octaves per slot.  With u the 32 bits of a coefficient, bin = clamp(((u >> 22) & 0x1FF) - 191,
+ * 0, 79) -- the exponent field and the top mantissa bit: bin 0 holds zeros, denormals and everything below 2^-31, bin 63
+ * holds [1, 1.5), bin 79 everything from 2^8 up, infinities and NaNs included.  Only the w x h samples of a plane count
+ * (rows of `pitch` >= w elements; the padding does not, though it may be read); several descriptors may share a slot.
+ * d_hist[slot][80] holds exact counts (uint32) and is zeroed by the caller.  max_w / max_h: the largest w / h among the
+ * descriptors, as for the DWT; max_w at most 2^21. */
+#define OJPHGPU_STATS_BINS 80
+typedef struct ojphgpu_stats_desc { uint64_t plane_off; uint32_t pitch, w, h, slot; } ojphgpu_stats_desc;
+int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
+                       const void* d_coef, uint32_t* d_hist);
+
 /* ------------------------------------------------------------------------------------------ *
  * 5. Whole-frame codec objects: what an ojph::codestream-compatible facade calls from
  *    flush() (encode) and create()/pull() (decode).
@@ -604,6 +617,55 @@ int  ojphgpu_encoder_ht_timing(ojphgpu_encoder* enc, float* out, uint32_t cap, u
  * highest resolution first; decode: lowest first); *n = number of levels written */
 int  ojphgpu_encoder_level_timing(ojphgpu_encoder* enc, float* out, uint32_t cap, uint32_t* n);
 int  ojphgpu_decoder_level_timing(ojphgpu_decoder* dec, float* out, uint32_t cap, uint32_t* n);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 5b. Encoding to a byte budget.  The reference has no rate control for HTJ2K: the size of an irreversible codestream
+ *    follows from the base step handed to param_qcd::set_irrev_quant, which scales it per sub-band and writes it with
+ *    encode_SPqcd (ojph_params.cpp:1542-1612).  What is added here searches that one number: a fixed grid of
+ *    OJPHGPU_RATE_GRID base steps, qstep(j) = (float) exp2(-1 - j / 16) evaluated in double and rounded once -- j = 0 the
+ *    coarsest (0.5), j = 240 the finest (2^-16) -- and size(j) = the length, SOC to EOC, of the codestream the encoder
+ *    writes for its plan's parameters with qstep = qstep(j).  A budgeted encode with max_bytes = B returns an index j* and
+ *    the codestream of j* with size(j*) <= B and either j* == 240 or size(j* + 1) > B (the certificate); the bytes are
+ *    exactly those of a plain encode at qstep(j*), QCD / QCC included, so decoders need nothing new.  size(0) > B:
+ *    OJPHGPU_E_BUDGET, nothing written.
+ * ------------------------------------------------------------------------------------------ */
+#define OJPHGPU_RATE_GRID 241
+int  ojphgpu_rate_grid_qstep(uint32_t j, float* qstep);            /* OJPHGPU_E_INVALID: j >= OJPHGPU_RATE_GRID */
+
+typedef int64_t (*ojphgpu_size_fn)(void* user, uint32_t grid_index);   /* size(j); < 0 = error */
+typedef struct ojphgpu_rate_info {
+  uint32_t grid_index; float qstep; uint64_t bytes;      /* j*, qstep(j*), size(j*)               */
+  uint64_t bytes_finer;                                  /* size(j* + 1), 0 when j* == 240        */
+  uint32_t passes, first_guess;                          /* calls of size_fn; the model's first j */
+} ojphgpu_rate_info;
+/* The search, host only: hist = the band statistics of the frame, [bands of the plan][OJPHGPU_STATS_BINS] in band order
+ * (NULL: no model, plain interval halving).  A model predicts size(j) from the histograms and every band's step at j; the
+ * first trial is its index for the budget, and after every trial it is rescaled by observed / predicted before it proposes
+ * the next.  Correctness does not rest on it: every trial shrinks the interval of candidates, a proposal outside the
+ * interval is moved inside, and once six trials have produced no certificate the proposals are the interval's midpoint.
+ * No index is asked twice, and passes <= 16 for every input -- fn need not be monotone.  The plan must be irreversible
+ * throughout, without quality factors.  Returns OJPHGPU_E_BUDGET (out->passes, first_guess filled) when size(0) >
+ * max_bytes, a negative value of fn as it is. */
+int  ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes,
+                         ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
+/* the model alone: predicted bytes of every grid index, out[OJPHGPU_RATE_GRID] (what tools/rate_bench.py reports) */
+int  ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out);
+
+/* max_bytes > 0: the encoder codes every following frame to that budget; 0 switches it off (every call then behaves as
+ * without this section).  With a budget, ojphgpu_encoder_run_device* enqueues conversion, DWT and the band statistics;
+ * ojphgpu_encoder_finish* runs the search -- per trial the block coder's launches with the blocks' delta / K_max of
+ * qstep(j), the block lengths come to the host and the Tier-2 layout gives size(j) -- and downloads the coded bytes
+ * once, for j*.  OJPHGPU_E_BUDGET leaves the encoder usable.  OJPHGPU_E_INVALID: a plan with a reversible component (COC
+ * included), a quality factor (global or per component), ATK / DFS wavelets, a band of 2^32 samples or more; an encoder
+ * of a tile range that does not cover the frame; a batch encoder.  The per-block scratch slots and the output buffer
+ * are re-sized for the finest step of the grid on the first call. */
+int  ojphgpu_encoder_set_budget(ojphgpu_encoder* enc, uint64_t max_bytes);
+/* what the last budgeted ojphgpu_encoder_finish* found (OJPHGPU_E_INVALID before one) */
+int  ojphgpu_encoder_rate_info(ojphgpu_encoder* enc, ojphgpu_rate_info* info);
+/* host clock of the last budgeted finish, ms: out[0] the search (every pass), [1] the part of it spent waiting for the
+ * device and the copies of the block lengths, [2] the download and Tier-2 of j*; out[3] the band statistics kernel of the
+ * run before it (device events; needs ojphgpu_encoder_set_timing's per-launch spans, the default) */
+int  ojphgpu_encoder_rate_timing(ojphgpu_encoder* enc, float out[4]);
 
 /* ------------------------------------------------------------------------------------------ *
  * 6. Frame pipelines: sequences of frames of one shape with PCIe copies, kernels and host Tier-2 of

@@ -10,7 +10,7 @@
 #include "../../include/ojph_gpu_codestream.h"
 
 static void usage() {
-  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100]\n"
+  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n]\n"
          "  [-num_decomps n] [-block_size {w,h}] [-precincts {w,h}] [-prog_order LRCP|RLCP|RPCL|PCRL|CPRL]\n"
          "  [-colour_trans true|false] [-tile_size {w,h}] [-tlm_marker true|false] [-device n | -devices n,n,...]\n"
          "  [-image_offset {x,y}] [-tile_offset {x,y}] [-tileparts R|C|RC] [-profile IMF|BROADCAST] [-com \"text\"]\n"
@@ -97,6 +97,14 @@ int main(int argc, char** argv) {
       if (img.num_comps != 1 && img.num_comps != 3) throw std::runtime_error("-qfactor is only supported for images with 1 or 3 components");   // :921-926
       cs.access_qcd().set_qfactor((ojph::ui8)atoi(a.get("-qfactor")));
     }
+    if (a.get("-max_bytes")) {                                  // GPU path only: the finest step of the rate grid that fits
+      if (reversible) throw std::runtime_error("-max_bytes needs irreversible coding (-reversible false)");
+      if (a.get("-qfactor") || a.get("-qstep")) throw std::runtime_error("-max_bytes chooses the quantisation step itself: it cannot be used together with -qstep or -qfactor");
+      if (a.get("-devices")) throw std::runtime_error("-max_bytes codes on one device: it cannot be used together with -devices");
+      const long long mb = atoll(a.get("-max_bytes"));
+      if (mb <= 0) throw std::runtime_error("-max_bytes must be a positive number of bytes");
+      cs.set_byte_budget((size_t)mb);
+    }
     if (a.get("-tlm_marker")) cs.request_tlm_marker(Args::to_bool(a.get("-tlm_marker")));
     if (a.get("-profile")) cs.set_profile(a.get("-profile"));
     if (a.get("-tileparts")) {                                  // ojph_compress.cpp:324-356: letters R and / or C
@@ -121,6 +129,11 @@ int main(int argc, char** argv) {
       line = cs.exchange(line, next);
     }
     cs.flush();
+    {
+      ojph::ui32 gi = 0, passes = 0; float q = 0; ojph::ui64 nbytes = 0;
+      if (a.get("-max_bytes") && cs.get_byte_budget_result(gi, q, nbytes, passes))
+        printf("Byte budget %s: qstep = %.9g (grid index %u), %llu bytes, %u passes\n", a.get("-max_bytes"), (double)q, gi, (unsigned long long)nbytes, passes);
+    }
     cs.close();
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("Elapsed time = %f\n", dt);

@@ -10,7 +10,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libojphgpu.so")
 
-OK, E_INVALID, E_NOMEM, E_HIP, E_CODESTREAM, E_OVERFLOW, E_BLOCK, E_AGAIN, E_UNCOLLECTED = 0, -1, -2, -3, -4, -5, -6, -7, -8
+OK, E_INVALID, E_NOMEM, E_HIP, E_CODESTREAM, E_OVERFLOW, E_BLOCK, E_AGAIN, E_UNCOLLECTED, E_BUDGET = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
+RATE_GRID, STATS_BINS = 241, 80
 PROG_ORDERS = {"LRCP": 0, "RLCP": 1, "RPCL": 2, "PCRL": 3, "CPRL": 4}
 
 
@@ -140,6 +141,17 @@ class ConvertDesc(C.Structure):
                 ("h", C.c_uint32), ("src_x0", C.c_uint32), ("src_y0", C.c_uint32),
                 ("img_pitch", C.c_uint32), ("img_off", C.c_uint64), ("fmt", C.c_uint32), ("reserved", C.c_uint32)]
 
+
+class StatsDesc(C.Structure):             # ojphgpu_stats_desc
+    _fields_ = [("plane_off", C.c_uint64), ("pitch", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("slot", C.c_uint32)]
+
+
+class RateInfo(C.Structure):              # ojphgpu_rate_info
+    _fields_ = [("grid_index", C.c_uint32), ("qstep", C.c_float), ("bytes", C.c_uint64), ("bytes_finer", C.c_uint64),
+                ("passes", C.c_uint32), ("first_guess", C.c_uint32)]
+
+
+SIZE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint32)      # ojphgpu_size_fn
 
 _lib = None
 
@@ -295,6 +307,13 @@ SIGNATURES = {
     "ojphgpu_dec_pipe_set_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ojphgpu_unpack_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "ojphgpu_pack_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+    "ojphgpu_band_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ojphgpu_rate_grid_qstep": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
+    "ojphgpu_rate_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),
+    "ojphgpu_rate_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "ojphgpu_encoder_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_encoder_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
+    "ojphgpu_encoder_rate_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "ojphgpu_version": (C.c_char_p, []),
 }
 
@@ -332,7 +351,8 @@ class OjphError(RuntimeError):
                  E_HIP: "HIP runtime error (no GPU?)", E_CODESTREAM: "malformed codestream",
                  E_OVERFLOW: "output buffer too small", E_BLOCK: "error decoding a codeblock",
                  E_AGAIN: "no free pipeline slot",
-                 E_UNCOLLECTED: "the previous run of this decoder asked for a repeat and was never collected"}
+                 E_UNCOLLECTED: "the previous run of this decoder asked for a repeat and was never collected",
+                 E_BUDGET: "the byte budget is below the codestream of the coarsest quantisation step"}
         super().__init__("ojph error: %s (%d) %s" % (names.get(code, "?"), code, what))
         self.code = code
 

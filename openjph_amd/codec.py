@@ -42,9 +42,10 @@ def to_device(arr: np.ndarray, device=0):
 class Encoder:
     """Whole-frame encoder for one frame shape / parameter set (ojphgpu_encoder)."""
 
-    def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, **kw):
+    def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, max_bytes=0, **kw):
         """tiles=(first, count) restricts the encoder to a run of tiles (multi-GPU sharding);
-        frames=B makes it code a batch of B independent frames per run ([B,C,H,W] input)."""
+        frames=B makes it code a batch of B independent frames per run ([B,C,H,W] input);
+        max_bytes=N codes every frame to a byte budget (set_budget)."""
         torch = _torch()
         self.device = device
         self.plan = plan if plan is not None else Plan(params if params is not None else make_params(**kw))
@@ -63,6 +64,32 @@ class Encoder:
                       "encoder_create")
         fs = self.plan.frame_shape          # [C,H,W], or flat (frame_elems,) when components differ in size
         self.shape = fs if self.frames == 1 else (self.frames,) + fs
+        self.max_bytes = 0
+        if max_bytes:
+            self.set_budget(max_bytes)
+
+    def set_budget(self, max_bytes):
+        """Every following frame is coded at the finest step of the rate grid (plan.rate_grid_qstep) whose codestream is at
+        most max_bytes long; the plan's own qstep is then not used.  0 switches the budget off.  Irreversible whole-frame
+        single-frame encoders without quality factors only; a budget nothing fits raises OjphError with code E_BUDGET from
+        finish() / encode()."""
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_encoder_set_budget(self._h, int(max_bytes)), "encoder_set_budget")
+        self.max_bytes = int(max_bytes)
+
+    def rate_info(self):
+        """what the last budgeted finish() found: dict(grid_index, qstep, bytes, bytes_finer = the length one step finer
+        (0 at the end of the grid), passes = block-coder runs made, first_guess = the model's first index)"""
+        info = capi.RateInfo()
+        check(self._lib.ojphgpu_encoder_rate_info(self._h, C.byref(info)), "encoder_rate_info")
+        return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+
+    def rate_timing(self):
+        """host clock of the last budgeted finish(), ms: dict(search_ms = all passes, wait_ms = of that, waiting for the device,
+        final_ms = download + Tier-2 of the chosen step, stats_ms = the band statistics kernel (device events))"""
+        t = (C.c_float * 4)()
+        check(self._lib.ojphgpu_encoder_rate_timing(self._h, t), "encoder_rate_timing")
+        return dict(search_ms=t[0], wait_ms=t[1], final_ms=t[2], stats_ms=t[3])
 
     def __del__(self):
         try:
@@ -96,7 +123,10 @@ class Encoder:
 
     def finish(self, frame=0) -> bytes:
         """codestream of frame `frame` of the last run"""
-        cap = self.coded_bytes() // self.frames * 2 + 64 * self.plan.num_blocks + (1 << 20)
+        if self.max_bytes:                 # (a budget far above what the frame can need: the second round below)
+            cap = min(self.max_bytes, self.plan.frame_elems * 4 + 64 * self.plan.num_blocks + (1 << 20))
+        else:
+            cap = self.coded_bytes() // self.frames * 2 + 64 * self.plan.num_blocks + (1 << 20)
         out = np.empty(cap, np.uint8)
         n = C.c_size_t()
         rc = self._lib.ojphgpu_encoder_finish_frame(self._h, frame, out.ctypes.data, cap, C.byref(n))
@@ -378,10 +408,11 @@ class MultiDecoder:
         return v.copy() if copy else v
 
 
-def encode(image: np.ndarray, device=0, **kw) -> bytes:
-    """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes)."""
+def encode(image: np.ndarray, device=0, max_bytes=0, **kw) -> bytes:
+    """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes); max_bytes=N: coded to a byte
+    budget (Encoder.set_budget)."""
     nc, h, w = image.shape
-    return Encoder(make_params(w, h, nc, **kw), device=device).encode(image)
+    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes).encode(image)
 
 
 def decode(codestream: bytes, device=0, resilient=False, skip_res=None, region=None) -> np.ndarray:
@@ -438,6 +469,24 @@ def dwt_image(direction, params: Params, descs: np.ndarray, image, arena, max_w,
     check(f(_stream_ptr(torch, dev), C.byref(params), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
             C.c_void_p(image.data_ptr()), C.c_void_p(arena.data_ptr()), int(container), int(bool(colour))), "dwt_image_" + direction)
     torch.cuda.synchronize(dev)
+
+
+stats_desc_dtype = np.dtype(capi.StatsDesc)
+
+
+def band_stats(descs: np.ndarray, arena, slots):
+    """ojphgpu_band_stats: descs stats_desc_dtype (host), arena a device tensor of 32-bit elements -> uint32 [slots, 80]
+    half-octave histograms of the magnitudes of the planes' fp32 coefficients"""
+    torch = _torch()
+    dev = arena.device.index
+    d = to_device(descs, dev)
+    hist = torch.zeros((int(slots), capi.STATS_BINS), dtype=torch.int32, device=arena.device)
+    max_w = int(descs["w"].max()) if len(descs) else 0
+    max_h = int(descs["h"].max()) if len(descs) else 0
+    check(capi.lib().ojphgpu_band_stats(_stream_ptr(torch, dev), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
+                                        C.c_void_p(arena.data_ptr()), C.c_void_p(hist.data_ptr())), "band_stats")
+    torch.cuda.synchronize(dev)
+    return hist.cpu().numpy().view(np.uint32)
 
 
 def dwt_general_image(direction, steps, elem, params: Params, descs: np.ndarray, image, arena, max_w, max_h, K=1.0, container=32):

@@ -115,6 +115,7 @@ struct codestream_state {
   bool headers_written = false, headers_read = false, decoded = false;
   std::string profile;
   int device = 0;
+  size_t byte_budget = 0;             // set_byte_budget: flush() codes the frame to at most this many bytes (0: off)
   // more than one device: a tiled frame is coded by all of them, each a contiguous run of tiles (include/ojphgpu.h section 8)
   std::vector<int> devices;
   ojphgpu_multi_encoder* menc = nullptr; ojphgpu_multi_decoder* mdec = nullptr;
@@ -552,6 +553,14 @@ void codestream::set_devices(const int* devices, ui32 num_devices)
   if (!state->devices.empty()) state->device = state->devices[0];
 }
 void codestream::set_narrow_sample_containers(bool narrow) { state->narrow = narrow; }
+void codestream::set_byte_budget(size_t max_bytes) { state->byte_budget = max_bytes; }
+bool codestream::get_byte_budget_result(ui32& grid_index, float& qstep, ui64& bytes, ui32& passes)
+{
+  ojphgpu_rate_info info;
+  if (!state->enc || ojphgpu_encoder_rate_info(state->enc, &info) != OJPHGPU_OK) return false;
+  grid_index = info.grid_index; qstep = info.qstep; bytes = info.bytes; passes = info.passes;
+  return true;
+}
 void codestream::enable_frame_pipelining(ui32 frames_in_flight)
 {
   state->drain();
@@ -709,8 +718,11 @@ void codestream::write_headers(outfile_base* file, const comment_exchange* comme
   } else {
     rc = ojphgpu_encoder_create(S.plan, S.device, nullptr, &S.enc);
     if (rc) ojph_error(0x00030F08, "cannot create the GPU encoder (status %d): no GPU?", rc);
+    if (S.byte_budget && ojphgpu_encoder_set_budget(S.enc, S.byte_budget) != OJPHGPU_OK)
+      ojph_error(0x00030F13, "a byte budget needs irreversible coding of every component with the Part-1 wavelet and no quality factor");
     S.alloc_frame();
   }
+  if (S.byte_budget && !S.enc) ojph_error(0x00030F14, "a byte budget is available for single frames on one device (no restart()ed sequence, no set_devices)");
   // a frame still queued for this very file object (enable_frame_pipelining, and the application re-opened the object for
   // the next frame): its codestream is written before the object is used again
   for (const codestream_state::Pending& pd : S.pending) if (pd.file == file) { S.drain(); break; }
@@ -765,6 +777,7 @@ void codestream::flush()
   }
   size_t len = 0;
   int rc = ojphgpu_encode(S.enc, S.frame, nullptr, 0, &len);            // runs the GPU path; reports the codestream size
+  if (rc == OJPHGPU_E_BUDGET) ojph_error(0x00030F15, "the byte budget of %zu bytes is below the codestream of the coarsest quantisation step (status %d)", S.byte_budget, rc);
   if (rc != OJPHGPU_E_OVERFLOW && rc != OJPHGPU_OK) ojph_error(0x00030F0B, "GPU encode failed (status %d)", rc);
   std::unique_ptr<ui8[]> out(new ui8[len + 16]);
   rc = ojphgpu_encoder_finish(S.enc, out.get(), len + 16, &len);         // host Tier-2 only (block bytes are already here)

@@ -220,6 +220,25 @@ int t2_layout_tiles(const Plan& P, const ojphgpu_coded_block* cb, size_t t0, siz
 int t2_layout_codestream(const Plan& P, const ojphgpu_coded_block* cb, T2Layout& L);
 void t2_place_host(const T2Layout& L, const uint8_t* data, uint8_t* out);
 
+// Encoding to a byte budget (include/ojphgpu.h section 5b; ojph_rate.cpp).  A band's K_max / delta follow from its
+// component, resolution and orientation alone: those triples are the CLASSES of a plan, and a RateTable holds their
+// quantisation at every step of the rate grid -- what the model evaluates and what the encoder uploads per trial.
+struct BandQuant { float delta; uint32_t K_max; };         // as in Band: delta = step / 2^(31 - K_max)
+struct RateTable {
+  uint32_t nclasses = 0;
+  std::vector<uint32_t> band_class;                          // per band of the plan
+  std::vector<BandQuant> quant;                              // [OJPHGPU_RATE_GRID][nclasses]
+  std::vector<double> log2_step;                             // the same shape: log2 of the band's step
+  uint64_t num_blocks = 0;
+};
+float rate_grid_qstep(uint32_t j);
+bool rate_plan_ok(const Plan& P);                            // irreversible throughout, no quality factor, Part-1 wavelets
+// p.qstep = qstep, the QCD / QCCs derived again and the bands' K_max / delta with them: the plan of a plain encode at that step
+bool rate_apply_step(Plan& Q, float qstep);
+int  rate_table_build(const Plan& P, RateTable& T);
+int  rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
+int  requant_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t n, const uint32_t* d_class, const BandQuant* d_quant);
+
 // Nothing may leave the C ABI as a C++ exception (a codestream from anywhere can ask for tables the
 // host cannot hold): entry points that build containers run their bodies through this.
 template <typename F>

@@ -1,0 +1,192 @@
+// openjph_amd/csrc/ojph_rate.cpp -- encoding to a byte budget, host side (include/ojphgpu.h section 5b): the grid of base
+// steps, the quantisation of every band at every step of it, the model that turns the band statistics into predicted bytes
+// and the search that finds the finest step whose codestream fits.  Needs no GPU: the size of a trial comes from a callback.
+//
+// The reference side of it is param_qcd::set_irrev_quant (ojph_params.cpp:1542-1599), which scales the base step per
+// sub-band, and encode_SPqcd (:1602-1613), which rounds it to 5 + 11 bits; derive_quant (ojph_plan.cpp) restates both, and
+// the table below is nothing but derive_quant at the 241 steps.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "ojph_plan.h"
+
+namespace ojphgpu {
+
+float rate_grid_qstep(uint32_t j) { return (float)std::exp2(-1.0 - (double)j / 16.0); }
+
+bool rate_plan_ok(const Plan& P)
+{
+  if (P.parsed || P.p.reserved[2] != 0 || !P.atks.empty() || !P.dfss.empty() || P.p.wavelet != 0) return false;
+  for (uint32_t c = 0; c < P.p.num_comps; ++c) {
+    const CodStyle& st = P.style(c);
+    if (st.rev || st.wavelet >= 2 || st.dfs >= 0) return false;
+    if (c < OJPHGPU_MAX_COC_COMPS && P.p.qcc_qfactor[c] != 0) return false;
+  }
+  return !P.cod.rev;
+}
+
+bool rate_apply_step(Plan& Q, float qstep)
+{
+  Q.p.qstep = qstep;
+  if (!derive_quant(Q)) return false;
+  for (Band& B : Q.bands) {                                  // as build_plan fills them (ojph_subband.cpp:156-164)
+    B.K_max = band_Kmax(Q, B.comp, B.res, B.band);
+    if (B.K_max == 0 || B.K_max > 31) return false;
+    float d = band_delta(Q, B.comp, B.res, B.band);
+    d /= (float)(1u << ((31u - B.K_max) & 31u));
+    B.delta = d; B.delta_inv = 1.0f / d;
+  }
+  return true;
+}
+
+int rate_table_build(const Plan& P, RateTable& T)
+{
+  if (!rate_plan_ok(P)) return OJPHGPU_E_INVALID;
+  std::map<uint64_t, uint32_t> ids;
+  std::vector<Band> reps;                                    // one band per class
+  T.band_class.resize(P.bands.size());
+  for (size_t i = 0; i < P.bands.size(); ++i) {
+    const Band& B = P.bands[i];
+    const uint64_t key = ((uint64_t)B.comp << 16) | ((uint64_t)B.res << 8) | B.band;
+    auto it = ids.find(key);
+    if (it == ids.end()) { it = ids.emplace(key, (uint32_t)reps.size()).first; reps.push_back(B); }
+    T.band_class[i] = it->second;
+  }
+  T.nclasses = (uint32_t)reps.size();
+  T.num_blocks = P.blocks.size();
+  // what derive_quant and band_Kmax / band_delta read of a plan, and nothing of its tables
+  Plan L;
+  L.p = P.p; L.comps = P.comps; L.cod = P.cod; L.coc = P.coc; L.frame_elems = P.frame_elems;
+  L.bands = reps;
+  T.quant.assign((size_t)OJPHGPU_RATE_GRID * T.nclasses, BandQuant{ 0.0f, 0 });
+  T.log2_step.assign(T.quant.size(), 0.0);
+  for (uint32_t j = 0; j < OJPHGPU_RATE_GRID; ++j) {
+    if (!rate_apply_step(L, rate_grid_qstep(j))) return OJPHGPU_E_INVALID;
+    for (uint32_t c = 0; c < T.nclasses; ++c) {
+      const Band& B = L.bands[c];
+      T.quant[(size_t)j * T.nclasses + c] = BandQuant{ B.delta, B.K_max };
+      T.log2_step[(size_t)j * T.nclasses + c] = std::log2((double)B.delta) + (double)(31u - B.K_max);
+    }
+  }
+  return OJPHGPU_OK;
+}
+
+namespace {
+
+// The model.  A coefficient whose half octave lies below its band's step costs nothing; one at t = log2(|c| / step) > 0
+// costs t magnitude bits plus about three for its sign and its share of the VLC and MEL strings; the half octave around
+// the step is significant for part of its members.  Per block a few bytes of packet header, per codestream its markers.
+// Its absolute level is off by 10 % at the usual rates and by far more near the knee, where most coefficients are
+// within a factor of two of the step -- the search rescales it by what a trial measures.
+struct Model {
+  const RateTable& T;
+  std::vector<double> h;                                     // [nclasses][BINS]: the bands' histograms summed per class
+  std::vector<uint8_t> used;                                 // per class: the bins that hold anything, as a list
+  std::vector<uint32_t> used_first;
+  double memo[OJPHGPU_RATE_GRID];
+  Model(const RateTable& t, const uint32_t* hist) : T(t), h((size_t)t.nclasses * OJPHGPU_STATS_BINS, 0.0)
+  {
+    for (size_t b = 0; b < T.band_class.size(); ++b)
+      for (uint32_t k = 0; k < OJPHGPU_STATS_BINS; ++k) h[(size_t)T.band_class[b] * OJPHGPU_STATS_BINS + k] += hist[b * OJPHGPU_STATS_BINS + k];
+    used_first.assign(T.nclasses + 1, 0);
+    for (uint32_t c = 0; c < T.nclasses; ++c) {
+      for (uint32_t k = 1; k < OJPHGPU_STATS_BINS; ++k) if (h[(size_t)c * OJPHGPU_STATS_BINS + k] > 0) used.push_back((uint8_t)k);
+      used_first[c + 1] = (uint32_t)used.size();
+    }
+    for (double& m : memo) m = -1.0;
+  }
+  double bytes(uint32_t j)
+  {
+    if (memo[j] >= 0) return memo[j];
+    double bits = 0;
+    for (uint32_t c = 0; c < T.nclasses; ++c) {
+      const double ld = T.log2_step[(size_t)j * T.nclasses + c];
+      for (uint32_t i = used_first[c]; i < used_first[c + 1]; ++i) {
+        const uint32_t k = used[i];
+        // bin k holds 2^e (1 + m / 2) .. with e = (k + 1) / 2 - 32, m = the top mantissa bit: log2 of its middle
+        const double mid = (double)((int)((k + 1) / 2) - 32) + (((k + 1) & 1u) == 0 ? 0.29 : 0.79);
+        const double t = mid - ld;
+        if (t > -0.5) bits += h[(size_t)c * OJPHGPU_STATS_BINS + k] * (std::max(t, 0.0) + 3.0) * (t > 0.5 ? 1.0 : 0.6);
+      }
+    }
+    return memo[j] = bits / 8.0 + 300.0 + 6.0 * (double)T.num_blocks;
+  }
+};
+
+}  // namespace
+
+int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out)
+{
+  if (!fn || !out) return OJPHGPU_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  const int N = OJPHGPU_RATE_GRID;
+  std::vector<int64_t> size((size_t)N, -1);
+  Model* model = hist ? new Model(T, hist) : nullptr;
+  struct Free { Model* m; ~Free() { delete m; } } fr{ model };
+  // every index <= lo that was tried fits, every index >= hi that was tried does not; lo and hi themselves were tried (or are
+  // the ends -1 / N).  hi - lo == 1 is the certificate: size(lo) <= B < size(lo + 1), both measured.
+  int lo = -1, hi = N;
+  double scale = 1.0;
+  uint32_t passes = 0;
+  while (hi - lo > 1) {
+    int j = (lo + hi) / 2;
+    if (model && passes < 6) {
+      // the finest candidate the rescaled model lets fit (its prediction grows with j: bisection over the candidates)
+      int a = lo, b = hi;                                    // a fits (or is the end), b does not
+      while (b - a > 1) { const int m = (a + b) / 2; if (scale * model->bytes((uint32_t)m) <= (double)max_bytes) a = m; else b = m; }
+      j = std::min(std::max(a, lo + 1), hi - 1);
+    }
+    if (passes == 0) out->first_guess = (uint32_t)j;
+    const int64_t s = fn(user, (uint32_t)j);
+    ++passes;
+    out->passes = passes;
+    if (s < 0) return s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s;
+    size[(size_t)j] = s;
+    if (model) { const double p = model->bytes((uint32_t)j); scale = p > 0 ? (double)s / p : 1.0; }
+    if ((uint64_t)s <= max_bytes) lo = j; else hi = j;
+  }
+  if (lo < 0) return OJPHGPU_E_BUDGET;
+  out->grid_index = (uint32_t)lo; out->qstep = rate_grid_qstep((uint32_t)lo);
+  out->bytes = (uint64_t)size[(size_t)lo];
+  out->bytes_finer = hi < N ? (uint64_t)size[(size_t)hi] : 0;
+  return OJPHGPU_OK;
+}
+
+}  // namespace ojphgpu
+
+using namespace ojphgpu;
+
+extern "C" int ojphgpu_rate_grid_qstep(uint32_t j, float* qstep)
+{
+  if (j >= OJPHGPU_RATE_GRID || !qstep) return OJPHGPU_E_INVALID;
+  *qstep = rate_grid_qstep(j);
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
+                                   ojphgpu_rate_info* out)
+{
+  if (!plan || !fn || !out) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    RateTable T;
+    const int rc = rate_table_build(plan->plan, T);
+    if (rc) return rc;
+    return rate_search(T, hist, max_bytes, fn, user, out);
+  });
+}
+
+extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out)
+{
+  if (!plan || !hist || !out) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    RateTable T;
+    const int rc = rate_table_build(plan->plan, T);
+    if (rc) return rc;
+    Model m(T, hist);
+    for (uint32_t j = 0; j < OJPHGPU_RATE_GRID; ++j) out[j] = m.bytes(j);
+    return OJPHGPU_OK;
+  });
+}

@@ -61,6 +61,7 @@ extern "C" void ojphgpu_encoder_destroy(ojphgpu_encoder* e)
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   e->timer.destroy();
+  delete e->rate;
   delete e;
 }
 
@@ -84,6 +85,80 @@ extern "C" int ojphgpu_encoder_create_batch(const ojphgpu_plan* plan, int device
 {
   if (!plan) return OJPHGPU_E_INVALID;
   return no_throw([&] { return encoder_create(plan, device, stream, 0, (uint32_t)plan->plan.tiles.size(), num_frames, out); });
+}
+
+// The block descriptors of the encoder's blocks with their scratch slots, and the compacted output with its regions (e->
+// out_cap, nreg, h_regions, counters_bytes).  band_kmax: per band of the plan, the K_max the slots and the output are sized
+// for where it exceeds the plan's own (an encoder with a byte budget: the finest step its search may visit); null = the plan's.
+static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, std::vector<ojphgpu_cb_desc>& bd, uint64_t& scratch_total)
+{
+  const Plan& P = *e->P;
+  const uint32_t nframes = e->nframes;
+  bd.assign(e->block_ids.size(), ojphgpu_cb_desc());
+  uint64_t scratch_bytes = 0, samples = 0;
+  bool over32_top = false, over32_rest = false, over128_top = false, over128_rest = false;
+  for (size_t i = 0; i < bd.size(); ++i) {
+    const Block& k = P.blocks[e->block_ids[i]]; const Band& B = P.bands[k.band];
+    samples += (uint64_t)k.r.w * k.r.h;
+    ojphgpu_cb_desc& d = bd[i]; memset(&d, 0, sizeof(d));
+    const bool wide = is_wide(P, B.comp);                  // 64-bit samples: two arena elements each
+    d.coef_off = B.plane_off + ((uint64_t)k.r.y0 * B.pitch + k.r.x0) * (wide ? 2u : 1u); d.pitch = B.pitch;
+    d.w = (uint16_t)k.r.w; d.h = (uint16_t)k.r.h; d.K_max = (uint8_t)B.K_max; d.reversible = (uint8_t)((P.style(B.comp).rev ? 1 : 0) | (wide ? 4 : 0));
+    d.missing_msbs = (uint8_t)(B.K_max - 1); d.num_passes = 1; d.delta = B.delta;
+    d.data_off = scratch_bytes; d.scratch_cap = block_scratch_bytes(k.r.w, k.r.h, band_kmax ? std::max(B.K_max, band_kmax[k.band]) : B.K_max);
+    scratch_bytes += d.scratch_cap;
+    (i < e->n_top ? e->widths_top : e->widths_rest) |= wide ? 32 : ((k.r.w > 64 ? 2 : 1) | ((d.reversible & 1) ? 4 : 8));   // which kernel variants the range needs
+    if (!wide && k.r.w > 32 && k.r.w <= 64) (i < e->n_top ? over32_top : over32_rest) = true;
+    if (!wide && k.r.w > 128) (i < e->n_top ? over128_top : over128_rest) = true;
+  }
+  if (!over32_top) e->widths_top |= 16;                    // every block of the range at most 32 samples wide (e.g. the IMF profile's 32 x 32)
+  if (!over32_rest) e->widths_rest |= 16;
+  if (!over128_top) e->widths_top |= 64;                   // no block wider than 128 samples: 128 x 32 blocks take the narrow kernel, too
+  if (!over128_rest) e->widths_rest |= 64;
+  if (nframes > 1) {                                      // replicate the block descriptors, frame-major
+    const size_t nb = bd.size();
+    bd.resize(nb * nframes);
+    for (uint32_t f = 1; f < nframes; ++f)
+      for (size_t i = 0; i < nb; ++i) {
+        ojphgpu_cb_desc d = bd[i];
+        d.coef_off += (uint64_t)f * P.arena_elems; d.data_off += (uint64_t)f * scratch_bytes;
+        bd[f * nb + i] = d;
+      }
+    scratch_bytes *= nframes; samples *= nframes;
+  }
+  // The compacted output: scratch_bytes is a true upper bound of what the blocks can produce (K_max + 2 bits per
+  // sample plus stuffing); samples * 3 bytes covers every bit depth up to 20 on any content and keeps the buffer of
+  // the usual frames small -- deeper samples get the true bound, so that incompressible content cannot overflow.
+  // The byte cursor is 32 bits wide: a batch whose bound exceeds 4 GiB is clamped there and a frame batch that
+  // really produces more reports OJPHGPU_E_OVERFLOW (code fewer frames per batch).
+  uint32_t kmax_all = 0;
+  for (size_t b = 0; b < P.bands.size(); ++b) kmax_all = std::max(kmax_all, band_kmax ? std::max(P.bands[b].K_max, band_kmax[b]) : P.bands[b].K_max);
+  uint64_t cap = kmax_all > 20 ? scratch_bytes : std::min<uint64_t>(scratch_bytes, samples * 3 + (1u << 20));
+  cap = std::min<uint64_t>(cap, 0xFFFFFF00ull);
+  // ... split into regions (see ojphgpu_objects.h): a region holds the sum of its own blocks' shares of that bound
+  {
+    const char* ev = getenv("OJPHGPU_ENC_REGIONS"); const long v = ev ? atol(ev) : 16;
+    uint32_t R = (v >= 0 && v <= 64 && (v & (v - 1)) == 0) ? (uint32_t)v : 16u;
+    if (bd.size() < 4 * (size_t)R) R = 0;                   // a handful of blocks: one cursor
+    std::vector<uint64_t> rc(R ? R : 1, 0);
+    if (R) for (size_t i = 0; i < bd.size(); ++i) {
+      const uint64_t own = kmax_all > 20 ? bd[i].scratch_cap : std::min<uint64_t>(bd[i].scratch_cap, (uint64_t)bd[i].w * bd[i].h * 3 + 64);
+      rc[(i < e->n_top ? i : i - e->n_top) & (R - 1)] += own;   // the kernel sees the index inside its launch
+    }
+    uint64_t total = 0;
+    e->h_regions.assign(2 * (size_t)R, 0);
+    for (uint32_t r = 0; r < R; ++r) {
+      const uint64_t c = (rc[r] + (1u << 16) + 255) & ~(uint64_t)255;
+      if (total + c > 0xFFFFFF00ull) { R = 0; break; }      // the byte offsets are 32 bits wide: one clamped cursor, as before
+      e->h_regions[2 * r] = (uint32_t)total; e->h_regions[2 * r + 1] = (uint32_t)c;
+      total += c;
+    }
+    e->nreg = R;
+    if (R) cap = total; else e->h_regions.clear();
+    e->counters_bytes = R ? (size_t)R * 128 : 16;
+  }
+  e->out_cap = (uint32_t)cap;
+  scratch_total = scratch_bytes;
 }
 
 static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count,
@@ -155,70 +230,10 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
           hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
     }
   }
-  std::vector<ojphgpu_cb_desc> bd(e->block_ids.size());
-  uint64_t scratch_bytes = 0, samples = 0;
-  bool over32_top = false, over32_rest = false, over128_top = false, over128_rest = false;
-  for (size_t i = 0; i < bd.size(); ++i) {
-    const Block& k = P.blocks[e->block_ids[i]]; const Band& B = P.bands[k.band];
-    samples += (uint64_t)k.r.w * k.r.h;
-    ojphgpu_cb_desc& d = bd[i]; memset(&d, 0, sizeof(d));
-    const bool wide = is_wide(P, B.comp);                  // 64-bit samples: two arena elements each
-    d.coef_off = B.plane_off + ((uint64_t)k.r.y0 * B.pitch + k.r.x0) * (wide ? 2u : 1u); d.pitch = B.pitch;
-    d.w = (uint16_t)k.r.w; d.h = (uint16_t)k.r.h; d.K_max = (uint8_t)B.K_max; d.reversible = (uint8_t)((P.style(B.comp).rev ? 1 : 0) | (wide ? 4 : 0));
-    d.missing_msbs = (uint8_t)(B.K_max - 1); d.num_passes = 1; d.delta = B.delta;
-    d.data_off = scratch_bytes; d.scratch_cap = block_scratch_bytes(k.r.w, k.r.h, B.K_max);
-    scratch_bytes += d.scratch_cap;
-    (i < e->n_top ? e->widths_top : e->widths_rest) |= wide ? 32 : ((k.r.w > 64 ? 2 : 1) | ((d.reversible & 1) ? 4 : 8));   // which kernel variants the range needs
-    if (!wide && k.r.w > 32 && k.r.w <= 64) (i < e->n_top ? over32_top : over32_rest) = true;
-    if (!wide && k.r.w > 128) (i < e->n_top ? over128_top : over128_rest) = true;
-  }
-  if (!over32_top) e->widths_top |= 16;                    // every block of the range at most 32 samples wide (e.g. the IMF profile's 32 x 32)
-  if (!over32_rest) e->widths_rest |= 16;
-  if (!over128_top) e->widths_top |= 64;                   // no block wider than 128 samples: 128 x 32 blocks take the narrow kernel, too
-  if (!over128_rest) e->widths_rest |= 64;
-  if (nframes > 1) {                                      // replicate the block descriptors, frame-major
-    const size_t nb = bd.size();
-    bd.resize(nb * nframes);
-    for (uint32_t f = 1; f < nframes; ++f)
-      for (size_t i = 0; i < nb; ++i) {
-        ojphgpu_cb_desc d = bd[i];
-        d.coef_off += (uint64_t)f * P.arena_elems; d.data_off += (uint64_t)f * scratch_bytes;
-        bd[f * nb + i] = d;
-      }
-    scratch_bytes *= nframes; samples *= nframes;
-  }
-  // The compacted output: scratch_bytes is a true upper bound of what the blocks can produce (K_max + 2 bits per
-  // sample plus stuffing); samples * 3 bytes covers every bit depth up to 20 on any content and keeps the buffer of
-  // the usual frames small -- deeper samples get the true bound, so that incompressible content cannot overflow.
-  // The byte cursor is 32 bits wide: a batch whose bound exceeds 4 GiB is clamped there and a frame batch that
-  // really produces more reports OJPHGPU_E_OVERFLOW (code fewer frames per batch).
-  uint32_t kmax_all = 0;
-  for (const Band& B : P.bands) kmax_all = std::max(kmax_all, B.K_max);
-  uint64_t cap = kmax_all > 20 ? scratch_bytes : std::min<uint64_t>(scratch_bytes, samples * 3 + (1u << 20));
-  cap = std::min<uint64_t>(cap, 0xFFFFFF00ull);
-  // ... split into regions (see ojphgpu_objects.h): a region holds the sum of its own blocks' shares of that bound
-  {
-    const char* ev = getenv("OJPHGPU_ENC_REGIONS"); const long v = ev ? atol(ev) : 16;
-    uint32_t R = (v >= 0 && v <= 64 && (v & (v - 1)) == 0) ? (uint32_t)v : 16u;
-    if (bd.size() < 4 * (size_t)R) R = 0;                   // a handful of blocks: one cursor
-    std::vector<uint64_t> rc(R ? R : 1, 0);
-    if (R) for (size_t i = 0; i < bd.size(); ++i) {
-      const uint64_t own = kmax_all > 20 ? bd[i].scratch_cap : std::min<uint64_t>(bd[i].scratch_cap, (uint64_t)bd[i].w * bd[i].h * 3 + 64);
-      rc[(i < e->n_top ? i : i - e->n_top) & (R - 1)] += own;   // the kernel sees the index inside its launch
-    }
-    uint64_t total = 0;
-    e->h_regions.assign(2 * (size_t)R, 0);
-    for (uint32_t r = 0; r < R; ++r) {
-      const uint64_t c = (rc[r] + (1u << 16) + 255) & ~(uint64_t)255;
-      if (total + c > 0xFFFFFF00ull) { R = 0; break; }      // the byte offsets are 32 bits wide: one clamped cursor, as before
-      e->h_regions[2 * r] = (uint32_t)total; e->h_regions[2 * r + 1] = (uint32_t)c;
-      total += c;
-    }
-    e->nreg = R;
-    if (R) cap = total; else e->h_regions.clear();
-    e->counters_bytes = R ? (size_t)R * 128 : 16;
-  }
-  e->out_cap = (uint32_t)cap;
+  std::vector<ojphgpu_cb_desc> bd;
+  uint64_t scratch_bytes = 0;
+  encoder_block_layout(e, nullptr, bd, scratch_bytes);
+  const uint64_t cap = e->out_cap;
 
   if (e->arena.alloc(P.arena_elems * 4 * nframes) || e->dwt_descs.alloc(dd.size() * sizeof(dd[0])) ||
       e->img_descs.alloc(idd.size() * sizeof(dd[0])) || e->cb_descs.alloc(bd.size() * sizeof(bd[0])) || e->conv_descs.alloc(cd.size() * sizeof(cd[0])) ||
@@ -268,6 +283,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
   }
   if (rc) return rc;
   const ojphgpu_cb_desc* cbd = (const ojphgpu_cb_desc*)e->cb_descs.p;
+  const bool budget = e->max_bytes != 0;                    // the blocks are coded by the search, in ojphgpu_encoder_finish*
   bool forked = false;
   auto fork_top = [&]() -> int {                            // the top resolution's blocks are ready to be coded
     forked = true;
@@ -297,7 +313,19 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     if (rc) return rc;
     T.end(sp, s);
     const bool top_done = b.depth == 0 && (i + 1 == e->batches.size() || e->batches[i + 1].depth != 0);
-    if (e->n_top && top_done && (rc = fork_top()) != 0) return rc;
+    if (!budget && e->n_top && top_done && (rc = fork_top()) != 0) return rc;
+  }
+  if (budget) {
+    EncoderRate& R = *e->rate;
+    HIPCHK(hipMemsetAsync(R.hist.p, 0, R.hist.n, s));
+    const int sp = T.begin(SP_STATS, s);
+    rc = ojphgpu_band_stats(s, (const ojphgpu_stats_desc*)R.stats_descs.p, R.n_stats, R.stats_max_w, R.stats_max_h, e->arena.p, (uint32_t*)R.hist.p);
+    if (rc) return rc;
+    T.end(sp, s);
+    T.finish(s);
+    R.searched = false; R.at = -1;
+    e->ran = true; e->fetched = false;
+    return OJPHGPU_OK;
   }
   if (e->n_top && !forked && (rc = fork_top()) != 0) return rc;
   const uint32_t nb_all = (uint32_t)e->block_ids.size() * e->nframes;
@@ -335,7 +363,7 @@ extern "C" int ojphgpu_encoder_coded_bytes(ojphgpu_encoder* e, uint64_t* bytes)
 // table of frame `frame`
 static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu_coded_block>& cb)
 {
-  const Plan& P = *e->P;
+  const Plan& P = e->max_bytes ? e->rate->plan->plan : *e->P;   // (a byte budget: the plan at the step the search chose)
   if (frame >= e->nframes) return OJPHGPU_E_INVALID;
   if (!e->fetched) {
     int rc = ojphgpu_encoder_coded_bytes(e, &e->nbytes);
@@ -376,6 +404,8 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
   return OJPHGPU_OK;
 }
 
+static int encoder_rate_search(ojphgpu_encoder* e);
+
 extern "C" int ojphgpu_encoder_finish(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len)
 {
   if (!e || !out_len || !e->ran) return OJPHGPU_E_INVALID;
@@ -391,10 +421,14 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
   const bool tm = getenv("OJPHGPU_TIMING") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
-  int rc = encoder_fetch(e, frame, cb);
+  int rc = e->max_bytes ? encoder_rate_search(e) : OJPHGPU_OK;
+  if (rc) return rc;
+  if (e->max_bytes) t0 = now();
+  rc = encoder_fetch(e, frame, cb);
   if (rc) return rc;
   auto t1 = now();
-  rc = ojphgpu_t2_write(e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
+  rc = ojphgpu_t2_write(e->max_bytes ? e->rate->plan : e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
+  if (e->max_bytes) e->rate->final_ms = std::chrono::duration<double, std::milli>(now() - t0).count();
   if (tm) fprintf(stderr, "ojphgpu: finish frame %u: D2H %.2f ms, Tier-2 %.2f ms\n", frame,
                   std::chrono::duration<double, std::milli>(t1 - t0).count(),
                   std::chrono::duration<double, std::milli>(now() - t1).count());
@@ -405,7 +439,7 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
 extern "C" int ojphgpu_encoder_finish_tiles(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len,
                                              uint32_t* tile_part_len)
 {
-  if (!e || !out_len || !e->ran) return OJPHGPU_E_INVALID;
+  if (!e || !out_len || !e->ran || e->max_bytes) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     std::vector<ojphgpu_coded_block> cb;
     int rc = encoder_fetch(e, 0, cb);
@@ -425,7 +459,7 @@ int assemble_launch(void* stream, const T2Job* d_jobs, uint32_t njobs, const uin
 extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* d_out, size_t cap, size_t* out_len,
                                                     uint32_t* tile_part_len)
 {
-  if (!e || !out_len || !e->ran) return OJPHGPU_E_INVALID;
+  if (!e || !out_len || !e->ran || e->max_bytes) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     const Plan& P = *e->P;
     uint64_t nbytes = 0;
@@ -461,6 +495,168 @@ extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* 
     HIPCHK(hipStreamSynchronize(e->stream));            // the layout staging goes away with this call
     return OJPHGPU_OK;
   });
+}
+
+// ---------------------------------------------------------------------------------------------
+// encoding to a byte budget (include/ojphgpu.h section 5b)
+// ---------------------------------------------------------------------------------------------
+extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes)
+{
+  if (!e) return OJPHGPU_E_INVALID;
+  if (max_bytes == 0) {
+    if (e->max_bytes && e->rate) {                          // the descriptors go back to the plan's own step
+      HIPCHK(hipSetDevice(e->device));
+      HIPCHK(hipStreamSynchronize(e->stream));
+      const std::vector<ojphgpu_cb_desc>& bd = e->rate->bd;
+      if (!bd.empty()) HIPCHK(hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice));
+      e->ran = false;
+    }
+    e->max_bytes = 0;
+    return OJPHGPU_OK;
+  }
+  const Plan& P = *e->P;
+  if (e->nframes != 1 || e->tiles.first != 0 || e->tiles.count != P.tiles.size() || e->o_out || !rate_plan_ok(P)) return OJPHGPU_E_INVALID;
+  if (e->rate) { e->max_bytes = max_bytes; e->ran = false; return OJPHGPU_OK; }
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(e->device));
+    EncoderRate* R = new EncoderRate();
+    struct Owner { EncoderRate* p; ~Owner() { delete p; } } owner{ R };
+    for (const Band& B : P.bands) if ((uint64_t)B.r.w * B.r.h > 0xFFFFFFFFull) return OJPHGPU_E_INVALID;   // the counts are 32 bits wide
+    int rc = rate_table_build(P, R->table);
+    if (rc) return rc;
+    R->plan = new ojphgpu_plan{ P };
+    std::vector<ojphgpu_stats_desc> sd;
+    for (size_t i = 0; i < P.bands.size(); ++i) {
+      const Band& B = P.bands[i];
+      if (B.empty) continue;
+      sd.push_back(ojphgpu_stats_desc{ B.plane_off, B.pitch, B.r.w, B.r.h, (uint32_t)i });
+      R->stats_max_w = std::max(R->stats_max_w, B.r.w); R->stats_max_h = std::max(R->stats_max_h, B.r.h);
+    }
+    R->n_stats = (uint32_t)sd.size();
+    std::vector<uint32_t> cls(e->block_ids.size());
+    for (size_t i = 0; i < cls.size(); ++i) cls[i] = R->table.band_class[P.blocks[e->block_ids[i]].band];
+    // The scratch slots and the compacted output are sized for the finest step of the grid -- the largest K_max a trial can
+    // give a band -- so that no trial can overflow them whatever the budget
+    const uint32_t nc = R->table.nclasses;
+    std::vector<uint32_t> kfine(P.bands.size());
+    for (size_t i = 0; i < kfine.size(); ++i) kfine[i] = R->table.quant[(size_t)(OJPHGPU_RATE_GRID - 1) * nc + R->table.band_class[i]].K_max;
+    std::vector<ojphgpu_cb_desc>& bd = R->bd;
+    uint64_t scratch_bytes = 0;
+    encoder_block_layout(e, kfine.data(), bd, scratch_bytes);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->side) HIPCHK(hipStreamSynchronize(e->side));
+    e->scratch.release(); e->out.release(); e->regions.release(); e->counters.release();
+    if (e->scratch.alloc(scratch_bytes) || e->out.alloc(e->out_cap) || e->counters.alloc(e->counters_bytes) ||
+        (e->nreg && e->regions.alloc(e->h_regions.size() * 4)) ||
+        R->stats_descs.alloc(sd.size() * sizeof(sd[0])) || R->hist.alloc(P.bands.size() * OJPHGPU_STATS_BINS * 4) ||
+        R->block_class.alloc(cls.size() * 4) || R->quant.alloc((size_t)nc * sizeof(BandQuant)))
+      return OJPHGPU_E_NOMEM;
+    if (e->nreg) HIPCHK(hipMemcpy(e->regions.p, e->h_regions.data(), e->h_regions.size() * 4, hipMemcpyHostToDevice));
+    if (!bd.empty()) HIPCHK(hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice));
+    if (!sd.empty()) HIPCHK(hipMemcpy(R->stats_descs.p, sd.data(), sd.size() * sizeof(sd[0]), hipMemcpyHostToDevice));
+    if (!cls.empty()) HIPCHK(hipMemcpy(R->block_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
+    R->h_hist.assign(P.bands.size() * OJPHGPU_STATS_BINS, 0);
+    e->rate = R; owner.p = nullptr;
+    e->max_bytes = max_bytes; e->ran = false;
+    return OJPHGPU_OK;
+  });
+}
+
+// one trial of the search: the blocks coded at grid index j, in the schedule of a plain run (the top resolution's share on
+// the side stream); the block lengths come to the host and the Tier-2 layout gives the codestream's length
+static int64_t encoder_rate_trial(void* user, uint32_t j)
+{
+  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
+  EncoderRate& R = *e->rate;
+  Plan& Q = R.plan->plan;
+  hipStream_t s = e->stream;
+  auto hip = [](hipError_t x) { return x == hipSuccess; };
+  R.at = -1;
+  if (!rate_apply_step(Q, rate_grid_qstep(j))) return OJPHGPU_E_INVALID;
+  const uint32_t nc = R.table.nclasses, nb = (uint32_t)e->block_ids.size();
+  ojphgpu_cb_desc* cbd = (ojphgpu_cb_desc*)e->cb_descs.p;
+  uint32_t* cnt = (uint32_t*)e->counters.p;
+  ojphgpu_cb_result* res = (ojphgpu_cb_result*)e->results.p;
+  if (!hip(hipMemcpyAsync(R.quant.p, &R.table.quant[(size_t)j * nc], (size_t)nc * sizeof(BandQuant), hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
+  int rc = requant_launch(s, cbd, nb, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p);
+  if (rc) return rc;
+  if (!hip(hipMemsetAsync(cnt, 0, e->counters_bytes, s))) return OJPHGPU_E_HIP;
+  if (e->n_top) {
+    if (!hip(hipEventRecord(e->ev_fork, s)) || !hip(hipStreamWaitEvent(e->side, e->ev_fork, 0))) return OJPHGPU_E_HIP;
+    rc = ojphgpu::ht_encode_launch(e->side, cbd, e->n_top, e->arena.p, (uint8_t*)e->scratch.p, (uint8_t*)e->out.p, e->out_cap, res, cnt, cnt + 1,
+                                   e->widths_top, (const uint32_t*)e->regions.p, e->nreg);
+    if (rc) return rc;
+    if (!hip(hipEventRecord(e->ev_join, e->side))) return OJPHGPU_E_HIP;
+  }
+  rc = ojphgpu::ht_encode_launch(s, cbd + e->n_top, nb - e->n_top, e->arena.p, (uint8_t*)e->scratch.p, (uint8_t*)e->out.p, e->out_cap,
+                                 res + e->n_top, cnt, cnt + 1, e->widths_rest, (const uint32_t*)e->regions.p, e->nreg);
+  if (rc) return rc;
+  if (e->n_top && !hip(hipStreamWaitEvent(s, e->ev_join, 0))) return OJPHGPU_E_HIP;
+  const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
+  uint32_t status = 0;
+  const auto w0 = std::chrono::steady_clock::now();         // (a copy into pageable memory waits for the launches before it)
+  if (rbytes && !hip(hipMemcpyAsync(e->h_results.data(), res, rbytes, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
+  if (!hip(hipMemcpyAsync(&status, cnt + 1, 4, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
+  if (!hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
+  R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  e->fetched = false;
+  if (status) return OJPHGPU_E_OVERFLOW;                    // (cannot happen: the buffers hold the finest step's bound)
+  std::vector<ojphgpu_coded_block> cb(Q.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
+  for (size_t i = 0; i < nb; ++i) {
+    const ojphgpu_cb_result& r = e->h_results[i];
+    ojphgpu_coded_block& c = cb[e->block_ids[i]];
+    c.offset = r.offset; c.len1 = r.length;
+    c.missing_msbs = r.length ? Q.bands[Q.blocks[e->block_ids[i]].band].K_max - 1 : 0;
+    c.num_passes = r.length ? 1 : 0;
+  }
+  T2Layout L;
+  rc = t2_layout_codestream(Q, cb.data(), L);
+  if (rc) return rc;
+  R.at = (int)j;
+  return (int64_t)L.total;
+}
+
+// the search of the last run, once: afterwards the device holds the coded blocks of j* and R.plan stands at its step
+static int encoder_rate_search(ojphgpu_encoder* e)
+{
+  EncoderRate& R = *e->rate;
+  if (R.searched) return R.search_rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  R.wait_ms = 0;
+  auto run = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    int rc = rate_search(R.table, R.h_hist.data(), e->max_bytes, encoder_rate_trial, e, &R.info);
+    R.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
+    if (rc) return rc;
+    if (R.at != (int)R.info.grid_index) {                   // the last trial was j* + 1: j* is coded once more, and counted
+      const int64_t s = encoder_rate_trial(e, R.info.grid_index);
+      R.info.passes++;
+      if (s < 0) return (int)s;
+      if ((uint64_t)s != R.info.bytes) return OJPHGPU_E_HIP;  // the same blocks at the same step: anything else is a fault
+    }
+    return OJPHGPU_OK;
+  };
+  R.search_rc = no_throw(run);
+  R.searched = true;
+  R.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return R.search_rc;
+}
+
+extern "C" int ojphgpu_encoder_rate_info(ojphgpu_encoder* e, ojphgpu_rate_info* info)
+{
+  if (!e || !info || !e->rate || !e->rate->have_info) return OJPHGPU_E_INVALID;
+  *info = e->rate->info;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_rate_timing(ojphgpu_encoder* e, float out[4])
+{
+  if (!e || !out || !e->rate || !e->rate->searched || !e->ran) return OJPHGPU_E_INVALID;
+  out[0] = (float)e->rate->search_ms; out[1] = (float)e->rate->wait_ms; out[2] = (float)e->rate->final_ms;
+  if (e->timer.read(SP_STATS, &out[3])) return OJPHGPU_E_HIP;
+  return OJPHGPU_OK;
 }
 
 static int encode_host(ojphgpu_encoder* e, const void* h_image, int container, uint8_t* h_out, size_t cap, size_t* out_len)

@@ -448,9 +448,28 @@ struct Spans {
     return n;
   }
 };
-enum { SP_CONVERT = 0, SP_DWT = 1, SP_HT_ENC = 2, SP_PREP = 3, SP_STEP1 = 4, SP_STEP2 = 5, SP_REFINE = 6 };
+enum { SP_CONVERT = 0, SP_DWT = 1, SP_HT_ENC = 2, SP_PREP = 3, SP_STEP1 = 4, SP_STEP2 = 5, SP_REFINE = 6, SP_STATS = 7 };
 
 }  // namespace
+
+// What an encoder with a byte budget keeps (include/ojphgpu.h section 5b; made by the first ojphgpu_encoder_set_budget)
+struct EncoderRate {
+  RateTable table;                                 // the quantisation of every class of bands at every step of the grid
+  ojphgpu_plan* plan = nullptr;                    // the encoder's plan at the step of the last trial: what Tier-2 writes from
+  int at = -1;                                     // grid index the device results and `plan` stand at (-1: none)
+  DeviceBuf stats_descs, hist, block_class, quant;
+  uint32_t n_stats = 0, stats_max_w = 0, stats_max_h = 0;
+  std::vector<uint32_t> h_hist;
+  std::vector<ojphgpu_cb_desc> bd;                 // the block descriptors at the plan's own step (what budget 0 puts back)
+  bool searched = false; int search_rc = 0;        // the last run has been searched, with this verdict
+  bool have_info = false;
+  ojphgpu_rate_info info;
+  double search_ms = 0, wait_ms = 0, final_ms = 0;
+  ~EncoderRate() {
+    for (DeviceBuf* b : { &stats_descs, &hist, &block_class, &quant }) b->release();
+    delete plan;
+  }
+};
 
 struct ojphgpu_encoder {
   const ojphgpu_plan* handle = nullptr;
@@ -486,6 +505,8 @@ struct ojphgpu_encoder {
   std::vector<uint32_t> h_regions, h_cursors;
   DeviceBuf regions;
   size_t counters_bytes = 16;
+  uint64_t max_bytes = 0;                          // != 0: every frame is coded to this budget
+  EncoderRate* rate = nullptr;
 };
 // the device part of an encode: d_image holds the frame in `container`-bit elements (32 / 16)
 int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int container);

@@ -326,6 +326,39 @@ class Plan:
         return out[:need.value].tobytes()
 
 
+def rate_grid_qstep(j):
+    """base step j of the rate grid (ojphgpu_rate_grid_qstep): 0 = the coarsest (0.5) .. 240 = the finest (2^-16)"""
+    q = C.c_float()
+    check(capi.lib().ojphgpu_rate_grid_qstep(int(j), C.byref(q)), "rate_grid_qstep")
+    return float(q.value)
+
+
+def rate_search(plan: Plan, hist, max_bytes, size_fn):
+    """ojphgpu_rate_search: hist uint32 [plan.num_bands, 80] (None: no model), size_fn(j) -> bytes of the codestream at grid
+    index j.  -> dict(grid_index, qstep, bytes, bytes_finer, passes, first_guess); capi.OjphError with .code == capi.E_BUDGET
+    (and .info = the dict) when not even index 0 fits."""
+    info = capi.RateInfo()
+    cb = capi.SIZE_FN(lambda user, j: int(size_fn(int(j))))
+    h = None if hist is None else np.ascontiguousarray(hist, dtype=np.uint32)
+    if h is not None and h.size != plan.num_bands * capi.STATS_BINS:
+        raise ValueError("hist must hold 80 bins for every band of the plan")
+    rc = capi.lib().ojphgpu_rate_search(plan.handle, None if h is None else h.ctypes.data, int(max_bytes), cb, None, C.byref(info))
+    out = {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+    if rc != capi.OK:
+        err = capi.OjphError(rc, "rate_search")
+        err.info = out
+        raise err
+    return out
+
+
+def rate_predict(plan: Plan, hist):
+    """the model of ojphgpu_rate_search alone: predicted bytes at every grid index (float64 [241])"""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    out = np.zeros(capi.RATE_GRID, np.float64)
+    check(capi.lib().ojphgpu_rate_predict(plan.handle, h.ctypes.data, out.ctypes.data_as(C.POINTER(C.c_double))), "rate_predict")
+    return out
+
+
 def parse_codestream(data: bytes, resilient=False, skip=None) -> Plan:
     """skip = (skipped_res_for_data, skipped_res_for_recon): restrict_input_resolution BEFORE the tile-parts are read, as the
     reference orders it (ojphgpu_t2_parse_restricted) -- on undamaged codestreams the same as Plan.restrict_resolution afterwards"""

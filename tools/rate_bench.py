@@ -1,0 +1,120 @@
+"""Encoding to a byte budget against what a caller could do without it, device-resident: the C3 8K frame (16-bit containers
+in HBM) at budgets of 0.73, 0.2 and 0.05 bytes per sample.  Per budget three encoders take turns, `--runs` rounds after
+`--warmup`: (a) the budgeted encode, run_device + finish; (b) a plain encode at the fixed step qstep(j*) -- what the budget
+costs over knowing the answer; (c) a bisection over the grid made of plain encodes (both ends, then halving), each a
+run_device + finish at its own step -- what the parent commit offers.  Host clock around calls that end in a stream
+synchronise.  Prints one JSON line per budget: j*, passes, first guess, the model's prediction over the true length, median
+ms of (a) (b) (c), one pass's device wait and host share, the statistics kernel's time (device events) and its fraction of
+the 8 TB/s HBM peak (bytes = 4 x coefficients), beside the level-1 DWT launch of the same run.
+  python tools/rate_bench.py [--runs 10] [--warmup 3] [--rows 4320] [--no-bisect]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_PEAK = 8.0e12
+BPS = (0.73, 0.2, 0.05)
+GRID = 241
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rows", type=int, default=4320, help="top rows of the frame (rehearsals at a small size)")
+    ap.add_argument("--no-bisect", action="store_true")
+    a = ap.parse_args()
+    import torch
+    from openjph_amd import codec
+    from openjph_amd import plan as planmod
+    from openjph_amd.plan import make_params
+    from tests import synth
+    img = synth.survey_c3(rows=a.rows)
+    nc, h, w = img.shape
+    d_img = torch.from_numpy(img.astype(np.uint16).view(np.int16)).cuda()
+    samples = img.size
+    del img
+
+    def params(qstep):
+        return make_params(w, h, nc, bit_depth=12, reversible=False, qstep=qstep)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    budgeted = codec.Encoder(params(0.001))
+    # one plain encoder per grid index a bisection visits, made once (a caller would keep them, or pay for a plan each time)
+    plain = {}
+
+    def plain_len(j):
+        if j not in plain:
+            plain[j] = codec.Encoder(params(planmod.rate_grid_qstep(j)))
+        plain[j].run_device(d_img)
+        return len(plain[j].finish())
+
+    def bisect(budget):
+        n = [0]
+
+        def size(j):
+            n[0] += 1
+            return plain_len(j)
+        if size(0) > budget:
+            return None, n[0]
+        if size(GRID - 1) <= budget:
+            return GRID - 1, n[0]
+        lo, hi = 0, GRID - 1
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if size(mid) <= budget:
+                lo = mid
+            else:
+                hi = mid
+        return lo, n[0]
+
+    for bps in BPS:
+        budget = int(samples * bps)
+        budgeted.set_budget(budget)
+
+        def run_budgeted():
+            budgeted.run_device(d_img)
+            return budgeted.finish()
+        t = {"budget": [], "fixed": [], "bisect": []}
+        info = timing = stats = None
+        for i in range(a.warmup + a.runs):
+            ms, cs = timed(run_budgeted)
+            info, timing, stats = budgeted.rate_info(), budgeted.rate_timing(), budgeted.timing()
+            j = info["grid_index"]
+            ms_fixed, n_fixed = timed(lambda: plain_len(j))
+            assert n_fixed == len(cs) == info["bytes"]
+            if not a.no_bisect:
+                ms_bis, (jb, encodes) = timed(lambda: bisect(budget))
+                assert jb == j
+            if i >= a.warmup:
+                t["budget"].append(ms); t["fixed"].append(ms_fixed)
+                if not a.no_bisect:
+                    t["bisect"].append(ms_bis)
+        coefs = samples                                         # the sub-band planes hold one coefficient per sample
+        med = {k: round(float(np.median(v)), 3) if v else None for k, v in t.items()}
+        passes = info["passes"]
+        print(json.dumps(dict(
+            frame="c3 %dx%dx%d 12-bit, 16-bit containers" % (w, h, nc), bytes_per_sample=bps, budget=budget, grid_index=j,
+            qstep=info["qstep"], bytes=info["bytes"], bytes_finer=info["bytes_finer"], passes=passes, first_guess=info["first_guess"],
+            ms_budgeted=med["budget"], ms_fixed_step=med["fixed"], ms_bisection=med["bisect"],
+            bisection_encodes=None if a.no_bisect else encodes,
+            search_ms=round(timing["search_ms"], 3), pass_ms=round(timing["search_ms"] / passes, 3),
+            pass_device_wait_ms=round(timing["wait_ms"] / passes, 3), pass_host_ms=round((timing["search_ms"] - timing["wait_ms"]) / passes, 3),
+            final_download_t2_ms=round(timing["final_ms"], 3), run_device_ms=round(stats["total_ms"], 3),
+            stats_kernel_ms=round(timing["stats_ms"], 4), stats_hbm_fraction=round(4.0 * coefs / (timing["stats_ms"] * 1e-3) / HBM_PEAK, 3),
+            dwt_level1_ms=round(stats["dwt_levels_ms"][0], 4))), flush=True)
+
+
+if __name__ == "__main__":
+    main()
