@@ -615,33 +615,40 @@ __device__ __forceinline__ int fit_container(int v, const Conv& cv)
   return min(max(v, lo), hi);
 }
 
-template <bool REV, int IMG>
-__device__ __forceinline__ void store_image_pair(void* __restrict__ rowp, const Geo& g, int a, int b, const Conv& cv)
+// REG (the top level of a region synthesis): only plane columns [cx0, cx1) are stored, column x at x - cx0 of the row; a
+// lane whose column pair straddles a region edge stores the one sample inside
+template <bool REV, int IMG, bool REG = false>
+__device__ __forceinline__ void store_image_pair(void* __restrict__ rowp, const Geo& g, int a, int b, const Conv& cv, int cx0 = 0, int cx1 = 0)
 {
   a = fit_container<IMG>(a, cv); b = fit_container<IMG>(b, cv);
-  const int xl = 2 * g.j - g.ox;
+  const int x = 2 * g.j - g.ox, xl = REG ? x - cx0 : x;
+  const bool inL = REG && g.eL && x >= cx0 && x < cx1, inH = REG && g.eH && x + 1 >= cx0 && x + 1 < cx1;
+  // is the low / high sample stored?  Whole planes read g.eL / g.eH where a branch asks for them: copied to locals in front,
+  // like inL / inH, they cost the 9/7 colour kernels two registers (127 -> 129) and with them a wavefront per SIMD
+  auto eL = [&] { if constexpr (REG) return inL; else return g.eL; };
+  auto eH = [&] { if constexpr (REG) return inH; else return g.eH; };
   typedef typename ImgElem<IMG, int>::type E;
   E* row = (E*)rowp;
   if (IMG == 32) {
-    if (g.eL && g.eH) { I2 v; v.x = a; v.y = b; *reinterpret_cast<I2*>(row + xl) = v; }
-    else if (g.eL) row[xl] = (E)a;
-    else if (g.eH) row[xl + 1] = (E)b;
+    if (eL() && eH()) { I2 v; v.x = a; v.y = b; *reinterpret_cast<I2*>(row + xl) = v; }
+    else if (eL()) row[xl] = (E)a;
+    else if (eH()) row[xl + 1] = (E)b;
   } else {
-    if (g.eL && g.eH) { typename Vec2<E>::type v; v.x = (E)a; v.y = (E)b; *reinterpret_cast<typename Vec2<E>::type*>(row + xl) = v; }
-    else if (g.eL) row[xl] = (E)a;
-    else if (g.eH) row[xl + 1] = (E)b;
+    if (eL() && eH()) { typename Vec2<E>::type v; v.x = (E)a; v.y = (E)b; *reinterpret_cast<typename Vec2<E>::type*>(row + xl) = v; }
+    else if (eL()) row[xl] = (E)a;
+    else if (eH()) row[xl + 1] = (E)b;
   }
 }
 
-template <class WP, int IMG>
+template <class WP, int IMG, bool REG = false>
 __device__ __forceinline__ void store_pair(void* __restrict__ rowp, const Geo& g, typename WP::T l, typename WP::T h,
-                                           const Conv& cv)
+                                           const Conv& cv, int cx0 = 0, int cx1 = 0)
 {
   typedef typename WP::T T;
   constexpr bool REV = WP::REV;
   if (!g.store) return;
   const int xl = 2 * g.j - g.ox;
-  if constexpr (IMG != 0) store_image_pair<REV, IMG>(rowp, g, Cv<REV>::to_image(l, cv), Cv<REV>::to_image(h, cv), cv);
+  if constexpr (IMG != 0) store_image_pair<REV, IMG, REG>(rowp, g, Cv<REV>::to_image(l, cv), Cv<REV>::to_image(h, cv), cv, cx0, cx1);
   else {
     T* row = (T*)rowp;
     if (g.ox == 0 && g.eL && g.eH) {
@@ -656,75 +663,11 @@ __device__ __forceinline__ void store_pair(void* __restrict__ rowp, const Geo& g
 }
 
 // one reconstructed row of all NC planes; NC = 3: Y, Cb, Cr -> R, G, B on the way out
-template <class WP, int IMG, int NC>
-__device__ __forceinline__ void store_rows(char* const* dst, size_t off, const Geo& g, const Pair<typename WP::T>* v, const Conv* cv)
-{
-  typedef typename WP::T T;
-  constexpr bool REV = WP::REV;
-  if constexpr (NC == 3) {
-    if (!g.store) return;
-    T rl, gl, bl, rh, gh, bh;
-    Ct<REV>::inv(v[0].l, v[1].l, v[2].l, rl, gl, bl);
-    Ct<REV>::inv(v[0].h, v[1].h, v[2].h, rh, gh, bh);
-    store_image_pair<REV, IMG>(dst[0] + off, g, Cv<REV>::to_image(rl, cv[0]), Cv<REV>::to_image(rh, cv[0]), cv[0]);
-    store_image_pair<REV, IMG>(dst[1] + off, g, Cv<REV>::to_image(gl, cv[1]), Cv<REV>::to_image(gh, cv[1]), cv[1]);
-    store_image_pair<REV, IMG>(dst[2] + off, g, Cv<REV>::to_image(bl, cv[2]), Cv<REV>::to_image(bh, cv[2]), cv[2]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) store_pair<WP, IMG>(dst[k] + off, g, v[k].l, v[k].h, cv[k]);
-  }
-}
-
-// Clip (region synthesis, REG): only plane columns [clip.x0, clip.x1) are stored, column x at x - clip.x0 of the row; a lane
-// whose column pair straddles a region edge stores the one sample inside
-struct Clip { int x0, x1; };
-
-template <bool REV, int IMG, bool REG = false>
-__device__ __forceinline__ void store_image_pair_clip(void* __restrict__ rowp, const Geo& g, int a, int b, const Conv& cv, Clip clip = Clip{ 0, 0 })
-{
-  a = fit_container<IMG>(a, cv); b = fit_container<IMG>(b, cv);
-  int xl = 2 * g.j - g.ox;
-  bool eL = g.eL, eH = g.eH;
-  if constexpr (REG) { eL = eL && xl >= clip.x0 && xl < clip.x1; eH = eH && xl + 1 >= clip.x0 && xl + 1 < clip.x1; xl -= clip.x0; }
-  typedef typename ImgElem<IMG, int>::type E;
-  E* row = (E*)rowp;
-  if (IMG == 32) {
-    if (eL && eH) { I2 v; v.x = a; v.y = b; *reinterpret_cast<I2*>(row + xl) = v; }
-    else if (eL) row[xl] = (E)a;
-    else if (eH) row[xl + 1] = (E)b;
-  } else {
-    if (eL && eH) { typename Vec2<E>::type v; v.x = (E)a; v.y = (E)b; *reinterpret_cast<typename Vec2<E>::type*>(row + xl) = v; }
-    else if (eL) row[xl] = (E)a;
-    else if (eH) row[xl + 1] = (E)b;
-  }
-}
-
-template <class WP, int IMG, bool REG = false>
-__device__ __forceinline__ void store_pair_clip(void* __restrict__ rowp, const Geo& g, typename WP::T l, typename WP::T h,
-                                           const Conv& cv, Clip clip = Clip{ 0, 0 })
-{
-  typedef typename WP::T T;
-  constexpr bool REV = WP::REV;
-  if (!g.store) return;
-  const int xl = 2 * g.j - g.ox;
-  if constexpr (IMG != 0) store_image_pair_clip<REV, IMG, REG>(rowp, g, Cv<REV>::to_image(l, cv), Cv<REV>::to_image(h, cv), cv, clip);
-  else {
-    T* row = (T*)rowp;
-    if (g.ox == 0 && g.eL && g.eH) {
-      typedef T V2 __attribute__((ext_vector_type(2)));
-      V2 v; v.x = l; v.y = h;
-      *reinterpret_cast<V2*>(row + xl) = v;
-    } else {
-      if (g.eL) row[xl] = l;
-      if (g.eH) row[xl + 1] = h;
-    }
-  }
-}
-
 template <class WP, int IMG, int NC, bool REG = false>
-__device__ __forceinline__ void store_rows_clip(char* const* dst, size_t off, const Geo& g, const Pair<typename WP::T>* v, const Conv* cv,
-                                           Clip clip = Clip{ 0, 0 })
+__device__ __forceinline__ void store_rows(char* const* dst, size_t off, const Geo& g, const Pair<typename WP::T>* v, const Conv* cv,
+                                           int cx0 = 0, int cx1 = 0)
 {
+  static_assert(!REG || IMG != 0, "only image rows are clipped");
   typedef typename WP::T T;
   constexpr bool REV = WP::REV;
   if constexpr (NC == 3) {
@@ -732,210 +675,29 @@ __device__ __forceinline__ void store_rows_clip(char* const* dst, size_t off, co
     T rl, gl, bl, rh, gh, bh;
     Ct<REV>::inv(v[0].l, v[1].l, v[2].l, rl, gl, bl);
     Ct<REV>::inv(v[0].h, v[1].h, v[2].h, rh, gh, bh);
-    store_image_pair_clip<REV, IMG, REG>(dst[0] + off, g, Cv<REV>::to_image(rl, cv[0]), Cv<REV>::to_image(rh, cv[0]), cv[0], clip);
-    store_image_pair_clip<REV, IMG, REG>(dst[1] + off, g, Cv<REV>::to_image(gl, cv[1]), Cv<REV>::to_image(gh, cv[1]), cv[1], clip);
-    store_image_pair_clip<REV, IMG, REG>(dst[2] + off, g, Cv<REV>::to_image(bl, cv[2]), Cv<REV>::to_image(bh, cv[2]), cv[2], clip);
+    store_image_pair<REV, IMG, REG>(dst[0] + off, g, Cv<REV>::to_image(rl, cv[0]), Cv<REV>::to_image(rh, cv[0]), cv[0], cx0, cx1);
+    store_image_pair<REV, IMG, REG>(dst[1] + off, g, Cv<REV>::to_image(gl, cv[1]), Cv<REV>::to_image(gh, cv[1]), cv[1], cx0, cx1);
+    store_image_pair<REV, IMG, REG>(dst[2] + off, g, Cv<REV>::to_image(bl, cv[2]), Cv<REV>::to_image(bh, cv[2]), cv[2], cx0, cx1);
   } else {
 #pragma unroll
-    for (int k = 0; k < NC; ++k) store_pair_clip<WP, IMG, REG>(dst[k] + off, g, v[k].l, v[k].h, cv[k], clip);
+    for (int k = 0; k < NC; ++k) store_pair<WP, IMG, REG>(dst[k] + off, g, v[k].l, v[k].h, cv[k], cx0, cx1);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
 // inverse: LL, HL, LH, HH -> plane (or image plane, IMG); NC as in the forward kernel
 // ---------------------------------------------------------------------------------------------
-template <class WP, int IMG, int NC, int U = 1, int MODE = 0>
-__global__ __launch_bounds__(256) void dwt_inverse_kernel(const ojphgpu_dwt_desc* __restrict__ descs,
-                                                          uint32_t* __restrict__ base32,
-                                                          void* __restrict__ image, Conv cv, int row_pairs_arg, const WP w)
-{
-  typedef typename WP::T T;
-  constexpr bool REV = WP::REV;
-  (void)REV;
-  // a DWT launch is short and the next stage waits for it: when it shares the SIMDs with the long
-  // block-coder launch of the side stream, its wavefronts go first
-  __builtin_amdgcn_s_setprio(2);
-  const ojphgpu_dwt_desc d = descs[blockIdx.z * NC];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform, and the compiler knows it
-  int bx, by;
-  dwt_block_coords(row_pairs_arg, bx, by);
-  const int row_pairs = row_pairs_arg & 0xFFFF;
-  const int strip_x = bx * 4 + wave;
-  if (d.w == 0 || d.h == 0) return;
-  static_assert(MODE == 0 || (IMG == 0 && NC == 1), "one-direction levels exist below the top level of general-lifting components only");
-  const Geo g = make_geo(d, strip_x, lane, MODE == 2, MODE == 1);
-  const int npx = (g.w + g.ox + 1) >> 1, npy = (g.h + g.oy + 1) >> 1;
-  if (strip_x * VALID >= npx) return;
-  const int i0 = by * row_pairs;
-  if (i0 >= npy) return;
-  const int i1 = min(i0 + row_pairs, npy);
-
-  typedef typename ImgElem<IMG, T>::type E;                        // element type of the destination rows
-  char* dst[NC]; const T* ll[NC]; const T* hl[NC]; const T* lh[NC]; const T* hh[NC];
-  Conv cvs[NC];                                            // every plane's own sample format (ojph_tile.cpp:439-518 converts component by component)
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    const ojphgpu_dwt_desc dk = k ? descs[blockIdx.z * NC + k] : d;
-    cvs[k] = cv;
-    if (IMG && dk.reserved) { cvs[k].bit_depth = (int)(dk.reserved & 0xFFu); cvs[k].is_signed = (int)((dk.reserved >> 8) & 1u); }
-    dst[k] = IMG ? (char*)image + dk.src_off * sizeof(E) : (char*)(base32 + dk.src_off);
-    ll[k] = (const T*)(base32 + dk.ll_off); hl[k] = (const T*)(base32 + dk.hl_off); lh[k] = (const T*)(base32 + dk.lh_off); hh[k] = (const T*)(base32 + dk.hh_off);
-  }
-  const size_t dp = (size_t)d.src_pitch * sizeof(E);
-  const int h = g.h, oy = g.oy;
-  auto exL = [&](int t) { int y = 2 * t - oy; return y >= 0 && y < h; };
-  auto exH = [&](int t) { int y = 2 * t + 1 - oy; return y >= 0 && y < h; };
-  // raw sub-band samples of the lane's column pair in the low (LL|HL) or high (LH|HH) row of pair t, every plane
-  auto fetch = [&](int t, bool low_row, bool ex, Pair<T>* p) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      p[k].l = p[k].h = 0;
-      if (!ex) continue;
-      const int r = low_row ? t - oy : t;
-      if constexpr (MODE == 2) {                            // both columns from the same band
-        const T* band = low_row ? ll[k] : lh[k];
-        const uint32_t bp = low_row ? d.ll_pitch : d.lh_pitch;
-        if (g.eL) p[k].l = band[(size_t)r * bp + 2 * g.j];
-        if (g.eH) p[k].h = band[(size_t)r * bp + 2 * g.j + 1];
-      } else {
-        const T* lo = low_row ? ll[k] : lh[k]; const T* hi = low_row ? hl[k] : hh[k];
-        const uint32_t lop = low_row ? d.ll_pitch : d.lh_pitch, hip = low_row ? d.hl_pitch : d.hh_pitch;
-        if (g.eL) p[k].l = lo[(size_t)r * lop + (g.j - g.ox)];
-        if (g.eH) p[k].h = hi[(size_t)r * hip + g.j];
-      }
-    }
-  };
-
-  if constexpr (MODE == 1) {                               // rows only: row y of LL | HL -> row y of the plane, two rows per trip
-    const int y1 = min(2 * i1, h);
-    for (int y = 2 * i0; y < y1; y += 2) {
-      Pair<T> xa[NC], xb[NC];
-      fetch(y, true, true, xa); fetch(y + 1, true, y + 1 < y1, xb);
-#pragma unroll
-      for (int k = 0; k < NC; ++k) { horz_synthesis<WP>(w, xa[k].l, xa[k].h, g); horz_synthesis<WP>(w, xb[k].l, xb[k].h, g); }
-      store_rows<WP, IMG, NC>(dst, (size_t)y * dp, g, xa, cvs);
-      if (y + 1 < y1) store_rows<WP, IMG, NC>(dst, (size_t)(y + 1) * dp, g, xb, cvs);
-    }
-    return;
-  }
-
-  if (h == 1) {                                            // ojph_resolution.cpp:794-829, :900-923
-    if (i0 > 0) return;
-    Pair<T> x[NC];
-    fetch(0, oy == 0, true, x);
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      if constexpr (MODE != 2) horz_synthesis<WP>(w, x[k].l, x[k].h, g);
-      if (oy != 0) { x[k].l = w.halve(x[k].l); x[k].h = w.halve(x[k].h); }
-    }
-    store_rows<WP, IMG, NC>(dst, 0, g, x, cvs);
-    return;
-  }
-
-  // The pipeline loop, in two instantiations.  W1 = false (every plane but the one-column ones): the sub-band rows are fetched
-  // UNCONDITIONALLY, from a row and a column clamped into the band (every band of a plane of at least 2 x 2 samples has
-  // samples), and what does not exist becomes zero when the fetched registers are consumed a trip later -- no branch and no
-  // instruction touches a loaded register next to its load, so nothing waits there.  (With the loads under "if (exists)" the
-  // compiler merged them with the zero they replace and, depending on the instantiation, put a wait behind every one of
-  // them: eight round trips per trip where one is needed.)  W1 = true: the conditional loads, as before.
-  auto pipeline = [&](auto w1) {
-  constexpr bool W1 = decltype(w1)::value;
-  const int nlc = ((g.ox + g.w + 1) >> 1) - ((g.ox + 1) >> 1), nlr = ((oy + h + 1) >> 1) - ((oy + 1) >> 1);   // low columns / rows of the plane
-  const int col_l = MODE == 2 ? min(max(2 * g.j, 0), g.w - 1) : min(max(g.j - g.ox, 0), max(nlc - 1, 0));
-  const int col_h = MODE == 2 ? min(max(2 * g.j + 1, 0), g.w - 1) : min(max(g.j, 0), max(g.w - nlc - 1, 0));
-  auto fetch_any = [&](int t, bool low_row, Pair<T>* p) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      const T* lo = low_row ? ll[k] : lh[k]; const T* hi = MODE == 2 ? lo : (low_row ? hl[k] : hh[k]);
-      const uint32_t lop = low_row ? d.ll_pitch : d.lh_pitch, hip = MODE == 2 ? lop : (low_row ? d.hl_pitch : d.hh_pitch);
-      const int rows = low_row ? nlr : h - nlr;
-      const int r = min(max(low_row ? t - oy : t, 0), rows - 1);
-      p[k].l = lo[(size_t)r * lop + col_l];
-      p[k].h = hi[(size_t)r * hip + col_h];
-    }
-  };
-  auto request = [&](int t, Pair<T>* plo, Pair<T>* phi) {
-    if constexpr (W1) { fetch(t, true, exL(t), plo); fetch(t, false, exH(t), phi); }
-    else { fetch_any(t, true, plo); fetch_any(t, false, phi); }
-  };
-  auto existing = [&](int t, bool low_row, const Pair<T>& v) {   // a fetched pair as the lifting steps take it
-    if constexpr (W1) return v;
-    else { const bool ex = low_row ? exL(t) : exH(t); Pair<T> o; o.l = (ex && g.eL) ? v.l : (T)0; o.h = (ex && g.eH) ? v.h : (T)0; return o; }
-  };
-  const int t0 = max(i0 - WP::WARM, 0);
-  Pair<T> z; z.l = z.h = 0;
-  Pair<T> c[NC], cp[NC], b[NC], bp[NC], a[NC], ap[NC], xL[NC], xLp[NC];
-  // c[t], c[t-1], b[t], b[t-1], a[t-1], a[t-2], xL[t-1], xL[t-2]
-#pragma unroll
-  for (int k = 0; k < NC; ++k) c[k] = cp[k] = b[k] = bp[k] = a[k] = ap[k] = xL[k] = xLp[k] = z;
-  Pair<T> nlo[U][NC], nhi[U][NC];
-#pragma unroll
-  for (int u = 0; u < U; ++u) request(t0 + u, nlo[u], nhi[u]);      // sub-band rows of the first trip
-  for (int t = t0; t <= i1 + 1; t += U) {
-    Pair<T> in_lo[U][NC], in_hi[U][NC];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int k = 0; k < NC; ++k) { in_lo[u][k] = existing(t + u, true, nlo[u][k]); in_hi[u][k] = existing(t + u, false, nhi[u][k]); }
-    if (t + U <= i1 + 1) {                                  // request the next trip's rows now
-#pragma unroll
-      for (int u = 0; u < U; ++u) request(t + U + u, nlo[u], nhi[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int tt = t + u;
-      if (u != 0 && tt > i1 + 1) break;
-      // interior of the plane (every row tt-2 .. tt exists, no strip edge): the selects fold away
-      auto lift = [&](auto chk) {
-        constexpr bool CHK = decltype(chk)::value;
-        const bool eLt = exL(tt), eHt = exH(tt), eLp = exL(tt - 1), eHp = exH(tt - 1);
-        const bool eLpp = exL(tt - 2), eHpp = exH(tt - 2);
-        Pair<T> xh[NC];
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-          Pair<T> dd = in_lo[u][k], cc = in_hi[u][k];
-          cp[k] = c[k]; c[k] = z;
-          if (!CHK || eLt) { if constexpr (MODE != 2) horz_synthesis<WP, CHK>(w, dd.l, dd.h, g); dd.l = w.mulK(dd.l); dd.h = w.mulK(dd.h); } else dd = z;   // :855-856
-          if (!CHK || eHt) { if constexpr (MODE != 2) horz_synthesis<WP, CHK>(w, cc.l, cc.h, g); c[k].l = w.mulKinv(cc.l); c[k].h = w.mulKinv(cc.h); }    // :871-872
-          // b[t]
-          bp[k] = b[k];
-          b[k].l = w.s0(dd.l, pick<CHK>(eHp, cp[k].l, c[k].l), pick<CHK>(eHt, c[k].l, cp[k].l));
-          b[k].h = w.s0(dd.h, pick<CHK>(eHp, cp[k].h, c[k].h), pick<CHK>(eHt, c[k].h, cp[k].h));
-          // a[t-1]
-          ap[k] = a[k];
-          a[k].l = w.s1(cp[k].l, pick<CHK>(eLp, bp[k].l, b[k].l), pick<CHK>(eLt, b[k].l, bp[k].l));
-          a[k].h = w.s1(cp[k].h, pick<CHK>(eLp, bp[k].h, b[k].h), pick<CHK>(eLt, b[k].h, bp[k].h));
-          // xL[t-1]
-          xLp[k] = xL[k];
-          xL[k].l = w.s2(bp[k].l, pick<CHK>(eHpp, ap[k].l, a[k].l), pick<CHK>(eHp, a[k].l, ap[k].l));
-          xL[k].h = w.s2(bp[k].h, pick<CHK>(eHpp, ap[k].h, a[k].h), pick<CHK>(eHp, a[k].h, ap[k].h));
-          // xH[t-2]
-          xh[k].l = w.s3(ap[k].l, pick<CHK>(eLpp, xLp[k].l, xL[k].l), pick<CHK>(eLp, xL[k].l, xLp[k].l));
-          xh[k].h = w.s3(ap[k].h, pick<CHK>(eLpp, xLp[k].h, xL[k].h), pick<CHK>(eLp, xL[k].h, xLp[k].h));
-        }
-        if (tt - 2 >= i0 && tt - 2 < i1 && (!CHK || eHpp))
-          store_rows<WP, IMG, NC>(dst, (size_t)(2 * (tt - 2) + 1 - oy) * dp, g, xh, cvs);
-        if (tt - 1 >= i0 && tt - 1 < i1 && (!CHK || eLp))
-          store_rows<WP, IMG, NC>(dst, (size_t)(2 * (tt - 1) - oy) * dp, g, xL, cvs);
-      };
-      if (g.inner && 2 * (tt - 2) - oy >= 0 && 2 * tt + 1 - oy < h) lift(std::false_type());
-      else lift(std::true_type());
-    }
-  }
-  };
-  if (g.w == 1) pipeline(std::true_type()); else pipeline(std::false_type());
-}
-
-// Region synthesis (ojphgpu_dwt_inverse_region): dwt_inverse_kernel's pipeline with the flag REG, kept apart from it so that
-// the whole-plane kernels compile exactly as they did.  regions[i] is the exact output range of descriptor i.  The strips and
-// vertical chunks start at the ones that cover its first column / row -- the geometry (make_geo) stays the whole plane's, so
-// the halo and the warm-up read real neighbours and mirroring happens at the plane's edges only.  A lower level (no IMG)
-// stores whole strips into its plane; the top level (IMG) stores the region's samples only, row y / column x of the plane at
-// (y - ry0, x - rx0) of the region frame (out_off, out_pitch).
+// The one synthesis pipeline, behind both kernels below: dwt_inverse_kernel (whole planes: REG = false, no regions) and
+// dwt_inverse_region_kernel (ojphgpu_dwt_inverse_region: REG = true).  What a region adds sits under "if constexpr" or a
+// compile-time select, so the whole-plane kernels carry none of it.
+// REG: regions[i] is the exact output range of descriptor i.  The strips and vertical chunks start at the ones that cover
+// its first column / row -- the geometry (make_geo) stays the whole plane's, so the halo and the warm-up read real neighbours
+// and mirroring happens at the plane's edges only.  A lower level (no IMG) stores whole strips into its plane; the top level
+// (IMG) stores the region's samples only, row y / column x of the plane at (y - ry0, x - rx0) of the region frame (out_off,
+// out_pitch).
 template <class WP, int IMG, int NC, int U, int MODE, bool REG>
-__device__ __forceinline__ void dwt_inverse_region_body(const ojphgpu_dwt_desc* descs, uint32_t* base32, void* image, Conv cv, int row_pairs_arg,
-                                                 const WP& w, const ojphgpu_dwt_region* regions)
+__device__ __forceinline__ void dwt_inverse_body(const ojphgpu_dwt_desc* descs, uint32_t* base32, void* image, Conv cv, int row_pairs_arg,
+                                          const WP& w, const ojphgpu_dwt_region* regions)
 {
   typedef typename WP::T T;
   constexpr bool REV = WP::REV;
@@ -985,7 +747,7 @@ __device__ __forceinline__ void dwt_inverse_region_body(const ojphgpu_dwt_desc* 
   const size_t dp = (size_t)d.src_pitch * sizeof(E);
   // the top level of a region: plane row y goes to row y - ry0 of the region frame, only the region's rows are stored
   const size_t rdp = CLIP ? (size_t)rg.out_pitch * sizeof(E) : 0;
-  const Clip clip{ CLIP ? (int)rg.rx0 : 0, CLIP ? (int)rg.rx1 : 0 };
+  const int cx0 = CLIP ? (int)rg.rx0 : 0, cx1 = CLIP ? (int)rg.rx1 : 0;
   auto row_off = [&](int y) -> size_t { return (size_t)(y - (int)rg.ry0) * rdp; };
   auto row_in = [&](int y) { return y >= (int)rg.ry0 && y < (int)rg.ry1; };
   const int h = g.h, oy = g.oy;
@@ -1034,7 +796,7 @@ __device__ __forceinline__ void dwt_inverse_region_body(const ojphgpu_dwt_desc* 
       if constexpr (MODE != 2) horz_synthesis<WP>(w, x[k].l, x[k].h, g);
       if (oy != 0) { x[k].l = w.halve(x[k].l); x[k].h = w.halve(x[k].h); }
     }
-    if constexpr (CLIP) store_rows_clip<WP, IMG, NC, true>(dst, 0, g, x, cvs, clip);
+    if constexpr (CLIP) store_rows<WP, IMG, NC, true>(dst, 0, g, x, cvs, cx0, cx1);
     else store_rows<WP, IMG, NC>(dst, 0, g, x, cvs);
     return;
   }
@@ -1122,9 +884,9 @@ __device__ __forceinline__ void dwt_inverse_region_body(const ojphgpu_dwt_desc* 
         }
         if constexpr (CLIP) {
           if (tt - 2 >= i0 && tt - 2 < i1 && (!CHK || eHpp) && row_in(2 * (tt - 2) + 1 - oy))
-            store_rows_clip<WP, IMG, NC, true>(dst, row_off(2 * (tt - 2) + 1 - oy), g, xh, cvs, clip);
+            store_rows<WP, IMG, NC, true>(dst, row_off(2 * (tt - 2) + 1 - oy), g, xh, cvs, cx0, cx1);
           if (tt - 1 >= i0 && tt - 1 < i1 && (!CHK || eLp) && row_in(2 * (tt - 1) - oy))
-            store_rows_clip<WP, IMG, NC, true>(dst, row_off(2 * (tt - 1) - oy), g, xL, cvs, clip);
+            store_rows<WP, IMG, NC, true>(dst, row_off(2 * (tt - 1) - oy), g, xL, cvs, cx0, cx1);
         } else {
           if (tt - 2 >= i0 && tt - 2 < i1 && (!CHK || eHpp))
             store_rows<WP, IMG, NC>(dst, (size_t)(2 * (tt - 2) + 1 - oy) * dp, g, xh, cvs);
@@ -1140,13 +902,21 @@ __device__ __forceinline__ void dwt_inverse_region_body(const ojphgpu_dwt_desc* 
   if (g.w == 1) pipeline(std::true_type()); else pipeline(std::false_type());
 }
 
+template <class WP, int IMG, int NC, int U = 1, int MODE = 0>
+__global__ __launch_bounds__(256) void dwt_inverse_kernel(const ojphgpu_dwt_desc* __restrict__ descs,
+                                                          uint32_t* __restrict__ base32,
+                                                          void* __restrict__ image, Conv cv, int row_pairs_arg, const WP w)
+{
+  dwt_inverse_body<WP, IMG, NC, U, MODE, false>(descs, base32, image, cv, row_pairs_arg, w, nullptr);
+}
+
 template <class WP, int IMG, int NC, int U = 1>
 __global__ __launch_bounds__(256) void dwt_inverse_region_kernel(const ojphgpu_dwt_desc* __restrict__ descs,
                                                                  const ojphgpu_dwt_region* __restrict__ regions,
                                                                  uint32_t* __restrict__ base32,
                                                                  void* __restrict__ image, Conv cv, int row_pairs_arg, const WP w)
 {
-  dwt_inverse_region_body<WP, IMG, NC, U, 0, true>(descs, base32, image, cv, row_pairs_arg, w, regions);
+  dwt_inverse_body<WP, IMG, NC, U, 0, true>(descs, base32, image, cv, row_pairs_arg, w, regions);
 }
 
 // Vertical chunk of a strip per workgroup; the result is wave-uniform per launch.  Tall chunks
@@ -1224,6 +994,24 @@ int fit_rounds(const void* fn, uint32_t planes, uint32_t max_w, uint32_t max_h)
 #ifndef DWT_TRIP_DEFAULT
 #define DWT_TRIP_DEFAULT 2
 #endif
+// two row pairs per trip of the pipeline loop for the one-plane launches (see the kernels' U; OJPHGPU_DWT_TRIP=1: one)
+int dwt_trip()
+{
+  static const int trip = [] { const char* e = getenv("OJPHGPU_DWT_TRIP"); const int v = e ? atoi(e) : DWT_TRIP_DEFAULT; return v == 2 ? 2 : 1; }();
+  return trip;
+}
+
+// The one dispatch of the 5/3 and 9/7 launches, whole planes and regions: the instantiation of kernel template K for
+// `reversible` x the container (`d_image`, `container`) x `nc` x the trip goes to go(fn, policy), which sizes the grid and
+// launches it
+#define OJPH_DWT_PICK(K, REV, IMG, NC, go) do { auto fn = K<Wv<REV>, IMG, NC, 1>; \
+    if (NC == 1 && dwt_trip() == 2) fn = K<Wv<REV>, IMG, NC, (NC == 1 ? 2 : 1)>; \
+    go(fn, Wv<REV>()); } while (0)
+#define OJPH_DWT_PICK_NC(K, REV, IMG, go) do { if (nc == 3) OJPH_DWT_PICK(K, REV, IMG, 3, go); else OJPH_DWT_PICK(K, REV, IMG, 1, go); } while (0)
+#define OJPH_DWT_PICK_IMG(K, REV, go) do { if (!d_image) OJPH_DWT_PICK(K, REV, 0, 1, go); else if (container == 16) OJPH_DWT_PICK_NC(K, REV, 16, go); \
+                                           else if (container == 8) OJPH_DWT_PICK_NC(K, REV, 8, go); else OJPH_DWT_PICK_NC(K, REV, 32, go); } while (0)
+#define OJPH_DWT_DISPATCH(K, go) do { if (reversible) OJPH_DWT_PICK_IMG(K, true, go); else OJPH_DWT_PICK_IMG(K, false, go); } while (0)
+
 template <bool FWD>
 int launch(void* stream, int reversible, const ojphgpu_dwt_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
            void* d_base, void* d_image, Conv cv, int container = 32, int nc = 1)
@@ -1250,20 +1038,11 @@ int launch(void* stream, int reversible, const ojphgpu_dwt_desc* d_descs, uint32
   if (nc == 3) rp = rp3 ? rp3 : 8;
   dim3 grid = dwt_grid(n / (uint32_t)nc, max_w, max_h, rp);
   hipStream_t s = (hipStream_t)stream;
-  // two row pairs per trip of the pipeline loop for the one-plane launches (see the kernels' U; OJPHGPU_DWT_TRIP=1: one)
-  static const int trip = [] { const char* e = getenv("OJPHGPU_DWT_TRIP"); const int v = e ? atoi(e) : DWT_TRIP_DEFAULT; return v == 2 ? 2 : 1; }();
-#define OJPH_LAUNCH(K, REV, IMG, NC, TP) do { auto fn = K<Wv<REV>, IMG, NC, 1>; \
-    if (NC == 1 && trip == 2) fn = K<Wv<REV>, IMG, NC, (NC == 1 ? 2 : 1)>; \
-    if (NC == 3 && !rp3) { rp = fit_rounds((const void*)fn, n / 3u, max_w, max_h); grid = dwt_grid(n / 3u, max_w, max_h, rp); } \
-    hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, d_descs, (uint32_t*)d_base, d_image, cv, row_pairs_arg(rp), Wv<REV>()); } while (0)
-#define OJPH_LAUNCH_NC(K, REV, IMG, TP) do { if (nc == 3) OJPH_LAUNCH(K, REV, IMG, 3, TP); else OJPH_LAUNCH(K, REV, IMG, 1, TP); } while (0)
-#define OJPH_LAUNCH_IMG(K, REV, TP) do { if (!d_image) OJPH_LAUNCH(K, REV, 0, 1, TP); else if (container == 16) OJPH_LAUNCH_NC(K, REV, 16, TP); \
-                                         else if (container == 8) OJPH_LAUNCH_NC(K, REV, 8, TP); else OJPH_LAUNCH_NC(K, REV, 32, TP); } while (0)
-  if (FWD) { if (reversible) OJPH_LAUNCH_IMG(dwt_forward_kernel, true, int); else OJPH_LAUNCH_IMG(dwt_forward_kernel, false, float); }
-  else { if (reversible) OJPH_LAUNCH_IMG(dwt_inverse_kernel, true, int); else OJPH_LAUNCH_IMG(dwt_inverse_kernel, false, float); }
-#undef OJPH_LAUNCH_IMG
-#undef OJPH_LAUNCH_NC
-#undef OJPH_LAUNCH
+  auto go = [&](auto fn, auto w) {
+    if (nc == 3 && !rp3) { rp = fit_rounds((const void*)fn, n / 3u, max_w, max_h); grid = dwt_grid(n / 3u, max_w, max_h, rp); }
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, d_descs, (uint32_t*)d_base, d_image, cv, row_pairs_arg(rp), w);
+  };
+  if (FWD) OJPH_DWT_DISPATCH(dwt_forward_kernel, go); else OJPH_DWT_DISPATCH(dwt_inverse_kernel, go);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 
@@ -1377,22 +1156,15 @@ int dwt_inverse_region_launch(void* stream, int reversible, const ojphgpu_dwt_de
   if (d_image && container != 32 && container != 16 && container != 8) return OJPHGPU_E_INVALID;
   // the same chunk heights as the whole-plane launches, on the region's extents
   int rp = pick_row_pairs(n, rg.max_w, rg.max_h, true);
-  static const int trip = [] { const char* e = getenv("OJPHGPU_DWT_TRIP"); const int v = e ? atoi(e) : DWT_TRIP_DEFAULT; return v == 2 ? 2 : 1; }();
   const uint32_t planes = n / (uint32_t)nc;
   auto grid_of = [&](int r) { return dim3((rg.strips + 3) / 4, (rg.pairs_y + (uint32_t)r - 1) / (uint32_t)r, planes); };
   hipStream_t s = (hipStream_t)stream;
   const Conv cv{ 0, 0 };
-#define OJPH_LAUNCH_R(REV, IMG, NC) do { auto fn = dwt_inverse_region_kernel<Wv<REV>, IMG, NC, 1>; \
-    if (NC == 1 && trip == 2) fn = dwt_inverse_region_kernel<Wv<REV>, IMG, NC, (NC == 1 ? 2 : 1)>; \
-    if (NC == 3) rp = fit_rounds((const void*)fn, planes, rg.max_w, rg.max_h); \
-    hipLaunchKernelGGL(fn, grid_of(rp), dim3(256), 0, s, d_descs, d_regions, (uint32_t*)d_base, d_image, cv, row_pairs_arg(rp), Wv<REV>()); } while (0)
-#define OJPH_LAUNCH_R_NC(REV, IMG) do { if (nc == 3) OJPH_LAUNCH_R(REV, IMG, 3); else OJPH_LAUNCH_R(REV, IMG, 1); } while (0)
-#define OJPH_LAUNCH_R_IMG(REV) do { if (!d_image) OJPH_LAUNCH_R(REV, 0, 1); else if (container == 16) OJPH_LAUNCH_R_NC(REV, 16); \
-                                    else if (container == 8) OJPH_LAUNCH_R_NC(REV, 8); else OJPH_LAUNCH_R_NC(REV, 32); } while (0)
-  if (reversible) OJPH_LAUNCH_R_IMG(true); else OJPH_LAUNCH_R_IMG(false);
-#undef OJPH_LAUNCH_R_IMG
-#undef OJPH_LAUNCH_R_NC
-#undef OJPH_LAUNCH_R
+  auto go = [&](auto fn, auto w) {
+    if (nc == 3) rp = fit_rounds((const void*)fn, planes, rg.max_w, rg.max_h);
+    hipLaunchKernelGGL(fn, grid_of(rp), dim3(256), 0, s, d_descs, d_regions, (uint32_t*)d_base, d_image, cv, row_pairs_arg(rp), w);
+  };
+  OJPH_DWT_DISPATCH(dwt_inverse_region_kernel, go);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 

@@ -1879,8 +1879,9 @@ constexpr int RWAVES = 2;
 constexpr uint32_t SIG_ENTRIES = 1040;        // (stripes + 1) * (groups + 2) 16-bit words, w * h <= 4096
 constexpr uint32_t PREV_ENTRIES = 264;
 
+template <typename S>        // S: the sample word, uint32_t or uint64_t
 struct RefineLds {
-  uint32_t smp[4096];
+  S smp[4096];
   uint16_t sigma[SIG_ENTRIES];
   uint16_t prev_row[PREV_ENTRIES];
   uint8_t  bytes[2048];
@@ -1937,22 +1938,36 @@ __device__ __forceinline__ void sigma_from_records(const uint32_t* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(64 * RWAVES) void ht_dec_refine_kernel(
-    const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint8_t* __restrict__ data,
-    const uint32_t* __restrict__ quads, uint32_t* __restrict__ coef, const uint8_t* __restrict__ block_status)
+// What a refined sign-magnitude word becomes in the plane.  32-bit samples are de-quantised like step 2's; 64-bit samples
+// (reversible only) take the transfer gen_rev_tx_from_cb64 (ojph_codestream_gen.cpp:140-153)
+struct RefineOut32 {
+  typedef uint32_t S;
+  bool rev; uint32_t shift; float delta;
+  __device__ __forceinline__ explicit RefineOut32(const ojphgpu_cb_desc& d) : rev((d.reversible & 1u) != 0), shift(31 - d.K_max), delta(d.delta) {}
+  __device__ __forceinline__ S operator()(S v) const { return dequantise(v, rev, shift, delta); }
+};
+struct RefineOut64 {
+  typedef uint64_t S;
+  uint32_t shift;
+  __device__ __forceinline__ explicit RefineOut64(const ojphgpu_cb_desc& d) : shift(63u - d.K_max) {}
+  __device__ __forceinline__ S operator()(S v) const {
+    const long long mag = (long long)((v & 0x7FFFFFFFFFFFFFFFull) >> shift);
+    return (S)((v >> 63) ? -mag : mag);
+  }
+};
+
+// The two passes of one block by one wavefront, for either sample word (ojph_block_decoder32.cpp:1364-1609 and
+// ojph_block_decoder64.cpp:1360-1657: the same scans, the sign in the word's top bit and the magnitude below it)
+template <class OUT>
+__device__ __forceinline__ void refine_block(const ojphgpu_cb_desc& d, RefineLds<typename OUT::S>& L, const uint8_t* __restrict__ data,
+                                             const uint32_t* __restrict__ quads, uint32_t* __restrict__ coef, int lane)
 {
-  __shared__ RefineLds s_wave[RWAVES];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t bi = blockIdx.x * RWAVES + wave;
-  if (bi >= n) return;
-  const ojphgpu_cb_desc d = blocks[bi];
-  if (!needs_refinement(d) || d.w == 0 || d.h == 0 || d.len1 == 0 || block_status[bi] != 0 || (d.reversible & 4u)) return;   // (64-bit: ht_dec64_refine_kernel)
-  RefineLds& L = s_wave[wave];
+  typedef typename OUT::S S;
+  constexpr uint32_t TOP = 8u * sizeof(S) - 1u;              // the sign bit: 31 / 63
   const uint32_t W = d.w, H = d.h, pitch = d.pitch;
-  uint32_t* plane = coef + d.coef_off;
-  const bool rev = (d.reversible & 1u) != 0, causal = (d.reversible & 2u) != 0;
-  const uint32_t p = 30u - d.missing_msbs;
+  S* plane = reinterpret_cast<S*>(coef + d.coef_off);
+  const bool causal = (d.reversible & 2u) != 0;
+  const uint32_t p = TOP - 1u - d.missing_msbs;
   const int ngroups = (int)((W + 3) >> 2), mstr = ngroups + 2;
 
   for (uint32_t i = lane; i < SIG_ENTRIES / 2; i += 64) reinterpret_cast<uint32_t*>(L.sigma)[i] = 0;
@@ -1960,7 +1975,7 @@ __global__ __launch_bounds__(64 * RWAVES) void ht_dec_refine_kernel(
   wave_sync();
   for (uint32_t y = 0; y < H; ++y)
     for (uint32_t x = lane; x < W; x += 64) L.smp[y * W + x] = plane[(size_t)y * pitch + x];
-  sigma_from_records(quads + d.scratch_cap, (W + 1u) >> 1, (H + 1u) >> 1, L.sigma, (uint32_t)mstr, lane);
+  sigma_from_records(quads + d.scratch_cap, (W + 1u) >> 1, (H + 1u) >> 1, L.sigma, (uint32_t)mstr, lane);   // (block_decoder64.cpp:1363-1393)
   const uint8_t* seg = data + d.data_off + d.len1;
   const int len2 = (int)d.len2;                              // < 2047 (ojph_precinct.cpp:509)
   for (int i = lane; i < len2 && i < 2048; i += 64) L.bytes[i] = seg[i];
@@ -2004,7 +2019,7 @@ __global__ __launch_bounds__(64 * RWAVES) void ht_dec_refine_kernel(
           for (int c = 0; c < 4; ++c)
             for (int r = 0; r < 4; ++r)
               if (new_sig & (1u << (4 * c + r)))
-                L.smp[(uint32_t)(y + r) * W + (uint32_t)(x + c)] = (spp.bit() << 31) | (3u << (p - 2));
+                L.smp[(uint32_t)(y + r) * W + (uint32_t)(x + c)] = ((S)spp.bit() << TOP) | ((S)3 << (p - 2));
         }
         new_sig |= cs;
         L.prev_row[g] = (uint16_t)new_sig;
@@ -2016,23 +2031,50 @@ __global__ __launch_bounds__(64 * RWAVES) void ht_dec_refine_kernel(
     // ---- magnitude refinement (:1561-1609) ----
     if (d.num_passes > 2) {
       BwdBits mrp; mrp.init(L.bytes, len2 < 2048 ? len2 : 2048);
-      const uint32_t half = 1u << (p - 2);
+      const S half = (S)1 << (p - 2);
       for (int y = 0; y < (int)H; y += 4)
         for (int x = 0; x < 4 * ngroups; ++x) {
           const uint32_t nib = ((uint32_t)L.sigma[(y >> 2) * mstr + (x >> 2)] >> (4 * (x & 3))) & 0xFu;
           for (int r = 0; r < 4; ++r)
             if (nib & (1u << r)) {
               const uint32_t sym = mrp.bit();           // (a flagged sample outside the block takes its bit too: :1583-1606)
-              if (x < (int)W && y + r < (int)H) L.smp[(uint32_t)(y + r) * W + (uint32_t)x] ^= ((1u - sym) << (p - 1)) | half;
+              if (x < (int)W && y + r < (int)H) L.smp[(uint32_t)(y + r) * W + (uint32_t)x] ^= ((S)(1u - sym) << (p - 1)) | half;
             }
         }
     }
   }
   wave_sync();
-  const uint32_t shift = 31 - d.K_max;
-  const float delta = d.delta;
+  const OUT out(d);
   for (uint32_t y = 0; y < H; ++y)
-    for (uint32_t x = lane; x < W; x += 64) plane[(size_t)y * pitch + x] = dequantise(L.smp[y * W + x], rev, shift, delta);
+    for (uint32_t x = lane; x < W; x += 64) plane[(size_t)y * pitch + x] = out(L.smp[y * W + x]);
+}
+
+__global__ __launch_bounds__(64 * RWAVES) void ht_dec_refine_kernel(
+    const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint8_t* __restrict__ data,
+    const uint32_t* __restrict__ quads, uint32_t* __restrict__ coef, const uint8_t* __restrict__ block_status)
+{
+  __shared__ RefineLds<uint32_t> s_wave[RWAVES];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t bi = blockIdx.x * RWAVES + wave;
+  if (bi >= n) return;
+  const ojphgpu_cb_desc d = blocks[bi];
+  if (!needs_refinement(d) || d.w == 0 || d.h == 0 || d.len1 == 0 || block_status[bi] != 0 || (d.reversible & 4u)) return;   // (64-bit: ht_dec64_refine_kernel)
+  refine_block<RefineOut32>(d, s_wave[wave], data, quads, coef, lane);
+}
+
+// the blocks of 64-bit samples (the 64-bit sample path below): one wavefront per workgroup, its LDS is twice the size
+__global__ __launch_bounds__(64) void ht_dec64_refine_kernel(
+    const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint8_t* __restrict__ data,
+    const uint32_t* __restrict__ quads, uint32_t* __restrict__ coef, const uint8_t* __restrict__ block_status)
+{
+  __shared__ RefineLds<uint64_t> L;
+  const int lane = threadIdx.x & 63;
+  const uint32_t bi = blockIdx.x;
+  if (bi >= n) return;
+  const ojphgpu_cb_desc d = blocks[bi];
+  if (!(d.reversible & 4u) || !needs_refinement(d) || d.w == 0 || d.h == 0 || d.len1 == 0 || block_status[bi] != 0) return;
+  refine_block<RefineOut64>(d, L, data, quads, coef, lane);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -2241,108 +2283,7 @@ __global__ __launch_bounds__(64 * W64_WAVES) void ht_dec64_step2_kernel(
   if (bad) { zero_block(); if (lane == 0) block_status[bi] = 1; }
 }
 
-// SigProp + MagRef of a block of 64-bit samples (block_decoder64.cpp:1360-1657): ht_dec_refine_kernel with 64-bit words
-struct RefineLds64 {
-  uint64_t smp[4096];
-  uint16_t sigma[SIG_ENTRIES];
-  uint16_t prev_row[PREV_ENTRIES];
-  uint8_t  bytes[2048];
-};
-
-__global__ __launch_bounds__(64) void ht_dec64_refine_kernel(
-    const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint8_t* __restrict__ data,
-    const uint32_t* __restrict__ quads, uint32_t* __restrict__ coef, const uint8_t* __restrict__ block_status)
-{
-  __shared__ RefineLds64 L;
-  const int lane = threadIdx.x & 63;
-  const uint32_t bi = blockIdx.x;
-  if (bi >= n) return;
-  const ojphgpu_cb_desc d = blocks[bi];
-  if (!(d.reversible & 4u) || !needs_refinement(d) || d.w == 0 || d.h == 0 || d.len1 == 0 || block_status[bi] != 0) return;
-  const uint32_t W = d.w, H = d.h, pitch = d.pitch;
-  unsigned long long* plane = reinterpret_cast<unsigned long long*>(coef + d.coef_off);
-  const bool causal = (d.reversible & 2u) != 0;
-  const uint32_t p = 62u - d.missing_msbs;
-  const int ngroups = (int)((W + 3) >> 2), mstr = ngroups + 2;
-  for (uint32_t i = lane; i < SIG_ENTRIES / 2; i += 64) reinterpret_cast<uint32_t*>(L.sigma)[i] = 0;
-  for (uint32_t i = lane; i < PREV_ENTRIES / 2; i += 64) reinterpret_cast<uint32_t*>(L.prev_row)[i] = 0;
-  wave_sync();
-  for (uint32_t y = 0; y < H; ++y)
-    for (uint32_t x = lane; x < W; x += 64) L.smp[y * W + x] = plane[(size_t)y * pitch + x];
-  sigma_from_records(quads + d.scratch_cap, (W + 1u) >> 1, (H + 1u) >> 1, L.sigma, (uint32_t)mstr, lane);   // (block_decoder64.cpp:1363-1393)
-  const uint8_t* seg = data + d.data_off + d.len1;
-  const int len2 = (int)d.len2;
-  for (int i = lane; i < len2 && i < 2048; i += 64) L.bytes[i] = seg[i];
-  wave_sync();
-  if (lane == 0) {
-    FwdBits spp; spp.init(L.bytes, len2 < 2048 ? len2 : 2048);
-    for (int y = 0; y < (int)H; y += 4) {
-      uint32_t pattern = 0xFFFFu;
-      if ((int)H - y < 4) { pattern = 0x7777u; if ((int)H - y < 3) { pattern = 0x3333u; if ((int)H - y < 2) pattern = 0x1111u; } }
-      uint32_t prev = 0;
-      const uint16_t* cur_sig = L.sigma + (y >> 2) * mstr;
-      const uint16_t* nxt_sig = cur_sig + mstr;
-      for (int x = 0, g = 0; x < (int)W; x += 4, ++g) {
-        int sft = x + 4 - (int)W; if (sft < 0) sft = 0;
-        pattern >>= sft * 4;
-        const uint32_t ps = L.prev_row[g] | ((uint32_t)L.prev_row[g + 1] << 16);
-        const uint32_t ns = nxt_sig[g] | ((uint32_t)nxt_sig[g + 1] << 16);
-        uint32_t u = (ps & 0x88888888u) >> 3;
-        if (!causal) u |= (ns & 0x11111111u) << 3;
-        const uint32_t cs = cur_sig[g] | ((uint32_t)cur_sig[g + 1] << 16);
-        uint32_t mbr = cs | ((cs & 0x77777777u) << 1) | ((cs & 0xEEEEEEEEu) >> 1) | u;
-        uint32_t t = mbr;
-        mbr |= (t << 4) | (t >> 4) | (prev >> 12);
-        mbr &= pattern; mbr &= ~cs;
-        uint32_t new_sig = mbr;
-        if (new_sig) {
-          const uint32_t inv_sig = ~cs & pattern;
-          for (int c = 0; c < 4; ++c)
-            for (int r = 0; r < 4; ++r) {
-              const uint32_t b = 1u << (4 * c + r);
-              if (!(new_sig & b)) continue;
-              new_sig &= ~b;
-              if (spp.bit()) {
-                const uint32_t grow = r == 0 ? 0x33u : (r == 1 ? 0x76u : (r == 2 ? 0xECu : 0xC8u));
-                new_sig |= (grow << (4 * c)) & inv_sig;
-              }
-            }
-          new_sig &= 0xFFFFu;
-          for (int c = 0; c < 4; ++c)
-            for (int r = 0; r < 4; ++r)
-              if (new_sig & (1u << (4 * c + r)))
-                L.smp[(uint32_t)(y + r) * W + (uint32_t)(x + c)] = ((uint64_t)spp.bit() << 63) | (3ull << (p - 2));
-        }
-        new_sig |= cs;
-        L.prev_row[g] = (uint16_t)new_sig;
-        t = new_sig;
-        new_sig |= ((t & 0x7777u) << 1) | ((t & 0xEEEEu) >> 1);
-        prev = (new_sig | u) & 0xF000u;
-      }
-    }
-    if (d.num_passes > 2) {
-      BwdBits mrp; mrp.init(L.bytes, len2 < 2048 ? len2 : 2048);
-      const uint64_t half = 1ull << (p - 2);
-      for (int y = 0; y < (int)H; y += 4)
-        for (int x = 0; x < 4 * ngroups; ++x) {
-          const uint32_t nib = ((uint32_t)L.sigma[(y >> 2) * mstr + (x >> 2)] >> (4 * (x & 3))) & 0xFu;
-          for (int r = 0; r < 4; ++r)
-            if (nib & (1u << r)) {
-              const uint32_t sym = mrp.bit();           // (also for a flagged sample outside the block)
-              if (x < (int)W && y + r < (int)H) L.smp[(uint32_t)(y + r) * W + (uint32_t)x] ^= ((uint64_t)(1u - sym) << (p - 1)) | half;
-            }
-        }
-    }
-  }
-  wave_sync();
-  const uint32_t shift = 63u - d.K_max;
-  for (uint32_t y = 0; y < H; ++y)
-    for (uint32_t x = lane; x < W; x += 64) {
-      const uint64_t v = L.smp[y * W + x];
-      const long long mag = (long long)((v & 0x7FFFFFFFFFFFFFFFull) >> shift);
-      plane[(size_t)y * pitch + x] = (unsigned long long)((v >> 63) ? -mag : mag);
-    }
-}
+// (SigProp + MagRef of a block of 64-bit samples: ht_dec64_refine_kernel, beside the 32-bit one above)
 
 }  // namespace
 

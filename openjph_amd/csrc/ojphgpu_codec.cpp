@@ -260,6 +260,43 @@ extern "C" int ojphgpu_encoder_run_device(ojphgpu_encoder* e, const int32_t* d_i
 extern "C" int ojphgpu_encoder_run_device16(ojphgpu_encoder* e, const uint16_t* d_image) { return ojphgpu_encoder_run_container(e, d_image, 16); }
 extern "C" int ojphgpu_encoder_run_device8(ojphgpu_encoder* e, const uint8_t* d_image) { return ojphgpu_encoder_run_container(e, d_image, 8); }
 
+// The block coder's schedule over an encoder's `nblocks` blocks (all frames of the run): the counters are cleared; the top
+// resolution's share [0, n_top) is coded on the side stream from the point where the main stream stands at fork_top() -- its
+// blocks need the first DWT level only -- the rest on the main stream, which then waits for the side stream (join).  The
+// products go to out / res / cnt; T (optional) takes an SP_HT_ENC span per launch.
+namespace {
+struct BlockCoderRun {
+  ojphgpu_encoder* e; uint8_t* out; ojphgpu_cb_result* res; uint32_t* cnt; uint32_t nblocks; Spans* T;
+  bool forked = false;
+  int launch(hipStream_t st, uint32_t first, uint32_t n, int widths) {
+    const int sh = T ? T->begin(SP_HT_ENC, st) : -1;
+    int rc = ojphgpu::ht_encode_launch(st, (const ojphgpu_cb_desc*)e->cb_descs.p + first, n, e->arena.p, (uint8_t*)e->scratch.p, out,
+                                       e->out_cap, res + first, cnt, cnt + 1, widths, (const uint32_t*)e->regions.p, e->nreg);
+    if (rc) return rc;
+    if (T) T->end(sh, st);
+    return OJPHGPU_OK;
+  }
+  int clear() { HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->stream)); return OJPHGPU_OK; }
+  int fork_top() {                                          // the top resolution's blocks are ready to be coded
+    forked = true;
+    HIPCHK(hipEventRecord(e->ev_fork, e->stream));
+    HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+    int rc = launch(e->side, 0, e->n_top, e->widths_top);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(e->ev_join, e->side));
+    return OJPHGPU_OK;
+  }
+  int rest_and_join() {                                     // (forks here if nobody has)
+    int rc = e->n_top && !forked ? fork_top() : OJPHGPU_OK;
+    if (rc) return rc;
+    rc = launch(e->stream, e->n_top, nblocks - e->n_top, e->widths_rest);
+    if (rc) return rc;
+    if (e->n_top) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+    return OJPHGPU_OK;
+  }
+};
+}  // namespace
+
 // container: 32 = int32 samples, 16 / 8 = 16- / 8-bit samples (two's complement for signed components, else unsigned)
 int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int container)
 {
@@ -269,12 +306,12 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
   if (container != 32) for (const CompGeo& g : P.comps) if (g.bit_depth > (uint32_t)container) return OJPHGPU_E_INVALID;
   hipStream_t s = e->stream;
   Spans& T = e->timer;
-  uint8_t* const d_out = (uint8_t*)(e->o_out ? e->o_out : e->out.p);          // a pipeline slot's buffers, or the object's own
-  ojphgpu_cb_result* const res = (ojphgpu_cb_result*)(e->o_results ? e->o_results : e->results.p);
-  uint32_t* const cnt = (uint32_t*)(e->o_counters ? e->o_counters : e->counters.p);
-  HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, s));
+  BlockCoderRun coder{ e, (uint8_t*)(e->o_out ? e->o_out : e->out.p),         // a pipeline slot's buffers, or the object's own
+                       (ojphgpu_cb_result*)(e->o_results ? e->o_results : e->results.p),
+                       (uint32_t*)(e->o_counters ? e->o_counters : e->counters.p), (uint32_t)e->block_ids.size() * e->nframes, &T };
+  int rc = coder.clear();
+  if (rc) return rc;
   T.start(s);
-  int rc = OJPHGPU_OK;
   if (e->need_convert) {
     const int sp = T.begin(SP_CONVERT, s);
     rc = ojphgpu_convert_forward_ex(s, &P.p, (const ojphgpu_convert_desc*)e->conv_descs.p, e->tiles.count * e->nframes,
@@ -282,21 +319,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     T.end(sp, s);
   }
   if (rc) return rc;
-  const ojphgpu_cb_desc* cbd = (const ojphgpu_cb_desc*)e->cb_descs.p;
   const bool budget = e->max_bytes != 0;                    // the blocks are coded by the search, in ojphgpu_encoder_finish*
-  bool forked = false;
-  auto fork_top = [&]() -> int {                            // the top resolution's blocks are ready to be coded
-    forked = true;
-    HIPCHK(hipEventRecord(e->ev_fork, s));
-    HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-    const int sh = T.begin(SP_HT_ENC, e->side);
-    int r2 = ojphgpu::ht_encode_launch(e->side, cbd, e->n_top, e->arena.p, (uint8_t*)e->scratch.p, d_out,
-                                       e->out_cap, res, cnt, cnt + 1, e->widths_top, (const uint32_t*)e->regions.p, e->nreg);
-    if (r2) return r2;
-    T.end(sh, e->side);
-    HIPCHK(hipEventRecord(e->ev_join, e->side));
-    return OJPHGPU_OK;
-  };
   for (size_t i = 0; i < e->batches.size(); ++i) {
     const LevelBatch& b = e->batches[i];
     const int sp = T.begin(SP_DWT, s);
@@ -313,7 +336,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     if (rc) return rc;
     T.end(sp, s);
     const bool top_done = b.depth == 0 && (i + 1 == e->batches.size() || e->batches[i + 1].depth != 0);
-    if (!budget && e->n_top && top_done && (rc = fork_top()) != 0) return rc;
+    if (!budget && e->n_top && top_done && (rc = coder.fork_top()) != 0) return rc;
   }
   if (budget) {
     EncoderRate& R = *e->rate;
@@ -327,14 +350,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     e->ran = true; e->fetched = false;
     return OJPHGPU_OK;
   }
-  if (e->n_top && !forked && (rc = fork_top()) != 0) return rc;
-  const uint32_t nb_all = (uint32_t)e->block_ids.size() * e->nframes;
-  const int sh = T.begin(SP_HT_ENC, s);
-  rc = ojphgpu::ht_encode_launch(s, cbd + e->n_top, nb_all - e->n_top, e->arena.p, (uint8_t*)e->scratch.p,
-                                 d_out, e->out_cap, res + e->n_top, cnt, cnt + 1, e->widths_rest, (const uint32_t*)e->regions.p, e->nreg);
-  if (rc) return rc;
-  T.end(sh, s);
-  if (e->n_top) HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));     // join
+  if ((rc = coder.rest_and_join()) != 0) return rc;
   T.finish(s);
   e->ran = true; e->fetched = false;
   return OJPHGPU_OK;
@@ -392,15 +408,7 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
       }
     e->fetched = true;
   }
-  cb.assign(P.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
-  const size_t nb = e->block_ids.size();
-  for (size_t i = 0; i < nb; ++i) {
-    const ojphgpu_cb_result& r = e->h_results[(size_t)frame * nb + i];
-    ojphgpu_coded_block& c = cb[e->block_ids[i]];
-    c.offset = r.offset; c.len1 = r.length; c.len2 = 0;
-    c.missing_msbs = r.length ? P.bands[P.blocks[e->block_ids[i]].band].K_max - 1 : 0;      // ojph_codeblock.cpp:148
-    c.num_passes = r.length ? 1 : 0;
-  }
+  ojphgpu_coded_blocks(P, e->block_ids, e->h_results.data() + (size_t)frame * e->block_ids.size(), cb);
   return OJPHGPU_OK;
 }
 
@@ -465,19 +473,12 @@ extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* 
     uint64_t nbytes = 0;
     int rc = ojphgpu_encoder_coded_bytes(e, &nbytes);
     if (rc) return rc;
-    const size_t nb = e->block_ids.size();
     const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
     if (rbytes) HIPCHK(hipMemcpyAsync(e->h_results.data(), e->results.p, rbytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->fetched = false;                                   // h_results holds device offsets again
-    std::vector<ojphgpu_coded_block> cb(P.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
-    for (size_t i = 0; i < nb; ++i) {
-      const ojphgpu_cb_result& r = e->h_results[i];
-      ojphgpu_coded_block& c = cb[e->block_ids[i]];
-      c.offset = r.offset; c.len1 = r.length; c.len2 = 0;
-      c.missing_msbs = r.length ? P.bands[P.blocks[e->block_ids[i]].band].K_max - 1 : 0;
-      c.num_passes = r.length ? 1 : 0;
-    }
+    std::vector<ojphgpu_coded_block> cb;
+    ojphgpu_coded_blocks(P, e->block_ids, e->h_results.data(), cb);
     T2Layout L;
     rc = t2_layout_tiles(P, cb.data(), e->tiles.first, (size_t)e->tiles.first + e->tiles.count, L, tile_part_len);
     if (rc) return rc;
@@ -562,8 +563,8 @@ extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes
   });
 }
 
-// one trial of the search: the blocks coded at grid index j, in the schedule of a plain run (the top resolution's share on
-// the side stream); the block lengths come to the host and the Tier-2 layout gives the codestream's length
+// one trial of the search: the blocks coded at grid index j, in the schedule of a plain run (BlockCoderRun, fork and rest back
+// to back); the block lengths come to the host and the Tier-2 layout gives the codestream's length
 static int64_t encoder_rate_trial(void* user, uint32_t j)
 {
   ojphgpu_encoder* e = (ojphgpu_encoder*)user;
@@ -580,18 +581,8 @@ static int64_t encoder_rate_trial(void* user, uint32_t j)
   if (!hip(hipMemcpyAsync(R.quant.p, &R.table.quant[(size_t)j * nc], (size_t)nc * sizeof(BandQuant), hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
   int rc = requant_launch(s, cbd, nb, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p);
   if (rc) return rc;
-  if (!hip(hipMemsetAsync(cnt, 0, e->counters_bytes, s))) return OJPHGPU_E_HIP;
-  if (e->n_top) {
-    if (!hip(hipEventRecord(e->ev_fork, s)) || !hip(hipStreamWaitEvent(e->side, e->ev_fork, 0))) return OJPHGPU_E_HIP;
-    rc = ojphgpu::ht_encode_launch(e->side, cbd, e->n_top, e->arena.p, (uint8_t*)e->scratch.p, (uint8_t*)e->out.p, e->out_cap, res, cnt, cnt + 1,
-                                   e->widths_top, (const uint32_t*)e->regions.p, e->nreg);
-    if (rc) return rc;
-    if (!hip(hipEventRecord(e->ev_join, e->side))) return OJPHGPU_E_HIP;
-  }
-  rc = ojphgpu::ht_encode_launch(s, cbd + e->n_top, nb - e->n_top, e->arena.p, (uint8_t*)e->scratch.p, (uint8_t*)e->out.p, e->out_cap,
-                                 res + e->n_top, cnt, cnt + 1, e->widths_rest, (const uint32_t*)e->regions.p, e->nreg);
-  if (rc) return rc;
-  if (e->n_top && !hip(hipStreamWaitEvent(s, e->ev_join, 0))) return OJPHGPU_E_HIP;
+  BlockCoderRun coder{ e, (uint8_t*)e->out.p, res, cnt, nb, nullptr };
+  if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) return rc;
   const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
   uint32_t status = 0;
   const auto w0 = std::chrono::steady_clock::now();         // (a copy into pageable memory waits for the launches before it)
@@ -601,14 +592,8 @@ static int64_t encoder_rate_trial(void* user, uint32_t j)
   R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   e->fetched = false;
   if (status) return OJPHGPU_E_OVERFLOW;                    // (cannot happen: the buffers hold the finest step's bound)
-  std::vector<ojphgpu_coded_block> cb(Q.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
-  for (size_t i = 0; i < nb; ++i) {
-    const ojphgpu_cb_result& r = e->h_results[i];
-    ojphgpu_coded_block& c = cb[e->block_ids[i]];
-    c.offset = r.offset; c.len1 = r.length;
-    c.missing_msbs = r.length ? Q.bands[Q.blocks[e->block_ids[i]].band].K_max - 1 : 0;
-    c.num_passes = r.length ? 1 : 0;
-  }
+  std::vector<ojphgpu_coded_block> cb;
+  ojphgpu_coded_blocks(Q, e->block_ids, e->h_results.data(), cb);
   T2Layout L;
   rc = t2_layout_codestream(Q, cb.data(), L);
   if (rc) return rc;

@@ -511,6 +511,21 @@ struct ojphgpu_encoder {
 // the device part of an encode: d_image holds the frame in `container`-bit elements (32 / 16)
 int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int container);
 
+// The plan-order coded-block table of one frame from the block coder's results: res[i] = the frame's block block_ids[i];
+// P = the plan the blocks were quantised with (its bands give K_max); blocks outside block_ids stay empty
+inline void ojphgpu_coded_blocks(const Plan& P, const std::vector<uint32_t>& block_ids, const ojphgpu_cb_result* res,
+                                 std::vector<ojphgpu_coded_block>& cb)
+{
+  cb.assign(P.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
+  for (size_t i = 0; i < block_ids.size(); ++i) {
+    const ojphgpu_cb_result& r = res[i];
+    ojphgpu_coded_block& c = cb[block_ids[i]];
+    c.offset = r.offset; c.len1 = r.length; c.len2 = 0;
+    c.missing_msbs = r.length ? P.bands[P.blocks[block_ids[i]].band].K_max - 1 : 0;      // ojph_codeblock.cpp:148
+    c.num_passes = r.length ? 1 : 0;
+  }
+}
+
 // A block the reference decodes from bytes the codestream does not hold (Plan::padded: its tile-part ended early and
 // bb_read_chunk, ojph_bitbuffer_read.h:134-150, handed over zeros for the rest): `got` bytes at `src` of the codestream,
 // then zeros up to `total`, placed at `dst` -- an offset into the frame's part of the device data buffer, BEHIND the byte

@@ -152,14 +152,8 @@ static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
   const uint32_t* cnt = (const uint32_t*)(s.h_res.p + nb * sizeof(ojphgpu_cb_result));
   if (cnt[1]) return fail(OJPHGPU_E_OVERFLOW);
   int rc = no_throw([&]() -> int {
-    std::vector<ojphgpu_coded_block> cb(P.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
-    for (size_t i = 0; i < nb; ++i) {
-      const ojphgpu_cb_result& r = res[i];
-      ojphgpu_coded_block& c = cb[e->block_ids[i]];
-      c.offset = r.offset; c.len1 = r.length; c.len2 = 0;
-      c.missing_msbs = r.length ? P.bands[P.blocks[e->block_ids[i]].band].K_max - 1 : 0;      // ojph_codeblock.cpp:148
-      c.num_passes = r.length ? 1 : 0;
-    }
+    std::vector<ojphgpu_coded_block> cb;
+    ojphgpu_coded_blocks(P, e->block_ids, res, cb);
     T2Layout L;
     int r2 = t2_layout_codestream(P, cb.data(), L);
     if (r2) return r2;
