@@ -648,6 +648,16 @@ typedef struct ojphgpu_rate_info {
  * max_bytes, a negative value of fn as it is. */
 int  ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes,
                          ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
+/* The same search started from a guess, for the frames of a sequence (hint = the previous frame's j*): the first trial is
+ * `hint`, the second the neighbour its result points to (hint + 1 when it fit, hint - 1 when not) and, when that one points
+ * the same way, the third the index beyond it -- each only where the index exists and the certificate is not complete --
+ * so hint == j* takes the two trials the certificate consists of and hint == j* +- 1 at most three.  Where these have
+ * not produced the certificate the search above goes on inside the interval they left, its model rescaled by the last
+ * of them.  The hinted trials count among the six model-led ones: no index asked twice, passes <= 16.  out->first_guess
+ * = hint.  hint = -1: no hint, exactly ojphgpu_rate_search; any other value outside 0 .. OJPHGPU_RATE_GRID - 1:
+ * OJPHGPU_E_INVALID.  hist may be NULL (the hinted trials, then halving). */
+int  ojphgpu_rate_search_hint(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
+                              ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
 /* the model alone: predicted bytes of every grid index, out[OJPHGPU_RATE_GRID] (what tools/rate_bench.py reports) */
 int  ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out);
 
@@ -710,6 +720,24 @@ int  ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* pipe, int pixel_bits, int big
  * the plane order of the planar layout): _acquire hands out ceil(samples * bits / 8) bytes rounded up to whole groups
  * of 32 samples.  Unsigned components whose depth fits `bits`, 16- or 32-bit containers.  bits = 0 switches back. */
 int  ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* pipe, int bits);
+
+/* Every frame of this pipe is coded to a byte budget (section 5b): each collected codestream is, byte for byte, the plain
+ * encode of its frame at qstep(j*), with the certificate size(j*) <= budget < size(j* + 1) measured for that frame.
+ * Switched on by a call with max_bytes > 0 before the first _acquire (the refusals are ojphgpu_encoder_set_budget's, and
+ * the output buffers are re-sized for the finest step of the grid: one per slot and one spare); from then on the call may
+ * be repeated between frames, and the value in force at _submit is that frame's budget (a bit-reservoir controller moves
+ * it every frame).  OJPHGPU_E_INVALID: switching on after the first _acquire, and 0 once the mode is on; 0 on a plain
+ * pipe before the first _acquire changes nothing.  The search of a frame starts from the j* of the last certified frame
+ * (ojphgpu_rate_search_hint) and alternates its trials between two output buffers, so a frame whose answer is its
+ * predecessor's costs the two trials the certificate consists of and nothing is coded twice.  A frame whose budget not
+ * even index 0 meets: its _collect returns OJPHGPU_E_BUDGET, its slot is free again, the frames around it are not
+ * affected.  Combines with _set_pixels / _set_packed.  A pipe that never had a budget issues what it issued without
+ * this call.  A refusal leaves the pipe as it was; should switching on fail later (OJPHGPU_E_NOMEM while the buffers
+ * change size), the pipe is neither plain nor budgeted any more and every call but _destroy returns OJPHGPU_E_INVALID. */
+int  ojphgpu_enc_pipe_set_budget(ojphgpu_enc_pipe* pipe, uint64_t max_bytes);
+/* what the search of the frame collected last found (after OJPHGPU_E_BUDGET: passes and first_guess); OJPHGPU_E_INVALID
+ * before the first _collect of a budgeted pipe and after a frame that failed otherwise */
+int  ojphgpu_enc_pipe_rate_info(ojphgpu_enc_pipe* pipe, ojphgpu_rate_info* info);
 
 /* the first codestream of the sequence fixes the frame geometry (it is only parsed, not decoded); every
  * submitted codestream must describe the same frame format and code-block grid (quantisation may differ) */

@@ -301,6 +301,8 @@ SIGNATURES = {
     "ojphgpu_multi_decode_container": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
     "ojphgpu_enc_pipe_set_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ojphgpu_enc_pipe_set_packed": (C.c_int, [C.c_void_p, C.c_int]),
+    "ojphgpu_enc_pipe_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_enc_pipe_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_dec_pipe_set_packed": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_unpack_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int]),
     "ojphgpu_pack_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int]),
@@ -310,6 +312,7 @@ SIGNATURES = {
     "ojphgpu_band_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ojphgpu_rate_grid_qstep": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
     "ojphgpu_rate_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),
+    "ojphgpu_rate_search_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_rate_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "ojphgpu_encoder_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
     "ojphgpu_encoder_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),

@@ -236,7 +236,7 @@ bool rate_plan_ok(const Plan& P);                            // irreversible thr
 // p.qstep = qstep, the QCD / QCCs derived again and the bands' K_max / delta with them: the plan of a plain encode at that step
 bool rate_apply_step(Plan& Q, float qstep);
 int  rate_table_build(const Plan& P, RateTable& T);
-int  rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
+int  rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);   // hint: -1 = none
 int  requant_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t n, const uint32_t* d_class, const BandQuant* d_quant);
 
 // Nothing may leave the C ABI as a C++ exception (a codestream from anywhere can ask for tables the

@@ -118,9 +118,12 @@ struct Model {
 
 }  // namespace
 
-int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out)
+// hint: a grid index to try first (the previous frame's answer), then its neighbour on the side the result points to and, if
+// that points the same way, the index beyond it, before the model proposes anything; -1 = none.  The hinted trials shrink
+// the interval like any other and count among the six model-led ones, so the guarantees of the plain search hold.
+int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out)
 {
-  if (!fn || !out) return OJPHGPU_E_INVALID;
+  if (!fn || !out || hint < -1 || hint >= (int)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
   memset(out, 0, sizeof(*out));
   const int N = OJPHGPU_RATE_GRID;
   std::vector<int64_t> size((size_t)N, -1);
@@ -131,6 +134,31 @@ int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, oj
   int lo = -1, hi = N;
   double scale = 1.0;
   uint32_t passes = 0;
+  int err = 0;
+  auto trial = [&](int j) -> bool {                          // false: fn failed, err holds what to return
+    if (passes == 0) out->first_guess = (uint32_t)j;
+    const int64_t s = fn(user, (uint32_t)j);
+    ++passes;
+    out->passes = passes;
+    if (s < 0) { err = s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s; return false; }
+    size[(size_t)j] = s;
+    if (model) { const double p = model->bytes((uint32_t)j); scale = p > 0 ? (double)s / p : 1.0; }
+    if ((uint64_t)s <= max_bytes) lo = j; else hi = j;
+    return true;
+  };
+  if (hint >= 0) {
+    if (!trial(hint)) return err;
+    // the neighbour the result points to and, when that one points the same way, the next index on: an answer one step
+    // from the hint is certified by three trials whatever the model makes of the frame.  Each only where the index
+    // exists and the certificate is still open.
+    const int dir = lo == hint ? 1 : -1;
+    for (int k = 1; k <= 2 && hi - lo > 1; ++k) {
+      const int nb = hint + k * dir;
+      if (nb <= lo || nb >= hi) break;
+      if (!trial(nb)) return err;
+      if ((dir > 0) != (lo == nb)) break;                    // it turned round: the certificate, or a table that is not monotone
+    }
+  }
   while (hi - lo > 1) {
     int j = (lo + hi) / 2;
     if (model && passes < 6) {
@@ -139,14 +167,7 @@ int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, oj
       while (b - a > 1) { const int m = (a + b) / 2; if (scale * model->bytes((uint32_t)m) <= (double)max_bytes) a = m; else b = m; }
       j = std::min(std::max(a, lo + 1), hi - 1);
     }
-    if (passes == 0) out->first_guess = (uint32_t)j;
-    const int64_t s = fn(user, (uint32_t)j);
-    ++passes;
-    out->passes = passes;
-    if (s < 0) return s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s;
-    size[(size_t)j] = s;
-    if (model) { const double p = model->bytes((uint32_t)j); scale = p > 0 ? (double)s / p : 1.0; }
-    if ((uint64_t)s <= max_bytes) lo = j; else hi = j;
+    if (!trial(j)) return err;
   }
   if (lo < 0) return OJPHGPU_E_BUDGET;
   out->grid_index = (uint32_t)lo; out->qstep = rate_grid_qstep((uint32_t)lo);
@@ -166,16 +187,22 @@ extern "C" int ojphgpu_rate_grid_qstep(uint32_t j, float* qstep)
   return OJPHGPU_OK;
 }
 
-extern "C" int ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
-                                   ojphgpu_rate_info* out)
+extern "C" int ojphgpu_rate_search_hint(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint, ojphgpu_size_fn fn,
+                                        void* user, ojphgpu_rate_info* out)
 {
   if (!plan || !fn || !out) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     RateTable T;
     const int rc = rate_table_build(plan->plan, T);
     if (rc) return rc;
-    return rate_search(T, hist, max_bytes, fn, user, out);
+    return rate_search(T, hist, max_bytes, hint, fn, user, out);
   });
+}
+
+extern "C" int ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
+                                   ojphgpu_rate_info* out)
+{
+  return ojphgpu_rate_search_hint(plan, hist, max_bytes, -1, fn, user, out);
 }
 
 extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out)

@@ -459,6 +459,7 @@ extern "C" int ojphgpu_encoder_finish_tiles(ojphgpu_encoder* e, uint8_t* h_out, 
 
 namespace ojphgpu {
 int assemble_launch(void* stream, const T2Job* d_jobs, uint32_t njobs, const uint8_t* d_blob, const uint8_t* d_data, uint8_t* d_out);
+int publish_words_launch(void* stream, uint32_t* d_dst, const uint32_t* src, uint32_t n);
 }
 
 // The tile-parts of the range assembled in HBM (kernels_assemble.hip) instead of on the host: only the block
@@ -563,42 +564,58 @@ extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes
   });
 }
 
-// one trial of the search: the blocks coded at grid index j, in the schedule of a plain run (BlockCoderRun, fork and rest back
-// to back); the block lengths come to the host and the Tier-2 layout gives the codestream's length
-static int64_t encoder_rate_trial(void* user, uint32_t j)
+// one trial of the search: the blocks coded at grid index j into the output set `o`, in the schedule of a plain run
+// (BlockCoderRun, fork and rest back to back); the block lengths come to the host and the Tier-2 layout, from Q -- a copy of
+// the encoder's plan, left at the step of j -- gives the codestream's length.  The lengths travel the way the set says: into
+// mapped pinned memory the coder writes itself (a frame pipeline), or by a copy into the encoder's pageable table.
+int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j)
 {
-  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
   EncoderRate& R = *e->rate;
-  Plan& Q = R.plan->plan;
   hipStream_t s = e->stream;
   auto hip = [](hipError_t x) { return x == hipSuccess; };
-  R.at = -1;
   if (!rate_apply_step(Q, rate_grid_qstep(j))) return OJPHGPU_E_INVALID;
   const uint32_t nc = R.table.nclasses, nb = (uint32_t)e->block_ids.size();
   ojphgpu_cb_desc* cbd = (ojphgpu_cb_desc*)e->cb_descs.p;
-  uint32_t* cnt = (uint32_t*)e->counters.p;
-  ojphgpu_cb_result* res = (ojphgpu_cb_result*)e->results.p;
   if (!hip(hipMemcpyAsync(R.quant.p, &R.table.quant[(size_t)j * nc], (size_t)nc * sizeof(BandQuant), hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
   int rc = requant_launch(s, cbd, nb, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p);
   if (rc) return rc;
-  BlockCoderRun coder{ e, (uint8_t*)e->out.p, res, cnt, nb, nullptr };
+  BlockCoderRun coder{ e, (uint8_t*)o.out, o.d_results, o.d_counters, nb, nullptr };
   if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) return rc;
-  const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
   uint32_t status = 0;
-  const auto w0 = std::chrono::steady_clock::now();         // (a copy into pageable memory waits for the launches before it)
-  if (rbytes && !hip(hipMemcpyAsync(e->h_results.data(), res, rbytes, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
-  if (!hip(hipMemcpyAsync(&status, cnt + 1, 4, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
-  if (!hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
+  const ojphgpu_cb_result* lengths = o.h_results;
+  const auto w0 = std::chrono::steady_clock::now();
+  if (o.h_results) {                                        // the coder wrote them there; the cursors follow, then the event
+    if ((rc = publish_words_launch(s, o.d_publish, o.d_counters, 2)) != 0) return rc;
+    if (!hip(hipEventRecord(o.done, s)) || !hip(hipEventSynchronize(o.done))) return OJPHGPU_E_HIP;
+    status = o.h_publish[1];
+  } else {                                                  // (a copy into pageable memory waits for the launches before it)
+    const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
+    if (rbytes && !hip(hipMemcpyAsync(e->h_results.data(), o.d_results, rbytes, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
+    if (!hip(hipMemcpyAsync(&status, o.d_counters + 1, 4, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
+    if (!hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
+    lengths = e->h_results.data();
+  }
   R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   e->fetched = false;
   if (status) return OJPHGPU_E_OVERFLOW;                    // (cannot happen: the buffers hold the finest step's bound)
   std::vector<ojphgpu_coded_block> cb;
-  ojphgpu_coded_blocks(Q, e->block_ids, e->h_results.data(), cb);
+  ojphgpu_coded_blocks(Q, e->block_ids, lengths, cb);
   T2Layout L;
   rc = t2_layout_codestream(Q, cb.data(), L);
   if (rc) return rc;
-  R.at = (int)j;
   return (int64_t)L.total;
+}
+
+// ... of a single encoder: into its own output set, with its own plan copy
+static int64_t encoder_rate_trial(void* user, uint32_t j)
+{
+  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
+  EncoderRate& R = *e->rate;
+  R.at = -1;
+  const RateTrialOut own{ e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nullptr, nullptr, nullptr, nullptr };
+  const int64_t size = ojphgpu_encoder_rate_trial(e, R.plan->plan, own, j);
+  if (size >= 0) R.at = (int)j;
+  return size;
 }
 
 // the search of the last run, once: afterwards the device holds the coded blocks of j* and R.plan stands at its step
@@ -612,7 +629,7 @@ static int encoder_rate_search(ojphgpu_encoder* e)
     HIPCHK(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    int rc = rate_search(R.table, R.h_hist.data(), e->max_bytes, encoder_rate_trial, e, &R.info);
+    int rc = rate_search(R.table, R.h_hist.data(), e->max_bytes, -1, encoder_rate_trial, e, &R.info);
     R.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
     if (rc) return rc;
     if (R.at != (int)R.info.grid_index) {                   // the last trial was j* + 1: j* is coded once more, and counted

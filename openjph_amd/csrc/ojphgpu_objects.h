@@ -475,6 +475,9 @@ struct ojphgpu_encoder {
   const ojphgpu_plan* handle = nullptr;
   const Plan* P = nullptr;
   int device = 0; hipStream_t stream = nullptr;
+  // out / counters are null in the encoder of a frame pipeline with a byte budget: the pipe takes them over as its spare
+  // output set (ojphgpu_enc_pipe_set_budget).  Such an encoder runs only through o_out / o_results / o_counters and
+  // ojphgpu_encoder_rate_trial; _finish, _coded_bytes and the encoder's own search, which read these two, are not for it.
   DeviceBuf arena, image, dwt_descs, img_descs, cb_descs, conv_descs, scratch, out, results, counters;
   bool need_convert = false;                       // some component is not converted inside its top DWT level
   std::vector<LevelBatch> batches;
@@ -508,6 +511,15 @@ struct ojphgpu_encoder {
   uint64_t max_bytes = 0;                          // != 0: every frame is coded to this budget
   EncoderRate* rate = nullptr;
 };
+// Where one trial of the budget search writes, and how its block lengths reach the host.  h_results != null: d_results is the
+// device address of that mapped pinned memory, the coder's records land in it, the two status words of d_counters are
+// published to d_publish (h_publish on the host) and `done` is recorded behind them and waited for.  Null: the records are
+// copied into the encoder's own pageable table.
+struct RateTrialOut {
+  void* out; ojphgpu_cb_result* d_results; uint32_t* d_counters;
+  const ojphgpu_cb_result* h_results; uint32_t* d_publish; const uint32_t* h_publish; hipEvent_t done;
+};
+int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j);   // size(j), or an error (< 0)
 // the device part of an encode: d_image holds the frame in `container`-bit elements (32 / 16)
 int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int container);
 

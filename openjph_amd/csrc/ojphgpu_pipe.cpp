@@ -15,6 +15,11 @@
 // pass through a host memcpy: the encoder's codestream is assembled in HBM (kernels_assemble.hip) from the
 // layout the host Tier-2 computes out of the block LENGTHS, and arrives in pinned memory ready to be
 // written to a file; the decoder uploads the codestream as it is and addresses the blocks inside it.
+//
+// An encoder pipe with a byte budget (ojphgpu_enc_pipe_set_budget) searches the quantisation step of every frame: the
+// compute stream then carries, per frame, transform + statistics and the trials of the search, issued by one ordered
+// worker thread -- the pipe has one encoder and one arena, so frame n+1's transform must not be enqueued before frame n's
+// last trial -- while uploads, Tier-2 of the chosen step and copy-outs of the neighbouring frames go on as above.
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -110,14 +115,29 @@ double now_ms()
 // =============================================================================================
 // encoder pipe
 // =============================================================================================
+// What the block coder writes for one frame: the compacted bytes, the cursors, and the per-block records + the two
+// published status words in pinned memory.  A slot owns one; a pipe with a byte budget keeps one more (the spare), and the
+// trials of a frame's search alternate between the slot's and the spare so that the best fitting trial is never overwritten.
+struct EncOut {
+  Pinned h_res;
+  DeviceBuf out, counters;
+  void release() { h_res.release(); out.release(); counters.release(); }
+};
+
 struct EncSlot {
   SlotState state = FREE;
-  Pinned h_in, h_res, h_lay, h_cs;
-  DeviceBuf image, out, counters, pixels;           // pixels: the frame as it was handed over, when it comes pixel-interleaved
+  Pinned h_in, h_lay, h_cs;
+  EncOut o;
+  DeviceBuf image, pixels;                          // pixels: the frame as it was handed over, when it comes pixel-interleaved
   Grow cs;
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   int rc = 0; size_t cs_len = 0;
   double t_submit = 0, t_done = 0, t_t2 = 0;
+  // a pipe with a byte budget: the frame's budget, what its search found, and the plan at the step it chose (the
+  // finisher lays the codestream out from it while the worker re-quantises for the next frame)
+  uint64_t budget = 0;
+  ojphgpu_plan* rplan = nullptr;
+  ojphgpu_rate_info info{}; bool have_info = false;
 };
 
 struct ojphgpu_enc_pipe {
@@ -137,19 +157,31 @@ struct ojphgpu_enc_pipe {
   std::deque<uint32_t> work; bool stop = false;
   std::vector<std::thread> finishers;
   double sum_t2 = 0, sum_latency = 0; uint64_t n_done = 0;
+  // byte budget (ojphgpu_enc_pipe_set_budget): on from before the first _acquire, or never
+  bool budget_on = false;
+  bool dead = false;                                // switching the budget on failed half way: nothing more runs on this pipe
+  uint64_t max_bytes = 0;                           // the budget the next _submit gives its frame
+  EncOut spare;
+  Pinned h_hist;                                    // the band statistics of the frame being searched (the worker's)
+  hipEvent_t ev_trial = nullptr;
+  int hint = -1;                                    // j* of the last frame that was certified
+  std::deque<uint32_t> rate_work; bool stop_rate = false;
+  std::condition_variable cv_rate;
+  std::thread rate_worker;
+  ojphgpu_rate_info last_info{}; bool have_last_info = false;   // of the frame collected last
 };
 
 static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
 {
-  const Plan& P = *p->P;
+  const Plan& P = p->budget_on ? s.rplan->plan : *p->P;      // (a byte budget: the plan at the step the frame's search chose)
   ojphgpu_encoder* e = p->enc;
   auto fail = [&](int rc) { s.rc = rc; };
   if (hipSetDevice(p->device) != hipSuccess) return fail(OJPHGPU_E_HIP);
   if (hipEventSynchronize(s.ev_kern) != hipSuccess) return fail(OJPHGPU_E_HIP);
   const double t0 = now_ms();
   const size_t nb = e->block_ids.size();
-  const ojphgpu_cb_result* res = (const ojphgpu_cb_result*)s.h_res.p;
-  const uint32_t* cnt = (const uint32_t*)(s.h_res.p + nb * sizeof(ojphgpu_cb_result));
+  const ojphgpu_cb_result* res = (const ojphgpu_cb_result*)s.o.h_res.p;
+  const uint32_t* cnt = (const uint32_t*)(s.o.h_res.p + nb * sizeof(ojphgpu_cb_result));
   if (cnt[1]) return fail(OJPHGPU_E_OVERFLOW);
   int rc = no_throw([&]() -> int {
     std::vector<ojphgpu_coded_block> cb;
@@ -168,7 +200,7 @@ static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
     memcpy(s.h_lay.p, L.jobs.data(), jbytes);
     memcpy(s.h_lay.p + boff, L.blob.data(), L.blob.size());
     r2 = assemble_launch(p->s_d2h, (const T2Job*)s.h_lay.d, (uint32_t)L.jobs.size(), s.h_lay.d + boff,
-                         (const uint8_t*)s.out.p, (uint8_t*)s.cs.b.p);
+                         (const uint8_t*)s.o.out.p, (uint8_t*)s.cs.b.p);
     if (r2) return r2;
     r2 = download(p->mode, p->s_d2h, s.h_cs, s.cs.b.p, (size_t)L.total);
     if (r2) return r2;
@@ -182,6 +214,87 @@ static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
     // re-reserved (hipHostFree / hipFree in reserve()) by the next _acquire while they are in flight
     hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp); hipStreamSynchronize(p->s_d2h);
     fail(rc);
+  }
+}
+
+// ---- byte budget: the ordered worker.  Per frame, on the compute stream: unpack, transform and statistics; the histograms
+// come back; the search, started from the last certified frame's answer, codes its trials into the slot's output set and
+// the spare in turn.  Afterwards the slot holds the set with j*, its plan copy stands at qstep(j*), and the finishers take
+// over as for any frame.
+static int enc_unpack(ojphgpu_enc_pipe* p, EncSlot& s);
+
+struct EncTrialCtx {
+  ojphgpu_enc_pipe* p; EncSlot* s;
+  EncOut* best; EncOut* next;                        // best: holds the finest trial that fit so far (null: none); next: written next
+  int at;                                            // grid index s->rplan stands at
+};
+
+static int64_t enc_pipe_trial(void* user, uint32_t j)
+{
+  EncTrialCtx& c = *(EncTrialCtx*)user;
+  ojphgpu_encoder* e = c.p->enc;
+  const size_t nb = e->block_ids.size();
+  EncOut& o = *c.next;
+  uint32_t* d_pub = (uint32_t*)(o.h_res.d + nb * sizeof(ojphgpu_cb_result));
+  const RateTrialOut to{ o.out.p, (ojphgpu_cb_result*)o.h_res.d, (uint32_t*)o.counters.p, (const ojphgpu_cb_result*)o.h_res.p,
+                         d_pub, (const uint32_t*)(o.h_res.p + nb * sizeof(ojphgpu_cb_result)), c.p->ev_trial };
+  c.at = -1;
+  const int64_t size = ojphgpu_encoder_rate_trial(e, c.s->rplan->plan, to, j);
+  if (size < 0) return size;
+  c.at = (int)j;
+  if ((uint64_t)size <= c.s->budget) {               // the finest that fits so far (the search never goes back below one): keep it
+    EncOut* other = c.best ? c.best : (c.next == &c.s->o ? &c.p->spare : &c.s->o);
+    c.best = c.next; c.next = other;
+  }
+  return size;
+}
+
+static int enc_rate_frame(ojphgpu_enc_pipe* p, EncSlot& s)
+{
+  ojphgpu_encoder* e = p->enc;
+  EncoderRate& R = *e->rate;
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
+  int rc = enc_unpack(p, s);
+  if (rc) return rc;
+  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
+  if ((rc = ojphgpu_encoder_run_container(e, s.image.p, p->container)) != 0) return rc;   // transform + statistics (e->max_bytes != 0)
+  if ((rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
+  HIPCHK(hipEventRecord(p->ev_trial, p->s_comp));
+  HIPCHK(hipEventSynchronize(p->ev_trial));
+  EncTrialCtx c{ p, &s, nullptr, &s.o, -1 };
+  rc = rate_search(R.table, (const uint32_t*)p->h_hist.p, s.budget, p->hint, enc_pipe_trial, &c, &s.info);
+  s.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
+  if (rc) return rc;
+  p->hint = (int)s.info.grid_index;
+  if (c.best != &s.o) std::swap(s.o, p->spare);      // (pointers only) the slot keeps the set with j*, the other is the spare
+  if (c.at != (int)s.info.grid_index && !rate_apply_step(s.rplan->plan, s.info.qstep)) return OJPHGPU_E_INVALID;
+  HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
+  return OJPHGPU_OK;
+}
+
+static void enc_rate_worker(ojphgpu_enc_pipe* p)
+{
+  for (;;) {
+    uint32_t si;
+    {
+      std::unique_lock<std::mutex> lk(p->mu);
+      p->cv_rate.wait(lk, [&] { return p->stop_rate || !p->rate_work.empty(); });
+      if (p->rate_work.empty()) return;
+      si = p->rate_work.front(); p->rate_work.pop_front();
+    }
+    EncSlot& s = p->slots[si];
+    const int rc = no_throw([&] { return enc_rate_frame(p, s); });
+    if (rc) {                                        // the frame ends here (OJPHGPU_E_BUDGET among the reasons); see enc_finish_frame
+      hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp);
+      std::lock_guard<std::mutex> lk(p->mu);
+      s.rc = rc; s.t_done = now_ms(); s.state = DONE;
+      p->sum_latency += s.t_done - s.t_submit; p->n_done++;
+      p->cv_done.notify_all();
+      continue;
+    }
+    { std::lock_guard<std::mutex> lk(p->mu); p->work.push_back(si); }
+    p->cv_work.notify_one();
   }
 }
 
@@ -211,16 +324,24 @@ extern "C" void ojphgpu_enc_pipe_destroy(ojphgpu_enc_pipe* p)
 {
   if (!p) return;
   (void)hipSetDevice(p->device);
+  if (p->rate_worker.joinable()) {                   // it hands its frames to the finishers: it ends first
+    { std::lock_guard<std::mutex> lk(p->mu); p->stop_rate = true; }
+    p->cv_rate.notify_all();
+    p->rate_worker.join();
+  }
   { std::lock_guard<std::mutex> lk(p->mu); p->stop = true; }
   p->cv_work.notify_all();
   for (std::thread& t : p->finishers) t.join();
   for (hipStream_t s : { p->s_h2d, p->s_comp, p->s_d2h }) if (s) (void)hipStreamSynchronize(s);
   if (p->enc) ojphgpu_encoder_destroy(p->enc);
   for (EncSlot& s : p->slots) {
-    s.h_in.release(); s.h_res.release(); s.h_lay.release(); s.h_cs.release();
-    for (DeviceBuf* b : { &s.image, &s.out, &s.counters, &s.cs.b, &s.pixels }) b->release();
+    s.h_in.release(); s.o.release(); s.h_lay.release(); s.h_cs.release();
+    for (DeviceBuf* b : { &s.image, &s.cs.b, &s.pixels }) b->release();
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
+    delete s.rplan;
   }
+  p->spare.release(); p->h_hist.release();
+  if (p->ev_trial) (void)hipEventDestroy(p->ev_trial);
   for (hipStream_t s : { p->s_h2d, p->s_comp, p->s_d2h }) if (s) (void)hipStreamDestroy(s);
   delete p;
 }
@@ -252,8 +373,8 @@ extern "C" int ojphgpu_enc_pipe_create(const ojphgpu_plan* plan, int device, uin
     const size_t cs_guess = std::min<size_t>((size_t)e->out_cap, (size_t)P.frame_elems + (1u << 20));
     p->slots.resize(depth);
     for (EncSlot& s : p->slots) {
-      if (s.h_in.reserve(p->frame_bytes + 64) || s.h_res.reserve(p->res_bytes + 64) || s.h_cs.reserve(cs_guess)) return OJPHGPU_E_NOMEM;
-      if (s.image.alloc(p->frame_bytes + 64) || s.out.alloc((size_t)e->out_cap + 64) || s.counters.alloc(e->counters_bytes) ||
+      if (s.h_in.reserve(p->frame_bytes + 64) || s.o.h_res.reserve(p->res_bytes + 64) || s.h_cs.reserve(cs_guess)) return OJPHGPU_E_NOMEM;
+      if (s.image.alloc(p->frame_bytes + 64) || s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes) ||
           s.cs.reserve(cs_guess)) return OJPHGPU_E_NOMEM;
       const size_t lay_guess = nb * sizeof(T2Job) + nb * 8 + (1u << 16);
       if (s.h_lay.reserve(lay_guess)) return OJPHGPU_E_NOMEM;
@@ -269,7 +390,7 @@ extern "C" int ojphgpu_enc_pipe_create(const ojphgpu_plan* plan, int device, uin
 
 extern "C" int ojphgpu_enc_pipe_acquire(ojphgpu_enc_pipe* p, void** h_frame, size_t* bytes)
 {
-  if (!p || !h_frame) return OJPHGPU_E_INVALID;
+  if (!p || !h_frame || p->dead) return OJPHGPU_E_INVALID;
   EncSlot& s = p->slots[p->n_acq % p->depth];
   {
     std::lock_guard<std::mutex> lk(p->mu);
@@ -294,7 +415,7 @@ static int pixels_fit(const Plan& P, int pixel_bits, int container_bits)
 
 extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian)
 {
-  if (!p || p->n_acq != 0 || p->slots[0].state != FREE || p->packed_bits) return OJPHGPU_E_INVALID;
+  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->packed_bits) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (pixel_bits == 0) { p->pixel_bits = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
     const Plan& P = *p->P;
@@ -322,7 +443,7 @@ static int packed_fit(const Plan& P, int bits, int container_bits)
 
 extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits)
 {
-  if (!p || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits) return OJPHGPU_E_INVALID;
+  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (bits == 0) { p->packed_bits = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
     const Plan& P = *p->P;
@@ -339,18 +460,9 @@ extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits)
   });
 }
 
-extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
+// the frame as it was handed over -> planes in the slot's image, on the compute stream (nothing for planar frames)
+static int enc_unpack(ojphgpu_enc_pipe* p, EncSlot& s)
 {
-  if (!p) return OJPHGPU_E_INVALID;
-  const uint32_t si = (uint32_t)(p->n_acq % p->depth);
-  EncSlot& s = p->slots[si];
-  { std::lock_guard<std::mutex> lk(p->mu); if (s.state != ACQUIRED) return OJPHGPU_E_INVALID; }
-  HIPCHK(hipSetDevice(p->device));
-  ojphgpu_encoder* e = p->enc;
-  s.rc = 0; s.cs_len = 0; s.t_submit = now_ms();
-  { const int r0 = upload(p->mode, p->s_h2d, (p->pixel_bits || p->packed_bits) ? s.pixels.p : s.image.p, s.h_in, 0, p->in_bytes); if (r0) return r0; }
-  HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
-  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
   if (p->pixel_bits) {                               // the file's / capture buffer's bytes -> planes, on the device
     const Plan& P = *p->P;
     const int r0 = ojphgpu_unpack_pixels(p->s_comp, s.pixels.p, s.image.p, P.p.width, P.p.height, P.p.num_comps, p->pixel_bits,
@@ -361,13 +473,38 @@ extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
     const int r0 = ojphgpu_unpack_bits(p->s_comp, s.pixels.p, s.image.p, p->P->frame_elems, p->packed_bits, p->container);
     if (r0) return r0;
   }
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
+{
+  if (!p || p->dead) return OJPHGPU_E_INVALID;
+  const uint32_t si = (uint32_t)(p->n_acq % p->depth);
+  EncSlot& s = p->slots[si];
+  { std::lock_guard<std::mutex> lk(p->mu); if (s.state != ACQUIRED) return OJPHGPU_E_INVALID; }
+  HIPCHK(hipSetDevice(p->device));
+  ojphgpu_encoder* e = p->enc;
+  s.rc = 0; s.cs_len = 0; s.t_submit = now_ms();
+  { const int r0 = upload(p->mode, p->s_h2d, (p->pixel_bits || p->packed_bits) ? s.pixels.p : s.image.p, s.h_in, 0, p->in_bytes); if (r0) return r0; }
+  HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
+  if (p->budget_on) {                                // everything on the compute stream is the rate worker's, frame by frame
+    std::lock_guard<std::mutex> lk(p->mu);
+    s.budget = p->max_bytes; s.have_info = false;
+    s.state = SUBMITTED;
+    p->rate_work.push_back(si);
+    p->n_acq++; p->n_sub++;
+    p->cv_rate.notify_one();
+    return OJPHGPU_OK;
+  }
+  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
+  { const int r0 = enc_unpack(p, s); if (r0) return r0; }
   // the block coder writes its per-block {offset, length} records straight into the slot's pinned memory
   // (8 bytes per block, posted PCIe writes): all the host needs to code the packet headers
   const size_t nb = e->block_ids.size();
-  e->o_out = s.out.p; e->o_results = s.h_res.d; e->o_counters = s.counters.p;
+  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
   int rc = ojphgpu_encoder_run_container(e, s.image.p, p->container);
   if (rc) return rc;
-  rc = publish_words_launch(p->s_comp, (uint32_t*)(s.h_res.d + nb * sizeof(ojphgpu_cb_result)), (const uint32_t*)s.counters.p, 2);
+  rc = publish_words_launch(p->s_comp, (uint32_t*)(s.o.h_res.d + nb * sizeof(ojphgpu_cb_result)), (const uint32_t*)s.o.counters.p, 2);
   if (rc) return rc;
   HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
   {
@@ -392,9 +529,55 @@ extern "C" int ojphgpu_enc_pipe_collect(ojphgpu_enc_pipe* p, const uint8_t** h_c
   EncSlot& s = p->slots[p->n_col % p->depth];
   p->cv_done.wait(lk, [&] { return s.state == DONE; });
   p->n_col++;
+  if (p->budget_on) { p->last_info = s.info; p->have_last_info = s.have_info; }
   if (s.rc) { s.state = FREE; return s.rc; }
   s.state = HELD;
   *h_codestream = s.h_cs.p; *len = s.cs_len;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_enc_pipe_set_budget(ojphgpu_enc_pipe* p, uint64_t max_bytes)
+{
+  if (!p || p->dead) return OJPHGPU_E_INVALID;
+  if (p->n_acq != 0 || p->slots[0].state != FREE) {  // frames have been handed out: the mode stays, the budget may move
+    if (!p->budget_on || max_bytes == 0) return OJPHGPU_E_INVALID;
+    p->max_bytes = max_bytes;
+    return OJPHGPU_OK;
+  }
+  if (max_bytes == 0) return p->budget_on ? OJPHGPU_E_INVALID : OJPHGPU_OK;   // (once on, the buffers and the worker are there)
+  if (p->budget_on) { p->max_bytes = max_bytes; return OJPHGPU_OK; }
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(p->device));
+    ojphgpu_encoder* e = p->enc;
+    int rc = ojphgpu_encoder_set_budget(e, max_bytes);   // the refusals, the statistics, scratch and output bound of the finest step
+    if (rc) return rc;                                   // (refused: the encoder and the pipe are as they were)
+    // From here the encoder runs in budget mode and the buffers change hands: a failure below (memory, the thread) leaves
+    // neither a plain pipe nor a budgeted one, so the pipe refuses everything but _destroy afterwards.
+    struct Guard { ojphgpu_enc_pipe* p; ~Guard() { if (p) p->dead = true; } } guard{ p };
+    // the output sets at that bound: one per slot, and the encoder's own becomes the spare
+    for (EncSlot& s : p->slots) {
+      s.o.out.release(); s.o.counters.release();
+      if (s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
+      if (!s.rplan) s.rplan = new ojphgpu_plan{ *p->P };
+    }
+    p->spare.out = e->out; p->spare.counters = e->counters;
+    e->out = DeviceBuf(); e->counters = DeviceBuf();
+    if (p->spare.h_res.reserve(p->res_bytes + 64)) return OJPHGPU_E_NOMEM;
+    if (p->h_hist.reserve(e->rate->h_hist.size() * 4 + 64)) return OJPHGPU_E_NOMEM;
+    if (!p->ev_trial) HIPCHK(hipEventCreateWithFlags(&p->ev_trial, hipEventDisableTiming | hipEventReleaseToSystem));
+    p->rate_worker = std::thread(enc_rate_worker, p);
+    p->budget_on = true; p->max_bytes = max_bytes; p->hint = -1;
+    guard.p = nullptr;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_enc_pipe_rate_info(ojphgpu_enc_pipe* p, ojphgpu_rate_info* info)
+{
+  if (!p || !info) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->have_last_info) return OJPHGPU_E_INVALID;
+  *info = p->last_info;
   return OJPHGPU_OK;
 }
 

@@ -47,10 +47,10 @@ def unpack_bits(packed, bits, n):
 
 
 class EncoderPipe:
-    def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, **kw):
+    def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
-        the device"""
+        the device.  max_bytes: every frame is coded to that byte budget (set_budget)"""
         from .codec import _torch
         _torch()
         self.plan = plan if plan is not None else Plan(params if params is not None else make_params(**kw))
@@ -68,7 +68,23 @@ class EncoderPipe:
         if packed:                                        # planes of bit-packed samples (10 / 12 / 14 bits): acquire() -> uint8 view
             check(self._lib.ojphgpu_enc_pipe_set_packed(self._h, int(packed)), "enc_pipe_set_packed")
             self.packed = int(packed)
+        if max_bytes:
+            self.set_budget(max_bytes)
         self.in_flight = 0
+
+    def set_budget(self, max_bytes):
+        """Every frame is coded at the finest step of the rate grid whose codestream is at most max_bytes long, the search
+        started from the previous frame's answer (ojphgpu_enc_pipe_set_budget).  Switched on before the first acquire();
+        afterwards the budget may change between frames -- the value at submit() is the frame's -- but not go to 0.  A frame
+        no step fits raises OjphError (capi.E_BUDGET) from its collect()."""
+        check(self._lib.ojphgpu_enc_pipe_set_budget(self._h, int(max_bytes)), "enc_pipe_set_budget")
+
+    def rate_info(self):
+        """of the frame collected last: dict(grid_index, qstep, bytes, bytes_finer, passes, first_guess), as
+        codec.Encoder.rate_info"""
+        info = capi.RateInfo()
+        check(self._lib.ojphgpu_enc_pipe_rate_info(self._h, C.byref(info)), "enc_pipe_rate_info")
+        return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
 
     def close(self):
         if self._h:
@@ -113,9 +129,19 @@ class EncoderPipe:
         check(self._lib.ojphgpu_enc_pipe_stats(self._h, out), "enc_pipe_stats")
         return dict(frames=int(out[0]), host_tier2_ms=out[1], latency_ms=out[2], tier2_threads=int(out[3]))
 
-    def encode_sequence(self, frames):
-        """frames: iterable of [C,H,W] arrays -> generator of codestreams, in order"""
-        for f in frames:
+    def encode_sequence(self, frames, budgets=None):
+        """frames: iterable of [C,H,W] arrays -> generator of codestreams, in order.  budgets (a pipe with a byte budget):
+        one int for every frame, or an iterable parallel to frames; a frame no step fits raises from here as from collect()"""
+        if budgets is not None and not hasattr(budgets, "__iter__"):
+            self.set_budget(budgets)
+            budgets = None
+        budgets = iter(budgets) if budgets is not None else None
+        for n, f in enumerate(frames):
+            if budgets is not None:                       # (before the first acquire() this is what switches the mode on)
+                b = next(budgets, None)
+                if b is None:
+                    raise ValueError("encode_sequence: budgets ended after %d values, frames go on" % n)
+                self.set_budget(b)
             buf = self.acquire()
             while buf is None:
                 yield self.collect()

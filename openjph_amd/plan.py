@@ -333,16 +333,23 @@ def rate_grid_qstep(j):
     return float(q.value)
 
 
-def rate_search(plan: Plan, hist, max_bytes, size_fn):
-    """ojphgpu_rate_search: hist uint32 [plan.num_bands, 80] (None: no model), size_fn(j) -> bytes of the codestream at grid
-    index j.  -> dict(grid_index, qstep, bytes, bytes_finer, passes, first_guess); capi.OjphError with .code == capi.E_BUDGET
-    (and .info = the dict) when not even index 0 fits."""
+def rate_search(plan: Plan, hist, max_bytes, size_fn, hint=None):
+    """ojphgpu_rate_search, or with hint = a grid index ojphgpu_rate_search_hint (the first trial is `hint`, the second the
+    neighbour its result points to; in a sequence: the previous frame's answer): hist uint32 [plan.num_bands, 80] (None: no
+    model), size_fn(j) -> bytes of the codestream at grid index j.  -> dict(grid_index, qstep, bytes, bytes_finer, passes,
+    first_guess); capi.OjphError with .code == capi.E_BUDGET (and .info = the dict) when not even index 0 fits."""
     info = capi.RateInfo()
     cb = capi.SIZE_FN(lambda user, j: int(size_fn(int(j))))
     h = None if hist is None else np.ascontiguousarray(hist, dtype=np.uint32)
     if h is not None and h.size != plan.num_bands * capi.STATS_BINS:
         raise ValueError("hist must hold 80 bins for every band of the plan")
-    rc = capi.lib().ojphgpu_rate_search(plan.handle, None if h is None else h.ctypes.data, int(max_bytes), cb, None, C.byref(info))
+    hp = None if h is None else h.ctypes.data
+    if hint is None:
+        rc = capi.lib().ojphgpu_rate_search(plan.handle, hp, int(max_bytes), cb, None, C.byref(info))
+    elif not -2 ** 31 <= int(hint) < 2 ** 31:              # (no grid index, and c_int32 would wrap it into one)
+        rc = capi.E_INVALID
+    else:
+        rc = capi.lib().ojphgpu_rate_search_hint(plan.handle, hp, int(max_bytes), int(hint), cb, None, C.byref(info))
     out = {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
     if rc != capi.OK:
         err = capi.OjphError(rc, "rate_search")
