@@ -309,6 +309,16 @@ public:
   // after such a flush(): the step it chose (its index in the grid and its value), the codestream's length and the number
   // of block-coder runs the search made; false when there was none
   bool get_byte_budget_result(ui32& grid_index, float& qstep, ui64& bytes, ui32& passes);
+  // GPU-side addition: flush() codes the frame to a quality target (include/ojphgpu.h section 5c: the coarsest base step of
+  // that grid found whose decoded frame differs from the frame by a squared error, summed over all components, of at most
+  // max_sse; 0 is a target).  Call it before write_headers; clear_max_sse switches it off.  Where set_byte_budget applies,
+  // components of at most 16 bits, and not together with a byte budget: anything else is reported by write_headers, a
+  // target beyond the finest step by flush().
+  void set_max_sse(ui64 max_sse);
+  void clear_max_sse();
+  // after such a flush(): the step it chose, the squared error there and one step coarser (0 at index 0), the largest
+  // absolute difference, the codestream's length and the number of trials the search made; false when there was none
+  bool get_quality_info(ui32& grid_index, float& qstep, ui64& sse, ui64& sse_coarser, ui32& pae, ui64& bytes, ui32& passes);
 
 private:
   codestream(const codestream&) = delete;

@@ -38,6 +38,7 @@ extern "C" {
 #define OJPHGPU_E_UNCOLLECTED  -8   /* ojphgpu_decoder_run_device*: the run BEFORE this one asked to be decoded again (see
                                      * ojphgpu_decoder_failed_blocks) and was never collected -- its frame was incomplete */
 #define OJPHGPU_E_BUDGET       -9   /* a byte budget that not even the coarsest step of the rate grid meets (section 5b) */
+#define OJPHGPU_E_QUALITY      -10  /* a quality target that not even the finest step of the rate grid meets (section 5c) */
 
 /* ------------------------------------------------------------------------------------------ *
  * 1. Codestream parameters: what ojph::param_siz / param_cod / param_qcd setters carry
@@ -507,6 +508,37 @@ typedef struct ojphgpu_stats_desc { uint64_t plane_off; uint32_t pitch, w, h, sl
 int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
                        const void* d_coef, uint32_t* d_hist);
 
+/* The two passes of a trial of the quality search (section 5c builds on them; kernels_quality.hip).
+ *
+ * ojphgpu_band_requantise: sub-band planes of fp32 coefficients in d_src_arena -> the same planes in d_dst_arena (same
+ * offsets) as the decoder holds them after the block decoder, had the planes been coded with these band parameters.  Per
+ * sample, in this order: the irreversible quantise transfer of the block encoder (f = coefficient * delta_inv rounded to
+ * nearest, truncated to an integer; a product beyond +-2^31 or a NaN gives the zero word); with p = 31 - K_max and m =
+ * magnitude >> p the word 0 when m == 0, else sign | m << p | 1 << (p - 1) -- the bits the cleanup pass carries and the
+ * half bit the decoder puts below them; the irreversible de-quantise transfer of the block decoder ((float) magnitude *
+ * delta, the sign OR-ed in; a zero word is +0.0f).  Writes the w x h samples of every plane and nothing else, reads the
+ * source only.  A descriptor with K_max outside 1 .. 30, or wider than max_w, is skipped.  max_w / max_h: the largest w /
+ * h among the descriptors, max_w at most 2^21. */
+typedef struct ojphgpu_requant_desc { uint64_t plane_off; uint32_t pitch, w, h; float delta_inv, delta; uint32_t K_max; } ojphgpu_requant_desc;
+int ojphgpu_band_requantise(void* stream, const ojphgpu_requant_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
+                            const void* d_src_arena, void* d_dst_arena);
+/* ojphgpu_frame_error: component c = the elements [first_elem, first_elem + count) of two frames d_a, d_b in
+ * container_bits (8 | 16 | 32)-bit containers -- int8 / int16 for is_signed != 0, else uint8 / uint16; 32-bit containers
+ * hold int32 whatever is_signed says.  d_out[c].sse += the sum of (a - b)^2 over the run (exact; modulo 2^64, which
+ * differences of 16 bits or fewer cannot reach below 2^32 samples), d_out[c].pae = max(d_out[c].pae, the largest |a - b|):
+ * the caller zeroes d_out.  Integer sums: the result does not depend on the order.  A run may start at any element, count
+ * may be 0; n_comps at most 65535. */
+typedef struct ojphgpu_error_comp { uint64_t first_elem, count; uint32_t is_signed, reserved; } ojphgpu_error_comp;
+typedef struct ojphgpu_frame_err { uint64_t sse; uint32_t pae, reserved; } ojphgpu_frame_err;
+int ojphgpu_frame_error(void* stream, const void* d_a, const void* d_b, int container_bits, const ojphgpu_error_comp* d_comps,
+                        uint32_t n_comps, ojphgpu_frame_err* d_out);
+/* the same with the second frame in a container of its own: bits_b == bits_a, or 32 -- int32 samples against a frame in 8-
+ * or 16-bit containers (is_signed says how the first frame's samples read).  What the quality search compares: a decoded
+ * sample may lie one past its nominal range (256 for an 8-bit component: the reference rounds after its range test), which
+ * int32 hands over as it is and a narrower container saturates. */
+int ojphgpu_frame_error_ex(void* stream, const void* d_a, int bits_a, const void* d_b, int bits_b, const ojphgpu_error_comp* d_comps,
+                           uint32_t n_comps, ojphgpu_frame_err* d_out);
+
 /* ------------------------------------------------------------------------------------------ *
  * 5. Whole-frame codec objects: what an ojph::codestream-compatible facade calls from
  *    flush() (encode) and create()/pull() (decode).
@@ -676,6 +708,55 @@ int  ojphgpu_encoder_rate_info(ojphgpu_encoder* enc, ojphgpu_rate_info* info);
  * device and the copies of the block lengths, [2] the download and Tier-2 of j*; out[3] the band statistics kernel of the
  * run before it (device events; needs ojphgpu_encoder_set_timing's per-launch spans, the default) */
 int  ojphgpu_encoder_rate_timing(ojphgpu_encoder* enc, float out[4]);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 5c. Encoding to a quality target: the other half of rate control.  Over the grid of section 5b, SSE(j) = the sum, over
+ *    every component and every sample of it on its own grid, of (original - decoded)^2, where `decoded` is what
+ *    ojphgpu_decoder_run_device returns (int32 samples: a sample the reference leaves one past its range stays there, where a
+ *    narrower container would saturate) for the codestream the encoder writes at qstep(j); PAE(j) = the largest absolute
+ *    difference.  Both are exact integers (the decoder is sample-exact against the reference).  An encode with max_sse = T
+ *    returns an index j*, the codestream of j* -- byte for byte the plain encode at qstep(j*) -- and the certificate
+ *    SSE(j*) <= T and (j* == 0 or SSE(j* - 1) > T), both sides measured: the coarsest step found to meet the target.  SSE
+ *    is not monotone in j (it rises again in places on real frames) and the search does not assume it is: any index with
+ *    the certificate is an answer.  SSE(240) > T: OJPHGPU_E_QUALITY, nothing written.
+ *
+ *    No block is coded for a trial.  The block coder is lossless over the quantised indices, so the decode of the
+ *    codestream of step j is fixed by the unquantised planes the forward transform left in the arena and the band
+ *    parameters of j: ojphgpu_band_requantise writes the planes the decoder would hold into a second arena, the decoder's
+ *    own synthesis launches (a synthesis-only decoder object made from the encoder's plan) turn them into an int32 frame, and
+ *    ojphgpu_frame_error_ex compares it with the caller's: 16 bytes per component come to the host.  j* is then block-coded
+ *    once.  Not available in the frame pipelines, for batches, tile ranges or the multi-GPU encoder.
+ * ------------------------------------------------------------------------------------------ */
+typedef int64_t (*ojphgpu_sse_fn)(void* user, uint32_t grid_index, uint64_t* sse);   /* 0 and *sse = SSE(j); < 0 = error */
+typedef struct ojphgpu_quality_info {
+  uint32_t grid_index; float qstep;                      /* j*, qstep(j*)                                              */
+  uint64_t sse, sse_coarser;                             /* SSE(j*); SSE(j* - 1), 0 when j* == 0                       */
+  uint32_t pae, passes;                                  /* PAE(j*) (the encoder fills it); calls of the sse_fn        */
+  uint64_t bytes;                                        /* the codestream's length (the encoder fills it)             */
+} ojphgpu_quality_info;
+/* The search, host only.  The first trial is j = 240 (not met: OJPHGPU_E_QUALITY, out->passes = 1), the second j = 0 (met:
+ * the answer); from then on the interval between an index that fails (lo) and one that meets (hi) is halved until hi - lo
+ * == 1, which is the certificate.  passes <= 10 and no index is asked twice, whatever fn returns.  A negative value of fn
+ * is returned as it is. */
+int  ojphgpu_quality_search(uint64_t max_sse, ojphgpu_sse_fn fn, void* user, ojphgpu_quality_info* out);
+
+/* The encoder codes every following frame to max_sse (0 is a target like any other: the finest step at which nothing is
+ * lost may exist); ojphgpu_encoder_clear_quality switches the mode off.  With a target, ojphgpu_encoder_run_device*
+ * enqueues conversion and DWT and returns -- the caller's frame must stay valid and unchanged until ojphgpu_encoder_finish*
+ * has returned, which runs the search against it, codes the blocks of j* and writes its codestream.  OJPHGPU_E_QUALITY
+ * leaves the encoder usable (quality_info: passes).  OJPHGPU_E_INVALID: everything ojphgpu_encoder_set_budget refuses; a
+ * component deeper than 16 bits; a band whose K_max at the finest step is above 30; a byte budget set at the same time
+ * (and set_budget while a target is set); ojphgpu_encoder_finish_tiles*.  The first call re-sizes the scratch slots and
+ * the output for the finest step and allocates the second arena and the reconstructed frame. */
+int  ojphgpu_encoder_set_quality(ojphgpu_encoder* enc, uint64_t max_sse);
+int  ojphgpu_encoder_clear_quality(ojphgpu_encoder* enc);
+/* what the last finish with a target found (OJPHGPU_E_INVALID before one) */
+int  ojphgpu_encoder_quality_info(ojphgpu_encoder* enc, ojphgpu_quality_info* info);
+/* SSE and PAE of component `comp` at j* */
+int  ojphgpu_encoder_quality_comp(ojphgpu_encoder* enc, uint32_t comp, uint64_t* sse, uint32_t* pae);
+/* host clock of the last finish with a target, ms: out[0] the search (every trial), [1] the part of it spent waiting for
+ * the device, [2] coding j*, its download and Tier-2 */
+int  ojphgpu_encoder_quality_timing(ojphgpu_encoder* enc, float out[3]);
 
 /* ------------------------------------------------------------------------------------------ *
  * 6. Frame pipelines: sequences of frames of one shape with PCIe copies, kernels and host Tier-2 of

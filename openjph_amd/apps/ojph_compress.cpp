@@ -6,11 +6,12 @@
 // :997-1021).  Prints "Elapsed time = ..." like the reference (:1220-1222).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include "ojph_app_common.h"
 #include "../../include/ojph_gpu_codestream.h"
 
 static void usage() {
-  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n]\n"
+  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n | -min_psnr dB]\n"
          "  [-num_decomps n] [-block_size {w,h}] [-precincts {w,h}] [-prog_order LRCP|RLCP|RPCL|PCRL|CPRL]\n"
          "  [-colour_trans true|false] [-tile_size {w,h}] [-tlm_marker true|false] [-device n | -devices n,n,...]\n"
          "  [-image_offset {x,y}] [-tile_offset {x,y}] [-tileparts R|C|RC] [-profile IMF|BROADCAST] [-com \"text\"]\n"
@@ -105,6 +106,22 @@ int main(int argc, char** argv) {
       if (mb <= 0) throw std::runtime_error("-max_bytes must be a positive number of bytes");
       cs.set_byte_budget((size_t)mb);
     }
+    unsigned long long max_sse = 0;
+    if (a.get("-min_psnr")) {                                   // GPU path only: the coarsest step of the rate grid found to reach the PSNR
+      if (reversible) throw std::runtime_error("-min_psnr needs irreversible coding (-reversible false)");
+      if (a.get("-qfactor") || a.get("-qstep")) throw std::runtime_error("-min_psnr chooses the quantisation step itself: it cannot be used together with -qstep or -qfactor");
+      if (a.get("-max_bytes")) throw std::runtime_error("-min_psnr and -max_bytes cannot be used together");
+      if (a.get("-devices")) throw std::runtime_error("-min_psnr codes on one device: it cannot be used together with -devices");
+      unsigned long long n = 0;
+      for (unsigned c = 0; c < img.num_comps; ++c) {
+        if (img.bd(c) != img.bd(0)) throw std::runtime_error("-min_psnr needs components of one bit depth");
+        n += (unsigned long long)img.cw[c] * img.ch[c];
+      }
+      if (img.bd(0) > 16) throw std::runtime_error("-min_psnr needs components of at most 16 bits");
+      const unsigned long long peak = (1ull << img.bd(0)) - 1;
+      max_sse = (unsigned long long)((double)(n * peak * peak) / pow(10.0, atof(a.get("-min_psnr")) / 10.0));   // (plan.psnr_to_sse)
+      cs.set_max_sse(max_sse);
+    }
     if (a.get("-tlm_marker")) cs.request_tlm_marker(Args::to_bool(a.get("-tlm_marker")));
     if (a.get("-profile")) cs.set_profile(a.get("-profile"));
     if (a.get("-tileparts")) {                                  // ojph_compress.cpp:324-356: letters R and / or C
@@ -133,6 +150,12 @@ int main(int argc, char** argv) {
       ojph::ui32 gi = 0, passes = 0; float q = 0; ojph::ui64 nbytes = 0;
       if (a.get("-max_bytes") && cs.get_byte_budget_result(gi, q, nbytes, passes))
         printf("Byte budget %s: qstep = %.9g (grid index %u), %llu bytes, %u passes\n", a.get("-max_bytes"), (double)q, gi, (unsigned long long)nbytes, passes);
+    }
+    {
+      ojph::ui32 gi = 0, passes = 0, pae = 0; float q = 0; ojph::ui64 nbytes = 0, sse = 0, coarser = 0;
+      if (a.get("-min_psnr") && cs.get_quality_info(gi, q, sse, coarser, pae, nbytes, passes))
+        printf("Quality target %s dB: max_sse %llu, qstep = %.9g (grid index %u), sse %llu, one step coarser %llu, largest difference %u, %llu bytes, %u trials\n",
+               a.get("-min_psnr"), max_sse, (double)q, gi, (unsigned long long)sse, (unsigned long long)coarser, pae, (unsigned long long)nbytes, passes);
     }
     cs.close();
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libojphgpu.so")
 
-OK, E_INVALID, E_NOMEM, E_HIP, E_CODESTREAM, E_OVERFLOW, E_BLOCK, E_AGAIN, E_UNCOLLECTED, E_BUDGET = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
+OK, E_INVALID, E_NOMEM, E_HIP, E_CODESTREAM, E_OVERFLOW, E_BLOCK, E_AGAIN, E_UNCOLLECTED, E_BUDGET, E_QUALITY = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
 RATE_GRID, STATS_BINS = 241, 80
 PROG_ORDERS = {"LRCP": 0, "RLCP": 1, "RPCL": 2, "PCRL": 3, "CPRL": 4}
 
@@ -152,6 +152,27 @@ class RateInfo(C.Structure):              # ojphgpu_rate_info
 
 
 SIZE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint32)      # ojphgpu_size_fn
+
+
+class RequantDesc(C.Structure):           # ojphgpu_requant_desc
+    _fields_ = [("plane_off", C.c_uint64), ("pitch", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("delta_inv", C.c_float),
+                ("delta", C.c_float), ("K_max", C.c_uint32)]
+
+
+class ErrorComp(C.Structure):             # ojphgpu_error_comp
+    _fields_ = [("first_elem", C.c_uint64), ("count", C.c_uint64), ("is_signed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FrameErr(C.Structure):              # ojphgpu_frame_err
+    _fields_ = [("sse", C.c_uint64), ("pae", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class QualityInfo(C.Structure):           # ojphgpu_quality_info
+    _fields_ = [("grid_index", C.c_uint32), ("qstep", C.c_float), ("sse", C.c_uint64), ("sse_coarser", C.c_uint64),
+                ("pae", C.c_uint32), ("passes", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+SSE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64))      # ojphgpu_sse_fn
 
 _lib = None
 
@@ -317,6 +338,15 @@ SIGNATURES = {
     "ojphgpu_encoder_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
     "ojphgpu_encoder_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_encoder_rate_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_band_requantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ojphgpu_frame_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ojphgpu_frame_error_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ojphgpu_quality_search": (C.c_int, [C.c_uint64, SSE_FN, C.c_void_p, C.POINTER(QualityInfo)]),
+    "ojphgpu_encoder_set_quality": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_encoder_clear_quality": (C.c_int, [C.c_void_p]),
+    "ojphgpu_encoder_quality_info": (C.c_int, [C.c_void_p, C.POINTER(QualityInfo)]),
+    "ojphgpu_encoder_quality_comp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "ojphgpu_encoder_quality_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "ojphgpu_version": (C.c_char_p, []),
 }
 
@@ -355,7 +385,8 @@ class OjphError(RuntimeError):
                  E_OVERFLOW: "output buffer too small", E_BLOCK: "error decoding a codeblock",
                  E_AGAIN: "no free pipeline slot",
                  E_UNCOLLECTED: "the previous run of this decoder asked for a repeat and was never collected",
-                 E_BUDGET: "the byte budget is below the codestream of the coarsest quantisation step"}
+                 E_BUDGET: "the byte budget is below the codestream of the coarsest quantisation step",
+                 E_QUALITY: "the quality target is beyond the finest quantisation step"}
         super().__init__("ojph error: %s (%d) %s" % (names.get(code, "?"), code, what))
         self.code = code
 

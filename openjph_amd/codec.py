@@ -42,10 +42,12 @@ def to_device(arr: np.ndarray, device=0):
 class Encoder:
     """Whole-frame encoder for one frame shape / parameter set (ojphgpu_encoder)."""
 
-    def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, max_bytes=0, **kw):
+    def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, max_bytes=0, max_sse=None, min_psnr=None,
+                 **kw):
         """tiles=(first, count) restricts the encoder to a run of tiles (multi-GPU sharding);
         frames=B makes it code a batch of B independent frames per run ([B,C,H,W] input);
-        max_bytes=N codes every frame to a byte budget (set_budget)."""
+        max_bytes=N codes every frame to a byte budget (set_budget);
+        max_sse=N / min_psnr=dB codes every frame to a quality target (set_quality)."""
         torch = _torch()
         self.device = device
         self.plan = plan if plan is not None else Plan(params if params is not None else make_params(**kw))
@@ -65,8 +67,12 @@ class Encoder:
         fs = self.plan.frame_shape          # [C,H,W], or flat (frame_elems,) when components differ in size
         self.shape = fs if self.frames == 1 else (self.frames,) + fs
         self.max_bytes = 0
+        self.max_sse = None
+        self._frame = None
         if max_bytes:
             self.set_budget(max_bytes)
+        if max_sse is not None or min_psnr is not None:
+            self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
 
     def set_budget(self, max_bytes):
         """Every following frame is coded at the finest step of the rate grid (plan.rate_grid_qstep) whose codestream is at
@@ -76,6 +82,49 @@ class Encoder:
         with _torch().cuda.device(self.device):
             check(self._lib.ojphgpu_encoder_set_budget(self._h, int(max_bytes)), "encoder_set_budget")
         self.max_bytes = int(max_bytes)
+
+    def set_quality(self, max_sse=None, min_psnr=None):
+        """Every following frame is coded at the coarsest step of the rate grid found to meet the target: the squared error
+        between the frame and the decode of its codestream, summed over all components, is at most max_sse (an integer; 0 is
+        a target) -- or min_psnr in dB, turned into one by plan.psnr_to_sse.  Both None switches the target off.  Where
+        set_budget applies, and components of at most 16 bits; not together with a budget.  A target that not even the
+        finest step meets raises OjphError with code E_QUALITY from finish() / encode().  The frame handed to run_device
+        is kept until finish() has returned: the search compares against it."""
+        from .plan import psnr_to_sse
+        if max_sse is not None and min_psnr is not None:
+            raise ValueError("set_quality: max_sse or min_psnr, not both")
+        with _torch().cuda.device(self.device):
+            if max_sse is None and min_psnr is None:
+                check(self._lib.ojphgpu_encoder_clear_quality(self._h), "encoder_clear_quality")
+                self.max_sse = None
+                return
+            t = int(max_sse) if max_sse is not None else psnr_to_sse(self.plan, float(min_psnr))
+            if not 0 <= t < 2 ** 64:
+                raise ValueError("set_quality: max_sse must fit 64 bits")
+            check(self._lib.ojphgpu_encoder_set_quality(self._h, t), "encoder_set_quality")
+        self.max_sse = t
+
+    def quality_info(self):
+        """what the last finish() with a quality target found: dict(grid_index, qstep, sse, sse_coarser = the error one step
+        coarser (0 at index 0), pae = the largest absolute difference, passes = trials made, bytes, comps = [(sse, pae) per
+        component]); after E_QUALITY only passes is meaningful and comps is empty"""
+        info = capi.QualityInfo()
+        check(self._lib.ojphgpu_encoder_quality_info(self._h, C.byref(info)), "encoder_quality_info")
+        out = {k: getattr(info, k) for k, _ in capi.QualityInfo._fields_}
+        out["comps"] = []
+        for c in range(int(self.plan.params.num_comps)):
+            sse, pae = C.c_uint64(), C.c_uint32()
+            if self._lib.ojphgpu_encoder_quality_comp(self._h, c, C.byref(sse), C.byref(pae)) != capi.OK:
+                break
+            out["comps"].append((int(sse.value), int(pae.value)))
+        return out
+
+    def quality_timing(self):
+        """host clock of the last finish() with a quality target, ms: dict(search_ms = all trials, wait_ms = of that, waiting
+        for the device, final_ms = coding the chosen step, its download and Tier-2)"""
+        t = (C.c_float * 3)()
+        check(self._lib.ojphgpu_encoder_quality_timing(self._h, t), "encoder_quality_timing")
+        return dict(search_ms=t[0], wait_ms=t[1], final_ms=t[2])
 
     def rate_info(self):
         """what the last budgeted finish() found: dict(grid_index, qstep, bytes, bytes_finer = the length one step finer
@@ -104,6 +153,7 @@ class Encoder:
         resident on the device. Asynchronous."""
         torch = _torch()
         assert d_image.is_cuda and tuple(d_image.shape) == self.shape and d_image.is_contiguous()
+        self._frame = d_image if self.max_sse is not None else None      # a quality target: finish() reads the frame again
         if d_image.dtype in (torch.int16, torch.uint16):     # 16-bit containers: int16 for signed components, else uint16
             check(self._lib.ojphgpu_encoder_run_device16(self._h, C.c_void_p(d_image.data_ptr())), "encoder_run_device16")
             return
@@ -125,6 +175,8 @@ class Encoder:
         """codestream of frame `frame` of the last run"""
         if self.max_bytes:                 # (a budget far above what the frame can need: the second round below)
             cap = min(self.max_bytes, self.plan.frame_elems * 4 + 64 * self.plan.num_blocks + (1 << 20))
+        elif self.max_sse is not None:     # (the blocks are coded inside finish: nothing to size the buffer by yet)
+            cap = self.plan.frame_elems * 3 + 64 * self.plan.num_blocks + (1 << 20)
         else:
             cap = self.coded_bytes() // self.frames * 2 + 64 * self.plan.num_blocks + (1 << 20)
         out = np.empty(cap, np.uint8)
@@ -134,6 +186,7 @@ class Encoder:
             cap = int(n.value)
             out = np.empty(cap, np.uint8)
             rc = self._lib.ojphgpu_encoder_finish_frame(self._h, frame, out.ctypes.data, cap, C.byref(n))
+        self._frame = None
         check(rc, "encoder_finish")
         return out[:n.value].tobytes()
 
@@ -408,11 +461,11 @@ class MultiDecoder:
         return v.copy() if copy else v
 
 
-def encode(image: np.ndarray, device=0, max_bytes=0, **kw) -> bytes:
+def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, **kw) -> bytes:
     """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes); max_bytes=N: coded to a byte
-    budget (Encoder.set_budget)."""
+    budget (Encoder.set_budget); max_sse=N / min_psnr=dB: coded to a quality target (Encoder.set_quality)."""
     nc, h, w = image.shape
-    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes).encode(image)
+    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes, max_sse=max_sse, min_psnr=min_psnr).encode(image)
 
 
 def decode(codestream: bytes, device=0, resilient=False, skip_res=None, region=None) -> np.ndarray:
@@ -487,6 +540,43 @@ def band_stats(descs: np.ndarray, arena, slots):
                                         C.c_void_p(arena.data_ptr()), C.c_void_p(hist.data_ptr())), "band_stats")
     torch.cuda.synchronize(dev)
     return hist.cpu().numpy().view(np.uint32)
+
+
+requant_desc_dtype = np.dtype(capi.RequantDesc)
+error_comp_dtype = np.dtype(capi.ErrorComp)
+frame_err_dtype = np.dtype(capi.FrameErr)
+
+
+def band_requantise(descs: np.ndarray, src, dst):
+    """ojphgpu_band_requantise: descs requant_desc_dtype (host); src, dst device tensors of 32-bit elements (the arenas).
+    Writes the w x h samples of every descriptor's plane into dst, in place; src is only read."""
+    torch = _torch()
+    dev = src.device.index
+    d = to_device(descs, dev)
+    max_w = int(descs["w"].max()) if len(descs) else 0
+    max_h = int(descs["h"].max()) if len(descs) else 0
+    check(capi.lib().ojphgpu_band_requantise(_stream_ptr(torch, dev), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
+                                             C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr())), "band_requantise")
+    torch.cuda.synchronize(dev)
+
+
+def frame_error(a, b, comps):
+    """ojphgpu_frame_error / _ex: a, b device tensors holding two frames, of one integer dtype (8-, 16- or 32-bit containers) or
+    b int32 against a narrower a; comps = [(first_elem, count, is_signed), ...] -> [(sse, pae), ...] per component, exact"""
+    torch = _torch()
+    assert a.is_cuda and b.is_cuda and a.is_contiguous() and b.is_contiguous()
+    assert a.element_size() == b.element_size() or b.element_size() == 4
+    dev = a.device.index
+    cd = np.zeros(len(comps), error_comp_dtype)
+    for i, (first, count, sg) in enumerate(comps):
+        cd[i]["first_elem"], cd[i]["count"], cd[i]["is_signed"] = int(first), int(count), int(bool(sg))
+    d = to_device(cd, dev)
+    out = torch.zeros(max(len(comps), 1) * frame_err_dtype.itemsize, dtype=torch.uint8, device=a.device)
+    check(capi.lib().ojphgpu_frame_error_ex(_stream_ptr(torch, dev), C.c_void_p(a.data_ptr()), 8 * a.element_size(), C.c_void_p(b.data_ptr()),
+                                            8 * b.element_size(), C.c_void_p(d.data_ptr()), len(comps), C.c_void_p(out.data_ptr())), "frame_error")
+    torch.cuda.synchronize(dev)
+    r = out.cpu().numpy().view(frame_err_dtype)[:len(comps)]
+    return [(int(x["sse"]), int(x["pae"])) for x in r]
 
 
 def dwt_general_image(direction, steps, elem, params: Params, descs: np.ndarray, image, arena, max_w, max_h, K=1.0, container=32):

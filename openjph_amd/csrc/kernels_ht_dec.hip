@@ -55,6 +55,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/ojphgpu.h"
+#include "ht_quant.h"
 #include "ht_tables.h"
 #include "ht_uvlc.h"
 
@@ -65,6 +66,8 @@ __device__ uint16_t g_dec_uvlc0[320];
 }
 
 namespace {
+
+using ojphgpu::dequantise;                 // the de-quantise transfer (ht_quant.h)
 
 constexpr int WAVES = 4;
 constexpr uint32_t RING_WORDS = 256;          // step 2: 8 Kbit of un-stuffed MagSgn per wavefront (>= 4160 + 2048 + 32 in flight)
@@ -944,16 +947,6 @@ __global__ __launch_bounds__(128 * CH) void ht_dec_step1_kernel(
 #ifndef S2_ABL
 #define S2_ABL 0                  // attribution experiments on step 2's row loop (never in the product; results are wrong): 1 the sample stores only happen
 #endif                            // for a value that never occurs, 2 no prefix sum (a product stands in), 4 no ring reads, 8 no neighbour exponents, 16 no un-stuffing
-// de-quantise transfer of one sign-magnitude word (ojph_codestream_gen.cpp:124-168)
-__device__ __forceinline__ uint32_t dequantise(uint32_t val, bool rev, uint32_t shift, float delta)
-{
-  const uint32_t mag = val & 0x7FFFFFFFu;
-  if (rev) { const uint32_t iv = mag >> shift, sg = (uint32_t)((int)val >> 31); return (iv ^ sg) - sg; }   // -iv for a set sign
-  // (the product of two non-negative floats has a clear sign bit: OR-ing the sample's sign in negates it, -0.0f for a zero
-  // magnitude included -- as "-fv" does)
-  return __float_as_uint(__fmul_rn((float)mag, delta)) | (val & 0x80000000u);
-}
-
 // does the block carry SigProp / MagRef passes that will be decoded (block_decoder32.cpp:752-789)?
 __device__ __forceinline__ bool needs_refinement(const ojphgpu_cb_desc& d)
 {

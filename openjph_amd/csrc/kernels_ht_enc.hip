@@ -41,6 +41,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "../../include/ojphgpu.h"
+#include "ht_quant.h"
 #include "ht_tables.h"
 
 namespace ojphgpu {
@@ -48,6 +49,8 @@ __device__ __attribute__((aligned(16))) uint16_t g_enc_vlc[2][2048];   // filled
 }
 
 namespace {
+
+using ojphgpu::to_sign_mag;                // the quantise transfer (ht_quant.h)
 
 constexpr int MS_WORDS = 512;     // 64 lanes * 8 samples * 31 bits + carry  < 2048 bytes
 constexpr int VLC_WORDS = 64;     // 64 lanes * 30 bits + carry < 256 bytes
@@ -103,29 +106,6 @@ __device__ __forceinline__ void or_bits(uint32_t* buf, uint32_t pos, uint32_t v,
 
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 __device__ __forceinline__ uint32_t rdfirst(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-// quantise transfer of one raw coefficient: sign | magnitude, MSB aligned.  A coefficient with more than K_max magnitude
-// bits (Part-2 kernels whose gain outruns the guard bits) leaves the reference's transfer the way its 32-bit arithmetic
-// has it: reversible, |v| << shift drops what does not fit and bit K_max of |v| lands on the sign position
-// (ojph_codestream_gen.cpp:70-76); irreversible, the float -> int conversion of a product beyond 2^31 gives INT_MIN (what
-// cvttss2si and its vector forms return for every out-of-range input, NaN included), i.e. the word 0x80000000: a zero.
-// Either way that bit counts in max_val, and codeblock::encode (ojph_codeblock.cpp:142-175) codes a block whose max_val
-// is not zero even when no sample of it is significant: `over` collects it.
-__device__ __forceinline__ uint32_t to_sign_mag(uint32_t raw, bool reversible, uint32_t shift, float delta_inv, uint32_t& over)
-{
-  if (reversible) {
-    const int v = (int)raw;
-    const uint32_t m = (v >= 0 ? (uint32_t)v : 0u - (uint32_t)v) << shift;
-    over |= m >> 31;
-    return (v >= 0 ? 0u : 0x80000000u) | m;
-  }
-  const float f = __fmul_rn(__uint_as_float(raw), delta_inv);            // :113-118, C truncation
-  const bool out = !(fabsf(f) < 2147483648.0f);
-  const int t = out ? (int)0x80000000u : (int)f;
-  const uint32_t m = t >= 0 ? (uint32_t)t : 0u - (uint32_t)t;
-  over |= m >> 31;
-  return (t >= 0 ? 0u : 0x80000000u) | m;
-}
 
 __device__ __forceinline__ uint32_t expo(uint32_t val) { return val ? 32u - (uint32_t)__clz((int)(val - 1)) : 0u; }
 __device__ __forceinline__ uint32_t expo(uint64_t val) { return val ? 64u - (uint32_t)__clzll((long long)(val - 1)) : 0u; }

@@ -116,6 +116,7 @@ struct codestream_state {
   std::string profile;
   int device = 0;
   size_t byte_budget = 0;             // set_byte_budget: flush() codes the frame to at most this many bytes (0: off)
+  bool quality_on = false; ui64 max_sse = 0;   // set_max_sse: flush() codes the frame to at most this squared error
   // more than one device: a tiled frame is coded by all of them, each a contiguous run of tiles (include/ojphgpu.h section 8)
   std::vector<int> devices;
   ojphgpu_multi_encoder* menc = nullptr; ojphgpu_multi_decoder* mdec = nullptr;
@@ -561,6 +562,16 @@ bool codestream::get_byte_budget_result(ui32& grid_index, float& qstep, ui64& by
   grid_index = info.grid_index; qstep = info.qstep; bytes = info.bytes; passes = info.passes;
   return true;
 }
+void codestream::set_max_sse(ui64 max_sse) { state->quality_on = true; state->max_sse = max_sse; }
+void codestream::clear_max_sse() { state->quality_on = false; }
+bool codestream::get_quality_info(ui32& grid_index, float& qstep, ui64& sse, ui64& sse_coarser, ui32& pae, ui64& bytes, ui32& passes)
+{
+  ojphgpu_quality_info info;
+  if (!state->enc || ojphgpu_encoder_quality_info(state->enc, &info) != OJPHGPU_OK) return false;
+  grid_index = info.grid_index; qstep = info.qstep; sse = info.sse; sse_coarser = info.sse_coarser; pae = info.pae;
+  bytes = info.bytes; passes = info.passes;
+  return true;
+}
 void codestream::enable_frame_pipelining(ui32 frames_in_flight)
 {
   state->drain();
@@ -720,8 +731,11 @@ void codestream::write_headers(outfile_base* file, const comment_exchange* comme
     if (rc) ojph_error(0x00030F08, "cannot create the GPU encoder (status %d): no GPU?", rc);
     if (S.byte_budget && ojphgpu_encoder_set_budget(S.enc, S.byte_budget) != OJPHGPU_OK)
       ojph_error(0x00030F13, "a byte budget needs irreversible coding of every component with the Part-1 wavelet and no quality factor");
+    if (S.quality_on && ojphgpu_encoder_set_quality(S.enc, S.max_sse) != OJPHGPU_OK)
+      ojph_error(0x00030F16, "a quality target needs irreversible coding of every component with the Part-1 wavelet, no quality factor, no byte budget and components of at most 16 bits");
     S.alloc_frame();
   }
+  if (S.quality_on && !S.enc) ojph_error(0x00030F17, "a quality target is available for single frames on one device (no restart()ed sequence, no set_devices)");
   if (S.byte_budget && !S.enc) ojph_error(0x00030F14, "a byte budget is available for single frames on one device (no restart()ed sequence, no set_devices)");
   // a frame still queued for this very file object (enable_frame_pipelining, and the application re-opened the object for
   // the next frame): its codestream is written before the object is used again
@@ -778,6 +792,7 @@ void codestream::flush()
   size_t len = 0;
   int rc = ojphgpu_encode(S.enc, S.frame, nullptr, 0, &len);            // runs the GPU path; reports the codestream size
   if (rc == OJPHGPU_E_BUDGET) ojph_error(0x00030F15, "the byte budget of %zu bytes is below the codestream of the coarsest quantisation step (status %d)", S.byte_budget, rc);
+  if (rc == OJPHGPU_E_QUALITY) ojph_error(0x00030F18, "the quality target of %llu is beyond the finest quantisation step (status %d)", (unsigned long long)S.max_sse, rc);
   if (rc != OJPHGPU_E_OVERFLOW && rc != OJPHGPU_OK) ojph_error(0x00030F0B, "GPU encode failed (status %d)", rc);
   std::unique_ptr<ui8[]> out(new ui8[len + 16]);
   rc = ojphgpu_encoder_finish(S.enc, out.get(), len + 16, &len);         // host Tier-2 only (block bytes are already here)

@@ -205,6 +205,40 @@ extern "C" int ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* his
   return ojphgpu_rate_search_hint(plan, hist, max_bytes, -1, fn, user, out);
 }
 
+// Encoding to a quality target (include/ojphgpu.h section 5c): the coarsest index found whose trial meets max_sse.  Index 240
+// first (the target cannot be met at all: OJPHGPU_E_QUALITY), then 0 (everything meets it), then halving between an index
+// that failed (lo) and one that met (hi).  Nothing is assumed about fn between the two: whatever it returns, lo fails and hi
+// meets and both were measured, so hi - lo == 1 is the certificate.  2 + ceil(log2(240)) = 10 trials at most, each at an
+// index strictly inside the interval: none twice.
+extern "C" int ojphgpu_quality_search(uint64_t max_sse, ojphgpu_sse_fn fn, void* user, ojphgpu_quality_info* out)
+{
+  if (!fn || !out) return OJPHGPU_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  int64_t err = 0;
+  auto trial = [&](uint32_t j, uint64_t& sse) -> bool {
+    sse = 0;
+    err = fn(user, j, &sse);
+    out->passes++;
+    return err >= 0;
+  };
+  auto fail = [&]() -> int { return err < INT32_MIN ? OJPHGPU_E_INVALID : (int)err; };
+  uint32_t lo = 0, hi = OJPHGPU_RATE_GRID - 1;
+  uint64_t sse_lo = 0, sse_hi = 0;
+  if (!trial(hi, sse_hi)) return fail();
+  if (sse_hi > max_sse) return OJPHGPU_E_QUALITY;
+  if (!trial(lo, sse_lo)) return fail();
+  if (sse_lo <= max_sse) { hi = 0; sse_hi = sse_lo; sse_lo = 0; }
+  while (hi > lo + 1) {
+    const uint32_t j = (lo + hi) / 2;
+    uint64_t s;
+    if (!trial(j, s)) return fail();
+    if (s <= max_sse) { hi = j; sse_hi = s; } else { lo = j; sse_lo = s; }
+  }
+  out->grid_index = hi; out->qstep = rate_grid_qstep(hi);
+  out->sse = sse_hi; out->sse_coarser = hi ? sse_lo : 0;
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out)
 {
   if (!plan || !hist || !out) return OJPHGPU_E_INVALID;

@@ -61,6 +61,7 @@ extern "C" void ojphgpu_encoder_destroy(ojphgpu_encoder* e)
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   e->timer.destroy();
+  delete e->quality;
   delete e->rate;
   delete e;
 }
@@ -319,7 +320,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     T.end(sp, s);
   }
   if (rc) return rc;
-  const bool budget = e->max_bytes != 0;                    // the blocks are coded by the search, in ojphgpu_encoder_finish*
+  const bool budget = e->searches();                        // the blocks are coded by the search, in ojphgpu_encoder_finish*
   for (size_t i = 0; i < e->batches.size(); ++i) {
     const LevelBatch& b = e->batches[i];
     const int sp = T.begin(SP_DWT, s);
@@ -337,6 +338,13 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     T.end(sp, s);
     const bool top_done = b.depth == 0 && (i + 1 == e->batches.size() || e->batches[i + 1].depth != 0);
     if (!budget && e->n_top && top_done && (rc = coder.fork_top()) != 0) return rc;
+  }
+  if (e->quality_on) {                                      // the search reads the planes in the arena and the caller's frame
+    T.finish(s);
+    e->quality->frame = d_image; e->quality->container = container;
+    e->rate->searched = false; e->rate->at = -1;
+    e->ran = true; e->fetched = false;
+    return OJPHGPU_OK;
   }
   if (budget) {
     EncoderRate& R = *e->rate;
@@ -379,7 +387,7 @@ extern "C" int ojphgpu_encoder_coded_bytes(ojphgpu_encoder* e, uint64_t* bytes)
 // table of frame `frame`
 static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu_coded_block>& cb)
 {
-  const Plan& P = e->max_bytes ? e->rate->plan->plan : *e->P;   // (a byte budget: the plan at the step the search chose)
+  const Plan& P = e->searches() ? e->rate->plan->plan : *e->P;   // (a byte budget, a quality target: the plan at the step the search chose)
   if (frame >= e->nframes) return OJPHGPU_E_INVALID;
   if (!e->fetched) {
     int rc = ojphgpu_encoder_coded_bytes(e, &e->nbytes);
@@ -413,6 +421,7 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
 }
 
 static int encoder_rate_search(ojphgpu_encoder* e);
+static int encoder_quality_search(ojphgpu_encoder* e);
 
 extern "C" int ojphgpu_encoder_finish(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len)
 {
@@ -429,14 +438,15 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
   const bool tm = getenv("OJPHGPU_TIMING") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
-  int rc = e->max_bytes ? encoder_rate_search(e) : OJPHGPU_OK;
+  int rc = e->quality_on ? encoder_quality_search(e) : e->max_bytes ? encoder_rate_search(e) : OJPHGPU_OK;
   if (rc) return rc;
-  if (e->max_bytes) t0 = now();
+  if (e->searches()) t0 = now();
   rc = encoder_fetch(e, frame, cb);
   if (rc) return rc;
   auto t1 = now();
-  rc = ojphgpu_t2_write(e->max_bytes ? e->rate->plan : e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
+  rc = ojphgpu_t2_write(e->searches() ? e->rate->plan : e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
   if (e->max_bytes) e->rate->final_ms = std::chrono::duration<double, std::milli>(now() - t0).count();
+  if (e->quality_on) e->quality->final_ms += std::chrono::duration<double, std::milli>(now() - t0).count();
   if (tm) fprintf(stderr, "ojphgpu: finish frame %u: D2H %.2f ms, Tier-2 %.2f ms\n", frame,
                   std::chrono::duration<double, std::milli>(t1 - t0).count(),
                   std::chrono::duration<double, std::milli>(now() - t1).count());
@@ -447,7 +457,7 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
 extern "C" int ojphgpu_encoder_finish_tiles(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len,
                                              uint32_t* tile_part_len)
 {
-  if (!e || !out_len || !e->ran || e->max_bytes) return OJPHGPU_E_INVALID;
+  if (!e || !out_len || !e->ran || e->searches()) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     std::vector<ojphgpu_coded_block> cb;
     int rc = encoder_fetch(e, 0, cb);
@@ -468,7 +478,7 @@ int publish_words_launch(void* stream, uint32_t* d_dst, const uint32_t* src, uin
 extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* d_out, size_t cap, size_t* out_len,
                                                     uint32_t* tile_part_len)
 {
-  if (!e || !out_len || !e->ran || e->max_bytes) return OJPHGPU_E_INVALID;
+  if (!e || !out_len || !e->ran || e->searches()) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     const Plan& P = *e->P;
     uint64_t nbytes = 0;
@@ -502,23 +512,44 @@ extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* 
 // ---------------------------------------------------------------------------------------------
 // encoding to a byte budget (include/ojphgpu.h section 5b)
 // ---------------------------------------------------------------------------------------------
+// the block descriptors of an encoder that searched go back to the plan's own step
+static int encoder_restore_descs(ojphgpu_encoder* e)
+{
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const std::vector<ojphgpu_cb_desc>& bd = e->rate->bd;
+  if (!bd.empty()) HIPCHK(hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice));
+  e->ran = false;
+  return OJPHGPU_OK;
+}
+
+static bool encoder_may_search(const ojphgpu_encoder* e)
+{
+  const Plan& P = *e->P;
+  return e->nframes == 1 && e->tiles.first == 0 && e->tiles.count == P.tiles.size() && !e->o_out && rate_plan_ok(P);
+}
+
+static int encoder_rate_setup(ojphgpu_encoder* e);
+
 extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes)
 {
   if (!e) return OJPHGPU_E_INVALID;
   if (max_bytes == 0) {
-    if (e->max_bytes && e->rate) {                          // the descriptors go back to the plan's own step
-      HIPCHK(hipSetDevice(e->device));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      const std::vector<ojphgpu_cb_desc>& bd = e->rate->bd;
-      if (!bd.empty()) HIPCHK(hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice));
-      e->ran = false;
-    }
+    if (e->max_bytes && e->rate) { const int rc = encoder_restore_descs(e); if (rc) return rc; }
     e->max_bytes = 0;
     return OJPHGPU_OK;
   }
+  if (!encoder_may_search(e) || e->quality_on) return OJPHGPU_E_INVALID;
+  if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
+  e->max_bytes = max_bytes; e->ran = false;
+  return OJPHGPU_OK;
+}
+
+// what a searching encoder needs (the first ojphgpu_encoder_set_budget / _set_quality): the quantisation of every step, the
+// band statistics' tables, the blocks' classes, and scratch slots and an output that hold the finest step of the grid
+static int encoder_rate_setup(ojphgpu_encoder* e)
+{
   const Plan& P = *e->P;
-  if (e->nframes != 1 || e->tiles.first != 0 || e->tiles.count != P.tiles.size() || e->o_out || !rate_plan_ok(P)) return OJPHGPU_E_INVALID;
-  if (e->rate) { e->max_bytes = max_bytes; e->ran = false; return OJPHGPU_OK; }
   return no_throw([&]() -> int {
     HIPCHK(hipSetDevice(e->device));
     EncoderRate* R = new EncoderRate();
@@ -559,7 +590,7 @@ extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes
     if (!cls.empty()) HIPCHK(hipMemcpy(R->block_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
     R->h_hist.assign(P.bands.size() * OJPHGPU_STATS_BINS, 0);
     e->rate = R; owner.p = nullptr;
-    e->max_bytes = max_bytes; e->ran = false;
+    e->ran = false;
     return OJPHGPU_OK;
   });
 }
@@ -658,6 +689,145 @@ extern "C" int ojphgpu_encoder_rate_timing(ojphgpu_encoder* e, float out[4])
   if (!e || !out || !e->rate || !e->rate->searched || !e->ran) return OJPHGPU_E_INVALID;
   out[0] = (float)e->rate->search_ms; out[1] = (float)e->rate->wait_ms; out[2] = (float)e->rate->final_ms;
   if (e->timer.read(SP_STATS, &out[3])) return OJPHGPU_E_HIP;
+  return OJPHGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// encoding to a quality target (include/ojphgpu.h section 5c)
+// ---------------------------------------------------------------------------------------------
+static int decoder_create_synthesis(const ojphgpu_plan* plan, int device, void* stream, ojphgpu_decoder** out);
+static int decoder_synthesis_only(ojphgpu_decoder* d, void* d_image, int container);
+
+extern "C" int ojphgpu_encoder_clear_quality(ojphgpu_encoder* e)
+{
+  if (!e) return OJPHGPU_E_INVALID;
+  if (e->quality_on && e->rate) { const int rc = encoder_restore_descs(e); if (rc) return rc; }
+  e->quality_on = false;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_set_quality(ojphgpu_encoder* e, uint64_t max_sse)
+{
+  if (!e) return OJPHGPU_E_INVALID;
+  if (!encoder_may_search(e) || e->max_bytes) return OJPHGPU_E_INVALID;
+  const Plan& P = *e->P;
+  for (const CompGeo& g : P.comps) if (g.bit_depth > 16) return OJPHGPU_E_INVALID;
+  if (e->quality) { e->max_sse = max_sse; e->quality_on = true; e->ran = false; return OJPHGPU_OK; }
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(e->device));
+    {                                                       // the half bit needs room below the coded bits at every step
+      RateTable T;
+      const int rc = e->rate ? OJPHGPU_OK : rate_table_build(P, T);
+      if (rc) return rc;
+      const RateTable& U = e->rate ? e->rate->table : T;
+      for (uint32_t c = 0; c < U.nclasses; ++c) if (U.quant[(size_t)(OJPHGPU_RATE_GRID - 1) * U.nclasses + c].K_max > 30) return OJPHGPU_E_INVALID;
+    }
+    if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
+    EncoderQuality* Q = new EncoderQuality();
+    struct Owner { EncoderQuality* p; ~Owner() { delete p; } } owner{ Q };
+    int rc = decoder_create_synthesis(e->handle, e->device, e->stream, &Q->syn);
+    if (rc) return rc;
+    for (size_t i = 0; i < P.bands.size(); ++i) {
+      const Band& B = P.bands[i];
+      if (B.empty) continue;
+      ojphgpu_requant_desc d; memset(&d, 0, sizeof(d));
+      d.plane_off = B.plane_off; d.pitch = B.pitch; d.w = B.r.w; d.h = B.r.h;
+      Q->h_descs.push_back(d); Q->desc_band.push_back((uint32_t)i);
+      Q->max_w = std::max(Q->max_w, B.r.w); Q->max_h = std::max(Q->max_h, B.r.h);
+    }
+    std::vector<ojphgpu_error_comp> ec;
+    for (const CompGeo& g : P.comps) ec.push_back(ojphgpu_error_comp{ g.frame_off, (uint64_t)g.w * g.h, g.is_signed ? 1u : 0u, 0u });
+    Q->h_err.assign(ec.size(), ojphgpu_frame_err{ 0, 0, 0 }); Q->best = Q->h_err;
+    if (Q->recon.alloc((size_t)P.frame_elems * 4) || Q->descs.alloc(Q->h_descs.size() * sizeof(ojphgpu_requant_desc)) ||
+        Q->comps.alloc(ec.size() * sizeof(ec[0])) || Q->err.alloc(ec.size() * sizeof(ojphgpu_frame_err)))
+      return OJPHGPU_E_NOMEM;
+    if (!ec.empty()) HIPCHK(hipMemcpy(Q->comps.p, ec.data(), ec.size() * sizeof(ec[0]), hipMemcpyHostToDevice));
+    e->quality = Q; owner.p = nullptr;
+    e->max_sse = max_sse; e->quality_on = true; e->ran = false;
+    return OJPHGPU_OK;
+  });
+}
+
+// One trial of the search: SSE(j) of the frame of the last run.  The planes of the arena, requantised with the band
+// parameters of j into the synthesis decoder's arena, go through the decoder's synthesis launches into the reconstructed
+// frame (int32); the error sums against the caller's frame, in its own container, come to the host.  No block is coded.
+static int64_t encoder_quality_trial(void* user, uint32_t j, uint64_t* sse)
+{
+  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
+  EncoderRate& R = *e->rate; EncoderQuality& Q = *e->quality;
+  hipStream_t s = e->stream;
+  auto hip = [](hipError_t x) { return x == hipSuccess; };
+  const uint32_t nc = R.table.nclasses;
+  for (size_t i = 0; i < Q.h_descs.size(); ++i) {
+    const BandQuant& q = R.table.quant[(size_t)j * nc + R.table.band_class[Q.desc_band[i]]];
+    Q.h_descs[i].delta = q.delta; Q.h_descs[i].delta_inv = 1.0f / q.delta; Q.h_descs[i].K_max = q.K_max;   // (as rate_apply_step has them)
+  }
+  const size_t dbytes = Q.h_descs.size() * sizeof(ojphgpu_requant_desc), ebytes = Q.h_err.size() * sizeof(ojphgpu_frame_err);
+  if (dbytes && !hip(hipMemcpyAsync(Q.descs.p, Q.h_descs.data(), dbytes, hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
+  int rc = ojphgpu_band_requantise(s, (const ojphgpu_requant_desc*)Q.descs.p, (uint32_t)Q.h_descs.size(), Q.max_w, Q.max_h, e->arena.p, Q.syn->arena.p);
+  if (rc) return rc;
+  // (int32 whatever the run's container: a sample the reference leaves one past its range must not saturate, fit_container)
+  if ((rc = decoder_synthesis_only(Q.syn, Q.recon.p, 32)) != 0) return rc;
+  if (!hip(hipMemsetAsync(Q.err.p, 0, ebytes, s))) return OJPHGPU_E_HIP;
+  rc = ojphgpu_frame_error_ex(s, Q.frame, Q.container, Q.recon.p, 32, (const ojphgpu_error_comp*)Q.comps.p, (uint32_t)Q.h_err.size(), (ojphgpu_frame_err*)Q.err.p);
+  if (rc) return rc;
+  const auto w0 = std::chrono::steady_clock::now();
+  if (!hip(hipMemcpyAsync(Q.h_err.data(), Q.err.p, ebytes, hipMemcpyDeviceToHost, s)) || !hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
+  Q.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  uint64_t total = 0;
+  for (const ojphgpu_frame_err& c : Q.h_err) total += c.sse;
+  Q.by_index[j] = Q.h_err;
+  *sse = total;
+  return 0;
+}
+
+// the search of the last run, once: afterwards the device holds the coded blocks of j* and R.plan stands at its step
+static int encoder_quality_search(ojphgpu_encoder* e)
+{
+  EncoderRate& R = *e->rate; EncoderQuality& Q = *e->quality;
+  if (R.searched) return R.search_rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  Q.wait_ms = 0; Q.final_ms = 0;
+  auto run = [&]() -> int {
+    if (!Q.frame) return OJPHGPU_E_INVALID;
+    Q.by_index.assign(OJPHGPU_RATE_GRID, {});
+    int rc = ojphgpu_quality_search(e->max_sse, encoder_quality_trial, e, &Q.info);
+    Q.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_QUALITY;
+    Q.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) return rc;
+    Q.best = Q.by_index[Q.info.grid_index];
+    for (const ojphgpu_frame_err& c : Q.best) Q.info.pae = std::max(Q.info.pae, c.pae);
+    const auto t1 = std::chrono::steady_clock::now();
+    const int64_t size = encoder_rate_trial(e, Q.info.grid_index);   // j* is block-coded, once, as a trial of the byte budget is
+    Q.final_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    if (size < 0) return size < INT32_MIN ? OJPHGPU_E_INVALID : (int)size;
+    Q.info.bytes = (uint64_t)size;
+    return OJPHGPU_OK;
+  };
+  R.search_rc = no_throw(run);
+  R.searched = true;
+  return R.search_rc;
+}
+
+extern "C" int ojphgpu_encoder_quality_info(ojphgpu_encoder* e, ojphgpu_quality_info* info)
+{
+  if (!e || !info || !e->quality || !e->quality->have_info) return OJPHGPU_E_INVALID;
+  *info = e->quality->info;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_quality_comp(ojphgpu_encoder* e, uint32_t comp, uint64_t* sse, uint32_t* pae)
+{
+  if (!e || !sse || !pae || !e->quality || !e->quality->have_info || !e->rate->searched || e->rate->search_rc || comp >= e->quality->best.size())
+    return OJPHGPU_E_INVALID;
+  *sse = e->quality->best[comp].sse; *pae = e->quality->best[comp].pae;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_quality_timing(ojphgpu_encoder* e, float out[3])
+{
+  if (!e || !out || !e->quality || !e->rate->searched) return OJPHGPU_E_INVALID;
+  out[0] = (float)e->quality->search_ms; out[1] = (float)e->quality->wait_ms; out[2] = (float)e->quality->final_ms;
   return OJPHGPU_OK;
 }
 
@@ -1083,6 +1253,52 @@ static int decode_samples(ojphgpu_decoder* d, hipStream_t s, uint32_t first, uin
   return OJPHGPU_OK;
 }
 
+// The synthesis of a run, from the level batches through the conversion: the sub-band planes in the decoder's arena ->
+// d_image.  n_low != 0: the levels below the top run on the side stream (forked by the caller) and finish_blocks -- the
+// rest of the block decoder on the main stream, then the join; it sets `joined` -- is called before the top level.  What
+// ojphgpu_decoder_run_container issues behind its block decoder, and all that the synthesis-only decoder of an encoder
+// with a quality target (section 5c) ever issues: one schedule, so a trial of that search sees the decoder's own samples.
+template <typename F>
+static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, uint32_t n_low, bool& joined, F finish_blocks)
+{
+  const Plan& P = *d->P;
+  hipStream_t s = d->stream;
+  Spans& T = d->timer;
+  int rc = OJPHGPU_OK;
+  for (const LevelBatch& b : d->batches) {
+    const bool top = b.depth == 0;                          // the last level of its components (there may be two such launches)
+    hipStream_t ls = (n_low && !top) ? d->side : s;
+    if (top && n_low && !joined && (rc = finish_blocks()) != 0) return rc;
+    const int sp = T.begin(SP_DWT, ls);
+    if (d->region) {                                        // region synthesis (the Part-1 wavelets only: plan_restrict_region)
+      const ojphgpu_dwt_region* regs = (const ojphgpu_dwt_region*)(b.img_first >= 0 ? d->img_regs.p : d->dwt_regs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
+      const ojphgpu_dwt_desc* descs = (const ojphgpu_dwt_desc*)(b.img_first >= 0 ? d->img_descs.p : d->dwt_descs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
+      rc = ojphgpu::dwt_inverse_region_launch(ls, b.rev ? 1 : 0, descs, regs, b.count, b.rgrid, d->arena.p, b.img_first >= 0 ? d_image : nullptr,
+                                              container, b.img_first >= 0 ? b.nc : 1);
+    } else if (b.img_first >= 0) {                          // float->int / level shift applied in the stores
+      ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0; pp.bit_depth = b.img_depth; pp.is_signed = b.img_signed;
+      const ojphgpu_dwt_desc* idesc = (const ojphgpu_dwt_desc*)d->img_descs.p + b.img_first;
+      rc = b.general ? ojphgpu_dwt_inverse_general_image(ls, &b.k, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container)
+                     : ojphgpu_dwt_inverse_image_ex(ls, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container, b.nc == 3);
+    } else if (b.general)
+      rc = ojphgpu_dwt_inverse_general(ls, &b.k, (const ojphgpu_dwt_desc*)d->dwt_descs.p + b.first, b.count, b.max_w, b.max_h, d->arena.p);
+    else
+      rc = ojphgpu_dwt_inverse(ls, b.rev ? 1 : 0, (const ojphgpu_dwt_desc*)d->dwt_descs.p + b.first, b.count,
+                               b.max_w, b.max_h, d->arena.p);
+    if (rc) return rc;
+    T.end(sp, ls);
+  }
+  if (n_low && !joined && (rc = finish_blocks()) != 0) return rc;
+  if (d->need_convert) {
+    const int sp = T.begin(SP_CONVERT, s);
+    rc = ojphgpu_convert_inverse_ex(s, &P.p, (const ojphgpu_convert_desc*)d->conv_descs.p, d->conv_tiles * d->nframes,
+                                    d->conv_max_w, d->conv_max_h, d_image, d->arena.p, container);
+    if (rc) return rc;
+    T.end(sp, s);
+  }
+  return OJPHGPU_OK;
+}
+
 int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int container);
 static int decode_host(ojphgpu_decoder* d, const uint8_t* h_codestream, size_t len, void* h_image, int container);
 
@@ -1148,39 +1364,50 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
     HIPCHK(hipStreamWaitEvent(s, d->ev_join, 0));           // join before the top synthesis level
     return OJPHGPU_OK;
   };
-  for (const LevelBatch& b : d->batches) {
-    const bool top = b.depth == 0;                          // the last level of its components (there may be two such launches)
-    hipStream_t ls = (n_low && !top) ? d->side : s;
-    if (top && n_low && !joined && (rc = finish_blocks()) != 0) return rc;
-    const int sp = T.begin(SP_DWT, ls);
-    if (d->region) {                                        // region synthesis (the Part-1 wavelets only: plan_restrict_region)
-      const ojphgpu_dwt_region* regs = (const ojphgpu_dwt_region*)(b.img_first >= 0 ? d->img_regs.p : d->dwt_regs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
-      const ojphgpu_dwt_desc* descs = (const ojphgpu_dwt_desc*)(b.img_first >= 0 ? d->img_descs.p : d->dwt_descs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
-      rc = ojphgpu::dwt_inverse_region_launch(ls, b.rev ? 1 : 0, descs, regs, b.count, b.rgrid, d->arena.p, b.img_first >= 0 ? d_image : nullptr,
-                                              container, b.img_first >= 0 ? b.nc : 1);
-    } else if (b.img_first >= 0) {                          // float->int / level shift applied in the stores
-      ojphgpu_params pp = P.p; pp.reversible = b.rev ? 1 : 0; pp.bit_depth = b.img_depth; pp.is_signed = b.img_signed;
-      const ojphgpu_dwt_desc* idesc = (const ojphgpu_dwt_desc*)d->img_descs.p + b.img_first;
-      rc = b.general ? ojphgpu_dwt_inverse_general_image(ls, &b.k, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container)
-                     : ojphgpu_dwt_inverse_image_ex(ls, &pp, idesc, b.count, b.max_w, b.max_h, d_image, d->arena.p, container, b.nc == 3);
-    } else if (b.general)
-      rc = ojphgpu_dwt_inverse_general(ls, &b.k, (const ojphgpu_dwt_desc*)d->dwt_descs.p + b.first, b.count, b.max_w, b.max_h, d->arena.p);
-    else
-      rc = ojphgpu_dwt_inverse(ls, b.rev ? 1 : 0, (const ojphgpu_dwt_desc*)d->dwt_descs.p + b.first, b.count,
-                               b.max_w, b.max_h, d->arena.p);
-    if (rc) return rc;
-    T.end(sp, ls);
-  }
-  if (n_low && !joined && (rc = finish_blocks()) != 0) return rc;
-  if (d->need_convert) {
-    const int sp = T.begin(SP_CONVERT, s);
-    rc = ojphgpu_convert_inverse_ex(s, &P.p, (const ojphgpu_convert_desc*)d->conv_descs.p, d->conv_tiles * d->nframes,
-                                    d->conv_max_w, d->conv_max_h, d_image, d->arena.p, container);
-    if (rc) return rc;
-    T.end(sp, s);
-  }
+  if ((rc = decoder_synthesis(d, d_image, container, n_low, joined, finish_blocks)) != 0) return rc;
   T.finish(s);
   d->ran = true;
+  return OJPHGPU_OK;
+}
+
+static int decoder_synthesis_only(ojphgpu_decoder* d, void* d_image, int container)
+{
+  bool joined = true;
+  return decoder_synthesis(d, d_image, container, 0, joined, [] { return OJPHGPU_OK; });
+}
+
+// A decoder object that only synthesises: the level batches, the conversion and an arena (zeroed, as a decoder's is) of a
+// plan that was not parsed from a codestream -- an encoder's own.  No block decoder, no codestream bytes; whoever owns it
+// fills the sub-band planes of its arena and calls decoder_synthesis_only.
+static int decoder_create_synthesis(const ojphgpu_plan* plan, int device, void* stream, ojphgpu_decoder** out)
+{
+  if (!plan || !out) return OJPHGPU_E_INVALID;
+  *out = nullptr;
+  const Plan& P = plan->plan;
+  if (P.has_region || P.skip_read || P.skip_recon) return OJPHGPU_E_INVALID;
+  HIPCHK(hipSetDevice(device));
+  ojphgpu_decoder* d = new (std::nothrow) ojphgpu_decoder();
+  if (!d) return OJPHGPU_E_NOMEM;
+  struct Owner { ojphgpu_decoder* p; ~Owner() { if (p) ojphgpu_decoder_destroy(p); } } owner{ d };
+  d->P = &P; d->device = device; d->stream = (hipStream_t)stream;
+  d->tiles = TileRange{ 0, (uint32_t)P.tiles.size() };
+  const TileRange tr = d->tiles;
+  std::vector<ojphgpu_dwt_desc> dd, idd;
+  build_level_batches(P, tr, dd, d->batches);
+  build_image_level_descs(P, tr, dd, d->batches, idd);
+  std::reverse(d->batches.begin(), d->batches.end());                 // synthesis: lowest resolution first
+  std::vector<ojphgpu_convert_desc> cd; d->need_convert = build_convert_descs(P, tr, cd, d->conv_max_w, d->conv_max_h);
+  d->conv_tiles = d->tiles_touched = tr.count;
+  if (d->arena.alloc(P.arena_elems * 4) || d->dwt_descs.alloc(dd.size() * sizeof(dd[0])) || d->img_descs.alloc(idd.size() * sizeof(dd[0])) ||
+      d->conv_descs.alloc(cd.size() * sizeof(cd[0])))
+    return OJPHGPU_E_NOMEM;
+  HIPCHK(hipMemset(d->arena.p, 0, P.arena_elems * 4));
+  if (!dd.empty()) HIPCHK(hipMemcpy(d->dwt_descs.p, dd.data(), dd.size() * sizeof(dd[0]), hipMemcpyHostToDevice));
+  if (!idd.empty()) HIPCHK(hipMemcpy(d->img_descs.p, idd.data(), idd.size() * sizeof(idd[0]), hipMemcpyHostToDevice));
+  if (!cd.empty()) HIPCHK(hipMemcpy(d->conv_descs.p, cd.data(), cd.size() * sizeof(cd[0]), hipMemcpyHostToDevice));
+  d->timer.detail = false;                                  // (no spans: nobody reads this object's timing)
+  owner.p = nullptr;
+  *out = d;
   return OJPHGPU_OK;
 }
 

@@ -471,6 +471,24 @@ struct EncoderRate {
   }
 };
 
+// What an encoder with a quality target keeps on top of that (section 5c; made by the first ojphgpu_encoder_set_quality).
+// The final coding of j* goes through the byte budget's trial machinery, so such an encoder has an EncoderRate as well.
+struct ojphgpu_decoder;
+struct EncoderQuality {
+  ojphgpu_decoder* syn = nullptr;                  // synthesis-only decoder made from the encoder's plan; its arena is the second arena
+  DeviceBuf recon, descs, comps, err;              // the reconstructed frame, the requantise / component descriptors, the trial's figures
+  std::vector<uint32_t> desc_band;                 // band of the plan behind each requantise descriptor (the non-empty ones)
+  std::vector<ojphgpu_requant_desc> h_descs;
+  uint32_t max_w = 0, max_h = 0;
+  const void* frame = nullptr; int container = 0;  // the caller's frame of the last run: the search compares against it
+  std::vector<ojphgpu_frame_err> h_err, best;      // per component: of the last trial, of j*
+  std::vector<std::vector<ojphgpu_frame_err>> by_index;   // the figures of every index tried in this search
+  bool have_info = false;
+  ojphgpu_quality_info info;
+  double search_ms = 0, wait_ms = 0, final_ms = 0;
+  ~EncoderQuality();
+};
+
 struct ojphgpu_encoder {
   const ojphgpu_plan* handle = nullptr;
   const Plan* P = nullptr;
@@ -510,6 +528,10 @@ struct ojphgpu_encoder {
   size_t counters_bytes = 16;
   uint64_t max_bytes = 0;                          // != 0: every frame is coded to this budget
   EncoderRate* rate = nullptr;
+  bool quality_on = false; uint64_t max_sse = 0;   // every frame is coded to this quality target (never together with a budget)
+  EncoderQuality* quality = nullptr;
+  // the blocks are coded by a search in ojphgpu_encoder_finish*, and Tier-2 writes from the search's plan
+  bool searches() const { return max_bytes != 0 || quality_on; }
 };
 // Where one trial of the budget search writes, and how its block lengths reach the host.  h_results != null: d_results is the
 // device address of that mapped pinned memory, the coder's records land in it, the two status words of d_counters are
@@ -611,6 +633,11 @@ int  ojphgpu_same_frame_geometry(const Plan& P, const Plan& Q, bool compare_bloc
 void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<uint32_t>& ids, uint64_t arena_off,
                                 uint64_t data_base, ojphgpu_cb_desc* bd, DecFrameInfo& fi);
 int  ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int container);
+inline EncoderQuality::~EncoderQuality()
+{
+  for (DeviceBuf* b : { &recon, &descs, &comps, &err }) b->release();
+  if (syn) ojphgpu_decoder_destroy(syn);
+}
 // after a run has completed, with the status bytes + the RETRY word behind them on the host (nblocks bytes, then the word at
 // the next multiple of 4): did the fused launch of that run (epoch) ask for a repeat?
 inline bool ojphgpu_fused_retry_wanted(const uint8_t* h_status, uint32_t nblocks, uint32_t epoch)

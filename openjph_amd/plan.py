@@ -358,6 +358,42 @@ def rate_search(plan: Plan, hist, max_bytes, size_fn, hint=None):
     return out
 
 
+def quality_search(max_sse, sse_fn):
+    """ojphgpu_quality_search: sse_fn(j) -> SSE of the frame at grid index j (a negative value: an error code).  -> dict(
+    grid_index, qstep, sse, sse_coarser, pae, passes, bytes); capi.OjphError with .code == capi.E_QUALITY (and .info = the dict)
+    when not even index 240 meets max_sse."""
+    info = capi.QualityInfo()
+
+    def fn(user, j, out):
+        v = int(sse_fn(int(j)))
+        if v < 0:
+            return v
+        out[0] = v
+        return 0
+    cb = capi.SSE_FN(fn)
+    if not 0 <= int(max_sse) < 2 ** 64:
+        raise ValueError("max_sse must fit 64 bits")
+    rc = capi.lib().ojphgpu_quality_search(int(max_sse), cb, None, C.byref(info))
+    out = {k: getattr(info, k) for k, _ in capi.QualityInfo._fields_}
+    if rc != capi.OK:
+        err = capi.OjphError(rc, "quality_search")
+        err.info = out
+        raise err
+    return out
+
+
+def psnr_to_sse(plan: Plan, db):
+    """the max_sse of a PSNR over the whole frame: int(n peak^2 / 10^(dB / 10)) with n = the samples of all components and
+    peak = 2^bit_depth - 1.  ValueError when the components differ in depth (a frame then has no one peak)."""
+    nc = int(plan.params.num_comps)
+    depths = {plan.comp_format(c)[0] for c in range(nc)}
+    if len(depths) != 1:
+        raise ValueError("psnr_to_sse: the components differ in bit depth (%s)" % sorted(depths))
+    peak = (1 << depths.pop()) - 1
+    n = sum(plan.comp_info(c)["w"] * plan.comp_info(c)["h"] for c in range(nc))
+    return int(n * peak * peak / 10 ** (db / 10))
+
+
 def rate_predict(plan: Plan, hist):
     """the model of ojphgpu_rate_search alone: predicted bytes at every grid index (float64 [241])"""
     h = np.ascontiguousarray(hist, dtype=np.uint32)
