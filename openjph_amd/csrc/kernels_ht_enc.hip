@@ -32,6 +32,8 @@
 //   * the block's bytes are staged in LDS (MagSgn growing up, VLC growing down); a stage that fills up flushes its whole
 //     dwords to the block's scratch slot in HBM and goes on; when the three lengths are known the block takes its place in
 //     the compacted output with one atomicAdd -- on the cursor of one of 16 regions, not on one cursor for all (claim_output);
+//   * the memory round trips around the step loop have company: the first step's rows are requested before the workgroup's
+//     table copy and barrier, the atomicAdd goes out before the staged bytes are closed up and is read at the first store;
 //   * launches whose blocks are all at most 32 columns wide (the IMF profile's 32x32) use a layout of 8 quad pairs x 8
 //     quad rows per step instead of 16 x 4 (template parameter LOGP).
 // The produced bytes are identical to the reference's (oracle/ht_oracle.c is the CPU model and is pinned against the
@@ -160,20 +162,37 @@ __device__ __forceinline__ void mel_one(MelState& m, uint8_t* buf, int lane)
 // it waiting in that queue (measured with the allocation taken out).  With `nreg` regions (a power of two) block bi
 // allocates in region bi % nreg: regions[2r] = first byte, regions[2r + 1] = bytes, its cursor in a cache line of its
 // own at cursor[32 r].  nreg = 0: the single cursor of the C ABI entry point.
-__device__ __forceinline__ uint32_t claim_output(uint32_t* cursor, const uint32_t* regions, uint32_t nreg, uint32_t bi,
-                                                 uint32_t bytes, uint32_t out_cap, int lane)
+// In two halves, so that a caller can work while the atomic is on its way: claim_request issues it and returns what it
+// came back with in lane 0's register, UNREAD; claim_offset reads that register -- the wait for the atomic lands there.
+struct Claim { uint32_t raw, base, cap; };
+__device__ __forceinline__ Claim claim_request(uint32_t* cursor, const uint32_t* regions, uint32_t nreg, uint32_t bi,
+                                               uint32_t bytes, uint32_t out_cap, int lane)
 {
-  uint32_t base = 0, cap = out_cap;
+  Claim c = { 0, 0, out_cap };
   uint32_t* cur = cursor;
   if (nreg) {
     const uint32_t r = bi & (nreg - 1u);
-    base = regions[2u * r]; cap = regions[2u * r + 1u];
+    c.base = regions[2u * r]; c.cap = regions[2u * r + 1u];
     cur = cursor + 32u * r;
   }
-  uint32_t off = 0;
-  if (lane == 0) off = atomicAdd(cur, bytes);
-  off = rdfirst(off);
-  return (off > cap || bytes > cap - off) ? 0xFFFFFFFFu : base + off;
+  if (lane == 0) {
+    // (an address the compiler cannot prove wave-uniform: for a uniform one it rewrites the atomic as a loop over the active
+    // lanes with the read-back of the result right behind it -- the wait this split is there to move)
+    uint32_t z = 0;
+    asm volatile("" : "+v"(z));
+    c.raw = atomicAdd(cur + z, bytes);
+  }
+  return c;
+}
+__device__ __forceinline__ uint32_t claim_offset(const Claim& c, uint32_t bytes)
+{
+  const uint32_t off = rdfirst(c.raw);
+  return (off > c.cap || bytes > c.cap - off) ? 0xFFFFFFFFu : c.base + off;
+}
+__device__ __forceinline__ uint32_t claim_output(uint32_t* cursor, const uint32_t* regions, uint32_t nreg, uint32_t bi,
+                                                 uint32_t bytes, uint32_t out_cap, int lane)
+{
+  return claim_offset(claim_request(cursor, regions, nreg, bi, bytes, out_cap, lane), bytes);
 }
 
 // S64: the blocks of components on the 64-bit sample path (ojph_encode_codeblock64, ojph_block_encoder.cpp:1026-1520; the
@@ -689,27 +708,36 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   __shared__ __attribute__((aligned(16))) uint16_t s_vlc[2][2048];
   __shared__ uint32_t s_uvlc[64];                   // U-VLC codewords of u = 0..63 (u <= 31 here), see uvlc_word
   __shared__ NarrowLds s_wave[NWAVES];
-  // (16 bytes per lane and turn.  A workgroup lives for 12-40 us and meets at the barrier below before anything else: with
-  // 2-byte turns, sixteen of them, the 8K frame's encode was 0.458 ms instead of 0.440, 32 x 32 blocks 0.603 instead of 0.562)
-  for (int i = threadIdx.x; i < 2 * 2048 / 8; i += blockDim.x)
-    reinterpret_cast<uint4*>(&s_vlc[0][0])[i] = reinterpret_cast<const uint4*>(&ojphgpu::g_enc_vlc[0][0])[i];
-  if (threadIdx.x < 64) s_uvlc[threadIdx.x] = uvlc_word(threadIdx.x);
-  __syncthreads();
-
+  // Entry order: the wavefront's descriptor, the addresses of its first step's rows and the REQUEST for those rows come
+  // first; the table copy, the LDS clears and the workgroup's barrier run while that request -- the block's first HBM access
+  // -- is in flight.  (With the table copy and the barrier in front, a block's start was three dependent round trips with
+  // nothing beside them: table, descriptor, first rows.)  Every wavefront of the workgroup reaches the barrier; one with
+  // nothing to code (`mine` false: an index beyond n, a block of another instantiation or of the wide kernel, an empty
+  // block) forms no address from its descriptor -- the clamps of load_rows underflow for an empty block -- and leaves
+  // behind the barrier.
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform, and the compiler knows it
   const uint32_t bi = blockIdx.x * NWAVES + wave;
-  if (bi >= n) return;
-  const ojphgpu_cb_desc d = blocks[bi];
+  // (read as whole dwords: they are scalar loads, all issued at once; the byte fields read one by one were vector loads
+  // counted with the sample loads, and the first use of K_max waited for those)
+  struct DescWords { uint32_t v[sizeof(ojphgpu_cb_desc) / 4]; } dw;
+  __builtin_memcpy(&dw, blocks + min(bi, n - 1u), sizeof dw);             // (n > 0: ht_encode_launch)
+  ojphgpu_cb_desc d;
+  __builtin_memcpy(&d, &dw, sizeof d);
+  static_assert(offsetof(ojphgpu_cb_desc, K_max) == 16 && offsetof(ojphgpu_cb_desc, reversible) == 17, "K_max, reversible: bytes 0, 1 of dword 4");
+  uint32_t kr = dw.v[4];
+  asm volatile("" : "+s"(kr));                                            // (the dword as a whole, in a scalar register)
+  const uint32_t d_K_max = kr & 0xFFu, d_reversible = (kr >> 8) & 0xFFu;
   const uint32_t W = d.w, H = d.h;
   constexpr uint32_t PPR = 1u << LOGP, RPS = 64u >> LOGP;                 // quad pairs per row of a step, quad rows per step
   // LOGP 5 (32 pairs by 2 quad rows): the blocks of 65..128 columns of a launch none of whose blocks is wider (128 x 32)
   const bool my_width = LOGP == 5 ? (W > NARROW_MAX_W && W <= 4u * PPR) : (W <= NARROW_MAX_W && W <= 4u * PPR);
-  if (!my_width || ((d.reversible & 1u) != 0) != REV || (d.reversible & 4u) != 0) return;   // ht_encode_wide_kernel's, or another instantiation's
-  if (W == 0 || H == 0) { if (lane == 0) { results[bi].offset = 0; results[bi].length = 0; } return; }
+  // (false: ht_encode_wide_kernel's, or another instantiation's)
+  const bool my_kind = bi < n && my_width && ((d_reversible & 1u) != 0) == REV && (d_reversible & 4u) == 0;
+  const bool mine = my_kind && W != 0 && H != 0;
   NarrowLds& L = s_wave[wave];
   uint8_t* outb = reinterpret_cast<uint8_t*>(L.out);
-  const uint32_t K = d.K_max, p = 31u - K;      // missing_msbs = K_max - 1, p = 30 - missing_msbs
+  const uint32_t K = d_K_max, p = 31u - K;      // missing_msbs = K_max - 1, p = 30 - missing_msbs
   constexpr bool rev = REV;
   const float delta_inv = rev ? 0.0f : __fdiv_rn(1.0f, d.delta);         // ojph_codeblock.cpp:98
   const uint32_t* src = coef + d.coef_off;
@@ -719,12 +747,59 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   const uint32_t QW = (W + 1) >> 1, QH = (H + 1) >> 1, PW = (QW + 1) >> 1;
   const uint32_t nsteps = (QH + RPS - 1u) / RPS;
 
-  for (int i = lane; i < PMS_WORDS; i += 64) L.ms[i] = 0;
-  for (int i = lane; i < PVLC_WORDS; i += 64) L.vlc[i] = 0;
-  if (lane < (int)MEL_RAW_WORDS) reinterpret_cast<uint32_t*>(L.mel)[lane] = 0;
-  wave_sync();
-  if (lane == 0) { L.vlc[0] = 0xF; outb[OUT_CAP - 1] = 0xFF; }            // vlc_init: head byte, 4 bits already used (:365-375)
-  wave_sync();
+  const uint32_t r = (uint32_t)lane >> LOGP, px = (uint32_t)lane & (PPR - 1u);
+  const bool pxok = px < PW;
+  const uint32_t x0 = 4u * px;
+  const bool has_q1 = pxok && x0 + 2 < W;
+
+  // Samples of one quad row of this lane's pair: top[0..3], bot[0..3].  The loads are UNCONDITIONAL: rows and columns
+  // are clamped into the block, a lane / row / column that does not exist fetches something valid and is masked when
+  // the values are consumed, one step later.  (With a branch per case the two rows of the full-width case were
+  // separated by a wait for everything in flight -- the zero-initialisation of the registers the partial-width case
+  // loads into -- and the wavefront sat out a full memory latency in the middle of every step: SQ_WAIT_ANY 52 %.)
+  // Whether the block is a multiple of four columns wide is wave-uniform: the usual blocks take two 16-byte loads per
+  // lane, the others eight dword loads with clamped columns.
+  const bool w4 = (W & 3u) == 0;
+  auto load_rows = [&](uint32_t qy, uint32_t* top, uint32_t* bot) {
+    const uint32_t qyc = min(qy, QH - 1u);
+    const uint32_t y0 = 2u * qyc, y1 = min(y0 + 1u, H - 1u);
+    const uint32_t* r0 = src + (size_t)y0 * pitch;
+    const uint32_t* r1 = src + (size_t)y1 * pitch;
+    if (ABL & 32) { r0 = coef + (size_t)bi * 4096u + y0 * 64u; r1 = coef + (size_t)bi * 4096u + y1 * 64u; }   // timing experiment: block-contiguous samples
+    if (w4) {
+      const uint32_t xc = min(x0, W - 4u);
+      const U4 a = *reinterpret_cast<const U4*>(r0 + xc);
+      const U4 c = *reinterpret_cast<const U4*>(r1 + xc);
+      top[0] = a.x; top[1] = a.y; top[2] = a.z; top[3] = a.w;
+      bot[0] = c.x; bot[1] = c.y; bot[2] = c.z; bot[3] = c.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { const uint32_t xk = min(x0 + (uint32_t)k, W - 1u); top[k] = r0[xk]; bot[k] = r1[xk]; }
+    }
+  };
+  // The first step's rows.  The branch is wave-uniform, and a wavefront that skips it never reads the registers: nothing
+  // is merged into them, so no wait lands behind the loads.
+  uint32_t ntop[4], nbot[4];
+  if (mine) load_rows(r, ntop, nbot);
+
+  // (16 bytes per lane and turn.  A workgroup lives for 12-40 us and meets at the barrier below before it codes anything: with
+  // 2-byte turns, sixteen of them, the 8K frame's encode was 0.458 ms instead of 0.440, 32 x 32 blocks 0.603 instead of 0.562)
+  for (int i = threadIdx.x; i < 2 * 2048 / 8; i += blockDim.x)
+    reinterpret_cast<uint4*>(&s_vlc[0][0])[i] = reinterpret_cast<const uint4*>(&ojphgpu::g_enc_vlc[0][0])[i];
+  if (threadIdx.x < 64) s_uvlc[threadIdx.x] = uvlc_word(threadIdx.x);
+  if (mine) {
+    for (int i = lane; i < PMS_WORDS; i += 64) L.ms[i] = 0;
+    for (int i = lane; i < PVLC_WORDS; i += 64) L.vlc[i] = 0;
+    if (lane < (int)MEL_RAW_WORDS) reinterpret_cast<uint32_t*>(L.mel)[lane] = 0;
+    wave_sync();
+    if (lane == 0) { L.vlc[0] = 0xF; outb[OUT_CAP - 1] = 0xFF; }          // vlc_init: head byte, 4 bits already used (:365-375)
+    wave_sync();
+  }
+  __syncthreads();
+  if (!mine) {
+    if (my_kind && lane == 0) { results[bi].offset = 0; results[bi].length = 0; }   // an empty block
+    return;
+  }
 
   // wave-uniform stream state
   uint32_t ms_pend = 0, ms_base = 0, ms_k = 0, ms_ff = 0;   // pending bits in L.ms and where they start, bytes written, last byte was 0xFF
@@ -779,37 +854,8 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     return true;
   };
 
-  const uint32_t r = (uint32_t)lane >> LOGP, px = (uint32_t)lane & (PPR - 1u);
-  const bool pxok = px < PW;
-  const uint32_t x0 = 4u * px;
-  const bool has_q1 = pxok && x0 + 2 < W;
   uint32_t last_S = 0;                                   // what the last quad row of the previous step hands to the first one of this step
 
-  // Samples of one quad row of this lane's pair: top[0..3], bot[0..3].  The loads are UNCONDITIONAL: rows and columns
-  // are clamped into the block, a lane / row / column that does not exist fetches something valid and is masked when
-  // the values are consumed, one step later.  (With a branch per case the two rows of the full-width case were
-  // separated by a wait for everything in flight -- the zero-initialisation of the registers the partial-width case
-  // loads into -- and the wavefront sat out a full memory latency in the middle of every step: SQ_WAIT_ANY 52 %.)
-  // Whether the block is a multiple of four columns wide is wave-uniform: the usual blocks take two 16-byte loads per
-  // lane, the others eight dword loads with clamped columns.
-  const bool w4 = (W & 3u) == 0;
-  auto load_rows = [&](uint32_t qy, uint32_t* top, uint32_t* bot) {
-    const uint32_t qyc = min(qy, QH - 1u);
-    const uint32_t y0 = 2u * qyc, y1 = min(y0 + 1u, H - 1u);
-    const uint32_t* r0 = src + (size_t)y0 * pitch;
-    const uint32_t* r1 = src + (size_t)y1 * pitch;
-    if (ABL & 32) { r0 = coef + (size_t)bi * 4096u + y0 * 64u; r1 = coef + (size_t)bi * 4096u + y1 * 64u; }   // timing experiment: block-contiguous samples
-    if (w4) {
-      const uint32_t xc = min(x0, W - 4u);
-      const U4 a = *reinterpret_cast<const U4*>(r0 + xc);
-      const U4 c = *reinterpret_cast<const U4*>(r1 + xc);
-      top[0] = a.x; top[1] = a.y; top[2] = a.z; top[3] = a.w;
-      bot[0] = c.x; bot[1] = c.y; bot[2] = c.z; bot[3] = c.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { const uint32_t xk = min(x0 + (uint32_t)k, W - 1u); top[k] = r0[xk]; bot[k] = r1[xk]; }
-    }
-  };
   // Stuffs whole 256-byte windows of the MagSgn bit buffer ("after 0xFF only 7 bits", :471-491): a lane
   // takes four consecutive bytes, speculating that none of the window's bytes is 0xFF; the window is cut
   // behind the first 0xFF (the byte after it carries 7 bits and shifts everything that follows) and the
@@ -987,8 +1033,8 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     const uint32_t t = dpp_next(v); return px == PPR - 1u ? 0u : t;
   };
 
-  uint32_t ntop[4], nbot[4];
-  load_rows(r, ntop, nbot);
+  // the first step's rows, requested at the kernel's entry, stay in the registers they arrived in until the quantise below
+  asm volatile("" :: "v"(ntop[0]), "v"(ntop[1]), "v"(ntop[2]), "v"(ntop[3]), "v"(nbot[0]), "v"(nbot[1]), "v"(nbot[2]), "v"(nbot[3]));
   for (uint32_t step = 0; step < nsteps && !err; ++step) {
     const uint32_t qy = RPS * step + r;
     const bool active = pxok && qy < QH;
@@ -1351,39 +1397,48 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   __threadfence_block();
 
   // ---- claim a 4-byte aligned slot in the compacted output: MagSgn | MEL | VLC (:1003-1014) ----
-  uint32_t off = 0;
+  // The atomic goes out as soon as the length is known; what does not need the offset -- closing the gap between the
+  // stage's MagSgn bytes and the MEL / VLC bytes, the two Scup bytes -- is done while it is on its way, and the offset is
+  // read at the first store that needs it.  (A claim that then fails has cost some moves inside LDS.)
   if (err) total = 0;
+  const uint32_t slot = (total + 3u) & ~3u;
+  Claim claim = { 0, 0, 0 };
+  if (total) claim = claim_request(cursor, regions, nreg, bi, slot, out_cap, lane);
+  const uint32_t scup = mel.pos + v_pos;
+  const uint32_t tail = mel.pos + v_pos;
+  const uint32_t gpart = min(ms_out, ms_len), local = ms_len - gpart;   // MagSgn bytes in the scratch slot / still in the stage
+  const bool packed = (gpart & 3u) == 0 && local + tail <= OUT_CAP;     // (ms_out is a multiple of 4; ms_len < ms_out only when a final 0xFF was dropped)
+  if (total && packed) {
+    // close the gap: MEL and VLC bytes move down behind the MagSgn bytes of the stage (destination <= source)
+    for (uint32_t base = 0; base < tail; base += 64) {
+      const uint32_t i = base + lane;
+      uint32_t b = 0;
+      if (i < mel.pos) b = L.mel[i];
+      else if (i < tail) b = outb[OUT_CAP - v_pos + (i - mel.pos)];
+      wave_sync();
+      if (i < tail) {
+        if (i == tail - 1) b = scup >> 4;
+        else if (i == tail - 2) b = (b & 0xF0u) | (scup & 0xFu);
+        outb[local + i] = (uint8_t)b;
+      }
+      wave_sync();
+    }
+  }
+  uint32_t off = 0;
   if (total) {
-    off = claim_output(cursor, regions, nreg, bi, (total + 3u) & ~3u, out_cap, lane);
+    off = claim_offset(claim, slot);
     if (off == 0xFFFFFFFFu) { err = 1; total = 0; off = 0; }
   }
   if (total) {
-    const uint32_t scup = mel.pos + v_pos;
-    const uint32_t tail = mel.pos + v_pos;
-    const uint32_t gpart = min(ms_out, ms_len), local = ms_len - gpart;   // MagSgn bytes in the scratch slot / still in the stage
     uint8_t* dst = out + off;
-    if (gpart) {                                          // (ms_out is a multiple of 4; ms_len < ms_out only when a final 0xFF was dropped)
+    if (gpart) {
       const uint32_t nwd = gpart >> 2;
       const uint32_t* s32 = reinterpret_cast<const uint32_t*>(ms_spill);
       uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);
       for (uint32_t i = lane; i < nwd; i += 64) d32[i] = s32[i];
       if ((uint32_t)lane < (gpart & 3u)) dst[4u * nwd + lane] = ms_spill[4u * nwd + lane];
     }
-    if ((gpart & 3u) == 0 && local + tail <= OUT_CAP) {
-      // close the gap: MEL and VLC bytes move down behind the MagSgn bytes of the stage (destination <= source)
-      for (uint32_t base = 0; base < tail; base += 64) {
-        const uint32_t i = base + lane;
-        uint32_t b = 0;
-        if (i < mel.pos) b = L.mel[i];
-        else if (i < tail) b = outb[OUT_CAP - v_pos + (i - mel.pos)];
-        wave_sync();
-        if (i < tail) {
-          if (i == tail - 1) b = scup >> 4;
-          else if (i == tail - 2) b = (b & 0xF0u) | (scup & 0xFu);
-          outb[local + i] = (uint8_t)b;
-        }
-        wave_sync();
-      }
+    if (packed) {
       uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + gpart);
       const uint32_t nw = (local + tail + 3u) >> 2;
       for (uint32_t i = lane; i < nw; i += 64) d32[i] = L.out[i];
