@@ -725,7 +725,8 @@ int  ojphgpu_encoder_rate_timing(ojphgpu_encoder* enc, float out[4]);
  *    parameters of j: ojphgpu_band_requantise writes the planes the decoder would hold into a second arena, the decoder's
  *    own synthesis launches (a synthesis-only decoder object made from the encoder's plan) turn them into an int32 frame, and
  *    ojphgpu_frame_error_ex compares it with the caller's: 16 bytes per component come to the host.  j* is then block-coded
- *    once.  Not available in the frame pipelines, for batches, tile ranges or the multi-GPU encoder.
+ *    once.  In a frame pipeline: ojphgpu_enc_pipe_set_quality (section 6).  Not available for batches, tile ranges or the
+ *    multi-GPU encoder.
  * ------------------------------------------------------------------------------------------ */
 typedef int64_t (*ojphgpu_sse_fn)(void* user, uint32_t grid_index, uint64_t* sse);   /* 0 and *sse = SSE(j); < 0 = error */
 typedef struct ojphgpu_quality_info {
@@ -739,6 +740,18 @@ typedef struct ojphgpu_quality_info {
  * == 1, which is the certificate.  passes <= 10 and no index is asked twice, whatever fn returns.  A negative value of fn
  * is returned as it is. */
 int  ojphgpu_quality_search(uint64_t max_sse, ojphgpu_sse_fn fn, void* user, ojphgpu_quality_info* out);
+/* The same search started from a guess, for the frames of a sequence (hint = the previous frame's j*).  It keeps an index
+ * measured to fail (lo; none at first) and one measured to meet (hi; none at first) and assumes nothing between two measured
+ * indices.  The first trial is `hint`; then up to two neighbours on the side its result points to -- hint - 1, hint - 2
+ * while they still meet, hint + 1, hint + 2 while they still fail -- stopping at the first that turns round, which is the
+ * certificate.  While nothing has met, the next trial is 240 (OJPHGPU_E_QUALITY only on a measured SSE(240) > max_sse);
+ * while nothing has failed and hi > 0, it is 0 (met: the answer); then (lo, hi) is halved until hi - lo == 1.  So an
+ * unchanged answer costs the two trials of its certificate (one at index 0), passes <= 12 = 3 + 1 + ceil(log2(238)), and
+ * no index is asked twice.  *first_guess = the first index tried.  hint = -1: no hint, the indices of ojphgpu_quality_search
+ * in its order; any other value outside 0 .. OJPHGPU_RATE_GRID - 1: OJPHGPU_E_INVALID.  A negative value of fn is returned
+ * as it is. */
+int  ojphgpu_quality_search_hint(uint64_t max_sse, int32_t hint, ojphgpu_sse_fn fn, void* user, ojphgpu_quality_info* out,
+                                 uint32_t* first_guess);
 
 /* The encoder codes every following frame to max_sse (0 is a target like any other: the finest step at which nothing is
  * lost may exist); ojphgpu_encoder_clear_quality switches the mode off.  With a target, ojphgpu_encoder_run_device*
@@ -819,6 +832,29 @@ int  ojphgpu_enc_pipe_set_budget(ojphgpu_enc_pipe* pipe, uint64_t max_bytes);
 /* what the search of the frame collected last found (after OJPHGPU_E_BUDGET: passes and first_guess); OJPHGPU_E_INVALID
  * before the first _collect of a budgeted pipe and after a frame that failed otherwise */
 int  ojphgpu_enc_pipe_rate_info(ojphgpu_enc_pipe* pipe, ojphgpu_rate_info* info);
+
+/* Every frame of this pipe is coded to a quality target (section 5c): each collected codestream is, byte for byte, the
+ * plain encode of its frame at qstep(j*), with the certificate SSE(j*) <= max_sse and (j* == 0 or SSE(j* - 1) > max_sse)
+ * measured for that frame.  The rules are the budget's: switched on by the first call before the first _acquire -- 0 is a
+ * target, so the call itself is the switch, not its value -- and from then on the call may be repeated between frames; the
+ * value in force at _submit is that frame's target; there is no way back.  OJPHGPU_E_INVALID: whatever
+ * ojphgpu_encoder_set_quality refuses; switching on after the first _acquire; a pipe with a byte budget (and _set_budget on
+ * a pipe with a target: the two do not combine yet).  The first call re-sizes every slot's output buffer for the finest
+ * step of the grid and allocates what ojphgpu_encoder_set_quality allocates; should it fail later than its refusals, the
+ * pipe answers as ojphgpu_enc_pipe_set_budget describes.  The search of a frame starts from the j* of the last certified
+ * frame (ojphgpu_quality_search_hint), runs on the pipe's compute stream in frame order and compares against the slot's own
+ * copy of the frame -- the planes in container_bits-bit elements, after the unpacking of _set_pixels / _set_packed -- so the
+ * caller keeps nothing valid; the decoded side stays int32 (a sample one past an 8-bit container's range counts as it is).
+ * A frame whose answer is its predecessor's costs the two trials of the certificate (one at index 0) and the one coding of
+ * its blocks.  A frame whose target not even index 240 meets: its _collect returns OJPHGPU_E_QUALITY, its slot is free
+ * again, the hint stays where it was and the frames around it are not affected.  A pipe that never had a target issues
+ * what it issued without this call. */
+int  ojphgpu_enc_pipe_set_quality(ojphgpu_enc_pipe* pipe, uint64_t max_sse);
+/* what the search of the frame collected last found, and the first index it tried (after OJPHGPU_E_QUALITY: passes and
+ * first_guess); OJPHGPU_E_INVALID before the first _collect of such a pipe and after a frame that failed otherwise */
+int  ojphgpu_enc_pipe_quality_info(ojphgpu_enc_pipe* pipe, ojphgpu_quality_info* info, uint32_t* first_guess);
+/* SSE and PAE of component `comp` of that frame at j* (OJPHGPU_E_INVALID when it was not certified) */
+int  ojphgpu_enc_pipe_quality_comp(ojphgpu_enc_pipe* pipe, uint32_t comp, uint64_t* sse, uint32_t* pae);
 
 /* the first codestream of the sequence fixes the frame geometry (it is only parsed, not decoded); every
  * submitted codestream must describe the same frame format and code-block grid (quantisation may differ) */

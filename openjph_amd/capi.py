@@ -342,6 +342,10 @@ SIGNATURES = {
     "ojphgpu_frame_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ojphgpu_frame_error_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ojphgpu_quality_search": (C.c_int, [C.c_uint64, SSE_FN, C.c_void_p, C.POINTER(QualityInfo)]),
+    "ojphgpu_quality_search_hint": (C.c_int, [C.c_uint64, C.c_int32, SSE_FN, C.c_void_p, C.POINTER(QualityInfo), C.POINTER(C.c_uint32)]),
+    "ojphgpu_enc_pipe_set_quality": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_enc_pipe_quality_info": (C.c_int, [C.c_void_p, C.POINTER(QualityInfo), C.POINTER(C.c_uint32)]),
+    "ojphgpu_enc_pipe_quality_comp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ojphgpu_encoder_set_quality": (C.c_int, [C.c_void_p, C.c_uint64]),
     "ojphgpu_encoder_clear_quality": (C.c_int, [C.c_void_p]),
     "ojphgpu_encoder_quality_info": (C.c_int, [C.c_void_p, C.POINTER(QualityInfo)]),

@@ -239,6 +239,54 @@ extern "C" int ojphgpu_quality_search(uint64_t max_sse, ojphgpu_sse_fn fn, void*
   return OJPHGPU_OK;
 }
 
+// The same search started from a guess, for the frames of a sequence (hint = the j* of the last certified frame).  lo = an
+// index measured to fail (-1: none yet), hi = one measured to meet (241: none yet); hi - lo == 1 is the certificate, with lo
+// == -1 standing for "j* == 0".  The hint first, then up to two neighbours on the side its result points to -- downwards
+// while they still meet, upwards while they still fail -- and the first that turns round completes the certificate.  What
+// is still open afterwards has one measured side: the probe of the other end (240, then 0, as the plain search asks them)
+// and halving.  Nothing is assumed between two measured indices.  3 + 1 + ceil(log2(238)) = 12 trials at most, each
+// strictly inside (lo, hi): none twice.
+extern "C" int ojphgpu_quality_search_hint(uint64_t max_sse, int32_t hint, ojphgpu_sse_fn fn, void* user, ojphgpu_quality_info* out,
+                                           uint32_t* first_guess)
+{
+  const int N = OJPHGPU_RATE_GRID;
+  if (!fn || !out || !first_guess || hint < -1 || hint >= N) return OJPHGPU_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  *first_guess = 0;
+  int lo = -1, hi = N;
+  uint64_t sse_lo = 0, sse_hi = 0;
+  int64_t err = 0;
+  auto trial = [&](int j) -> bool {                          // false: fn failed, err holds its value
+    if (out->passes == 0) *first_guess = (uint32_t)j;
+    uint64_t s = 0;
+    err = fn(user, (uint32_t)j, &s);
+    out->passes++;
+    if (err < 0) return false;
+    if (s <= max_sse) { hi = j; sse_hi = s; } else { lo = j; sse_lo = s; }
+    return true;
+  };
+  auto fail = [&]() -> int { return err < INT32_MIN ? OJPHGPU_E_INVALID : (int)err; };
+  if (hint >= 0) {
+    if (!trial(hint)) return fail();
+    const int dir = hi == hint ? -1 : 1;                     // it meets: a coarser step may, too; it fails: a finer one is needed
+    for (int k = 1; k <= 2 && hi - lo > 1; ++k) {
+      const int nb = hint + k * dir;
+      if (nb <= lo || nb >= hi) break;                       // (off the grid)
+      if (!trial(nb)) return fail();
+    }
+  }
+  if (hi == N) {                                             // nothing meets so far: the finest step must
+    if (lo < N - 1 && !trial(N - 1)) return fail();
+    if (hi == N) return OJPHGPU_E_QUALITY;                   // SSE(240) > max_sse, measured
+  }
+  if (lo < 0 && hi > 0 && !trial(0)) return fail();          // nothing fails so far: the coarsest step may meet
+  while (hi - lo > 1)
+    if (!trial((lo + hi) / 2)) return fail();
+  out->grid_index = (uint32_t)hi; out->qstep = rate_grid_qstep((uint32_t)hi);
+  out->sse = sse_hi; out->sse_coarser = hi ? sse_lo : 0;
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out)
 {
   if (!plan || !hist || !out) return OJPHGPU_E_INVALID;

@@ -470,6 +470,7 @@ extern "C" int ojphgpu_encoder_finish_tiles(ojphgpu_encoder* e, uint8_t* h_out, 
 namespace ojphgpu {
 int assemble_launch(void* stream, const T2Job* d_jobs, uint32_t njobs, const uint8_t* d_blob, const uint8_t* d_data, uint8_t* d_out);
 int publish_words_launch(void* stream, uint32_t* d_dst, const uint32_t* src, uint32_t n);
+int copy_to_host_launch(void* stream, void* d_dst, const void* src, size_t bytes);
 }
 
 // The tile-parts of the range assembled in HBM (kernels_assemble.hip) instead of on the host: only the block
@@ -750,10 +751,11 @@ extern "C" int ojphgpu_encoder_set_quality(ojphgpu_encoder* e, uint64_t max_sse)
 
 // One trial of the search: SSE(j) of the frame of the last run.  The planes of the arena, requantised with the band
 // parameters of j into the synthesis decoder's arena, go through the decoder's synthesis launches into the reconstructed
-// frame (int32); the error sums against the caller's frame, in its own container, come to the host.  No block is coded.
-static int64_t encoder_quality_trial(void* user, uint32_t j, uint64_t* sse)
+// frame (int32); the error sums against the frame `io` names, in its own container, come to the host: comps[component].
+// No block is coded.  The descriptors and the sums travel the way `io` says: through mapped pinned memory and an event (a
+// frame pipeline), or by copies from and into the encoder's pageable tables.
+int ojphgpu_encoder_quality_trial(ojphgpu_encoder* e, const QualityTrialIo& io, uint32_t j, ojphgpu_frame_err* comps)
 {
-  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
   EncoderRate& R = *e->rate; EncoderQuality& Q = *e->quality;
   hipStream_t s = e->stream;
   auto hip = [](hipError_t x) { return x == hipSuccess; };
@@ -763,17 +765,36 @@ static int64_t encoder_quality_trial(void* user, uint32_t j, uint64_t* sse)
     Q.h_descs[i].delta = q.delta; Q.h_descs[i].delta_inv = 1.0f / q.delta; Q.h_descs[i].K_max = q.K_max;   // (as rate_apply_step has them)
   }
   const size_t dbytes = Q.h_descs.size() * sizeof(ojphgpu_requant_desc), ebytes = Q.h_err.size() * sizeof(ojphgpu_frame_err);
-  if (dbytes && !hip(hipMemcpyAsync(Q.descs.p, Q.h_descs.data(), dbytes, hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
-  int rc = ojphgpu_band_requantise(s, (const ojphgpu_requant_desc*)Q.descs.p, (uint32_t)Q.h_descs.size(), Q.max_w, Q.max_h, e->arena.p, Q.syn->arena.p);
+  int rc;
+  if (io.h_descs) {                                         // (the last trial that read them has been waited for)
+    memcpy(io.h_descs, Q.h_descs.data(), dbytes);
+    if ((rc = copy_to_host_launch(s, Q.descs.p, io.d_descs, dbytes)) != 0) return rc;   // the kernel copies either way
+  } else if (dbytes && !hip(hipMemcpyAsync(Q.descs.p, Q.h_descs.data(), dbytes, hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
+  rc = ojphgpu_band_requantise(s, (const ojphgpu_requant_desc*)Q.descs.p, (uint32_t)Q.h_descs.size(), Q.max_w, Q.max_h, e->arena.p, Q.syn->arena.p);
   if (rc) return rc;
   // (int32 whatever the run's container: a sample the reference leaves one past its range must not saturate, fit_container)
   if ((rc = decoder_synthesis_only(Q.syn, Q.recon.p, 32)) != 0) return rc;
   if (!hip(hipMemsetAsync(Q.err.p, 0, ebytes, s))) return OJPHGPU_E_HIP;
-  rc = ojphgpu_frame_error_ex(s, Q.frame, Q.container, Q.recon.p, 32, (const ojphgpu_error_comp*)Q.comps.p, (uint32_t)Q.h_err.size(), (ojphgpu_frame_err*)Q.err.p);
+  rc = ojphgpu_frame_error_ex(s, io.frame, io.container, Q.recon.p, 32, (const ojphgpu_error_comp*)Q.comps.p, (uint32_t)Q.h_err.size(), (ojphgpu_frame_err*)Q.err.p);
   if (rc) return rc;
   const auto w0 = std::chrono::steady_clock::now();
-  if (!hip(hipMemcpyAsync(Q.h_err.data(), Q.err.p, ebytes, hipMemcpyDeviceToHost, s)) || !hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
+  if (io.h_err) {
+    if ((rc = copy_to_host_launch(s, io.d_err, Q.err.p, ebytes)) != 0) return rc;
+    if (!hip(hipEventRecord(io.done, s)) || !hip(hipEventSynchronize(io.done))) return OJPHGPU_E_HIP;
+    memcpy(comps, io.h_err, ebytes);
+  } else if (!hip(hipMemcpyAsync(comps, Q.err.p, ebytes, hipMemcpyDeviceToHost, s)) || !hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
   Q.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  return OJPHGPU_OK;
+}
+
+// ... of a single encoder: against the caller's frame of the last run, through its own tables
+static int64_t encoder_quality_trial(void* user, uint32_t j, uint64_t* sse)
+{
+  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
+  EncoderQuality& Q = *e->quality;
+  const QualityTrialIo own{ Q.frame, Q.container, nullptr, nullptr, nullptr, nullptr, nullptr };
+  const int rc = ojphgpu_encoder_quality_trial(e, own, j, Q.h_err.data());
+  if (rc) return rc;
   uint64_t total = 0;
   for (const ojphgpu_frame_err& c : Q.h_err) total += c.sse;
   Q.by_index[j] = Q.h_err;

@@ -494,8 +494,10 @@ struct ojphgpu_encoder {
   const Plan* P = nullptr;
   int device = 0; hipStream_t stream = nullptr;
   // out / counters are null in the encoder of a frame pipeline with a byte budget: the pipe takes them over as its spare
-  // output set (ojphgpu_enc_pipe_set_budget).  Such an encoder runs only through o_out / o_results / o_counters and
-  // ojphgpu_encoder_rate_trial; _finish, _coded_bytes and the encoder's own search, which read these two, are not for it.
+  // output set (ojphgpu_enc_pipe_set_budget); one with a quality target codes every frame once, into its slot's set, and
+  // releases them (ojphgpu_enc_pipe_set_quality).  Such an encoder runs only through o_out / o_results / o_counters,
+  // ojphgpu_encoder_rate_trial and ojphgpu_encoder_quality_trial; _finish, _coded_bytes and the encoder's own searches,
+  // which read these two, are not for it.
   DeviceBuf arena, image, dwt_descs, img_descs, cb_descs, conv_descs, scratch, out, results, counters;
   bool need_convert = false;                       // some component is not converted inside its top DWT level
   std::vector<LevelBatch> batches;
@@ -542,6 +544,17 @@ struct RateTrialOut {
   const ojphgpu_cb_result* h_results; uint32_t* d_publish; const uint32_t* h_publish; hipEvent_t done;
 };
 int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j);   // size(j), or an error (< 0)
+// What one trial of the quality search compares against, and how its small data travel.  frame / container: the original,
+// on the device.  h_descs != null: mapped pinned memory the requantise descriptors are written into (d_descs: its device
+// address; a copy kernel takes them to the device), the error words (one ojphgpu_frame_err per component) are written to
+// d_err (h_err on the host) by a copy kernel and `done` is recorded behind them and waited for.  Null: copies from and into
+// the encoder's own pageable tables.
+struct QualityTrialIo {
+  const void* frame; int container;
+  ojphgpu_requant_desc* h_descs; const void* d_descs;
+  const ojphgpu_frame_err* h_err; void* d_err; hipEvent_t done;
+};
+int ojphgpu_encoder_quality_trial(ojphgpu_encoder* e, const QualityTrialIo& io, uint32_t j, ojphgpu_frame_err* comps);   // comps[component] = SSE / PAE at j
 // the device part of an encode: d_image holds the frame in `container`-bit elements (32 / 16)
 int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int container);
 

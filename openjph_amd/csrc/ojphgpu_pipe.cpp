@@ -19,7 +19,10 @@
 // An encoder pipe with a byte budget (ojphgpu_enc_pipe_set_budget) searches the quantisation step of every frame: the
 // compute stream then carries, per frame, transform + statistics and the trials of the search, issued by one ordered
 // worker thread -- the pipe has one encoder and one arena, so frame n+1's transform must not be enqueued before frame n's
-// last trial -- while uploads, Tier-2 of the chosen step and copy-outs of the neighbouring frames go on as above.
+// last trial -- while uploads, Tier-2 of the chosen step and copy-outs of the neighbouring frames go on as above.  A quality
+// target (ojphgpu_enc_pipe_set_quality) rides on the same worker: transform, the trials of its search -- requantise, the
+// decoder's synthesis and the error sums against the slot's own copy of the frame, no block coded -- then the blocks of j*,
+// once.
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -138,6 +141,11 @@ struct EncSlot {
   uint64_t budget = 0;
   ojphgpu_plan* rplan = nullptr;
   ojphgpu_rate_info info{}; bool have_info = false;
+  // a pipe with a quality target: the frame's target, what its search found, the first index it tried and the figures of
+  // every component at j* (rplan as above: the plan at qstep(j*))
+  uint64_t target = 0;
+  ojphgpu_quality_info qinfo{}; uint32_t first_guess = 0; bool have_qinfo = false;
+  std::vector<ojphgpu_frame_err> qcomps;
 };
 
 struct ojphgpu_enc_pipe {
@@ -165,15 +173,24 @@ struct ojphgpu_enc_pipe {
   Pinned h_hist;                                    // the band statistics of the frame being searched (the worker's)
   hipEvent_t ev_trial = nullptr;
   int hint = -1;                                    // j* of the last frame that was certified
-  std::deque<uint32_t> rate_work; bool stop_rate = false;
-  std::condition_variable cv_rate;
-  std::thread rate_worker;
   ojphgpu_rate_info last_info{}; bool have_last_info = false;   // of the frame collected last
+  // quality target (ojphgpu_enc_pipe_set_quality): the same rules, never together with a budget
+  bool quality_on = false;
+  uint64_t max_sse = 0;                             // the target the next _submit gives its frame
+  Pinned h_qdescs, h_qerr;                          // a trial's requantise descriptors going out, its error words coming back
+  std::vector<std::vector<ojphgpu_frame_err>> q_by_index;   // the figures of every index the search of the worker's frame tried
+  ojphgpu_quality_info last_qinfo{}; uint32_t last_first_guess = 0; bool have_last_qinfo = false;
+  std::vector<ojphgpu_frame_err> last_qcomps;
+  // the ordered worker of a pipe that searches, whichever search it is: it owns the compute stream
+  bool searching() const { return budget_on || quality_on; }
+  std::deque<uint32_t> search_work; bool stop_search = false;
+  std::condition_variable cv_search;
+  std::thread search_worker;
 };
 
 static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
 {
-  const Plan& P = p->budget_on ? s.rplan->plan : *p->P;      // (a byte budget: the plan at the step the frame's search chose)
+  const Plan& P = p->searching() ? s.rplan->plan : *p->P;    // (a budget, a target: the plan at the step the frame's search chose)
   ojphgpu_encoder* e = p->enc;
   auto fail = [&](int rc) { s.rc = rc; };
   if (hipSetDevice(p->device) != hipSuccess) return fail(OJPHGPU_E_HIP);
@@ -273,19 +290,68 @@ static int enc_rate_frame(ojphgpu_enc_pipe* p, EncSlot& s)
   return OJPHGPU_OK;
 }
 
-static void enc_rate_worker(ojphgpu_enc_pipe* p)
+// ---- quality target: the same worker.  Per frame, on the compute stream: unpack and transform; the search, started from
+// the last certified frame's answer, measures SSE(j) against the slot's image -- the planes in the pipe's container, which
+// the slot owns until _collect -- with the descriptors and the error words in pinned memory; then j* is block-coded, once,
+// into the slot's output set, as a trial of the budget is.
+struct EncQualityCtx { ojphgpu_enc_pipe* p; EncSlot* s; };
+
+static int64_t enc_pipe_quality_trial(void* user, uint32_t j, uint64_t* sse)
+{
+  EncQualityCtx& c = *(EncQualityCtx*)user;
+  ojphgpu_enc_pipe* p = c.p;
+  std::vector<ojphgpu_frame_err>& got = p->q_by_index[j];
+  got.assign(p->P->comps.size(), ojphgpu_frame_err{ 0, 0, 0 });
+  const QualityTrialIo io{ c.s->image.p, p->container, (ojphgpu_requant_desc*)p->h_qdescs.p, p->h_qdescs.d,
+                           (const ojphgpu_frame_err*)p->h_qerr.p, p->h_qerr.d, p->ev_trial };
+  const int rc = ojphgpu_encoder_quality_trial(p->enc, io, j, got.data());
+  if (rc) return rc;
+  uint64_t total = 0;
+  for (const ojphgpu_frame_err& e : got) total += e.sse;
+  *sse = total;
+  return 0;
+}
+
+static int enc_quality_frame(ojphgpu_enc_pipe* p, EncSlot& s)
+{
+  ojphgpu_encoder* e = p->enc;
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
+  int rc = enc_unpack(p, s);
+  if (rc) return rc;
+  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
+  if ((rc = ojphgpu_encoder_run_container(e, s.image.p, p->container)) != 0) return rc;   // conversion + DWT (e->quality_on)
+  EncQualityCtx c{ p, &s };
+  rc = ojphgpu_quality_search_hint(s.target, p->hint, enc_pipe_quality_trial, &c, &s.qinfo, &s.first_guess);
+  s.have_qinfo = rc == OJPHGPU_OK || rc == OJPHGPU_E_QUALITY;
+  if (rc) return rc;
+  s.qcomps = p->q_by_index[s.qinfo.grid_index];
+  for (const ojphgpu_frame_err& k : s.qcomps) s.qinfo.pae = std::max(s.qinfo.pae, k.pae);
+  p->hint = (int)s.qinfo.grid_index;
+  const size_t nb = e->block_ids.size();
+  const RateTrialOut to{ s.o.out.p, (ojphgpu_cb_result*)s.o.h_res.d, (uint32_t*)s.o.counters.p, (const ojphgpu_cb_result*)s.o.h_res.p,
+                         (uint32_t*)(s.o.h_res.d + nb * sizeof(ojphgpu_cb_result)),
+                         (const uint32_t*)(s.o.h_res.p + nb * sizeof(ojphgpu_cb_result)), p->ev_trial };
+  const int64_t size = ojphgpu_encoder_rate_trial(e, s.rplan->plan, to, s.qinfo.grid_index);   // (leaves rplan at qstep(j*))
+  if (size < 0) { s.have_qinfo = false; return size < INT32_MIN ? OJPHGPU_E_INVALID : (int)size; }
+  s.qinfo.bytes = (uint64_t)size;
+  HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
+  return OJPHGPU_OK;
+}
+
+static void enc_search_worker(ojphgpu_enc_pipe* p)
 {
   for (;;) {
     uint32_t si;
     {
       std::unique_lock<std::mutex> lk(p->mu);
-      p->cv_rate.wait(lk, [&] { return p->stop_rate || !p->rate_work.empty(); });
-      if (p->rate_work.empty()) return;
-      si = p->rate_work.front(); p->rate_work.pop_front();
+      p->cv_search.wait(lk, [&] { return p->stop_search || !p->search_work.empty(); });
+      if (p->search_work.empty()) return;
+      si = p->search_work.front(); p->search_work.pop_front();
     }
     EncSlot& s = p->slots[si];
-    const int rc = no_throw([&] { return enc_rate_frame(p, s); });
-    if (rc) {                                        // the frame ends here (OJPHGPU_E_BUDGET among the reasons); see enc_finish_frame
+    const int rc = no_throw([&] { return p->quality_on ? enc_quality_frame(p, s) : enc_rate_frame(p, s); });
+    if (rc) {                                        // the frame ends here (OJPHGPU_E_BUDGET / _E_QUALITY among the reasons); see enc_finish_frame
       hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp);
       std::lock_guard<std::mutex> lk(p->mu);
       s.rc = rc; s.t_done = now_ms(); s.state = DONE;
@@ -324,10 +390,10 @@ extern "C" void ojphgpu_enc_pipe_destroy(ojphgpu_enc_pipe* p)
 {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  if (p->rate_worker.joinable()) {                   // it hands its frames to the finishers: it ends first
-    { std::lock_guard<std::mutex> lk(p->mu); p->stop_rate = true; }
-    p->cv_rate.notify_all();
-    p->rate_worker.join();
+  if (p->search_worker.joinable()) {                 // it hands its frames to the finishers: it ends first
+    { std::lock_guard<std::mutex> lk(p->mu); p->stop_search = true; }
+    p->cv_search.notify_all();
+    p->search_worker.join();
   }
   { std::lock_guard<std::mutex> lk(p->mu); p->stop = true; }
   p->cv_work.notify_all();
@@ -340,7 +406,7 @@ extern "C" void ojphgpu_enc_pipe_destroy(ojphgpu_enc_pipe* p)
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
     delete s.rplan;
   }
-  p->spare.release(); p->h_hist.release();
+  p->spare.release(); p->h_hist.release(); p->h_qdescs.release(); p->h_qerr.release();
   if (p->ev_trial) (void)hipEventDestroy(p->ev_trial);
   for (hipStream_t s : { p->s_h2d, p->s_comp, p->s_d2h }) if (s) (void)hipStreamDestroy(s);
   delete p;
@@ -487,13 +553,14 @@ extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
   s.rc = 0; s.cs_len = 0; s.t_submit = now_ms();
   { const int r0 = upload(p->mode, p->s_h2d, (p->pixel_bits || p->packed_bits) ? s.pixels.p : s.image.p, s.h_in, 0, p->in_bytes); if (r0) return r0; }
   HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
-  if (p->budget_on) {                                // everything on the compute stream is the rate worker's, frame by frame
+  if (p->searching()) {                              // everything on the compute stream is the search worker's, frame by frame
     std::lock_guard<std::mutex> lk(p->mu);
     s.budget = p->max_bytes; s.have_info = false;
+    s.target = p->max_sse; s.have_qinfo = false; s.qcomps.clear();
     s.state = SUBMITTED;
-    p->rate_work.push_back(si);
+    p->search_work.push_back(si);
     p->n_acq++; p->n_sub++;
-    p->cv_rate.notify_one();
+    p->cv_search.notify_one();
     return OJPHGPU_OK;
   }
   HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
@@ -530,6 +597,10 @@ extern "C" int ojphgpu_enc_pipe_collect(ojphgpu_enc_pipe* p, const uint8_t** h_c
   p->cv_done.wait(lk, [&] { return s.state == DONE; });
   p->n_col++;
   if (p->budget_on) { p->last_info = s.info; p->have_last_info = s.have_info; }
+  if (p->quality_on) {
+    p->last_qinfo = s.qinfo; p->last_first_guess = s.first_guess; p->have_last_qinfo = s.have_qinfo;
+    p->last_qcomps = s.qcomps;
+  }
   if (s.rc) { s.state = FREE; return s.rc; }
   s.state = HELD;
   *h_codestream = s.h_cs.p; *len = s.cs_len;
@@ -538,7 +609,7 @@ extern "C" int ojphgpu_enc_pipe_collect(ojphgpu_enc_pipe* p, const uint8_t** h_c
 
 extern "C" int ojphgpu_enc_pipe_set_budget(ojphgpu_enc_pipe* p, uint64_t max_bytes)
 {
-  if (!p || p->dead) return OJPHGPU_E_INVALID;
+  if (!p || p->dead || p->quality_on) return OJPHGPU_E_INVALID;
   if (p->n_acq != 0 || p->slots[0].state != FREE) {  // frames have been handed out: the mode stays, the budget may move
     if (!p->budget_on || max_bytes == 0) return OJPHGPU_E_INVALID;
     p->max_bytes = max_bytes;
@@ -565,7 +636,7 @@ extern "C" int ojphgpu_enc_pipe_set_budget(ojphgpu_enc_pipe* p, uint64_t max_byt
     if (p->spare.h_res.reserve(p->res_bytes + 64)) return OJPHGPU_E_NOMEM;
     if (p->h_hist.reserve(e->rate->h_hist.size() * 4 + 64)) return OJPHGPU_E_NOMEM;
     if (!p->ev_trial) HIPCHK(hipEventCreateWithFlags(&p->ev_trial, hipEventDisableTiming | hipEventReleaseToSystem));
-    p->rate_worker = std::thread(enc_rate_worker, p);
+    p->search_worker = std::thread(enc_search_worker, p);
     p->budget_on = true; p->max_bytes = max_bytes; p->hint = -1;
     guard.p = nullptr;
     return OJPHGPU_OK;
@@ -578,6 +649,62 @@ extern "C" int ojphgpu_enc_pipe_rate_info(ojphgpu_enc_pipe* p, ojphgpu_rate_info
   std::lock_guard<std::mutex> lk(p->mu);
   if (!p->have_last_info) return OJPHGPU_E_INVALID;
   *info = p->last_info;
+  return OJPHGPU_OK;
+}
+
+// The mode is the budget's, with another search: on from before the first _acquire, or never; the target may move between
+// frames; 0 is a target, so the first call is the switch.
+extern "C" int ojphgpu_enc_pipe_set_quality(ojphgpu_enc_pipe* p, uint64_t max_sse)
+{
+  if (!p || p->dead || p->budget_on) return OJPHGPU_E_INVALID;
+  if (p->n_acq != 0 || p->slots[0].state != FREE) {  // frames have been handed out: the mode stays, the target may move
+    if (!p->quality_on) return OJPHGPU_E_INVALID;
+    p->max_sse = max_sse;
+    return OJPHGPU_OK;
+  }
+  if (p->quality_on) { p->max_sse = max_sse; return OJPHGPU_OK; }
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(p->device));
+    ojphgpu_encoder* e = p->enc;
+    // the refusals; scratch and output bound of the finest step, the second arena, the synthesis-only decoder and the
+    // int32 reconstructed frame
+    int rc = ojphgpu_encoder_set_quality(e, max_sse);
+    if (rc) return rc;                                   // (refused: the encoder and the pipe are as they were)
+    struct Guard { ojphgpu_enc_pipe* p; ~Guard() { if (p) p->dead = true; } } guard{ p };   // as in _set_budget
+    // the output sets at that bound, one per slot: a frame's blocks are coded once, so there is no spare, and the
+    // encoder's own set goes
+    for (EncSlot& s : p->slots) {
+      s.o.out.release(); s.o.counters.release();
+      if (s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
+      if (!s.rplan) s.rplan = new ojphgpu_plan{ *p->P };
+    }
+    e->out.release(); e->counters.release();
+    if (p->h_qdescs.reserve(e->quality->h_descs.size() * sizeof(ojphgpu_requant_desc) + 64) ||
+        p->h_qerr.reserve(p->P->comps.size() * sizeof(ojphgpu_frame_err) + 64)) return OJPHGPU_E_NOMEM;
+    p->q_by_index.assign(OJPHGPU_RATE_GRID, {});
+    if (!p->ev_trial) HIPCHK(hipEventCreateWithFlags(&p->ev_trial, hipEventDisableTiming | hipEventReleaseToSystem));
+    p->search_worker = std::thread(enc_search_worker, p);
+    p->quality_on = true; p->max_sse = max_sse; p->hint = -1;
+    guard.p = nullptr;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_enc_pipe_quality_info(ojphgpu_enc_pipe* p, ojphgpu_quality_info* info, uint32_t* first_guess)
+{
+  if (!p || !info || !first_guess) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->have_last_qinfo) return OJPHGPU_E_INVALID;
+  *info = p->last_qinfo; *first_guess = p->last_first_guess;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_enc_pipe_quality_comp(ojphgpu_enc_pipe* p, uint32_t comp, uint64_t* sse, uint32_t* pae)
+{
+  if (!p || !sse || !pae) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->have_last_qinfo || comp >= p->last_qcomps.size()) return OJPHGPU_E_INVALID;
+  *sse = p->last_qcomps[comp].sse; *pae = p->last_qcomps[comp].pae;
   return OJPHGPU_OK;
 }
 

@@ -47,10 +47,12 @@ def unpack_bits(packed, bits, n):
 
 
 class EncoderPipe:
-    def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None, **kw):
+    def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None,
+                 max_sse=None, min_psnr=None, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
-        the device.  max_bytes: every frame is coded to that byte budget (set_budget)"""
+        the device.  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
+        quality target (set_quality) -- one or the other"""
         from .codec import _torch
         _torch()
         self.plan = plan if plan is not None else Plan(params if params is not None else make_params(**kw))
@@ -70,6 +72,8 @@ class EncoderPipe:
             self.packed = int(packed)
         if max_bytes:
             self.set_budget(max_bytes)
+        if max_sse is not None or min_psnr is not None:
+            self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
         self.in_flight = 0
 
     def set_budget(self, max_bytes):
@@ -85,6 +89,37 @@ class EncoderPipe:
         info = capi.RateInfo()
         check(self._lib.ojphgpu_enc_pipe_rate_info(self._h, C.byref(info)), "enc_pipe_rate_info")
         return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+
+    def set_quality(self, max_sse=None, min_psnr=None):
+        """Every frame is coded at the coarsest step of the rate grid found to meet the target -- the squared error between
+        the frame and the decode of its codestream, over all components, is at most max_sse (an integer; 0 is a target), or
+        min_psnr in dB turned into one by plan.psnr_to_sse -- the search started from the previous frame's answer
+        (ojphgpu_enc_pipe_set_quality).  Switched on before the first acquire(); afterwards the target may change between
+        frames -- the value at submit() is the frame's -- but not be switched off.  Not together with a byte budget.  A frame
+        whose target no step meets raises OjphError (capi.E_QUALITY) from its collect()."""
+        from .plan import psnr_to_sse
+        if (max_sse is None) == (min_psnr is None):
+            raise ValueError("set_quality: max_sse or min_psnr, one of them")
+        t = int(max_sse) if max_sse is not None else psnr_to_sse(self.plan, float(min_psnr))
+        if not 0 <= t < 2 ** 64:
+            raise ValueError("set_quality: max_sse must fit 64 bits")
+        check(self._lib.ojphgpu_enc_pipe_set_quality(self._h, t), "enc_pipe_set_quality")
+
+    def quality_info(self):
+        """of the frame collected last: dict(grid_index, qstep, sse, sse_coarser, pae, passes, bytes, comps), as
+        codec.Encoder.quality_info, plus first_guess = the first index its search tried; after E_QUALITY only passes and
+        first_guess are meaningful and comps is empty"""
+        info, first = capi.QualityInfo(), C.c_uint32()
+        check(self._lib.ojphgpu_enc_pipe_quality_info(self._h, C.byref(info), C.byref(first)), "enc_pipe_quality_info")
+        out = {k: getattr(info, k) for k, _ in capi.QualityInfo._fields_}
+        out["first_guess"] = int(first.value)
+        out["comps"] = []
+        for c in range(int(self.plan.params.num_comps)):
+            sse, pae = C.c_uint64(), C.c_uint32()
+            if self._lib.ojphgpu_enc_pipe_quality_comp(self._h, c, C.byref(sse), C.byref(pae)) != capi.OK:
+                break
+            out["comps"].append((int(sse.value), int(pae.value)))
+        return out
 
     def close(self):
         if self._h:
@@ -129,19 +164,24 @@ class EncoderPipe:
         check(self._lib.ojphgpu_enc_pipe_stats(self._h, out), "enc_pipe_stats")
         return dict(frames=int(out[0]), host_tier2_ms=out[1], latency_ms=out[2], tier2_threads=int(out[3]))
 
-    def encode_sequence(self, frames, budgets=None):
+    def encode_sequence(self, frames, budgets=None, targets=None):
         """frames: iterable of [C,H,W] arrays -> generator of codestreams, in order.  budgets (a pipe with a byte budget):
-        one int for every frame, or an iterable parallel to frames; a frame no step fits raises from here as from collect()"""
-        if budgets is not None and not hasattr(budgets, "__iter__"):
-            self.set_budget(budgets)
-            budgets = None
-        budgets = iter(budgets) if budgets is not None else None
+        one int for every frame, or an iterable parallel to frames; a frame no step fits raises from here as from collect().
+        targets (a pipe with a quality target): the same with max_sse values; not both"""
+        if budgets is not None and targets is not None:
+            raise ValueError("encode_sequence: budgets or targets, not both")
+        what, values = ("targets", targets) if targets is not None else ("budgets", budgets)
+        setter = (lambda v: self.set_quality(max_sse=v)) if targets is not None else self.set_budget
+        if values is not None and not hasattr(values, "__iter__"):
+            setter(values)
+            values = None
+        values = iter(values) if values is not None else None
         for n, f in enumerate(frames):
-            if budgets is not None:                       # (before the first acquire() this is what switches the mode on)
-                b = next(budgets, None)
+            if values is not None:                        # (before the first acquire() this is what switches the mode on)
+                b = next(values, None)
                 if b is None:
-                    raise ValueError("encode_sequence: budgets ended after %d values, frames go on" % n)
-                self.set_budget(b)
+                    raise ValueError("encode_sequence: %s ended after %d values, frames go on" % (what, n))
+                setter(b)
             buf = self.acquire()
             while buf is None:
                 yield self.collect()

@@ -358,11 +358,14 @@ def rate_search(plan: Plan, hist, max_bytes, size_fn, hint=None):
     return out
 
 
-def quality_search(max_sse, sse_fn):
-    """ojphgpu_quality_search: sse_fn(j) -> SSE of the frame at grid index j (a negative value: an error code).  -> dict(
-    grid_index, qstep, sse, sse_coarser, pae, passes, bytes); capi.OjphError with .code == capi.E_QUALITY (and .info = the dict)
-    when not even index 240 meets max_sse."""
+def quality_search(max_sse, sse_fn, hint=None):
+    """ojphgpu_quality_search, or with hint = a grid index (-1: none) ojphgpu_quality_search_hint (the first trial is `hint`,
+    then its neighbours on the side the result points to; in a sequence: the previous frame's answer): sse_fn(j) -> SSE of
+    the frame at grid index j (a negative value: an error code).  -> dict(grid_index, qstep, sse, sse_coarser, pae, passes,
+    bytes), with a hint also first_guess; capi.OjphError with .code == capi.E_QUALITY (and .info = the dict) when not even
+    index 240 meets max_sse."""
     info = capi.QualityInfo()
+    first = C.c_uint32()
 
     def fn(user, j, out):
         v = int(sse_fn(int(j)))
@@ -373,8 +376,15 @@ def quality_search(max_sse, sse_fn):
     cb = capi.SSE_FN(fn)
     if not 0 <= int(max_sse) < 2 ** 64:
         raise ValueError("max_sse must fit 64 bits")
-    rc = capi.lib().ojphgpu_quality_search(int(max_sse), cb, None, C.byref(info))
+    if hint is None:
+        rc = capi.lib().ojphgpu_quality_search(int(max_sse), cb, None, C.byref(info))
+    elif not -2 ** 31 <= int(hint) < 2 ** 31:              # (no grid index, and c_int32 would wrap it into one)
+        rc = capi.E_INVALID
+    else:
+        rc = capi.lib().ojphgpu_quality_search_hint(int(max_sse), int(hint), cb, None, C.byref(info), C.byref(first))
     out = {k: getattr(info, k) for k, _ in capi.QualityInfo._fields_}
+    if hint is not None:
+        out["first_guess"] = int(first.value)
     if rc != capi.OK:
         err = capi.OjphError(rc, "quality_search")
         err.info = out

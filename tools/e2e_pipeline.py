@@ -19,11 +19,13 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run_budget_pipe(plan, img, n, max_bytes, depth=4, threads=2, container=16, packed=None):
-    """bench.run_encoder_pipe for a pipe with a byte budget (max_bytes = 0: a plain pipe through the same loop): every
-    slot filled once, then n frames in steady state -> (seconds, stats with the rate figures, the codestream)"""
+def run_budget_pipe(plan, img, n, max_bytes, depth=4, threads=2, container=16, packed=None, max_sse=None):
+    """bench.run_encoder_pipe for a pipe with a byte budget (max_bytes = 0: a plain pipe through the same loop) or, with
+    max_sse, a quality target: every slot filled once, then n frames in steady state -> (seconds, stats with the rate or
+    quality figures, the codestream)"""
     from openjph_amd.pipeline import EncoderPipe, pack_bits
-    pipe = EncoderPipe(plan=plan, depth=depth, container=container, host_threads=threads, packed=packed, max_bytes=max_bytes or None)
+    pipe = EncoderPipe(plan=plan, depth=depth, container=container, host_threads=threads, packed=packed, max_bytes=max_bytes or None,
+                       max_sse=max_sse)
     filled = pack_bits(img, packed) if packed else None
     for _ in range(depth):
         buf = pipe.acquire()
@@ -40,8 +42,8 @@ def run_budget_pipe(plan, img, n, max_bytes, depth=4, threads=2, container=16, p
         while sub < n and pipe.acquire() is not None:
             pipe.submit(); sub += 1
         nbytes += len(pipe.collect(copy=False)); col += 1
-        if max_bytes:
-            info = pipe.rate_info()
+        if max_bytes or max_sse is not None:
+            info = pipe.rate_info() if max_bytes else pipe.quality_info()
             passes += info["passes"]
     dt = time.perf_counter() - t0
     st = pipe.stats()
@@ -50,6 +52,9 @@ def run_budget_pipe(plan, img, n, max_bytes, depth=4, threads=2, container=16, p
     if max_bytes:
         st.update(max_bytes=max_bytes, grid_index=info["grid_index"], qstep=info["qstep"], bytes=info["bytes"],
                   bytes_finer=info["bytes_finer"], mean_passes=round(passes / n, 3))
+    elif max_sse is not None:
+        st.update(max_sse=max_sse, grid_index=info["grid_index"], qstep=info["qstep"], bytes=info["bytes"], sse=info["sse"],
+                  sse_coarser=info["sse_coarser"], mean_passes=round(passes / n, 3))
     return dt, st, first
 
 

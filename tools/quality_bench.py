@@ -6,7 +6,16 @@ trial is a plain encode (codec.Encoder), an upload and decode of its codestream 
 torch, then the encode of j*.  Host clock around calls that end in a stream synchronise.  At each target the certificate is
 checked once by decoding the codestreams of j* and j* - 1.  Prints one JSON line per target: j*, trials, the medians in ms of
 (a) (b) (c), and of (a) the search alone, one trial, the device wait of a trial, and the coding of j* with its download.
-  python tools/quality_bench.py [--runs 10] [--warmup 2] [--rows 4320] [--no-caller]"""
+  python tools/quality_bench.py [--runs 10] [--warmup 2] [--rows 4320] [--no-caller]
+
+--pipe: the target in the encoder pipe instead, from host memory to codestream in host memory: a sequence of identical C3
+frames (16-bit containers, depth 4) at the same three targets.  Per target three contenders take turns, `--rounds` rounds
+of `--frames` frames each: (a) the pipe with the target; (b) a plain pipe at the fixed step qstep(j*) -- the same bytes,
+no search: the difference is what the search costs; (c) codec.Encoder(min_psnr) frame by frame from host memory -- what
+there was before the pipe had a target, the full search on every frame; its frames are uploaded from pageable numpy memory
+(Encoder.encode), the pipes' from their pinned slots.  Prints one JSON line per target: j*, mean trials per frame, and per
+contender the frames/s of every round, their median and their spread (max - min) / median.
+  python tools/quality_bench.py --pipe [--rounds 3] [--frames 24] [--rows 4320]"""
 import argparse
 import json
 import os
@@ -21,13 +30,62 @@ TARGETS_DB = (40, 45, 50)
 GRID = 241
 
 
+def pipe_bench(a):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from e2e_pipeline import run_budget_pipe
+    from openjph_amd import codec
+    from openjph_amd import plan as planmod
+    from openjph_amd.plan import Plan, make_params
+    from tests import synth
+    img = synth.survey_c3(rows=a.rows)
+    nc, h, w = img.shape
+    img16 = img.astype(np.uint16)
+
+    def params(qstep):
+        return make_params(w, h, nc, bit_depth=12, reversible=False, qstep=qstep)
+    searched = Plan(params(0.001))
+    single = codec.Encoder(params(0.001))
+    for db in TARGETS_DB:
+        T = planmod.psnr_to_sse(searched, db)
+        single.set_quality(max_sse=T)
+        fps = {"pipe_target": [], "pipe_fixed_step": [], "encoder_per_frame": []}
+        st = fixed = None
+        for r in range(a.rounds + 1):                           # round 0 warms every contender up and is not counted
+            dt, st, cs = run_budget_pipe(searched, img16, a.frames, 0, depth=4, max_sse=T)
+            if fixed is None:
+                fixed = Plan(params(planmod.rate_grid_qstep(st["grid_index"])))
+            dt_fixed, _, cs_fixed = run_budget_pipe(fixed, img16, a.frames, 0, depth=4)
+            assert cs == cs_fixed and len(cs) == st["bytes"] and st["sse"] <= T
+            t0 = time.perf_counter()
+            for _ in range(a.frames):
+                cs_single = single.encode(img16)
+            dt_single = time.perf_counter() - t0
+            assert cs_single == cs
+            if r:
+                fps["pipe_target"].append(a.frames / dt); fps["pipe_fixed_step"].append(a.frames / dt_fixed)
+                fps["encoder_per_frame"].append(a.frames / dt_single)
+        out = dict(frame="c3 %dx%dx%d 12-bit, 16-bit containers, host memory" % (w, h, nc), depth=4, frames_per_round=a.frames,
+                   min_psnr_db=db, max_sse=T, grid_index=st["grid_index"], bytes=st["bytes"], sse=st["sse"], sse_coarser=st["sse_coarser"],
+                   mean_trials=st["mean_passes"], single_encoder_trials=single.quality_info()["passes"])
+        for k, v in fps.items():
+            med = float(np.median(v))
+            out[k] = dict(fps=[round(x, 1) for x in v], median_fps=round(med, 1), ms_per_frame=round(1e3 / med, 3),
+                          spread=round((max(v) - min(v)) / med, 3))
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=4320, help="top rows of the frame (rehearsals at a small size)")
     ap.add_argument("--no-caller", action="store_true", help="skip contender (c)")
+    ap.add_argument("--pipe", action="store_true", help="the target in the encoder pipe, from host memory")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=24)
     a = ap.parse_args()
+    if a.pipe:
+        return pipe_bench(a)
     import torch
     from openjph_amd import codec
     from openjph_amd import plan as planmod
