@@ -287,6 +287,16 @@ int  ojphgpu_plan_restrict_region(ojphgpu_plan* plan, uint32_t x0, uint32_t y0, 
 /* per block of the plan (plan order, n = the plan's block count): 1 = decoded for the region; blocks of resolutions that
  * are not read are 0.  A plan without a region: the blocks a whole-frame decoder decodes. */
 int  ojphgpu_plan_region_blocks(const ojphgpu_plan* plan, uint8_t* mask, size_t n);
+/* What a view decoder of a parsed plan (after any restriction) uploads: the bytes of the coded blocks it decodes
+ * (ojphgpu_plan_region_blocks), as runs of blocks adjacent in the codestream.  Run i = n bytes at offset src of the
+ * codestream, placed at dst of the staged bytes; sorted by src and strictly apart (src[i + 1] > src[i] + n[i]); every dst a
+ * multiple of 64, the first one 64, dst[i + 1] >= align64(dst[i] + n[i]) + 64; *staged_len = align64(end of the last run) + 64.
+ * Everything between the runs is zeros (the block decoder's 16-byte loads reach into the margins).  No coded block: no
+ * runs, *staged_len = 0.  Blocks cut short by a damaged tile-part (ojphgpu_plan_padded_blocks) are not part of a run: their
+ * copies go behind the staged bytes.  Host logic, no device: the table ojphgpu_gather_runs takes.
+ * out == NULL: *count and *staged_len only; cap < *count: OJPHGPU_E_OVERFLOW with both set. */
+typedef struct ojphgpu_run { uint64_t src, dst, n; } ojphgpu_run;
+int  ojphgpu_plan_upload_runs(const ojphgpu_plan* plan, ojphgpu_run* out, size_t cap, size_t* count, uint64_t* staged_len);
 
 /* ------------------------------------------------------------------------------------------ *
  * 4. Batched device stages.  Descriptor arrays live in device memory.
@@ -860,6 +870,25 @@ int  ojphgpu_enc_pipe_quality_comp(ojphgpu_enc_pipe* pipe, uint32_t comp, uint64
  * submitted codestream must describe the same frame format and code-block grid (quantisation may differ) */
 int  ojphgpu_dec_pipe_create(const uint8_t* h_codestream, size_t len, int resilient, int device, uint32_t depth,
                              int container_bits, uint32_t host_threads, ojphgpu_dec_pipe** out);
+/* A pipe that decodes a VIEW of every frame: at reduced resolution (ojphgpu_plan_restrict_resolution with the two counts;
+ * 0, 0: none), a rectangle { x0, y0, w, h } of the reference grid (ojphgpu_plan_restrict_region, applied after the
+ * resolution; NULL: none), or both -- frame for frame what a decoder object created from the plan restricted that way
+ * decodes.  What those two calls refuse (a skip beyond the decompositions, w or h 0, a rectangle outside the image, a region
+ * on Part-2 or 64-bit components) is refused here with OJPHGPU_E_INVALID.  The frames handed out, ojphgpu_dec_pipe_plan and
+ * _set_pixels / _set_packed describe the view's frame (_set_pixels: the view's component planes must be of one size).
+ * Of the codestream only the bytes of the code-blocks the view depends on cross PCIe (and the aligned dwords around each
+ * run): a kernel reads them as runs (ojphgpu_plan_upload_runs) out of the slot's pinned codestream and lays them out in
+ * device memory (ojphgpu_gather_runs).  Beside them go, as in a plain pipe, the block descriptors, and the run table (24
+ * bytes per run, one copy into device memory ahead of the kernel).  0, 0, NULL is
+ * ojphgpu_dec_pipe_create.  The view is fixed for the life of the pipe. */
+int  ojphgpu_dec_pipe_create_view(const uint8_t* h_codestream, size_t len, int resilient, uint32_t skipped_res_for_data,
+                                  uint32_t skipped_res_for_recon, const uint32_t* region, int device, uint32_t depth,
+                                  int container_bits, uint32_t host_threads, ojphgpu_dec_pipe** out);
+/* of the frame collected last (whatever its outcome; zeros where it failed before its descriptors were filled):
+ * out[0] code-blocks decoded, [1] code-blocks of the codestream, [2] bytes staged for the block decoder -- of a view: what
+ * the gather lays out; of a plain pipe: the byte range uploaded -- [3] runs (0: a plain pipe), [4] coded bytes of the
+ * decoded blocks.  OJPHGPU_E_INVALID before the first _collect. */
+int  ojphgpu_dec_pipe_view_info(ojphgpu_dec_pipe* pipe, uint64_t out[5]);
 void ojphgpu_dec_pipe_destroy(ojphgpu_dec_pipe* pipe);
 int  ojphgpu_dec_pipe_plan(ojphgpu_dec_pipe* pipe, const ojphgpu_plan** plan);   /* owned by the pipe */
 /* pinned host memory for the next codestream of `len` bytes (read the file straight into it) */
@@ -899,6 +928,16 @@ int  ojphgpu_pack_pixels(void* stream, const void* d_planes, void* d_pixels, uin
  * such samples in 16-bit words. */
 int  ojphgpu_unpack_bits(void* stream, const void* d_packed, void* d_samples, uint64_t num_samples, int bits, int container_bits);
 int  ojphgpu_pack_bits(void* stream, const void* d_samples, void* d_packed, uint64_t num_samples, int container_bits, int bits);
+/* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
+ * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
+ * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a
+ * multiple of 4 from 16 to below 2^34 (otherwise OJPHGPU_E_INVALID).  d_runs: n entries as ojphgpu_plan_upload_runs builds
+ * them, where the device can read them -- device memory for choice: every workgroup reads a window of the table per
+ * 16 KB step, which from mapped host memory would cross PCIe beside the payload.  Every byte of d_dst[0, staged_len) is written: run i's bytes at dst[i], zeros everywhere else; nothing at or
+ * beyond staged_len (a multiple of 64; d_dst 16-byte aligned).  Loads stay inside [0, src_cap) whatever the table holds (a
+ * run that reaches beyond it is the caller's mistake: those bytes come out unspecified).  staged_len == 0: no launch. */
+int  ojphgpu_gather_runs(void* stream, const void* d_src, size_t src_cap, const ojphgpu_run* d_runs, uint32_t n, void* d_dst,
+                         uint64_t staged_len);
 
 const char* ojphgpu_version(void);
 

@@ -174,6 +174,11 @@ class QualityInfo(C.Structure):           # ojphgpu_quality_info
 
 SSE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64))      # ojphgpu_sse_fn
 
+
+class Run(C.Structure):                   # ojphgpu_run
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("n", C.c_uint64)]
+
+
 _lib = None
 
 # name -> (restype, argtypes); also the list every test checks against include/ojphgpu.h
@@ -351,6 +356,11 @@ SIGNATURES = {
     "ojphgpu_encoder_quality_info": (C.c_int, [C.c_void_p, C.POINTER(QualityInfo)]),
     "ojphgpu_encoder_quality_comp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ojphgpu_encoder_quality_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_plan_upload_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "ojphgpu_gather_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ojphgpu_dec_pipe_create_view": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.c_uint32,
+                                               C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ojphgpu_dec_pipe_view_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ojphgpu_version": (C.c_char_p, []),
 }
 

@@ -468,6 +468,24 @@ def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None
     return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes, max_sse=max_sse, min_psnr=min_psnr).encode(image)
 
 
+def gather_runs(src, runs, staged_len, out=None):
+    """the upload of a view as a stage (ojphgpu_gather_runs): src = uint8 tensor on the device (the codestream), runs =
+    run_dtype array (Plan.upload_runs), -> uint8 tensor of staged_len bytes: the runs at their places, zeros elsewhere.
+    out: a uint8 tensor of at least staged_len bytes to write into (bytes behind staged_len are left alone)"""
+    from .plan import run_dtype
+    torch = _torch()
+    dev = src.device.index or 0
+    runs = np.ascontiguousarray(runs, dtype=run_dtype)
+    if out is None:
+        out = torch.empty(max(int(staged_len), 16), dtype=torch.uint8, device=src.device)
+    d_runs = to_device(runs, dev)
+    with torch.cuda.device(dev):
+        check(capi.lib().ojphgpu_gather_runs(_stream_ptr(torch, dev), C.c_void_p(src.data_ptr()), int(src.numel()), C.c_void_p(d_runs.data_ptr()),
+                                             int(runs.size), C.c_void_p(out.data_ptr()), int(staged_len)), "gather_runs")
+        torch.cuda.synchronize(dev)       # (d_runs may go away after this call)
+    return out
+
+
 def decode(codestream: bytes, device=0, resilient=False, skip_res=None, region=None) -> np.ndarray:
     return Decoder(codestream, device=device, resilient=resilient, skip_res=skip_res, region=region).decode()
 

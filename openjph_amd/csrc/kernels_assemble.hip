@@ -89,6 +89,96 @@ __global__ __launch_bounds__(256) void copy_to_host_kernel(v4u* __restrict__ dst
   if (blockIdx.x == 0 && threadIdx.x < tail) dst_tail[threadIdx.x] = src_tail[threadIdx.x];
 }
 
+// The upload of a VIEW (reduced resolution, a window): the bytes a frame's decoder needs are runs of code-blocks scattered
+// over a codestream that lies in mapped pinned memory; this kernel reads them across PCIe and lays the staged bytes out in
+// HBM -- run i at dst_i (64-byte aligned, 64 zero bytes either side), zeros everywhere else -- so that no host pass gathers
+// them and only the view's bytes cross the link.  The work is split over the DESTINATION as in copy_to_host_kernel: a few
+// workgroups, each walking one contiguous segment in steps of 16 KB, a lane writing four aligned 16-byte pieces per step.
+// A piece meets at most one run (runs start on 64-byte boundaries, 64 bytes apart at least): the last one that starts at or
+// before it, found
+//   * in the table (device memory in the pipes, which copy it there first: a workgroup reads a window of up to 6 KB of it
+//     per 16 KB step, too much to fetch across PCIe beside the payload) once per workgroup by a binary search, then carried from step to step: every thread loads one entry of the window [cur, cur + 256) -- a step holds 129 run
+//     starts at the most -- and the count of those starting up to the step's end moves `cur`; the next step's window is
+//     requested before this step's data, so both are in flight together;
+//   * per piece among the step's entries, in LDS (no trip at all when the step lies in one run).
+// The source is arbitrary in alignment: a lane loads the four aligned dwords that hold its first byte (one dwordx4, so that
+// every source byte crosses the link once), takes the fifth from its neighbour's load -- or from a load of its own where
+// the neighbour does not continue it; the other lanes aim that load at one common dword -- and shifts with v_alignbyte.
+// Loads are issued unconditionally from addresses clamped into [0, src_cap): bytes behind a run's end, and the whole
+// piece where there is none, are selected to zero when the registers are consumed.  Whatever the table holds, nothing
+// outside the source is read and nothing outside [0, staged_len) is written.
+struct GatherRun { uint64_t src, dst, n; };        // = ojphgpu_run
+typedef v4u v4u_a4 __attribute__((aligned(4)));
+
+__global__ __launch_bounds__(256) void gather_runs_kernel(const GatherRun* __restrict__ runs, uint32_t nruns, const uint32_t* __restrict__ src,
+                                                          uint32_t ndw, v4u* __restrict__ dst, size_t n16, size_t seg)
+{
+  __shared__ uint64_t s_src[2][256], s_dst[2][256], s_n[2][256];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const size_t lo = (size_t)blockIdx.x * seg, hi = lo + seg < n16 ? lo + seg : n16;
+  if (lo >= hi) return;
+  uint32_t cur = 0;                                               // the last run starting at or before the segment (0: none does)
+  for (uint32_t cnt = nruns; cnt > 1;) {
+    const uint32_t half = cnt >> 1;
+    if (runs[cur + half].dst <= (uint64_t)lo * 16u) cur += half;
+    cnt -= half;
+  }
+  auto entry = [&](uint32_t first, bool& ok) { const uint32_t i = first + tid; ok = i < nruns; return runs[ok ? i : nruns - 1u]; };
+  bool ok; GatherRun e = entry(cur, ok);
+  uint32_t sel = 0;
+  for (size_t base = lo; base < hi; base += 1024, sel ^= 1u) {
+    s_src[sel][tid] = e.src; s_dst[sel][tid] = ok ? e.dst : ~0ull; s_n[sel][tid] = e.n;
+    const uint32_t c = (uint32_t)__syncthreads_count(ok && e.dst <= (uint64_t)(base + 1024) * 16u);   // starts up to the step's end
+    cur += (c ? c : 1u) - 1u;
+    e = entry(cur, ok);                                           // the next step's window
+    v4u L[4]; uint32_t W[4], sh[4], d[4], m[4]; bool own[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t i = base + tid + 256u * j;
+      const uint64_t p = (uint64_t)(i < hi ? i : hi - 1) * 16u;
+      uint32_t k = 0;
+      for (uint32_t cnt = c; cnt > 1;) {                          // (c is the workgroup's: no divergence)
+        const uint32_t half = cnt >> 1;
+        if (s_dst[sel][k + half] <= p) k += half;
+        cnt -= half;
+      }
+      const uint64_t rs = s_src[sel][k], rd = s_dst[sel][k], rn = s_n[sel][k];
+      const uint64_t off = p - rd;                                // (p < rd, before the first run: wraps, >= rn)
+      m[j] = off < rn ? (uint32_t)(rn - off < 16u ? rn - off : 16u) : 0u;
+      const uint64_t a = rs + (off < rn ? off : 0u);
+      const uint32_t q = (uint32_t)((a >> 2) < ndw ? (a >> 2) : ndw);          // the dword holding the piece's first byte
+      const uint32_t b = q < ndw - 4u ? q : ndw - 4u;             // where the four dwords are loaded from
+      sh[j] = (uint32_t)a & 3u; d[j] = q - b;
+      own[j] = lane == 63u || (uint32_t)__shfl_down((int)b, 1) != q + 4u;
+      const uint32_t xi = own[j] ? (q + 4u < ndw ? q + 4u : ndw - 1u) : (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+      L[j] = *(const v4u_a4*)(src + b);
+      W[j] = src[xi];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t i = base + tid + 256u * j;
+      uint32_t x0 = L[j].x, x1 = L[j].y, x2 = L[j].z, x3 = L[j].w;
+      const uint32_t nb = (uint32_t)__shfl_down((int)x0, 1);
+      uint32_t x4 = own[j] ? W[j] : nb;
+      if (d[j]) {                                                 // the last dwords of the source: the load was moved down
+        x4 = 0;
+        if (d[j] & 1u) { x0 = x1; x1 = x2; x2 = x3; x3 = 0; }
+        if (d[j] & 2u) { x0 = x2; x1 = x3; x2 = 0; x3 = 0; }
+        if (d[j] & 4u) { x0 = 0; x1 = 0; x2 = 0; x3 = 0; }
+      }
+      const uint32_t w[4] = { __builtin_amdgcn_alignbyte(x1, x0, sh[j]), __builtin_amdgcn_alignbyte(x2, x1, sh[j]),
+                              __builtin_amdgcn_alignbyte(x3, x2, sh[j]), __builtin_amdgcn_alignbyte(x4, x3, sh[j]) };
+      v4u v;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {                               // bytes at and behind the run's end are zeros
+        const uint32_t have = m[j] > 4u * t ? m[j] - 4u * t : 0u;
+        v[t] = have >= 4u ? w[t] : (w[t] & ((1u << (8u * have)) - 1u));
+      }
+      if (i < hi) dst[i] = v;
+    }
+  }
+}
+
 // byte counter + overflow flag of the block coder (device words) -> two words of pinned host memory
 __global__ void publish_words_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t n)
 {
@@ -99,18 +189,43 @@ __global__ void publish_words_kernel(uint32_t* __restrict__ dst, const uint32_t*
 
 namespace ojphgpu {
 
+// workgroups of the kernels that move bytes across PCIe (see copy_to_host_kernel)
+static unsigned copy_workgroups()
+{
+  static const unsigned n = [] { const char* e = getenv("OJPHGPU_COPY_WGS"); const long v = e ? atol(e) : 0; return v > 0 && v <= 4096 ? (unsigned)v : 8u; }();
+  return n;
+}
+
 // src: device memory, 16-byte aligned; d_dst: the DEVICE address of pinned host memory (hipHostGetDevicePointer), 16-byte aligned
 int copy_to_host_launch(void* stream, void* d_dst, const void* src, size_t bytes)
 {
   if (bytes == 0) return OJPHGPU_OK;
   if (!d_dst || !src || (((uintptr_t)d_dst | (uintptr_t)src) & 15u)) return OJPHGPU_E_INVALID;
   const size_t n16 = bytes >> 4; const uint32_t tail = (uint32_t)(bytes & 15u);
-  static const unsigned max_blocks = [] { const char* e = getenv("OJPHGPU_COPY_WGS"); const long v = e ? atol(e) : 0; return v > 0 && v <= 4096 ? (unsigned)v : 8u; }();
+  const unsigned max_blocks = copy_workgroups();
   size_t seg = (n16 + max_blocks - 1) / max_blocks;
-  seg = (seg + 1023) & ~(size_t)1023;                        // whole 16 KB steps
+  seg = std::max<size_t>((seg + 1023) & ~(size_t)1023, 1024);   // whole 16 KB steps (fewer than 16 bytes: the tail alone, one workgroup)
   const unsigned blocks = (unsigned)std::max<size_t>(1, (n16 + seg - 1) / seg);
   hipLaunchKernelGGL(copy_to_host_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (v4u*)d_dst, (const v4u*)src, n16, seg,
                      (uint8_t*)d_dst + (n16 << 4), (const uint8_t*)src + (n16 << 4), tail);
+  return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
+}
+
+// d_src: the device address of the source (pinned host memory, or device memory), 16-byte aligned, src_cap bytes of it
+// readable (a multiple of 4, from 16 to below 2^34: the kernel counts the source in 32-bit dword indices); d_runs: the table where the kernel can read it; d_dst: 16-byte aligned
+int gather_runs_launch(void* stream, const void* d_src, size_t src_cap, const void* d_runs, uint32_t nruns, void* d_dst, uint64_t staged_len)
+{
+  if (staged_len == 0) return OJPHGPU_OK;
+  if (!d_src || !d_dst || (nruns && !d_runs) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 15u) || ((uintptr_t)d_runs & 7u) || (staged_len & 63u) ||
+      (src_cap & 3u) || src_cap < 16 || src_cap >= ((size_t)1 << 34)) return OJPHGPU_E_INVALID;
+  if (nruns == 0) return hipMemsetAsync(d_dst, 0, (size_t)staged_len, (hipStream_t)stream) == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
+  const size_t n16 = (size_t)(staged_len >> 4);
+  const unsigned max_blocks = copy_workgroups();
+  size_t seg = (n16 + max_blocks - 1) / max_blocks;
+  seg = (seg + 1023) & ~(size_t)1023;                        // whole 16 KB steps
+  const unsigned blocks = (unsigned)((n16 + seg - 1) / seg);
+  hipLaunchKernelGGL(gather_runs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const GatherRun*)d_runs, nruns, (const uint32_t*)d_src,
+                     (uint32_t)(src_cap >> 2), (v4u*)d_dst, n16, seg);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 
@@ -131,3 +246,10 @@ int assemble_launch(void* stream, const T2Job* d_jobs, uint32_t njobs, const uin
 }
 
 }  // namespace ojphgpu
+
+static_assert(sizeof(ojphgpu_run) == sizeof(GatherRun), "ojphgpu_run is the kernel's table entry");
+
+extern "C" int ojphgpu_gather_runs(void* stream, const void* d_src, size_t src_cap, const ojphgpu_run* d_runs, uint32_t n, void* d_dst, uint64_t staged_len)
+{
+  return ojphgpu::gather_runs_launch(stream, d_src, src_cap, d_runs, n, d_dst, staged_len);
+}

@@ -973,9 +973,11 @@ int ojphgpu_same_frame_geometry(const Plan& P, const Plan& Q, bool compare_block
 // Block descriptors of one frame: geometry from P (the decoder's plan), what the packet headers and the
 // QCD / QCC of THIS frame's codestream say from Q.  arena_off = element offset of the frame's arena,
 // data_base = where the frame's byte range [fi.first, fi.first + fi.len) of the codestream will sit in the
-// device data buffer.  scratch_cap / reserved are left to ojphgpu_ht_decode_layout.
+// device data buffer.  scratch_cap / reserved are left to ojphgpu_ht_decode_layout.  want_runs: the frame's bytes as runs
+// (fi.runs) also for a plan without a region -- one restricted in resolution under PCRL / CPRL has the skipped resolutions'
+// blocks between the others all over the codestream; a region plan always gets runs.
 void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<uint32_t>& ids, uint64_t arena_off,
-                                uint64_t data_base, ojphgpu_cb_desc* bd, DecFrameInfo& fi)
+                                uint64_t data_base, ojphgpu_cb_desc* bd, DecFrameInfo& fi, bool want_runs)
 {
   uint64_t max_off = 0, min_off = ~0ull;
   fi.any_refine = false; fi.max_len1 = 0; fi.kinds = 0; fi.pads.clear(); fi.pad_len = 0;
@@ -1014,7 +1016,7 @@ void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<
   if (min_off > max_off) min_off = max_off = 0;
   min_off &= ~(uint64_t)15;                                             // only this byte range of the codestream is uploaded
   fi.runs.clear();
-  if (P.has_region) {
+  if (P.has_region || want_runs) {
     // a region decoder's blocks are scattered over the codestream (progression orders interleave them): the runs of blocks
     // adjacent in the codestream are placed one after another, 64 zero bytes on either side of each
     std::vector<std::pair<uint64_t, uint64_t>> spans;                    // (offset, end) of every block with bytes here
@@ -1062,6 +1064,24 @@ void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<
   }
   if (!fi.pads.empty()) at += 64;                                       // (ojphgpu_decoder_upload_pads zeroes a 64-byte margin behind the last block too)
   fi.pad_len = at - ((fi.len + 63) & ~(uint64_t)63);
+}
+
+extern "C" int ojphgpu_plan_upload_runs(const ojphgpu_plan* plan, ojphgpu_run* out, size_t cap, size_t* count, uint64_t* staged_len)
+{
+  if (!plan || !count || !staged_len) return OJPHGPU_E_INVALID;
+  const Plan& P = plan->plan;
+  if (P.coded.size() != P.blocks.size()) return OJPHGPU_E_INVALID;    // a parsed codestream only
+  return no_throw([&]() -> int {
+    const std::vector<uint32_t> ids = blocks_of_tiles(P, TileRange{ 0, (uint32_t)P.tiles.size() });
+    std::vector<ojphgpu_cb_desc> bd(ids.size());
+    DecFrameInfo fi;
+    ojphgpu_decoder_fill_descs(P, P, ids, 0, 0, bd.data(), fi, true);
+    *count = fi.runs.size(); *staged_len = fi.len;
+    if (!out) return OJPHGPU_OK;
+    if (cap < fi.runs.size()) return OJPHGPU_E_OVERFLOW;
+    for (size_t i = 0; i < fi.runs.size(); ++i) out[i] = ojphgpu_run{ fi.runs[i].src, fi.runs[i].dst, fi.runs[i].n };
+    return OJPHGPU_OK;
+  });
 }
 
 int ojphgpu_decoder_upload_pads(hipStream_t s, uint8_t* d_frame_data, const uint8_t* h_codestream, size_t cs_len, const std::vector<PadCopy>& pads)

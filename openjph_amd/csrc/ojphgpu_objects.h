@@ -644,7 +644,7 @@ struct DecFrameInfo {
 int ojphgpu_decoder_upload_pads(hipStream_t s, uint8_t* d_frame_data, const uint8_t* h_codestream, size_t cs_len, const std::vector<PadCopy>& pads);
 int  ojphgpu_same_frame_geometry(const Plan& P, const Plan& Q, bool compare_blocks);
 void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<uint32_t>& ids, uint64_t arena_off,
-                                uint64_t data_base, ojphgpu_cb_desc* bd, DecFrameInfo& fi);
+                                uint64_t data_base, ojphgpu_cb_desc* bd, DecFrameInfo& fi, bool want_runs = false);
 int  ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int container);
 inline EncoderQuality::~EncoderQuality()
 {

@@ -10,6 +10,9 @@
 //             lengths -> packet headers on host threads -> placement kernel -> D2H of n-1's finished codestream
 //   decoder   host threads parse n+1's packet headers  |  H2D of n+1's bytes + descriptors  |  kernels of n  |
 //             D2H of n-1's frame into pinned memory the caller reads rows from
+//   a view    (ojphgpu_dec_pipe_create_view: reduced resolution, a window) the same, with the plan of every frame restricted
+//             as the first one's was and the H2D of the bytes done by a kernel that reads the runs of the view's blocks out
+//             of the pinned codestream (kernels_assemble.hip, gather_runs_kernel): only those bytes cross PCIe
 //
 // on separate HIP streams (copy-in, compute, copy-out) with events between them.  The coded bytes never
 // pass through a host memcpy: the encoder's codestream is assembled in HBM (kernels_assemble.hip) from the
@@ -37,6 +40,7 @@ namespace ojphgpu {
 int assemble_launch(void* stream, const T2Job* d_jobs, uint32_t njobs, const uint8_t* d_blob, const uint8_t* d_data, uint8_t* d_out);
 int copy_to_host_launch(void* stream, void* d_dst, const void* src, size_t bytes);
 int publish_words_launch(void* stream, uint32_t* d_dst, const uint32_t* src, uint32_t n);
+int gather_runs_launch(void* stream, const void* d_src, size_t src_cap, const void* d_runs, uint32_t nruns, void* d_dst, uint64_t staged_len);
 }
 
 namespace {
@@ -474,7 +478,9 @@ static int pixels_fit(const Plan& P, int pixel_bits, int container_bits)
 {
   if (pixel_bits != 8 && pixel_bits != 16) return OJPHGPU_E_INVALID;
   if (pixel_bits > container_bits) return OJPHGPU_E_INVALID;
-  if (P.frame_elems != (uint64_t)P.p.width * P.p.height * P.p.num_comps) return OJPHGPU_E_INVALID;   // sub-sampled components
+  if (P.skip_recon || P.has_region) {                  // a view's frame (a decoder pipe): planes of one size
+    for (const CompGeo& g : P.comps) if (g.w != P.comps[0].w || g.h != P.comps[0].h || g.w == 0 || g.h == 0) return OJPHGPU_E_INVALID;
+  } else if (P.frame_elems != (uint64_t)P.p.width * P.p.height * P.p.num_comps) return OJPHGPU_E_INVALID;   // sub-sampled components
   for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth > (uint32_t)pixel_bits) return OJPHGPU_E_INVALID;
   return OJPHGPU_OK;
 }
@@ -726,17 +732,25 @@ struct DecSlot {
   SlotState state = FREE;
   Pinned h_cs, h_descs, h_img, h_status;
   Grow data;
-  DeviceBuf image, cb_descs, status, pixels;
+  DeviceBuf image, cb_descs, status, pixels, runs;  // runs: a view's run table, copied there for the gather kernel
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   size_t cs_len = 0;
   int rc = 0; uint32_t failed = 0;
   double t_submit = 0, t_done = 0, t_parse = 0;
+  uint64_t view_info[5] = {};                       // see ojphgpu_dec_pipe_view_info
 };
 
 struct ojphgpu_dec_pipe {
   ojphgpu_plan* first = nullptr;                     // parsed from the first codestream: the geometry of every frame
   const Plan* P = nullptr;
   int device = 0, container = 16, resilient = 0;
+  // a view (ojphgpu_dec_pipe_create_view): what every frame's plan is restricted by, as the first one's was; the frame's
+  // bytes then go up as runs, gathered by a kernel from the slot's pinned codestream (the run table: in h_descs at runs_off,
+  // copied to the slot's `runs` in HBM)
+  bool view = false, has_region = false;
+  uint32_t skip_data = 0, skip_recon = 0, region[4] = {};
+  size_t runs_off = 0;
+  uint64_t last_view_info[5] = {}; bool have_view_info = false;   // of the frame collected last
   int mode = copy_mode("OJPHGPU_DEC_COPY_MODE", 0);
   uint32_t depth = 0;
   // Consecutive frames go to different decoder objects (own scratch, own compute stream): step 1 of the block decoder
@@ -776,20 +790,37 @@ static void dec_process_frame(ojphgpu_dec_pipe* p, DecSlot& s)
   if (rc) return fail(rc);
   struct Hold { ojphgpu_plan* q; ~Hold() { ojphgpu_plan_destroy(q); } } hold{ q };
   rc = no_throw([&]() -> int {
+    int r2;
+    if ((p->skip_data || p->skip_recon) && (r2 = ojphgpu_plan_restrict_resolution(q, p->skip_data, p->skip_recon)) != 0) return r2;
+    if (p->has_region && (r2 = ojphgpu_plan_restrict_region(q, p->region[0], p->region[1], p->region[2], p->region[3])) != 0) return r2;
     const Plan& Q = q->plan;
-    int r2 = ojphgpu_same_frame_geometry(P, Q, true);
+    r2 = ojphgpu_same_frame_geometry(P, Q, true);
     if (r2) return r2;
     const size_t nb = d->block_ids.size();
     ojphgpu_cb_desc* bd = (ojphgpu_cb_desc*)s.h_descs.p;
     DecFrameInfo fi;
-    ojphgpu_decoder_fill_descs(P, Q, d->block_ids, 0, 0, bd, fi);
+    ojphgpu_decoder_fill_descs(P, Q, d->block_ids, 0, 0, bd, fi, p->view);
+    uint64_t coded = 0;
+    for (size_t i = 0; i < nb; ++i) coded += (uint64_t)bd[i].len1 + bd[i].len2;
+    s.view_info[0] = nb; s.view_info[1] = Q.blocks.size(); s.view_info[2] = fi.len; s.view_info[3] = fi.runs.size(); s.view_info[4] = coded;
     uint64_t nquads = 0, naux = 0;
     if (ojphgpu_ht_decode_layout(bd, (uint32_t)nb, &nquads, &naux) != OJPHGPU_OK) return OJPHGPU_E_INVALID;
     if ((naux + 16) * 4 > d->aux.n || (nquads + 16) * 4 > d->quads.n) return OJPHGPU_E_INVALID;     // sized for the worst case at create
     s.t_parse = now_ms() - t0;
-    if (fi.first + fi.len > s.cs_len) return OJPHGPU_E_CODESTREAM;
+    if (p->view) {                                     // the runs of the view's blocks: every one inside this codestream
+      if (fi.runs.size() > nb) return OJPHGPU_E_INVALID;          // (a run holds a block at least: the table's room)
+      for (const DecRun& r : fi.runs) if (r.src > s.cs_len || r.n > s.cs_len - r.src) return OJPHGPU_E_CODESTREAM;
+    } else if (fi.first + fi.len > s.cs_len) return OJPHGPU_E_CODESTREAM;
     if (s.data.reserve((size_t)fi.data_bytes() + (size_t)fi.len / 4 + 128)) return OJPHGPU_E_NOMEM;
-    if ((r2 = upload(p->mode, p->s_h2d, s.data.b.p, s.h_cs, (size_t)fi.first, (size_t)fi.len)) != 0) return r2;
+    if (p->view) {
+      // the table goes into the slot's pinned descriptor memory behind the block descriptors and from there in one small
+      // copy into HBM: every workgroup of the kernel reads a window of it per step, which would otherwise cross PCIe
+      // beside the payload.  The kernel writes all of [0, fi.len): the runs, and zeros over whatever a longer frame left
+      if (!fi.runs.empty()) memcpy(s.h_descs.p + p->runs_off, fi.runs.data(), fi.runs.size() * sizeof(DecRun));
+      if ((r2 = upload(p->mode, p->s_h2d, s.runs.p, s.h_descs, p->runs_off, fi.runs.size() * sizeof(DecRun))) != 0) return r2;
+      if ((r2 = gather_runs_launch(p->s_h2d, s.h_cs.d, s.h_cs.cap & ~(size_t)3, s.runs.p, (uint32_t)fi.runs.size(),
+                                   s.data.b.p, fi.len)) != 0) return r2;
+    } else if ((r2 = upload(p->mode, p->s_h2d, s.data.b.p, s.h_cs, (size_t)fi.first, (size_t)fi.len)) != 0) return r2;
     if ((r2 = ojphgpu_decoder_upload_pads(p->s_h2d, (uint8_t*)s.data.b.p, s.h_cs.p, s.cs_len, fi.pads)) != 0) return r2;   // (damaged codestreams only)
     if ((r2 = upload(p->mode, p->s_h2d, s.cb_descs.p, s.h_descs, 0, nb * sizeof(ojphgpu_cb_desc))) != 0) return r2;
     HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
@@ -813,7 +844,7 @@ static void dec_process_frame(ojphgpu_dec_pipe* p, DecSlot& s)
         if (p->pixel_bits) {                           // planes -> the pixel order of the file / display buffer
           uint32_t depth = 0;
           for (const CompGeo& g : P.comps) depth = std::max(depth, g.bit_depth);
-          r3 = ojphgpu_pack_pixels(s_comp, s.image.p, s.pixels.p, P.p.width, P.p.height, P.p.num_comps, p->container, p->pixel_bits,
+          r3 = ojphgpu_pack_pixels(s_comp, s.image.p, s.pixels.p, P.comps[0].w, P.comps[0].h, P.p.num_comps, p->container, p->pixel_bits,
                                    p->big_endian, depth);
           if (r3) return r3;
         }
@@ -883,7 +914,7 @@ extern "C" void ojphgpu_dec_pipe_destroy(ojphgpu_dec_pipe* p)
   for (ojphgpu_decoder* d : p->decs) if (d) ojphgpu_decoder_destroy(d);
   for (DecSlot& s : p->slots) {
     s.h_cs.release(); s.h_descs.release(); s.h_img.release(); s.h_status.release();
-    for (DeviceBuf* b : { &s.data.b, &s.image, &s.cb_descs, &s.status, &s.pixels }) b->release();
+    for (DeviceBuf* b : { &s.data.b, &s.image, &s.cb_descs, &s.status, &s.pixels, &s.runs }) b->release();
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
   }
   for (hipStream_t s : { p->s_h2d, p->s_comps[0], p->s_comps[1], p->s_comps[2], p->s_comps[3], p->s_d2h }) if (s) (void)hipStreamDestroy(s);
@@ -894,6 +925,13 @@ extern "C" void ojphgpu_dec_pipe_destroy(ojphgpu_dec_pipe* p)
 extern "C" int ojphgpu_dec_pipe_create(const uint8_t* h_codestream, size_t len, int resilient, int device, uint32_t depth,
                                         int container_bits, uint32_t host_threads, ojphgpu_dec_pipe** out)
 {
+  return ojphgpu_dec_pipe_create_view(h_codestream, len, resilient, 0, 0, nullptr, device, depth, container_bits, host_threads, out);
+}
+
+extern "C" int ojphgpu_dec_pipe_create_view(const uint8_t* h_codestream, size_t len, int resilient, uint32_t skipped_res_for_data,
+                                             uint32_t skipped_res_for_recon, const uint32_t* region, int device, uint32_t depth,
+                                             int container_bits, uint32_t host_threads, ojphgpu_dec_pipe** out)
+{
   if (!h_codestream || !out || depth < 2 || depth > 16 || (container_bits != 8 && container_bits != 16 && container_bits != 32)) return OJPHGPU_E_INVALID;
   *out = nullptr;
   return no_throw([&]() -> int {
@@ -903,6 +941,13 @@ extern "C" int ojphgpu_dec_pipe_create(const uint8_t* h_codestream, size_t len, 
     struct Owner { ojphgpu_dec_pipe* p; ~Owner() { if (p) ojphgpu_dec_pipe_destroy(p); } } owner{ p };
     int rc = ojphgpu_t2_parse(h_codestream, len, resilient, &p->first);
     if (rc) return rc;
+    // the view: the first plan restricted as a single decoder's would be (the refusals of the two calls are the pipe's)
+    if ((skipped_res_for_data || skipped_res_for_recon) &&
+        (rc = ojphgpu_plan_restrict_resolution(p->first, skipped_res_for_data, skipped_res_for_recon)) != 0) return rc;
+    if (region && (rc = ojphgpu_plan_restrict_region(p->first, region[0], region[1], region[2], region[3])) != 0) return rc;
+    p->skip_data = skipped_res_for_data; p->skip_recon = skipped_res_for_recon; p->has_region = region != nullptr;
+    if (region) memcpy(p->region, region, sizeof(p->region));
+    p->view = p->has_region || skipped_res_for_data || skipped_res_for_recon;
     const Plan& P = p->first->plan;
     p->P = &P; p->device = device; p->container = container_bits; p->depth = depth; p->resilient = resilient;
     if (container_bits != 32) for (const CompGeo& g : P.comps) if (g.bit_depth > (uint32_t)container_bits) return OJPHGPU_E_INVALID;
@@ -936,12 +981,14 @@ extern "C" int ojphgpu_dec_pipe_create(const uint8_t* h_codestream, size_t len, 
     const size_t nb = d->block_ids.size();
     p->frame_bytes = (size_t)P.frame_elems * (size_t)(container_bits / 8);
     p->out_bytes = p->frame_bytes;
+    p->runs_off = (nb * sizeof(ojphgpu_cb_desc) + 63) & ~(size_t)63;   // a view's run table: a run holds a block at least
+    const size_t descs_bytes = p->view ? p->runs_off + nb * sizeof(DecRun) : nb * sizeof(ojphgpu_cb_desc);
     p->slots.resize(depth);
     for (DecSlot& s : p->slots) {
-      if (s.h_cs.reserve(len + len / 4 + (1u << 16)) || s.h_descs.reserve(nb * sizeof(ojphgpu_cb_desc) + 64) ||
+      if (s.h_cs.reserve(len + len / 4 + (1u << 16)) || s.h_descs.reserve(descs_bytes + 64) ||
           s.h_img.reserve(p->frame_bytes + 64) || s.h_status.reserve(nb + 64)) return OJPHGPU_E_NOMEM;
       if (s.data.reserve(len + len / 4 + 64) || s.image.alloc((size_t)P.frame_elems * 4 + 64) || s.cb_descs.alloc(nb * sizeof(ojphgpu_cb_desc) + 64) ||
-          s.status.alloc(nb + 64)) return OJPHGPU_E_NOMEM;
+          s.status.alloc(nb + 64) || (p->view && s.runs.alloc(nb * sizeof(DecRun) + 64))) return OJPHGPU_E_NOMEM;
       HIPCHK(hipMemset(s.status.p, 0, nb + 64));
       for (hipEvent_t* ev : { &s.ev_in, &s.ev_kern, &s.ev_done }) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming | hipEventReleaseToSystem));
     }
@@ -977,6 +1024,7 @@ extern "C" int ojphgpu_dec_pipe_submit(ojphgpu_dec_pipe* p)
   std::lock_guard<std::mutex> lk(p->mu);
   if (s.state != ACQUIRED) return OJPHGPU_E_INVALID;
   s.rc = 0; s.failed = 0; s.t_submit = now_ms();
+  memset(s.view_info, 0, sizeof(s.view_info));
   s.state = SUBMITTED;
   p->work.push_back(si);
   p->n_acq++; p->n_sub++;
@@ -996,6 +1044,7 @@ extern "C" int ojphgpu_dec_pipe_collect(ojphgpu_dec_pipe* p, const void** h_fram
   DecSlot& s = p->slots[p->n_col % p->depth];
   p->cv_done.wait(lk, [&] { return s.state == DONE; });
   p->n_col++;
+  memcpy(p->last_view_info, s.view_info, sizeof(s.view_info)); p->have_view_info = true;
   if (s.rc) { s.state = FREE; return s.rc; }
   s.state = HELD;
   *h_frame = s.h_img.p;
@@ -1047,6 +1096,15 @@ extern "C" int ojphgpu_dec_pipe_plan(ojphgpu_dec_pipe* p, const ojphgpu_plan** p
 {
   if (!p || !plan) return OJPHGPU_E_INVALID;
   *plan = p->first;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_dec_pipe_view_info(ojphgpu_dec_pipe* p, uint64_t out[5])
+{
+  if (!p || !out) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->have_view_info) return OJPHGPU_E_INVALID;
+  memcpy(out, p->last_view_info, sizeof(p->last_view_info));
   return OJPHGPU_OK;
 }
 

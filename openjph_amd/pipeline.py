@@ -193,19 +193,26 @@ class EncoderPipe:
 
 
 class DecoderPipe:
-    def __init__(self, first_codestream: bytes, device=0, depth=4, container=16, host_threads=0, resilient=False, pixels=None, packed=None):
-        """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth"""
+    def __init__(self, first_codestream: bytes, device=0, depth=4, container=16, host_threads=0, resilient=False, pixels=None, packed=None,
+                 skip_res=None, region=None):
+        """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
+        skip_res=n or (for_data, for_recon), region=(x0, y0, w, h): the pipe decodes that view of every frame, as
+        codec.Decoder takes them (ojphgpu_dec_pipe_create_view); .plan, the frames and pixels / packed are the view's"""
         from .codec import _torch
         _torch()
         self.container = int(container)
         self._lib = capi.lib()
         self._h = C.c_void_p()
         buf = np.frombuffer(first_codestream, dtype=np.uint8)
-        check(self._lib.ojphgpu_dec_pipe_create(buf.ctypes.data, len(first_codestream), int(resilient), device, depth,
-                                                self.container, host_threads, C.byref(self._h)), "dec_pipe_create")
+        a, b = (0, 0) if not skip_res else ((skip_res, skip_res) if isinstance(skip_res, int) else skip_res)
+        reg = None if region is None else (C.c_uint32 * 4)(*[int(v) for v in region])
+        check(self._lib.ojphgpu_dec_pipe_create_view(buf.ctypes.data, len(first_codestream), int(resilient), int(a), int(b), reg, device, depth,
+                                                     self.container, host_threads, C.byref(self._h)), "dec_pipe_create")
         h = C.c_void_p()
         check(self._lib.ojphgpu_dec_pipe_plan(self._h, C.byref(h)), "dec_pipe_plan")
         self.plan = Plan(handle=h, owned=False)
+        self.plan.skip = (int(a), int(b))
+        self.plan.region = None if region is None else tuple(int(v) for v in region)
         self.pixels = None
         if pixels is not None:
             check(self._lib.ojphgpu_dec_pipe_set_pixels(self._h, int(pixels[0]), int(bool(pixels[1]))), "dec_pipe_set_pixels")
@@ -267,6 +274,15 @@ class DecoderPipe:
         n = C.c_uint32()
         check(self._lib.ojphgpu_dec_pipe_fused_retries(self._h, C.byref(n)), "dec_pipe_fused_retries")
         return dict(frames=int(out[0]), host_parse_ms=out[1], latency_ms=out[2], host_threads=int(out[3]), fused_retries=int(n.value))
+
+    def view_info(self):
+        """of the frame collected last (ojphgpu_dec_pipe_view_info): dict(blocks = code-blocks decoded, plan_blocks = code-blocks
+        of the codestream, staged_bytes = bytes laid out for the block decoder (a plain pipe's cross PCIe; of a view's, the runs' do, the zeros between
+        them do not), runs (0: a plain
+        pipe, which uploads one byte range), coded_bytes = of the decoded blocks)"""
+        out = (C.c_uint64 * 5)()
+        check(self._lib.ojphgpu_dec_pipe_view_info(self._h, out), "dec_pipe_view_info")
+        return dict(blocks=int(out[0]), plan_blocks=int(out[1]), staged_bytes=int(out[2]), runs=int(out[3]), coded_bytes=int(out[4]))
 
     def decode_sequence(self, codestreams):
         for cs in codestreams:

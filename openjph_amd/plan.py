@@ -3,13 +3,14 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import Params, BandInfo, BlockInfo, LevelInfo, CodedBlock, PaddedBlock, check, PROG_ORDERS
+from .capi import Params, BandInfo, BlockInfo, LevelInfo, CodedBlock, PaddedBlock, Run, check, PROG_ORDERS
 
 band_dtype = np.dtype(BandInfo)
 block_dtype = np.dtype(BlockInfo)
 level_dtype = np.dtype(LevelInfo)
 coded_dtype = np.dtype(CodedBlock)
 padded_dtype = np.dtype(PaddedBlock)
+run_dtype = np.dtype(Run)
 
 
 def make_params(width, height, num_comps=1, bit_depth=8, is_signed=False, reversible=True,
@@ -188,6 +189,16 @@ class Plan:
         if self.num_blocks:
             check(self._lib.ojphgpu_plan_region_blocks(self.handle, out.ctypes.data, self.num_blocks), "plan_region_blocks")
         return out.astype(bool)
+
+    def upload_runs(self):
+        """-> (runs, staged_len): what a view decoder of this parsed plan uploads (ojphgpu_plan_upload_runs) -- runs: run_dtype
+        array (src = offset in the codestream, dst = place in the staged bytes, n), staged_len: the bytes staged"""
+        n, staged = C.c_size_t(), C.c_uint64()
+        check(self._lib.ojphgpu_plan_upload_runs(self.handle, None, 0, C.byref(n), C.byref(staged)), "plan_upload_runs")
+        out = np.zeros(int(n.value), run_dtype)
+        if n.value:
+            check(self._lib.ojphgpu_plan_upload_runs(self.handle, out.ctypes.data, int(n.value), C.byref(n), C.byref(staged)), "plan_upload_runs")
+        return out, int(staged.value)
 
     def comp_info(self, comp):
         """-> dict(x0, y0, w, h, frame_off, dx, dy) of component `comp` (see ojphgpu_plan_comp_info)"""
