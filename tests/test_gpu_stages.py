@@ -29,6 +29,8 @@ def _plane_layout(shapes):
 
 @pytest.mark.parametrize("reversible", [True, False])
 def test_dwt_forward_inverse_vs_oracle(reversible):
+    """arena planes of 15 shapes in one launch, at the one geometry that launch works out to; the launch geometries (chunk
+    height, trip, XCD order), the strip / chunk boundaries and stray stores are covered by tests/test_gpu_dwt_geometry.py"""
     torch = _torch()
     from openjph_amd import codec
     from oracle import oraclebind as ob
