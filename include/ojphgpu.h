@@ -824,6 +824,12 @@ int  ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* pipe, int pixel_bits, int big
  * the plane order of the planar layout): _acquire hands out ceil(samples * bits / 8) bytes rounded up to whole groups
  * of 32 samples.  Unsigned components whose depth fits `bits`, 16- or 32-bit containers.  bits = 0 switches back. */
 int  ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* pipe, int bits);
+/* ... or as one 4:2:2 video buffer (section 7b: format = OJPHGPU_VIDEO_*; 0 switches back to planes): _acquire hands out
+ * the format's frame_bytes (ojphgpu_video_layout) and a launch on the device turns them into the planes
+ * (ojphgpu_unpack_video).  Call before the first _acquire, not together with _set_pixels / _set_packed.
+ * OJPHGPU_E_INVALID unless the pipe's plan has exactly three unsigned components of one bit depth that fits the format and
+ * the container, of sizes (w, h), (ceil(w / 2), h), (ceil(w / 2), h); a refusal leaves the pipe as it was. */
+int  ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* pipe, int format);
 
 /* Every frame of this pipe is coded to a byte budget (section 5b): each collected codestream is, byte for byte, the plain
  * encode of its frame at qstep(j*), with the certificate size(j*) <= budget < size(j* + 1) measured for that frame.
@@ -908,6 +914,11 @@ int  ojphgpu_dec_pipe_fused_retries(ojphgpu_dec_pipe* pipe, uint32_t* count);
  * ojph_img_io.cpp:99-226, :539-556); same conditions as ojphgpu_enc_pipe_set_pixels; call before the first _submit */
 int  ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* pipe, int pixel_bits, int big_endian);
 int  ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* pipe, int bits);     /* decoded frames come back bit-packed, clamped to [0, 2^bits - 1] */
+/* decoded frames come back as one 4:2:2 video buffer (section 7b), clamped to [0, 2^depth - 1]: _collect hands back the
+ * format's frame_bytes.  The conditions of ojphgpu_enc_pipe_set_video, judged on the view's plan when the pipe decodes a
+ * view: a reduced resolution always passes, a region when its planes have those sizes (an even x0 guarantees it).  Call
+ * before the first _submit, not together with _set_pixels / _set_packed; 0 switches back to planes. */
+int  ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* pipe, int format);
 
 /* ---------------------------------------------------------------------------------------------
  * 7. Pixel-interleaved samples <-> planar containers on the device (kernels_pixels.hip)
@@ -928,6 +939,34 @@ int  ojphgpu_pack_pixels(void* stream, const void* d_planes, void* d_pixels, uin
  * such samples in 16-bit words. */
 int  ojphgpu_unpack_bits(void* stream, const void* d_packed, void* d_samples, uint64_t num_samples, int bits, int container_bits);
 int  ojphgpu_pack_bits(void* stream, const void* d_samples, void* d_packed, uint64_t num_samples, int container_bits, int bits);
+/* ---- 7b. 4:2:2 video buffers (kernels_video.hip): the frame as capture cards, SDI / ST 2110 receivers, ffmpeg's rawvideo
+ * and display paths hold it, one packed buffer.  The frame is width x height luma samples; Cb and Cr hold cw = ceil(width /
+ * 2) samples per row; pair k of a row holds Y[2k], Y[2k + 1], Cb[k], Cr[k], and for odd width the last pair's second luma is
+ * padding.  Rows follow each other at row_bytes.
+ *   OJPHGPU_VIDEO_UYVY  bytes Cb Y0 Cr Y1 per pair                                    row_bytes 4 * cw     depth <= 8
+ *   OJPHGPU_VIDEO_YUY2  bytes Y0 Cb Y1 Cr per pair                                    row_bytes 4 * cw     depth <= 8
+ *   OJPHGPU_VIDEO_V210  groups of 6 pixels = four little-endian dwords of three 10-bit fields each (bits 0-9, 10-19, 20-29;
+ *                       bits 30-31 zero): (Cb0, Y0, Cr0) (Y1, Cb1, Y2) (Cr1, Y3, Cb2) (Y4, Cr2, Y5); the row padded with
+ *                       zero groups to a multiple of 48 pixels          row_bytes 128 * ceil(width / 48)   depth <= 10
+ *   OJPHGPU_VIDEO_Y2XX  little-endian 16-bit words Y0 Cb Y1 Cr per pair, the sample in the high `depth` bits (Y210, Y212,
+ *                       Y216)                                                         row_bytes 8 * cw     9 <= depth <= 16
+ * Unpacking: a sample is its field (Y2XX: word >> (16 - depth)); padding fields and groups, bits 30-31 and the low bits of
+ * a Y2XX word are not looked at, no value is range-checked.  Packing: every sample is clamped to [0, 2^depth - 1] as
+ * ojphgpu_pack_pixels does (no "legal range"), a Y2XX sample is shifted up with zero low bits, and every byte of [0,
+ * row_bytes * height) is written -- padding fields, padding groups and bits 30-31 as zero -- and nothing beyond.
+ * d_planes: the frame layout of ojphgpu_plan_comp_info for such a frame -- Y width x height, then Cb and Cr cw x height
+ * each, tightly packed -- in container_bits-bit elements (8: UYVY and YUY2 only; 16; 32).  OJPHGPU_E_INVALID: an unknown
+ * format, a null pointer, a zero size, a bit_depth outside the format's column, a container narrower than bit_depth, a
+ * d_video that is not 16-byte aligned. */
+#define OJPHGPU_VIDEO_UYVY 1
+#define OJPHGPU_VIDEO_YUY2 2
+#define OJPHGPU_VIDEO_V210 3
+#define OJPHGPU_VIDEO_Y2XX 4
+int  ojphgpu_video_layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* frame_bytes);   /* host only */
+int  ojphgpu_unpack_video(void* stream, int format, const void* d_video, void* d_planes, uint32_t width, uint32_t height,
+                          uint32_t bit_depth, int container_bits);
+int  ojphgpu_pack_video(void* stream, int format, const void* d_planes, void* d_video, uint32_t width, uint32_t height,
+                        int container_bits, uint32_t bit_depth);
 /* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
  * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
  * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a

@@ -702,6 +702,44 @@ def unpack_pixels(pixels, num_comps=None, big_endian=False, dtype=None):
     return out
 
 
+def unpack_video(d_buf, fmt, width, height, bit_depth=None, dtype=None, out=None):
+    """a 4:2:2 video buffer on the device (uint8 tensor of the format's frame_bytes, 16-byte aligned; fmt = "uyvy" | "yuy2" |
+    "v210" | "y210" | "y212" | "y216", pipeline.pack_video's layout) -> the frame's planes as ONE flat tensor, Y [H,W] then Cb
+    and Cr [H,ceil(W/2)], in `dtype` (uint8 -- the 8-bit formats only -- / int16 / uint16 / int32; default: uint8 for the
+    8-bit formats, else int16), or in `out` (contiguous, at least that many elements; its dtype is the container).
+    ojphgpu_unpack_video."""
+    from .pipeline import video_format, video_layout
+    torch = _torch()
+    code, b = video_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    n = w * h + 2 * ((w + 1) // 2) * h
+    assert d_buf.is_cuda and d_buf.is_contiguous() and d_buf.numel() * d_buf.element_size() >= video_layout(fmt, w, h)[1]
+    if out is None:
+        out = torch.empty(n, dtype=dtype if dtype is not None else (torch.uint8 if code in (1, 2) else torch.int16), device=d_buf.device)
+    assert out.is_cuda and out.is_contiguous() and out.numel() >= n
+    check(capi.lib().ojphgpu_unpack_video(_stream_ptr(torch, d_buf.device.index or 0), code, C.c_void_p(d_buf.data_ptr()),
+                                          C.c_void_p(out.data_ptr()), w, h, b, out.element_size() * 8), "unpack_video")
+    return out.reshape(-1)[:n]
+
+
+def pack_video(d_planes, fmt, width, height, bit_depth=None, out=None):
+    """the way back: the planes as one flat tensor (the frame layout above; uint8 / int16 / uint16 / int32) -> uint8
+    [H, row_bytes], clamped to [0, 2^bit_depth - 1], every padding position zero; `out`: a contiguous uint8 tensor of at
+    least frame_bytes, 16-byte aligned.  ojphgpu_pack_video."""
+    from .pipeline import video_format, video_layout
+    torch = _torch()
+    code, b = video_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    row, total = video_layout(fmt, w, h)
+    assert d_planes.is_cuda and d_planes.is_contiguous() and d_planes.numel() >= w * h + 2 * ((w + 1) // 2) * h
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=d_planes.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= total
+    check(capi.lib().ojphgpu_pack_video(_stream_ptr(torch, d_planes.device.index or 0), code, C.c_void_p(d_planes.data_ptr()),
+                                        C.c_void_p(out.data_ptr()), w, h, d_planes.element_size() * 8, b), "pack_video")
+    return out.reshape(-1)[:total].reshape(h, row)
+
+
 def pack_pixels(planes, bit_depth, pixel_bits=None, big_endian=False):
     """planes [C,H,W] on the device -> pixel-interleaved [H,W,C] (uint8 for pixel_bits 8, else int16 holding the bytes
     of uint16 samples, byte-swapped when big_endian), clamped to [0, 2^bit_depth - 1] as the reference's writers do."""

@@ -163,6 +163,7 @@ struct ojphgpu_enc_pipe {
   size_t frame_bytes = 0, res_bytes = 0;
   int pixel_bits = 0, big_endian = 0;               // != 0: frames are handed over pixel-interleaved (ojphgpu_enc_pipe_set_pixels)
   int packed_bits = 0;                              // != 0: ... as bit-packed planes (ojphgpu_enc_pipe_set_packed)
+  int video = 0;                                    // != 0: ... as one 4:2:2 video buffer of that format (ojphgpu_enc_pipe_set_video)
   size_t in_bytes = 0;                              // what _acquire hands out: frame_bytes, or the interleaved frame
   uint64_t n_acq = 0, n_sub = 0, n_col = 0;
   std::mutex mu; std::condition_variable cv_work, cv_done;
@@ -487,7 +488,7 @@ static int pixels_fit(const Plan& P, int pixel_bits, int container_bits)
 
 extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian)
 {
-  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->packed_bits) return OJPHGPU_E_INVALID;
+  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->packed_bits || p->video) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (pixel_bits == 0) { p->pixel_bits = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
     const Plan& P = *p->P;
@@ -515,7 +516,7 @@ static int packed_fit(const Plan& P, int bits, int container_bits)
 
 extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits)
 {
-  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits) return OJPHGPU_E_INVALID;
+  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits || p->video) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (bits == 0) { p->packed_bits = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
     const Plan& P = *p->P;
@@ -528,6 +529,41 @@ extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits)
       if (!s.pixels.p && s.pixels.alloc(nbytes + 64)) return OJPHGPU_E_NOMEM;
     }
     p->packed_bits = bits; p->in_bytes = nbytes;
+    return OJPHGPU_OK;
+  });
+}
+
+// the conditions of the 4:2:2 video hand-over (ojphgpu.h section 7b): three unsigned components of one depth that fits the
+// format, the chroma planes half as wide (rounded up) and as high as the luma plane; -> the format's layout of that frame
+static int video_fit(const Plan& P, int format, int container_bits, uint64_t* bytes)
+{
+  if (format < OJPHGPU_VIDEO_UYVY || format > OJPHGPU_VIDEO_Y2XX || P.comps.size() != 3) return OJPHGPU_E_INVALID;
+  const CompGeo& Y = P.comps[0];
+  if (Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
+  const uint32_t cw = (uint32_t)(((uint64_t)Y.w + 1) / 2), b = Y.bit_depth;
+  for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != b) return OJPHGPU_E_INVALID;
+  for (size_t c = 1; c < 3; ++c) if (P.comps[c].w != cw || P.comps[c].h != Y.h) return OJPHGPU_E_INVALID;
+  if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != (uint64_t)Y.w * Y.h + (uint64_t)cw * Y.h) return OJPHGPU_E_INVALID;
+  if (format == OJPHGPU_VIDEO_Y2XX ? (b < 9 || b > 16) : b > (format == OJPHGPU_VIDEO_V210 ? 10u : 8u)) return OJPHGPU_E_INVALID;
+  if (container_bits == 8 && format != OJPHGPU_VIDEO_UYVY && format != OJPHGPU_VIDEO_YUY2) return OJPHGPU_E_INVALID;
+  uint32_t row_bytes = 0;
+  return ojphgpu_video_layout(format, Y.w, Y.h, &row_bytes, bytes);
+}
+
+extern "C" int ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* p, int format)
+{
+  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits || p->packed_bits) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    if (format == 0) { p->video = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
+    uint64_t nbytes = 0;
+    const int rc = video_fit(*p->P, format, p->container, &nbytes);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    for (EncSlot& s : p->slots) {
+      if (s.h_in.reserve((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM;
+      if (!s.pixels.p || s.pixels.n < (size_t)nbytes + 64) { s.pixels.release(); if (s.pixels.alloc((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM; }
+    }
+    p->video = format; p->in_bytes = (size_t)nbytes;
     return OJPHGPU_OK;
   });
 }
@@ -545,6 +581,11 @@ static int enc_unpack(ojphgpu_enc_pipe* p, EncSlot& s)
     const int r0 = ojphgpu_unpack_bits(p->s_comp, s.pixels.p, s.image.p, p->P->frame_elems, p->packed_bits, p->container);
     if (r0) return r0;
   }
+  if (p->video) {
+    const CompGeo& Y = p->P->comps[0];
+    const int r0 = ojphgpu_unpack_video(p->s_comp, p->video, s.pixels.p, s.image.p, Y.w, Y.h, Y.bit_depth, p->container);
+    if (r0) return r0;
+  }
   return OJPHGPU_OK;
 }
 
@@ -557,7 +598,7 @@ extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
   HIPCHK(hipSetDevice(p->device));
   ojphgpu_encoder* e = p->enc;
   s.rc = 0; s.cs_len = 0; s.t_submit = now_ms();
-  { const int r0 = upload(p->mode, p->s_h2d, (p->pixel_bits || p->packed_bits) ? s.pixels.p : s.image.p, s.h_in, 0, p->in_bytes); if (r0) return r0; }
+  { const int r0 = upload(p->mode, p->s_h2d, (p->pixel_bits || p->packed_bits || p->video) ? s.pixels.p : s.image.p, s.h_in, 0, p->in_bytes); if (r0) return r0; }
   HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
   if (p->searching()) {                              // everything on the compute stream is the search worker's, frame by frame
     std::lock_guard<std::mutex> lk(p->mu);
@@ -768,6 +809,7 @@ struct ojphgpu_dec_pipe {
   size_t frame_bytes = 0;
   int pixel_bits = 0, big_endian = 0;               // != 0: frames come back pixel-interleaved (ojphgpu_dec_pipe_set_pixels)
   int packed_bits = 0;                              // != 0: ... bit-packed (ojphgpu_dec_pipe_set_packed)
+  int video = 0;                                    // != 0: ... as one 4:2:2 video buffer of that format (ojphgpu_dec_pipe_set_video)
   size_t out_bytes = 0;
   uint64_t n_acq = 0, n_sub = 0, n_col = 0;
   std::mutex mu; std::condition_variable cv_work, cv_done;
@@ -849,10 +891,12 @@ static void dec_process_frame(ojphgpu_dec_pipe* p, DecSlot& s)
           if (r3) return r3;
         }
         if (p->packed_bits && (r3 = ojphgpu_pack_bits(s_comp, s.image.p, s.pixels.p, P.frame_elems, p->container, p->packed_bits)) != 0) return r3;
+        if (p->video && (r3 = ojphgpu_pack_video(s_comp, p->video, s.image.p, s.pixels.p, P.comps[0].w, P.comps[0].h, p->container,
+                                                 P.comps[0].bit_depth)) != 0) return r3;
         HIPCHK(hipEventRecord(s.ev_kern, s_comp));
       }
       HIPCHK(hipStreamWaitEvent(p->s_d2h, s.ev_kern, 0));
-      if ((r3 = download(p->mode, p->s_d2h, s.h_img, (p->pixel_bits || p->packed_bits) ? s.pixels.p : s.image.p, p->out_bytes)) != 0) return r3;       // beside the next frame's upload
+      if ((r3 = download(p->mode, p->s_d2h, s.h_img, (p->pixel_bits || p->packed_bits || p->video) ? s.pixels.p : s.image.p, p->out_bytes)) != 0) return r3;       // beside the next frame's upload
       if ((r3 = download(p->mode, p->s_d2h, s.h_status, s.status.p, st_bytes)) != 0) return r3;
       HIPCHK(hipEventRecord(s.ev_done, p->s_d2h));
       HIPCHK(hipEventSynchronize(s.ev_done));
@@ -1055,7 +1099,7 @@ extern "C" int ojphgpu_dec_pipe_collect(ojphgpu_dec_pipe* p, const void** h_fram
 
 extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, int big_endian)
 {
-  if (!p || p->n_sub != 0 || p->packed_bits) return OJPHGPU_E_INVALID;
+  if (!p || p->n_sub != 0 || p->packed_bits || p->video) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (pixel_bits == 0) { p->pixel_bits = 0; p->out_bytes = p->frame_bytes; return OJPHGPU_OK; }
     const Plan& P = *p->P;
@@ -1075,7 +1119,7 @@ extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, 
 
 extern "C" int ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* p, int bits)
 {
-  if (!p || p->n_sub != 0 || p->pixel_bits) return OJPHGPU_E_INVALID;
+  if (!p || p->n_sub != 0 || p->pixel_bits || p->video) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (bits == 0) { p->packed_bits = 0; p->out_bytes = p->frame_bytes; return OJPHGPU_OK; }
     const Plan& P = *p->P;
@@ -1088,6 +1132,25 @@ extern "C" int ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* p, int bits)
       if (!s.pixels.p && s.pixels.alloc(nbytes + 64)) return OJPHGPU_E_NOMEM;
     }
     p->packed_bits = bits; p->out_bytes = nbytes;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* p, int format)
+{
+  if (!p || p->n_sub != 0 || p->pixel_bits || p->packed_bits) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    if (format == 0) { p->video = 0; p->out_bytes = p->frame_bytes; return OJPHGPU_OK; }
+    uint64_t nbytes = 0;
+    const int rc = video_fit(*p->P, format, p->container, &nbytes);
+    if (rc) return rc;
+    if (p->has_region && (p->region[0] & 1u)) return OJPHGPU_E_INVALID;   // (a window's first column must open a pair)
+    HIPCHK(hipSetDevice(p->device));
+    for (DecSlot& s : p->slots) {
+      if (s.h_img.reserve((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM;
+      if (!s.pixels.p || s.pixels.n < (size_t)nbytes + 64) { s.pixels.release(); if (s.pixels.alloc((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM; }
+    }
+    p->video = format; p->out_bytes = (size_t)nbytes;
     return OJPHGPU_OK;
   });
 }

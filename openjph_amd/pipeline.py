@@ -46,12 +46,98 @@ def unpack_bits(packed, bits, n):
     return (b << np.arange(bits, dtype=np.uint32)[None, :]).sum(axis=1).astype(np.uint32)
 
 
+# 4:2:2 video buffers (ojphgpu.h section 7b): name -> (OJPHGPU_VIDEO_* constant, the depth the name fixes or None)
+VIDEO_FORMATS = {"uyvy": (1, None), "yuy2": (2, None), "v210": (3, None), "y2xx": (4, None), "y210": (4, 10), "y212": (4, 12), "y216": (4, 16)}
+
+
+def video_format(fmt, bit_depth):
+    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a format name, refused when the depth is outside the format's column"""
+    if fmt not in VIDEO_FORMATS:
+        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS))))
+    code, fixed = VIDEO_FORMATS[fmt]
+    b = int(fixed if bit_depth is None else bit_depth)
+    lo, hi = {1: (1, 8), 2: (1, 8), 3: (1, 10), 4: (9, 16)}[code]
+    if not lo <= b <= hi or (fixed is not None and b != fixed):
+        raise ValueError("video format %r does not hold %d-bit samples" % (fmt, b))
+    return code, b
+
+
+def _video_code(plan, fmt, what):
+    """the constant a pipe's _set_video takes for a format name (None: 0, planes); a name that fixes a depth the plan's
+    samples do not have is refused here as the library refuses the rest"""
+    if fmt is None:
+        return 0
+    if fmt not in VIDEO_FORMATS:
+        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS))))
+    code, fixed = VIDEO_FORMATS[fmt]
+    if fixed is not None and plan.comp_format(0)[0] != fixed:
+        raise capi.OjphError(capi.E_INVALID, "%s: %r on %d-bit samples" % (what, fmt, plan.comp_format(0)[0]))
+    return code
+
+
+def video_layout(fmt, width, height):
+    """-> (row_bytes, frame_bytes) of a width x height frame, as ojphgpu_video_layout"""
+    code, cw = VIDEO_FORMATS[fmt][0], (int(width) + 1) // 2
+    if width < 1 or height < 1:
+        raise ValueError("video_layout: a frame has at least one sample")
+    row = {1: 4 * cw, 2: 4 * cw, 3: 128 * ((int(width) + 47) // 48), 4: 8 * cw}[code]
+    return row, row * int(height)
+
+
+def pack_video(planes, fmt, bit_depth=None):
+    """numpy: planes = [Y [H,W], Cb [H,cw], Cr [H,cw]] (cw = ceil(W / 2)) -> the frame as one 4:2:2 video buffer, uint8
+    [H, row_bytes]: the host-side statement of ojphgpu_pack_video.  Samples are clamped to [0, 2^bit_depth - 1]; padding
+    (the second luma of an odd row's last pair, the fields and groups a v210 row is padded with, bits 30-31 of a v210 dword,
+    the low bits of a Y2XX word) is zero."""
+    code, b = video_format(fmt, bit_depth)
+    y, cb, cr = [np.clip(np.asarray(p).astype(np.int64), 0, (1 << b) - 1) for p in planes]
+    h, w = y.shape
+    cw = (w + 1) // 2
+    if cb.shape != (h, cw) or cr.shape != (h, cw):
+        raise ValueError("pack_video: chroma planes of %s, not %s" % (cb.shape, (h, cw)))
+    np_ = 24 * ((w + 47) // 48) if code == 3 else cw          # pairs of a row, with the padding of v210
+    f = np.zeros((h, np_, 4), np.int64)                        # the pairs as Y0 Y1 Cb Cr
+    f[:, :cw, 0][:, : (w + 1) // 2] = y[:, 0::2]
+    f[:, : w // 2, 1] = y[:, 1::2]
+    f[:, :cw, 2], f[:, :cw, 3] = cb, cr
+    if code in (1, 2):
+        return f[:, :, [2, 0, 3, 1] if code == 1 else [0, 2, 1, 3]].astype(np.uint8).reshape(h, 4 * cw)
+    if code == 4:
+        return np.ascontiguousarray((f[:, :, [0, 2, 1, 3]] << (16 - b)).astype("<u2")).view(np.uint8).reshape(h, 8 * cw)
+    t = f[:, :, [2, 0, 3, 1]].reshape(h, np_ * 4 // 3, 3)      # v210: the fields in order Cb Y0 Cr Y1, three to a dword
+    return np.ascontiguousarray((t[:, :, 0] | t[:, :, 1] << 10 | t[:, :, 2] << 20).astype("<u4")).view(np.uint8).reshape(h, -1)
+
+
+def unpack_video(buf, fmt, width, height, bit_depth=None):
+    """numpy inverse of pack_video: the bytes of a 4:2:2 video buffer -> [Y [H,W], Cb [H,cw], Cr [H,cw]] (uint16).  A sample
+    is its field (Y2XX: word >> (16 - bit_depth)); padding is not looked at and no value is range-checked."""
+    code, b = video_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    cw = (w + 1) // 2
+    row, total = video_layout(fmt, w, h)
+    raw = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if raw.size != total:
+        raise ValueError("unpack_video: %d bytes, the frame has %d" % (raw.size, total))
+    raw = raw.reshape(h, row)
+    if code in (1, 2):
+        f = raw.reshape(h, cw, 4)[:, :, [1, 3, 0, 2] if code == 1 else [0, 2, 1, 3]].astype(np.uint16)
+    elif code == 4:
+        f = (raw.view("<u2").reshape(h, cw, 4)[:, :, [0, 2, 1, 3]] >> (16 - b)).astype(np.uint16)
+    else:
+        d = raw.view("<u4")
+        t = np.stack([d & 0x3FF, (d >> 10) & 0x3FF, (d >> 20) & 0x3FF], axis=2).reshape(h, -1, 4)   # pairs as Cb Y0 Cr Y1
+        f = t[:, :cw, [1, 3, 0, 2]].astype(np.uint16)
+    y = f[:, :, :2].reshape(h, 2 * cw)[:, :w]
+    return [np.ascontiguousarray(y), np.ascontiguousarray(f[:, :, 2]), np.ascontiguousarray(f[:, :, 3])]
+
+
 class EncoderPipe:
     def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None,
-                 max_sse=None, min_psnr=None, **kw):
+                 max_sse=None, min_psnr=None, video=None, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
-        the device.  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
+        the device.  video="uyvy" | "yuy2" | "v210" | "y210" | "y212" | "y216": the frames are handed over as one 4:2:2 video
+        buffer (uint8 [H, row_bytes], pack_video's layout) and unpacked on the device.  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
         quality target (set_quality) -- one or the other"""
         from .codec import _torch
         _torch()
@@ -70,11 +156,22 @@ class EncoderPipe:
         if packed:                                        # planes of bit-packed samples (10 / 12 / 14 bits): acquire() -> uint8 view
             check(self._lib.ojphgpu_enc_pipe_set_packed(self._h, int(packed)), "enc_pipe_set_packed")
             self.packed = int(packed)
+        self.video = None
+        if video is not None:                             # one 4:2:2 video buffer: acquire() -> uint8 [H, row_bytes]
+            self.set_video(video)
         if max_bytes:
             self.set_budget(max_bytes)
         if max_sse is not None or min_psnr is not None:
             self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
         self.in_flight = 0
+
+    def set_video(self, fmt):
+        """frames are handed over as 4:2:2 video buffers of that format (ojphgpu_enc_pipe_set_video; None: planes again).
+        Before the first acquire(), not together with pixels / packed; a plan that is not three unsigned components of one
+        depth the format holds, the chroma half as wide, raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
+        code = _video_code(self.plan, fmt, "enc_pipe_set_video")
+        check(self._lib.ojphgpu_enc_pipe_set_video(self._h, code), "enc_pipe_set_video")
+        self.video = fmt
 
     def set_budget(self, max_bytes):
         """Every frame is coded at the finest step of the rate grid whose codestream is at most max_bytes long, the search
@@ -138,6 +235,9 @@ class EncoderPipe:
         check(rc, "enc_pipe_acquire")
         if self.packed:
             return _view(ptr.value, n.value, np.uint8)
+        if self.video:
+            h = self.plan.comp_info(0)["h"]
+            return _view(ptr.value, n.value, np.uint8).reshape(h, n.value // h)
         if self.pixels is not None:                     # [H,W,C] in the file's sample type (big endian: the raw bytes)
             c, h, w = self.plan.frame_shape
             dt = np.uint8 if self.pixels[0] == 8 else np.dtype(">u2" if self.pixels[1] else "<u2")
@@ -194,9 +294,10 @@ class EncoderPipe:
 
 class DecoderPipe:
     def __init__(self, first_codestream: bytes, device=0, depth=4, container=16, host_threads=0, resilient=False, pixels=None, packed=None,
-                 skip_res=None, region=None):
+                 skip_res=None, region=None, video=None):
         """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
         skip_res=n or (for_data, for_recon), region=(x0, y0, w, h): the pipe decodes that view of every frame, as
+        video="uyvy" | ...: they come back as one 4:2:2 video buffer (uint8 [H, row_bytes], pack_video of the planes).
         codec.Decoder takes them (ojphgpu_dec_pipe_create_view); .plan, the frames and pixels / packed are the view's"""
         from .codec import _torch
         _torch()
@@ -221,7 +322,18 @@ class DecoderPipe:
         if packed:
             check(self._lib.ojphgpu_dec_pipe_set_packed(self._h, int(packed)), "dec_pipe_set_packed")
             self.packed = int(packed)
+        self.video = None
+        if video is not None:
+            self.set_video(video)
         self.in_flight = 0
+
+    def set_video(self, fmt):
+        """decoded frames come back as 4:2:2 video buffers of that format (ojphgpu_dec_pipe_set_video; None: planes again).
+        Before the first submit(), not together with pixels / packed; judged on the view's plan (a region with odd x0 is
+        refused); a refusal raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
+        code = _video_code(self.plan, fmt, "dec_pipe_set_video")
+        check(self._lib.ojphgpu_dec_pipe_set_video(self._h, code), "dec_pipe_set_video")
+        self.video = fmt
 
     def close(self):
         if self._h:
@@ -256,6 +368,9 @@ class DecoderPipe:
             check(rc, "dec_pipe_collect")
         if self.packed:
             v = _view(ptr.value, n.value, np.uint8)
+        elif self.video:
+            h = self.plan.comp_info(0)["h"]
+            v = _view(ptr.value, n.value, np.uint8).reshape(h, n.value // h)
         elif self.pixels is not None:
             c, h, w = self.plan.frame_shape
             dt = np.uint8 if self.pixels[0] == 8 else np.dtype(">u2" if self.pixels[1] else "<u2")
