@@ -818,15 +818,20 @@ int  ojphgpu_enc_pipe_stats(ojphgpu_enc_pipe* pipe, double out[4]);
  * sample, 16-bit samples big endian (as in the files) when big_endian != 0.  _acquire then hands out width * height *
  * components * pixel_bits / 8 bytes, and a launch on the device turns them into the planar containers
  * (ojphgpu_unpack_pixels).  Components must have one size and be unsigned, pixel_bits must hold the bit depth and
- * must not exceed container_bits.  Call before the first _acquire; pixel_bits = 0 switches back to planes. */
+ * must not exceed container_bits.  Call before the first _acquire; until then the call may be repeated with a different
+ * value (the buffers follow), and pixel_bits = 0 switches back to planes.  The three hand-overs -- this one, _set_packed,
+ * _set_video -- exclude each other: while one is on, the setters of the other two return OJPHGPU_E_INVALID whatever their
+ * argument, 0 included.  A refusal leaves the pipe as it was. */
 int  ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* pipe, int pixel_bits, int big_endian);
 /* ... or as planes of bit-packed samples (ojphgpu_unpack_bits: bits = 10, 12, 14; the whole frame one bit string in
  * the plane order of the planar layout): _acquire hands out ceil(samples * bits / 8) bytes rounded up to whole groups
- * of 32 samples.  Unsigned components whose depth fits `bits`, 16- or 32-bit containers.  bits = 0 switches back. */
+ * of 32 samples.  Unsigned components whose depth fits `bits`, 16- or 32-bit containers.  Before the first _acquire,
+ * repeatable until then with a different value; bits = 0 switches back. */
 int  ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* pipe, int bits);
 /* ... or as one 4:2:2 video buffer (section 7b: format = OJPHGPU_VIDEO_*; 0 switches back to planes): _acquire hands out
  * the format's frame_bytes (ojphgpu_video_layout) and a launch on the device turns them into the planes
- * (ojphgpu_unpack_video).  Call before the first _acquire, not together with _set_pixels / _set_packed.
+ * (ojphgpu_unpack_video).  Call before the first _acquire -- until then the call may be repeated with a different format --
+ * not together with _set_pixels / _set_packed.
  * OJPHGPU_E_INVALID unless the pipe's plan has exactly three unsigned components of one bit depth that fits the format and
  * the container, of sizes (w, h), (ceil(w / 2), h), (ceil(w / 2), h); a refusal leaves the pipe as it was. */
 int  ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* pipe, int format);
@@ -911,7 +916,9 @@ int  ojphgpu_dec_pipe_stats(ojphgpu_dec_pipe* pipe, double out[4]);
 int  ojphgpu_dec_pipe_fused_retries(ojphgpu_dec_pipe* pipe, uint32_t* count);
 /* decoded frames come back pixel-interleaved, clamped to [0, 2^depth - 1] -- ONE depth for the frame: the components
  * must share their bit depth (a .ppm has one maxval), otherwise OJPHGPU_E_INVALID -- (ppm_out::write and its converters,
- * ojph_img_io.cpp:99-226, :539-556); same conditions as ojphgpu_enc_pipe_set_pixels; call before the first _submit */
+ * ojph_img_io.cpp:99-226, :539-556); same conditions as ojphgpu_enc_pipe_set_pixels; call before the first _submit.  For
+ * all three setters of a decoder pipe: until then the call may be repeated with a different value, and they exclude each
+ * other as the encoder pipe's do. */
 int  ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* pipe, int pixel_bits, int big_endian);
 int  ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* pipe, int bits);     /* decoded frames come back bit-packed, clamped to [0, 2^bits - 1] */
 /* decoded frames come back as one 4:2:2 video buffer (section 7b), clamped to [0, 2^depth - 1]: _collect hands back the

@@ -117,6 +117,124 @@ double now_ms()
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// The worker loops: the next slot of a queue, or false once `stop` is up and the queue is empty.
+bool pop_work(std::mutex& mu, std::condition_variable& cv, std::deque<uint32_t>& q, const bool& stop, uint32_t& si)
+{
+  std::unique_lock<std::mutex> lk(mu);
+  cv.wait(lk, [&] { return stop || !q.empty(); });
+  if (q.empty()) return false;
+  si = q.front(); q.pop_front();
+  return true;
+}
+
+// ---- the hand-over: how a frame crosses PCIe -- the encoder's going in, the decoder's coming out.  PLANES: as the codec
+// holds it, straight into / out of the slot's image.  The other kinds go through the slot's staging buffer (`pixels`) and a
+// launch on the compute stream: PIXELS pixel-interleaved (_set_pixels), PACKED one bit string (_set_packed), VIDEO one 4:2:2
+// video buffer (_set_video, ojphgpu.h section 7b).  A pipe has one; everything the launch needs is fixed when it is set.
+enum HandoverKind { PLANES = 0, PIXELS, PACKED, VIDEO };
+
+struct Handover {
+  int kind = PLANES;
+  int bits = 0, big_endian = 0;                      // PIXELS: 8 / 16 per sample; PACKED: 10 / 12 / 14
+  int format = 0;                                    // VIDEO: OJPHGPU_VIDEO_*
+  uint32_t w = 0, h = 0, depth = 0;                  // PIXELS, VIDEO: the (luma) plane; the depth a decoder clamps to
+  size_t bytes = 0;                                  // of a frame as handed over: what _acquire / _collect report and PCIe carries
+};
+
+// Every refusal of the three setters, and the size of the frame: `want` (kind, bits, big_endian, format) -> the rest of it.
+// decoding: the frame comes back, clamped to one range; odd_x0: the pipe decodes a window whose first column is odd.
+int handover_fit(const Plan& P, int container, bool decoding, bool odd_x0, Handover& want)
+{
+  const CompGeo& Y = P.comps[0];
+  want.w = Y.w; want.h = Y.h; want.depth = 0;
+  for (const CompGeo& g : P.comps) want.depth = std::max(want.depth, g.bit_depth);
+  switch (want.kind) {
+  case PLANES:
+    want.bytes = (size_t)P.frame_elems * (size_t)(container / 8);
+    return OJPHGPU_OK;
+  case PIXELS:                                        // one size for all components (so every plane is w x h), unsigned, depths that fit
+    if ((want.bits != 8 && want.bits != 16) || want.bits > container) return OJPHGPU_E_INVALID;
+    if (P.skip_recon || P.has_region) {               // a view's frame (a decoder pipe): planes of one size
+      for (const CompGeo& g : P.comps) if (g.w != Y.w || g.h != Y.h || g.w == 0 || g.h == 0) return OJPHGPU_E_INVALID;
+    } else if (P.frame_elems != (uint64_t)P.p.width * P.p.height * P.p.num_comps) return OJPHGPU_E_INVALID;   // sub-sampled components
+    for (const CompGeo& g : P.comps) {
+      if (g.is_signed || g.bit_depth > (uint32_t)want.bits) return OJPHGPU_E_INVALID;
+      if (decoding && g.bit_depth != Y.bit_depth) return OJPHGPU_E_INVALID;   // one clamp range per frame
+    }
+    want.bytes = (size_t)P.frame_elems * (size_t)(want.bits / 8);
+    return OJPHGPU_OK;
+  case PACKED:
+    if ((want.bits != 10 && want.bits != 12 && want.bits != 14) || (container != 16 && container != 32)) return OJPHGPU_E_INVALID;
+    for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth > (uint32_t)want.bits) return OJPHGPU_E_INVALID;
+    want.bytes = (size_t)((P.frame_elems + 31) / 32) * 4u * (size_t)want.bits;
+    return OJPHGPU_OK;
+  case VIDEO: {
+    // three unsigned components of one depth that fits the format, the chroma planes half as wide (rounded up) and as high
+    // as the luma plane, tightly packed; -> the format's layout of that frame
+    const int format = want.format;
+    if (format < OJPHGPU_VIDEO_UYVY || format > OJPHGPU_VIDEO_Y2XX || P.comps.size() != 3) return OJPHGPU_E_INVALID;
+    if (Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
+    const uint32_t cw = (uint32_t)(((uint64_t)Y.w + 1) / 2), b = Y.bit_depth;
+    for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != b) return OJPHGPU_E_INVALID;
+    for (size_t c = 1; c < 3; ++c) if (P.comps[c].w != cw || P.comps[c].h != Y.h) return OJPHGPU_E_INVALID;
+    if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != (uint64_t)Y.w * Y.h + (uint64_t)cw * Y.h) return OJPHGPU_E_INVALID;
+    if (format == OJPHGPU_VIDEO_Y2XX ? (b < 9 || b > 16) : b > (format == OJPHGPU_VIDEO_V210 ? 10u : 8u)) return OJPHGPU_E_INVALID;
+    if (container == 8 && format != OJPHGPU_VIDEO_UYVY && format != OJPHGPU_VIDEO_YUY2) return OJPHGPU_E_INVALID;
+    uint32_t row_bytes = 0; uint64_t bytes = 0;
+    const int rc = ojphgpu_video_layout(format, Y.w, Y.h, &row_bytes, &bytes);
+    if (rc) return rc;
+    if (odd_x0) return OJPHGPU_E_INVALID;             // (a window's first column must open a pair)
+    want.bytes = (size_t)bytes;
+    return OJPHGPU_OK;
+  }
+  }
+  return OJPHGPU_E_INVALID;
+}
+
+// The launch of a hand-over on `stream`: staged frame -> planes (unpack: the encoder) or planes -> staged frame, clamped
+// (the decoder).  Nothing for PLANES.
+int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int container, bool unpack, void* d_staged, void* d_planes)
+{
+  switch (h.kind) {
+  case PIXELS:                                        // the file's / capture buffer's / display buffer's pixel order
+    return unpack ? ojphgpu_unpack_pixels(stream, d_staged, d_planes, h.w, h.h, P.p.num_comps, h.bits, h.big_endian, container)
+                  : ojphgpu_pack_pixels(stream, d_planes, d_staged, h.w, h.h, P.p.num_comps, container, h.bits, h.big_endian, h.depth);
+  case PACKED:
+    return unpack ? ojphgpu_unpack_bits(stream, d_staged, d_planes, P.frame_elems, h.bits, container)
+                  : ojphgpu_pack_bits(stream, d_planes, d_staged, P.frame_elems, container, h.bits);
+  case VIDEO:
+    return unpack ? ojphgpu_unpack_video(stream, h.format, d_staged, d_planes, h.w, h.h, h.depth, container)
+                  : ojphgpu_pack_video(stream, h.format, d_planes, d_staged, h.w, h.h, container, h.depth);
+  }
+  return OJPHGPU_OK;
+}
+
+// the device buffer of a slot that the PCIe copy of the frame touches
+template <class Slot> void* handover_device_side(const Handover& h, Slot& s) { return h.kind == PLANES ? s.image.p : s.pixels.b.p; }
+
+// The three setters of a pipe, after their own precondition.  `kind`: the setter's, arg: its bits / format (0: planes
+// again); frame: the slot's pinned frame.  Refused while another kind is on, and by handover_fit; then every slot's pinned
+// frame and staging buffer hold the new size -- both only grow, so the call may be repeated -- and the pipe takes the
+// hand-over.  A refusal changes nothing.
+template <class Pipe, class Slot>
+int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, bool odd_x0, int kind, int arg, int big_endian)
+{
+  if (p->ho.kind != PLANES && p->ho.kind != kind) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    Handover h;
+    h.kind = arg ? kind : PLANES; h.big_endian = big_endian ? 1 : 0;
+    (kind == VIDEO ? h.format : h.bits) = arg;
+    const int rc = handover_fit(*p->P, p->container, decoding, odd_x0, h);
+    if (rc) return rc;
+    if (h.kind != PLANES) {
+      HIPCHK(hipSetDevice(p->device));
+      for (Slot& s : p->slots) if ((s.*frame).reserve(h.bytes + 64) || s.pixels.reserve(h.bytes)) return OJPHGPU_E_NOMEM;
+    }
+    p->ho = h;
+    return OJPHGPU_OK;
+  });
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -129,27 +247,36 @@ struct EncOut {
   Pinned h_res;
   DeviceBuf out, counters;
   void release() { h_res.release(); out.release(); counters.release(); }
+  // where a coding of nb blocks into this set lands: the records, then the two published words; `done`: recorded behind a trial
+  RateTrialOut trial(size_t nb, hipEvent_t done) const {
+    const size_t words = nb * sizeof(ojphgpu_cb_result);
+    return RateTrialOut{ out.p, (ojphgpu_cb_result*)h_res.d, (uint32_t*)counters.p, (const ojphgpu_cb_result*)h_res.p,
+                         (uint32_t*)(h_res.d + words), (const uint32_t*)(h_res.p + words), done };
+  }
+};
+
+// What the search of a frame found (a pipe with a byte budget: rate; with a quality target: quality, the first index it
+// tried and the figures of every component at j*).  A slot holds its frame's; the pipe, the frame's collected last.
+struct EncSearchResult {
+  ojphgpu_rate_info rate{}; bool have_rate = false;
+  ojphgpu_quality_info quality{}; uint32_t first_guess = 0; bool have_quality = false;
+  std::vector<ojphgpu_frame_err> comps;
 };
 
 struct EncSlot {
   SlotState state = FREE;
   Pinned h_in, h_lay, h_cs;
   EncOut o;
-  DeviceBuf image, pixels;                          // pixels: the frame as it was handed over, when it comes pixel-interleaved
-  Grow cs;
+  DeviceBuf image;
+  Grow cs, pixels;                                  // pixels: the frame as it was handed over, unless that is as planes
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   int rc = 0; size_t cs_len = 0;
   double t_submit = 0, t_done = 0, t_t2 = 0;
-  // a pipe with a byte budget: the frame's budget, what its search found, and the plan at the step it chose (the
-  // finisher lays the codestream out from it while the worker re-quantises for the next frame)
-  uint64_t budget = 0;
+  // a pipe that searches: the frame's byte budget or quality target, what its search found, and the plan at the step it
+  // chose (the finisher lays the codestream out from it while the worker re-quantises for the next frame)
+  uint64_t budget = 0, target = 0;
   ojphgpu_plan* rplan = nullptr;
-  ojphgpu_rate_info info{}; bool have_info = false;
-  // a pipe with a quality target: the frame's target, what its search found, the first index it tried and the figures of
-  // every component at j* (rplan as above: the plan at qstep(j*))
-  uint64_t target = 0;
-  ojphgpu_quality_info qinfo{}; uint32_t first_guess = 0; bool have_qinfo = false;
-  std::vector<ojphgpu_frame_err> qcomps;
+  EncSearchResult found;
 };
 
 struct ojphgpu_enc_pipe {
@@ -161,10 +288,7 @@ struct ojphgpu_enc_pipe {
   hipStream_t s_h2d = nullptr, s_comp = nullptr, s_d2h = nullptr;
   std::vector<EncSlot> slots;
   size_t frame_bytes = 0, res_bytes = 0;
-  int pixel_bits = 0, big_endian = 0;               // != 0: frames are handed over pixel-interleaved (ojphgpu_enc_pipe_set_pixels)
-  int packed_bits = 0;                              // != 0: ... as bit-packed planes (ojphgpu_enc_pipe_set_packed)
-  int video = 0;                                    // != 0: ... as one 4:2:2 video buffer of that format (ojphgpu_enc_pipe_set_video)
-  size_t in_bytes = 0;                              // what _acquire hands out: frame_bytes, or the interleaved frame
+  Handover ho;                                      // how frames are handed over; ho.bytes: what _acquire hands out
   uint64_t n_acq = 0, n_sub = 0, n_col = 0;
   std::mutex mu; std::condition_variable cv_work, cv_done;
   std::deque<uint32_t> work; bool stop = false;
@@ -172,20 +296,18 @@ struct ojphgpu_enc_pipe {
   double sum_t2 = 0, sum_latency = 0; uint64_t n_done = 0;
   // byte budget (ojphgpu_enc_pipe_set_budget): on from before the first _acquire, or never
   bool budget_on = false;
-  bool dead = false;                                // switching the budget on failed half way: nothing more runs on this pipe
+  bool dead = false;                                // switching a search on failed half way (enc_search_on): nothing more runs on this pipe
   uint64_t max_bytes = 0;                           // the budget the next _submit gives its frame
   EncOut spare;
   Pinned h_hist;                                    // the band statistics of the frame being searched (the worker's)
   hipEvent_t ev_trial = nullptr;
   int hint = -1;                                    // j* of the last frame that was certified
-  ojphgpu_rate_info last_info{}; bool have_last_info = false;   // of the frame collected last
+  EncSearchResult last;                             // of the frame collected last
   // quality target (ojphgpu_enc_pipe_set_quality): the same rules, never together with a budget
   bool quality_on = false;
   uint64_t max_sse = 0;                             // the target the next _submit gives its frame
   Pinned h_qdescs, h_qerr;                          // a trial's requantise descriptors going out, its error words coming back
   std::vector<std::vector<ojphgpu_frame_err>> q_by_index;   // the figures of every index the search of the worker's frame tried
-  ojphgpu_quality_info last_qinfo{}; uint32_t last_first_guess = 0; bool have_last_qinfo = false;
-  std::vector<ojphgpu_frame_err> last_qcomps;
   // the ordered worker of a pipe that searches, whichever search it is: it owns the compute stream
   bool searching() const { return budget_on || quality_on; }
   std::deque<uint32_t> search_work; bool stop_search = false;
@@ -202,9 +324,9 @@ static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
   if (hipEventSynchronize(s.ev_kern) != hipSuccess) return fail(OJPHGPU_E_HIP);
   const double t0 = now_ms();
   const size_t nb = e->block_ids.size();
-  const ojphgpu_cb_result* res = (const ojphgpu_cb_result*)s.o.h_res.p;
-  const uint32_t* cnt = (const uint32_t*)(s.o.h_res.p + nb * sizeof(ojphgpu_cb_result));
-  if (cnt[1]) return fail(OJPHGPU_E_OVERFLOW);
+  const RateTrialOut coded = s.o.trial(nb, nullptr);
+  const ojphgpu_cb_result* res = coded.h_results;
+  if (coded.h_publish[1]) return fail(OJPHGPU_E_OVERFLOW);
   int rc = no_throw([&]() -> int {
     std::vector<ojphgpu_coded_block> cb;
     ojphgpu_coded_blocks(P, e->block_ids, res, cb);
@@ -239,12 +361,37 @@ static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
   }
 }
 
+// The kernels of every frame start the same way, on the compute stream behind the frame's upload: the frame as it was handed
+// over -> planes in the slot's image, then the encoder's run into the slot's output set (a plain pipe: the whole encode;
+// a budget: transform + statistics; a target: conversion + DWT).  The block coder writes its per-block {offset, length}
+// records straight into the set's pinned memory (8 bytes per block, posted PCIe writes): all the host needs to code the
+// packet headers.
+static int enc_begin_frame(ojphgpu_enc_pipe* p, EncSlot& s)
+{
+  ojphgpu_encoder* e = p->enc;
+  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
+  const int rc = handover_launch(p->s_comp, p->ho, *p->P, p->container, true, s.pixels.b.p, s.image.p);
+  if (rc) return rc;
+  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
+  return ojphgpu_encoder_run_container(e, s.image.p, p->container);
+}
+
+// the frame of a slot is over, whatever its outcome (s.rc): collectable, and counted
+static void retire(ojphgpu_enc_pipe* p, EncSlot& s)
+{
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    s.t_done = now_ms();
+    s.state = DONE;
+    p->sum_t2 += s.t_t2; p->sum_latency += s.t_done - s.t_submit; p->n_done++;
+  }
+  p->cv_done.notify_all();
+}
+
 // ---- byte budget: the ordered worker.  Per frame, on the compute stream: unpack, transform and statistics; the histograms
 // come back; the search, started from the last certified frame's answer, codes its trials into the slot's output set and
 // the spare in turn.  Afterwards the slot holds the set with j*, its plan copy stands at qstep(j*), and the finishers take
 // over as for any frame.
-static int enc_unpack(ojphgpu_enc_pipe* p, EncSlot& s);
-
 struct EncTrialCtx {
   ojphgpu_enc_pipe* p; EncSlot* s;
   EncOut* best; EncOut* next;                        // best: holds the finest trial that fit so far (null: none); next: written next
@@ -255,13 +402,8 @@ static int64_t enc_pipe_trial(void* user, uint32_t j)
 {
   EncTrialCtx& c = *(EncTrialCtx*)user;
   ojphgpu_encoder* e = c.p->enc;
-  const size_t nb = e->block_ids.size();
-  EncOut& o = *c.next;
-  uint32_t* d_pub = (uint32_t*)(o.h_res.d + nb * sizeof(ojphgpu_cb_result));
-  const RateTrialOut to{ o.out.p, (ojphgpu_cb_result*)o.h_res.d, (uint32_t*)o.counters.p, (const ojphgpu_cb_result*)o.h_res.p,
-                         d_pub, (const uint32_t*)(o.h_res.p + nb * sizeof(ojphgpu_cb_result)), c.p->ev_trial };
   c.at = -1;
-  const int64_t size = ojphgpu_encoder_rate_trial(e, c.s->rplan->plan, to, j);
+  const int64_t size = ojphgpu_encoder_rate_trial(e, c.s->rplan->plan, c.next->trial(e->block_ids.size(), c.p->ev_trial), j);
   if (size < 0) return size;
   c.at = (int)j;
   if ((uint64_t)size <= c.s->budget) {               // the finest that fits so far (the search never goes back below one): keep it
@@ -275,22 +417,20 @@ static int enc_rate_frame(ojphgpu_enc_pipe* p, EncSlot& s)
 {
   ojphgpu_encoder* e = p->enc;
   EncoderRate& R = *e->rate;
+  ojphgpu_rate_info& info = s.found.rate;
   HIPCHK(hipSetDevice(p->device));
-  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
-  int rc = enc_unpack(p, s);
+  int rc = enc_begin_frame(p, s);                    // transform + statistics (e->max_bytes != 0)
   if (rc) return rc;
-  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
-  if ((rc = ojphgpu_encoder_run_container(e, s.image.p, p->container)) != 0) return rc;   // transform + statistics (e->max_bytes != 0)
   if ((rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
   HIPCHK(hipEventRecord(p->ev_trial, p->s_comp));
   HIPCHK(hipEventSynchronize(p->ev_trial));
   EncTrialCtx c{ p, &s, nullptr, &s.o, -1 };
-  rc = rate_search(R.table, (const uint32_t*)p->h_hist.p, s.budget, p->hint, enc_pipe_trial, &c, &s.info);
-  s.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
+  rc = rate_search(R.table, (const uint32_t*)p->h_hist.p, s.budget, p->hint, enc_pipe_trial, &c, &info);
+  s.found.have_rate = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
   if (rc) return rc;
-  p->hint = (int)s.info.grid_index;
+  p->hint = (int)info.grid_index;
   if (c.best != &s.o) std::swap(s.o, p->spare);      // (pointers only) the slot keeps the set with j*, the other is the spare
-  if (c.at != (int)s.info.grid_index && !rate_apply_step(s.rplan->plan, s.info.qstep)) return OJPHGPU_E_INVALID;
+  if (c.at != (int)info.grid_index && !rate_apply_step(s.rplan->plan, info.qstep)) return OJPHGPU_E_INVALID;
   HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
   return OJPHGPU_OK;
 }
@@ -320,48 +460,33 @@ static int64_t enc_pipe_quality_trial(void* user, uint32_t j, uint64_t* sse)
 static int enc_quality_frame(ojphgpu_enc_pipe* p, EncSlot& s)
 {
   ojphgpu_encoder* e = p->enc;
+  EncSearchResult& f = s.found;
   HIPCHK(hipSetDevice(p->device));
-  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
-  int rc = enc_unpack(p, s);
+  int rc = enc_begin_frame(p, s);                    // conversion + DWT (e->quality_on)
   if (rc) return rc;
-  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
-  if ((rc = ojphgpu_encoder_run_container(e, s.image.p, p->container)) != 0) return rc;   // conversion + DWT (e->quality_on)
   EncQualityCtx c{ p, &s };
-  rc = ojphgpu_quality_search_hint(s.target, p->hint, enc_pipe_quality_trial, &c, &s.qinfo, &s.first_guess);
-  s.have_qinfo = rc == OJPHGPU_OK || rc == OJPHGPU_E_QUALITY;
+  rc = ojphgpu_quality_search_hint(s.target, p->hint, enc_pipe_quality_trial, &c, &f.quality, &f.first_guess);
+  f.have_quality = rc == OJPHGPU_OK || rc == OJPHGPU_E_QUALITY;
   if (rc) return rc;
-  s.qcomps = p->q_by_index[s.qinfo.grid_index];
-  for (const ojphgpu_frame_err& k : s.qcomps) s.qinfo.pae = std::max(s.qinfo.pae, k.pae);
-  p->hint = (int)s.qinfo.grid_index;
-  const size_t nb = e->block_ids.size();
-  const RateTrialOut to{ s.o.out.p, (ojphgpu_cb_result*)s.o.h_res.d, (uint32_t*)s.o.counters.p, (const ojphgpu_cb_result*)s.o.h_res.p,
-                         (uint32_t*)(s.o.h_res.d + nb * sizeof(ojphgpu_cb_result)),
-                         (const uint32_t*)(s.o.h_res.p + nb * sizeof(ojphgpu_cb_result)), p->ev_trial };
-  const int64_t size = ojphgpu_encoder_rate_trial(e, s.rplan->plan, to, s.qinfo.grid_index);   // (leaves rplan at qstep(j*))
-  if (size < 0) { s.have_qinfo = false; return size < INT32_MIN ? OJPHGPU_E_INVALID : (int)size; }
-  s.qinfo.bytes = (uint64_t)size;
+  f.comps = p->q_by_index[f.quality.grid_index];
+  for (const ojphgpu_frame_err& k : f.comps) f.quality.pae = std::max(f.quality.pae, k.pae);
+  p->hint = (int)f.quality.grid_index;
+  const int64_t size = ojphgpu_encoder_rate_trial(e, s.rplan->plan, s.o.trial(e->block_ids.size(), p->ev_trial), f.quality.grid_index);   // (leaves rplan at qstep(j*))
+  if (size < 0) { f.have_quality = false; return size < INT32_MIN ? OJPHGPU_E_INVALID : (int)size; }
+  f.quality.bytes = (uint64_t)size;
   HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
   return OJPHGPU_OK;
 }
 
 static void enc_search_worker(ojphgpu_enc_pipe* p)
 {
-  for (;;) {
-    uint32_t si;
-    {
-      std::unique_lock<std::mutex> lk(p->mu);
-      p->cv_search.wait(lk, [&] { return p->stop_search || !p->search_work.empty(); });
-      if (p->search_work.empty()) return;
-      si = p->search_work.front(); p->search_work.pop_front();
-    }
+  for (uint32_t si; pop_work(p->mu, p->cv_search, p->search_work, p->stop_search, si);) {
     EncSlot& s = p->slots[si];
     const int rc = no_throw([&] { return p->quality_on ? enc_quality_frame(p, s) : enc_rate_frame(p, s); });
     if (rc) {                                        // the frame ends here (OJPHGPU_E_BUDGET / _E_QUALITY among the reasons); see enc_finish_frame
       hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp);
-      std::lock_guard<std::mutex> lk(p->mu);
-      s.rc = rc; s.t_done = now_ms(); s.state = DONE;
-      p->sum_latency += s.t_done - s.t_submit; p->n_done++;
-      p->cv_done.notify_all();
+      s.rc = rc;
+      retire(p, s);
       continue;
     }
     { std::lock_guard<std::mutex> lk(p->mu); p->work.push_back(si); }
@@ -371,23 +496,9 @@ static void enc_search_worker(ojphgpu_enc_pipe* p)
 
 static void enc_finisher(ojphgpu_enc_pipe* p)
 {
-  for (;;) {
-    uint32_t si;
-    {
-      std::unique_lock<std::mutex> lk(p->mu);
-      p->cv_work.wait(lk, [&] { return p->stop || !p->work.empty(); });
-      if (p->work.empty()) return;                   // stop requested and nothing left
-      si = p->work.front(); p->work.pop_front();
-    }
-    EncSlot& s = p->slots[si];
-    enc_finish_frame(p, s);
-    {
-      std::lock_guard<std::mutex> lk(p->mu);
-      s.t_done = now_ms();
-      s.state = DONE;
-      p->sum_t2 += s.t_t2; p->sum_latency += s.t_done - s.t_submit; p->n_done++;
-    }
-    p->cv_done.notify_all();
+  for (uint32_t si; pop_work(p->mu, p->cv_work, p->work, p->stop, si);) {
+    enc_finish_frame(p, p->slots[si]);
+    retire(p, p->slots[si]);
   }
 }
 
@@ -407,7 +518,7 @@ extern "C" void ojphgpu_enc_pipe_destroy(ojphgpu_enc_pipe* p)
   if (p->enc) ojphgpu_encoder_destroy(p->enc);
   for (EncSlot& s : p->slots) {
     s.h_in.release(); s.o.release(); s.h_lay.release(); s.h_cs.release();
-    for (DeviceBuf* b : { &s.image, &s.cs.b, &s.pixels }) b->release();
+    for (DeviceBuf* b : { &s.image, &s.cs.b, &s.pixels.b }) b->release();
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
     delete s.rplan;
   }
@@ -438,7 +549,7 @@ extern "C" int ojphgpu_enc_pipe_create(const ojphgpu_plan* plan, int device, uin
     ojphgpu_encoder* e = p->enc;
     const size_t nb = e->block_ids.size();
     p->frame_bytes = (size_t)P.frame_elems * (size_t)(container_bits / 8);
-    p->in_bytes = p->frame_bytes;
+    p->ho.bytes = p->frame_bytes;
     p->res_bytes = nb * sizeof(ojphgpu_cb_result) + 16;
     // the codestream of a frame: sized from the samples (1 byte each is generous for natural content), grown when a frame needs more
     const size_t cs_guess = std::min<size_t>((size_t)e->out_cap, (size_t)P.frame_elems + (1u << 20));
@@ -465,129 +576,25 @@ extern "C" int ojphgpu_enc_pipe_acquire(ojphgpu_enc_pipe* p, void** h_frame, siz
   EncSlot& s = p->slots[p->n_acq % p->depth];
   {
     std::lock_guard<std::mutex> lk(p->mu);
-    if (s.state == ACQUIRED) { *h_frame = s.h_in.p; if (bytes) *bytes = p->in_bytes; return OJPHGPU_OK; }   // asked twice
+    if (s.state == ACQUIRED) { *h_frame = s.h_in.p; if (bytes) *bytes = p->ho.bytes; return OJPHGPU_OK; }   // asked twice
     if (s.state != FREE) return OJPHGPU_E_AGAIN;      // every slot is in flight: collect a codestream first
     s.state = ACQUIRED;
   }
   *h_frame = s.h_in.p;
-  if (bytes) *bytes = p->in_bytes;
+  if (bytes) *bytes = p->ho.bytes;
   return OJPHGPU_OK;
 }
 
-// the conditions of the pixel-interleaved hand-over: one size for all components, unsigned, depths that fit
-static int pixels_fit(const Plan& P, int pixel_bits, int container_bits)
+// before the first _acquire: the hand-over may still be set (and set again)
+static int enc_set_handover(ojphgpu_enc_pipe* p, int kind, int arg, int big_endian)
 {
-  if (pixel_bits != 8 && pixel_bits != 16) return OJPHGPU_E_INVALID;
-  if (pixel_bits > container_bits) return OJPHGPU_E_INVALID;
-  if (P.skip_recon || P.has_region) {                  // a view's frame (a decoder pipe): planes of one size
-    for (const CompGeo& g : P.comps) if (g.w != P.comps[0].w || g.h != P.comps[0].h || g.w == 0 || g.h == 0) return OJPHGPU_E_INVALID;
-  } else if (P.frame_elems != (uint64_t)P.p.width * P.p.height * P.p.num_comps) return OJPHGPU_E_INVALID;   // sub-sampled components
-  for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth > (uint32_t)pixel_bits) return OJPHGPU_E_INVALID;
-  return OJPHGPU_OK;
+  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE) return OJPHGPU_E_INVALID;
+  return handover_set(p, &EncSlot::h_in, false, false, kind, arg, big_endian);
 }
 
-extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian)
-{
-  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->packed_bits || p->video) return OJPHGPU_E_INVALID;
-  return no_throw([&]() -> int {
-    if (pixel_bits == 0) { p->pixel_bits = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
-    const Plan& P = *p->P;
-    const int rc = pixels_fit(P, pixel_bits, p->container);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    const size_t nbytes = (size_t)P.frame_elems * (size_t)(pixel_bits / 8);
-    for (EncSlot& s : p->slots) {
-      if (s.h_in.reserve(nbytes + 64)) return OJPHGPU_E_NOMEM;
-      if (!s.pixels.p && s.pixels.alloc(nbytes + 64)) return OJPHGPU_E_NOMEM;
-    }
-    p->pixel_bits = pixel_bits; p->big_endian = big_endian ? 1 : 0; p->in_bytes = nbytes;
-    return OJPHGPU_OK;
-  });
-}
-
-static size_t packed_bytes(uint64_t samples, int bits) { return (size_t)((samples + 31) / 32) * 4u * (size_t)bits; }
-
-static int packed_fit(const Plan& P, int bits, int container_bits)
-{
-  if ((bits != 10 && bits != 12 && bits != 14) || (container_bits != 16 && container_bits != 32)) return OJPHGPU_E_INVALID;
-  for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth > (uint32_t)bits) return OJPHGPU_E_INVALID;
-  return OJPHGPU_OK;
-}
-
-extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits)
-{
-  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits || p->video) return OJPHGPU_E_INVALID;
-  return no_throw([&]() -> int {
-    if (bits == 0) { p->packed_bits = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
-    const Plan& P = *p->P;
-    const int rc = packed_fit(P, bits, p->container);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    const size_t nbytes = packed_bytes(P.frame_elems, bits);
-    for (EncSlot& s : p->slots) {
-      if (s.h_in.reserve(nbytes + 64)) return OJPHGPU_E_NOMEM;
-      if (!s.pixels.p && s.pixels.alloc(nbytes + 64)) return OJPHGPU_E_NOMEM;
-    }
-    p->packed_bits = bits; p->in_bytes = nbytes;
-    return OJPHGPU_OK;
-  });
-}
-
-// the conditions of the 4:2:2 video hand-over (ojphgpu.h section 7b): three unsigned components of one depth that fits the
-// format, the chroma planes half as wide (rounded up) and as high as the luma plane; -> the format's layout of that frame
-static int video_fit(const Plan& P, int format, int container_bits, uint64_t* bytes)
-{
-  if (format < OJPHGPU_VIDEO_UYVY || format > OJPHGPU_VIDEO_Y2XX || P.comps.size() != 3) return OJPHGPU_E_INVALID;
-  const CompGeo& Y = P.comps[0];
-  if (Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
-  const uint32_t cw = (uint32_t)(((uint64_t)Y.w + 1) / 2), b = Y.bit_depth;
-  for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != b) return OJPHGPU_E_INVALID;
-  for (size_t c = 1; c < 3; ++c) if (P.comps[c].w != cw || P.comps[c].h != Y.h) return OJPHGPU_E_INVALID;
-  if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != (uint64_t)Y.w * Y.h + (uint64_t)cw * Y.h) return OJPHGPU_E_INVALID;
-  if (format == OJPHGPU_VIDEO_Y2XX ? (b < 9 || b > 16) : b > (format == OJPHGPU_VIDEO_V210 ? 10u : 8u)) return OJPHGPU_E_INVALID;
-  if (container_bits == 8 && format != OJPHGPU_VIDEO_UYVY && format != OJPHGPU_VIDEO_YUY2) return OJPHGPU_E_INVALID;
-  uint32_t row_bytes = 0;
-  return ojphgpu_video_layout(format, Y.w, Y.h, &row_bytes, bytes);
-}
-
-extern "C" int ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* p, int format)
-{
-  if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE || p->pixel_bits || p->packed_bits) return OJPHGPU_E_INVALID;
-  return no_throw([&]() -> int {
-    if (format == 0) { p->video = 0; p->in_bytes = p->frame_bytes; return OJPHGPU_OK; }
-    uint64_t nbytes = 0;
-    const int rc = video_fit(*p->P, format, p->container, &nbytes);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    for (EncSlot& s : p->slots) {
-      if (s.h_in.reserve((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM;
-      if (!s.pixels.p || s.pixels.n < (size_t)nbytes + 64) { s.pixels.release(); if (s.pixels.alloc((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM; }
-    }
-    p->video = format; p->in_bytes = (size_t)nbytes;
-    return OJPHGPU_OK;
-  });
-}
-
-// the frame as it was handed over -> planes in the slot's image, on the compute stream (nothing for planar frames)
-static int enc_unpack(ojphgpu_enc_pipe* p, EncSlot& s)
-{
-  if (p->pixel_bits) {                               // the file's / capture buffer's bytes -> planes, on the device
-    const Plan& P = *p->P;
-    const int r0 = ojphgpu_unpack_pixels(p->s_comp, s.pixels.p, s.image.p, P.p.width, P.p.height, P.p.num_comps, p->pixel_bits,
-                                         p->big_endian, p->container);
-    if (r0) return r0;
-  }
-  if (p->packed_bits) {
-    const int r0 = ojphgpu_unpack_bits(p->s_comp, s.pixels.p, s.image.p, p->P->frame_elems, p->packed_bits, p->container);
-    if (r0) return r0;
-  }
-  if (p->video) {
-    const CompGeo& Y = p->P->comps[0];
-    const int r0 = ojphgpu_unpack_video(p->s_comp, p->video, s.pixels.p, s.image.p, Y.w, Y.h, Y.bit_depth, p->container);
-    if (r0) return r0;
-  }
-  return OJPHGPU_OK;
-}
+extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian) { return enc_set_handover(p, PIXELS, pixel_bits, big_endian); }
+extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits) { return enc_set_handover(p, PACKED, bits, 0); }
+extern "C" int ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* p, int format) { return enc_set_handover(p, VIDEO, format, 0); }
 
 extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
 {
@@ -596,29 +603,22 @@ extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
   EncSlot& s = p->slots[si];
   { std::lock_guard<std::mutex> lk(p->mu); if (s.state != ACQUIRED) return OJPHGPU_E_INVALID; }
   HIPCHK(hipSetDevice(p->device));
-  ojphgpu_encoder* e = p->enc;
-  s.rc = 0; s.cs_len = 0; s.t_submit = now_ms();
-  { const int r0 = upload(p->mode, p->s_h2d, (p->pixel_bits || p->packed_bits || p->video) ? s.pixels.p : s.image.p, s.h_in, 0, p->in_bytes); if (r0) return r0; }
+  s.rc = 0; s.cs_len = 0; s.t_t2 = 0; s.t_submit = now_ms();
+  { const int r0 = upload(p->mode, p->s_h2d, handover_device_side(p->ho, s), s.h_in, 0, p->ho.bytes); if (r0) return r0; }
   HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
   if (p->searching()) {                              // everything on the compute stream is the search worker's, frame by frame
     std::lock_guard<std::mutex> lk(p->mu);
-    s.budget = p->max_bytes; s.have_info = false;
-    s.target = p->max_sse; s.have_qinfo = false; s.qcomps.clear();
+    s.budget = p->max_bytes; s.target = p->max_sse; s.found = EncSearchResult{};
     s.state = SUBMITTED;
     p->search_work.push_back(si);
     p->n_acq++; p->n_sub++;
     p->cv_search.notify_one();
     return OJPHGPU_OK;
   }
-  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
-  { const int r0 = enc_unpack(p, s); if (r0) return r0; }
-  // the block coder writes its per-block {offset, length} records straight into the slot's pinned memory
-  // (8 bytes per block, posted PCIe writes): all the host needs to code the packet headers
-  const size_t nb = e->block_ids.size();
-  e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
-  int rc = ojphgpu_encoder_run_container(e, s.image.p, p->container);
+  int rc = enc_begin_frame(p, s);
   if (rc) return rc;
-  rc = publish_words_launch(p->s_comp, (uint32_t*)(s.o.h_res.d + nb * sizeof(ojphgpu_cb_result)), (const uint32_t*)s.o.counters.p, 2);
+  const RateTrialOut coded = s.o.trial(p->enc->block_ids.size(), nullptr);
+  rc = publish_words_launch(p->s_comp, coded.d_publish, coded.d_counters, 2);
   if (rc) return rc;
   HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
   {
@@ -643,14 +643,31 @@ extern "C" int ojphgpu_enc_pipe_collect(ojphgpu_enc_pipe* p, const uint8_t** h_c
   EncSlot& s = p->slots[p->n_col % p->depth];
   p->cv_done.wait(lk, [&] { return s.state == DONE; });
   p->n_col++;
-  if (p->budget_on) { p->last_info = s.info; p->have_last_info = s.have_info; }
-  if (p->quality_on) {
-    p->last_qinfo = s.qinfo; p->last_first_guess = s.first_guess; p->have_last_qinfo = s.have_qinfo;
-    p->last_qcomps = s.qcomps;
-  }
+  p->last = s.found;
   if (s.rc) { s.state = FREE; return s.rc; }
   s.state = HELD;
   *h_codestream = s.h_cs.p; *len = s.cs_len;
+  return OJPHGPU_OK;
+}
+
+// Switching a search mode on, once the encoder has taken it (ojphgpu_encoder_set_budget / _set_quality: refused there, the
+// encoder and the pipe are as they were).  From here the encoder runs in that mode and the buffers change hands: a failure
+// (memory, the thread) leaves neither a plain pipe nor a searching one, so the pipe is dead -- it refuses everything but
+// _destroy -- until the setter that called this has its own buffers too and says otherwise.  Here: every slot's output set
+// at the bound of the finest step and its copy of the plan, the spare set's pinned half, the event of the trials, the worker.
+static int enc_search_on(ojphgpu_enc_pipe* p, bool with_spare)
+{
+  ojphgpu_encoder* e = p->enc;
+  p->dead = true;
+  for (EncSlot& s : p->slots) {
+    s.o.out.release(); s.o.counters.release();
+    if (s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
+    if (!s.rplan) s.rplan = new ojphgpu_plan{ *p->P };
+  }
+  if (with_spare && p->spare.h_res.reserve(p->res_bytes + 64)) return OJPHGPU_E_NOMEM;
+  if (!p->ev_trial) HIPCHK(hipEventCreateWithFlags(&p->ev_trial, hipEventDisableTiming | hipEventReleaseToSystem));
+  p->search_worker = std::thread(enc_search_worker, p);
+  p->hint = -1;
   return OJPHGPU_OK;
 }
 
@@ -668,24 +685,11 @@ extern "C" int ojphgpu_enc_pipe_set_budget(ojphgpu_enc_pipe* p, uint64_t max_byt
     HIPCHK(hipSetDevice(p->device));
     ojphgpu_encoder* e = p->enc;
     int rc = ojphgpu_encoder_set_budget(e, max_bytes);   // the refusals, the statistics, scratch and output bound of the finest step
-    if (rc) return rc;                                   // (refused: the encoder and the pipe are as they were)
-    // From here the encoder runs in budget mode and the buffers change hands: a failure below (memory, the thread) leaves
-    // neither a plain pipe nor a budgeted one, so the pipe refuses everything but _destroy afterwards.
-    struct Guard { ojphgpu_enc_pipe* p; ~Guard() { if (p) p->dead = true; } } guard{ p };
-    // the output sets at that bound: one per slot, and the encoder's own becomes the spare
-    for (EncSlot& s : p->slots) {
-      s.o.out.release(); s.o.counters.release();
-      if (s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
-      if (!s.rplan) s.rplan = new ojphgpu_plan{ *p->P };
-    }
-    p->spare.out = e->out; p->spare.counters = e->counters;
+    if (rc || (rc = enc_search_on(p, true)) != 0) return rc;
+    p->spare.out = e->out; p->spare.counters = e->counters;   // the encoder's own output set becomes the spare
     e->out = DeviceBuf(); e->counters = DeviceBuf();
-    if (p->spare.h_res.reserve(p->res_bytes + 64)) return OJPHGPU_E_NOMEM;
     if (p->h_hist.reserve(e->rate->h_hist.size() * 4 + 64)) return OJPHGPU_E_NOMEM;
-    if (!p->ev_trial) HIPCHK(hipEventCreateWithFlags(&p->ev_trial, hipEventDisableTiming | hipEventReleaseToSystem));
-    p->search_worker = std::thread(enc_search_worker, p);
-    p->budget_on = true; p->max_bytes = max_bytes; p->hint = -1;
-    guard.p = nullptr;
+    p->budget_on = true; p->max_bytes = max_bytes; p->dead = false;
     return OJPHGPU_OK;
   });
 }
@@ -694,8 +698,8 @@ extern "C" int ojphgpu_enc_pipe_rate_info(ojphgpu_enc_pipe* p, ojphgpu_rate_info
 {
   if (!p || !info) return OJPHGPU_E_INVALID;
   std::lock_guard<std::mutex> lk(p->mu);
-  if (!p->have_last_info) return OJPHGPU_E_INVALID;
-  *info = p->last_info;
+  if (!p->last.have_rate) return OJPHGPU_E_INVALID;
+  *info = p->last.rate;
   return OJPHGPU_OK;
 }
 
@@ -716,23 +720,12 @@ extern "C" int ojphgpu_enc_pipe_set_quality(ojphgpu_enc_pipe* p, uint64_t max_ss
     // the refusals; scratch and output bound of the finest step, the second arena, the synthesis-only decoder and the
     // int32 reconstructed frame
     int rc = ojphgpu_encoder_set_quality(e, max_sse);
-    if (rc) return rc;                                   // (refused: the encoder and the pipe are as they were)
-    struct Guard { ojphgpu_enc_pipe* p; ~Guard() { if (p) p->dead = true; } } guard{ p };   // as in _set_budget
-    // the output sets at that bound, one per slot: a frame's blocks are coded once, so there is no spare, and the
-    // encoder's own set goes
-    for (EncSlot& s : p->slots) {
-      s.o.out.release(); s.o.counters.release();
-      if (s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
-      if (!s.rplan) s.rplan = new ojphgpu_plan{ *p->P };
-    }
-    e->out.release(); e->counters.release();
+    if (rc || (rc = enc_search_on(p, false)) != 0) return rc;
+    e->out.release(); e->counters.release();             // a frame's blocks are coded once: no spare, the encoder's own set goes
     if (p->h_qdescs.reserve(e->quality->h_descs.size() * sizeof(ojphgpu_requant_desc) + 64) ||
         p->h_qerr.reserve(p->P->comps.size() * sizeof(ojphgpu_frame_err) + 64)) return OJPHGPU_E_NOMEM;
     p->q_by_index.assign(OJPHGPU_RATE_GRID, {});
-    if (!p->ev_trial) HIPCHK(hipEventCreateWithFlags(&p->ev_trial, hipEventDisableTiming | hipEventReleaseToSystem));
-    p->search_worker = std::thread(enc_search_worker, p);
-    p->quality_on = true; p->max_sse = max_sse; p->hint = -1;
-    guard.p = nullptr;
+    p->quality_on = true; p->max_sse = max_sse; p->dead = false;
     return OJPHGPU_OK;
   });
 }
@@ -741,8 +734,8 @@ extern "C" int ojphgpu_enc_pipe_quality_info(ojphgpu_enc_pipe* p, ojphgpu_qualit
 {
   if (!p || !info || !first_guess) return OJPHGPU_E_INVALID;
   std::lock_guard<std::mutex> lk(p->mu);
-  if (!p->have_last_qinfo) return OJPHGPU_E_INVALID;
-  *info = p->last_qinfo; *first_guess = p->last_first_guess;
+  if (!p->last.have_quality) return OJPHGPU_E_INVALID;
+  *info = p->last.quality; *first_guess = p->last.first_guess;
   return OJPHGPU_OK;
 }
 
@@ -750,8 +743,8 @@ extern "C" int ojphgpu_enc_pipe_quality_comp(ojphgpu_enc_pipe* p, uint32_t comp,
 {
   if (!p || !sse || !pae) return OJPHGPU_E_INVALID;
   std::lock_guard<std::mutex> lk(p->mu);
-  if (!p->have_last_qinfo || comp >= p->last_qcomps.size()) return OJPHGPU_E_INVALID;
-  *sse = p->last_qcomps[comp].sse; *pae = p->last_qcomps[comp].pae;
+  if (!p->last.have_quality || comp >= p->last.comps.size()) return OJPHGPU_E_INVALID;
+  *sse = p->last.comps[comp].sse; *pae = p->last.comps[comp].pae;
   return OJPHGPU_OK;
 }
 
@@ -772,8 +765,8 @@ extern "C" int ojphgpu_enc_pipe_stats(ojphgpu_enc_pipe* p, double out[4])
 struct DecSlot {
   SlotState state = FREE;
   Pinned h_cs, h_descs, h_img, h_status;
-  Grow data;
-  DeviceBuf image, cb_descs, status, pixels, runs;  // runs: a view's run table, copied there for the gather kernel
+  Grow data, pixels;                                // pixels: the frame as it is handed back, unless that is as planes
+  DeviceBuf image, cb_descs, status, runs;          // runs: a view's run table, copied there for the gather kernel
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   size_t cs_len = 0;
   int rc = 0; uint32_t failed = 0;
@@ -807,10 +800,7 @@ struct ojphgpu_dec_pipe {
   hipStream_t s_h2d = nullptr, s_d2h = nullptr;
   std::vector<DecSlot> slots;
   size_t frame_bytes = 0;
-  int pixel_bits = 0, big_endian = 0;               // != 0: frames come back pixel-interleaved (ojphgpu_dec_pipe_set_pixels)
-  int packed_bits = 0;                              // != 0: ... bit-packed (ojphgpu_dec_pipe_set_packed)
-  int video = 0;                                    // != 0: ... as one 4:2:2 video buffer of that format (ojphgpu_dec_pipe_set_video)
-  size_t out_bytes = 0;
+  Handover ho;                                      // how frames are handed back; ho.bytes: what _collect hands out
   uint64_t n_acq = 0, n_sub = 0, n_col = 0;
   std::mutex mu; std::condition_variable cv_work, cv_done;
   std::deque<uint32_t> work; bool stop = false;
@@ -883,20 +873,11 @@ static void dec_process_frame(ojphgpu_dec_pipe* p, DecSlot& s)
         if (r3) return r3;
         epoch = d->fused_epoch; was_fused = d->last_fused;
         if (separate) d->fused_retries++;
-        if (p->pixel_bits) {                           // planes -> the pixel order of the file / display buffer
-          uint32_t depth = 0;
-          for (const CompGeo& g : P.comps) depth = std::max(depth, g.bit_depth);
-          r3 = ojphgpu_pack_pixels(s_comp, s.image.p, s.pixels.p, P.comps[0].w, P.comps[0].h, P.p.num_comps, p->container, p->pixel_bits,
-                                   p->big_endian, depth);
-          if (r3) return r3;
-        }
-        if (p->packed_bits && (r3 = ojphgpu_pack_bits(s_comp, s.image.p, s.pixels.p, P.frame_elems, p->container, p->packed_bits)) != 0) return r3;
-        if (p->video && (r3 = ojphgpu_pack_video(s_comp, p->video, s.image.p, s.pixels.p, P.comps[0].w, P.comps[0].h, p->container,
-                                                 P.comps[0].bit_depth)) != 0) return r3;
+        if ((r3 = handover_launch(s_comp, p->ho, P, p->container, false, s.pixels.b.p, s.image.p)) != 0) return r3;   // planes -> the frame as it is handed back
         HIPCHK(hipEventRecord(s.ev_kern, s_comp));
       }
       HIPCHK(hipStreamWaitEvent(p->s_d2h, s.ev_kern, 0));
-      if ((r3 = download(p->mode, p->s_d2h, s.h_img, (p->pixel_bits || p->packed_bits || p->video) ? s.pixels.p : s.image.p, p->out_bytes)) != 0) return r3;       // beside the next frame's upload
+      if ((r3 = download(p->mode, p->s_d2h, s.h_img, handover_device_side(p->ho, s), p->ho.bytes)) != 0) return r3;       // beside the next frame's upload
       if ((r3 = download(p->mode, p->s_d2h, s.h_status, s.status.p, st_bytes)) != 0) return r3;
       HIPCHK(hipEventRecord(s.ev_done, p->s_d2h));
       HIPCHK(hipEventSynchronize(s.ev_done));
@@ -925,25 +906,23 @@ static void dec_process_frame(ojphgpu_dec_pipe* p, DecSlot& s)
   }
 }
 
+// the frame of a slot is over, whatever its outcome (s.rc): collectable, and counted
+static void retire(ojphgpu_dec_pipe* p, DecSlot& s)
+{
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    s.t_done = now_ms();
+    s.state = DONE;
+    p->sum_parse += s.t_parse; p->sum_latency += s.t_done - s.t_submit; p->n_done++;
+  }
+  p->cv_done.notify_all();
+}
+
 static void dec_worker(ojphgpu_dec_pipe* p)
 {
-  for (;;) {
-    uint32_t si;
-    {
-      std::unique_lock<std::mutex> lk(p->mu);
-      p->cv_work.wait(lk, [&] { return p->stop || !p->work.empty(); });
-      if (p->work.empty()) return;
-      si = p->work.front(); p->work.pop_front();
-    }
-    DecSlot& s = p->slots[si];
-    dec_process_frame(p, s);
-    {
-      std::lock_guard<std::mutex> lk(p->mu);
-      s.t_done = now_ms();
-      s.state = DONE;
-      p->sum_parse += s.t_parse; p->sum_latency += s.t_done - s.t_submit; p->n_done++;
-    }
-    p->cv_done.notify_all();
+  for (uint32_t si; pop_work(p->mu, p->cv_work, p->work, p->stop, si);) {
+    dec_process_frame(p, p->slots[si]);
+    retire(p, p->slots[si]);
   }
 }
 
@@ -958,7 +937,7 @@ extern "C" void ojphgpu_dec_pipe_destroy(ojphgpu_dec_pipe* p)
   for (ojphgpu_decoder* d : p->decs) if (d) ojphgpu_decoder_destroy(d);
   for (DecSlot& s : p->slots) {
     s.h_cs.release(); s.h_descs.release(); s.h_img.release(); s.h_status.release();
-    for (DeviceBuf* b : { &s.data.b, &s.image, &s.cb_descs, &s.status, &s.pixels, &s.runs }) b->release();
+    for (DeviceBuf* b : { &s.data.b, &s.image, &s.cb_descs, &s.status, &s.pixels.b, &s.runs }) b->release();
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
   }
   for (hipStream_t s : { p->s_h2d, p->s_comps[0], p->s_comps[1], p->s_comps[2], p->s_comps[3], p->s_d2h }) if (s) (void)hipStreamDestroy(s);
@@ -1024,7 +1003,7 @@ extern "C" int ojphgpu_dec_pipe_create_view(const uint8_t* h_codestream, size_t 
     ojphgpu_decoder* d = p->decs[0];
     const size_t nb = d->block_ids.size();
     p->frame_bytes = (size_t)P.frame_elems * (size_t)(container_bits / 8);
-    p->out_bytes = p->frame_bytes;
+    p->ho.bytes = p->frame_bytes;
     p->runs_off = (nb * sizeof(ojphgpu_cb_desc) + 63) & ~(size_t)63;   // a view's run table: a run holds a block at least
     const size_t descs_bytes = p->view ? p->runs_off + nb * sizeof(DecRun) : nb * sizeof(ojphgpu_cb_desc);
     p->slots.resize(depth);
@@ -1092,68 +1071,21 @@ extern "C" int ojphgpu_dec_pipe_collect(ojphgpu_dec_pipe* p, const void** h_fram
   if (s.rc) { s.state = FREE; return s.rc; }
   s.state = HELD;
   *h_frame = s.h_img.p;
-  if (bytes) *bytes = p->out_bytes;
+  if (bytes) *bytes = p->ho.bytes;
   if (failed_blocks) *failed_blocks = s.failed;
   return (s.failed && !p->resilient) ? OJPHGPU_E_BLOCK : OJPHGPU_OK;
 }
 
-extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, int big_endian)
+// before the first _submit: the hand-over may still be set (and set again)
+static int dec_set_handover(ojphgpu_dec_pipe* p, int kind, int arg, int big_endian)
 {
-  if (!p || p->n_sub != 0 || p->packed_bits || p->video) return OJPHGPU_E_INVALID;
-  return no_throw([&]() -> int {
-    if (pixel_bits == 0) { p->pixel_bits = 0; p->out_bytes = p->frame_bytes; return OJPHGPU_OK; }
-    const Plan& P = *p->P;
-    const int rc = pixels_fit(P, pixel_bits, p->container);
-    if (rc) return rc;
-    for (const CompGeo& g : P.comps) if (g.bit_depth != P.comps[0].bit_depth) return OJPHGPU_E_INVALID;   // one clamp range per frame
-    HIPCHK(hipSetDevice(p->device));
-    const size_t nbytes = (size_t)P.frame_elems * (size_t)(pixel_bits / 8);
-    for (DecSlot& s : p->slots) {
-      if (s.h_img.reserve(nbytes + 64)) return OJPHGPU_E_NOMEM;
-      if (!s.pixels.p && s.pixels.alloc(nbytes + 64)) return OJPHGPU_E_NOMEM;
-    }
-    p->pixel_bits = pixel_bits; p->big_endian = big_endian ? 1 : 0; p->out_bytes = nbytes;
-    return OJPHGPU_OK;
-  });
+  if (!p || p->n_sub != 0) return OJPHGPU_E_INVALID;
+  return handover_set(p, &DecSlot::h_img, true, p->has_region && (p->region[0] & 1u), kind, arg, big_endian);
 }
 
-extern "C" int ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* p, int bits)
-{
-  if (!p || p->n_sub != 0 || p->pixel_bits || p->video) return OJPHGPU_E_INVALID;
-  return no_throw([&]() -> int {
-    if (bits == 0) { p->packed_bits = 0; p->out_bytes = p->frame_bytes; return OJPHGPU_OK; }
-    const Plan& P = *p->P;
-    const int rc = packed_fit(P, bits, p->container);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    const size_t nbytes = packed_bytes(P.frame_elems, bits);
-    for (DecSlot& s : p->slots) {
-      if (s.h_img.reserve(nbytes + 64)) return OJPHGPU_E_NOMEM;
-      if (!s.pixels.p && s.pixels.alloc(nbytes + 64)) return OJPHGPU_E_NOMEM;
-    }
-    p->packed_bits = bits; p->out_bytes = nbytes;
-    return OJPHGPU_OK;
-  });
-}
-
-extern "C" int ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* p, int format)
-{
-  if (!p || p->n_sub != 0 || p->pixel_bits || p->packed_bits) return OJPHGPU_E_INVALID;
-  return no_throw([&]() -> int {
-    if (format == 0) { p->video = 0; p->out_bytes = p->frame_bytes; return OJPHGPU_OK; }
-    uint64_t nbytes = 0;
-    const int rc = video_fit(*p->P, format, p->container, &nbytes);
-    if (rc) return rc;
-    if (p->has_region && (p->region[0] & 1u)) return OJPHGPU_E_INVALID;   // (a window's first column must open a pair)
-    HIPCHK(hipSetDevice(p->device));
-    for (DecSlot& s : p->slots) {
-      if (s.h_img.reserve((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM;
-      if (!s.pixels.p || s.pixels.n < (size_t)nbytes + 64) { s.pixels.release(); if (s.pixels.alloc((size_t)nbytes + 64)) return OJPHGPU_E_NOMEM; }
-    }
-    p->video = format; p->out_bytes = (size_t)nbytes;
-    return OJPHGPU_OK;
-  });
-}
+extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, int big_endian) { return dec_set_handover(p, PIXELS, pixel_bits, big_endian); }
+extern "C" int ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* p, int bits) { return dec_set_handover(p, PACKED, bits, 0); }
+extern "C" int ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* p, int format) { return dec_set_handover(p, VIDEO, format, 0); }
 
 extern "C" int ojphgpu_dec_pipe_plan(ojphgpu_dec_pipe* p, const ojphgpu_plan** plan)
 {

@@ -16,9 +16,48 @@ from .plan import Plan, make_params
 _CONTAINER = {8: np.uint8, 16: np.uint16, 32: np.int32}      # numpy view of a frame slot by container width
 
 
-def _view(ptr, nbytes, dtype=np.uint8):
-    buf = (C.c_uint8 * nbytes).from_address(ptr)
-    return np.frombuffer(buf, dtype=dtype)
+def _view(ptr, nbytes):
+    return np.frombuffer((C.c_uint8 * nbytes).from_address(ptr), dtype=np.uint8)
+
+
+def _frame_view(pipe, ptr, nbytes):
+    """numpy view of a pinned frame in the pipe's current hand-over"""
+    raw = _view(ptr, nbytes)
+    if pipe.packed:                                   # one bit string
+        return raw
+    if pipe.video:                                    # [H, row_bytes]
+        h = pipe.plan.comp_info(0)["h"]
+        return raw.reshape(h, nbytes // h)
+    if pipe.pixels is not None:                       # [H,W,C] in the file's sample type (big endian: the raw bytes)
+        c, h, w = pipe.plan.frame_shape
+        dt = np.uint8 if pipe.pixels[0] == 8 else np.dtype(">u2" if pipe.pixels[1] else "<u2")
+        return raw.view(dt).reshape(h, w, c)
+    return raw.view(_CONTAINER[pipe.container]).reshape(pipe.plan.frame_shape)
+
+
+class _Handover:
+    """The hand-over setters of both pipes (ojphgpu_{enc,dec}_pipe_set_pixels / _set_packed / _set_video; None or 0: planes
+    again): before the first acquire() of an encoder pipe / submit() of a decoder pipe, repeatable until then, one kind at a
+    time.  A refusal raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
+    pixels = packed = video = None
+
+    def _set(self, kind, *args):
+        name = "%s_pipe_set_%s" % (self._side, kind)
+        check(getattr(self._lib, "ojphgpu_" + name)(self._h, *args), name)
+
+    def set_pixels(self, bits, big_endian=False):
+        self._set("pixels", int(bits or 0), int(bool(big_endian)))
+        self.pixels = (int(bits), bool(big_endian)) if bits else None
+
+    def set_packed(self, bits):
+        self._set("packed", int(bits or 0))
+        self.packed = int(bits) if bits else None
+
+    def set_video(self, fmt):
+        """judged on the pipe's plan (a view's: the view's; a region with odd x0 is refused): three unsigned components of
+        one depth the format holds, the chroma half as wide"""
+        self._set("video", _video_code(self.plan, fmt, "%s_pipe_set_video" % self._side))
+        self.video = fmt
 
 
 def pack_bits(samples, bits):
@@ -131,7 +170,9 @@ def unpack_video(buf, fmt, width, height, bit_depth=None):
     return [np.ascontiguousarray(y), np.ascontiguousarray(f[:, :, 2]), np.ascontiguousarray(f[:, :, 3])]
 
 
-class EncoderPipe:
+class EncoderPipe(_Handover):
+    _side = "enc"
+
     def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None,
                  max_sse=None, min_psnr=None, video=None, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
@@ -148,30 +189,17 @@ class EncoderPipe:
         self._h = C.c_void_p()
         check(self._lib.ojphgpu_enc_pipe_create(self.plan.handle, device, self.depth, self.container, host_threads,
                                                 C.byref(self._h)), "enc_pipe_create")
-        self.pixels = None
         if pixels is not None:
-            check(self._lib.ojphgpu_enc_pipe_set_pixels(self._h, int(pixels[0]), int(bool(pixels[1]))), "enc_pipe_set_pixels")
-            self.pixels = (int(pixels[0]), bool(pixels[1]))
-        self.packed = None
-        if packed:                                        # planes of bit-packed samples (10 / 12 / 14 bits): acquire() -> uint8 view
-            check(self._lib.ojphgpu_enc_pipe_set_packed(self._h, int(packed)), "enc_pipe_set_packed")
-            self.packed = int(packed)
-        self.video = None
-        if video is not None:                             # one 4:2:2 video buffer: acquire() -> uint8 [H, row_bytes]
+            self.set_pixels(*pixels)
+        if packed:
+            self.set_packed(packed)
+        if video is not None:
             self.set_video(video)
         if max_bytes:
             self.set_budget(max_bytes)
         if max_sse is not None or min_psnr is not None:
             self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
         self.in_flight = 0
-
-    def set_video(self, fmt):
-        """frames are handed over as 4:2:2 video buffers of that format (ojphgpu_enc_pipe_set_video; None: planes again).
-        Before the first acquire(), not together with pixels / packed; a plan that is not three unsigned components of one
-        depth the format holds, the chroma half as wide, raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
-        code = _video_code(self.plan, fmt, "enc_pipe_set_video")
-        check(self._lib.ojphgpu_enc_pipe_set_video(self._h, code), "enc_pipe_set_video")
-        self.video = fmt
 
     def set_budget(self, max_bytes):
         """Every frame is coded at the finest step of the rate grid whose codestream is at most max_bytes long, the search
@@ -233,16 +261,7 @@ class EncoderPipe:
         if rc == capi.E_AGAIN:
             return None
         check(rc, "enc_pipe_acquire")
-        if self.packed:
-            return _view(ptr.value, n.value, np.uint8)
-        if self.video:
-            h = self.plan.comp_info(0)["h"]
-            return _view(ptr.value, n.value, np.uint8).reshape(h, n.value // h)
-        if self.pixels is not None:                     # [H,W,C] in the file's sample type (big endian: the raw bytes)
-            c, h, w = self.plan.frame_shape
-            dt = np.uint8 if self.pixels[0] == 8 else np.dtype(">u2" if self.pixels[1] else "<u2")
-            return _view(ptr.value, n.value, np.uint8).view(dt).reshape(h, w, c)
-        return _view(ptr.value, n.value, _CONTAINER[self.container]).reshape(self.plan.frame_shape)
+        return _frame_view(self, ptr.value, n.value)
 
     def submit(self):
         check(self._lib.ojphgpu_enc_pipe_submit(self._h), "enc_pipe_submit")
@@ -292,7 +311,9 @@ class EncoderPipe:
             yield self.collect()
 
 
-class DecoderPipe:
+class DecoderPipe(_Handover):
+    _side = "dec"
+
     def __init__(self, first_codestream: bytes, device=0, depth=4, container=16, host_threads=0, resilient=False, pixels=None, packed=None,
                  skip_res=None, region=None, video=None):
         """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
@@ -314,26 +335,13 @@ class DecoderPipe:
         self.plan = Plan(handle=h, owned=False)
         self.plan.skip = (int(a), int(b))
         self.plan.region = None if region is None else tuple(int(v) for v in region)
-        self.pixels = None
         if pixels is not None:
-            check(self._lib.ojphgpu_dec_pipe_set_pixels(self._h, int(pixels[0]), int(bool(pixels[1]))), "dec_pipe_set_pixels")
-            self.pixels = (int(pixels[0]), bool(pixels[1]))
-        self.packed = None
+            self.set_pixels(*pixels)
         if packed:
-            check(self._lib.ojphgpu_dec_pipe_set_packed(self._h, int(packed)), "dec_pipe_set_packed")
-            self.packed = int(packed)
-        self.video = None
+            self.set_packed(packed)
         if video is not None:
             self.set_video(video)
         self.in_flight = 0
-
-    def set_video(self, fmt):
-        """decoded frames come back as 4:2:2 video buffers of that format (ojphgpu_dec_pipe_set_video; None: planes again).
-        Before the first submit(), not together with pixels / packed; judged on the view's plan (a region with odd x0 is
-        refused); a refusal raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
-        code = _video_code(self.plan, fmt, "dec_pipe_set_video")
-        check(self._lib.ojphgpu_dec_pipe_set_video(self._h, code), "dec_pipe_set_video")
-        self.video = fmt
 
     def close(self):
         if self._h:
@@ -366,17 +374,7 @@ class DecoderPipe:
         self.in_flight -= 1                  # the oldest frame is taken whatever its outcome (a codestream of another geometry fails with E_INVALID)
         if rc != capi.E_BLOCK:
             check(rc, "dec_pipe_collect")
-        if self.packed:
-            v = _view(ptr.value, n.value, np.uint8)
-        elif self.video:
-            h = self.plan.comp_info(0)["h"]
-            v = _view(ptr.value, n.value, np.uint8).reshape(h, n.value // h)
-        elif self.pixels is not None:
-            c, h, w = self.plan.frame_shape
-            dt = np.uint8 if self.pixels[0] == 8 else np.dtype(">u2" if self.pixels[1] else "<u2")
-            v = _view(ptr.value, n.value, np.uint8).view(dt).reshape(h, w, c)
-        else:
-            v = _view(ptr.value, n.value, _CONTAINER[self.container]).reshape(self.plan.frame_shape)
+        v = _frame_view(self, ptr.value, n.value)
         if rc == capi.E_BLOCK:
             err = capi.OjphError(rc, "dec_pipe_collect: %d code-blocks" % failed.value)
             err.frame, err.failed_blocks = v.copy(), int(failed.value)

@@ -1,0 +1,196 @@
+"""The hand-over of the frame pipelines (planes, pixel-interleaved, bit-packed, 4:2:2 video buffers) set more than once before
+the first frame, and the three setters excluding each other: whatever was set last is what the pipe runs with -- sizes,
+buffers and launches -- and a refused call changes nothing.  Tiny frames (3 components, 37 x 21: 2331 samples, 1575 as
+4:2:2, neither a multiple of 32, so the packed tail is exercised), pipes of depth 2 coding 3 frames, so the slots recycle."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests.test_gpu_video import make_plan
+
+pytestmark = pytest.mark.gpu
+
+W, H = 37, 21
+# name -> (bit depth of the plan, 4:2:2?, the setters called in turn before the first frame: the last one is what counts)
+SEQUENCES = {
+    "pixels 8 then 16 big endian": (8, False, [("pixels", (8, False)), ("pixels", (16, True))]),
+    "pixels 16 then 8": (8, False, [("pixels", (16, False)), ("pixels", (8, False))]),
+    "packed 10 then 14": (10, False, [("packed", 10), ("packed", 14)]),
+    "video uyvy, planes, packed 14": (8, True, [("video", "uyvy"), ("video", None), ("packed", 14)]),
+}
+
+
+def new_plan(depth, sub):
+    from openjph_amd.plan import Plan, make_params
+    return make_plan(W, depth, True, h=H) if sub else Plan(make_params(W, H, 3, bit_depth=depth))
+
+
+def setter(pipe, kind, arg):
+    {"pixels": lambda: pipe.set_pixels(*arg), "packed": lambda: pipe.set_packed(arg), "video": lambda: pipe.set_video(arg)}[kind]()
+
+
+def handed_over(plan, planes, kind, arg):
+    """the planes of a frame -> what the caller writes into the memory an encoder pipe hands out"""
+    from openjph_amd.pipeline import pack_bits, pack_video
+    if kind == "pixels":
+        return np.stack(planes, axis=2).astype(np.uint8 if arg[0] == 8 else np.dtype(">u2" if arg[1] else "<u2"))
+    if kind == "packed":
+        return pack_bits(plan.pack_frame(planes), arg)
+    if kind == "video":
+        return pack_video(planes, arg, plan.comp_format(0)[0])
+    return plan.pack_frame(planes)
+
+
+def planes_of(plan, frame, kind, arg):
+    """the inverse, on what a decoder pipe hands back"""
+    from openjph_amd.pipeline import unpack_bits, unpack_video
+    if kind == "pixels":
+        return [frame[:, :, c] for c in range(frame.shape[2])]
+    if kind == "packed":
+        return plan.unpack_frame(unpack_bits(frame, arg, plan.frame_elems))
+    if kind == "video":
+        return unpack_video(frame, arg, W, H, plan.comp_format(0)[0])
+    return plan.unpack_frame(frame)
+
+
+def frame_bytes(plan, kind, arg, container=16):
+    from openjph_amd.pipeline import video_layout
+    n = plan.frame_elems
+    return {"pixels": lambda: n * arg[0] // 8, "packed": lambda: (n + 31) // 32 * 4 * arg, "video": lambda: video_layout(arg, W, H)[1],
+            "planes": lambda: n * container // 8}[kind]()
+
+
+@functools.lru_cache(maxsize=None)
+def reference(depth, sub):
+    """three random frames of such a plan and the codestreams the single encoder writes for them"""
+    from openjph_amd import codec
+    rng = np.random.default_rng(depth + sub)
+    enc = codec.Encoder(plan=new_plan(depth, sub))
+    frames = [[rng.integers(0, 1 << depth, (H, (W + 1) // 2 if sub and c else W)).astype(np.int32) for c in range(3)] for _ in range(3)]
+    return frames, [enc.encode(enc.plan.pack_frame(p)) for p in frames]
+
+
+def encode_frames(pipe, frames, kind, arg):
+    want_bytes = frame_bytes(pipe.plan, kind, arg, pipe.container)
+    out = []
+    for planes in frames:
+        buf = pipe.acquire()
+        while buf is None:
+            out.append(pipe.collect())
+            buf = pipe.acquire()
+        assert buf.nbytes == want_bytes, (kind, arg, buf.nbytes, want_bytes)
+        buf[...] = handed_over(pipe.plan, planes, kind, arg).reshape(buf.shape)
+        pipe.submit()
+    while pipe.in_flight:
+        out.append(pipe.collect())
+    return out
+
+
+def decode_frames(pipe, streams, kind, arg):
+    want_bytes = frame_bytes(pipe.plan, kind, arg, pipe.container)
+    out = []
+    for frame in pipe.decode_sequence(streams):
+        assert frame.nbytes == want_bytes, (kind, arg, frame.nbytes, want_bytes)
+        out.append(planes_of(pipe.plan, frame, kind, arg))
+    return out
+
+
+def same_planes(got, want):
+    return len(got) == len(want) and all(np.array_equal(np.asarray(g).astype(np.int64), w) for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("name", list(SEQUENCES))
+def test_encoder_pipe_hand_over_set_again_before_the_first_frame(name):
+    from openjph_amd.pipeline import EncoderPipe
+    depth, sub, steps = SEQUENCES[name]
+    frames, want = reference(depth, sub)
+    kind, arg = steps[-1]
+    pipe = EncoderPipe(plan=new_plan(depth, sub), depth=2, container=16)
+    for k, a in steps:
+        setter(pipe, k, a)
+    got = encode_frames(pipe, frames, kind, arg)
+    pipe.close()
+    fresh = EncoderPipe(plan=new_plan(depth, sub), depth=2, container=16, **{kind: arg})       # created with the final hand-over
+    direct = encode_frames(fresh, frames, kind, arg)
+    fresh.close()
+    assert got == want and got == direct
+
+
+@pytest.mark.parametrize("name", list(SEQUENCES))
+def test_decoder_pipe_hand_over_set_again_before_the_first_frame(name):
+    from openjph_amd.pipeline import DecoderPipe
+    depth, sub, steps = SEQUENCES[name]
+    frames, streams = reference(depth, sub)
+    pipe = DecoderPipe(streams[0], depth=2, container=16)
+    for k, a in steps:
+        setter(pipe, k, a)
+    got = decode_frames(pipe, streams, *steps[-1])
+    pipe.close()
+    assert len(got) == 3 and all(same_planes(g, f) for g, f in zip(got, frames))
+
+
+# ---- the setters exclude each other
+ON = {"pixels": (8, False), "packed": 10, "video": "uyvy"}                  # a valid argument of each kind (8-bit plans) ...
+RAW = {"pixels": ((8, 0), (0, 0)), "packed": ((10,), (0,)), "video": ((1,), (0,))}   # ... as the C call takes it, and the kind's 0
+PAIRS = [(a, b) for a in ON for b in ON if a != b]
+
+
+def raw_call(pipe, side, kind, args):
+    return getattr(pipe._lib, "ojphgpu_%s_pipe_set_%s" % (side, kind))(pipe._h, *args)
+
+
+def pair_is_422(a, b):
+    """the plan of a pair: one the hand-over that is on is valid for, and the refused setter's argument too where a plan can
+    be both (pixels ask for planes of one size, video for 4:2:2: under the one, the other is refused twice over)"""
+    return a == "video" or (a == "packed" and b == "video")
+
+
+@pytest.mark.parametrize("a,b", PAIRS)
+def test_encoder_pipe_one_kind_on_refuses_the_setters_of_the_others(a, b):
+    from openjph_amd import capi
+    from openjph_amd.pipeline import EncoderPipe
+    sub = pair_is_422(a, b)
+    frames, want = reference(8, sub)
+    pipe = EncoderPipe(plan=new_plan(8, sub), depth=2, container=16, **{a: ON[a]})
+    assert [raw_call(pipe, "enc", b, args) for args in RAW[b]] == [capi.E_INVALID, capi.E_INVALID]
+    got = encode_frames(pipe, frames[:1], a, ON[a])
+    pipe.close()
+    assert got == want[:1]
+
+
+@pytest.mark.parametrize("a,b", PAIRS)
+def test_decoder_pipe_one_kind_on_refuses_the_setters_of_the_others(a, b):
+    from openjph_amd import capi
+    from openjph_amd.pipeline import DecoderPipe
+    sub = pair_is_422(a, b)
+    frames, streams = reference(8, sub)
+    pipe = DecoderPipe(streams[0], depth=2, container=16, **{a: ON[a]})
+    assert [raw_call(pipe, "dec", b, args) for args in RAW[b]] == [capi.E_INVALID, capi.E_INVALID]
+    got = decode_frames(pipe, streams[:1], a, ON[a])
+    pipe.close()
+    assert len(got) == 1 and same_planes(got[0], frames[0])
+
+
+@pytest.mark.parametrize("sub", [False, True])
+def test_every_setter_is_refused_once_frames_flow(sub):
+    """after the first acquire() of an encoder pipe / submit() of a decoder pipe: every setter, with a valid argument and with
+    0, and the frame under way is not disturbed (4:4:4: pixels and packed would fit; 4:2:2: packed and video)"""
+    from openjph_amd import capi
+    from openjph_amd.pipeline import DecoderPipe, EncoderPipe
+    frames, streams = reference(8, sub)
+    calls = [(kind, args) for kind in RAW for args in RAW[kind]]
+    pipe = EncoderPipe(plan=new_plan(8, sub), depth=2, container=16)
+    assert pipe.acquire() is not None
+    assert [raw_call(pipe, "enc", kind, args) for kind, args in calls] == [capi.E_INVALID] * 6
+    got = encode_frames(pipe, frames[:1], "planes", None)
+    pipe.close()
+    assert got == streams[:1]
+    pipe = DecoderPipe(streams[0], depth=2, container=16)
+    pipe.acquire(len(streams[0]))[:] = np.frombuffer(streams[0], np.uint8)
+    pipe.submit()
+    assert [raw_call(pipe, "dec", kind, args) for kind, args in calls] == [capi.E_INVALID] * 6
+    frame = pipe.collect()
+    ok = frame.nbytes == frame_bytes(pipe.plan, "planes", None) and same_planes(pipe.plan.unpack_frame(frame), frames[0])
+    pipe.close()
+    assert ok
