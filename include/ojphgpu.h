@@ -456,6 +456,31 @@ int ojphgpu_ht_decode_step1(void* stream, const ojphgpu_cb_desc* d_blocks, uint3
 int ojphgpu_ht_decode_step2(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
                             const uint8_t* d_data, const uint32_t* d_quad_scratch, void* d_coef,
                             uint8_t* d_block_status);
+/* Step 1 and step 2 in ONE launch (ht_dec_fused_kernel, what the decoder objects take for blocks of at most 64 columns
+ * without refinement passes where it pays), as a stage of its own.
+ * ojphgpu_ht_decode_fused_shape: host only -- how the launch deals n blocks out on `cus` compute units (0: 256) under the
+ *   process's OJPHGPU_FUSED_SHAPE / OJPHGPU_FUSED_RINGS: out[0] shape, [1] chains per step-1 workgroup, [2] wavefronts per
+ *   workgroup, [3] step-1 workgroups n1, [4] blocks per worker wavefront, [5] worker workgroups, [6] NR of the kernel
+ *   instantiation (un-stuffing rings per worker wavefront), [7] 1 where n1 <= cus (the launch is able to run), else 0,
+ *   [8] the blocks per worker wavefront the resident wavefront slots ask for, before the cap of 8 (more than [4]: worker
+ *   workgroups beyond the resident ones, which start when others end).  `out` holds 9 values.
+ * ojphgpu_ht_decode_fused_slices: host only -- the slices of quad rows of a launch whose tallest block has max_h rows:
+ *   *count of them, slice i = quad rows [out_bounds[2i], out_bounds[2i + 1]); E_INVALID (with *count set) where cap < *count.
+ * ojphgpu_ht_decode_fused_state_words: uint32 elements of d_state for n blocks.
+ * ojphgpu_ht_decode_fused: the launch.  d_blocks: the whole array ojphgpu_ht_decode_layout laid out, every block at most 64
+ *   columns wide, cleanup pass only, all reversible or all irreversible (`reversible`); d_quad_scratch: quad_elems elements
+ *   of that layout; d_state: ojphgpu_ht_decode_fused_state_words(n) elements, zeroed ONCE -- nothing is cleared between
+ *   runs, `epoch` > 0 must grow from run to run on it; max_h: the tallest block; d_block_status: n bytes and, at the next
+ *   multiple of 4, the 4-byte RETRY word (== epoch after the run: a wait ran out, the blocks have to be decoded again through
+ *   the separate launches); cus: the compute units to deal the work out for, 0 or more than the current device has = all
+ *   of the device's (fewer only: every workgroup of the launch must be resident).  E_INVALID where the launch would need
+ *   more step-1 workgroups than `cus`. */
+int ojphgpu_ht_decode_fused_shape(uint32_t n, uint32_t cus, uint32_t* out);
+int ojphgpu_ht_decode_fused_slices(uint32_t max_h, uint32_t* out_bounds, uint32_t cap, uint32_t* count);
+uint64_t ojphgpu_ht_decode_fused_state_words(uint32_t n);
+int ojphgpu_ht_decode_fused(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const uint8_t* d_data, void* d_coef,
+                            uint32_t* d_quad_scratch, uint32_t* d_state, uint8_t* d_block_status, uint32_t epoch,
+                            uint32_t max_h, int reversible, uint32_t cus);
 /* fourth launch, only needed when some block has num_passes > 1 (foreign codestreams): SigProp +
  * MagRef passes (ojph_block_decoder32.cpp:1318-1609) over the blocks that carry them; step 2 left
  * those blocks as sign-magnitude words, this launch refines and de-quantises them.  Bit 1 of

@@ -685,6 +685,74 @@ def ht_decode(descs: np.ndarray, data: np.ndarray, coef):
     return status.cpu().numpy()[:len(descs)]
 
 
+def ht_decode_fused_shape(n, cus=0):
+    """how the fused launch deals n blocks out on `cus` compute units under this process's OJPHGPU_FUSED_SHAPE / _RINGS
+    (host only): dict of shape, ch, wgw, n1, per_wave, wwgs, nr, able (n1 <= cus), want (per_wave before the cap of 8)"""
+    out = (C.c_uint32 * 9)()
+    check(capi.lib().ojphgpu_ht_decode_fused_shape(int(n), int(cus), out), "ht_decode_fused_shape")
+    return dict(zip(("shape", "ch", "wgw", "n1", "per_wave", "wwgs", "nr", "able", "want"), (int(v) for v in out)))
+
+
+def ht_decode_fused_slices(max_h):
+    """the fused launch's slices of quad rows for a tallest block of max_h rows (host only): [(lo, hi), ...]"""
+    L = capi.lib()
+    cnt = C.c_uint32()
+    L.ojphgpu_ht_decode_fused_slices(int(max_h), None, 0, C.byref(cnt))
+    out = (C.c_uint32 * (2 * max(cnt.value, 1)))()
+    check(L.ojphgpu_ht_decode_fused_slices(int(max_h), out, cnt.value, C.byref(cnt)), "ht_decode_fused_slices")
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(cnt.value)]
+
+
+def ht_decode_layout(descs: np.ndarray):
+    """(quad_elems, aux_elems) ojphgpu_ht_decode_layout asks for these descriptors (a copy is laid out, not `descs`)"""
+    descs = np.ascontiguousarray(descs.copy())
+    q, a = C.c_uint64(), C.c_uint64()
+    check(capi.lib().ojphgpu_ht_decode_layout(descs.ctypes.data, len(descs), C.byref(q), C.byref(a)), "ht_decode_layout")
+    return int(q.value), int(a.value)
+
+
+class FusedScratch:
+    """The scratch of ojphgpu_ht_decode_fused for launches of up to max_blocks blocks and quad_elems record words: records,
+    the state (zeroed once, here) and the status bytes with the RETRY word behind them; counts the epoch of the runs."""
+
+    def __init__(self, max_blocks, quad_elems, device=0):
+        torch = _torch()
+        dev = torch.device("cuda", device)
+        self.max_blocks, self.quad_elems, self.device, self.epoch = int(max_blocks), int(quad_elems), device, 0
+        self.quads = torch.zeros(self.quad_elems + 16, dtype=torch.int32, device=dev)
+        self.state = torch.zeros(int(capi.lib().ojphgpu_ht_decode_fused_state_words(self.max_blocks)), dtype=torch.int32, device=dev)
+        self.status = torch.zeros(((self.max_blocks + 3) & ~3) + 4, dtype=torch.uint8, device=dev)
+
+
+def ht_decode_fused(descs: np.ndarray, data: np.ndarray, coef, scratch: FusedScratch, reversible, cus=0):
+    """step 1 + step 2 of `descs` in the one fused launch, dealt out for `cus` compute units (0: the device's), on a scratch
+    that earlier runs have used; returns (status[:n], the RETRY word, the run's epoch).  Raises OjphError(E_INVALID) where
+    the launch is unable to run (more step-1 workgroups than `cus`)."""
+    torch = _torch()
+    dev = coef.device.index
+    L = capi.lib()
+    n = len(descs)
+    descs = np.ascontiguousarray(descs.copy())
+    q, a = C.c_uint64(), C.c_uint64()
+    check(L.ojphgpu_ht_decode_layout(descs.ctypes.data, n, C.byref(q), C.byref(a)), "ht_decode_layout")
+    if n > scratch.max_blocks or int(q.value) > scratch.quad_elems or dev != scratch.device:
+        raise ValueError("the FusedScratch is too small for this launch or on another device")
+    max_h = int(descs["h"].max()) if n else 0
+    d = to_device(descs, dev)
+    dd = to_device(np.concatenate([np.asarray(data, np.uint8), np.zeros(64, np.uint8)]), dev)
+    epoch = scratch.epoch + 1
+    with torch.cuda.device(dev):
+        check(L.ojphgpu_ht_decode_fused(_stream_ptr(torch, dev), C.c_void_p(d.data_ptr()), n, C.c_void_p(dd.data_ptr()),
+                                        C.c_void_p(coef.data_ptr()), C.c_void_p(scratch.quads.data_ptr()),
+                                        C.c_void_p(scratch.state.data_ptr()), C.c_void_p(scratch.status.data_ptr()), epoch,
+                                        max(max_h, 1), 1 if reversible else 0, int(cus)), "ht_decode_fused")
+    scratch.epoch = epoch
+    torch.cuda.synchronize(dev)
+    st = scratch.status.cpu().numpy()
+    r = (n + 3) & ~3
+    return st[:n].copy(), int(st[r:r + 4].view(np.uint32)[0]), epoch
+
+
 def unpack_pixels(pixels, num_comps=None, big_endian=False, dtype=None):
     """pixel-interleaved samples on the device ([H,W,C] uint8 / uint16 tensor -- for big-endian 16-bit data the tensor
     holds the file's bytes as they are) -> planes [C,H,W] in `dtype` (uint8 / int16 / uint16 / int32; default: as the

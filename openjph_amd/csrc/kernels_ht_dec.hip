@@ -1059,10 +1059,19 @@ __device__ __forceinline__ void step2_block(const ojphgpu_cb_desc& d, uint32_t b
     if (verdict == 2u && qy_begin == 0) { zero_block(); if (lane == 0) state[19] = 1u; wave_sync(); }
     if (verdict != 0u) return;
     ms_len = rdfirst(state[20]);
+  } else if (SLICED) {
+    // One ring per wavefront: the verdict of check_block is taken HERE as well, on the same bytes -- not from the block's status
+    // byte.  The lanes of a chain wavefront that refuse their block store that byte on the far side of a divergent branch,
+    // which the compiler places BEHIND the other lanes' chains: until the chain wavefront ends a worker read 0 there, decoded
+    // the refused block's slices from whatever records lay in the scratch and never zeroed it
+    // (tests/test_gpu_fused_geometry.py).  A live chain lane stores its 0 before its first row, so nothing else is lost.
+    const uint32_t scup0 = rdfirst(check_block(d, cb));
+    st = scup0 == 0u ? 1u : 0u;
+    ms_len = lcup - scup0;
   } else {
     // (what every lane reads from one address is kept as what it is, a scalar: comparisons and sums of such values then run
     // on the scalar unit, beside the vector instructions of another wavefront)
-    st = rdfirst(SLICED ? (uint32_t)__hip_atomic_load(block_status + bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (uint32_t)block_status[bi]);
+    st = rdfirst((uint32_t)block_status[bi]);
     const uint32_t len_b1 = rdfirst(cb[lcup - 1]), len_b2 = rdfirst(cb[lcup >= 2u ? lcup - 2u : 0u]);   // (a one-byte segment has failed in step 1; its bytes are not used)
     ms_len = lcup - ((len_b1 << 4) + (len_b2 & 0xFu));
   }
@@ -1839,7 +1848,9 @@ __global__ __launch_bounds__(64 * WGW) __attribute__((amdgpu_waves_per_eu(6))) v
       if (wv < 2u * (uint32_t)CH) raw_partner<1>(cb, d.len1, scup, room, v0, v1, evw, s_ev, s_eprog, s_econs, s_vr, s_vprog, s_vcons, s_done, lane);
       else raw_partner<2>(cb, d.len1, scup, room, v0, v1, evw, s_ev, s_eprog, s_econs, s_vr, s_vprog, s_vcons, s_done, lane);
     } else {
-      __hip_atomic_store(block_status + bi, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (what the last run left is not this run's)
+      // (what the last run left is not this run's.  ONLY this 0 is in memory before the block's first row: the 1 of a lane that
+      // refuses its block, above, is stored when the other lanes' chains have run -- nothing in this launch may read it)
+      __hip_atomic_store(block_status + bi, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       uint32_t* rec = quads + rec16_base(d, bi);
       RingRd vlc; vlc.init(s_vr, s_vprog, s_vcons, lane);
       EvRd mel; mel.init(s_ev, s_eprog, s_econs, evw, lane);
@@ -2407,7 +2418,7 @@ bool dec_fuses() { return dec_fuse_mode() != 0; }
 // Shape: workgroups of 12 wavefronts, 4 chains (+ 8 partners) in the step-1 role, two per CU (OJPHGPU_FUSED_SHAPE=0:
 // 8 wavefronts, 2 chains, < 40 KB of LDS, four per CU = all 32 wavefront slots of a CU in use -- measured slower, 0.43
 // against 0.39 ms for the 8K frame: the chains lose more issue slots to eight wavefronts per SIMD than the workers gain).
-struct FusedShape { uint32_t shape, ch, wgw, n1, per_wave, wwgs; };
+struct FusedShape { uint32_t shape, ch, wgw, n1, per_wave, wwgs, want; };   // want: per_wave before the cap of S2_MAX_PER_WAVE
 static FusedShape fused_shape(uint32_t n, uint32_t cus)
 {
   static const uint32_t shape = [] { const char* e = getenv("OJPHGPU_FUSED_SHAPE"); return e ? (uint32_t)atoi(e) : 1u; }();
@@ -2419,9 +2430,17 @@ static FusedShape fused_shape(uint32_t n, uint32_t cus)
   f.n1 = (n + 64u * f.ch - 1u) / (64u * f.ch);
   const uint32_t waves = (wg_slots > f.n1 ? wg_slots - f.n1 : 1u) * f.wgw;
   uint32_t per_wave = (n + waves - 1u) / waves;
+  f.want = per_wave;
   f.per_wave = per_wave < 1u ? 1u : per_wave > S2_MAX_PER_WAVE ? S2_MAX_PER_WAVE : per_wave;
   f.wwgs = ((n + f.per_wave - 1u) / f.per_wave + f.wgw - 1u) / f.wgw;
   return f;
+}
+// NR of the instantiation the launch takes: a ring per block where the twelve wavefronts' rings fit the LDS the step-1 role
+// needs anyway (OJPHGPU_FUSED_RINGS=1: never), one ring per wavefront otherwise
+static uint32_t fused_rings(const FusedShape& f)
+{
+  static const bool rings = [] { const char* e = getenv("OJPHGPU_FUSED_RINGS"); return !e || atoi(e) != 1; }();
+  return f.shape == 1 && rings && f.per_wave <= (uint32_t)S2_RINGS ? (uint32_t)S2_RINGS : 1u;
 }
 // compute units of a device (the decoder objects ask once, for THEIR device, and hand the number to the calls below)
 uint32_t device_cus(int device)
@@ -2472,9 +2491,7 @@ int ht_decode_fused_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32
   const dim3 grid(n1 + wwgs), wg(64 * wgw);
 #define FUSED_LAUNCH(T, C, W, R) hipLaunchKernelGGL((ht_dec_fused_kernel<T, C, W, R>), grid, wg, 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, \
                                                  (uint32_t*)d_coef, d_block_status, d_state, n1, per_wave, max_qh, epoch, dbg, ticket_off, wait_ticks, d_host_retry)
-  // a ring per block where the twelve wavefronts' rings fit the LDS the step-1 role needs anyway (OJPHGPU_FUSED_RINGS=1: never)
-  static const bool rings = [] { const char* e = getenv("OJPHGPU_FUSED_RINGS"); return !e || atoi(e) != 1; }();
-  if (shape == 1 && rings && per_wave <= (uint32_t)S2_RINGS) { if (tx == 1) FUSED_LAUNCH(1, 4, 12, S2_RINGS); else FUSED_LAUNCH(2, 4, 12, S2_RINGS); }
+  if (fused_rings(f) > 1u) { if (tx == 1) FUSED_LAUNCH(1, 4, 12, S2_RINGS); else FUSED_LAUNCH(2, 4, 12, S2_RINGS); }
   else if (shape == 1) { if (tx == 1) FUSED_LAUNCH(1, 4, 12, 1); else FUSED_LAUNCH(2, 4, 12, 1); }
   else                 { if (tx == 1) FUSED_LAUNCH(1, 2, 8, 1); else FUSED_LAUNCH(2, 2, 8, 1); }
 #undef FUSED_LAUNCH
@@ -2513,6 +2530,46 @@ extern "C" int ojphgpu_ht_decode_step2(void* stream, const ojphgpu_cb_desc* d_bl
                                         uint8_t* d_block_status)
 {
   return ojphgpu::ht_decode_step2_launch(stream, d_blocks, n, d_data, d_quad_scratch, d_coef, d_block_status, 0);
+}
+
+// ---- the fused launch as a stage: its geometry (host only) and the launch itself -------------------------------------------
+extern "C" int ojphgpu_ht_decode_fused_shape(uint32_t n, uint32_t cus, uint32_t* out)
+{
+  if (!out) return OJPHGPU_E_INVALID;
+  const ojphgpu::FusedShape f = ojphgpu::fused_shape(n, cus);
+  out[0] = f.shape; out[1] = f.ch; out[2] = f.wgw; out[3] = f.n1; out[4] = f.per_wave; out[5] = f.wwgs;
+  out[6] = ojphgpu::fused_rings(f);
+  out[7] = f.n1 <= (cus ? cus : 256u) ? 1u : 0u;
+  out[8] = f.want;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_ht_decode_fused_slices(uint32_t max_h, uint32_t* out_bounds, uint32_t cap, uint32_t* count)
+{
+  if (!count || max_h == 0 || (!out_bounds && cap)) return OJPHGPU_E_INVALID;
+  const SliceSched sched((max_h + 1u) >> 1);
+  *count = sched.n;
+  if (cap < sched.n) return OJPHGPU_E_INVALID;
+  for (uint32_t sl = 0; sl < sched.n; ++sl) sched.bounds(sl, out_bounds[2 * sl], out_bounds[2 * sl + 1]);
+  return OJPHGPU_OK;
+}
+
+extern "C" uint64_t ojphgpu_ht_decode_fused_state_words(uint32_t n) { return ojphgpu::ht_decode_fused_state_words(n); }
+
+extern "C" int ojphgpu_ht_decode_fused(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const uint8_t* d_data, void* d_coef,
+                                        uint32_t* d_quad_scratch, uint32_t* d_state, uint8_t* d_block_status, uint32_t epoch,
+                                        uint32_t max_h, int reversible, uint32_t cus)
+{
+  if (n == 0) return OJPHGPU_OK;
+  if (epoch == 0) return OJPHGPU_E_INVALID;
+  // a caller can pretend FEWER compute units than the chip has, never more: every workgroup of the launch stays resident
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return OJPHGPU_E_HIP;
+  const uint32_t have = ojphgpu::device_cus(dev);
+  if (cus == 0 || cus > have) cus = have;
+  if (ojphgpu::fused_shape(n, cus).n1 > cus) return OJPHGPU_E_INVALID;      // (a step-1 workgroup per CU at most: ht_decode_fused_pays)
+  return ojphgpu::ht_decode_fused_launch(stream, d_blocks, n, d_data, d_quad_scratch, d_coef, d_block_status, d_state, epoch, max_h,
+                                         1 | (reversible ? 4 : 8), cus, nullptr);
 }
 
 extern "C" int ojphgpu_ht_decode_refine(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
