@@ -608,7 +608,34 @@ static_assert(MEL_CAP + 8 >= 4 * (MEL_CAP / 4 + 2), "raw MEL words");
 #endif
 static_assert(NWG_PER_CU * (2 * 2048 * 2 + 64 * 4 + NWAVES * sizeof(NarrowLds)) <= 160 * 1024, "the narrow kernel's workgroups do not fit the LDS as planned");
 
+#ifndef ENC_ROWS_W4V
+#define ENC_ROWS_W4V 1                  // 1: blocks a multiple of four columns wide run a step loop of their own whose sample rows are ONE 16-byte load per
+#endif                                  // lane; 0: one loop for all, the kind of load selected per block (what that compiles to)
+#ifndef ENC_ROWS_AHEAD
+#define ENC_ROWS_AHEAD 1                // steps whose sample rows are in flight: 1 = one register set; 2 = two sets, the loop unrolled by two (built,
+#endif                                  // measured, no gain: DESIGN 4.4)
+static_assert(ENC_ROWS_AHEAD == 1 || ENC_ROWS_AHEAD == 2, "one or two steps of rows in flight");
+
 struct __attribute__((aligned(4))) U4 { uint32_t x, y, z, w; };
+// four samples as ONE load: a vector (a struct of four words is loaded word by word) that promises no more than the dword
+// alignment a row has -- coef_off and pitch are the caller's
+typedef uint32_t U4V __attribute__((ext_vector_type(4), aligned(4)));
+
+// The two sample rows of one quad row of a lane's pair, in the registers the loads filled: nothing reads them before
+// arrived(), the point where the step that codes them waits for them (a use next to a load is a wait for
+// everything in flight).  KIND 1: two 16-byte loads; 2 (and 0, the selected form): eight dword loads.
+template <int KIND> struct RawRows {
+  uint32_t t[4], b[4];
+  __device__ __forceinline__ void arrived() { asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])); }
+  __device__ __forceinline__ uint32_t top(int k) const { return t[k]; }
+  __device__ __forceinline__ uint32_t bot(int k) const { return b[k]; }
+};
+template <> struct RawRows<1> {
+  U4V t, b;
+  __device__ __forceinline__ void arrived() { asm volatile("" : "+v"(t), "+v"(b)); }
+  __device__ __forceinline__ uint32_t top(int k) const { return t[k]; }
+  __device__ __forceinline__ uint32_t bot(int k) const { return b[k]; }
+};
 
 __device__ __forceinline__ uint32_t dpp_prev(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false); }  // wave_shr:1 (0 into lane 0)
 __device__ __forceinline__ uint32_t dpp_next(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, false); }  // wave_shl:1 (0 into lane 63)
@@ -752,54 +779,32 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   const uint32_t x0 = 4u * px;
   const bool has_q1 = pxok && x0 + 2 < W;
 
-  // Samples of one quad row of this lane's pair: top[0..3], bot[0..3].  The loads are UNCONDITIONAL: rows and columns
-  // are clamped into the block, a lane / row / column that does not exist fetches something valid and is masked when
-  // the values are consumed, one step later.  (With a branch per case the two rows of the full-width case were
-  // separated by a wait for everything in flight -- the zero-initialisation of the registers the partial-width case
-  // loads into -- and the wavefront sat out a full memory latency in the middle of every step: SQ_WAIT_ANY 52 %.)
-  // Whether the block is a multiple of four columns wide is wave-uniform: the usual blocks take two 16-byte loads per
-  // lane, the others eight dword loads with clamped columns.
-  const bool w4 = (W & 3u) == 0;
-  auto load_rows = [&](uint32_t qy, uint32_t* top, uint32_t* bot) {
-    const uint32_t qyc = min(qy, QH - 1u);
-    const uint32_t y0 = 2u * qyc, y1 = min(y0 + 1u, H - 1u);
-    const uint32_t* r0 = src + (size_t)y0 * pitch;
-    const uint32_t* r1 = src + (size_t)y1 * pitch;
-    if (ABL & 32) { r0 = coef + (size_t)bi * 4096u + y0 * 64u; r1 = coef + (size_t)bi * 4096u + y1 * 64u; }   // timing experiment: block-contiguous samples
-    if (w4) {
-      const uint32_t xc = min(x0, W - 4u);
-      const U4 a = *reinterpret_cast<const U4*>(r0 + xc);
-      const U4 c = *reinterpret_cast<const U4*>(r1 + xc);
-      top[0] = a.x; top[1] = a.y; top[2] = a.z; top[3] = a.w;
-      bot[0] = c.x; bot[1] = c.y; bot[2] = c.z; bot[3] = c.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { const uint32_t xk = min(x0 + (uint32_t)k, W - 1u); top[k] = r0[xk]; bot[k] = r1[xk]; }
-    }
-  };
-  // The first step's rows.  The branch is wave-uniform, and a wavefront that skips it never reads the registers: nothing
-  // is merged into them, so no wait lands behind the loads.
-  uint32_t ntop[4], nbot[4];
-  if (mine) load_rows(r, ntop, nbot);
-
+  // The table copy, the LDS clears and the workgroup's barrier.  Every wavefront runs this ONCE, in whichever arm of the
+  // kernel it is (a barrier counts the wavefronts that arrive, not where they arrive from).
   // (16 bytes per lane and turn.  A workgroup lives for 12-40 us and meets at the barrier below before it codes anything: with
   // 2-byte turns, sixteen of them, the 8K frame's encode was 0.458 ms instead of 0.440, 32 x 32 blocks 0.603 instead of 0.562)
-  for (int i = threadIdx.x; i < 2 * 2048 / 8; i += blockDim.x)
-    reinterpret_cast<uint4*>(&s_vlc[0][0])[i] = reinterpret_cast<const uint4*>(&ojphgpu::g_enc_vlc[0][0])[i];
-  if (threadIdx.x < 64) s_uvlc[threadIdx.x] = uvlc_word(threadIdx.x);
-  if (mine) {
-    for (int i = lane; i < PMS_WORDS; i += 64) L.ms[i] = 0;
-    for (int i = lane; i < PVLC_WORDS; i += 64) L.vlc[i] = 0;
-    if (lane < (int)MEL_RAW_WORDS) reinterpret_cast<uint32_t*>(L.mel)[lane] = 0;
-    wave_sync();
-    if (lane == 0) { L.vlc[0] = 0xF; outb[OUT_CAP - 1] = 0xFF; }          // vlc_init: head byte, 4 bits already used (:365-375)
-    wave_sync();
-  }
-  __syncthreads();
+  auto prologue = [&](bool clear) __attribute__((always_inline)) {
+    for (int i = threadIdx.x; i < 2 * 2048 / 8; i += blockDim.x)
+      reinterpret_cast<uint4*>(&s_vlc[0][0])[i] = reinterpret_cast<const uint4*>(&ojphgpu::g_enc_vlc[0][0])[i];
+    if (threadIdx.x < 64) s_uvlc[threadIdx.x] = uvlc_word(threadIdx.x);
+    if (clear) {
+      for (int i = lane; i < PMS_WORDS; i += 64) L.ms[i] = 0;
+      for (int i = lane; i < PVLC_WORDS; i += 64) L.vlc[i] = 0;
+      if (lane < (int)MEL_RAW_WORDS) reinterpret_cast<uint32_t*>(L.mel)[lane] = 0;
+      wave_sync();
+      if (lane == 0) { L.vlc[0] = 0xF; outb[OUT_CAP - 1] = 0xFF; }          // vlc_init: head byte, 4 bits already used (:365-375)
+      wave_sync();
+    }
+    __syncthreads();
+  };
   if (!mine) {
+    prologue(false);
     if (my_kind && lane == 0) { results[bi].offset = 0; results[bi].length = 0; }   // an empty block
     return;
   }
+  // Whether the block is a multiple of four columns wide is wave-uniform: the usual blocks take two 16-byte loads per
+  // lane and step, the others eight dword loads with clamped columns -- each in a step loop of its own (code_steps).
+  const bool w4 = (W & 3u) == 0;
 
   // wave-uniform stream state
   uint32_t ms_pend = 0, ms_base = 0, ms_k = 0, ms_ff = 0;   // pending bits in L.ms and where they start, bytes written, last byte was 0xFF
@@ -807,7 +812,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   uint32_t mel_k = 0, mel_c = 0, mel_bits = 0, mel_err = 0;           // MEL coder: state (see mel_at), raw bits written
   uint32_t* const mel_raw = reinterpret_cast<uint32_t*>(L.mel);       // raw MEL bit string until the block ends, then its bytes
   // `len` bits of `code` at bit `pos` of the raw string, MSB first (len <= 24)
-  auto mel_or = [&](uint32_t code, uint32_t len, uint32_t pos) {
+  auto mel_or = [&](uint32_t code, uint32_t len, uint32_t pos) __attribute__((always_inline)) {
     if (len) {
       const uint32_t sh = pos & 31u, w = pos >> 5;
       const uint64_t v = (uint64_t)code << (64u - sh - len);
@@ -816,7 +821,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     }
   };
   // '1' bits of completed runs, from the scalar side (lane 0 writes them): n <= 24
-  auto mel_ones = [&](uint32_t n) {
+  auto mel_ones = [&](uint32_t n) __attribute__((always_inline)) {
     if (n == 0u) return;
     if (mel_bits + n > MEL_RAW_BITS) mel_err = 1;
     else if (lane == 0) mel_or((1u << n) - 1u, n, mel_bits);
@@ -824,7 +829,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   };
   // zeros that no "1" event follows in this step: c keeps them; once the coder is through a run at k = 12 the finished runs
   // leave their bits (c stays below 85 between steps)
-  auto mel_zeros = [&](uint32_t n) {
+  auto mel_zeros = [&](uint32_t n) __attribute__((always_inline)) {
     mel_c += n;
     if (mel_c >= 85u) {
       const uint32_t full = (mel_c - 53u) >> 5;
@@ -841,7 +846,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   // block's 64-byte aligned scratch slot in HBM, the 0..3 bytes left over move to the front, and coding goes on in
   // LDS -- so every byte that leaves for HBM leaves in aligned dwords, also at the end.
   uint32_t ms_out = 0;
-  auto flush_stage = [&]() -> bool {
+  auto flush_stage = [&]() __attribute__((always_inline)) -> bool {
     const uint32_t have = ms_k - ms_out, nwd = have >> 2;
     if (ms_out + 4u * nwd > ms_cap) return false;
     uint32_t* g = reinterpret_cast<uint32_t*>(ms_spill + ms_out);
@@ -860,7 +865,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   // takes four consecutive bytes, speculating that none of the window's bytes is 0xFF; the window is cut
   // behind the first 0xFF (the byte after it carries 7 bits and shifts everything that follows) and the
   // next one starts there.  `flush` also emits the final partial window.  Returns the bit position reached.
-  auto ms_windows = [&](uint32_t base, uint32_t T, bool flush) -> uint32_t {
+  auto ms_windows = [&](uint32_t base, uint32_t T, bool flush) __attribute__((always_inline)) -> uint32_t {
     uint32_t pos = base;
     for (;;) {
       const uint32_t first_n = ms_ff ? 7u : 8u;
@@ -902,7 +907,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   // runs while 256 whole bytes are pending): no per-lane byte counts, lane 0's 7-bit byte only when the previous window
   // ended on an 0xFF, and the lane's four bytes leave as ONE (unaligned) dword store -- the lane at the cut writes up to
   // three bytes too many, into space the next window overwrites (the capacity test keeps 72 bytes free above the cursor).
-  auto ms_windows_full = [&](uint32_t base, uint32_t T) -> uint32_t {
+  auto ms_windows_full = [&](uint32_t base, uint32_t T) __attribute__((always_inline)) -> uint32_t {
     uint32_t pos = base;
     for (;;) {
       const uint32_t first_n = ms_ff ? 7u : 8u;
@@ -924,7 +929,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     return pos;
   };
   // same for the VLC buffer: bytes grow downwards, the rule looks at the byte above (:386-405)
-  auto vlc_windows_full = [&](uint32_t base, uint32_t T) -> uint32_t {     // whole 64-byte windows only
+  auto vlc_windows_full = [&](uint32_t base, uint32_t T) __attribute__((always_inline)) -> uint32_t {     // whole 64-byte windows only
     uint32_t pos = base;
     for (;;) {
       if (pos + 8u * 64u > T) break;
@@ -944,7 +949,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     }
     return pos;
   };
-  auto vlc_windows = [&](uint32_t base, uint32_t T, bool flush) -> uint32_t {
+  auto vlc_windows = [&](uint32_t base, uint32_t T, bool flush) __attribute__((always_inline)) -> uint32_t {
     uint32_t pos = base;
     for (;;) {
       if (!flush && pos + 8u * 64u > T) break;
@@ -973,7 +978,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     return pos;
   };
   // moves the un-emitted bits [pos, T) of a bit buffer to its front and clears the rest
-  auto compact = [&](uint32_t* buf, uint32_t pos, uint32_t T, uint32_t nwords) -> uint32_t {
+  auto compact = [&](uint32_t* buf, uint32_t pos, uint32_t T, uint32_t nwords) __attribute__((always_inline)) -> uint32_t {
     const uint32_t rem = T - pos, nw = (rem + 31u) >> 5;           // nw <= 64 (MagSgn: < 2048 pending bits), <= 17 (VLC)
     const uint32_t w0 = pos >> 5, sh = pos & 31u;
     uint32_t keep = 0;
@@ -990,343 +995,411 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     return rem;
   };
 
-  // ---- per-lane constants of the block ----
-  // The quantise transfer of a sample is ONE multiply (9/7) or ONE and (5/3) by a per-lane, per-column constant that is
-  // zero for the columns of this lane outside the block: what the clamped loads fetched there quantises to zero, so
-  // rho, exponents and MagSgn lengths of samples that do not exist come out as zero without a select per sample.
-  // 9/7: floor(|x| * (1/delta)) >> p == floor(|x| * ((1/delta) * 2^-p)) -- the scaling by a power of two is exact.
-  float colf[4]; uint32_t colm[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool in = pxok && x0 + (uint32_t)k < W;
-    colf[k] = in ? ldexpf(delta_inv, -(int)p) : 0.0f;
-    colm[k] = in ? (1u << (31u - p)) - 1u : 0u;                          // the magnitude bits the coder keeps: mu < 2^K_max
-  }
-  const bool ragged = (QH & (RPS - 1u)) != 0 || (H & 1u) != 0;           // the last step has quad rows / sample rows that do not exist
-
   // one 32-bit value of at most 32 bits OR-ed into a bit buffer at bit position pos (the second word gets zeros when the
   // value does not straddle).  Lanes with nothing to add stay out: a lane without bits has the position of the next lane
   // that has some, and on sparse content -- most quads of a step without a significant sample -- sixty lanes sent their
   // zeros to ONE word, same-address LDS atomics that the bank serves one after the other (8K frame at 0.01 bytes per
   // sample: 0.46 ms of block coding, 0.18 with these ten atomics per lane and step left out altogether).
   // (the callers test once per buffer: `tot` / `vl`, the lane's bits of the step)
-  auto or32 = [&](uint32_t* buf, uint32_t pos, uint32_t v) {
+  auto or32 = [&](uint32_t* buf, uint32_t pos, uint32_t v) __attribute__((always_inline)) {
     const uint32_t sh = pos & 31u;
     uint32_t* wp = buf + (pos >> 5);
     atomicOr(wp, v << sh);
     atomicOr(wp + 1, (v >> 1) >> (sh ^ 31u));
   };
   // bytes of x that are not zero -> 0x80 in that byte (bytes < 0x80); 0x80-flags of four bytes -> bits 0..3
-  auto nz_flags = [](uint32_t x) -> uint32_t { return (x + 0x7F7F7F7Fu) & 0x80808080u; };
-  auto gather4 = [](uint32_t f) -> uint32_t { return ((f >> 7) * 0x10204080u) >> 28; };
+  auto nz_flags = [](uint32_t x) __attribute__((always_inline)) -> uint32_t { return (x + 0x7F7F7F7Fu) & 0x80808080u; };
+  auto gather4 = [](uint32_t f) __attribute__((always_inline)) -> uint32_t { return ((f >> 7) * 0x10204080u) >> 28; };
   typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-  auto pk_max = [](uint32_t a, uint32_t b2) -> uint32_t {
+  auto pk_max = [](uint32_t a, uint32_t b2) __attribute__((always_inline)) -> uint32_t {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b2)));
   };
   // neighbour lanes of the same quad row (zero at the row's ends)
-  auto left_of = [&](uint32_t v) -> uint32_t {
+  auto left_of = [&](uint32_t v) __attribute__((always_inline)) -> uint32_t {
     if (LOGP == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);      // row_shr:1
     const uint32_t t = dpp_prev(v); return px == 0 ? 0u : t;
   };
-  auto right_of = [&](uint32_t v) -> uint32_t {
+  auto right_of = [&](uint32_t v) __attribute__((always_inline)) -> uint32_t {
     if (LOGP == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xF, 0xF, false);      // row_shl:1
     const uint32_t t = dpp_next(v); return px == PPR - 1u ? 0u : t;
   };
 
-  // the first step's rows, requested at the kernel's entry, stay in the registers they arrived in until the quantise below
-  asm volatile("" :: "v"(ntop[0]), "v"(ntop[1]), "v"(ntop[2]), "v"(ntop[3]), "v"(nbot[0]), "v"(nbot[1]), "v"(nbot[2]), "v"(nbot[3]));
-  for (uint32_t step = 0; step < nsteps && !err; ++step) {
-    const uint32_t qy = RPS * step + r;
-    const bool active = pxok && qy < QH;
-    // ---- quantise transfer + the coder's view of a sample (ojph_codestream_gen.cpp:59-121, ojph_block_encoder.cpp:592-601):
-    // mu = the magnitude above bit-plane p (the reference's val = 2 mu), the exponent e = bit length of 2 mu - 1, and
-    // sv = 2 (mu - 1) + sign, what MagSgn takes its bits from.  The sign-magnitude word of the reference is never formed.
-    if (ragged && step + 1 == nsteps) {                 // rows below the block: what was fetched for them counts as zero
-      const bool bot = active && 2u * qy + 1u < H;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { ntop[k] = active ? ntop[k] : 0u; nbot[k] = bot ? nbot[k] : 0u; }
-    }
-    uint32_t mu[8], sx[8];                              // sx: a word whose bit 31 is the sample's sign
-    uint32_t nz = 0;                                    // OR of the step's magnitudes (rev: before the mask, bit K_max included)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                       // quad order: n = 0:(x,y) 1:(x,y+1) 2:(x+1,y) 3:(x+1,y+1)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const uint32_t raw = j ? nbot[k] : ntop[k];
-        if (rev) {
-          const int v = (int)raw;
-          const uint32_t a = (uint32_t)(v >= 0 ? v : -v);
-          mu[2 * k + j] = a & colm[k];                                        // :70-76, with the same wrap-around when |v| >= 2^K_max:
-          sx[2 * k + j] = raw | (a << p);                                     // its top bit lands on the sign
-          nz |= a;                                                            // (clamped loads: every lane holds samples of the block's own rows)
-        } else {
-          mu[2 * k + j] = (uint32_t)__fmul_rn(fabsf(__uint_as_float(raw)), colf[k]);   // :113-118, C truncation
-          sx[2 * k + j] = raw;
-          nz |= mu[2 * k + j];
-        }
-      }
-    }
-    // A magnitude of more than K_max bits (Part-2 kernels whose gain outruns the guard bits; see to_sign_mag): reversible,
-    // the bits above K_max are dropped and bit K_max has landed on the sign; irreversible, the reference's conversion of a
-    // product beyond 2^31 returns INT_MIN -- the sample codes as a zero.  Both leave a bit in the reference's max_val,
-    // and a block with a non-zero max_val is coded even if none of its samples is significant (ojph_codeblock.cpp:142-175).
-    if (__ballot((nz >> K) != 0u) != 0ull) {            // (wave-uniform, and never taken by a Part-1 codestream)
-      any_sig |= (rev ? __ballot(((nz >> K) & 1u) != 0u) != 0ull : true) ? 1u : 0u;
-      if (!rev) {
-        nz = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { mu[i] = (mu[i] >> K) ? 0u : mu[i]; nz |= mu[i]; }
-      }
-    }
-    if (rev) nz &= (1u << K) - 1u;                      // = the OR of the mu of the block's samples
-    if (step + 1 < nsteps) load_rows(qy + RPS, ntop, nbot); // request the next step's samples now
-    if (ABL & 16) { any_sig |= (uint32_t)(__ballot((mu[0] ^ mu[1] ^ mu[2] ^ mu[3] ^ mu[4] ^ mu[5] ^ mu[6] ^ mu[7]) == 0x12345u) != 0ull); continue; }
-    // A step without a significant sample, below a step without one: every quad has context 0 and rho 0, i.e. one
-    // MEL "0" event and nothing else (no VLC codeword, no U-VLC, no MagSgn bits).  The events are all alike, so only
-    // their number matters.  (Smooth content at moderate rates is mostly such steps in the top resolution's sub-bands.)
-    {
-      const bool step_sig = __ballot(nz != 0u) != 0ull;
-      const bool skip = !step_sig && !prev_sig;
-      prev_sig = step_sig;
-      if (skip) {
-        const uint32_t nq = (uint32_t)__popcll(__ballot(active)) + (uint32_t)__popcll(__ballot(has_q1 && active));
-        mel_zeros(nq);
-        last_S = 0;
-        continue;
-      }
-      any_sig |= step_sig ? 1u : 0u;
-    }
-    uint32_t e[8], sv[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint32_t m1 = mu[i] - 1u, w = m1 + mu[i];                         // 2 mu - 1 (all ones when mu = 0)
-      e[i] = (0u - (uint32_t)__builtin_clz(w)) & 31u;                         // 32 - clz(2 mu - 1), 0 for mu = 0 (w is never 0)
-      sv[i] = __builtin_amdgcn_alignbit(m1, sx[i], 31);                       // 2 (mu - 1) + sign (:601)
-    }
-    // exponents of a quad as four bytes; its significance pattern rho and, below, which samples reach the maximum
-    const uint32_t ep0 = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);
-    const uint32_t ep1 = e[4] | (e[5] << 8) | (e[6] << 16) | (e[7] << 24);
-    const uint32_t sf0 = nz_flags(ep0), sf1 = nz_flags(ep1);
-    const uint32_t rho0 = gather4(sf0), rho1 = gather4(sf1);
-    const uint32_t emax0 = max(max(e[0], e[1]), max(e[2], e[3])), emax1 = max(max(e[4], e[5]), max(e[6], e[7]));
-
-    // ---- what the quad row below needs from this one, worked out HERE and handed down as one word per lane: for each
-    // of its two quads the largest exponent among the four bottom-row samples above it (columns x-1 .. x+2: kappa) in
-    // bits 0..4 of a 16-bit half, and whether the two left / the two right ones of them hold a significant sample
-    // (context bits "nw | n" and "ne | nf") in bits 5 / 7 -- :802, :862, :878, :950-:991.
-    uint32_t S;
-    {
-      const uint32_t b0 = e[1], b1 = e[3], b2 = e[5], b3 = e[7];             // bottom-row exponents of columns 0..3
-      const uint32_t m12 = max(b1, b2);
-      const uint32_t own = max(b0, m12) | (max(m12, b3) << 16);              // columns 0..2 (quad 0 below) | columns 1..3 (quad 1)
-      const uint32_t X = b3 | (b0 << 16), Y = b0 | (b3 << 16);
-      const uint32_t nb = (left_of(X) & 0xFFFFu) | (right_of(X) & 0xFFFF0000u);   // left lane's column 3 | right lane's column 0
-      const uint32_t mx = pk_max(own, nb);
-      const uint32_t F = (pk_max(nb, Y) + 0x007F001Fu) & 0x00800020u;        // quad 0: bit 5 = nw | n; quad 1: bit 7 = ne | nf
-      const uint32_t f12 = ((m12 + 31u) & 32u) * 0x10004u;                   // columns 1, 2: quad 0's ne | nf (bit 7), quad 1's nw | n (bit 5)
-      S = mx | F | f12;
-    }
-    const uint32_t give = (uint32_t)lane >= 64u - PPR ? last_S : S;
-    const uint32_t above = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane - (int)PPR) & 63) << 2), (int)give);
-    last_S = S;                                          // (the first quad row of the block gets the zero last_S starts with)
-
-    // ---- per quad symbols ----
-    const uint32_t rho_left = left_of(rho1);            // rho of the quad to the left of quad 0
-    uint32_t uq[2], tup[2], Uq[2], chi[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const uint32_t rl = q == 0 ? rho_left : rho0, rho = q ? rho1 : rho0, emax = q ? emax1 : emax0, ep = q ? ep1 : ep0;
-      const uint32_t aq = q ? above >> 16 : above;
-      // context, kept as c << 5: rows below the first take nw / ne from above and "a quad to the left has a significant
-      // sample in its right column" (rho_left >= 4); the first row takes all three bits from the left quad (:731, :788)
-      uint32_t c5 = (aq & 0xA0u) | ((4u * rl + 48u) & 64u);
-      uint32_t tsel = 2048u;
-      if (step == 0) {
-        const bool fr = qy == 0;
-        c5 = fr ? ((rl >> 1) | (rl & 1u)) << 5 : c5;
-        tsel = fr ? 0u : 2048u;
-      }
-      // kappa = max(1, max exponent above - 1) for a quad with more than one significant sample, else 1 (:862, :950)
-      const uint32_t multi = 0u - ((0xFEE8u >> rho) & 1u);
-      const uint32_t me = aq & 31u;
-      const uint32_t kappa = 1u + ((me > 2u ? me - 2u : 0u) & multi);
-      const uint32_t U = max(emax, kappa), u = U - kappa;
-      const uint32_t xe = ep ^ (emax * 0x01010101u);
-      uint32_t eps = gather4((nz_flags(xe) ^ 0x80808080u));               // samples whose exponent is the quad's maximum
-      eps = u ? eps : 0u;
-      tup[q] = (&s_vlc[0][0])[tsel + (c5 << 3) + (rho << 4) + eps];
-      uq[q] = u; Uq[q] = U; chi[q] = c5;
-    }
-
-    // ---- VLC bits of the pair: cwd(q0) cwd(q1) then the interleaved U-VLC ----
-    uint32_t vb = 0, vl = 0;
-    bool ev2_valid = false; uint32_t ev2_bit = 0;
-    {
-      const uint32_t u0 = uq[0], u1 = has_q1 ? uq[1] : 0u;
-      vb = tup[0] >> 8; vl = (tup[0] >> 4) & 7u;
-      if (has_q1) { vb |= (tup[1] >> 8) << vl; vl += (tup[1] >> 4) & 7u; }
-      const bool first_row = qy == 0;
-      const bool both_big = first_row && u0 > 2 && u1 > 2;                                   // :766-772
-      const bool one_big = first_row && !both_big && u0 > 2 && u1 > 0;                       // :773-778
-      ev2_valid = first_row && u0 > 0 && u1 > 0; ev2_bit = min(u0, u1) > 2;                   // :763-764
-      const uint32_t w0 = s_uvlc[both_big ? u0 - 2u : u0];
-      uint32_t w1 = s_uvlc[both_big ? u1 - 2u : u1];
-      if (one_big) w1 = (u1 - 1u) | (1u << 8);          // u1 in {1,2} is a single bit, no suffix
-      vb |= (w0 & 0xFFu) << vl; vl += (w0 >> 8) & 0xFFu;                                     // prefix q0, prefix q1,
-      vb |= (w1 & 0xFFu) << vl; vl += (w1 >> 8) & 0xFFu;                                     // suffix q0, suffix q1 (:779-785, :985-988)
-      vb |= ((w0 >> 16) & 0xFFu) << vl; vl += w0 >> 24;
-      vb |= ((w1 >> 16) & 0xFFu) << vl; vl += w1 >> 24;
-      if (!active) { vb = 0; vl = 0; ev2_valid = false; }
-    }
-
-    // ---- MagSgn lengths: m_n = U - e_k bit for a significant sample, 0 otherwise (:667-674), four bytes per quad ----
-    uint32_t mp[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const uint32_t sf = q ? sf1 : sf0;
-      const uint32_t sig = (sf - (sf >> 7)) | sf;                             // 0xFF in the bytes of significant samples
-      const uint32_t ek = ((tup[q] & 15u) * 0x204081u) & 0x01010101u;         // the four e_k bits, one per byte
-      mp[q] = (Uq[q] * 0x01010101u - ek) & sig;
-    }
-    const uint32_t tot0 = __builtin_amdgcn_sad_u8(mp[0], 0u, 0u), tot = __builtin_amdgcn_sad_u8(mp[1], 0u, tot0);
-
-    // ---- stream positions of the lane's MagSgn and VLC bits: ONE wavefront prefix sum over both counts ----
-    const uint32_t incl = wave_incl_scan(tot | (vl << 16), lane);
-    const uint32_t sums = rdlane(incl, 63);
-    const uint32_t step_bits = sums & 0xFFFFu, step_vbits = sums >> 16;
-    // the pending bits of a buffer live at [base, base + pend); they only move to its front (and the buffer is
-    // cleared) when this step's bits would not fit behind them -- every third or fourth step on typical content
-    if (ms_base + ms_pend + step_bits + 64u > 32u * (uint32_t)PMS_WORDS) {
-      ms_pend = compact(L.ms, ms_base, ms_base + ms_pend, PMS_WORDS);
-      ms_base = 0;
-    }
-    if (v_base + v_pend + step_vbits + 64u > 32u * (uint32_t)PVLC_WORDS) {
-      v_pend = compact(L.vlc, v_base, v_base + v_pend, PVLC_WORDS);
-      v_base = 0;
-    }
-
-    // ---- MEL events of the step (quads with context 0, and in the first row the "both u > 0" event, :664, :763, :883):
-    // lane-major, within a lane quad 0, quad 1, then the u event (see the note at mel_at)
-    if (ABL & 8) { any_sig |= (uint32_t)(__ballot((vb ^ mp[0] ^ mp[1] ^ sv[0] ^ sv[7] ^ chi[1] ^ incl) == 0x12345u) != 0ull); continue; }
-    if (!(ABL & 1)) {
-      // the lane's events: bits 0..2 valid (quad 0, quad 1, u), bits 4..6 their values
-      const uint32_t fl = ((active && chi[0] == 0u) ? (rho0 != 0u ? 0x11u : 0x01u) : 0u) |
-                          ((active && has_q1 && chi[1] == 0u) ? (rho1 != 0u ? 0x22u : 0x02u) : 0u) |
-                          ((step == 0 && ev2_valid) ? (ev2_bit != 0u ? 0x44u : 0x04u) : 0u);
-      if (__ballot((fl & 7u) != 0u) != 0ull) {                                // (dense content: most steps have no quad with context 0)
-        // 64 consecutive events at a time, event e in lane e & 63: the first quad row of the block has three events per
-        // lane (its PPR lanes come first), every other row two
-        const uint32_t nwords = step == 0 ? 3u : 2u;
-        for (uint32_t wd = 0; wd < nwords; ++wd) {
-          const uint32_t e = 64u * wd + (uint32_t)lane;
-          uint32_t from, slot;
-          if (step == 0) {
-            const uint32_t e2 = e - 3u * PPR;
-            const bool fr = e < 3u * PPR;
-            from = fr ? e / 3u : PPR + (e2 >> 1);
-            slot = fr ? e - 3u * (e / 3u) : e2 & 1u;
-          } else { from = e >> 1; slot = e & 1u; }
-          const uint32_t g = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((from & 63u) << 2), (int)fl) >> slot;
-          const bool valid = from < 64u && (g & 1u) != 0u, one = valid && (g & 16u) != 0u;
-          const uint64_t Vw = __ballot(valid), Bw = __ballot(one);
-          if (Vw == 0ull) continue;
-          const uint32_t nvalid = (uint32_t)__popcll(Vw);
-          if (Bw == 0ull) { mel_c += nvalid; continue; }
-          // valid events in front of the lane's, in this word
-          const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(Vw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Vw, 0u));
-          uint32_t info = 0;                                                  // (k, c) at the lane's "1" event
-          {
-            uint64_t ones = Bw;
-            uint32_t consumed = 0;
-            while (ones) {
-              const uint32_t l = (uint32_t)__builtin_ctzll(ones);
-              asm("s_bitset0_b64 %0, %1" : "+s"(ones) : "s"(l));
-              const uint32_t bf = rdlane(before, (int)l);
-              mel_c += bf - consumed; consumed = bf + 1u;
-              info = (uint32_t)lane == l ? (mel_k | (mel_c << 4)) : info;     // (a v_writelane would need the lane number in M0: no shorter)
-              // :352-358: the coder steps down, its run starts anew -- k = max(K - 1, 0), c = P[k] (mel_at's pKm1: 0 for K = 0)
-              uint32_t K, pKm1;
-              if (mel_c >= 85u) mel_c -= (mel_c - 53u) & ~31u;                // (whole runs at k = 12 behind it: rare)
-              if (mel_c >= 53u) { K = 12u; pKm1 = 37u; }
-              else {
-                const uint64_t m = MEL_PM << (63u - mel_c);
-                K = (uint32_t)__popcll(m) - 1u;
-                const uint64_t m2 = m & ~(0x8000000000000000ull >> (uint32_t)__builtin_clzll(m));
-                pKm1 = m2 ? mel_c - (uint32_t)__builtin_clzll(m2) : 0u;
-              }
-              int km1 = (int)K - 1;
-              asm("s_max_i32 %0, %1, 0" : "=s"(km1) : "s"(km1) : "scc");      // (kept scalar: the compiler's saturating subtract is a vector instruction and a read-back)
-              mel_k = (uint32_t)km1; mel_c = pKm1;
-            }
-            mel_c += nvalid - consumed;
-          }
-          // the lanes' bits: '1' for every run completed since the last "1" event, then '0' and the open run's length in e bits
-          uint32_t code = 0, len = 0;
-          if (one) {
-            uint32_t K, run, nones, pKm1;
-            mel_at(info & 15u, info >> 4, K, run, nones, pKm1);
-            const uint32_t eb = mel_exp(K);
-            code = (((1u << nones) - 1u) << (eb + 1u)) | run;
-            len = nones + eb + 1u;
-          }
-          const uint32_t at_incl = wave_incl_scan(len, lane);
-          const uint32_t wbits = rdlane(at_incl, 63);
-          if (mel_bits + wbits > MEL_RAW_BITS) mel_err = 1;
-          else mel_or(code, len, mel_bits + at_incl - len);
-          mel_bits += wbits;
-        }
-        mel_zeros(0u);
-      }
-    }
-
-    // ---- MagSgn and VLC bits into the flat, un-stuffed bit buffers ----
-    if (ABL & 2) { any_sig |= (uint32_t)(__ballot((vb ^ mp[0] ^ mp[1] ^ sv[0] ^ sv[3] ^ sv[5] ^ sv[7] ^ incl) == 0x12345u) != 0ull); }
-    else {
-      const uint32_t at = ms_base + ms_pend + (incl & 0xFFFFu) - tot;
-      const bool wide_bits = __ballot(max(Uq[0], Uq[1]) > 16u) != 0ull;      // wave-uniform: some sample of the step has more than 16 bits
-      if (!wide_bits) {
-        // two samples make at most 32 bits: the lane's eight values leave as four words
-        uint32_t pr[4], ln[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const uint32_t m = mp[q];
-          const uint32_t m0 = m & 0xFFu, m2 = (m >> 16) & 0xFFu;
-          const uint32_t v0 = __builtin_amdgcn_ubfe(sv[4 * q + 0], 0u, m0), v1 = __builtin_amdgcn_ubfe(sv[4 * q + 1], 0u, (m >> 8) & 0xFFu);
-          const uint32_t v2 = __builtin_amdgcn_ubfe(sv[4 * q + 2], 0u, m2), v3 = __builtin_amdgcn_ubfe(sv[4 * q + 3], 0u, m >> 24);
-          pr[2 * q] = v0 | (v1 << m0); pr[2 * q + 1] = v2 | (v3 << m2);
-          ln[q] = (m + (m >> 8)) & 0xFFu;                                     // bits of the quad's first two samples
-        }
-        if (tot != 0u) {
-          or32(L.ms, at, pr[0]);
-          or32(L.ms, at + ln[0], pr[1]);
-          or32(L.ms, at + tot0, pr[2]);
-          or32(L.ms, at + tot0 + ln[1], pr[3]);
-        }
+  // The step loop, from the first request for sample rows to its end, ONCE PER KIND OF LOAD (1: 16-byte, 2: dwords; 0: both
+  // behind a select, ENC_ROWS_W4V 0), chosen once per block: two kinds of load that end in the same registers are merged by
+  // the compiler -- into selected dword loads, or into a wait right behind the loads.
+  auto code_steps = [&](auto kind_c) __attribute__((always_inline)) {
+    constexpr int KIND = decltype(kind_c)::value;
+    using Rows = RawRows<KIND>;
+    // Samples of one quad row of this lane's pair.  The loads are UNCONDITIONAL: rows and columns are clamped into the
+    // block, a lane / row / column that does not exist fetches something valid and is masked when the values are consumed,
+    // a step or two later.  (With a branch per case the two rows of the full-width case were separated by a wait for
+    // everything in flight -- the zero-initialisation of the registers the partial-width case loads into -- and the
+    // wavefront sat out a full memory latency in the middle of every step: SQ_WAIT_ANY 52 %.)
+    auto load_rows = [&](uint32_t qy, Rows& R) __attribute__((always_inline)) {
+      const uint32_t qyc = min(qy, QH - 1u);
+      const uint32_t y0 = 2u * qyc, y1 = min(y0 + 1u, H - 1u);
+      const uint32_t* r0 = src + (size_t)y0 * pitch;
+      const uint32_t* r1 = src + (size_t)y1 * pitch;
+      if (ABL & 32) { r0 = coef + (size_t)bi * 4096u + y0 * 64u; r1 = coef + (size_t)bi * 4096u + y1 * 64u; }   // timing experiment: block-contiguous samples
+      if constexpr (KIND == 1) {
+        const uint32_t xc = min(x0, W - 4u);
+        R.t = *reinterpret_cast<const U4V*>(r0 + xc);
+        R.b = *reinterpret_cast<const U4V*>(r1 + xc);
+      } else if (KIND == 0 && w4) {
+        const uint32_t xc = min(x0, W - 4u);
+        const U4 a = *reinterpret_cast<const U4*>(r0 + xc);
+        const U4 c = *reinterpret_cast<const U4*>(r1 + xc);
+        R.t[0] = a.x; R.t[1] = a.y; R.t[2] = a.z; R.t[3] = a.w;
+        R.b[0] = c.x; R.b[1] = c.y; R.b[2] = c.z; R.b[3] = c.w;
       } else {
-        uint32_t pos = at;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const uint32_t m = (mp[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-          or_bits(L.ms, pos, __builtin_amdgcn_ubfe(sv[i], 0u, m), m);
-          pos += m;
+        for (int k = 0; k < 4; ++k) { const uint32_t xk = min(x0 + (uint32_t)k, W - 1u); R.t[k] = r0[xk]; R.b[k] = r1[xk]; }
+      }
+    };
+    // Entry order: the requests for the rows of the first step (and of the second: set B) -- the block's first HBM accesses
+    // -- come first; the table copy, the LDS clears and the workgroup's barrier run while they are in flight.
+    Rows A;
+    [[maybe_unused]] Rows B;
+    load_rows(r, A);
+    if constexpr (ENC_ROWS_AHEAD == 2) load_rows(r + RPS, B);
+    prologue(true);
+
+    // ---- per-lane constants of the block ----
+    // The quantise transfer of a sample is ONE multiply (9/7) or ONE and (5/3) by a per-lane, per-column constant that is
+    // zero for the columns of this lane outside the block: what the clamped loads fetched there quantises to zero, so
+    // rho, exponents and MagSgn lengths of samples that do not exist come out as zero without a select per sample.
+    // 9/7: floor(|x| * (1/delta)) >> p == floor(|x| * ((1/delta) * 2^-p)) -- the scaling by a power of two is exact.
+    float colf[4]; uint32_t colm[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool in = pxok && x0 + (uint32_t)k < W;
+      colf[k] = in ? ldexpf(delta_inv, -(int)p) : 0.0f;
+      colm[k] = in ? (1u << (31u - p)) - 1u : 0u;                          // the magnitude bits the coder keeps: mu < 2^K_max
+    }
+    const bool ragged = (QH & (RPS - 1u)) != 0 || (H & 1u) != 0;           // the last step has quad rows / sample rows that do not exist
+
+    // One step: waits for the rows in R, codes them, and has requested the rows R holds next by then.  (`return` = on to
+    // the next step.)
+    auto one_step = [&](const uint32_t step, Rows& R) __attribute__((always_inline)) {
+      const uint32_t qy = RPS * step + r;
+      const bool active = pxok && qy < QH;
+      // ---- quantise transfer + the coder's view of a sample (ojph_codestream_gen.cpp:59-121, ojph_block_encoder.cpp:592-601):
+      // mu = the magnitude above bit-plane p (the reference's val = 2 mu), the exponent e = bit length of 2 mu - 1, and
+      // sv = 2 (mu - 1) + sign, what MagSgn takes its bits from.  The sign-magnitude word of the reference is never formed.
+      R.arrived();
+      uint32_t rt[4], rb[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { rt[k] = R.top(k); rb[k] = R.bot(k); }
+      if (ragged && step + 1 == nsteps) {                 // rows below the block: what was fetched for them counts as zero
+        const bool bot = active && 2u * qy + 1u < H;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { rt[k] = active ? rt[k] : 0u; rb[k] = bot ? rb[k] : 0u; }
+      }
+      uint32_t mu[8], sx[8];                              // sx: a word whose bit 31 is the sample's sign
+      uint32_t nz = 0;                                    // OR of the step's magnitudes (rev: before the mask, bit K_max included)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {                       // quad order: n = 0:(x,y) 1:(x,y+1) 2:(x+1,y) 3:(x+1,y+1)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const uint32_t raw = j ? rb[k] : rt[k];
+          if (rev) {
+            const int v = (int)raw;
+            const uint32_t a = (uint32_t)(v >= 0 ? v : -v);
+            mu[2 * k + j] = a & colm[k];                                        // :70-76, with the same wrap-around when |v| >= 2^K_max:
+            sx[2 * k + j] = raw | (a << p);                                     // its top bit lands on the sign
+            nz |= a;                                                            // (clamped loads: every lane holds samples of the block's own rows)
+          } else {
+            mu[2 * k + j] = (uint32_t)__fmul_rn(fabsf(__uint_as_float(raw)), colf[k]);   // :113-118, C truncation
+            sx[2 * k + j] = raw;
+            nz |= mu[2 * k + j];
+          }
         }
       }
-      if (vl != 0u) or32(L.vlc, v_base + v_pend + (incl >> 16) - vl, vb);
+      // A magnitude of more than K_max bits (Part-2 kernels whose gain outruns the guard bits; see to_sign_mag): reversible,
+      // the bits above K_max are dropped and bit K_max has landed on the sign; irreversible, the reference's conversion of a
+      // product beyond 2^31 returns INT_MIN -- the sample codes as a zero.  Both leave a bit in the reference's max_val,
+      // and a block with a non-zero max_val is coded even if none of its samples is significant (ojph_codeblock.cpp:142-175).
+      if (__ballot((nz >> K) != 0u) != 0ull) {            // (wave-uniform, and never taken by a Part-1 codestream)
+        any_sig |= (rev ? __ballot(((nz >> K) & 1u) != 0u) != 0ull : true) ? 1u : 0u;
+        if (!rev) {
+          nz = 0;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) { mu[i] = (mu[i] >> K) ? 0u : mu[i]; nz |= mu[i]; }
+        }
+      }
+      if (rev) nz &= (1u << K) - 1u;                      // = the OR of the mu of the block's samples
+      // request the rows of the step that takes this set next.  One set: not behind the last step.  Two sets: unconditional,
+      // rows past the block's last clamped into it like every other row (a request skipped at the block's end would be a
+      // branch that joins "set requested" with "set not requested", and the wait of the NEXT step could no longer leave
+      // this request outstanding)
+      if (ENC_ROWS_AHEAD == 2 || step + 1 < nsteps) load_rows(qy + ENC_ROWS_AHEAD * RPS, R);
+      if (ENC_ROWS_AHEAD == 2 && err) return;           // (the second step of a pair whose first one failed)
+      if (ABL & 16) { any_sig |= (uint32_t)(__ballot((mu[0] ^ mu[1] ^ mu[2] ^ mu[3] ^ mu[4] ^ mu[5] ^ mu[6] ^ mu[7]) == 0x12345u) != 0ull); return; }
+      // A step without a significant sample, below a step without one: every quad has context 0 and rho 0, i.e. one
+      // MEL "0" event and nothing else (no VLC codeword, no U-VLC, no MagSgn bits).  The events are all alike, so only
+      // their number matters.  (Smooth content at moderate rates is mostly such steps in the top resolution's sub-bands.)
+      {
+        const bool step_sig = __ballot(nz != 0u) != 0ull;
+        const bool skip = !step_sig && !prev_sig;
+        prev_sig = step_sig;
+        if (skip) {
+          const uint32_t nq = (uint32_t)__popcll(__ballot(active)) + (uint32_t)__popcll(__ballot(has_q1 && active));
+          mel_zeros(nq);
+          last_S = 0;
+          return;
+        }
+        any_sig |= step_sig ? 1u : 0u;
+      }
+      uint32_t e[8], sv[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const uint32_t m1 = mu[i] - 1u, w = m1 + mu[i];                         // 2 mu - 1 (all ones when mu = 0)
+        e[i] = (0u - (uint32_t)__builtin_clz(w)) & 31u;                         // 32 - clz(2 mu - 1), 0 for mu = 0 (w is never 0)
+        sv[i] = __builtin_amdgcn_alignbit(m1, sx[i], 31);                       // 2 (mu - 1) + sign (:601)
+      }
+      // exponents of a quad as four bytes; its significance pattern rho and, below, which samples reach the maximum
+      const uint32_t ep0 = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);
+      const uint32_t ep1 = e[4] | (e[5] << 8) | (e[6] << 16) | (e[7] << 24);
+      const uint32_t sf0 = nz_flags(ep0), sf1 = nz_flags(ep1);
+      const uint32_t rho0 = gather4(sf0), rho1 = gather4(sf1);
+      const uint32_t emax0 = max(max(e[0], e[1]), max(e[2], e[3])), emax1 = max(max(e[4], e[5]), max(e[6], e[7]));
+
+      // ---- what the quad row below needs from this one, worked out HERE and handed down as one word per lane: for each
+      // of its two quads the largest exponent among the four bottom-row samples above it (columns x-1 .. x+2: kappa) in
+      // bits 0..4 of a 16-bit half, and whether the two left / the two right ones of them hold a significant sample
+      // (context bits "nw | n" and "ne | nf") in bits 5 / 7 -- :802, :862, :878, :950-:991.
+      uint32_t S;
+      {
+        const uint32_t b0 = e[1], b1 = e[3], b2 = e[5], b3 = e[7];             // bottom-row exponents of columns 0..3
+        const uint32_t m12 = max(b1, b2);
+        const uint32_t own = max(b0, m12) | (max(m12, b3) << 16);              // columns 0..2 (quad 0 below) | columns 1..3 (quad 1)
+        const uint32_t X = b3 | (b0 << 16), Y = b0 | (b3 << 16);
+        const uint32_t nb = (left_of(X) & 0xFFFFu) | (right_of(X) & 0xFFFF0000u);   // left lane's column 3 | right lane's column 0
+        const uint32_t mx = pk_max(own, nb);
+        const uint32_t F = (pk_max(nb, Y) + 0x007F001Fu) & 0x00800020u;        // quad 0: bit 5 = nw | n; quad 1: bit 7 = ne | nf
+        const uint32_t f12 = ((m12 + 31u) & 32u) * 0x10004u;                   // columns 1, 2: quad 0's ne | nf (bit 7), quad 1's nw | n (bit 5)
+        S = mx | F | f12;
+      }
+      const uint32_t give = (uint32_t)lane >= 64u - PPR ? last_S : S;
+      const uint32_t above = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane - (int)PPR) & 63) << 2), (int)give);
+      last_S = S;                                          // (the first quad row of the block gets the zero last_S starts with)
+
+      // ---- per quad symbols ----
+      const uint32_t rho_left = left_of(rho1);            // rho of the quad to the left of quad 0
+      uint32_t uq[2], tup[2], Uq[2], chi[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const uint32_t rl = q == 0 ? rho_left : rho0, rho = q ? rho1 : rho0, emax = q ? emax1 : emax0, ep = q ? ep1 : ep0;
+        const uint32_t aq = q ? above >> 16 : above;
+        // context, kept as c << 5: rows below the first take nw / ne from above and "a quad to the left has a significant
+        // sample in its right column" (rho_left >= 4); the first row takes all three bits from the left quad (:731, :788)
+        uint32_t c5 = (aq & 0xA0u) | ((4u * rl + 48u) & 64u);
+        uint32_t tsel = 2048u;
+        if (step == 0) {
+          const bool fr = qy == 0;
+          c5 = fr ? ((rl >> 1) | (rl & 1u)) << 5 : c5;
+          tsel = fr ? 0u : 2048u;
+        }
+        // kappa = max(1, max exponent above - 1) for a quad with more than one significant sample, else 1 (:862, :950)
+        const uint32_t multi = 0u - ((0xFEE8u >> rho) & 1u);
+        const uint32_t me = aq & 31u;
+        const uint32_t kappa = 1u + ((me > 2u ? me - 2u : 0u) & multi);
+        const uint32_t U = max(emax, kappa), u = U - kappa;
+        const uint32_t xe = ep ^ (emax * 0x01010101u);
+        uint32_t eps = gather4((nz_flags(xe) ^ 0x80808080u));               // samples whose exponent is the quad's maximum
+        eps = u ? eps : 0u;
+        tup[q] = (&s_vlc[0][0])[tsel + (c5 << 3) + (rho << 4) + eps];
+        uq[q] = u; Uq[q] = U; chi[q] = c5;
+      }
+
+      // ---- VLC bits of the pair: cwd(q0) cwd(q1) then the interleaved U-VLC ----
+      uint32_t vb = 0, vl = 0;
+      bool ev2_valid = false; uint32_t ev2_bit = 0;
+      {
+        const uint32_t u0 = uq[0], u1 = has_q1 ? uq[1] : 0u;
+        vb = tup[0] >> 8; vl = (tup[0] >> 4) & 7u;
+        if (has_q1) { vb |= (tup[1] >> 8) << vl; vl += (tup[1] >> 4) & 7u; }
+        const bool first_row = qy == 0;
+        const bool both_big = first_row && u0 > 2 && u1 > 2;                                   // :766-772
+        const bool one_big = first_row && !both_big && u0 > 2 && u1 > 0;                       // :773-778
+        ev2_valid = first_row && u0 > 0 && u1 > 0; ev2_bit = min(u0, u1) > 2;                   // :763-764
+        const uint32_t w0 = s_uvlc[both_big ? u0 - 2u : u0];
+        uint32_t w1 = s_uvlc[both_big ? u1 - 2u : u1];
+        if (one_big) w1 = (u1 - 1u) | (1u << 8);          // u1 in {1,2} is a single bit, no suffix
+        vb |= (w0 & 0xFFu) << vl; vl += (w0 >> 8) & 0xFFu;                                     // prefix q0, prefix q1,
+        vb |= (w1 & 0xFFu) << vl; vl += (w1 >> 8) & 0xFFu;                                     // suffix q0, suffix q1 (:779-785, :985-988)
+        vb |= ((w0 >> 16) & 0xFFu) << vl; vl += w0 >> 24;
+        vb |= ((w1 >> 16) & 0xFFu) << vl; vl += w1 >> 24;
+        if (!active) { vb = 0; vl = 0; ev2_valid = false; }
+      }
+
+      // ---- MagSgn lengths: m_n = U - e_k bit for a significant sample, 0 otherwise (:667-674), four bytes per quad ----
+      uint32_t mp[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const uint32_t sf = q ? sf1 : sf0;
+        const uint32_t sig = (sf - (sf >> 7)) | sf;                             // 0xFF in the bytes of significant samples
+        const uint32_t ek = ((tup[q] & 15u) * 0x204081u) & 0x01010101u;         // the four e_k bits, one per byte
+        mp[q] = (Uq[q] * 0x01010101u - ek) & sig;
+      }
+      const uint32_t tot0 = __builtin_amdgcn_sad_u8(mp[0], 0u, 0u), tot = __builtin_amdgcn_sad_u8(mp[1], 0u, tot0);
+
+      // ---- stream positions of the lane's MagSgn and VLC bits: ONE wavefront prefix sum over both counts ----
+      const uint32_t incl = wave_incl_scan(tot | (vl << 16), lane);
+      const uint32_t sums = rdlane(incl, 63);
+      const uint32_t step_bits = sums & 0xFFFFu, step_vbits = sums >> 16;
+      // the pending bits of a buffer live at [base, base + pend); they only move to its front (and the buffer is
+      // cleared) when this step's bits would not fit behind them -- every third or fourth step on typical content
+      if (ms_base + ms_pend + step_bits + 64u > 32u * (uint32_t)PMS_WORDS) {
+        ms_pend = compact(L.ms, ms_base, ms_base + ms_pend, PMS_WORDS);
+        ms_base = 0;
+      }
+      if (v_base + v_pend + step_vbits + 64u > 32u * (uint32_t)PVLC_WORDS) {
+        v_pend = compact(L.vlc, v_base, v_base + v_pend, PVLC_WORDS);
+        v_base = 0;
+      }
+
+      // ---- MEL events of the step (quads with context 0, and in the first row the "both u > 0" event, :664, :763, :883):
+      // lane-major, within a lane quad 0, quad 1, then the u event (see the note at mel_at)
+      if (ABL & 8) { any_sig |= (uint32_t)(__ballot((vb ^ mp[0] ^ mp[1] ^ sv[0] ^ sv[7] ^ chi[1] ^ incl) == 0x12345u) != 0ull); return; }
+      if (!(ABL & 1)) {
+        // the lane's events: bits 0..2 valid (quad 0, quad 1, u), bits 4..6 their values
+        const uint32_t fl = ((active && chi[0] == 0u) ? (rho0 != 0u ? 0x11u : 0x01u) : 0u) |
+                            ((active && has_q1 && chi[1] == 0u) ? (rho1 != 0u ? 0x22u : 0x02u) : 0u) |
+                            ((step == 0 && ev2_valid) ? (ev2_bit != 0u ? 0x44u : 0x04u) : 0u);
+        if (__ballot((fl & 7u) != 0u) != 0ull) {                                // (dense content: most steps have no quad with context 0)
+          // 64 consecutive events at a time, event e in lane e & 63: the first quad row of the block has three events per
+          // lane (its PPR lanes come first), every other row two
+          const uint32_t nwords = step == 0 ? 3u : 2u;
+          for (uint32_t wd = 0; wd < nwords; ++wd) {
+            const uint32_t e = 64u * wd + (uint32_t)lane;
+            uint32_t from, slot;
+            if (step == 0) {
+              const uint32_t e2 = e - 3u * PPR;
+              const bool fr = e < 3u * PPR;
+              from = fr ? e / 3u : PPR + (e2 >> 1);
+              slot = fr ? e - 3u * (e / 3u) : e2 & 1u;
+            } else { from = e >> 1; slot = e & 1u; }
+            const uint32_t g = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((from & 63u) << 2), (int)fl) >> slot;
+            const bool valid = from < 64u && (g & 1u) != 0u, one = valid && (g & 16u) != 0u;
+            const uint64_t Vw = __ballot(valid), Bw = __ballot(one);
+            if (Vw == 0ull) continue;
+            const uint32_t nvalid = (uint32_t)__popcll(Vw);
+            if (Bw == 0ull) { mel_c += nvalid; continue; }
+            // valid events in front of the lane's, in this word
+            const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(Vw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Vw, 0u));
+            uint32_t info = 0;                                                  // (k, c) at the lane's "1" event
+            uint32_t consumed = 0;
+            {
+              uint64_t ones = Bw;
+              while (ones) {
+                const uint32_t l = (uint32_t)__builtin_ctzll(ones);
+                asm("s_bitset0_b64 %0, %1" : "+s"(ones) : "s"(l));
+                const uint32_t bf = rdlane(before, (int)l);
+                mel_c += bf - consumed; consumed = bf + 1u;
+                info = (uint32_t)lane == l ? (mel_k | (mel_c << 4)) : info;     // (a v_writelane would need the lane number in M0: no shorter)
+                // :352-358: the coder steps down, its run starts anew -- k = max(K - 1, 0), c = P[k] (mel_at's pKm1: 0 for K = 0)
+                uint32_t K, pKm1;
+                if (mel_c >= 85u) mel_c -= (mel_c - 53u) & ~31u;                // (whole runs at k = 12 behind it: rare)
+                if (mel_c >= 53u) { K = 12u; pKm1 = 37u; }
+                else {
+                  const uint64_t m = MEL_PM << (63u - mel_c);
+                  K = (uint32_t)__popcll(m) - 1u;
+                  const uint64_t m2 = m & ~(0x8000000000000000ull >> (uint32_t)__builtin_clzll(m));
+                  pKm1 = m2 ? mel_c - (uint32_t)__builtin_clzll(m2) : 0u;
+                }
+                int km1 = (int)K - 1;
+                asm("s_max_i32 %0, %1, 0" : "=s"(km1) : "s"(km1) : "scc");      // (kept scalar: the compiler's saturating subtract is a vector instruction and a read-back)
+                mel_k = (uint32_t)km1; mel_c = pKm1;
+              }
+            }
+            // the lanes' bits: '1' for every run completed since the last "1" event, then '0' and the open run's length in e bits
+            uint32_t code = 0, len = 0;
+            if (one) {
+              uint32_t K, run, nones, pKm1;
+              mel_at(info & 15u, info >> 4, K, run, nones, pKm1);
+              const uint32_t eb = mel_exp(K);
+              code = (((1u << nones) - 1u) << (eb + 1u)) | run;
+              len = nones + eb + 1u;
+            }
+            const uint32_t at_incl = wave_incl_scan(len, lane);
+            const uint32_t wbits = rdlane(at_incl, 63);
+            if (mel_bits + wbits > MEL_RAW_BITS) mel_err = 1;
+            else mel_or(code, len, mel_bits + at_incl - len);
+            mel_bits += wbits;
+            mel_c += nvalid - consumed;                                         // the zeros behind the word's last "1" event
+          }
+          mel_zeros(0u);
+        }
+      }
+
+      // ---- MagSgn and VLC bits into the flat, un-stuffed bit buffers ----
+      if (ABL & 2) { any_sig |= (uint32_t)(__ballot((vb ^ mp[0] ^ mp[1] ^ sv[0] ^ sv[3] ^ sv[5] ^ sv[7] ^ incl) == 0x12345u) != 0ull); }
+      else {
+        const uint32_t at = ms_base + ms_pend + (incl & 0xFFFFu) - tot;
+        const bool wide_bits = __ballot(max(Uq[0], Uq[1]) > 16u) != 0ull;      // wave-uniform: some sample of the step has more than 16 bits
+        if (!wide_bits) {
+          // two samples make at most 32 bits: the lane's eight values leave as four words
+          uint32_t pr[4], ln[2];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const uint32_t m = mp[q];
+            const uint32_t m0 = m & 0xFFu, m2 = (m >> 16) & 0xFFu;
+            const uint32_t v0 = __builtin_amdgcn_ubfe(sv[4 * q + 0], 0u, m0), v1 = __builtin_amdgcn_ubfe(sv[4 * q + 1], 0u, (m >> 8) & 0xFFu);
+            const uint32_t v2 = __builtin_amdgcn_ubfe(sv[4 * q + 2], 0u, m2), v3 = __builtin_amdgcn_ubfe(sv[4 * q + 3], 0u, m >> 24);
+            pr[2 * q] = v0 | (v1 << m0); pr[2 * q + 1] = v2 | (v3 << m2);
+            ln[q] = (m + (m >> 8)) & 0xFFu;                                     // bits of the quad's first two samples
+          }
+          if (tot != 0u) {
+            or32(L.ms, at, pr[0]);
+            or32(L.ms, at + ln[0], pr[1]);
+            or32(L.ms, at + tot0, pr[2]);
+            or32(L.ms, at + tot0 + ln[1], pr[3]);
+          }
+        } else {
+          uint32_t pos = at;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const uint32_t m = (mp[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+            or_bits(L.ms, pos, __builtin_amdgcn_ubfe(sv[i], 0u, m), m);
+            pos += m;
+          }
+        }
+        if (vl != 0u) or32(L.vlc, v_base + v_pend + (incl >> 16) - vl, vb);
+      }
+      wave_sync();
+      // ---- byte stuffing of the windows that are complete ----
+      if (ABL & 4) { ms_base = 0; ms_pend = step_bits & 7u; v_base = 0; v_pend = step_vbits & 7u; return; }
+      {
+        const uint32_t T = ms_base + ms_pend + step_bits;
+        const uint32_t pos = ms_windows_full(ms_base, T);
+        ms_base = pos; ms_pend = T - pos;
+      }
+      {
+        const uint32_t T = v_base + v_pend + step_vbits;
+        const uint32_t pos = vlc_windows_full(v_base, T);
+        v_base = pos; v_pend = T - pos;
+      }
+    };
+    // two sets: the loop is unrolled by two, so that each set is a set of registers (no index, no moves between sets).
+    // The pair loop has ONE exit, behind the step of B, and a block's odd last step is a copy of the step behind the loop:
+    // with a second way out between the two steps the compiled loop keeps an edge from there to its head, on which A's
+    // request is the youngest load -- and the wait in front of A's quantise becomes vmcnt(0).  (A step that finds `err` set
+    // returns right behind its request, for the same reason.)
+    if constexpr (ENC_ROWS_AHEAD == 2) {
+      uint32_t step = 0;
+      for (; step + 1u < nsteps && !err; step += 2) {
+        one_step(step, A);
+        one_step(step + 1u, B);
+      }
+      if (step < nsteps && !err) one_step(step, A);
+    } else {
+      for (uint32_t step = 0; step < nsteps && !err; ++step) one_step(step, A);
     }
-    wave_sync();
-    // ---- byte stuffing of the windows that are complete ----
-    if (ABL & 4) { ms_base = 0; ms_pend = step_bits & 7u; v_base = 0; v_pend = step_vbits & 7u; continue; }
-    {
-      const uint32_t T = ms_base + ms_pend + step_bits;
-      const uint32_t pos = ms_windows_full(ms_base, T);
-      ms_base = pos; ms_pend = T - pos;
-    }
-    {
-      const uint32_t T = v_base + v_pend + step_vbits;
-      const uint32_t pos = vlc_windows_full(v_base, T);
-      v_base = pos; v_pend = T - pos;
-    }
-  }
+  };
+  if (!ENC_ROWS_W4V) code_steps(std::integral_constant<int, 0>());
+  else if (w4) code_steps(std::integral_constant<int, 1>());
+  else code_steps(std::integral_constant<int, 2>());
 
   // ---- final flush of both bit buffers: what remains is < 8 bits each ----
   uint32_t ms_carry = 0, v_carry = 0;
