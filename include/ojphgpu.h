@@ -858,7 +858,12 @@ int  ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* pipe, int bits);
  * (ojphgpu_unpack_video).  Call before the first _acquire -- until then the call may be repeated with a different format --
  * not together with _set_pixels / _set_packed.
  * OJPHGPU_E_INVALID unless the pipe's plan has exactly three unsigned components of one bit depth that fits the format and
- * the container, of sizes (w, h), (ceil(w / 2), h), (ceil(w / 2), h); a refusal leaves the pipe as it was. */
+ * the container, of sizes (w, h), (ceil(w / 2), h), (ceil(w / 2), h); a refusal leaves the pipe as it was.
+ * Or as one 4:2:0 video buffer (section 7c: OJPHGPU_VIDEO_NV12 / _NV21 / _P0XX): the same rules, the chroma planes
+ * (ceil(w / 2), ceil(h / 2)) each; _acquire hands out frame_bytes of the TIGHT layout of ojphgpu_video420_layout -- the luma
+ * plane, then the chroma plane, both at row_bytes -- and the launch is ojphgpu_unpack_video420.  A 4:2:2 format on a 4:2:0
+ * plan is refused, and a 4:2:0 format on a 4:2:2 plan.  The bytes on the link are those of planes in the matching
+ * containers; what is saved is the host's de-interleaving pass. */
 int  ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* pipe, int format);
 
 /* Every frame of this pipe is coded to a byte budget (section 5b): each collected codestream is, byte for byte, the plain
@@ -949,7 +954,9 @@ int  ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* pipe, int bits);     /* decod
 /* decoded frames come back as one 4:2:2 video buffer (section 7b), clamped to [0, 2^depth - 1]: _collect hands back the
  * format's frame_bytes.  The conditions of ojphgpu_enc_pipe_set_video, judged on the view's plan when the pipe decodes a
  * view: a reduced resolution always passes, a region when its planes have those sizes (an even x0 guarantees it).  Call
- * before the first _submit, not together with _set_pixels / _set_packed; 0 switches back to planes. */
+ * before the first _submit, not together with _set_pixels / _set_packed; 0 switches back to planes.  The 4:2:0 formats
+ * of section 7c come back in the tight layout (ojphgpu_pack_video420); a window passes when its x0 AND y0 are even, and one
+ * with an odd y0 is refused whatever its height, as one with an odd x0 is. */
 int  ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* pipe, int format);
 
 /* ---------------------------------------------------------------------------------------------
@@ -999,6 +1006,40 @@ int  ojphgpu_unpack_video(void* stream, int format, const void* d_video, void* d
                           uint32_t bit_depth, int container_bits);
 int  ojphgpu_pack_video(void* stream, int format, const void* d_planes, void* d_video, uint32_t width, uint32_t height,
                         int container_bits, uint32_t bit_depth);
+/* ---- 7c. 4:2:0 video buffers (kernels_video420.hip): the frame as hardware video decoders and encoders, ffmpeg's hardware
+ * frames and most 8-bit and HDR delivery paths hold it, TWO planes.  The frame is width x height luma samples; with cw =
+ * ceil(width / 2) and ch = ceil(height / 2), Cb and Cr are cw x ch each.  The luma plane has `height` rows; the chroma plane
+ * has ch rows, element k of a row being the pair (Cb[k], Cr[k]).
+ *   OJPHGPU_VIDEO_NV12  bytes; chroma Cb Cr                                        row_bytes 2 * cw     depth <= 8
+ *   OJPHGPU_VIDEO_NV21  bytes; chroma Cr Cb                                        row_bytes 2 * cw     depth <= 8
+ *   OJPHGPU_VIDEO_P0XX  little-endian 16-bit words, the sample in the high `depth` bits (P010, P012, P016); chroma Cb Cr
+ *                                                                                  row_bytes 4 * cw     9 <= depth <= 16
+ * row_bytes is that of both planes: for odd width a luma row ends in one padding sample.  The TIGHT layout, which the pipes
+ * hand out (ojphgpu_video420_layout): luma rows at row_bytes, the chroma plane at chroma_offset = row_bytes * height,
+ * frame_bytes = row_bytes * (height + ch).  The two stages take the planes as two pointers, each with its own pitch in bytes
+ * (>= row_bytes), so that a decoder's surface, whose pitch and chroma offset are its own, is read or written in place.
+ * Unpacking: a sample is its element (P0XX: word >> (16 - depth)); the padding luma sample, the low bits of a P0XX word and
+ * everything between row_bytes and the pitch are not looked at, no value is range-checked.  Packing: every sample is clamped
+ * to [0, 2^depth - 1] as ojphgpu_pack_video does, a P0XX sample is shifted up with zero low bits, every byte of [0,
+ * row_bytes) of every row of both planes is written -- padding as zero -- and NOTHING else: the bytes between row_bytes and
+ * the pitch and everything outside the two planes keep their contents.
+ * d_planes: the frame layout of ojphgpu_plan_comp_info for such a frame -- Y width x height, then Cb, then Cr cw x ch, tightly
+ * packed -- in container_bits-bit elements (8: NV12 and NV21 only; 16; 32).  OJPHGPU_E_INVALID: an unknown format (the codes
+ * of section 7b included), a null pointer, a zero size, a bit_depth outside the format's column, a container narrower than
+ * bit_depth or 8 with P0XX, a pitch below row_bytes, a d_luma, d_chroma or pitch that is not a multiple of the chroma element
+ * (2 bytes for NV12 / NV21, 4 for P0XX), row_bytes or height + ch beyond 32 bits.  No further alignment is required: in the
+ * tight layout of an odd-sized frame the chroma plane starts 2 bytes off a dword, and a pitch may change the alignment row
+ * by row; the kernels take, per row, the widest piece its address allows. */
+#define OJPHGPU_VIDEO_NV12 0x11
+#define OJPHGPU_VIDEO_NV21 0x12
+#define OJPHGPU_VIDEO_P0XX 0x13
+int  ojphgpu_video420_layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* chroma_offset,
+                             uint64_t* frame_bytes);   /* host only */
+int  ojphgpu_unpack_video420(void* stream, int format, const void* d_luma, uint32_t luma_pitch, const void* d_chroma,
+                             uint32_t chroma_pitch, void* d_planes, uint32_t width, uint32_t height, uint32_t bit_depth,
+                             int container_bits);
+int  ojphgpu_pack_video420(void* stream, int format, const void* d_planes, void* d_luma, uint32_t luma_pitch, void* d_chroma,
+                           uint32_t chroma_pitch, uint32_t width, uint32_t height, int container_bits, uint32_t bit_depth);
 /* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
  * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
  * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a

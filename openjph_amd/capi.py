@@ -369,6 +369,11 @@ SIGNATURES = {
     "ojphgpu_video_layout": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "ojphgpu_unpack_video": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
     "ojphgpu_pack_video": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]),
+    "ojphgpu_video420_layout": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ojphgpu_unpack_video420": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, C.c_int]),
+    "ojphgpu_pack_video420": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_int, C.c_uint32]),
     "ojphgpu_enc_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_dec_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_version": (C.c_char_p, []),

@@ -808,6 +808,68 @@ def pack_video(d_planes, fmt, width, height, bit_depth=None, out=None):
     return out.reshape(-1)[:total].reshape(h, row)
 
 
+def _video420_args(torch, what, buf, fmt, width, height, bit_depth, luma_pitch, chroma, chroma_pitch):
+    """the surface of the two 4:2:0 stages -> (code, depth, w, h, row_bytes, luma pointer, luma pitch, chroma pointer, chroma
+    pitch).  The defaults are the tight layout inside `buf`; chroma=: a second tensor that holds the chroma plane"""
+    from .pipeline import video420_format, video420_layout
+    code, b = video420_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    row, off, total = video420_layout(fmt, w, h)
+    ch = (h + 1) // 2
+    lp = row if luma_pitch is None else int(luma_pitch)
+    cp = (lp if chroma is None else row) if chroma_pitch is None else int(chroma_pitch)
+    assert buf.is_cuda and buf.is_contiguous(), what
+    if lp >= row and cp >= row:                           # (a pitch below row_bytes: the library refuses it)
+        nbytes = lambda t: t.numel() * t.element_size()
+        if chroma is None:
+            assert nbytes(buf) >= lp * h + cp * (ch - 1) + row, what
+        else:
+            assert chroma.is_cuda and chroma.is_contiguous() and chroma.device == buf.device, what
+            assert nbytes(buf) >= lp * (h - 1) + row and nbytes(chroma) >= cp * (ch - 1) + row, what
+    cptr = buf.data_ptr() + lp * h if chroma is None else chroma.data_ptr()
+    return code, b, w, h, row, buf.data_ptr(), lp, cptr, cp
+
+
+def unpack_video420(d_buf, fmt, width, height, bit_depth=None, dtype=None, out=None, luma_pitch=None, chroma=None, chroma_pitch=None):
+    """a 4:2:0 video buffer on the device (fmt = "nv12" | "nv21" | "p0xx" | "p010" | "p012" | "p016"; uint8 tensor) -> the
+    frame's planes as ONE flat tensor, Y [H,W] then Cb and Cr [ceil(H/2),ceil(W/2)], in `dtype` (uint8 -- nv12 / nv21 only -- /
+    int16 / uint16 / int32; default: uint8 for nv12 / nv21, else int16), or in `out` (contiguous, at least that many elements;
+    its dtype is the container).  The defaults are pipeline.pack_video420's tight layout inside d_buf; luma_pitch: the bytes
+    from one luma row to the next, the chroma plane then following the last luma row at luma_pitch * H; chroma=: a second
+    tensor that holds the chroma plane (a surface whose planes are separate), chroma_pitch: its rows' distance.  Pointers and
+    pitches are multiples of 2 (p0xx: 4) bytes and need no other alignment.  ojphgpu_unpack_video420."""
+    torch = _torch()
+    code, b, w, h, row, lptr, lp, cptr, cp = _video420_args(torch, "unpack_video420", d_buf, fmt, width, height, bit_depth, luma_pitch, chroma, chroma_pitch)
+    n = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+    if out is None:
+        out = torch.empty(n, dtype=dtype if dtype is not None else (torch.uint8 if code != 0x13 else torch.int16), device=d_buf.device)
+    assert out.is_cuda and out.is_contiguous() and out.numel() >= n
+    check(capi.lib().ojphgpu_unpack_video420(_stream_ptr(torch, d_buf.device.index or 0), code, C.c_void_p(lptr), lp, C.c_void_p(cptr), cp,
+                                             C.c_void_p(out.data_ptr()), w, h, b, out.element_size() * 8), "unpack_video420")
+    return out.reshape(-1)[:n]
+
+
+def pack_video420(d_planes, fmt, width, height, bit_depth=None, out=None, luma_pitch=None, chroma=None, chroma_pitch=None):
+    """the way back: the planes as one flat tensor (the frame layout above; uint8 / int16 / uint16 / int32) -> the video buffer,
+    clamped to [0, 2^bit_depth - 1], every padding position zero.  Without `out`: a new uint8 [H + ch, row_bytes] in the tight
+    layout.  `out` (uint8, contiguous), luma_pitch, chroma= and chroma_pitch describe the surface as for unpack_video420; only
+    [0, row_bytes) of every row of the two planes is written.  Returns out (the tight layout: reshaped to [H + ch, row_bytes]).
+    ojphgpu_pack_video420."""
+    torch = _torch()
+    from .pipeline import video420_layout
+    w, h = int(width), int(height)
+    assert d_planes.is_cuda and d_planes.is_contiguous() and d_planes.numel() >= w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+    tight = luma_pitch is None and chroma is None and chroma_pitch is None
+    if out is None:
+        assert tight, "pack_video420: a pitched surface is the caller's (out=)"
+        out = torch.empty(video420_layout(fmt, w, h)[2], dtype=torch.uint8, device=d_planes.device)
+    code, b, w, h, row, lptr, lp, cptr, cp = _video420_args(torch, "pack_video420", out, fmt, w, h, bit_depth, luma_pitch, chroma, chroma_pitch)
+    check(capi.lib().ojphgpu_pack_video420(_stream_ptr(torch, d_planes.device.index or 0), code, C.c_void_p(d_planes.data_ptr()), C.c_void_p(lptr), lp,
+                                           C.c_void_p(cptr), cp, w, h, d_planes.element_size() * 8, b), "pack_video420")
+    rows = h + (h + 1) // 2
+    return out.reshape(-1)[:row * rows].reshape(rows, row) if tight else out
+
+
 def pack_pixels(planes, bit_depth, pixel_bits=None, big_endian=False):
     """planes [C,H,W] on the device -> pixel-interleaved [H,W,C] (uint8 for pixel_bits 8, else int16 holding the bytes
     of uint16 samples, byte-swapped when big_endian), clamped to [0, 2^bit_depth - 1] as the reference's writers do."""

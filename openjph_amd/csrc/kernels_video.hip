@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ojphgpu.h"
+#include "kernels_video_pieces.h"
 
 namespace {
 
@@ -31,61 +32,6 @@ template <int F, typename D> struct Unit {
   static constexpr int PW = F == V210 ? 32 : NP * PAIR_WORDS;                                // dwords on the packed side
   static constexpr int YW = 2 * NP * (int)sizeof(D) / 4, CW = NP * (int)sizeof(D) / 4;       // dwords in the planes
 };
-
-// sample j of a run of containers held as dwords (j is a compile-time constant wherever these are called)
-template <typename D> __device__ __forceinline__ void put(uint32_t* w, int j, uint32_t v)
-{
-  if (sizeof(D) == 4) w[j] = v;
-  else if (sizeof(D) == 2) w[j >> 1] |= v << (16 * (j & 1));
-  else w[j >> 2] |= v << (8 * (j & 3));
-}
-template <typename D> __device__ __forceinline__ int32_t get(const uint32_t* w, int j)
-{
-  if (sizeof(D) == 4) return (int32_t)w[j];
-  if (sizeof(D) == 2) return (int32_t)((w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
-  return (int32_t)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
-}
-
-// NW dwords <-> memory in the widest pieces the (wave-uniform) alignment `al` of the address allows; MIN: what the
-// element type guarantees anyway
-template <int NW, int MIN> __device__ __forceinline__ void store_words(uint8_t* p, const uint32_t* w, uint32_t al)
-{
-  if ((al & 15u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW / 4; ++i) *(uint4*)(p + 16 * i) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-  } else if ((al & 7u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW / 2; ++i) *(uint2*)(p + 8 * i) = make_uint2(w[2 * i], w[2 * i + 1]);
-  } else if (MIN >= 4 || (al & 3u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) *(uint32_t*)(p + 4 * i) = w[i];
-  } else if (MIN >= 2 || (al & 1u) == 0) {
-#pragma unroll
-    for (int i = 0; i < 2 * NW; ++i) *(uint16_t*)(p + 2 * i) = (uint16_t)(w[i >> 1] >> (16 * (i & 1)));
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4 * NW; ++i) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-  }
-}
-template <int NW, int MIN> __device__ __forceinline__ void load_words(const uint8_t* p, uint32_t* w, uint32_t al)
-{
-  if ((al & 15u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW / 4; ++i) { const uint4 v = *(const uint4*)(p + 16 * i); w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w; }
-  } else if ((al & 7u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW / 2; ++i) { const uint2 v = *(const uint2*)(p + 8 * i); w[2 * i] = v.x; w[2 * i + 1] = v.y; }
-  } else if (MIN >= 4 || (al & 3u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) w[i] = *(const uint32_t*)(p + 4 * i);
-  } else if (MIN >= 2 || (al & 1u) == 0) {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) w[i] = (uint32_t)*(const uint16_t*)(p + 4 * i) | (uint32_t)*(const uint16_t*)(p + 4 * i + 2) << 16;
-  } else {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) w[i] = (uint32_t)p[4 * i] | (uint32_t)p[4 * i + 1] << 8 | (uint32_t)p[4 * i + 2] << 16 | (uint32_t)p[4 * i + 3] << 24;
-  }
-}
 
 // pair k of a unit's packed dwords; sh = 16 - bit depth (Y2XX).  v210: the unit's 96 fields in order are the pairs' Cb Y0
 // Cr Y1, field q in bits [10 * (q % 3), +10) of dword q / 3
@@ -114,8 +60,6 @@ template <int F> __device__ __forceinline__ void put_pair(uint32_t* pw, int k, u
     pw[(q + 2) / 3] |= cr << (10 * ((q + 2) % 3)); pw[(q + 3) / 3] |= y1 << (10 * ((q + 3) % 3));
   }
 }
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // the rows' geometry, the same for both directions: planes = Y [height][width], Cb, Cr [height][cw]
 struct Geo { uint32_t width, height, cw, row_bytes, units, shift; };
@@ -190,8 +134,6 @@ __global__ __launch_bounds__(256) void unpack_video_kernel(const uint8_t* __rest
     }
   }
 }
-
-__device__ __forceinline__ uint32_t clamp_sample(int32_t v, int32_t maxv) { return (uint32_t)(v < 0 ? 0 : (v > maxv ? maxv : v)); }
 
 // planes -> the video buffer; samples clamped to [0, maxv] as pack_kernel does; every byte of the rows is written, padding as zero
 template <int F, typename D>

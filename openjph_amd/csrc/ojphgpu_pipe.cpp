@@ -130,20 +130,25 @@ bool pop_work(std::mutex& mu, std::condition_variable& cv, std::deque<uint32_t>&
 // ---- the hand-over: how a frame crosses PCIe -- the encoder's going in, the decoder's coming out.  PLANES: as the codec
 // holds it, straight into / out of the slot's image.  The other kinds go through the slot's staging buffer (`pixels`) and a
 // launch on the compute stream: PIXELS pixel-interleaved (_set_pixels), PACKED one bit string (_set_packed), VIDEO one 4:2:2
-// video buffer (_set_video, ojphgpu.h section 7b).  A pipe has one; everything the launch needs is fixed when it is set.
+// video buffer (_set_video, ojphgpu.h section 7b) or one 4:2:0 video buffer in its tight layout (section 7c).  A pipe has
+// one; everything the launch needs is fixed when it is set.
 enum HandoverKind { PLANES = 0, PIXELS, PACKED, VIDEO };
 
 struct Handover {
   int kind = PLANES;
   int bits = 0, big_endian = 0;                      // PIXELS: 8 / 16 per sample; PACKED: 10 / 12 / 14
   int format = 0;                                    // VIDEO: OJPHGPU_VIDEO_*
+  uint32_t row_bytes = 0; uint64_t chroma_offset = 0; // VIDEO, 4:2:0: the tight layout inside the staging buffer
   uint32_t w = 0, h = 0, depth = 0;                  // PIXELS, VIDEO: the (luma) plane; the depth a decoder clamps to
   size_t bytes = 0;                                  // of a frame as handed over: what _acquire / _collect report and PCIe carries
 };
 
 // Every refusal of the three setters, and the size of the frame: `want` (kind, bits, big_endian, format) -> the rest of it.
-// decoding: the frame comes back, clamped to one range; odd_x0: the pipe decodes a window whose first column is odd.
-int handover_fit(const Plan& P, int container, bool decoding, bool odd_x0, Handover& want)
+// decoding: the frame comes back, clamped to one range; odd_origin: the pipe decodes a window whose first column (ODD_X0) or
+// first row (ODD_Y0) is odd.
+enum { ODD_X0 = 1, ODD_Y0 = 2 };
+bool video_is_420(int format) { return format == OJPHGPU_VIDEO_NV12 || format == OJPHGPU_VIDEO_NV21 || format == OJPHGPU_VIDEO_P0XX; }
+int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Handover& want)
 {
   const CompGeo& Y = P.comps[0];
   want.w = Y.w; want.h = Y.h; want.depth = 0;
@@ -170,20 +175,31 @@ int handover_fit(const Plan& P, int container, bool decoding, bool odd_x0, Hando
     return OJPHGPU_OK;
   case VIDEO: {
     // three unsigned components of one depth that fits the format, the chroma planes half as wide (rounded up) and as high
-    // as the luma plane, tightly packed; -> the format's layout of that frame
+    // as the luma plane (4:2:0: half as high, rounded up), tightly packed; -> the format's layout of that frame
     const int format = want.format;
-    if (format < OJPHGPU_VIDEO_UYVY || format > OJPHGPU_VIDEO_Y2XX || P.comps.size() != 3) return OJPHGPU_E_INVALID;
+    const bool v420 = video_is_420(format);
+    if (((format < OJPHGPU_VIDEO_UYVY || format > OJPHGPU_VIDEO_Y2XX) && !v420) || P.comps.size() != 3) return OJPHGPU_E_INVALID;
     if (Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
-    const uint32_t cw = (uint32_t)(((uint64_t)Y.w + 1) / 2), b = Y.bit_depth;
+    const uint32_t cw = (uint32_t)(((uint64_t)Y.w + 1) / 2), ch = v420 ? (uint32_t)(((uint64_t)Y.h + 1) / 2) : Y.h, b = Y.bit_depth;
     for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != b) return OJPHGPU_E_INVALID;
-    for (size_t c = 1; c < 3; ++c) if (P.comps[c].w != cw || P.comps[c].h != Y.h) return OJPHGPU_E_INVALID;
-    if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != (uint64_t)Y.w * Y.h + (uint64_t)cw * Y.h) return OJPHGPU_E_INVALID;
+    for (size_t c = 1; c < 3; ++c) if (P.comps[c].w != cw || P.comps[c].h != ch) return OJPHGPU_E_INVALID;
+    if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != (uint64_t)Y.w * Y.h + (uint64_t)cw * ch) return OJPHGPU_E_INVALID;
+    if (v420) {
+      if (format == OJPHGPU_VIDEO_P0XX ? (b < 9 || b > 16 || container == 8) : b > 8u) return OJPHGPU_E_INVALID;
+      if ((uint32_t)container < b) return OJPHGPU_E_INVALID;
+      uint64_t bytes = 0;
+      const int rc = ojphgpu_video420_layout(format, Y.w, Y.h, &want.row_bytes, &want.chroma_offset, &bytes);
+      if (rc) return rc;
+      if (odd_origin) return OJPHGPU_E_INVALID;       // (a window's first column and first row must open a 2 x 2 cell)
+      want.bytes = (size_t)bytes;
+      return OJPHGPU_OK;
+    }
     if (format == OJPHGPU_VIDEO_Y2XX ? (b < 9 || b > 16) : b > (format == OJPHGPU_VIDEO_V210 ? 10u : 8u)) return OJPHGPU_E_INVALID;
     if (container == 8 && format != OJPHGPU_VIDEO_UYVY && format != OJPHGPU_VIDEO_YUY2) return OJPHGPU_E_INVALID;
     uint32_t row_bytes = 0; uint64_t bytes = 0;
     const int rc = ojphgpu_video_layout(format, Y.w, Y.h, &row_bytes, &bytes);
     if (rc) return rc;
-    if (odd_x0) return OJPHGPU_E_INVALID;             // (a window's first column must open a pair)
+    if (odd_origin & ODD_X0) return OJPHGPU_E_INVALID;   // (a window's first column must open a pair)
     want.bytes = (size_t)bytes;
     return OJPHGPU_OK;
   }
@@ -203,6 +219,11 @@ int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int co
     return unpack ? ojphgpu_unpack_bits(stream, d_staged, d_planes, P.frame_elems, h.bits, container)
                   : ojphgpu_pack_bits(stream, d_planes, d_staged, P.frame_elems, container, h.bits);
   case VIDEO:
+    if (video_is_420(h.format)) {                     // the tight layout: both planes at row_bytes
+      uint8_t* const luma = (uint8_t*)d_staged;
+      return unpack ? ojphgpu_unpack_video420(stream, h.format, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
+                    : ojphgpu_pack_video420(stream, h.format, d_planes, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, h.w, h.h, container, h.depth);
+    }
     return unpack ? ojphgpu_unpack_video(stream, h.format, d_staged, d_planes, h.w, h.h, h.depth, container)
                   : ojphgpu_pack_video(stream, h.format, d_planes, d_staged, h.w, h.h, container, h.depth);
   }
@@ -217,14 +238,14 @@ template <class Slot> void* handover_device_side(const Handover& h, Slot& s) { r
 // frame and staging buffer hold the new size -- both only grow, so the call may be repeated -- and the pipe takes the
 // hand-over.  A refusal changes nothing.
 template <class Pipe, class Slot>
-int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, bool odd_x0, int kind, int arg, int big_endian)
+int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, int odd_origin, int kind, int arg, int big_endian)
 {
   if (p->ho.kind != PLANES && p->ho.kind != kind) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     Handover h;
     h.kind = arg ? kind : PLANES; h.big_endian = big_endian ? 1 : 0;
     (kind == VIDEO ? h.format : h.bits) = arg;
-    const int rc = handover_fit(*p->P, p->container, decoding, odd_x0, h);
+    const int rc = handover_fit(*p->P, p->container, decoding, odd_origin, h);
     if (rc) return rc;
     if (h.kind != PLANES) {
       HIPCHK(hipSetDevice(p->device));
@@ -589,7 +610,7 @@ extern "C" int ojphgpu_enc_pipe_acquire(ojphgpu_enc_pipe* p, void** h_frame, siz
 static int enc_set_handover(ojphgpu_enc_pipe* p, int kind, int arg, int big_endian)
 {
   if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE) return OJPHGPU_E_INVALID;
-  return handover_set(p, &EncSlot::h_in, false, false, kind, arg, big_endian);
+  return handover_set(p, &EncSlot::h_in, false, 0, kind, arg, big_endian);
 }
 
 extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian) { return enc_set_handover(p, PIXELS, pixel_bits, big_endian); }
@@ -1080,7 +1101,8 @@ extern "C" int ojphgpu_dec_pipe_collect(ojphgpu_dec_pipe* p, const void** h_fram
 static int dec_set_handover(ojphgpu_dec_pipe* p, int kind, int arg, int big_endian)
 {
   if (!p || p->n_sub != 0) return OJPHGPU_E_INVALID;
-  return handover_set(p, &DecSlot::h_img, true, p->has_region && (p->region[0] & 1u), kind, arg, big_endian);
+  const int odd_origin = !p->has_region ? 0 : ((p->region[0] & 1u) ? ODD_X0 : 0) | ((p->region[1] & 1u) ? ODD_Y0 : 0);
+  return handover_set(p, &DecSlot::h_img, true, odd_origin, kind, arg, big_endian);
 }
 
 extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, int big_endian) { return dec_set_handover(p, PIXELS, pixel_bits, big_endian); }

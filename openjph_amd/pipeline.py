@@ -25,9 +25,10 @@ def _frame_view(pipe, ptr, nbytes):
     raw = _view(ptr, nbytes)
     if pipe.packed:                                   # one bit string
         return raw
-    if pipe.video:                                    # [H, row_bytes]
+    if pipe.video:                                    # [H, row_bytes]; 4:2:0: [H + ch, row_bytes], the chroma plane's rows behind the luma plane's
         h = pipe.plan.comp_info(0)["h"]
-        return raw.reshape(h, nbytes // h)
+        rows = h + (h + 1) // 2 if pipe.video in VIDEO420_FORMATS else h
+        return raw.reshape(rows, nbytes // rows)
     if pipe.pixels is not None:                       # [H,W,C] in the file's sample type (big endian: the raw bytes)
         c, h, w = pipe.plan.frame_shape
         dt = np.uint8 if pipe.pixels[0] == 8 else np.dtype(">u2" if pipe.pixels[1] else "<u2")
@@ -55,7 +56,8 @@ class _Handover:
 
     def set_video(self, fmt):
         """judged on the pipe's plan (a view's: the view's; a region with odd x0 is refused): three unsigned components of
-        one depth the format holds, the chroma half as wide"""
+        one depth the format holds, the chroma half as wide -- and, for the 4:2:0 names of VIDEO420_FORMATS, half as high (a
+        region with odd y0 is refused too)"""
         self._set("video", _video_code(self.plan, fmt, "%s_pipe_set_video" % self._side))
         self.video = fmt
 
@@ -106,9 +108,9 @@ def _video_code(plan, fmt, what):
     samples do not have is refused here as the library refuses the rest"""
     if fmt is None:
         return 0
-    if fmt not in VIDEO_FORMATS:
-        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS))))
-    code, fixed = VIDEO_FORMATS[fmt]
+    if fmt not in VIDEO_FORMATS and fmt not in VIDEO420_FORMATS:
+        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS) + sorted(VIDEO420_FORMATS))))
+    code, fixed = (VIDEO_FORMATS if fmt in VIDEO_FORMATS else VIDEO420_FORMATS)[fmt]
     if fixed is not None and plan.comp_format(0)[0] != fixed:
         raise capi.OjphError(capi.E_INVALID, "%s: %r on %d-bit samples" % (what, fmt, plan.comp_format(0)[0]))
     return code
@@ -170,6 +172,78 @@ def unpack_video(buf, fmt, width, height, bit_depth=None):
     return [np.ascontiguousarray(y), np.ascontiguousarray(f[:, :, 2]), np.ascontiguousarray(f[:, :, 3])]
 
 
+# 4:2:0 video buffers (ojphgpu.h section 7c), two planes: name -> (OJPHGPU_VIDEO_* constant, the depth the name fixes or None).
+# A table of its own: the 4:2:2 functions above keep refusing these names, as the 4:2:2 entry points refuse these codes.
+VIDEO420_FORMATS = {"nv12": (0x11, None), "nv21": (0x12, None), "p0xx": (0x13, None), "p010": (0x13, 10), "p012": (0x13, 12), "p016": (0x13, 16)}
+
+
+def video420_format(fmt, bit_depth):
+    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a 4:2:0 format name, refused when the depth is outside the format's column"""
+    if fmt not in VIDEO420_FORMATS:
+        raise ValueError("4:2:0 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO420_FORMATS))))
+    code, fixed = VIDEO420_FORMATS[fmt]
+    if fixed is None and bit_depth is None and code != 0x13:
+        bit_depth = 8
+    if fixed is None and bit_depth is None:
+        raise ValueError("video format %r needs a bit depth" % fmt)
+    b = int(fixed if bit_depth is None else bit_depth)
+    lo, hi = (9, 16) if code == 0x13 else (1, 8)
+    if not lo <= b <= hi or (fixed is not None and b != fixed):
+        raise ValueError("video format %r does not hold %d-bit samples" % (fmt, b))
+    return code, b
+
+
+def video420_layout(fmt, width, height):
+    """-> (row_bytes, chroma_offset, frame_bytes) of the tight layout of a width x height frame, as ojphgpu_video420_layout:
+    `height` luma rows, then ceil(height / 2) chroma rows, all at row_bytes"""
+    if fmt not in VIDEO420_FORMATS:
+        raise ValueError("4:2:0 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO420_FORMATS))))
+    if width < 1 or height < 1:
+        raise ValueError("video420_layout: a frame has at least one sample")
+    cw, ch = (int(width) + 1) // 2, (int(height) + 1) // 2
+    row = (4 if VIDEO420_FORMATS[fmt][0] == 0x13 else 2) * cw
+    return row, row * int(height), row * (int(height) + ch)
+
+
+def pack_video420(planes, fmt, bit_depth=None):
+    """numpy: planes = [Y [H,W], Cb [ch,cw], Cr [ch,cw]] (cw = ceil(W / 2), ch = ceil(H / 2)) -> the frame as one 4:2:0 video
+    buffer in the tight layout, uint8 [H + ch, row_bytes]: H luma rows, then ch rows of (Cb, Cr) pairs (nv21: (Cr, Cb)): the
+    host-side statement of ojphgpu_pack_video420.  Samples are clamped to [0, 2^bit_depth - 1]; padding (the sample behind an
+    odd luma row, the low bits of a P0XX word) is zero."""
+    code, b = video420_format(fmt, bit_depth)
+    y, cb, cr = [np.clip(np.asarray(p).astype(np.int64), 0, (1 << b) - 1) for p in planes]
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError("pack_video420: the luma plane is [H, W]")
+    h, w = y.shape
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
+        raise ValueError("pack_video420: chroma planes of %s and %s, not %s" % (cb.shape, cr.shape, (ch, cw)))
+    f = np.zeros((h + ch, 2 * cw), np.int64)
+    f[:h, :w] = y
+    f[h:, 0::2], f[h:, 1::2] = (cr, cb) if code == 0x12 else (cb, cr)
+    if code == 0x13:
+        return np.ascontiguousarray((f << (16 - b)).astype("<u2")).view(np.uint8).reshape(h + ch, 4 * cw)
+    return f.astype(np.uint8)
+
+
+def unpack_video420(buf, fmt, width, height, bit_depth=None):
+    """numpy inverse of pack_video420: the bytes of a 4:2:0 video buffer in the tight layout -> [Y [H,W], Cb [ch,cw], Cr
+    [ch,cw]] (uint16).  A sample is its element (P0XX: word >> (16 - bit_depth)); padding is not looked at and no value is
+    range-checked."""
+    code, b = video420_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    row, _, total = video420_layout(fmt, w, h)
+    raw = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if raw.size != total:
+        raise ValueError("unpack_video420: %d bytes, the frame has %d" % (raw.size, total))
+    raw = raw.reshape(h + ch, row)
+    f = (raw.view("<u2") >> (16 - b)).astype(np.uint16) if code == 0x13 else raw.astype(np.uint16)
+    c0, c1 = f[h:, 0::2], f[h:, 1::2]
+    cb, cr = (c1, c0) if code == 0x12 else (c0, c1)
+    return [np.ascontiguousarray(f[:h, :w]), np.ascontiguousarray(cb), np.ascontiguousarray(cr)]
+
+
 class EncoderPipe(_Handover):
     _side = "enc"
 
@@ -178,7 +252,8 @@ class EncoderPipe(_Handover):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
         the device.  video="uyvy" | "yuy2" | "v210" | "y210" | "y212" | "y216": the frames are handed over as one 4:2:2 video
-        buffer (uint8 [H, row_bytes], pack_video's layout) and unpacked on the device.  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
+        buffer (uint8 [H, row_bytes], pack_video's layout) and unpacked on the device; video="nv12" | "nv21" | "p010" | "p012" |
+        "p016": as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420's tight layout).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
         quality target (set_quality) -- one or the other"""
         from .codec import _torch
         _torch()
@@ -318,7 +393,8 @@ class DecoderPipe(_Handover):
                  skip_res=None, region=None, video=None):
         """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
         skip_res=n or (for_data, for_recon), region=(x0, y0, w, h): the pipe decodes that view of every frame, as
-        video="uyvy" | ...: they come back as one 4:2:2 video buffer (uint8 [H, row_bytes], pack_video of the planes).
+        video="uyvy" | ...: they come back as one 4:2:2 video buffer (uint8 [H, row_bytes], pack_video of the planes);
+        video="nv12" | "nv21" | "p010" | ...: as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420 of them).
         codec.Decoder takes them (ojphgpu_dec_pipe_create_view); .plan, the frames and pixels / packed are the view's"""
         from .codec import _torch
         _torch()

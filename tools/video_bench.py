@@ -4,6 +4,11 @@ handing a v210 buffer to the encoder pipe is worth against planar 16-bit contain
 
     python tools/video_bench.py [--rounds 5] [--reps 20] [--frames 48] [--depth 4] [--out profiles/video_bench.txt]
 
+--v420 measures the 4:2:0 kernels of kernels_video420.hip instead (NV12 into 8- and 16-bit containers, P010 into 16- and 32-bit
+ones, both directions, the tight layout) beside the yardstick and the 4:2:2 kernels of the same containers (UYVY 8, Y210 16),
+marks a 4:2:0 kernel whose median stays below that 4:2:2 kernel's by more than the larger of the two spreads, and runs
+EncoderPipe(video="p010") on a 4:2:0 plan against the same pipe fed planes; its default --out is profiles/video420_bench.txt.
+
 1. Every instantiation of ojphgpu_unpack_video / _pack_video (format x container), bytes read plus written per second, beside
    the yardstick: ojphgpu_unpack_pixels / _pack_pixels with 3 components, 16-bit samples into 16-bit containers, on the same
    number of pixels -- the same kind of copy.  All of them alternate inside every round; a kernel runs `reps` launches per
@@ -29,6 +34,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 W, H, DEPTH = 7680, 4320, 10
 NSETS = 4
 KERNELS = [(f, c) for f, cs in (("uyvy", (8, 16, 32)), ("yuy2", (8, 16, 32)), ("v210", (16, 32)), ("y210", (16, 32))) for c in cs]
+KERNELS_420 = [("nv12", 8), ("nv12", 16), ("p010", 16), ("p010", 32)]
+PEERS_420 = {8: ("uyvy", 8), 16: ("y210", 16)}              # the 4:2:2 kernel a 4:2:0 kernel is held against, by container (32: none measured beside it)
 
 
 def median_spread(v):
@@ -36,14 +43,23 @@ def median_spread(v):
     return med, (max(v) - min(v)) / med
 
 
-def kernel_rates(torch, rounds, reps, emit):
+def kernel_rates(torch, rounds, reps, emit, v420=False):
     from openjph_amd import codec
-    from openjph_amd.pipeline import video_layout
+    from openjph_amd.pipeline import video420_layout, video_layout
     cw = (W + 1) // 2
     n = W * H + 2 * cw * H
     dts = {8: torch.uint8, 16: torch.int16, 32: torch.int32}
     work = {}                                                # name -> (callable(set index), bytes read + written)
-    for fmt, cont in KERNELS:
+    for fmt, cont in KERNELS_420 if v420 else ():
+        b = 8 if fmt == "nv12" else DEPTH
+        n420 = W * H + 2 * cw * ((H + 1) // 2)
+        total = video420_layout(fmt, W, H)[2]
+        vid = [torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda") for _ in range(NSETS)]
+        pl = [torch.randint(0, 1 << b, (n420,), dtype=torch.int32, device="cuda").to(dts[cont]) for _ in range(NSETS)]
+        moved = total + n420 * (cont // 8)
+        work["unpack %s -> %d" % (fmt, cont)] = (lambda i, fmt=fmt, b=b, vid=vid, pl=pl: codec.unpack_video420(vid[i], fmt, W, H, b, out=pl[i]), moved)
+        work["pack %d -> %s" % (cont, fmt)] = (lambda i, fmt=fmt, b=b, vid=vid, pl=pl: codec.pack_video420(pl[i], fmt, W, H, b, out=vid[i]), moved)
+    for fmt, cont in sorted(set(PEERS_420.values())) if v420 else KERNELS:
         b = 8 if fmt in ("uyvy", "yuy2") else DEPTH
         total = video_layout(fmt, W, H)[1]
         vid = [torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda") for _ in range(NSETS)]
@@ -79,6 +95,24 @@ def kernel_rates(torch, rounds, reps, emit):
                 rates[name].append(moved * reps / (e0.elapsed_time(e1) * 1e-3) / 1e9)
     out = {}
     emit("1. kernels, %d x %d, GB/s read + written; %d rounds of %d launches" % (W, H, rounds, reps))
+    floor = None
+    if v420:
+        # the same loop on a 64 x 2 frame: the pace at which this host issues launches (the device's own fixed cost per launch
+        # hides below it).  The kernels here take 20 to 70 us per launch: the loop above stays ahead of the device when this
+        # figure is well below that.  --frame tells what a rate owes to the bytes of a launch
+        tv, tp = torch.zeros(4096, dtype=torch.uint8, device="cuda"), torch.zeros(4096, dtype=torch.uint8, device="cuda")
+        us = []
+        for r in range(rounds + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(10 * reps):
+                codec.unpack_video420(tv, "nv12", 64, 2, 8, out=tp)
+            e1.record()
+            e1.synchronize()
+            if r:
+                us.append(e0.elapsed_time(e1) * 1e3 / (10 * reps))
+        floor = statistics.median(us)
+        emit("  one launch on a 64 x 2 frame (the host's issue pace), us: %s  median %.2f" % (" ".join("%.2f" % x for x in us), floor))
     for name, v in rates.items():
         med, spread = median_spread(v)
         out[name] = {"GBps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "bytes": work[name][1]}
@@ -86,9 +120,19 @@ def kernel_rates(torch, rounds, reps, emit):
         yard = out["unpack_pixels 3 x 16 -> 16 (yardstick)" if name.startswith("unpack") else "pack_pixels 16 -> 3 x 16 (yardstick)"]
         below = o["median"] < yard["median"] * (1 - max(o["spread"], yard["spread"]))
         o["below_yardstick"] = bool(below and "yardstick" not in name)
-        emit("  %-40s %s  median %7.1f  spread %4.1f %%  %5.1f MB per launch%s" %
-             (name, " ".join("%7.1f" % x for x in o["GBps"]), o["median"], o["spread"] * 100, o["bytes"] / 1e6,
-              "   BELOW the yardstick by more than the spread" if o["below_yardstick"] else ""))
+        note = "   BELOW the yardstick by more than the spread" if o["below_yardstick"] else ""
+        words = name.split()
+        fmt, cont = (words[1], int(words[3])) if words[0] == "unpack" else (words[3], int(words[1])) if words[0] == "pack" else (None, 0)
+        if v420 and (fmt, cont) in KERNELS_420 and cont in PEERS_420:      # the claim of the 4:2:2 finding: at least the 4:2:2 kernel of its container
+            peer = out[("unpack %s -> %d" if words[0] == "unpack" else "pack %d -> %s") % (PEERS_420[cont] if words[0] == "unpack" else PEERS_420[cont][::-1])]
+            o["peer_422"] = "%s %d" % PEERS_420[cont]
+            o["reaches_peer_422"] = bool(o["median"] >= peer["median"] * (1 - max(o["spread"], peer["spread"])))
+            note += "   %s %s %d (%.1f)" % ("reaches" if o["reaches_peer_422"] else "BELOW", PEERS_420[cont][0], cont, peer["median"])
+        o["us_per_launch"] = round(o["bytes"] / o["median"] / 1e3, 2)
+        emit("  %-40s %s  median %7.1f  spread %4.1f %%  %5.1f MB, %5.1f us per launch%s" %
+             (name, " ".join("%7.1f" % x for x in o["GBps"]), o["median"], o["spread"] * 100, o["bytes"] / 1e6, o["us_per_launch"], note))
+    if floor is not None:
+        out["launch_floor_us"] = round(floor, 2)
     return out
 
 
@@ -126,24 +170,27 @@ def steady(pipe, n):
     return time.perf_counter() - t0
 
 
-def pipe_rates(rounds, frames, depth, emit):
-    from openjph_amd.pipeline import EncoderPipe, pack_video
+def pipe_rates(rounds, frames, depth, emit, v420=False):
+    from openjph_amd.pipeline import EncoderPipe, pack_video, pack_video420
     from openjph_amd.plan import Plan, make_params
     planes = workload_planes()
-    mk = lambda: Plan(make_params(W, H, 3, bit_depth=DEPTH, reversible=False, downsampling=[(1, 1), (2, 1), (2, 1)]))
-    video = EncoderPipe(plan=mk(), depth=depth, container=16, video="v210")
+    fmt = "p010" if v420 else "v210"
+    if v420:                                                 # the same frame as 4:2:0 planes
+        planes = [planes[0], np.ascontiguousarray(planes[1][0::2]), np.ascontiguousarray(planes[2][0::2])]
+    mk = lambda: Plan(make_params(W, H, 3, bit_depth=DEPTH, reversible=False, downsampling=[(1, 1), (2, 2 if v420 else 1), (2, 2 if v420 else 1)]))
+    video = EncoderPipe(plan=mk(), depth=depth, container=16, video=fmt)
     planar = EncoderPipe(plan=mk(), depth=depth, container=16)
-    a = fill_and_drain(video, pack_video(planes, "v210", DEPTH))
+    a = fill_and_drain(video, pack_video420(planes, fmt, DEPTH) if v420 else pack_video(planes, fmt, DEPTH))
     b = fill_and_drain(planar, planar.plan.pack_frame(planes))
     assert a == b, "the two pipes' codestreams differ"
-    link = {"v210": video.acquire().nbytes, "planar16": planar.acquire().nbytes}
-    fps = {"v210": [], "planar16": []}
+    link = {fmt: video.acquire().nbytes, "planar16": planar.acquire().nbytes}
+    fps = {fmt: [], "planar16": []}
     for _ in range(rounds):
-        fps["v210"].append(frames / steady(video, frames))
+        fps[fmt].append(frames / steady(video, frames))
         fps["planar16"].append(frames / steady(planar, frames))
     video.close(); planar.close()
     out = {}
-    emit("2. EncoderPipe, %d x %d 4:2:2 %d-bit 9/7, depth %d, %d frames per round, codestream %d bytes" % (W, H, DEPTH, depth, frames, len(a)))
+    emit("2. EncoderPipe, %d x %d %s %d-bit 9/7, depth %d, %d frames per round, codestream %d bytes" % (W, H, "4:2:0" if v420 else "4:2:2", DEPTH, depth, frames, len(a)))
     for way, v in fps.items():
         med, spread = median_spread(v)
         out[way] = {"fps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "link_bytes_per_frame": int(link[way])}
@@ -158,8 +205,15 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--depth", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "video_bench.txt"))
+    ap.add_argument("--v420", action="store_true", help="the 4:2:0 kernels and a p010 pipe beside the yardstick and their 4:2:2 peers")
+    ap.add_argument("--frame", default=None, metavar="WxH", help="another frame size for the kernels (the pipes are then left out): what a rate owes to the bytes of a launch")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "video420_bench.txt" if args.v420 else "video_bench.txt")
+    global W, H
+    if args.frame:
+        W, H = (int(v) for v in args.frame.lower().split("x"))
     import torch
     if not torch.cuda.is_available():
         sys.exit("video_bench: no GPU visible; there is nothing to measure without one")
@@ -169,11 +223,11 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    emit("tools/video_bench.py --rounds %d --reps %d --frames %d --depth %d on %s" % (args.rounds, args.reps, args.frames, args.depth,
-                                                                                   torch.cuda.get_device_name(0)))
-    kernels = kernel_rates(torch, args.rounds, args.reps, emit)
+    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
+                                                                                     args.depth, torch.cuda.get_device_name(0)))
+    kernels = kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
     torch.cuda.empty_cache()
-    pipes = pipe_rates(args.rounds, args.frames, args.depth, emit)
+    pipes = pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420) if not args.frame else {}
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print(json.dumps({"kernels": kernels, "pipes": pipes}))
