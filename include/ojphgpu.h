@@ -725,6 +725,19 @@ int  ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_
  * OJPHGPU_E_INVALID.  hist may be NULL (the hinted trials, then halving). */
 int  ojphgpu_rate_search_hint(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
                               ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
+/* The same search in steps, for callers whose measurements are shared (the batch encoder below advances one per frame
+ * over common launches): _next hands out the index to measure -- 1: measure size(*j) and _feed it; 0: certified, _info holds
+ * the answer; OJPHGPU_E_BUDGET: size(0) > max_bytes (_info: passes, first_guess) -- and _feed takes the size of the index
+ * _next handed out; a size < 0 ends the stepper and comes back as it is.  ojphgpu_rate_search_hint is a loop over this:
+ * the indices asked, passes, first_guess, the result and the codes are the same.  hist / hint as there; the histograms
+ * are read by _create only.  OJPHGPU_E_INVALID: _next after the end or with an index still out, _feed without a _next. */
+typedef struct ojphgpu_rate_stepper ojphgpu_rate_stepper;
+int  ojphgpu_rate_stepper_create(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
+                                 ojphgpu_rate_stepper** out);
+int  ojphgpu_rate_stepper_next(ojphgpu_rate_stepper* st, uint32_t* j);
+int  ojphgpu_rate_stepper_feed(ojphgpu_rate_stepper* st, int64_t size);
+int  ojphgpu_rate_stepper_info(const ojphgpu_rate_stepper* st, ojphgpu_rate_info* out);
+void ojphgpu_rate_stepper_destroy(ojphgpu_rate_stepper* st);
 /* the model alone: predicted bytes of every grid index, out[OJPHGPU_RATE_GRID] (what tools/rate_bench.py reports) */
 int  ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out);
 
@@ -734,11 +747,29 @@ int  ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double
  * qstep(j), the block lengths come to the host and the Tier-2 layout gives size(j) -- and downloads the coded bytes
  * once, for j*.  OJPHGPU_E_BUDGET leaves the encoder usable.  OJPHGPU_E_INVALID: a plan with a reversible component (COC
  * included), a quality factor (global or per component), ATK / DFS wavelets, a band of 2^32 samples or more; an encoder
- * of a tile range that does not cover the frame; a batch encoder.  The per-block scratch slots and the output buffer
- * are re-sized for the finest step of the grid on the first call. */
+ * of a tile range that does not cover the frame; a batch encoder -- ON PURPOSE, also for equal budgets: the batch form is
+ * the array call below, and callers rely on this refusal.  The per-block scratch slots and the output buffer are
+ * re-sized for the finest step of the grid on the first call. */
 int  ojphgpu_encoder_set_budget(ojphgpu_encoder* enc, uint64_t max_bytes);
-/* what the last budgeted ojphgpu_encoder_finish* found (OJPHGPU_E_INVALID before one) */
+/* what the last budgeted ojphgpu_encoder_finish* found (OJPHGPU_E_INVALID before one); a batch encoder: for frame 0 */
 int  ojphgpu_encoder_rate_info(ojphgpu_encoder* enc, ojphgpu_rate_info* info);
+/* A batch encoder (ojphgpu_encoder_create_batch) codes frame f of every following run to max_bytes[f]; n must be the
+ * encoder's frame count (a single-frame encoder: n == 1, exactly ojphgpu_encoder_set_budget).  All zeros switches the
+ * budgets off as set_budget(0) does; a zero among non-zero values is OJPHGPU_E_INVALID, and so is everything set_budget
+ * refuses except "a batch encoder", and a batch whose output bound at the finest step of the grid does not fit the 32-bit
+ * byte cursor (code fewer frames per batch).  ojphgpu_encoder_run_device* enqueues conversion, DWT and the statistics
+ * of every frame.  The first ojphgpu_encoder_finish_frame of a run searches all frames together, in ROUNDS: one launch
+ * sets every frame's step -- an open frame's the index its stepper hands out, a certified frame's its j*, a frame nothing
+ * fits index 0 -- the block coder runs over the blocks of all frames, the lengths come back once and every open frame's
+ * layout feeds its stepper; the rounds end when every frame was coded at its answer in the last one, and the bytes are
+ * downloaded once.  finish_frame(f) then writes frame f: byte for byte the single-frame budgeted encode of that frame at
+ * max_bytes[f].  A frame with size(0) > max_bytes[f] gets OJPHGPU_E_BUDGET from its own finish_frame only; the others
+ * are written, and the encoder stays usable.  _rate_info_frame answers as the single encoder's _rate_info would for that
+ * frame and budget (passes: the frame's own trials, plus one when the last of them was not j*); _rate_rounds gives the
+ * rounds of the last search. */
+int  ojphgpu_encoder_set_budgets(ojphgpu_encoder* enc, const uint64_t* max_bytes, uint32_t n);
+int  ojphgpu_encoder_rate_info_frame(ojphgpu_encoder* enc, uint32_t frame, ojphgpu_rate_info* info);
+int  ojphgpu_encoder_rate_rounds(ojphgpu_encoder* enc, uint32_t* rounds);
 /* host clock of the last budgeted finish, ms: out[0] the search (every pass), [1] the part of it spent waiting for the
  * device and the copies of the block lengths, [2] the download and Tier-2 of j*; out[3] the band statistics kernel of the
  * run before it (device events; needs ojphgpu_encoder_set_timing's per-launch spans, the default) */

@@ -348,6 +348,14 @@ SIGNATURES = {
     "ojphgpu_encoder_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
     "ojphgpu_encoder_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_encoder_rate_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_encoder_set_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]),
+    "ojphgpu_encoder_rate_info_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RateInfo)]),
+    "ojphgpu_encoder_rate_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ojphgpu_rate_stepper_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ojphgpu_rate_stepper_next": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ojphgpu_rate_stepper_feed": (C.c_int, [C.c_void_p, C.c_int64]),
+    "ojphgpu_rate_stepper_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
+    "ojphgpu_rate_stepper_destroy": (None, [C.c_void_p]),
     "ojphgpu_band_requantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ojphgpu_frame_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ojphgpu_frame_error_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),

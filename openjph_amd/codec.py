@@ -43,10 +43,11 @@ class Encoder:
     """Whole-frame encoder for one frame shape / parameter set (ojphgpu_encoder)."""
 
     def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, max_bytes=0, max_sse=None, min_psnr=None,
-                 **kw):
+                 budgets=None, **kw):
         """tiles=(first, count) restricts the encoder to a run of tiles (multi-GPU sharding);
         frames=B makes it code a batch of B independent frames per run ([B,C,H,W] input);
         max_bytes=N codes every frame to a byte budget (set_budget);
+        budgets=[N0, N1, ...] codes frame f of every batch to N_f bytes (set_budgets);
         max_sse=N / min_psnr=dB codes every frame to a quality target (set_quality)."""
         torch = _torch()
         self.device = device
@@ -67,10 +68,13 @@ class Encoder:
         fs = self.plan.frame_shape          # [C,H,W], or flat (frame_elems,) when components differ in size
         self.shape = fs if self.frames == 1 else (self.frames,) + fs
         self.max_bytes = 0
+        self.budgets = None
         self.max_sse = None
         self._frame = None
         if max_bytes:
             self.set_budget(max_bytes)
+        if budgets is not None:
+            self.set_budgets(budgets)
         if max_sse is not None or min_psnr is not None:
             self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
 
@@ -82,6 +86,23 @@ class Encoder:
         with _torch().cuda.device(self.device):
             check(self._lib.ojphgpu_encoder_set_budget(self._h, int(max_bytes)), "encoder_set_budget")
         self.max_bytes = int(max_bytes)
+        self.budgets = None
+
+    def set_budgets(self, budgets):
+        """A batch encoder codes frame f of every following batch to budgets[f] bytes (len(budgets) == frames): each
+        codestream is what a single-frame encoder with set_budget(budgets[f]) writes for that frame.  All zeros switches
+        the budgets off; a zero among others is refused.  The frames are searched together, in rounds over shared launches
+        (rate_rounds).  A frame nothing fits raises OjphError with code E_BUDGET from its own finish(f); the other frames
+        are written.  set_budget(N) stays refused on a batch encoder: this is the call, also for equal budgets."""
+        seq = [int(b) for b in budgets]
+        arr = (C.c_uint64 * max(len(seq), 1))(*seq)
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_encoder_set_budgets(self._h, arr, len(seq)), "encoder_set_budgets")
+        if self.frames == 1:
+            self.max_bytes, self.budgets = seq[0], None
+        else:
+            self.max_bytes = seq[0] if any(seq) else 0
+            self.budgets = seq if any(seq) else None
 
     def set_quality(self, max_sse=None, min_psnr=None):
         """Every following frame is coded at the coarsest step of the rate grid found to meet the target: the squared error
@@ -126,12 +147,29 @@ class Encoder:
         check(self._lib.ojphgpu_encoder_quality_timing(self._h, t), "encoder_quality_timing")
         return dict(search_ms=t[0], wait_ms=t[1], final_ms=t[2])
 
-    def rate_info(self):
+    def rate_info(self, frame=None):
         """what the last budgeted finish() found: dict(grid_index, qstep, bytes, bytes_finer = the length one step finer
-        (0 at the end of the grid), passes = block-coder runs made, first_guess = the model's first index)"""
+        (0 at the end of the grid), passes = block-coder runs made, first_guess = the model's first index).  A batch
+        encoder: the list of these per frame (frame=f: that frame's alone), None for a frame nothing fitted; passes are
+        the frame's own trials, as a single encoder would have made them."""
         info = capi.RateInfo()
-        check(self._lib.ojphgpu_encoder_rate_info(self._h, C.byref(info)), "encoder_rate_info")
-        return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+        if self.frames == 1:
+            check(self._lib.ojphgpu_encoder_rate_info(self._h, C.byref(info)), "encoder_rate_info")
+            return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+        out = []
+        for f in (range(self.frames) if frame is None else [int(frame)]):
+            rc = self._lib.ojphgpu_encoder_rate_info_frame(self._h, f, C.byref(info))
+            if rc != capi.E_BUDGET:
+                check(rc, "encoder_rate_info_frame")
+            out.append(None if rc == capi.E_BUDGET else {k: getattr(info, k) for k, _ in capi.RateInfo._fields_})
+        return out if frame is None else out[0]
+
+    def rate_rounds(self):
+        """block-coder runs the last budgeted finish() made: the rounds of a batch's search (every round codes all frames),
+        the passes of a single frame's"""
+        n = C.c_uint32()
+        check(self._lib.ojphgpu_encoder_rate_rounds(self._h, C.byref(n)), "encoder_rate_rounds")
+        return int(n.value)
 
     def rate_timing(self):
         """host clock of the last budgeted finish(), ms: dict(search_ms = all passes, wait_ms = of that, waiting for the device,
@@ -174,7 +212,8 @@ class Encoder:
     def finish(self, frame=0) -> bytes:
         """codestream of frame `frame` of the last run"""
         if self.max_bytes:                 # (a budget far above what the frame can need: the second round below)
-            cap = min(self.max_bytes, self.plan.frame_elems * 4 + 64 * self.plan.num_blocks + (1 << 20))
+            budget = self.budgets[frame] if self.budgets and 0 <= frame < self.frames else self.max_bytes
+            cap = min(budget, self.plan.frame_elems * 4 + 64 * self.plan.num_blocks + (1 << 20))
         elif self.max_sse is not None:     # (the blocks are coded inside finish: nothing to size the buffer by yet)
             cap = self.plan.frame_elems * 3 + 64 * self.plan.num_blocks + (1 << 20)
         else:

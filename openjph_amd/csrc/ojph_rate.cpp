@@ -74,20 +74,18 @@ int rate_table_build(const Plan& P, RateTable& T)
   return OJPHGPU_OK;
 }
 
-namespace {
-
 // The model.  A coefficient whose half octave lies below its band's step costs nothing; one at t = log2(|c| / step) > 0
 // costs t magnitude bits plus about three for its sign and its share of the VLC and MEL strings; the half octave around
 // the step is significant for part of its members.  Per block a few bytes of packet header, per codestream its markers.
 // Its absolute level is off by 10 % at the usual rates and by far more near the knee, where most coefficients are
 // within a factor of two of the step -- the search rescales it by what a trial measures.
-struct Model {
+struct RateModel {
   const RateTable& T;
   std::vector<double> h;                                     // [nclasses][BINS]: the bands' histograms summed per class
   std::vector<uint8_t> used;                                 // per class: the bins that hold anything, as a list
   std::vector<uint32_t> used_first;
   double memo[OJPHGPU_RATE_GRID];
-  Model(const RateTable& t, const uint32_t* hist) : T(t), h((size_t)t.nclasses * OJPHGPU_STATS_BINS, 0.0)
+  RateModel(const RateTable& t, const uint32_t* hist) : T(t), h((size_t)t.nclasses * OJPHGPU_STATS_BINS, 0.0)
   {
     for (size_t b = 0; b < T.band_class.size(); ++b)
       for (uint32_t k = 0; k < OJPHGPU_STATS_BINS; ++k) h[(size_t)T.band_class[b] * OJPHGPU_STATS_BINS + k] += hist[b * OJPHGPU_STATS_BINS + k];
@@ -116,64 +114,116 @@ struct Model {
   }
 };
 
-}  // namespace
+}  // namespace ojphgpu
 
-// hint: a grid index to try first (the previous frame's answer), then its neighbour on the side the result points to and, if
-// that points the same way, the index beyond it, before the model proposes anything; -1 = none.  The hinted trials shrink
-// the interval like any other and count among the six model-led ones, so the guarantees of the plain search hold.
-int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out)
-{
-  if (!fn || !out || hint < -1 || hint >= (int)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
-  memset(out, 0, sizeof(*out));
-  const int N = OJPHGPU_RATE_GRID;
-  std::vector<int64_t> size((size_t)N, -1);
-  Model* model = hist ? new Model(T, hist) : nullptr;
-  struct Free { Model* m; ~Free() { delete m; } } fr{ model };
+// The search as a state machine, so that several of them can advance together over shared measurements (a batch encoder):
+// _next hands out the index to measure, _feed takes its size.  hint: a grid index to try first (the previous frame's answer),
+// then its neighbour on the side the result points to and, if that points the same way, the index beyond it, before the
+// model proposes anything; -1 = none.  The hinted trials shrink the interval like any other and count among the six
+// model-led ones, so the guarantees of the plain search hold.
+struct ojphgpu_rate_stepper {
+  enum Phase { HINT, HINT_FED, NEIGHBOUR, MAIN, ENDED };
+  static constexpr int N = OJPHGPU_RATE_GRID;
+  ojphgpu::RateTable own;                                    // of a stepper made from a plan; T points at it
+  const ojphgpu::RateTable* T = nullptr;
+  ojphgpu::RateModel* model = nullptr;
+  uint64_t max_bytes = 0;
+  int hint = -1;
+  std::vector<int64_t> size = std::vector<int64_t>((size_t)N, -1);
   // every index <= lo that was tried fits, every index >= hi that was tried does not; lo and hi themselves were tried (or are
   // the ends -1 / N).  hi - lo == 1 is the certificate: size(lo) <= B < size(lo + 1), both measured.
   int lo = -1, hi = N;
   double scale = 1.0;
-  uint32_t passes = 0;
-  int err = 0;
-  auto trial = [&](int j) -> bool {                          // false: fn failed, err holds what to return
-    if (passes == 0) out->first_guess = (uint32_t)j;
-    const int64_t s = fn(user, (uint32_t)j);
-    ++passes;
-    out->passes = passes;
-    if (s < 0) { err = s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s; return false; }
+  Phase phase = MAIN;
+  int dir = 0, k = 0;                                        // of the hinted trials: the side they walk to, how far
+  int pending = -1;                                          // the index handed out and not fed yet
+  ojphgpu_rate_info info;
+  void start(const ojphgpu::RateTable& t, const uint32_t* hist, uint64_t budget, int h)
+  {
+    T = &t; max_bytes = budget; hint = h;
+    if (hist) model = new ojphgpu::RateModel(t, hist);
+    phase = h >= 0 ? HINT : MAIN;
+    memset(&info, 0, sizeof(info));
+  }
+  ~ojphgpu_rate_stepper() { delete model; }
+  int hand(int j, uint32_t* out)
+  {
+    if (info.passes == 0) info.first_guess = (uint32_t)j;
+    pending = j; *out = (uint32_t)j;
+    return 1;
+  }
+  int next(uint32_t* out)
+  {
+    if (phase == ENDED || pending >= 0) return OJPHGPU_E_INVALID;
+    if (phase == HINT) { phase = HINT_FED; return hand(hint, out); }
+    if (phase == NEIGHBOUR) {
+      // the neighbour the result points to and, when that one points the same way, the next index on: an answer one step
+      // from the hint is certified by three trials whatever the model makes of the frame.  Each only where the index
+      // exists and the certificate is still open.
+      const int nb = hint + k * dir;
+      if (k <= 2 && hi - lo > 1 && nb > lo && nb < hi) return hand(nb, out);
+      phase = MAIN;
+    }
+    if (hi - lo > 1) {
+      int j = (lo + hi) / 2;
+      if (model && info.passes < 6) {
+        // the finest candidate the rescaled model lets fit (its prediction grows with j: bisection over the candidates)
+        int a = lo, b = hi;                                  // a fits (or is the end), b does not
+        while (b - a > 1) { const int m = (a + b) / 2; if (scale * model->bytes((uint32_t)m) <= (double)max_bytes) a = m; else b = m; }
+        j = std::min(std::max(a, lo + 1), hi - 1);
+      }
+      return hand(j, out);
+    }
+    phase = ENDED;
+    if (lo < 0) return OJPHGPU_E_BUDGET;
+    info.grid_index = (uint32_t)lo; info.qstep = ojphgpu::rate_grid_qstep((uint32_t)lo);
+    info.bytes = (uint64_t)size[(size_t)lo];
+    info.bytes_finer = hi < N ? (uint64_t)size[(size_t)hi] : 0;
+    return OJPHGPU_OK;
+  }
+  int feed(int64_t s)
+  {
+    if (phase == ENDED || pending < 0) return OJPHGPU_E_INVALID;
+    const int j = pending;
+    pending = -1;
+    info.passes++;
+    if (s < 0) { phase = ENDED; return s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s; }
     size[(size_t)j] = s;
     if (model) { const double p = model->bytes((uint32_t)j); scale = p > 0 ? (double)s / p : 1.0; }
     if ((uint64_t)s <= max_bytes) lo = j; else hi = j;
-    return true;
-  };
-  if (hint >= 0) {
-    if (!trial(hint)) return err;
-    // the neighbour the result points to and, when that one points the same way, the next index on: an answer one step
-    // from the hint is certified by three trials whatever the model makes of the frame.  Each only where the index
-    // exists and the certificate is still open.
-    const int dir = lo == hint ? 1 : -1;
-    for (int k = 1; k <= 2 && hi - lo > 1; ++k) {
-      const int nb = hint + k * dir;
-      if (nb <= lo || nb >= hi) break;
-      if (!trial(nb)) return err;
-      if ((dir > 0) != (lo == nb)) break;                    // it turned round: the certificate, or a table that is not monotone
+    if (phase == HINT_FED) { dir = lo == hint ? 1 : -1; k = 1; phase = NEIGHBOUR; }
+    else if (phase == NEIGHBOUR) {
+      if ((dir > 0) != (lo == j)) phase = MAIN;              // it turned round: the certificate, or a table that is not monotone
+      else ++k;
     }
+    return OJPHGPU_OK;
   }
-  while (hi - lo > 1) {
-    int j = (lo + hi) / 2;
-    if (model && passes < 6) {
-      // the finest candidate the rescaled model lets fit (its prediction grows with j: bisection over the candidates)
-      int a = lo, b = hi;                                    // a fits (or is the end), b does not
-      while (b - a > 1) { const int m = (a + b) / 2; if (scale * model->bytes((uint32_t)m) <= (double)max_bytes) a = m; else b = m; }
-      j = std::min(std::max(a, lo + 1), hi - 1);
-    }
-    if (!trial(j)) return err;
-  }
-  if (lo < 0) return OJPHGPU_E_BUDGET;
-  out->grid_index = (uint32_t)lo; out->qstep = rate_grid_qstep((uint32_t)lo);
-  out->bytes = (uint64_t)size[(size_t)lo];
-  out->bytes_finer = hi < N ? (uint64_t)size[(size_t)hi] : 0;
+};
+
+namespace ojphgpu {
+
+int rate_stepper_create(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_rate_stepper** out)
+{
+  if (!out || hint < -1 || hint >= (int)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  ojphgpu_rate_stepper* st = new ojphgpu_rate_stepper();
+  st->start(T, hist, max_bytes, hint);
+  *out = st;
   return OJPHGPU_OK;
+}
+
+// the one search there is: a loop over the stepper
+int rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out)
+{
+  if (!fn || !out || hint < -1 || hint >= (int)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  ojphgpu_rate_stepper st;
+  st.start(T, hist, max_bytes, hint);
+  for (;;) {
+    uint32_t j = 0;
+    int rc = st.next(&j);
+    if (rc == 1) rc = st.feed(fn(user, j)); else { *out = st.info; return rc; }
+    if (rc) { *out = st.info; return rc; }
+  }
 }
 
 }  // namespace ojphgpu
@@ -198,6 +248,43 @@ extern "C" int ojphgpu_rate_search_hint(const ojphgpu_plan* plan, const uint32_t
     return rate_search(T, hist, max_bytes, hint, fn, user, out);
   });
 }
+
+extern "C" int ojphgpu_rate_stepper_create(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
+                                           ojphgpu_rate_stepper** out)
+{
+  if (!plan || !out || hint < -1 || hint >= (int32_t)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  *out = nullptr;
+  return no_throw([&]() -> int {
+    ojphgpu_rate_stepper* st = new ojphgpu_rate_stepper();
+    struct Owner { ojphgpu_rate_stepper* p; ~Owner() { delete p; } } owner{ st };
+    const int rc = rate_table_build(plan->plan, st->own);
+    if (rc) return rc;
+    st->start(st->own, hist, max_bytes, hint);
+    *out = st; owner.p = nullptr;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_rate_stepper_next(ojphgpu_rate_stepper* st, uint32_t* j)
+{
+  if (!st || !j) return OJPHGPU_E_INVALID;
+  return no_throw([&] { return st->next(j); });
+}
+
+extern "C" int ojphgpu_rate_stepper_feed(ojphgpu_rate_stepper* st, int64_t size)
+{
+  if (!st) return OJPHGPU_E_INVALID;
+  return no_throw([&] { return st->feed(size); });
+}
+
+extern "C" int ojphgpu_rate_stepper_info(const ojphgpu_rate_stepper* st, ojphgpu_rate_info* out)
+{
+  if (!st || !out) return OJPHGPU_E_INVALID;
+  *out = st->info;
+  return OJPHGPU_OK;
+}
+
+extern "C" void ojphgpu_rate_stepper_destroy(ojphgpu_rate_stepper* st) { delete st; }
 
 extern "C" int ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
                                    ojphgpu_rate_info* out)
@@ -294,7 +381,7 @@ extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hi
     RateTable T;
     const int rc = rate_table_build(plan->plan, T);
     if (rc) return rc;
-    Model m(T, hist);
+    RateModel m(T, hist);
     for (uint32_t j = 0; j < OJPHGPU_RATE_GRID; ++j) out[j] = m.bytes(j);
     return OJPHGPU_OK;
   });

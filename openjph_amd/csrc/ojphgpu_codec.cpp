@@ -19,12 +19,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "ht_tables.h"
 #include "ojph_plan.h"
+#include "ojph_pool.h"
 
 using namespace ojphgpu;
 
@@ -91,8 +93,10 @@ extern "C" int ojphgpu_encoder_create_batch(const ojphgpu_plan* plan, int device
 // The block descriptors of the encoder's blocks with their scratch slots, and the compacted output with its regions (e->
 // out_cap, nreg, h_regions, counters_bytes).  band_kmax: per band of the plan, the K_max the slots and the output are sized
 // for where it exceeds the plan's own (an encoder with a byte budget: the finest step its search may visit); null = the plan's.
-static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, std::vector<ojphgpu_cb_desc>& bd, uint64_t& scratch_total)
+static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, std::vector<ojphgpu_cb_desc>& bd, uint64_t& scratch_total,
+                                 bool* clamped = nullptr)
 {
+  if (clamped) *clamped = false;
   const Plan& P = *e->P;
   const uint32_t nframes = e->nframes;
   bd.assign(e->block_ids.size(), ojphgpu_cb_desc());
@@ -135,6 +139,7 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
   uint32_t kmax_all = 0;
   for (size_t b = 0; b < P.bands.size(); ++b) kmax_all = std::max(kmax_all, band_kmax ? std::max(P.bands[b].K_max, band_kmax[b]) : P.bands[b].K_max);
   uint64_t cap = kmax_all > 20 ? scratch_bytes : std::min<uint64_t>(scratch_bytes, samples * 3 + (1u << 20));
+  if (clamped && cap > 0xFFFFFF00ull) *clamped = true;
   cap = std::min<uint64_t>(cap, 0xFFFFFF00ull);
   // ... split into regions (see ojphgpu_objects.h): a region holds the sum of its own blocks' shares of that bound
   {
@@ -150,7 +155,10 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
     e->h_regions.assign(2 * (size_t)R, 0);
     for (uint32_t r = 0; r < R; ++r) {
       const uint64_t c = (rc[r] + (1u << 16) + 255) & ~(uint64_t)255;
-      if (total + c > 0xFFFFFF00ull) { R = 0; break; }      // the byte offsets are 32 bits wide: one clamped cursor, as before
+      if (total + c > 0xFFFFFF00ull) {                       // the byte offsets are 32 bits wide: one clamped cursor, as before
+        if (clamped) *clamped = true;
+        R = 0; break;
+      }
       e->h_regions[2 * r] = (uint32_t)total; e->h_regions[2 * r + 1] = (uint32_t)c;
       total += c;
     }
@@ -387,8 +395,9 @@ extern "C" int ojphgpu_encoder_coded_bytes(ojphgpu_encoder* e, uint64_t* bytes)
 // table of frame `frame`
 static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu_coded_block>& cb)
 {
-  const Plan& P = e->searches() ? e->rate->plan->plan : *e->P;   // (a byte budget, a quality target: the plan at the step the search chose)
   if (frame >= e->nframes) return OJPHGPU_E_INVALID;
+  // (a byte budget, a quality target: the plan at the step the search chose -- of a batch, for this frame)
+  const Plan& P = !e->searches() ? *e->P : e->nframes > 1 ? e->rate->frame_plan[frame]->plan : e->rate->plan->plan;
   if (!e->fetched) {
     int rc = ojphgpu_encoder_coded_bytes(e, &e->nbytes);
     if (rc) return rc;
@@ -421,6 +430,7 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
 }
 
 static int encoder_rate_search(ojphgpu_encoder* e);
+static int encoder_rate_search_batch(ojphgpu_encoder* e);
 static int encoder_quality_search(ojphgpu_encoder* e);
 
 extern "C" int ojphgpu_encoder_finish(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len)
@@ -433,18 +443,21 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
 {
   if (!e || !out_len || !e->ran) return OJPHGPU_E_INVALID;
   if (e->tiles.first != 0 || e->tiles.count != e->P->tiles.size()) return OJPHGPU_E_INVALID;   // use _finish_tiles
+  if (frame >= e->nframes) return OJPHGPU_E_INVALID;
+  const bool batch_budgets = e->max_bytes && e->nframes > 1;
   return no_throw([&]() -> int {
   std::vector<ojphgpu_coded_block> cb;
   const bool tm = getenv("OJPHGPU_TIMING") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
-  int rc = e->quality_on ? encoder_quality_search(e) : e->max_bytes ? encoder_rate_search(e) : OJPHGPU_OK;
+  int rc = e->quality_on ? encoder_quality_search(e) : batch_budgets ? encoder_rate_search_batch(e) : e->max_bytes ? encoder_rate_search(e) : OJPHGPU_OK;
   if (rc) return rc;
+  if (batch_budgets && e->rate->frame_rc[frame]) return e->rate->frame_rc[frame];   // (OJPHGPU_E_BUDGET: this frame's alone)
   if (e->searches()) t0 = now();
   rc = encoder_fetch(e, frame, cb);
   if (rc) return rc;
   auto t1 = now();
-  rc = ojphgpu_t2_write(e->searches() ? e->rate->plan : e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
+  rc = ojphgpu_t2_write(!e->searches() ? e->handle : batch_budgets ? e->rate->frame_plan[frame] : e->rate->plan, e->h_out.p, cb.data(), h_out, cap, out_len);
   if (e->max_bytes) e->rate->final_ms = std::chrono::duration<double, std::milli>(now() - t0).count();
   if (e->quality_on) e->quality->final_ms += std::chrono::duration<double, std::milli>(now() - t0).count();
   if (tm) fprintf(stderr, "ojphgpu: finish frame %u: D2H %.2f ms, Tier-2 %.2f ms\n", frame,
@@ -524,10 +537,10 @@ static int encoder_restore_descs(ojphgpu_encoder* e)
   return OJPHGPU_OK;
 }
 
-static bool encoder_may_search(const ojphgpu_encoder* e)
+static bool encoder_may_search(const ojphgpu_encoder* e, bool batch = false)
 {
   const Plan& P = *e->P;
-  return e->nframes == 1 && e->tiles.first == 0 && e->tiles.count == P.tiles.size() && !e->o_out && rate_plan_ok(P);
+  return (batch || e->nframes == 1) && e->tiles.first == 0 && e->tiles.count == P.tiles.size() && !e->o_out && rate_plan_ok(P);
 }
 
 static int encoder_rate_setup(ojphgpu_encoder* e);
@@ -537,13 +550,30 @@ extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes
   if (!e) return OJPHGPU_E_INVALID;
   if (max_bytes == 0) {
     if (e->max_bytes && e->rate) { const int rc = encoder_restore_descs(e); if (rc) return rc; }
-    e->max_bytes = 0;
+    e->max_bytes = 0; e->budgets.clear();
     return OJPHGPU_OK;
   }
-  if (!encoder_may_search(e) || e->quality_on) return OJPHGPU_E_INVALID;
+  if (!encoder_may_search(e) || e->quality_on) return OJPHGPU_E_INVALID;   // (a batch encoder: ojphgpu_encoder_set_budgets, also for equal budgets)
   if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
   e->max_bytes = max_bytes; e->ran = false;
   return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_set_budgets(ojphgpu_encoder* e, const uint64_t* max_bytes, uint32_t n)
+{
+  if (!e || !max_bytes || n != e->nframes) return OJPHGPU_E_INVALID;
+  if (e->nframes == 1) return ojphgpu_encoder_set_budget(e, max_bytes[0]);
+  uint32_t zeros = 0;
+  for (uint32_t f = 0; f < n; ++f) zeros += max_bytes[f] == 0;
+  if (zeros == n) return ojphgpu_encoder_set_budget(e, 0);
+  if (zeros) return OJPHGPU_E_INVALID;
+  if (!encoder_may_search(e, true) || e->quality_on) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
+    e->budgets.assign(max_bytes, max_bytes + n);
+    e->max_bytes = max_bytes[0]; e->ran = false;
+    return OJPHGPU_OK;
+  });
 }
 
 // what a searching encoder needs (the first ojphgpu_encoder_set_budget / _set_quality): the quantisation of every step, the
@@ -559,13 +589,16 @@ static int encoder_rate_setup(ojphgpu_encoder* e)
     int rc = rate_table_build(P, R->table);
     if (rc) return rc;
     R->plan = new ojphgpu_plan{ P };
+    const uint32_t nframes = e->nframes;
+    if ((uint64_t)P.bands.size() * nframes > 0xFFFFFFFFull) return OJPHGPU_E_INVALID;   // (the slots are 32 bits wide)
     std::vector<ojphgpu_stats_desc> sd;
-    for (size_t i = 0; i < P.bands.size(); ++i) {
-      const Band& B = P.bands[i];
-      if (B.empty) continue;
-      sd.push_back(ojphgpu_stats_desc{ B.plane_off, B.pitch, B.r.w, B.r.h, (uint32_t)i });
-      R->stats_max_w = std::max(R->stats_max_w, B.r.w); R->stats_max_h = std::max(R->stats_max_h, B.r.h);
-    }
+    for (uint32_t f = 0; f < nframes; ++f)                    // frame-major: the histograms are [frames][bands][bins]
+      for (size_t i = 0; i < P.bands.size(); ++i) {
+        const Band& B = P.bands[i];
+        if (B.empty) continue;
+        sd.push_back(ojphgpu_stats_desc{ B.plane_off + (uint64_t)f * P.arena_elems, B.pitch, B.r.w, B.r.h, (uint32_t)(f * P.bands.size() + i) });
+        R->stats_max_w = std::max(R->stats_max_w, B.r.w); R->stats_max_h = std::max(R->stats_max_h, B.r.h);
+      }
     R->n_stats = (uint32_t)sd.size();
     std::vector<uint32_t> cls(e->block_ids.size());
     for (size_t i = 0; i < cls.size(); ++i) cls[i] = R->table.band_class[P.blocks[e->block_ids[i]].band];
@@ -576,20 +609,31 @@ static int encoder_rate_setup(ojphgpu_encoder* e)
     for (size_t i = 0; i < kfine.size(); ++i) kfine[i] = R->table.quant[(size_t)(OJPHGPU_RATE_GRID - 1) * nc + R->table.band_class[i]].K_max;
     std::vector<ojphgpu_cb_desc>& bd = R->bd;
     uint64_t scratch_bytes = 0;
-    encoder_block_layout(e, kfine.data(), bd, scratch_bytes);
+    {
+      // A batch: the bound of all frames at the finest step has to fit the 32-bit byte cursor unclamped -- a clamped output
+      // could overflow in a fine trial, which the search takes as impossible.  Refused with the encoder as it was.
+      const uint32_t out_cap = e->out_cap, nreg = e->nreg; const size_t counters_bytes = e->counters_bytes;
+      const std::vector<uint32_t> regions = e->h_regions;
+      bool clamped = false;
+      encoder_block_layout(e, kfine.data(), bd, scratch_bytes, &clamped);
+      if (clamped && nframes > 1) {                           // fewer frames per batch
+        e->out_cap = out_cap; e->nreg = nreg; e->counters_bytes = counters_bytes; e->h_regions = regions;
+        return OJPHGPU_E_INVALID;
+      }
+    }
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->side) HIPCHK(hipStreamSynchronize(e->side));
     e->scratch.release(); e->out.release(); e->regions.release(); e->counters.release();
     if (e->scratch.alloc(scratch_bytes) || e->out.alloc(e->out_cap) || e->counters.alloc(e->counters_bytes) ||
         (e->nreg && e->regions.alloc(e->h_regions.size() * 4)) ||
-        R->stats_descs.alloc(sd.size() * sizeof(sd[0])) || R->hist.alloc(P.bands.size() * OJPHGPU_STATS_BINS * 4) ||
-        R->block_class.alloc(cls.size() * 4) || R->quant.alloc((size_t)nc * sizeof(BandQuant)))
+        R->stats_descs.alloc(sd.size() * sizeof(sd[0])) || R->hist.alloc(P.bands.size() * OJPHGPU_STATS_BINS * 4 * nframes) ||
+        R->block_class.alloc(cls.size() * 4) || R->quant.alloc((size_t)nc * sizeof(BandQuant) * nframes))
       return OJPHGPU_E_NOMEM;
     if (e->nreg) HIPCHK(hipMemcpy(e->regions.p, e->h_regions.data(), e->h_regions.size() * 4, hipMemcpyHostToDevice));
     if (!bd.empty()) HIPCHK(hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice));
     if (!sd.empty()) HIPCHK(hipMemcpy(R->stats_descs.p, sd.data(), sd.size() * sizeof(sd[0]), hipMemcpyHostToDevice));
     if (!cls.empty()) HIPCHK(hipMemcpy(R->block_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
-    R->h_hist.assign(P.bands.size() * OJPHGPU_STATS_BINS, 0);
+    R->h_hist.assign(P.bands.size() * OJPHGPU_STATS_BINS * nframes, 0);
     e->rate = R; owner.p = nullptr;
     e->ran = false;
     return OJPHGPU_OK;
@@ -678,10 +722,148 @@ static int encoder_rate_search(ojphgpu_encoder* e)
   return R.search_rc;
 }
 
+// The plan at grid index j for the frames of a batch, from the copies kept by visited index
+static ojphgpu_plan* encoder_plan_at(ojphgpu_encoder* e, uint32_t j)
+{
+  EncoderRate& R = *e->rate;
+  auto it = R.plans.find(j);
+  if (it != R.plans.end()) return it->second;
+  std::unique_ptr<ojphgpu_plan> q(new ojphgpu_plan{ *e->P });
+  if (!rate_apply_step(q->plan, rate_grid_qstep(j))) return nullptr;
+  return R.plans.emplace(j, q.release()).first->second;
+}
+
+// The search of the last run of a batch encoder, once: one stepper per frame, advanced together in rounds.  A round codes
+// every frame -- an open one at the index its stepper hands out, a certified one at its j*, one nothing fits at index 0 --
+// in the plain batch schedule, so the compacted output and its cursors are what a plain batch run leaves; the block lengths
+// come back once, and the layouts of the frames that measure (independent of each other) run on the pool.  Closed frames
+// are coded again in every later round: device time, accepted for that.  The rounds end when nobody measures and every
+// frame stands at its answer; then the device holds all frames as finish_frame writes them.
+static int encoder_rate_search_batch(ojphgpu_encoder* e)
+{
+  EncoderRate& R = *e->rate;
+  if (R.searched) return R.search_rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  R.wait_ms = 0;
+  auto run = [&]() -> int {
+    hipStream_t s = e->stream;
+    const uint32_t F = e->nframes, nc = R.table.nclasses, nb = (uint32_t)e->block_ids.size();
+    const size_t hist_per = e->P->bands.size() * OJPHGPU_STATS_BINS;
+    if (e->budgets.size() != F) return OJPHGPU_E_INVALID;
+    HIPCHK(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    struct Steppers { std::vector<ojphgpu_rate_stepper*> v; ~Steppers() { for (ojphgpu_rate_stepper* p : v) ojphgpu_rate_stepper_destroy(p); } } S;
+    S.v.assign(F, nullptr);
+    ojphgpu_rate_info none; memset(&none, 0, sizeof(none));
+    R.rounds = 0;
+    R.frame_rc.assign(F, OJPHGPU_E_INVALID); R.frame_info.assign(F, none); R.frame_plan.assign(F, nullptr);
+    for (uint32_t f = 0; f < F; ++f) {
+      const int rc = rate_stepper_create(R.table, &R.h_hist[f * hist_per], e->budgets[f], -1, &S.v[f]);
+      if (rc) return rc;
+    }
+    enum { IDLE = 0, TRIAL = 1, VERIFY = 2 };
+    std::vector<int> at(F, -1), measure(F, IDLE);            // the index a frame was coded at in the last round; what its layout is for
+    std::vector<char> open(F, 1);
+    std::vector<uint32_t> idx(F, 0), list;
+    std::vector<int64_t> sizes(F, 0);
+    std::vector<BandQuant> hq((size_t)F * nc);
+    for (;;) {
+      bool work = false;
+      for (uint32_t f = 0; f < F; ++f) {
+        measure[f] = IDLE;
+        if (open[f]) {
+          uint32_t j = 0;
+          const int rc = ojphgpu_rate_stepper_next(S.v[f], &j);
+          if (rc == 1) { idx[f] = j; measure[f] = TRIAL; }
+          else if (rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET) {
+            open[f] = 0; R.frame_rc[f] = rc;
+            (void)ojphgpu_rate_stepper_info(S.v[f], &R.frame_info[f]);
+            idx[f] = rc == OJPHGPU_OK ? R.frame_info[f].grid_index : 0;
+            // the last trial was j* + 1: j* is coded once more, counted and checked, as the single encoder does
+            if (rc == OJPHGPU_OK && at[f] != (int)idx[f]) { R.frame_info[f].passes++; measure[f] = VERIFY; }
+          } else return rc;
+        }
+        if (measure[f] != IDLE || at[f] != (int)idx[f]) work = true;
+      }
+      if (!work) break;
+      ++R.rounds;
+      if (R.plans.size() > 32)                                // (a sequence that wanders: keep what this round uses)
+        for (auto it = R.plans.begin(); it != R.plans.end();) {
+          if (std::find(idx.begin(), idx.end(), it->first) == idx.end()) { delete it->second; it = R.plans.erase(it); } else ++it;
+        }
+      for (uint32_t f = 0; f < F; ++f) {
+        if ((R.frame_plan[f] = encoder_plan_at(e, idx[f])) == nullptr) return OJPHGPU_E_INVALID;
+        std::copy(&R.table.quant[(size_t)idx[f] * nc], &R.table.quant[(size_t)idx[f] * nc] + nc, &hq[(size_t)f * nc]);
+      }
+      HIPCHK(hipMemcpyAsync(R.quant.p, hq.data(), hq.size() * sizeof(BandQuant), hipMemcpyHostToDevice, s));
+      int rc = requant_frames_launch(s, (ojphgpu_cb_desc*)e->cb_descs.p, nb, F, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p, nc);
+      if (rc) return rc;
+      BlockCoderRun coder{ e, (uint8_t*)e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nb * F, nullptr };
+      if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) return rc;
+      uint32_t status = 0;
+      const auto w0 = std::chrono::steady_clock::now();
+      const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
+      if (rbytes) HIPCHK(hipMemcpyAsync(e->h_results.data(), e->results.p, rbytes, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(&status, (uint32_t*)e->counters.p + 1, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+      e->fetched = false;
+      if (status) return OJPHGPU_E_OVERFLOW;                  // (cannot happen: the buffers hold the finest step's bound, unclamped)
+      list.clear();
+      for (uint32_t f = 0; f < F; ++f) { at[f] = (int)idx[f]; if (measure[f] != IDLE) list.push_back(f); }
+      parallel_for(list.size(), [&](size_t k) {
+        const uint32_t f = list[k];
+        const Plan& Q = R.frame_plan[f]->plan;
+        std::vector<ojphgpu_coded_block> cb;
+        ojphgpu_coded_blocks(Q, e->block_ids, e->h_results.data() + (size_t)f * nb, cb);
+        T2Layout L;
+        const int lrc = t2_layout_codestream(Q, cb.data(), L);
+        sizes[f] = lrc ? (int64_t)lrc : (int64_t)L.total;
+      });
+      for (uint32_t f : list) {
+        if (measure[f] == TRIAL) { if ((rc = ojphgpu_rate_stepper_feed(S.v[f], sizes[f])) != 0) return rc; }
+        else if (sizes[f] < 0) return (int)sizes[f];
+        else if ((uint64_t)sizes[f] != R.frame_info[f].bytes) return OJPHGPU_E_HIP;   // the same blocks at the same step: anything else is a fault
+      }
+    }
+    return OJPHGPU_OK;
+  };
+  R.search_rc = no_throw(run);
+  if (R.search_rc) R.frame_rc.assign(e->nframes, R.search_rc);
+  R.searched = true;
+  R.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return R.search_rc;
+}
+
 extern "C" int ojphgpu_encoder_rate_info(ojphgpu_encoder* e, ojphgpu_rate_info* info)
 {
-  if (!e || !info || !e->rate || !e->rate->have_info) return OJPHGPU_E_INVALID;
+  if (!e || !info || !e->rate) return OJPHGPU_E_INVALID;
+  if (e->nframes > 1) {                                     // a batch: frame 0
+    const int rc = ojphgpu_encoder_rate_info_frame(e, 0, info);
+    return rc == OJPHGPU_E_BUDGET ? OJPHGPU_OK : rc;
+  }
+  if (!e->rate->have_info) return OJPHGPU_E_INVALID;
   *info = e->rate->info;
+  return OJPHGPU_OK;
+}
+
+// OJPHGPU_E_BUDGET: nothing fits that frame's budget (info: passes, first_guess)
+extern "C" int ojphgpu_encoder_rate_info_frame(ojphgpu_encoder* e, uint32_t frame, ojphgpu_rate_info* info)
+{
+  if (!e || !info || !e->rate || frame >= e->nframes) return OJPHGPU_E_INVALID;
+  if (e->nframes == 1) return ojphgpu_encoder_rate_info(e, info);
+  const EncoderRate& R = *e->rate;
+  if (!e->max_bytes || !R.searched || frame >= R.frame_rc.size() || (R.frame_rc[frame] != OJPHGPU_OK && R.frame_rc[frame] != OJPHGPU_E_BUDGET))
+    return OJPHGPU_E_INVALID;
+  *info = R.frame_info[frame];
+  return R.frame_rc[frame];
+}
+
+extern "C" int ojphgpu_encoder_rate_rounds(ojphgpu_encoder* e, uint32_t* rounds)
+{
+  if (!e || !rounds || !e->rate || !e->rate->searched || !e->max_bytes) return OJPHGPU_E_INVALID;
+  *rounds = e->nframes > 1 ? e->rate->rounds : e->rate->info.passes;
   return OJPHGPU_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <vector>
 
 #include "dwt_region.h"
@@ -465,8 +466,17 @@ struct EncoderRate {
   bool have_info = false;
   ojphgpu_rate_info info;
   double search_ms = 0, wait_ms = 0, final_ms = 0;
+  // A batch encoder (ojphgpu_encoder_set_budgets): stats_descs / hist / h_hist / quant hold a part per frame, and the search
+  // of a run leaves per frame its verdict (OJPHGPU_OK, OJPHGPU_E_BUDGET), what it found and the plan at its step.  The plan
+  // copies are kept by grid index across runs -- the frames of a sequence settle on a handful of indices.
+  std::vector<int> frame_rc;
+  std::vector<ojphgpu_rate_info> frame_info;
+  std::vector<ojphgpu_plan*> frame_plan;           // (owned by plans)
+  std::map<uint32_t, ojphgpu_plan*> plans;
+  uint32_t rounds = 0;
   ~EncoderRate() {
     for (DeviceBuf* b : { &stats_descs, &hist, &block_class, &quant }) b->release();
+    for (auto& kv : plans) delete kv.second;
     delete plan;
   }
 };
@@ -529,6 +539,7 @@ struct ojphgpu_encoder {
   DeviceBuf regions;
   size_t counters_bytes = 16;
   uint64_t max_bytes = 0;                          // != 0: every frame is coded to this budget
+  std::vector<uint64_t> budgets;                   // a batch encoder's: one per frame (max_bytes = the first, as the switch)
   EncoderRate* rate = nullptr;
   bool quality_on = false; uint64_t max_sse = 0;   // every frame is coded to this quality target (never together with a budget)
   EncoderQuality* quality = nullptr;

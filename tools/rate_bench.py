@@ -15,7 +15,16 @@ no search; (c) codec.Encoder(max_bytes) frame by frame from host memory -- what 
 its frames are uploaded from pageable numpy memory (Encoder.encode), the pipes' from their pinned slots.
 Prints one JSON line per budget: j*, mean passes per frame, and per contender the frames/s of every round, their median
 and their spread (max - min) / median.
-  python tools/rate_bench.py --pipe [--rounds 3] [--frames 24] [--rows 4320]"""
+  python tools/rate_bench.py --pipe [--rounds 3] [--frames 24] [--rows 4320]
+
+--batch B: the budgets of a batch encoder (Encoder(frames=B, budgets=...)): B 4K 4:4:4 12-bit frames (the C7 family, seed
+1234 + frame; 16-bit containers in HBM), every frame at the same budget of 0.73, 0.2 and 0.05 bytes per sample.  Per budget
+three contenders take turns, `--runs` rounds after `--warmup`: (a) the batch with budgets, run_device + finish of every
+frame; (b) the same frames through B budgeted single-frame encodes, one after the other -- what a caller has without the
+batch form; (c) a plain batch encode at the fixed step of the median j* -- the device and download cost of one coding of
+the batch.  The bytes of (a) and (b) are compared.  Prints one JSON line per budget: the j* of the frames, the rounds of
+the batch's search and the sum of the frames' passes, median ms of (a) (b) (c), the batch's search / device wait.
+  python tools/rate_bench.py --batch 8 [--runs 10] [--warmup 3] [--rows 2160]"""
 import argparse
 import json
 import os
@@ -75,6 +84,76 @@ def pipe_bench(a):
         print(json.dumps(out), flush=True)
 
 
+def batch_bench(a):
+    import torch
+    from openjph_amd import codec
+    from openjph_amd import plan as planmod
+    from openjph_amd.plan import make_params
+    from tests import synth
+    B = a.batch
+    rows = min(a.rows, 2160)
+    frames = np.stack([synth.survey_c7(seed=1234 + f)[:, :rows].astype(np.uint16) for f in range(B)])
+    _, nc, h, w = frames.shape
+    samples = frames[0].size
+    d_batch = torch.from_numpy(frames.view(np.int16)).cuda()
+    del frames
+
+    def params(qstep):
+        return make_params(w, h, nc, bit_depth=12, reversible=False, qstep=qstep)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    batch = codec.Encoder(params(0.001), frames=B)
+    single = codec.Encoder(params(0.001))
+    plain = {}
+
+    def run_batch(enc):
+        enc.run_device(d_batch)
+        return [enc.finish(f) for f in range(B)]
+
+    def run_singles():
+        out, passes = [], 0
+        for f in range(B):
+            single.run_device(d_batch[f])
+            out.append(single.finish())
+            passes += single.rate_info()["passes"]
+        return out, passes
+
+    for bps in BPS:
+        budget = int(samples * bps)
+        batch.set_budgets([budget] * B)
+        single.set_budget(budget)
+        t = {"batch": [], "singles": [], "plain": []}
+        for i in range(a.warmup + a.runs):
+            ms_batch, cs = timed(lambda: run_batch(batch))
+            infos, rounds, timing = batch.rate_info(), batch.rate_rounds(), batch.rate_timing()
+            ms_singles, (cs_single, single_passes) = timed(run_singles)
+            assert cs == cs_single and all(len(c) <= budget for c in cs)
+            jmed = sorted(x["grid_index"] for x in infos)[B // 2]
+            if jmed not in plain:
+                plain[jmed] = codec.Encoder(params(planmod.rate_grid_qstep(jmed)), frames=B)
+            ms_plain, _ = timed(lambda: run_batch(plain[jmed]))
+            if i >= a.warmup:
+                t["batch"].append(ms_batch); t["singles"].append(ms_singles); t["plain"].append(ms_plain)
+        med = {k: round(float(np.median(v)), 3) for k, v in t.items()}
+        passes = sum(x["passes"] for x in infos)
+        assert passes == single_passes
+        print(json.dumps(dict(
+            frames="%d x c7 %dx%dx%d 12-bit, 16-bit containers" % (B, w, h, nc), bytes_per_sample=bps, budget=budget,
+            grid_index=[x["grid_index"] for x in infos], bytes=[x["bytes"] for x in infos], rounds=rounds, sum_passes=passes,
+            ms_batch_budgets=med["batch"], ms_single_encodes=med["singles"], ms_plain_batch_fixed_step=med["plain"], plain_batch_grid_index=jmed,
+            singles_over_batch=round(med["singles"] / med["batch"], 3),
+            Gsamples_s_batch=round(B * samples / med["batch"] / 1e6, 2), Gsamples_s_singles=round(B * samples / med["singles"] / 1e6, 2),
+            search_ms=round(timing["search_ms"], 3), round_ms=round(timing["search_ms"] / rounds, 3),
+            round_device_wait_ms=round(timing["wait_ms"] / rounds, 3), round_host_ms=round((timing["search_ms"] - timing["wait_ms"]) / rounds, 3))),
+            flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10)
@@ -84,9 +163,12 @@ def main():
     ap.add_argument("--pipe", action="store_true", help="the budget in the encoder pipe, from host memory")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=24)
+    ap.add_argument("--batch", type=int, default=0, help="B: the budgets of a batch encoder of B 4K frames against B single encodes")
     a = ap.parse_args()
     if a.pipe:
         return pipe_bench(a)
+    if a.batch:
+        return batch_bench(a)
     import torch
     from openjph_amd import codec
     from openjph_amd import plan as planmod
