@@ -725,8 +725,8 @@ int  ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_
  * OJPHGPU_E_INVALID.  hist may be NULL (the hinted trials, then halving). */
 int  ojphgpu_rate_search_hint(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
                               ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);
-/* The same search in steps, for callers whose measurements are shared (the batch encoder below advances one per frame
- * over common launches): _next hands out the index to measure -- 1: measure size(*j) and _feed it; 0: certified, _info holds
+/* The same search in steps, for callers whose measurements are shared (the rounds below advance one per frame over
+ * common launches): _next hands out the index to measure -- 1: measure size(*j) and _feed it; 0: certified, _info holds
  * the answer; OJPHGPU_E_BUDGET: size(0) > max_bytes (_info: passes, first_guess) -- and _feed takes the size of the index
  * _next handed out; a size < 0 ends the stepper and comes back as it is.  ojphgpu_rate_search_hint is a loop over this:
  * the indices asked, passes, first_guess, the result and the codes are the same.  hist / hint as there; the histograms
@@ -738,6 +738,27 @@ int  ojphgpu_rate_stepper_next(ojphgpu_rate_stepper* st, uint32_t* j);
 int  ojphgpu_rate_stepper_feed(ojphgpu_rate_stepper* st, int64_t size);
 int  ojphgpu_rate_stepper_info(const ojphgpu_rate_stepper* st, ojphgpu_rate_info* out);
 void ojphgpu_rate_stepper_destroy(ojphgpu_rate_stepper* st);
+/* The searches of the `frames` frames of one encoder run, advanced together in ROUNDS over shared measurements, host only:
+ * what ojphgpu_encoder_finish* drives for any frame count, for callers and tests that bring sizes of their own.  A stepper
+ * per frame: hist = [frames][bands of the plan][OJPHGPU_STATS_BINS] (NULL: no model), max_bytes[frames], one hint for all.
+ * _next -- 1: a round; code EVERY frame f at idx[f] -- an open frame's the index its stepper hands out, a certified frame's
+ * its j*, a frame nothing fits index 0 -- and _feed sizes[f] = size(idx[f]) of the frames with measures[f] != 0 (1: a trial
+ * of the frame's search; 2: j* coded once more because the frame's last trial was not j*, counted in its passes; the size
+ * must be the one measured before, anything else is OJPHGPU_E_HIP); sizes of the other frames are not read.  0: the end
+ * -- nobody measures and every frame was coded at its index in the last round.  A size < 0 ends the search and comes back
+ * as it is, as does a stepper's error.  _frame: a closed frame's verdict, OJPHGPU_OK or OJPHGPU_E_BUDGET (info: passes,
+ * first_guess), and what ojphgpu_rate_search_hint would report for it -- the same indices in the same order, passes one
+ * higher exactly when its j* was coded once more; OJPHGPU_E_INVALID while the frame is open or after the search failed.
+ * _count: rounds handed out so far; one frame: its passes.  At most 17 rounds.  OJPHGPU_E_INVALID: what
+ * ojphgpu_rate_stepper_create refuses, frames == 0; _next after the end or with a round still out, _feed without one. */
+typedef struct ojphgpu_rate_rounds ojphgpu_rate_rounds;
+int  ojphgpu_rate_rounds_create(const ojphgpu_plan* plan, const uint32_t* hist, const uint64_t* max_bytes, uint32_t frames,
+                                int32_t hint, ojphgpu_rate_rounds** out);
+int  ojphgpu_rate_rounds_next(ojphgpu_rate_rounds* r, uint32_t* idx, uint8_t* measures);      /* idx[frames], measures[frames] */
+int  ojphgpu_rate_rounds_feed(ojphgpu_rate_rounds* r, const int64_t* sizes);                  /* sizes[frames] */
+int  ojphgpu_rate_rounds_frame(const ojphgpu_rate_rounds* r, uint32_t frame, ojphgpu_rate_info* info);
+int  ojphgpu_rate_rounds_count(const ojphgpu_rate_rounds* r, uint32_t* rounds);
+void ojphgpu_rate_rounds_destroy(ojphgpu_rate_rounds* r);
 /* the model alone: predicted bytes of every grid index, out[OJPHGPU_RATE_GRID] (what tools/rate_bench.py reports) */
 int  ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out);
 
@@ -751,7 +772,10 @@ int  ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double
  * the array call below, and callers rely on this refusal.  The per-block scratch slots and the output buffer are
  * re-sized for the finest step of the grid on the first call. */
 int  ojphgpu_encoder_set_budget(ojphgpu_encoder* enc, uint64_t max_bytes);
-/* what the last budgeted ojphgpu_encoder_finish* found (OJPHGPU_E_INVALID before one); a batch encoder: for frame 0 */
+/* What the budgeted ojphgpu_encoder_finish* of the LAST run found, frame 0 of _rate_info_frame below; after
+ * OJPHGPU_E_BUDGET: OJPHGPU_OK with passes and first_guess.  OJPHGPU_E_INVALID: before the first budgeted finish; between a
+ * ojphgpu_encoder_run_device* and its finish (the run has not been searched: the previous run's answer is not handed out);
+ * with the budget switched off or a quality target set; after a search that ended with an error of its own. */
 int  ojphgpu_encoder_rate_info(ojphgpu_encoder* enc, ojphgpu_rate_info* info);
 /* A batch encoder (ojphgpu_encoder_create_batch) codes frame f of every following run to max_bytes[f]; n must be the
  * encoder's frame count (a single-frame encoder: n == 1, exactly ojphgpu_encoder_set_budget).  All zeros switches the
@@ -765,8 +789,9 @@ int  ojphgpu_encoder_rate_info(ojphgpu_encoder* enc, ojphgpu_rate_info* info);
  * downloaded once.  finish_frame(f) then writes frame f: byte for byte the single-frame budgeted encode of that frame at
  * max_bytes[f].  A frame with size(0) > max_bytes[f] gets OJPHGPU_E_BUDGET from its own finish_frame only; the others
  * are written, and the encoder stays usable.  _rate_info_frame answers as the single encoder's _rate_info would for that
- * frame and budget (passes: the frame's own trials, plus one when the last of them was not j*); _rate_rounds gives the
- * rounds of the last search. */
+ * frame and budget (passes: the frame's own trials, plus one when the last of them was not j*) and is refused where
+ * _rate_info is; _rate_rounds gives the rounds of the last search (ojphgpu_rate_rounds above is its loop, for one frame
+ * and for many; a single-frame encoder: rounds == passes). */
 int  ojphgpu_encoder_set_budgets(ojphgpu_encoder* enc, const uint64_t* max_bytes, uint32_t n);
 int  ojphgpu_encoder_rate_info_frame(ojphgpu_encoder* enc, uint32_t frame, ojphgpu_rate_info* info);
 int  ojphgpu_encoder_rate_rounds(ojphgpu_encoder* enc, uint32_t* rounds);

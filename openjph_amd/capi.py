@@ -356,6 +356,12 @@ SIGNATURES = {
     "ojphgpu_rate_stepper_feed": (C.c_int, [C.c_void_p, C.c_int64]),
     "ojphgpu_rate_stepper_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_rate_stepper_destroy": (None, [C.c_void_p]),
+    "ojphgpu_rate_rounds_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ojphgpu_rate_rounds_next": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+    "ojphgpu_rate_rounds_feed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ojphgpu_rate_rounds_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RateInfo)]),
+    "ojphgpu_rate_rounds_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ojphgpu_rate_rounds_destroy": (None, [C.c_void_p]),
     "ojphgpu_band_requantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ojphgpu_frame_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ojphgpu_frame_error_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -1,7 +1,7 @@
 // openjph_amd/csrc/kernels_stats.hip -- what encoding to a byte budget (include/ojphgpu.h section 5b) adds on the device:
 //   band_stats_kernel  half-octave histograms of the magnitudes of the sub-band planes, one pass behind the forward DWT
-//   requant_kernel     the blocks' delta / K_max / missing_msbs of another base step into the block descriptors
-//   requant_frames_kernel  the same for the frames of a batch, every frame at a step of its own
+//   requant_frames_kernel  the blocks' delta / K_max / missing_msbs of another base step into the block descriptors, every
+//                      frame of the encoder at a step of its own
 //
 // The histogram pass reads 4 bytes per coefficient and writes next to nothing: its roof is HBM, like a DWT level's (what it
 // reaches of it: DESIGN 1.2), and the counting has to stay out of the loads' way.  The exponents of a real frame sit in ten to twenty bins, so an atomic per
@@ -120,17 +120,6 @@ __global__ __launch_bounds__(WG) void band_stats_kernel(const ojphgpu_stats_desc
   if (pending) flush(tab, t, hist, cur);
 }
 
-__global__ void requant_kernel(ojphgpu_cb_desc* __restrict__ descs, uint32_t n, const uint32_t* __restrict__ cls,
-                               const ojphgpu::BandQuant* __restrict__ q)
-{
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ojphgpu::BandQuant b = q[cls[i]];
-  descs[i].K_max = (uint8_t)b.K_max;
-  descs[i].missing_msbs = (uint8_t)(b.K_max - 1u);
-  descs[i].delta = b.delta;
-}
-
 // descriptor f * nb + i = block i of frame f: the class list is the frame shape's, the table holds a row per frame
 __global__ void requant_frames_kernel(ojphgpu_cb_desc* __restrict__ descs, uint32_t nb, uint32_t frames, const uint32_t* __restrict__ cls,
                                       const ojphgpu::BandQuant* __restrict__ q, uint32_t nclasses)
@@ -164,13 +153,6 @@ extern "C" int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_desc
 }
 
 namespace ojphgpu {
-
-int requant_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t n, const uint32_t* d_class, const BandQuant* d_quant)
-{
-  if (n == 0) return OJPHGPU_OK;
-  hipLaunchKernelGGL(requant_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d_descs, n, d_class, d_quant);
-  return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
-}
 
 int requant_frames_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, uint32_t frames, const uint32_t* d_class, const BandQuant* d_quant,
                           uint32_t nclasses)

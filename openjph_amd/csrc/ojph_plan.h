@@ -237,10 +237,12 @@ bool rate_plan_ok(const Plan& P);                            // irreversible thr
 bool rate_apply_step(Plan& Q, float qstep);
 int  rate_table_build(const Plan& P, RateTable& T);
 int  rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_size_fn fn, void* user, ojphgpu_rate_info* out);   // hint: -1 = none
-// the steppable form of the same search (ojphgpu_rate_stepper_*) over a table the caller keeps alive: the steppers of a batch share the encoder's
-int  rate_stepper_create(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_rate_stepper** out);
-int  requant_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t n, const uint32_t* d_class, const BandQuant* d_quant);
-// ... of a batch: block i of frame f (descriptor f * nb + i) from d_quant[f * nclasses + d_class[i]]
+// the searches of the frames of one encoder run, in rounds (ojphgpu_rate_rounds_*), over a table the caller keeps alive -- the
+// encoder's; hist: [frames][hist_per] words
+int  rate_rounds_create(const RateTable& T, const uint32_t* hist, size_t hist_per, const uint64_t* max_bytes, uint32_t frames, int hint,
+                        ojphgpu_rate_rounds** out);
+// the blocks' delta / K_max / missing_msbs of another step into the block descriptors: block i of frame f (descriptor
+// f * nb + i) from d_quant[f * nclasses + d_class[i]]
 int  requant_frames_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, uint32_t frames, const uint32_t* d_class, const BandQuant* d_quant,
                            uint32_t nclasses);
 

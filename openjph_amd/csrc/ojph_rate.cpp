@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "ojph_plan.h"
@@ -116,7 +117,7 @@ struct RateModel {
 
 }  // namespace ojphgpu
 
-// The search as a state machine, so that several of them can advance together over shared measurements (a batch encoder):
+// The search as a state machine, so that several of them can advance together over shared measurements (the rounds below):
 // _next hands out the index to measure, _feed takes its size.  hint: a grid index to try first (the previous frame's answer),
 // then its neighbour on the side the result points to and, if that points the same way, the index beyond it, before the
 // model proposes anything; -1 = none.  The hinted trials shrink the interval like any other and count among the six
@@ -124,9 +125,8 @@ struct RateModel {
 struct ojphgpu_rate_stepper {
   enum Phase { HINT, HINT_FED, NEIGHBOUR, MAIN, ENDED };
   static constexpr int N = OJPHGPU_RATE_GRID;
-  ojphgpu::RateTable own;                                    // of a stepper made from a plan; T points at it
-  const ojphgpu::RateTable* T = nullptr;
-  ojphgpu::RateModel* model = nullptr;
+  ojphgpu::RateTable own;                                    // of a stepper made from a plan: what its model reads
+  std::unique_ptr<ojphgpu::RateModel> model;
   uint64_t max_bytes = 0;
   int hint = -1;
   std::vector<int64_t> size = std::vector<int64_t>((size_t)N, -1);
@@ -140,12 +140,11 @@ struct ojphgpu_rate_stepper {
   ojphgpu_rate_info info;
   void start(const ojphgpu::RateTable& t, const uint32_t* hist, uint64_t budget, int h)
   {
-    T = &t; max_bytes = budget; hint = h;
-    if (hist) model = new ojphgpu::RateModel(t, hist);
+    max_bytes = budget; hint = h;
+    if (hist) model.reset(new ojphgpu::RateModel(t, hist));
     phase = h >= 0 ? HINT : MAIN;
     memset(&info, 0, sizeof(info));
   }
-  ~ojphgpu_rate_stepper() { delete model; }
   int hand(int j, uint32_t* out)
   {
     if (info.passes == 0) info.first_guess = (uint32_t)j;
@@ -200,14 +199,84 @@ struct ojphgpu_rate_stepper {
   }
 };
 
+// The searches of the F frames of one encoder run, advanced together in ROUNDS: one stepper per frame over shared
+// measurements.  A round codes every frame -- an open one at the index its stepper hands out, a certified one at its j*, one
+// nothing fits at index 0 -- and the sizes of the frames that measure come back together.  Closed frames are coded again
+// in every later round: device time, accepted for that.  Host only: whoever drives it does the coding (the encoder), or
+// reads the sizes from a table (the tests).  One frame is the single encoder's search: the indices of rate_search, then j*
+// once more when the last trial was not j*, and rounds == passes.
+struct ojphgpu_rate_rounds {
+  enum Measure { IDLE = 0, TRIAL = 1, VERIFY = 2 };          // what a frame's size of this round is for
+  ojphgpu::RateTable own;                                    // of an object made from a plan; the steppers point at it
+  std::vector<ojphgpu_rate_stepper> st;
+  std::vector<int> at, measure, rc;                          // the index a frame was coded at in the last round (-1: none); its verdict
+  std::vector<uint32_t> idx;                                 // the index a frame is coded at in this round
+  std::vector<char> open;
+  std::vector<ojphgpu_rate_info> info;
+  uint32_t rounds = 0;
+  bool out = false, ended = false; int failed = 0;           // a round is handed out and not fed; no round follows; what ended the search early
+  void start(const ojphgpu::RateTable& T, const uint32_t* hist, size_t hist_per, const uint64_t* budgets, uint32_t F, int hint)
+  {
+    st = std::vector<ojphgpu_rate_stepper>(F);
+    for (uint32_t f = 0; f < F; ++f) st[f].start(T, hist ? hist + f * hist_per : nullptr, budgets[f], hint);
+    at.assign(F, -1); measure.assign(F, IDLE); rc.assign(F, OJPHGPU_E_INVALID); idx.assign(F, 0); open.assign(F, 1);
+    ojphgpu_rate_info none; memset(&none, 0, sizeof(none));
+    info.assign(F, none);
+  }
+  int fail(int code) { ended = true; failed = code; return code; }
+  int next(uint32_t* idx_out, uint8_t* measures)
+  {
+    if (ended || out) return OJPHGPU_E_INVALID;
+    bool work = false;
+    for (size_t f = 0; f < st.size(); ++f) {
+      measure[f] = IDLE;
+      if (open[f]) {
+        uint32_t j = 0;
+        const int r = st[f].next(&j);
+        if (r == 1) { idx[f] = j; measure[f] = TRIAL; }
+        else if (r == OJPHGPU_OK || r == OJPHGPU_E_BUDGET) {
+          // A frame nothing fits stands at index 0 already: with lo == -1 the search can only end on the feed that set
+          // hi = 0, so its last trial was index 0 and it never causes a round of its own -- a single encoder's
+          // OJPHGPU_E_BUDGET costs the passes of its search and no more.
+          open[f] = 0; rc[f] = r; info[f] = st[f].info;
+          idx[f] = r == OJPHGPU_OK ? info[f].grid_index : 0;
+          // the last trial was j* + 1: j* is coded once more, counted and checked
+          if (r == OJPHGPU_OK && at[f] != (int)idx[f]) { info[f].passes++; measure[f] = VERIFY; }
+        } else return fail(r);
+      }
+      if (measure[f] != IDLE || at[f] != (int)idx[f]) work = true;
+    }
+    if (!work) { ended = true; return OJPHGPU_OK; }          // nobody measures and every frame stands at its index
+    ++rounds; out = true;
+    for (size_t f = 0; f < st.size(); ++f) { idx_out[f] = idx[f]; measures[f] = (uint8_t)measure[f]; }
+    return 1;
+  }
+  int feed(const int64_t* sizes)
+  {
+    if (ended || !out) return OJPHGPU_E_INVALID;
+    out = false;
+    for (size_t f = 0; f < st.size(); ++f) {
+      const int64_t s = sizes[f];
+      at[f] = (int)idx[f];
+      if (measure[f] == TRIAL) { const int r = st[f].feed(s); if (r) return fail(r); }
+      else if (measure[f] == VERIFY) {
+        if (s < 0) return fail(s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s);
+        if ((uint64_t)s != info[f].bytes) return fail(OJPHGPU_E_HIP);   // the same blocks at the same step: anything else is a fault
+      }
+    }
+    return OJPHGPU_OK;
+  }
+};
+
 namespace ojphgpu {
 
-int rate_stepper_create(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, int hint, ojphgpu_rate_stepper** out)
+int rate_rounds_create(const RateTable& T, const uint32_t* hist, size_t hist_per, const uint64_t* max_bytes, uint32_t frames, int hint,
+                       ojphgpu_rate_rounds** out)
 {
-  if (!out || hint < -1 || hint >= (int)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
-  ojphgpu_rate_stepper* st = new ojphgpu_rate_stepper();
-  st->start(T, hist, max_bytes, hint);
-  *out = st;
+  if (!out || !max_bytes || frames == 0 || hint < -1 || hint >= (int)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  std::unique_ptr<ojphgpu_rate_rounds> r(new ojphgpu_rate_rounds());
+  r->start(T, hist, hist_per, max_bytes, frames, hint);
+  *out = r.release();
   return OJPHGPU_OK;
 }
 
@@ -255,12 +324,11 @@ extern "C" int ojphgpu_rate_stepper_create(const ojphgpu_plan* plan, const uint3
   if (!plan || !out || hint < -1 || hint >= (int32_t)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
   *out = nullptr;
   return no_throw([&]() -> int {
-    ojphgpu_rate_stepper* st = new ojphgpu_rate_stepper();
-    struct Owner { ojphgpu_rate_stepper* p; ~Owner() { delete p; } } owner{ st };
+    std::unique_ptr<ojphgpu_rate_stepper> st(new ojphgpu_rate_stepper());
     const int rc = rate_table_build(plan->plan, st->own);
     if (rc) return rc;
     st->start(st->own, hist, max_bytes, hint);
-    *out = st; owner.p = nullptr;
+    *out = st.release();
     return OJPHGPU_OK;
   });
 }
@@ -285,6 +353,49 @@ extern "C" int ojphgpu_rate_stepper_info(const ojphgpu_rate_stepper* st, ojphgpu
 }
 
 extern "C" void ojphgpu_rate_stepper_destroy(ojphgpu_rate_stepper* st) { delete st; }
+
+extern "C" int ojphgpu_rate_rounds_create(const ojphgpu_plan* plan, const uint32_t* hist, const uint64_t* max_bytes, uint32_t frames, int32_t hint,
+                                          ojphgpu_rate_rounds** out)
+{
+  if (!plan || !out || !max_bytes || frames == 0 || hint < -1 || hint >= (int32_t)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  *out = nullptr;
+  return no_throw([&]() -> int {
+    std::unique_ptr<ojphgpu_rate_rounds> r(new ojphgpu_rate_rounds());
+    const int rc = rate_table_build(plan->plan, r->own);
+    if (rc) return rc;
+    r->start(r->own, hist, plan->plan.bands.size() * OJPHGPU_STATS_BINS, max_bytes, frames, hint);
+    *out = r.release();
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_rate_rounds_next(ojphgpu_rate_rounds* r, uint32_t* idx, uint8_t* measures)
+{
+  if (!r || !idx || !measures) return OJPHGPU_E_INVALID;
+  return no_throw([&] { return r->next(idx, measures); });
+}
+
+extern "C" int ojphgpu_rate_rounds_feed(ojphgpu_rate_rounds* r, const int64_t* sizes)
+{
+  if (!r || !sizes) return OJPHGPU_E_INVALID;
+  return no_throw([&] { return r->feed(sizes); });
+}
+
+extern "C" int ojphgpu_rate_rounds_frame(const ojphgpu_rate_rounds* r, uint32_t frame, ojphgpu_rate_info* info)
+{
+  if (!r || !info || frame >= r->st.size() || r->failed || r->open[frame]) return OJPHGPU_E_INVALID;
+  *info = r->info[frame];
+  return r->rc[frame];
+}
+
+extern "C" int ojphgpu_rate_rounds_count(const ojphgpu_rate_rounds* r, uint32_t* rounds)
+{
+  if (!r || !rounds) return OJPHGPU_E_INVALID;
+  *rounds = r->rounds;
+  return OJPHGPU_OK;
+}
+
+extern "C" void ojphgpu_rate_rounds_destroy(ojphgpu_rate_rounds* r) { delete r; }
 
 extern "C" int ojphgpu_rate_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
                                    ojphgpu_rate_info* out)

@@ -350,7 +350,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
   if (e->quality_on) {                                      // the search reads the planes in the arena and the caller's frame
     T.finish(s);
     e->quality->frame = d_image; e->quality->container = container;
-    e->rate->searched = false; e->rate->at = -1;
+    e->rate->searched = false;
     e->ran = true; e->fetched = false;
     return OJPHGPU_OK;
   }
@@ -362,7 +362,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     if (rc) return rc;
     T.end(sp, s);
     T.finish(s);
-    R.searched = false; R.at = -1;
+    R.searched = false;
     e->ran = true; e->fetched = false;
     return OJPHGPU_OK;
   }
@@ -396,8 +396,8 @@ extern "C" int ojphgpu_encoder_coded_bytes(ojphgpu_encoder* e, uint64_t* bytes)
 static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu_coded_block>& cb)
 {
   if (frame >= e->nframes) return OJPHGPU_E_INVALID;
-  // (a byte budget, a quality target: the plan at the step the search chose -- of a batch, for this frame)
-  const Plan& P = !e->searches() ? *e->P : e->nframes > 1 ? e->rate->frame_plan[frame]->plan : e->rate->plan->plan;
+  // (a byte budget, a quality target: the plan at the step the search chose for this frame)
+  const Plan& P = e->searches() ? e->rate->frame_plan[frame]->plan : *e->P;
   if (!e->fetched) {
     int rc = ojphgpu_encoder_coded_bytes(e, &e->nbytes);
     if (rc) return rc;
@@ -430,7 +430,6 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
 }
 
 static int encoder_rate_search(ojphgpu_encoder* e);
-static int encoder_rate_search_batch(ojphgpu_encoder* e);
 static int encoder_quality_search(ojphgpu_encoder* e);
 
 extern "C" int ojphgpu_encoder_finish(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len)
@@ -444,21 +443,22 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
   if (!e || !out_len || !e->ran) return OJPHGPU_E_INVALID;
   if (e->tiles.first != 0 || e->tiles.count != e->P->tiles.size()) return OJPHGPU_E_INVALID;   // use _finish_tiles
   if (frame >= e->nframes) return OJPHGPU_E_INVALID;
-  const bool batch_budgets = e->max_bytes && e->nframes > 1;
   return no_throw([&]() -> int {
   std::vector<ojphgpu_coded_block> cb;
   const bool tm = getenv("OJPHGPU_TIMING") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
-  int rc = e->quality_on ? encoder_quality_search(e) : batch_budgets ? encoder_rate_search_batch(e) : e->max_bytes ? encoder_rate_search(e) : OJPHGPU_OK;
+  const bool budgets = !e->budgets.empty();
+  int rc = e->quality_on ? encoder_quality_search(e) : budgets ? encoder_rate_search(e) : OJPHGPU_OK;
   if (rc) return rc;
-  if (batch_budgets && e->rate->frame_rc[frame]) return e->rate->frame_rc[frame];   // (OJPHGPU_E_BUDGET: this frame's alone)
+  ojphgpu_rate_info info;
+  if (budgets && (rc = ojphgpu_rate_rounds_frame(e->rate->rounds, frame, &info)) != 0) return rc;   // (OJPHGPU_E_BUDGET: this frame's alone)
   if (e->searches()) t0 = now();
   rc = encoder_fetch(e, frame, cb);
   if (rc) return rc;
   auto t1 = now();
-  rc = ojphgpu_t2_write(!e->searches() ? e->handle : batch_budgets ? e->rate->frame_plan[frame] : e->rate->plan, e->h_out.p, cb.data(), h_out, cap, out_len);
-  if (e->max_bytes) e->rate->final_ms = std::chrono::duration<double, std::milli>(now() - t0).count();
+  rc = ojphgpu_t2_write(e->searches() ? e->rate->frame_plan[frame] : e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
+  if (budgets) e->rate->final_ms = std::chrono::duration<double, std::milli>(now() - t0).count();
   if (e->quality_on) e->quality->final_ms += std::chrono::duration<double, std::milli>(now() - t0).count();
   if (tm) fprintf(stderr, "ojphgpu: finish frame %u: D2H %.2f ms, Tier-2 %.2f ms\n", frame,
                   std::chrono::duration<double, std::milli>(t1 - t0).count(),
@@ -537,10 +537,10 @@ static int encoder_restore_descs(ojphgpu_encoder* e)
   return OJPHGPU_OK;
 }
 
-static bool encoder_may_search(const ojphgpu_encoder* e, bool batch = false)
+static bool encoder_may_search(const ojphgpu_encoder* e)
 {
   const Plan& P = *e->P;
-  return (batch || e->nframes == 1) && e->tiles.first == 0 && e->tiles.count == P.tiles.size() && !e->o_out && rate_plan_ok(P);
+  return e->tiles.first == 0 && e->tiles.count == P.tiles.size() && !e->o_out && rate_plan_ok(P);
 }
 
 static int encoder_rate_setup(ojphgpu_encoder* e);
@@ -549,29 +549,26 @@ extern "C" int ojphgpu_encoder_set_budget(ojphgpu_encoder* e, uint64_t max_bytes
 {
   if (!e) return OJPHGPU_E_INVALID;
   if (max_bytes == 0) {
-    if (e->max_bytes && e->rate) { const int rc = encoder_restore_descs(e); if (rc) return rc; }
-    e->max_bytes = 0; e->budgets.clear();
+    if (!e->budgets.empty() && e->rate) { const int rc = encoder_restore_descs(e); if (rc) return rc; }
+    e->budgets.clear();
     return OJPHGPU_OK;
   }
-  if (!encoder_may_search(e) || e->quality_on) return OJPHGPU_E_INVALID;   // (a batch encoder: ojphgpu_encoder_set_budgets, also for equal budgets)
-  if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
-  e->max_bytes = max_bytes; e->ran = false;
-  return OJPHGPU_OK;
+  if (e->nframes > 1) return OJPHGPU_E_INVALID;             // (a batch encoder: ojphgpu_encoder_set_budgets, also for equal budgets)
+  return ojphgpu_encoder_set_budgets(e, &max_bytes, 1);
 }
 
 extern "C" int ojphgpu_encoder_set_budgets(ojphgpu_encoder* e, const uint64_t* max_bytes, uint32_t n)
 {
   if (!e || !max_bytes || n != e->nframes) return OJPHGPU_E_INVALID;
-  if (e->nframes == 1) return ojphgpu_encoder_set_budget(e, max_bytes[0]);
   uint32_t zeros = 0;
   for (uint32_t f = 0; f < n; ++f) zeros += max_bytes[f] == 0;
   if (zeros == n) return ojphgpu_encoder_set_budget(e, 0);
   if (zeros) return OJPHGPU_E_INVALID;
-  if (!encoder_may_search(e, true) || e->quality_on) return OJPHGPU_E_INVALID;
+  if (!encoder_may_search(e) || e->quality_on) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
     e->budgets.assign(max_bytes, max_bytes + n);
-    e->max_bytes = max_bytes[0]; e->ran = false;
+    e->ran = false;
     return OJPHGPU_OK;
   });
 }
@@ -588,7 +585,6 @@ static int encoder_rate_setup(ojphgpu_encoder* e)
     for (const Band& B : P.bands) if ((uint64_t)B.r.w * B.r.h > 0xFFFFFFFFull) return OJPHGPU_E_INVALID;   // the counts are 32 bits wide
     int rc = rate_table_build(P, R->table);
     if (rc) return rc;
-    R->plan = new ojphgpu_plan{ P };
     const uint32_t nframes = e->nframes;
     if ((uint64_t)P.bands.size() * nframes > 0xFFFFFFFFull) return OJPHGPU_E_INVALID;   // (the slots are 32 bits wide)
     std::vector<ojphgpu_stats_desc> sd;
@@ -634,67 +630,93 @@ static int encoder_rate_setup(ojphgpu_encoder* e)
     if (!sd.empty()) HIPCHK(hipMemcpy(R->stats_descs.p, sd.data(), sd.size() * sizeof(sd[0]), hipMemcpyHostToDevice));
     if (!cls.empty()) HIPCHK(hipMemcpy(R->block_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
     R->h_hist.assign(P.bands.size() * OJPHGPU_STATS_BINS * nframes, 0);
+    R->h_quant.assign((size_t)nc * nframes, BandQuant{ 0.0f, 0 });
     e->rate = R; owner.p = nullptr;
     e->ran = false;
     return OJPHGPU_OK;
   });
 }
 
-// one trial of the search: the blocks coded at grid index j into the output set `o`, in the schedule of a plain run
-// (BlockCoderRun, fork and rest back to back); the block lengths come to the host and the Tier-2 layout, from Q -- a copy of
-// the encoder's plan, left at the step of j -- gives the codestream's length.  The lengths travel the way the set says: into
-// mapped pinned memory the coder writes itself (a frame pipeline), or by a copy into the encoder's pageable table.
-int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j)
+// One coding round of a search: frame f of the encoder coded at grid index idx[f] into the output set `o`, in the schedule of
+// a plain run (BlockCoderRun, fork and rest back to back) -- so the compacted output and its cursors are what a plain run
+// leaves.  The block lengths of all frames come to the host, *lengths, the way the set says: into mapped pinned memory the
+// coder writes itself (a frame pipeline), or by a copy into the encoder's pageable table.
+static int encoder_code_round(ojphgpu_encoder* e, const RateTrialOut& o, const uint32_t* idx, const ojphgpu_cb_result** lengths)
 {
   EncoderRate& R = *e->rate;
   hipStream_t s = e->stream;
-  auto hip = [](hipError_t x) { return x == hipSuccess; };
-  if (!rate_apply_step(Q, rate_grid_qstep(j))) return OJPHGPU_E_INVALID;
-  const uint32_t nc = R.table.nclasses, nb = (uint32_t)e->block_ids.size();
-  ojphgpu_cb_desc* cbd = (ojphgpu_cb_desc*)e->cb_descs.p;
-  if (!hip(hipMemcpyAsync(R.quant.p, &R.table.quant[(size_t)j * nc], (size_t)nc * sizeof(BandQuant), hipMemcpyHostToDevice, s))) return OJPHGPU_E_HIP;
-  int rc = requant_launch(s, cbd, nb, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p);
+  const uint32_t F = e->nframes, nc = R.table.nclasses, nb = (uint32_t)e->block_ids.size();
+  for (uint32_t f = 0; f < F; ++f) std::copy_n(&R.table.quant[(size_t)idx[f] * nc], nc, &R.h_quant[(size_t)f * nc]);
+  HIPCHK(hipMemcpyAsync(R.quant.p, R.h_quant.data(), R.h_quant.size() * sizeof(BandQuant), hipMemcpyHostToDevice, s));
+  int rc = requant_frames_launch(s, (ojphgpu_cb_desc*)e->cb_descs.p, nb, F, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p, nc);
   if (rc) return rc;
-  BlockCoderRun coder{ e, (uint8_t*)o.out, o.d_results, o.d_counters, nb, nullptr };
+  BlockCoderRun coder{ e, (uint8_t*)o.out, o.d_results, o.d_counters, nb * F, nullptr };
   if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) return rc;
   uint32_t status = 0;
-  const ojphgpu_cb_result* lengths = o.h_results;
   const auto w0 = std::chrono::steady_clock::now();
   if (o.h_results) {                                        // the coder wrote them there; the cursors follow, then the event
     if ((rc = publish_words_launch(s, o.d_publish, o.d_counters, 2)) != 0) return rc;
-    if (!hip(hipEventRecord(o.done, s)) || !hip(hipEventSynchronize(o.done))) return OJPHGPU_E_HIP;
+    HIPCHK(hipEventRecord(o.done, s));
+    HIPCHK(hipEventSynchronize(o.done));
     status = o.h_publish[1];
+    *lengths = o.h_results;
   } else {                                                  // (a copy into pageable memory waits for the launches before it)
     const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
-    if (rbytes && !hip(hipMemcpyAsync(e->h_results.data(), o.d_results, rbytes, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
-    if (!hip(hipMemcpyAsync(&status, o.d_counters + 1, 4, hipMemcpyDeviceToHost, s))) return OJPHGPU_E_HIP;
-    if (!hip(hipStreamSynchronize(s))) return OJPHGPU_E_HIP;
-    lengths = e->h_results.data();
+    if (rbytes) HIPCHK(hipMemcpyAsync(e->h_results.data(), o.d_results, rbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&status, o.d_counters + 1, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *lengths = e->h_results.data();
   }
   R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   e->fetched = false;
-  if (status) return OJPHGPU_E_OVERFLOW;                    // (cannot happen: the buffers hold the finest step's bound)
-  std::vector<ojphgpu_coded_block> cb;
-  ojphgpu_coded_blocks(Q, e->block_ids, lengths, cb);
-  T2Layout L;
-  rc = t2_layout_codestream(Q, cb.data(), L);
-  if (rc) return rc;
-  return (int64_t)L.total;
+  return status ? OJPHGPU_E_OVERFLOW : OJPHGPU_OK;          // (cannot happen: the buffers hold the finest step's bound; a batch's unclamped)
 }
 
-// ... of a single encoder: into its own output set, with its own plan copy
-static int64_t encoder_rate_trial(void* user, uint32_t j)
+// size(j) of one frame: the length of the codestream Tier-2 lays out from the frame's block lengths, with Q -- the
+// encoder's plan at the step the blocks were coded at; or an error (< 0)
+static int64_t rate_layout_bytes(const Plan& Q, const std::vector<uint32_t>& block_ids, const ojphgpu_cb_result* lengths)
 {
-  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
-  EncoderRate& R = *e->rate;
-  R.at = -1;
-  const RateTrialOut own{ e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nullptr, nullptr, nullptr, nullptr };
-  const int64_t size = ojphgpu_encoder_rate_trial(e, R.plan->plan, own, j);
-  if (size >= 0) R.at = (int)j;
-  return size;
+  std::vector<ojphgpu_coded_block> cb;
+  ojphgpu_coded_blocks(Q, block_ids, lengths, cb);
+  T2Layout L;
+  const int rc = t2_layout_codestream(Q, cb.data(), L);
+  return rc ? (int64_t)rc : (int64_t)L.total;
 }
 
-// the search of the last run, once: afterwards the device holds the coded blocks of j* and R.plan stands at its step
+// one trial for a caller with a plan copy and output sets of its own (the frame pipelines): Q is left at the step of j
+int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j)
+{
+  if (!rate_apply_step(Q, rate_grid_qstep(j))) return OJPHGPU_E_INVALID;
+  const ojphgpu_cb_result* lengths = nullptr;
+  const int rc = encoder_code_round(e, o, &j, &lengths);
+  return rc ? (int64_t)rc : rate_layout_bytes(Q, e->block_ids, lengths);
+}
+
+// The encoder's plan at the index of every frame of a round, R.frame_plan, from the copies kept by visited index
+static int encoder_plans_at(ojphgpu_encoder* e, const std::vector<uint32_t>& idx)
+{
+  EncoderRate& R = *e->rate;
+  if (R.plans.size() > 32)                                  // (a sequence that wanders: keep what this round uses)
+    for (auto it = R.plans.begin(); it != R.plans.end();) {
+      if (std::find(idx.begin(), idx.end(), it->first) == idx.end()) { delete it->second; it = R.plans.erase(it); } else ++it;
+    }
+  R.frame_plan.assign(idx.size(), nullptr);
+  for (size_t f = 0; f < idx.size(); ++f) {
+    auto it = R.plans.find(idx[f]);
+    if (it == R.plans.end()) {
+      std::unique_ptr<ojphgpu_plan> q(new ojphgpu_plan{ *e->P });
+      if (!rate_apply_step(q->plan, rate_grid_qstep(idx[f]))) return OJPHGPU_E_INVALID;
+      it = R.plans.emplace(idx[f], q.release()).first;
+    }
+    R.frame_plan[f] = it->second;
+  }
+  return OJPHGPU_OK;
+}
+
+// The search of the last run, once, for the one frame of a single encoder or the frames of a batch: the rounds of
+// ojphgpu_rate_rounds (ojph_rate.cpp), which says what every frame is coded at and which frames measure.  The block
+// lengths of a round come back once, and the layouts of the frames that measure (independent of each other) run on the
+// pool.  When the rounds end the device holds every frame as finish_frame writes it, and R.frame_plan stands at its step.
 static int encoder_rate_search(ojphgpu_encoder* e)
 {
   EncoderRate& R = *e->rate;
@@ -702,169 +724,54 @@ static int encoder_rate_search(ojphgpu_encoder* e)
   const auto t0 = std::chrono::steady_clock::now();
   R.wait_ms = 0;
   auto run = [&]() -> int {
+    const uint32_t F = e->nframes, nb = (uint32_t)e->block_ids.size();
+    if (e->budgets.size() != F) return OJPHGPU_E_INVALID;
     HIPCHK(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    int rc = rate_search(R.table, R.h_hist.data(), e->max_bytes, -1, encoder_rate_trial, e, &R.info);
-    R.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
+    ojphgpu_rate_rounds_destroy(R.rounds); R.rounds = nullptr;
+    int rc = rate_rounds_create(R.table, R.h_hist.data(), e->P->bands.size() * OJPHGPU_STATS_BINS, e->budgets.data(), F, -1, &R.rounds);
     if (rc) return rc;
-    if (R.at != (int)R.info.grid_index) {                   // the last trial was j* + 1: j* is coded once more, and counted
-      const int64_t s = encoder_rate_trial(e, R.info.grid_index);
-      R.info.passes++;
-      if (s < 0) return (int)s;
-      if ((uint64_t)s != R.info.bytes) return OJPHGPU_E_HIP;  // the same blocks at the same step: anything else is a fault
-    }
-    return OJPHGPU_OK;
-  };
-  R.search_rc = no_throw(run);
-  R.searched = true;
-  R.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return R.search_rc;
-}
-
-// The plan at grid index j for the frames of a batch, from the copies kept by visited index
-static ojphgpu_plan* encoder_plan_at(ojphgpu_encoder* e, uint32_t j)
-{
-  EncoderRate& R = *e->rate;
-  auto it = R.plans.find(j);
-  if (it != R.plans.end()) return it->second;
-  std::unique_ptr<ojphgpu_plan> q(new ojphgpu_plan{ *e->P });
-  if (!rate_apply_step(q->plan, rate_grid_qstep(j))) return nullptr;
-  return R.plans.emplace(j, q.release()).first->second;
-}
-
-// The search of the last run of a batch encoder, once: one stepper per frame, advanced together in rounds.  A round codes
-// every frame -- an open one at the index its stepper hands out, a certified one at its j*, one nothing fits at index 0 --
-// in the plain batch schedule, so the compacted output and its cursors are what a plain batch run leaves; the block lengths
-// come back once, and the layouts of the frames that measure (independent of each other) run on the pool.  Closed frames
-// are coded again in every later round: device time, accepted for that.  The rounds end when nobody measures and every
-// frame stands at its answer; then the device holds all frames as finish_frame writes them.
-static int encoder_rate_search_batch(ojphgpu_encoder* e)
-{
-  EncoderRate& R = *e->rate;
-  if (R.searched) return R.search_rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  R.wait_ms = 0;
-  auto run = [&]() -> int {
-    hipStream_t s = e->stream;
-    const uint32_t F = e->nframes, nc = R.table.nclasses, nb = (uint32_t)e->block_ids.size();
-    const size_t hist_per = e->P->bands.size() * OJPHGPU_STATS_BINS;
-    if (e->budgets.size() != F) return OJPHGPU_E_INVALID;
-    HIPCHK(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    struct Steppers { std::vector<ojphgpu_rate_stepper*> v; ~Steppers() { for (ojphgpu_rate_stepper* p : v) ojphgpu_rate_stepper_destroy(p); } } S;
-    S.v.assign(F, nullptr);
-    ojphgpu_rate_info none; memset(&none, 0, sizeof(none));
-    R.rounds = 0;
-    R.frame_rc.assign(F, OJPHGPU_E_INVALID); R.frame_info.assign(F, none); R.frame_plan.assign(F, nullptr);
-    for (uint32_t f = 0; f < F; ++f) {
-      const int rc = rate_stepper_create(R.table, &R.h_hist[f * hist_per], e->budgets[f], -1, &S.v[f]);
-      if (rc) return rc;
-    }
-    enum { IDLE = 0, TRIAL = 1, VERIFY = 2 };
-    std::vector<int> at(F, -1), measure(F, IDLE);            // the index a frame was coded at in the last round; what its layout is for
-    std::vector<char> open(F, 1);
-    std::vector<uint32_t> idx(F, 0), list;
-    std::vector<int64_t> sizes(F, 0);
-    std::vector<BandQuant> hq((size_t)F * nc);
-    for (;;) {
-      bool work = false;
-      for (uint32_t f = 0; f < F; ++f) {
-        measure[f] = IDLE;
-        if (open[f]) {
-          uint32_t j = 0;
-          const int rc = ojphgpu_rate_stepper_next(S.v[f], &j);
-          if (rc == 1) { idx[f] = j; measure[f] = TRIAL; }
-          else if (rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET) {
-            open[f] = 0; R.frame_rc[f] = rc;
-            (void)ojphgpu_rate_stepper_info(S.v[f], &R.frame_info[f]);
-            idx[f] = rc == OJPHGPU_OK ? R.frame_info[f].grid_index : 0;
-            // the last trial was j* + 1: j* is coded once more, counted and checked, as the single encoder does
-            if (rc == OJPHGPU_OK && at[f] != (int)idx[f]) { R.frame_info[f].passes++; measure[f] = VERIFY; }
-          } else return rc;
-        }
-        if (measure[f] != IDLE || at[f] != (int)idx[f]) work = true;
-      }
-      if (!work) break;
-      ++R.rounds;
-      if (R.plans.size() > 32)                                // (a sequence that wanders: keep what this round uses)
-        for (auto it = R.plans.begin(); it != R.plans.end();) {
-          if (std::find(idx.begin(), idx.end(), it->first) == idx.end()) { delete it->second; it = R.plans.erase(it); } else ++it;
-        }
-      for (uint32_t f = 0; f < F; ++f) {
-        if ((R.frame_plan[f] = encoder_plan_at(e, idx[f])) == nullptr) return OJPHGPU_E_INVALID;
-        std::copy(&R.table.quant[(size_t)idx[f] * nc], &R.table.quant[(size_t)idx[f] * nc] + nc, &hq[(size_t)f * nc]);
-      }
-      HIPCHK(hipMemcpyAsync(R.quant.p, hq.data(), hq.size() * sizeof(BandQuant), hipMemcpyHostToDevice, s));
-      int rc = requant_frames_launch(s, (ojphgpu_cb_desc*)e->cb_descs.p, nb, F, (const uint32_t*)R.block_class.p, (const BandQuant*)R.quant.p, nc);
-      if (rc) return rc;
-      BlockCoderRun coder{ e, (uint8_t*)e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nb * F, nullptr };
-      if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) return rc;
-      uint32_t status = 0;
-      const auto w0 = std::chrono::steady_clock::now();
-      const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
-      if (rbytes) HIPCHK(hipMemcpyAsync(e->h_results.data(), e->results.p, rbytes, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(&status, (uint32_t*)e->counters.p + 1, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      R.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-      e->fetched = false;
-      if (status) return OJPHGPU_E_OVERFLOW;                  // (cannot happen: the buffers hold the finest step's bound, unclamped)
+    const RateTrialOut own{ e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nullptr, nullptr, nullptr, nullptr };
+    std::vector<uint32_t> idx(F, 0), list; std::vector<uint8_t> measures(F, 0); std::vector<int64_t> sizes(F, 0);
+    while ((rc = ojphgpu_rate_rounds_next(R.rounds, idx.data(), measures.data())) == 1) {
+      const ojphgpu_cb_result* lengths = nullptr;
+      if ((rc = encoder_plans_at(e, idx)) != 0 || (rc = encoder_code_round(e, own, idx.data(), &lengths)) != 0) return rc;
       list.clear();
-      for (uint32_t f = 0; f < F; ++f) { at[f] = (int)idx[f]; if (measure[f] != IDLE) list.push_back(f); }
+      for (uint32_t f = 0; f < F; ++f) if (measures[f]) list.push_back(f);
       parallel_for(list.size(), [&](size_t k) {
         const uint32_t f = list[k];
-        const Plan& Q = R.frame_plan[f]->plan;
-        std::vector<ojphgpu_coded_block> cb;
-        ojphgpu_coded_blocks(Q, e->block_ids, e->h_results.data() + (size_t)f * nb, cb);
-        T2Layout L;
-        const int lrc = t2_layout_codestream(Q, cb.data(), L);
-        sizes[f] = lrc ? (int64_t)lrc : (int64_t)L.total;
+        sizes[f] = rate_layout_bytes(R.frame_plan[f]->plan, e->block_ids, lengths + (size_t)f * nb);
       });
-      for (uint32_t f : list) {
-        if (measure[f] == TRIAL) { if ((rc = ojphgpu_rate_stepper_feed(S.v[f], sizes[f])) != 0) return rc; }
-        else if (sizes[f] < 0) return (int)sizes[f];
-        else if ((uint64_t)sizes[f] != R.frame_info[f].bytes) return OJPHGPU_E_HIP;   // the same blocks at the same step: anything else is a fault
-      }
+      if ((rc = ojphgpu_rate_rounds_feed(R.rounds, sizes.data())) != 0) return rc;
     }
-    return OJPHGPU_OK;
+    return rc;
   };
   R.search_rc = no_throw(run);
-  if (R.search_rc) R.frame_rc.assign(e->nframes, R.search_rc);
   R.searched = true;
   R.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return R.search_rc;
-}
-
-extern "C" int ojphgpu_encoder_rate_info(ojphgpu_encoder* e, ojphgpu_rate_info* info)
-{
-  if (!e || !info || !e->rate) return OJPHGPU_E_INVALID;
-  if (e->nframes > 1) {                                     // a batch: frame 0
-    const int rc = ojphgpu_encoder_rate_info_frame(e, 0, info);
-    return rc == OJPHGPU_E_BUDGET ? OJPHGPU_OK : rc;
-  }
-  if (!e->rate->have_info) return OJPHGPU_E_INVALID;
-  *info = e->rate->info;
-  return OJPHGPU_OK;
 }
 
 // OJPHGPU_E_BUDGET: nothing fits that frame's budget (info: passes, first_guess)
 extern "C" int ojphgpu_encoder_rate_info_frame(ojphgpu_encoder* e, uint32_t frame, ojphgpu_rate_info* info)
 {
   if (!e || !info || !e->rate || frame >= e->nframes) return OJPHGPU_E_INVALID;
-  if (e->nframes == 1) return ojphgpu_encoder_rate_info(e, info);
   const EncoderRate& R = *e->rate;
-  if (!e->max_bytes || !R.searched || frame >= R.frame_rc.size() || (R.frame_rc[frame] != OJPHGPU_OK && R.frame_rc[frame] != OJPHGPU_E_BUDGET))
-    return OJPHGPU_E_INVALID;
-  *info = R.frame_info[frame];
-  return R.frame_rc[frame];
+  if (e->budgets.empty() || !R.searched || R.search_rc) return OJPHGPU_E_INVALID;
+  return ojphgpu_rate_rounds_frame(R.rounds, frame, info);
+}
+
+extern "C" int ojphgpu_encoder_rate_info(ojphgpu_encoder* e, ojphgpu_rate_info* info)
+{
+  const int rc = ojphgpu_encoder_rate_info_frame(e, 0, info);
+  return rc == OJPHGPU_E_BUDGET ? OJPHGPU_OK : rc;
 }
 
 extern "C" int ojphgpu_encoder_rate_rounds(ojphgpu_encoder* e, uint32_t* rounds)
 {
-  if (!e || !rounds || !e->rate || !e->rate->searched || !e->max_bytes) return OJPHGPU_E_INVALID;
-  *rounds = e->nframes > 1 ? e->rate->rounds : e->rate->info.passes;
-  return OJPHGPU_OK;
+  if (!e || !rounds || !e->rate || !e->rate->searched || e->budgets.empty()) return OJPHGPU_E_INVALID;
+  return ojphgpu_rate_rounds_count(e->rate->rounds, rounds);
 }
 
 extern "C" int ojphgpu_encoder_rate_timing(ojphgpu_encoder* e, float out[4])
@@ -892,7 +799,7 @@ extern "C" int ojphgpu_encoder_clear_quality(ojphgpu_encoder* e)
 extern "C" int ojphgpu_encoder_set_quality(ojphgpu_encoder* e, uint64_t max_sse)
 {
   if (!e) return OJPHGPU_E_INVALID;
-  if (!encoder_may_search(e) || e->max_bytes) return OJPHGPU_E_INVALID;
+  if (e->nframes > 1 || !encoder_may_search(e) || !e->budgets.empty()) return OJPHGPU_E_INVALID;
   const Plan& P = *e->P;
   for (const CompGeo& g : P.comps) if (g.bit_depth > 16) return OJPHGPU_E_INVALID;
   if (e->quality) { e->max_sse = max_sse; e->quality_on = true; e->ran = false; return OJPHGPU_OK; }
@@ -984,7 +891,7 @@ static int64_t encoder_quality_trial(void* user, uint32_t j, uint64_t* sse)
   return 0;
 }
 
-// the search of the last run, once: afterwards the device holds the coded blocks of j* and R.plan stands at its step
+// the search of the last run, once: afterwards the device holds the coded blocks of j* and R.frame_plan[0] stands at its step
 static int encoder_quality_search(ojphgpu_encoder* e)
 {
   EncoderRate& R = *e->rate; EncoderQuality& Q = *e->quality;
@@ -1001,7 +908,11 @@ static int encoder_quality_search(ojphgpu_encoder* e)
     Q.best = Q.by_index[Q.info.grid_index];
     for (const ojphgpu_frame_err& c : Q.best) Q.info.pae = std::max(Q.info.pae, c.pae);
     const auto t1 = std::chrono::steady_clock::now();
-    const int64_t size = encoder_rate_trial(e, Q.info.grid_index);   // j* is block-coded, once, as a trial of the byte budget is
+    // j* is block-coded, once, as a round of the byte budget's search codes its frame
+    const RateTrialOut own{ e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nullptr, nullptr, nullptr, nullptr };
+    const ojphgpu_cb_result* lengths = nullptr;
+    if ((rc = encoder_plans_at(e, { Q.info.grid_index })) != 0 || (rc = encoder_code_round(e, own, &Q.info.grid_index, &lengths)) != 0) return rc;
+    const int64_t size = rate_layout_bytes(R.frame_plan[0]->plan, e->block_ids, lengths);
     Q.final_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (size < 0) return size < INT32_MIN ? OJPHGPU_E_INVALID : (int)size;
     Q.info.bytes = (uint64_t)size;

@@ -453,31 +453,27 @@ enum { SP_CONVERT = 0, SP_DWT = 1, SP_HT_ENC = 2, SP_PREP = 3, SP_STEP1 = 4, SP_
 
 }  // namespace
 
-// What an encoder with a byte budget keeps (include/ojphgpu.h section 5b; made by the first ojphgpu_encoder_set_budget)
+// What an encoder with a byte budget keeps (include/ojphgpu.h section 5b; made by the first ojphgpu_encoder_set_budget(s));
+// stats_descs / hist / h_hist / quant hold a part per frame of the encoder
 struct EncoderRate {
   RateTable table;                                 // the quantisation of every class of bands at every step of the grid
-  ojphgpu_plan* plan = nullptr;                    // the encoder's plan at the step of the last trial: what Tier-2 writes from
-  int at = -1;                                     // grid index the device results and `plan` stand at (-1: none)
   DeviceBuf stats_descs, hist, block_class, quant;
   uint32_t n_stats = 0, stats_max_w = 0, stats_max_h = 0;
   std::vector<uint32_t> h_hist;
+  std::vector<BandQuant> h_quant;                  // the rows of `table` a round uploads, one per frame
   std::vector<ojphgpu_cb_desc> bd;                 // the block descriptors at the plan's own step (what budget 0 puts back)
   bool searched = false; int search_rc = 0;        // the last run has been searched, with this verdict
-  bool have_info = false;
-  ojphgpu_rate_info info;
   double search_ms = 0, wait_ms = 0, final_ms = 0;
-  // A batch encoder (ojphgpu_encoder_set_budgets): stats_descs / hist / h_hist / quant hold a part per frame, and the search
-  // of a run leaves per frame its verdict (OJPHGPU_OK, OJPHGPU_E_BUDGET), what it found and the plan at its step.  The plan
-  // copies are kept by grid index across runs -- the frames of a sequence settle on a handful of indices.
-  std::vector<int> frame_rc;
-  std::vector<ojphgpu_rate_info> frame_info;
+  // The search of a run (ojphgpu_rate_rounds: per frame its verdict and what it found) and per frame the encoder's plan at
+  // the step the device results stand at: what Tier-2 writes from.  The plan copies are kept by grid index across runs --
+  // the frames of a sequence settle on a handful of indices.
+  ojphgpu_rate_rounds* rounds = nullptr;
   std::vector<ojphgpu_plan*> frame_plan;           // (owned by plans)
   std::map<uint32_t, ojphgpu_plan*> plans;
-  uint32_t rounds = 0;
   ~EncoderRate() {
     for (DeviceBuf* b : { &stats_descs, &hist, &block_class, &quant }) b->release();
     for (auto& kv : plans) delete kv.second;
-    delete plan;
+    ojphgpu_rate_rounds_destroy(rounds);
   }
 };
 
@@ -538,13 +534,12 @@ struct ojphgpu_encoder {
   std::vector<uint32_t> h_regions, h_cursors;
   DeviceBuf regions;
   size_t counters_bytes = 16;
-  uint64_t max_bytes = 0;                          // != 0: every frame is coded to this budget
-  std::vector<uint64_t> budgets;                   // a batch encoder's: one per frame (max_bytes = the first, as the switch)
+  std::vector<uint64_t> budgets;                   // one per frame: frame f of every run is coded to budgets[f]; empty: off
   EncoderRate* rate = nullptr;
   bool quality_on = false; uint64_t max_sse = 0;   // every frame is coded to this quality target (never together with a budget)
   EncoderQuality* quality = nullptr;
   // the blocks are coded by a search in ojphgpu_encoder_finish*, and Tier-2 writes from the search's plan
-  bool searches() const { return max_bytes != 0 || quality_on; }
+  bool searches() const { return !budgets.empty() || quality_on; }
 };
 // Where one trial of the budget search writes, and how its block lengths reach the host.  h_results != null: d_results is the
 // device address of that mapped pinned memory, the coder's records land in it, the two status words of d_counters are
@@ -554,7 +549,8 @@ struct RateTrialOut {
   void* out; ojphgpu_cb_result* d_results; uint32_t* d_counters;
   const ojphgpu_cb_result* h_results; uint32_t* d_publish; const uint32_t* h_publish; hipEvent_t done;
 };
-int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j);   // size(j), or an error (< 0)
+// a single-frame encoder's blocks coded at grid index j into `o`, Q left at that step: size(j), or an error (< 0)
+int64_t ojphgpu_encoder_rate_trial(ojphgpu_encoder* e, Plan& Q, const RateTrialOut& o, uint32_t j);
 // What one trial of the quality search compares against, and how its small data travel.  frame / container: the original,
 // on the device.  h_descs != null: mapped pinned memory the requantise descriptors are written into (d_descs: its device
 // address; a copy kernel takes them to the device), the error words (one ojphgpu_frame_err per component) are written to

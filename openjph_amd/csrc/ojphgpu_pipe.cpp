@@ -440,7 +440,7 @@ static int enc_rate_frame(ojphgpu_enc_pipe* p, EncSlot& s)
   EncoderRate& R = *e->rate;
   ojphgpu_rate_info& info = s.found.rate;
   HIPCHK(hipSetDevice(p->device));
-  int rc = enc_begin_frame(p, s);                    // transform + statistics (e->max_bytes != 0)
+  int rc = enc_begin_frame(p, s);                    // transform + statistics (the encoder has a budget)
   if (rc) return rc;
   if ((rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
   HIPCHK(hipEventRecord(p->ev_trial, p->s_comp));

@@ -24,7 +24,12 @@ frame; (b) the same frames through B budgeted single-frame encodes, one after th
 batch form; (c) a plain batch encode at the fixed step of the median j* -- the device and download cost of one coding of
 the batch.  The bytes of (a) and (b) are compared.  Prints one JSON line per budget: the j* of the frames, the rounds of
 the batch's search and the sum of the frames' passes, median ms of (a) (b) (c), the batch's search / device wait.
-  python tools/rate_bench.py --batch 8 [--runs 10] [--warmup 3] [--rows 2160]"""
+  python tools/rate_bench.py --batch 8 [--runs 10] [--warmup 3] [--rows 2160]
+
+--first N: the first budgeted frame of a fresh encoder -- what a one-shot caller (ojph_compress with a byte budget) pays, with
+no plan copy of any grid index made yet: per budget N encoders in turn, each made, run once on the C3 frame and timed on
+the host clock around finish() alone.  Prints one JSON line per budget: every time and the median.
+  python tools/rate_bench.py --first 7 [--rows 4320]"""
 import argparse
 import json
 import os
@@ -154,6 +159,35 @@ def batch_bench(a):
             flush=True)
 
 
+def first_frame_bench(a):
+    import torch
+    from openjph_amd import codec
+    from openjph_amd.plan import make_params
+    from tests import synth
+    img = synth.survey_c3(rows=a.rows)
+    nc, h, w = img.shape
+    d_img = torch.from_numpy(img.astype(np.uint16).view(np.int16)).cuda()
+    params = make_params(w, h, nc, bit_depth=12, reversible=False, qstep=0.001)
+    warm = codec.Encoder(params)                               # the runtime's own first-use costs are not the encoder's
+    warm.run_device(d_img)
+    warm.finish()
+    for bps in BPS:
+        budget = int(img.size * bps)
+        ms = []
+        for _ in range(a.first):
+            enc = codec.Encoder(params, max_bytes=budget)
+            enc.run_device(d_img)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            enc.finish()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            info = enc.rate_info()
+            del enc
+        print(json.dumps(dict(frame="c3 %dx%dx%d 12-bit, 16-bit containers" % (w, h, nc), bytes_per_sample=bps, budget=budget,
+                              grid_index=info["grid_index"], passes=info["passes"], first_frame_finish_ms=[round(x, 3) for x in ms],
+                              median=round(float(np.median(ms)), 3))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10)
@@ -164,7 +198,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--batch", type=int, default=0, help="B: the budgets of a batch encoder of B 4K frames against B single encodes")
+    ap.add_argument("--first", type=int, default=0, help="N: finish() of the first budgeted frame of N fresh encoders per budget")
     a = ap.parse_args()
+    if a.first:
+        return first_frame_bench(a)
     if a.pipe:
         return pipe_bench(a)
     if a.batch:
