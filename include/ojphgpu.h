@@ -919,7 +919,12 @@ int  ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* pipe, int bits);
  * (ceil(w / 2), ceil(h / 2)) each; _acquire hands out frame_bytes of the TIGHT layout of ojphgpu_video420_layout -- the luma
  * plane, then the chroma plane, both at row_bytes -- and the launch is ojphgpu_unpack_video420.  A 4:2:2 format on a 4:2:0
  * plan is refused, and a 4:2:0 format on a 4:2:2 plan.  The bytes on the link are those of planes in the matching
- * containers; what is saved is the host's de-interleaving pass. */
+ * containers; what is saved is the host's de-interleaving pass.
+ * Or as one 4:4:4 packed buffer (section 7d: OJPHGPU_VIDEO_V410 ... _ARGB): exactly three unsigned components of one depth
+ * that the format and the container hold, all of the size of component 0 (a sub-sampled plan is refused, as a 4:2:2 or 4:2:0
+ * format stays refused on a 4:4:4 plan); _acquire hands out frame_bytes of the tight layout of ojphgpu_video444_layout, rows at
+ * row_bytes, and the launch is ojphgpu_unpack_video444.  A 10-bit frame crosses the link in two thirds of the bytes of its
+ * planes in 16-bit containers. */
 int  ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* pipe, int format);
 
 /* Every frame of this pipe is coded to a byte budget (section 5b): each collected codestream is, byte for byte, the plain
@@ -1012,7 +1017,8 @@ int  ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* pipe, int bits);     /* decod
  * view: a reduced resolution always passes, a region when its planes have those sizes (an even x0 guarantees it).  Call
  * before the first _submit, not together with _set_pixels / _set_packed; 0 switches back to planes.  The 4:2:0 formats
  * of section 7c come back in the tight layout (ojphgpu_pack_video420); a window passes when its x0 AND y0 are even, and one
- * with an odd y0 is refused whatever its height, as one with an odd x0 is. */
+ * with an odd y0 is refused whatever its height, as one with an odd x0 is.  The 4:4:4 formats of section 7d come back in
+ * the tight layout too (ojphgpu_pack_video444, alpha opaque); there is no chroma cell, so a window passes at any x0, y0. */
 int  ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* pipe, int format);
 
 /* ---------------------------------------------------------------------------------------------
@@ -1096,6 +1102,47 @@ int  ojphgpu_unpack_video420(void* stream, int format, const void* d_luma, uint3
                              int container_bits);
 int  ojphgpu_pack_video420(void* stream, int format, const void* d_planes, void* d_luma, uint32_t luma_pitch, void* d_chroma,
                            uint32_t chroma_pitch, uint32_t width, uint32_t height, int container_bits, uint32_t bit_depth);
+/* ---- 7d. 4:4:4 packed video (kernels_video444.hip): the frame as capture cards, SDI / ST 2110 receivers, graphics surfaces
+ * and ffmpeg's rawvideo hold it, ONE buffer of width x height pixels, one interleaved word per pixel, the rows following each
+ * other at a pitch; row_bytes = pixel_bytes * width.  Components 0, 1, 2 of the plan are (Y, Cb, Cr) or (R, G, B), as the
+ * format names them; the codec's colour transform is the plan's business, as it is with _set_pixels.
+ *   constant            pixel                                fields                                            depth b    containers
+ *   OJPHGPU_VIDEO_V410  one little-endian dword              Cb bits 2-11, Y 12-21, Cr 22-31; bits 0-1 padding  b <= 10    16, 32
+ *   OJPHGPU_VIDEO_Y410  one little-endian dword              Cb 0-9, Y 10-19, Cr 20-29; bits 30-31 alpha        b <= 10    16, 32
+ *   OJPHGPU_VIDEO_R210  one BIG-endian dword                 R 20-29, G 10-19, B 0-9; bits 30-31 padding        b <= 10    16, 32
+ *   OJPHGPU_VIDEO_R10K  one BIG-endian dword                 R 22-31, G 12-21, B 2-11; bits 0-1 padding         b <= 10    16, 32
+ *   OJPHGPU_VIDEO_Y4XX  four little-endian 16-bit words      Cb, Y, Cr, A; the sample in the high b bits of its
+ *                                                            word (Y412, Y416)                                  9 <= b <= 16  16, 32
+ *   OJPHGPU_VIDEO_AYUV  bytes Cr, Cb, Y, A (Microsoft AYUV; ffmpeg vuya)                                        b <= 8     8, 16, 32
+ *   OJPHGPU_VIDEO_BGRA  bytes B, G, R, A                                                                        b <= 8     8, 16, 32
+ *   OJPHGPU_VIDEO_RGBA  bytes R, G, B, A                                                                        b <= 8     8, 16, 32
+ *   OJPHGPU_VIDEO_ARGB  bytes A, R, G, B                                                                        b <= 8     8, 16, 32
+ * Unpacking: a sample is its field (Y4XX: word >> (16 - b)); padding bits, alpha, the low bits of a Y4XX word and everything
+ * between row_bytes and the pitch are not looked at, no value is range-checked.  Packing: every sample is clamped to [0, 2^b -
+ * 1] as ojphgpu_pack_video does, padding bits are zero, alpha is opaque (3 for Y410, 0xFF for the byte formats, (2^b - 1) <<
+ * (16 - b) for Y4XX), a Y4XX sample is shifted up with zero low bits; every byte of [0, row_bytes) of every row is written and
+ * NOTHING else: the bytes between row_bytes and the pitch and everything in front of and behind the buffer keep their
+ * contents.
+ * d_planes: three planes width x height, tightly packed one after the other, in container_bits-bit elements.
+ * OJPHGPU_E_INVALID: an unknown format (the codes of sections 7b and 7c included), a null pointer, a zero size, a bit_depth
+ * outside the format's column, a container narrower than bit_depth, an 8-bit container with a format that is not a byte
+ * format, a pitch below row_bytes, a d_video or pitch that is not a multiple of the pixel's size (4 bytes, Y4XX: 8), row_bytes
+ * beyond 32 bits.  No further alignment is required, so a pitched surface that is already in device memory is read or written
+ * in place; the kernels take, per row, the widest piece its address allows.  Sections 7b and 7c refuse these codes. */
+#define OJPHGPU_VIDEO_V410 0x21
+#define OJPHGPU_VIDEO_Y410 0x22
+#define OJPHGPU_VIDEO_R210 0x23
+#define OJPHGPU_VIDEO_R10K 0x24
+#define OJPHGPU_VIDEO_Y4XX 0x25
+#define OJPHGPU_VIDEO_AYUV 0x26
+#define OJPHGPU_VIDEO_BGRA 0x27
+#define OJPHGPU_VIDEO_RGBA 0x28
+#define OJPHGPU_VIDEO_ARGB 0x29
+int  ojphgpu_video444_layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* frame_bytes);   /* host only */
+int  ojphgpu_unpack_video444(void* stream, int format, const void* d_video, uint32_t pitch, void* d_planes, uint32_t width,
+                             uint32_t height, uint32_t bit_depth, int container_bits);
+int  ojphgpu_pack_video444(void* stream, int format, const void* d_planes, void* d_video, uint32_t pitch, uint32_t width,
+                           uint32_t height, int container_bits, uint32_t bit_depth);
 /* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
  * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
  * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a

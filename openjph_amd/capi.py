@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libojphgpu.so")
 
 OK, E_INVALID, E_NOMEM, E_HIP, E_CODESTREAM, E_OVERFLOW, E_BLOCK, E_AGAIN, E_UNCOLLECTED, E_BUDGET, E_QUALITY = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
 RATE_GRID, STATS_BINS = 241, 80
+VIDEO_V410, VIDEO_Y410, VIDEO_R210, VIDEO_R10K, VIDEO_Y4XX, VIDEO_AYUV, VIDEO_BGRA, VIDEO_RGBA, VIDEO_ARGB = range(0x21, 0x2A)   # section 7d
 PROG_ORDERS = {"LRCP": 0, "RLCP": 1, "RPCL": 2, "PCRL": 3, "CPRL": 4}
 
 
@@ -388,6 +389,9 @@ SIGNATURES = {
                                           C.c_uint32, C.c_int]),
     "ojphgpu_pack_video420": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.c_int, C.c_uint32]),
+    "ojphgpu_video444_layout": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "ojphgpu_unpack_video444": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+    "ojphgpu_pack_video444": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]),
     "ojphgpu_enc_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_dec_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_version": (C.c_char_p, []),

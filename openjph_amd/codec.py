@@ -909,6 +909,55 @@ def pack_video420(d_planes, fmt, width, height, bit_depth=None, out=None, luma_p
     return out.reshape(-1)[:row * rows].reshape(rows, row) if tight else out
 
 
+def _video444_args(what, buf, fmt, width, height, bit_depth, pitch):
+    """the surface of the two 4:4:4 stages -> (code, depth, w, h, row_bytes, pitch); the default is the tight layout"""
+    from .pipeline import video444_format, video444_layout
+    code, b = video444_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    row = video444_layout(fmt, w, h)[0]
+    p = row if pitch is None else int(pitch)
+    assert buf.is_cuda and buf.is_contiguous(), what
+    if p >= row:                                          # (a pitch below row_bytes: the library refuses it)
+        assert buf.numel() * buf.element_size() >= p * (h - 1) + row, what
+    return code, b, w, h, row, p
+
+
+def unpack_video444(d_buf, fmt, width, height, bit_depth=None, dtype=None, out=None, pitch=None):
+    """a 4:4:4 packed video buffer on the device (fmt = "v410" | "y410" | "r210" | "r10k" | "y4xx" | "y412" | "y416" | "ayuv" |
+    "bgra" | "rgba" | "argb"; uint8 tensor) -> the frame's three planes [H,W] as ONE flat tensor in `dtype` (uint8 -- the byte
+    formats only -- / int16 / uint16 / int32; default: uint8 for the byte formats, else int16), or in `out` (contiguous, at
+    least that many elements; its dtype is the container).  The default is pipeline.pack_video444's tight layout; pitch: the
+    bytes from one row to the next of a surface that is used in place.  The pointer and the pitch are multiples of the
+    pixel's size (4 bytes, y4xx: 8) and need no other alignment.  ojphgpu_unpack_video444."""
+    torch = _torch()
+    code, b, w, h, row, p = _video444_args("unpack_video444", d_buf, fmt, width, height, bit_depth, pitch)
+    n = 3 * w * h
+    if out is None:
+        out = torch.empty(n, dtype=dtype if dtype is not None else (torch.uint8 if code >= 0x26 else torch.int16), device=d_buf.device)
+    assert out.is_cuda and out.is_contiguous() and out.numel() >= n
+    check(capi.lib().ojphgpu_unpack_video444(_stream_ptr(torch, d_buf.device.index or 0), code, C.c_void_p(d_buf.data_ptr()), p,
+                                             C.c_void_p(out.data_ptr()), w, h, b, out.element_size() * 8), "unpack_video444")
+    return out.reshape(-1)[:n]
+
+
+def pack_video444(d_planes, fmt, width, height, bit_depth=None, out=None, pitch=None):
+    """the way back: the three planes as one flat tensor (uint8 / int16 / uint16 / int32) -> the packed buffer, clamped to [0,
+    2^bit_depth - 1], padding zero, alpha opaque.  Without `out`: a new uint8 [H, row_bytes] in the tight layout.  `out`
+    (uint8, contiguous) and pitch describe the surface as for unpack_video444; only [0, row_bytes) of every row is written.
+    Returns out (the tight layout: reshaped to [H, row_bytes]).  ojphgpu_pack_video444."""
+    torch = _torch()
+    from .pipeline import video444_layout
+    w, h = int(width), int(height)
+    assert d_planes.is_cuda and d_planes.is_contiguous() and d_planes.numel() >= 3 * w * h
+    if out is None:
+        assert pitch is None, "pack_video444: a pitched surface is the caller's (out=)"
+        out = torch.empty(video444_layout(fmt, w, h)[1], dtype=torch.uint8, device=d_planes.device)
+    code, b, w, h, row, p = _video444_args("pack_video444", out, fmt, w, h, bit_depth, pitch)
+    check(capi.lib().ojphgpu_pack_video444(_stream_ptr(torch, d_planes.device.index or 0), code, C.c_void_p(d_planes.data_ptr()), C.c_void_p(out.data_ptr()), p,
+                                           w, h, d_planes.element_size() * 8, b), "pack_video444")
+    return out.reshape(-1)[:row * h].reshape(h, row) if pitch is None else out
+
+
 def pack_pixels(planes, bit_depth, pixel_bits=None, big_endian=False):
     """planes [C,H,W] on the device -> pixel-interleaved [H,W,C] (uint8 for pixel_bits 8, else int16 holding the bytes
     of uint16 samples, byte-swapped when big_endian), clamped to [0, 2^bit_depth - 1] as the reference's writers do."""

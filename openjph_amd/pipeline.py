@@ -25,7 +25,7 @@ def _frame_view(pipe, ptr, nbytes):
     raw = _view(ptr, nbytes)
     if pipe.packed:                                   # one bit string
         return raw
-    if pipe.video:                                    # [H, row_bytes]; 4:2:0: [H + ch, row_bytes], the chroma plane's rows behind the luma plane's
+    if pipe.video:                                    # [H, row_bytes] (4:2:2, 4:4:4); 4:2:0: [H + ch, row_bytes], the chroma plane's rows behind the luma plane's
         h = pipe.plan.comp_info(0)["h"]
         rows = h + (h + 1) // 2 if pipe.video in VIDEO420_FORMATS else h
         return raw.reshape(rows, nbytes // rows)
@@ -57,7 +57,8 @@ class _Handover:
     def set_video(self, fmt):
         """judged on the pipe's plan (a view's: the view's; a region with odd x0 is refused): three unsigned components of
         one depth the format holds, the chroma half as wide -- and, for the 4:2:0 names of VIDEO420_FORMATS, half as high (a
-        region with odd y0 is refused too)"""
+        region with odd y0 is refused too); for the 4:4:4 names of VIDEO444_FORMATS all three of one size, a region at any
+        origin"""
         self._set("video", _video_code(self.plan, fmt, "%s_pipe_set_video" % self._side))
         self.video = fmt
 
@@ -108,9 +109,10 @@ def _video_code(plan, fmt, what):
     samples do not have is refused here as the library refuses the rest"""
     if fmt is None:
         return 0
-    if fmt not in VIDEO_FORMATS and fmt not in VIDEO420_FORMATS:
-        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS) + sorted(VIDEO420_FORMATS))))
-    code, fixed = (VIDEO_FORMATS if fmt in VIDEO_FORMATS else VIDEO420_FORMATS)[fmt]
+    tables = [t for t in (VIDEO_FORMATS, VIDEO420_FORMATS, VIDEO444_FORMATS) if fmt in t]
+    if not tables:
+        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS) + sorted(VIDEO420_FORMATS) + sorted(VIDEO444_FORMATS))))
+    code, fixed = tables[0][fmt]
     if fixed is not None and plan.comp_format(0)[0] != fixed:
         raise capi.OjphError(capi.E_INVALID, "%s: %r on %d-bit samples" % (what, fmt, plan.comp_format(0)[0]))
     return code
@@ -244,6 +246,88 @@ def unpack_video420(buf, fmt, width, height, bit_depth=None):
     return [np.ascontiguousarray(f[:h, :w]), np.ascontiguousarray(cb), np.ascontiguousarray(cr)]
 
 
+# 4:4:4 packed video (ojphgpu.h section 7d), one interleaved word per pixel: name -> (OJPHGPU_VIDEO_* constant, the depth the
+# name fixes or None).  A table of its own again: pack_video and pack_video420 keep refusing these names.
+VIDEO444_FORMATS = {"v410": (0x21, None), "y410": (0x22, None), "r210": (0x23, None), "r10k": (0x24, None), "y4xx": (0x25, None), "y412": (0x25, 12),
+                    "y416": (0x25, 16), "ayuv": (0x26, None), "bgra": (0x27, None), "rgba": (0x28, None), "argb": (0x29, None)}
+# constant -> (bytes of a pixel, lowest and highest depth of the format's column)
+_VIDEO444_COLUMN = {0x21: (4, 1, 10), 0x22: (4, 1, 10), 0x23: (4, 1, 10), 0x24: (4, 1, 10), 0x25: (8, 9, 16), 0x26: (4, 1, 8), 0x27: (4, 1, 8),
+                    0x28: (4, 1, 8), 0x29: (4, 1, 8)}
+# the 10-bit dword formats: constant -> (dword byte order, first bit of component 0, 1, 2, the constant bits).  v410 and Y410
+# name Cb (component 1) first, R210 and R10k carry R (component 0) on top
+_VIDEO444_DWORD = {0x21: ("<u4", (12, 2, 22), 0), 0x22: ("<u4", (10, 0, 20), 3 << 30), 0x23: (">u4", (20, 10, 0), 0), 0x24: (">u4", (22, 12, 2), 0)}
+# the byte formats: constant -> the byte of component 0, 1, 2 and of alpha
+_VIDEO444_BYTES = {0x26: (2, 1, 0, 3), 0x27: (2, 1, 0, 3), 0x28: (0, 1, 2, 3), 0x29: (1, 2, 3, 0)}
+
+
+def video444_format(fmt, bit_depth):
+    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a 4:4:4 format name, refused when the depth is outside the format's column;
+    without a depth: the one the name fixes, else the widest of the column"""
+    if fmt not in VIDEO444_FORMATS:
+        raise ValueError("4:4:4 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO444_FORMATS))))
+    code, fixed = VIDEO444_FORMATS[fmt]
+    _, lo, hi = _VIDEO444_COLUMN[code]
+    b = int((hi if fixed is None else fixed) if bit_depth is None else bit_depth)
+    if not lo <= b <= hi or (fixed is not None and b != fixed):
+        raise ValueError("video format %r does not hold %d-bit samples" % (fmt, b))
+    return code, b
+
+
+def video444_layout(fmt, width, height):
+    """-> (row_bytes, frame_bytes) of the tight layout of a width x height frame, as ojphgpu_video444_layout"""
+    if fmt not in VIDEO444_FORMATS:
+        raise ValueError("4:4:4 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO444_FORMATS))))
+    if width < 1 or height < 1:
+        raise ValueError("video444_layout: a frame has at least one sample")
+    row = _VIDEO444_COLUMN[VIDEO444_FORMATS[fmt][0]][0] * int(width)
+    return row, row * int(height)
+
+
+def pack_video444(planes, fmt, bit_depth=None):
+    """numpy: planes = three [H,W] (Y, Cb, Cr or R, G, B, as the format names them) -> the frame as one 4:4:4 packed buffer in
+    the tight layout, uint8 [H, row_bytes]: the host-side statement of ojphgpu_pack_video444.  Samples are clamped to [0,
+    2^bit_depth - 1]; padding bits and the low bits of a Y4XX word are zero, alpha is opaque."""
+    code, b = video444_format(fmt, bit_depth)
+    if len(planes) != 3:
+        raise ValueError("pack_video444: three planes")
+    c = [np.clip(np.asarray(p).astype(np.int64), 0, (1 << b) - 1) for p in planes]
+    if c[0].ndim != 2 or c[0].size == 0 or c[1].shape != c[0].shape or c[2].shape != c[0].shape:
+        raise ValueError("pack_video444: three planes [H, W] of one size")
+    h, w = c[0].shape
+    if code in _VIDEO444_DWORD:
+        order, at, const = _VIDEO444_DWORD[code]
+        d = c[0] << at[0] | c[1] << at[1] | c[2] << at[2] | const
+        return np.ascontiguousarray(d.astype(order)).view(np.uint8).reshape(h, 4 * w)
+    if code == 0x25:                                           # words Cb, Y, Cr, A
+        f = np.stack([c[1], c[0], c[2], np.full((h, w), (1 << b) - 1, np.int64)], axis=2) << (16 - b)
+        return np.ascontiguousarray(f.astype("<u2")).view(np.uint8).reshape(h, 8 * w)
+    f = np.zeros((h, w, 4), np.uint8)
+    i0, i1, i2, ia = _VIDEO444_BYTES[code]
+    f[:, :, i0], f[:, :, i1], f[:, :, i2], f[:, :, ia] = c[0], c[1], c[2], 0xFF
+    return f.reshape(h, 4 * w)
+
+
+def unpack_video444(buf, fmt, width, height, bit_depth=None):
+    """numpy inverse of pack_video444: the bytes of a 4:4:4 packed buffer in the tight layout -> three [H,W] (uint16).  A
+    sample is its field (Y4XX: word >> (16 - bit_depth)); padding and alpha are not looked at and no value is range-checked."""
+    code, b = video444_format(fmt, bit_depth)
+    w, h = int(width), int(height)
+    row, total = video444_layout(fmt, w, h)
+    raw = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if raw.size != total:
+        raise ValueError("unpack_video444: %d bytes, the frame has %d" % (raw.size, total))
+    raw = raw.reshape(h, row)
+    if code in _VIDEO444_DWORD:
+        order, at, _ = _VIDEO444_DWORD[code]
+        d = raw.view(order).astype(np.uint32)
+        return [np.ascontiguousarray(((d >> a) & 0x3FF).astype(np.uint16)) for a in at]
+    if code == 0x25:
+        f = raw.view("<u2").reshape(h, w, 4) >> (16 - b)
+        return [np.ascontiguousarray(f[:, :, i].astype(np.uint16)) for i in (1, 0, 2)]
+    f = raw.reshape(h, w, 4)
+    return [np.ascontiguousarray(f[:, :, i].astype(np.uint16)) for i in _VIDEO444_BYTES[code][:3]]
+
+
 class EncoderPipe(_Handover):
     _side = "enc"
 
@@ -253,7 +337,9 @@ class EncoderPipe(_Handover):
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
         the device.  video="uyvy" | "yuy2" | "v210" | "y210" | "y212" | "y216": the frames are handed over as one 4:2:2 video
         buffer (uint8 [H, row_bytes], pack_video's layout) and unpacked on the device; video="nv12" | "nv21" | "p010" | "p012" |
-        "p016": as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420's tight layout).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
+        "p016": as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420's tight layout); video="v410" | "y410" |
+        "r210" | "r10k" | "y412" | "y416" | "ayuv" | "bgra" | "rgba" | "argb": as one 4:4:4 packed buffer (uint8 [H, row_bytes],
+        pack_video444's layout).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
         quality target (set_quality) -- one or the other"""
         from .codec import _torch
         _torch()
@@ -394,7 +480,8 @@ class DecoderPipe(_Handover):
         """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
         skip_res=n or (for_data, for_recon), region=(x0, y0, w, h): the pipe decodes that view of every frame, as
         video="uyvy" | ...: they come back as one 4:2:2 video buffer (uint8 [H, row_bytes], pack_video of the planes);
-        video="nv12" | "nv21" | "p010" | ...: as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420 of them).
+        video="nv12" | "nv21" | "p010" | ...: as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420 of them);
+        video="v410" | "bgra" | ...: as one 4:4:4 packed buffer (uint8 [H, row_bytes], pack_video444 of them).
         codec.Decoder takes them (ojphgpu_dec_pipe_create_view); .plan, the frames and pixels / packed are the view's"""
         from .codec import _torch
         _torch()

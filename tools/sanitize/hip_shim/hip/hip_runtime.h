@@ -39,6 +39,19 @@ inline int readfirstlane(int v)
   else if (wave_values[lane_calls] != v) { fprintf(stderr, "hip_shim: readfirstlane of a value that differs inside the wavefront\n"); abort(); }
   return wave_values[lane_calls++];
 }
+// v_perm_b32: byte i of the result is the byte of the eight of {hi, lo} that byte i of the selector names (0 to 3: of lo, 4 to 7:
+// of hi); the selectors above 7 (constants, sign bytes) are not used by the kernels compiled here
+inline uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+  const uint64_t both = (uint64_t)hi << 32 | lo;
+  uint32_t r = 0;
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t s = (sel >> (8 * i)) & 0xFFu;
+    if (s > 7) { fprintf(stderr, "hip_shim: perm selector byte 0x%x\n", s); abort(); }
+    r |= (uint32_t)((both >> (8 * s)) & 0xFFu) << (8 * i);
+  }
+  return r;
+}
 template <class F> void launch(dim3 grid, dim3 block, F&& body)
 {
   gridDim = grid; blockDim = block;
@@ -56,4 +69,5 @@ template <class F> void launch(dim3 grid, dim3 block, F&& body)
 }  // namespace hip_shim
 
 #define __builtin_amdgcn_readfirstlane hip_shim::readfirstlane
+#define __builtin_amdgcn_perm hip_shim::perm
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) hip_shim::launch(grid, block, [&] { kernel(__VA_ARGS__); })

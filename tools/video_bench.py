@@ -9,6 +9,12 @@ ones, both directions, the tight layout) beside the yardstick and the 4:2:2 kern
 marks a 4:2:0 kernel whose median stays below that 4:2:2 kernel's by more than the larger of the two spreads, and runs
 EncoderPipe(video="p010") on a 4:2:0 plan against the same pipe fed planes; its default --out is profiles/video420_bench.txt.
 
+--v444 measures the 4:4:4 kernels of kernels_video444.hip instead (v410 and r210 into 16- and 32-bit containers, y416 into 16-
+and 32-bit ones, bgra into 8-, 16- and 32-bit ones, both directions, the tight layout) beside the yardstick and the P010 kernels,
+holds each against the kernel of those with the nearest bytes per launch in its direction, and runs EncoderPipe(video="v410")
+against the same pipe fed planes in 16-bit containers and fed the 10-bit string of packed=10; its default --out is
+profiles/video444_bench.txt.
+
 1. Every instantiation of ojphgpu_unpack_video / _pack_video (format x container), bytes read plus written per second, beside
    the yardstick: ojphgpu_unpack_pixels / _pack_pixels with 3 components, 16-bit samples into 16-bit containers, on the same
    number of pixels -- the same kind of copy.  All of them alternate inside every round; a kernel runs `reps` launches per
@@ -35,12 +41,95 @@ W, H, DEPTH = 7680, 4320, 10
 NSETS = 4
 KERNELS = [(f, c) for f, cs in (("uyvy", (8, 16, 32)), ("yuy2", (8, 16, 32)), ("v210", (16, 32)), ("y210", (16, 32))) for c in cs]
 KERNELS_420 = [("nv12", 8), ("nv12", 16), ("p010", 16), ("p010", 32)]
+KERNELS_444 = [("v410", 16), ("v410", 32), ("r210", 16), ("r210", 32), ("y416", 16), ("y416", 32), ("bgra", 8), ("bgra", 16), ("bgra", 32)]
 PEERS_420 = {8: ("uyvy", 8), 16: ("y210", 16)}              # the 4:2:2 kernel a 4:2:0 kernel is held against, by container (32: none measured beside it)
 
 
 def median_spread(v):
     med = statistics.median(v)
     return med, (max(v) - min(v)) / med
+
+
+def timed_rounds(torch, work, rounds, reps):
+    """work: name -> (callable(set index), bytes read + written); every kernel in every round, `reps` launches between two
+    device events, after a warm-up round that is not counted -> name -> GB/s per round"""
+    rates = {k: [] for k in work}
+    for r in range(rounds + 1):                              # round 0: the warm-up
+        for name, (fn, moved) in work.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fn(0)
+            e0.record()
+            for k in range(reps):
+                fn(k % NSETS)
+            e1.record()
+            e1.synchronize()
+            if r:
+                rates[name].append(moved * reps / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+    return rates
+
+
+def yardstick_work(torch, work):
+    """adds ojphgpu_unpack_pixels / _pack_pixels, 3 components of 16-bit samples into 16-bit containers, to `work`"""
+    from openjph_amd import codec
+    L = __import__("openjph_amd.capi", fromlist=["lib"]).lib()
+    import ctypes as C
+    pix = [torch.randint(0, 1 << 15, (H, W, 3), dtype=torch.int16, device="cuda") for _ in range(NSETS)]
+    pla = [torch.empty((3, H, W), dtype=torch.int16, device="cuda") for _ in range(NSETS)]
+    st = codec._stream_ptr(torch, 0)
+
+    def y_unpack(i):
+        codec.check(L.ojphgpu_unpack_pixels(st, C.c_void_p(pix[i].data_ptr()), C.c_void_p(pla[i].data_ptr()), W, H, 3, 16, 0, 16), "unpack_pixels")
+
+    def y_pack(i):
+        codec.check(L.ojphgpu_pack_pixels(st, C.c_void_p(pla[i].data_ptr()), C.c_void_p(pix[i].data_ptr()), W, H, 3, 16, 16, 0, 16), "pack_pixels")
+
+    work["unpack_pixels 3 x 16 -> 16 (yardstick)"] = (y_unpack, 2 * W * H * 3 * 2)
+    work["pack_pixels 16 -> 3 x 16 (yardstick)"] = (y_pack, 2 * W * H * 3 * 2)
+
+
+def kernel_rates_444(torch, rounds, reps, emit):
+    """the 4:4:4 kernels, the yardstick and the P010 kernels, alternating inside every round; each 4:4:4 kernel beside the one of
+    the others with the nearest bytes per launch in its direction"""
+    from openjph_amd import codec
+    from openjph_amd.pipeline import video420_layout, video444_layout
+    dts = {8: torch.uint8, 16: torch.int16, 32: torch.int32}
+    work, new = {}, []
+    for fmt, cont in KERNELS_444:
+        b = {"bgra": 8, "y416": 16}.get(fmt, DEPTH)
+        total = video444_layout(fmt, W, H)[1]
+        vid = [torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda") for _ in range(NSETS)]
+        pl = [torch.randint(0, 1 << b, (3 * W * H,), dtype=torch.int32, device="cuda").to(dts[cont]) for _ in range(NSETS)]
+        moved = total + 3 * W * H * (cont // 8)
+        work["unpack %s -> %d" % (fmt, cont)] = (lambda i, fmt=fmt, b=b, vid=vid, pl=pl: codec.unpack_video444(vid[i], fmt, W, H, b, out=pl[i]), moved)
+        work["pack %d -> %s" % (cont, fmt)] = (lambda i, fmt=fmt, b=b, vid=vid, pl=pl: codec.pack_video444(pl[i], fmt, W, H, b, out=vid[i]), moved)
+        new += ["unpack %s -> %d" % (fmt, cont), "pack %d -> %s" % (cont, fmt)]
+    n420 = W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)
+    for cont in (16, 32):
+        total = video420_layout("p010", W, H)[2]
+        vid = [torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda") for _ in range(NSETS)]
+        pl = [torch.randint(0, 1 << DEPTH, (n420,), dtype=torch.int32, device="cuda").to(dts[cont]) for _ in range(NSETS)]
+        moved = total + n420 * (cont // 8)
+        work["unpack p010 -> %d" % cont] = (lambda i, vid=vid, pl=pl: codec.unpack_video420(vid[i], "p010", W, H, DEPTH, out=pl[i]), moved)
+        work["pack %d -> p010" % cont] = (lambda i, vid=vid, pl=pl: codec.pack_video420(pl[i], "p010", W, H, DEPTH, out=vid[i]), moved)
+    yardstick_work(torch, work)
+    rates = timed_rounds(torch, work, rounds, reps)
+    emit("1. kernels, %d x %d, GB/s read + written; %d rounds of %d launches" % (W, H, rounds, reps))
+    out = {}
+    for name, v in rates.items():
+        med, spread = median_spread(v)
+        out[name] = {"GBps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "bytes": work[name][1],
+                     "us_per_launch": round(work[name][1] / med / 1e3, 2)}
+    for name, o in out.items():
+        note = ""
+        if name in new:                                      # the claim of DESIGN 1.5: the rate of the existing kernel with the nearest bytes per launch
+            peers = [k for k in out if k not in new and k.split()[0].split("_")[0] == name.split()[0]]
+            peer = min(peers, key=lambda k: abs(out[k]["bytes"] - o["bytes"]))
+            o["peer"] = peer
+            o["reaches_peer"] = bool(o["median"] >= out[peer]["median"] * (1 - max(o["spread"], out[peer]["spread"])))
+            note = "   %s %s (%.1f)" % ("reaches" if o["reaches_peer"] else "BELOW", peer, out[peer]["median"])
+        emit("  %-40s %s  median %7.1f  spread %4.1f %%  %5.1f MB, %5.1f us per launch%s" %
+             (name, " ".join("%7.1f" % x for x in o["GBps"]), o["median"], o["spread"] * 100, o["bytes"] / 1e6, o["us_per_launch"], note))
+    return out
 
 
 def kernel_rates(torch, rounds, reps, emit, v420=False):
@@ -67,32 +156,8 @@ def kernel_rates(torch, rounds, reps, emit, v420=False):
         moved = total + n * (cont // 8)
         work["unpack %s -> %d" % (fmt, cont)] = (lambda i, fmt=fmt, b=b, vid=vid, pl=pl: codec.unpack_video(vid[i], fmt, W, H, b, out=pl[i]), moved)
         work["pack %d -> %s" % (cont, fmt)] = (lambda i, fmt=fmt, b=b, vid=vid, pl=pl: codec.pack_video(pl[i], fmt, W, H, b, out=vid[i]), moved)
-    L = __import__("openjph_amd.capi", fromlist=["lib"]).lib()
-    import ctypes as C
-    pix = [torch.randint(0, 1 << 15, (H, W, 3), dtype=torch.int16, device="cuda") for _ in range(NSETS)]
-    pla = [torch.empty((3, H, W), dtype=torch.int16, device="cuda") for _ in range(NSETS)]
-    st = codec._stream_ptr(torch, 0)
-
-    def y_unpack(i):
-        codec.check(L.ojphgpu_unpack_pixels(st, C.c_void_p(pix[i].data_ptr()), C.c_void_p(pla[i].data_ptr()), W, H, 3, 16, 0, 16), "unpack_pixels")
-
-    def y_pack(i):
-        codec.check(L.ojphgpu_pack_pixels(st, C.c_void_p(pla[i].data_ptr()), C.c_void_p(pix[i].data_ptr()), W, H, 3, 16, 16, 0, 16), "pack_pixels")
-
-    work["unpack_pixels 3 x 16 -> 16 (yardstick)"] = (y_unpack, 2 * W * H * 3 * 2)
-    work["pack_pixels 16 -> 3 x 16 (yardstick)"] = (y_pack, 2 * W * H * 3 * 2)
-    rates = {k: [] for k in work}
-    for r in range(rounds + 1):                              # round 0: the warm-up
-        for name, (fn, moved) in work.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            fn(0)
-            e0.record()
-            for k in range(reps):
-                fn(k % NSETS)
-            e1.record()
-            e1.synchronize()
-            if r:
-                rates[name].append(moved * reps / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+    yardstick_work(torch, work)
+    rates = timed_rounds(torch, work, rounds, reps)
     out = {}
     emit("1. kernels, %d x %d, GB/s read + written; %d rounds of %d launches" % (W, H, rounds, reps))
     floor = None
@@ -199,6 +264,41 @@ def pipe_rates(rounds, frames, depth, emit, v420=False):
     return out
 
 
+def pipe_rates_444(rounds, frames, depth, emit):
+    """EncoderPipe on the 8K 10-bit 4:4:4 frame three ways, alternating: one v410 buffer, planes in 16-bit containers, the 10-bit
+    string of packed=10"""
+    from bench import workload_image
+    from openjph_amd.pipeline import EncoderPipe, pack_bits, pack_video444
+    from openjph_amd.plan import Plan, make_params
+    img = workload_image("c3_8k_444_12b_irv97")
+    assert img.shape == (3, H, W), img.shape
+    planes = [np.ascontiguousarray(img[c] >> 2) for c in range(3)]
+    mk = lambda: Plan(make_params(W, H, 3, bit_depth=DEPTH, reversible=False))
+    pipes = {"v410": EncoderPipe(plan=mk(), depth=depth, container=16, video="v410"), "planar16": EncoderPipe(plan=mk(), depth=depth, container=16),
+             "packed10": EncoderPipe(plan=mk(), depth=depth, container=16, packed=10)}
+    flat = pipes["planar16"].plan.pack_frame(planes).reshape(-1)
+    chunk = 1 << 22                                          # (a multiple of 32 samples: the chunks' strings follow each other byte-aligned)
+    frame = {"v410": pack_video444(planes, "v410", DEPTH), "planar16": flat,
+             "packed10": np.concatenate([pack_bits(flat[i:i + chunk], 10) for i in range(0, flat.size, chunk)])}
+    first = {way: fill_and_drain(p, frame[way]) for way, p in pipes.items()}
+    assert first["v410"] == first["planar16"] == first["packed10"], "the pipes' codestreams differ"
+    link = {way: p.acquire().nbytes for way, p in pipes.items()}
+    fps = {way: [] for way in pipes}
+    for _ in range(rounds):
+        for way, p in pipes.items():
+            fps[way].append(frames / steady(p, frames))
+    for p in pipes.values():
+        p.close()
+    out = {}
+    emit("2. EncoderPipe, %d x %d 4:4:4 %d-bit 9/7, depth %d, %d frames per round, codestream %d bytes" % (W, H, DEPTH, depth, frames, len(first["v410"])))
+    for way, v in fps.items():
+        med, spread = median_spread(v)
+        out[way] = {"fps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "link_bytes_per_frame": int(link[way])}
+        emit("  %-10s frames/s per round %s  median %7.1f  spread %4.1f %%  %6.1f MB per frame over the link" %
+             (way, " ".join("%7.1f" % x for x in v), med, spread * 100, link[way] / 1e6))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -206,11 +306,13 @@ def main():
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--v420", action="store_true", help="the 4:2:0 kernels and a p010 pipe beside the yardstick and their 4:2:2 peers")
+    ap.add_argument("--v444", action="store_true", help="the 4:4:4 kernels and a v410 pipe beside the yardstick, the P010 kernels, planes and packed=10")
     ap.add_argument("--frame", default=None, metavar="WxH", help="another frame size for the kernels (the pipes are then left out): what a rate owes to the bytes of a launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "video420_bench.txt" if args.v420 else "video_bench.txt")
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "video444_bench.txt" if args.v444 else "video420_bench.txt" if args.v420 else "video_bench.txt")
     global W, H
     if args.frame:
         W, H = (int(v) for v in args.frame.lower().split("x"))
@@ -223,11 +325,14 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
+    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --v444" if args.v444 else " --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
                                                                                      args.depth, torch.cuda.get_device_name(0)))
-    kernels = kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
+    kernels = kernel_rates_444(torch, args.rounds, args.reps, emit) if args.v444 else kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
     torch.cuda.empty_cache()
-    pipes = pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420) if not args.frame else {}
+    if args.frame:
+        pipes = {}
+    else:
+        pipes = pipe_rates_444(args.rounds, args.frames, args.depth, emit) if args.v444 else pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print(json.dumps({"kernels": kernels, "pipes": pipes}))
