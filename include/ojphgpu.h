@@ -863,6 +863,52 @@ int  ojphgpu_encoder_quality_comp(ojphgpu_encoder* enc, uint32_t comp, uint64_t*
 int  ojphgpu_encoder_quality_timing(ojphgpu_encoder* enc, float out[3]);
 
 /* ------------------------------------------------------------------------------------------ *
+ * 5d. Transcoding: a codestream recoded to another packaging, step or byte budget without leaving the coefficient domain.
+ *    T(cs, out) is the codestream a plain encode of the plan `out` writes when its sub-band planes hold what the block
+ *    decoder leaves of `cs`: every code-block of the source decoded and de-quantised as the decoder does (a block that is
+ *    not coded is zero), the planes quantised with out's K_max / delta as the encoder's transfer does (its skip rule
+ *    included), the result block-coded and laid out by Tier-2.  No inverse transform, no samples, no forward transform:
+ *    the block decoder writes the planes of ONE arena and the block coder reads them.
+ *    Two identities follow from the decoder's reconstruction point (q + 0.5) delta: at the source's own step the planes
+ *    quantise back to q, so T is byte for byte the direct encode of the original image with out's packaging; and at a
+ *    step 2^k times the source's, floor((q + 0.5) / 2^k) = floor(q / 2^k), again the direct encode at that step.  A
+ *    reversible source is carried over coefficient by coefficient.  Any other step gives a codestream of its own.
+ *
+ *    ojphgpu_plan_create_transcode (host only): the plan of out_params, checked against the parsed `src`.  out_params =
+ *    ojphgpu_plan_params(src) with only these changed: block_w / block_h, precinct_w / precinct_h / precinct_exps,
+ *    prog_order, tlm, reserved[1] (tile-part divisions), qstep.  OJPHGPU_E_INVALID, no plan: any other difference; a
+ *    differing arena size, or a band whose rectangle, place or pitch differs; a source restricted in resolution or to a
+ *    region; ATK / DFS wavelets, a component on the 64-bit sample path, vertically causal blocks; quality factors; a
+ *    reversible output with qstep > 0; a reversible band whose K_max is below the source's.  An irreversible output with
+ *    qstep <= 0 (a codestream does not carry its base step) is a plan for a transcoder with a byte budget only.
+ * ------------------------------------------------------------------------------------------ */
+int  ojphgpu_plan_create_transcode(const ojphgpu_plan* src, const ojphgpu_params* out_params, ojphgpu_plan** out);
+/* The object: the block decoder of `src` and the block coder of `out` (both outlive it) on one arena -- no frame, no
+ * conversion or DWT descriptors.  OJPHGPU_E_INVALID: plans ojphgpu_plan_create_transcode would not have paired.
+ * _set_budget: as ojphgpu_encoder_set_budget (section 5b) with size(j) = the length of T(cs, out at qstep(j)); what that
+ *   call refuses is refused (a reversible output), 0 switches the budget off.
+ * _submit: parses the codestream (resilient as in ojphgpu_t2_parse), checks it against `src` -- another geometry is
+ *   OJPHGPU_E_INVALID and leaves the object usable --, uploads its block bytes (the host buffer may go when the call
+ *   returns) and enqueues the block decoder as ojphgpu_decoder_run_device chooses it, with a budget the band statistics
+ *   behind it.  OJPHGPU_E_INVALID also for an irreversible output with qstep <= 0 and no budget.
+ * _finish: collects the decode first (as ojphgpu_decoder_failed_blocks does, repeat included); *failed_blocks (may be
+ *   NULL) = the blocks that failed.  A source that was not parsed resiliently with a failed block: OJPHGPU_E_BLOCK, nothing
+ *   written; a resilient one: those blocks are zero.  Then the blocks are coded -- without a budget in the encoder's plain
+ *   schedule, with one by the search of section 5b -- downloaded and written as ojphgpu_encoder_finish writes them
+ *   (OJPHGPU_E_OVERFLOW: *out_len holds the need, call again; OJPHGPU_E_BUDGET leaves the object usable).
+ * _rate_info: ojphgpu_encoder_rate_info of the last budgeted finish.
+ * _timing (ms): out[0] the block decoder, [1] the band statistics (device events of the last submit); [2] search and
+ *   coding, [3] download and Tier-2 (host clock of the last finish). */
+typedef struct ojphgpu_transcoder ojphgpu_transcoder;
+int  ojphgpu_transcoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_transcoder** t);
+int  ojphgpu_transcoder_set_budget(ojphgpu_transcoder* t, uint64_t max_bytes);
+int  ojphgpu_transcoder_submit(ojphgpu_transcoder* t, const uint8_t* h_codestream, size_t len, int resilient);
+int  ojphgpu_transcoder_finish(ojphgpu_transcoder* t, uint8_t* h_out, size_t cap, size_t* out_len, uint32_t* failed_blocks);
+int  ojphgpu_transcoder_rate_info(ojphgpu_transcoder* t, ojphgpu_rate_info* info);
+int  ojphgpu_transcoder_timing(ojphgpu_transcoder* t, float out[4]);
+void ojphgpu_transcoder_destroy(ojphgpu_transcoder* t);
+
+/* ------------------------------------------------------------------------------------------ *
  * 6. Frame pipelines: sequences of frames of one shape with PCIe copies, kernels and host Tier-2 of
  *    consecutive frames overlapped (pinned staging, separate copy-in / compute / copy-out streams).
  *    In the reference one codestream object is re-used across the frames of a sequence through

@@ -376,6 +376,14 @@ SIGNATURES = {
     "ojphgpu_encoder_quality_info": (C.c_int, [C.c_void_p, C.POINTER(QualityInfo)]),
     "ojphgpu_encoder_quality_comp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ojphgpu_encoder_quality_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_plan_create_transcode": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_void_p)]),
+    "ojphgpu_transcoder_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ojphgpu_transcoder_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_transcoder_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    "ojphgpu_transcoder_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "ojphgpu_transcoder_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
+    "ojphgpu_transcoder_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_transcoder_destroy": (None, [C.c_void_p]),
     "ojphgpu_plan_upload_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "ojphgpu_gather_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "ojphgpu_dec_pipe_create_view": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.c_uint32,

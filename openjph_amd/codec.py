@@ -500,6 +500,96 @@ class MultiDecoder:
         return v.copy() if copy else v
 
 
+class Transcoder:
+    """A codestream recoded to another packaging, quantisation step or byte budget without leaving the coefficient domain
+    (ojphgpu_transcoder): the block decoder of the source and the block coder of the output on one arena, no transform and no
+    samples in between.  At the source's own step, or one a whole number of octaves coarser, the result is byte for byte the
+    direct encode of the original image with the output's parameters; a reversible source is carried over as it is."""
+
+    def __init__(self, codestream: bytes, device=0, resilient=False, max_bytes=0, **kw):
+        """codestream: the first source (parsed for the geometry; every later one must have the same).  kw: what changes, as
+        plan.transcode_params takes it (qstep, block, prog_order, precinct, precincts, tlm, tileparts).  max_bytes=N: every
+        source is recoded to a byte budget (set_budget); an irreversible output needs qstep or a budget."""
+        from .plan import transcode_params, transcode_plan
+        torch = _torch()
+        self.device = device
+        self.resilient = bool(resilient)
+        self.src_plan = parse_codestream(codestream, resilient)
+        self.params = transcode_params(self.src_plan, **kw)
+        self.plan = transcode_plan(self.src_plan, self.params)
+        self._lib = capi.lib()
+        self._h = C.c_void_p()
+        with torch.cuda.device(device):
+            check(self._lib.ojphgpu_transcoder_create(self.src_plan.handle, self.plan.handle, device, _stream_ptr(torch, device),
+                                                      C.byref(self._h)), "transcoder_create")
+        self.max_bytes = 0
+        self.failed_blocks = 0
+        self._cs_len = 0
+        if max_bytes:
+            self.set_budget(max_bytes)
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.ojphgpu_transcoder_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def set_budget(self, max_bytes):
+        """Every following source is recoded at the finest step of the rate grid whose codestream is at most max_bytes long
+        (Encoder.set_budget, with the transcode of the source in the place of the encode of a frame); 0 switches it off.
+        Irreversible outputs only."""
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_transcoder_set_budget(self._h, int(max_bytes)), "transcoder_set_budget")
+        self.max_bytes = int(max_bytes)
+
+    def submit(self, codestream: bytes):
+        """parses and uploads the source and enqueues its block decoder (with a budget: the band statistics behind it)"""
+        buf = np.frombuffer(codestream, dtype=np.uint8)
+        self._cs_len = len(codestream)
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_transcoder_submit(self._h, buf.ctypes.data, len(codestream), int(self.resilient)), "transcoder_submit")
+
+    def finish(self) -> bytes:
+        """the output codestream of the source submitted last; failed_blocks = the source's blocks that did not decode (zero
+        blocks of a resilient transcoder; OjphError E_BLOCK otherwise)"""
+        cap = (min(self.max_bytes, self._cs_len * 4) if self.max_bytes else self._cs_len * 2) + 64 * self.plan.num_blocks + (1 << 20)
+        out = np.empty(cap, np.uint8)
+        n, failed = C.c_size_t(), C.c_uint32()
+        with _torch().cuda.device(self.device):
+            rc = self._lib.ojphgpu_transcoder_finish(self._h, out.ctypes.data, cap, C.byref(n), C.byref(failed))
+            if rc == capi.E_OVERFLOW and n.value > cap:
+                cap = int(n.value)
+                out = np.empty(cap, np.uint8)
+                rc = self._lib.ojphgpu_transcoder_finish(self._h, out.ctypes.data, cap, C.byref(n), C.byref(failed))
+        self.failed_blocks = int(failed.value)
+        check(rc, "transcoder_finish")
+        return out[:n.value].tobytes()
+
+    def transcode(self, codestream: bytes) -> bytes:
+        self.submit(codestream)
+        return self.finish()
+
+    def rate_info(self):
+        """what the last budgeted finish() found, as Encoder.rate_info"""
+        info = capi.RateInfo()
+        check(self._lib.ojphgpu_transcoder_rate_info(self._h, C.byref(info)), "transcoder_rate_info")
+        return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+
+    def timing(self):
+        """ms: dict(decode_ms = the block decoder, stats_ms = the band statistics (device events of the last submit), code_ms =
+        search and coding, final_ms = download and Tier-2 (host clock of the last finish))"""
+        t = (C.c_float * 4)()
+        check(self._lib.ojphgpu_transcoder_timing(self._h, t), "transcoder_timing")
+        return dict(decode_ms=t[0], stats_ms=t[1], code_ms=t[2], final_ms=t[3])
+
+
+def transcode(codestream: bytes, device=0, resilient=False, max_bytes=0, **kw) -> bytes:
+    """One-shot helper: codestream -> codestream; keyword args as plan.transcode_params, max_bytes=N: to a byte budget"""
+    return Transcoder(codestream, device=device, resilient=resilient, max_bytes=max_bytes, **kw).transcode(codestream)
+
+
 def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, **kw) -> bytes:
     """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes); max_bytes=N: coded to a byte
     budget (Encoder.set_budget); max_sse=N / min_psnr=dB: coded to a quality target (Encoder.set_quality)."""

@@ -246,6 +246,12 @@ int  rate_rounds_create(const RateTable& T, const uint32_t* hist, size_t hist_pe
 int  requant_frames_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, uint32_t frames, const uint32_t* d_class, const BandQuant* d_quant,
                            uint32_t nclasses);
 
+// Transcoding (include/ojphgpu.h section 5d; ojph_transcode.cpp): a block decoder of S and a block coder of O can share one
+// arena -- both plans unrestricted, Part-1 wavelets and 32-bit samples throughout, the same arena size, and every band with the
+// same rectangle at the same place; a reversible band of O holds the magnitudes of S's (K_max).  S is a parsed plan.
+bool transcode_plans_fit(const Plan& S, const Plan& O);
+inline bool plan_all_reversible(const Plan& P) { for (uint32_t c = 0; c < P.p.num_comps; ++c) if (!P.style(c).rev) return false; return true; }
+
 // Nothing may leave the C ABI as a C++ exception (a codestream from anywhere can ask for tables the
 // host cannot hold): entry points that build containers run their bodies through this.
 template <typename F>

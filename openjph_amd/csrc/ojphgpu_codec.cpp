@@ -74,8 +74,10 @@ extern "C" int ojphgpu_encoder_create(const ojphgpu_plan* plan, int device, void
   return ojphgpu_encoder_create_tiles(plan, device, stream, 0, (uint32_t)plan->plan.tiles.size(), out);
 }
 
+// blocks_only: the encoder half of a transcoder (section 5d) -- the block coder alone: no conversion or DWT descriptors and no
+// arena of its own (its owner lends it one)
 static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count,
-                          uint32_t nframes, ojphgpu_encoder** out);
+                          uint32_t nframes, ojphgpu_encoder** out, bool blocks_only = false);
 
 extern "C" int ojphgpu_encoder_create_tiles(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first,
                                              uint32_t tile_count, ojphgpu_encoder** out)
@@ -171,7 +173,7 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
 }
 
 static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count,
-                          uint32_t nframes, ojphgpu_encoder** out)
+                          uint32_t nframes, ojphgpu_encoder** out, bool blocks_only)
 {
   if (!plan || !out || nframes == 0) return OJPHGPU_E_INVALID;
   *out = nullptr;
@@ -190,12 +192,15 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
   e->nframes = nframes;
   const TileRange tr = e->tiles;
   const uint64_t frame_elems = P.frame_elems;
-  std::vector<ojphgpu_dwt_desc> dd; build_level_batches(P, tr, dd, e->batches);
-  std::vector<ojphgpu_dwt_desc> idd;
-  build_image_level_descs(P, tr, dd, e->batches, idd);
-  replicate_levels(dd, idd, e->batches, nframes, P.arena_elems, frame_elems);
-  std::vector<ojphgpu_convert_desc> cd; e->need_convert = build_convert_descs(P, tr, cd, e->conv_max_w, e->conv_max_h);
-  replicate_converts(cd, nframes, P.arena_elems, P.frame_elems);
+  std::vector<ojphgpu_dwt_desc> dd, idd;
+  std::vector<ojphgpu_convert_desc> cd;
+  if (!blocks_only) {
+    build_level_batches(P, tr, dd, e->batches);
+    build_image_level_descs(P, tr, dd, e->batches, idd);
+    replicate_levels(dd, idd, e->batches, nframes, P.arena_elems, frame_elems);
+    e->need_convert = build_convert_descs(P, tr, cd, e->conv_max_w, e->conv_max_h);
+    replicate_converts(cd, nframes, P.arena_elems, P.frame_elems);
+  }
   e->block_ids = blocks_of_tiles(P, tr);
   if (nframes == 1 && max_recon_decomps(P) >= 2 && getenv("OJPHGPU_NO_OVERLAP") == nullptr) {
     auto top = [&](uint32_t id) { const Band& B = P.bands[P.blocks[id].band]; return B.res == P.style(B.comp).L; };
@@ -244,14 +249,15 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
   encoder_block_layout(e, nullptr, bd, scratch_bytes);
   const uint64_t cap = e->out_cap;
 
-  if (e->arena.alloc(P.arena_elems * 4 * nframes) || e->dwt_descs.alloc(dd.size() * sizeof(dd[0])) ||
-      e->img_descs.alloc(idd.size() * sizeof(dd[0])) || e->cb_descs.alloc(bd.size() * sizeof(bd[0])) || e->conv_descs.alloc(cd.size() * sizeof(cd[0])) ||
+  if ((!blocks_only && (e->arena.alloc(P.arena_elems * 4 * nframes) || e->dwt_descs.alloc(dd.size() * sizeof(dd[0])) ||
+                        e->img_descs.alloc(idd.size() * sizeof(dd[0])) || e->conv_descs.alloc(cd.size() * sizeof(cd[0])))) ||
+      e->cb_descs.alloc(bd.size() * sizeof(bd[0])) ||
       e->scratch.alloc(scratch_bytes) || e->out.alloc(cap) ||
       e->results.alloc(bd.size() * sizeof(ojphgpu_cb_result)) || e->counters.alloc(e->counters_bytes) ||
       (e->nreg && e->regions.alloc(e->h_regions.size() * 4)))
     return bail(OJPHGPU_E_NOMEM);
   if (e->nreg && hipMemcpy(e->regions.p, e->h_regions.data(), e->h_regions.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
-  if (hipMemset(e->arena.p, 0, P.arena_elems * 4 * nframes) != hipSuccess) return bail(OJPHGPU_E_HIP);
+  if (!blocks_only && hipMemset(e->arena.p, 0, P.arena_elems * 4 * nframes) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!dd.empty() && hipMemcpy(e->dwt_descs.p, dd.data(), dd.size() * sizeof(dd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!idd.empty() && hipMemcpy(e->img_descs.p, idd.data(), idd.size() * sizeof(idd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!bd.empty() && hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
@@ -1018,8 +1024,9 @@ extern "C" int ojphgpu_decoder_create(const ojphgpu_plan* plan, int device, void
   return ojphgpu_decoder_create_tiles(plan, device, stream, 0, (uint32_t)plan->plan.tiles.size(), out);
 }
 
+// blocks_only: the decoder half of a transcoder (section 5d) -- the block decoder alone: no level batches, no conversion
 static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, int device, void* stream, uint32_t tile_first,
-                          uint32_t tile_count, ojphgpu_decoder** out);
+                          uint32_t tile_count, ojphgpu_decoder** out, bool blocks_only = false);
 
 extern "C" int ojphgpu_decoder_create_tiles(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first,
                                              uint32_t tile_count, ojphgpu_decoder** out)
@@ -1188,7 +1195,7 @@ int ojphgpu_decoder_upload_pads(hipStream_t s, uint8_t* d_frame_data, const uint
 }
 
 static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, int device, void* stream, uint32_t tile_first,
-                          uint32_t tile_count, ojphgpu_decoder** out)
+                          uint32_t tile_count, ojphgpu_decoder** out, bool blocks_only)
 {
   if (!plans || !plans[0] || !out || nframes == 0) return OJPHGPU_E_INVALID;
   *out = nullptr;
@@ -1214,9 +1221,12 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
   d->nframes = nframes;
   const TileRange tr = d->tiles;
   const uint64_t frame_elems = P.frame_elems;
-  std::vector<ojphgpu_dwt_desc> dd; build_level_batches(P, tr, dd, d->batches);
-  std::vector<ojphgpu_dwt_desc> idd;
-  build_image_level_descs(P, tr, dd, d->batches, idd);
+  d->blocks_only = blocks_only;
+  std::vector<ojphgpu_dwt_desc> dd, idd;
+  if (!blocks_only) {
+    build_level_batches(P, tr, dd, d->batches);
+    build_image_level_descs(P, tr, dd, d->batches, idd);
+  }
   std::vector<ojphgpu_dwt_region> rg, irg;
   d->region = P.has_region;
   if (d->region) {                                          // region synthesis: the levels the region needs, each with its exact range
@@ -1225,7 +1235,8 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
   }
   replicate_levels(dd, idd, d->batches, nframes, P.arena_elems, frame_elems);
   std::reverse(d->batches.begin(), d->batches.end());                 // synthesis: lowest resolution first
-  std::vector<ojphgpu_convert_desc> cd; d->need_convert = build_convert_descs(P, tr, cd, d->conv_max_w, d->conv_max_h);
+  std::vector<ojphgpu_convert_desc> cd;
+  if (!blocks_only) d->need_convert = build_convert_descs(P, tr, cd, d->conv_max_w, d->conv_max_h);
   d->conv_tiles = tile_count; d->tiles_touched = tile_count;
   if (d->region) {
     d->conv_tiles = d->tiles_touched = restrict_converts_to_region(P, tr, cd, d->conv_max_w, d->conv_max_h);
@@ -1433,6 +1444,52 @@ static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, u
   return OJPHGPU_OK;
 }
 
+// The block decoder of a run takes the one launch for step 1 and step 2 (chains first, step-2 workers behind them slice by
+// slice, kernels_ht_dec.hip) when every block is at most 64 samples wide, of one wavelet and without refinement passes -- and
+// where it pays: blocks of 64 rows, few enough for resident workers (ht_decode_fused_pays).  Otherwise: the separate launches.
+static bool decoder_fuses(const ojphgpu_decoder* d)
+{
+  return d->fstate.p && !d->force_separate && !d->fused_off && !d->any_refine && (d->kinds & (3 | 32)) == 1 && ((d->kinds & 12) == 4 || (d->kinds & 12) == 8) &&
+         d->nblocks > 0 && ojphgpu::ht_decode_fused_pays(d->nblocks, d->max_block_h, d->cus);
+}
+
+// ... and its launches on the main stream: the one launch over all blocks, or prep + step 1 of all blocks and step 2 of the
+// first `count` descriptors (the rest is the caller's: decode_samples beside the lower synthesis levels)
+static int decoder_block_launches(ojphgpu_decoder* d, bool fused, uint32_t count)
+{
+  hipStream_t s = d->stream;
+  Spans& T = d->timer;
+  if (fused) {
+    const ojphgpu_cb_desc* cbd = (const ojphgpu_cb_desc*)(d->o_cb_descs ? d->o_cb_descs : d->cb_descs.p);
+    uint8_t* status = (uint8_t*)(d->o_status ? d->o_status : d->status.p);
+    const uint8_t* data = (const uint8_t*)(d->o_data ? d->o_data : d->data.p);
+    const int sp = T.begin(SP_STEP2, s);
+    const int rc = ojphgpu::ht_decode_fused_launch(s, cbd, d->nblocks, data, (uint32_t*)d->quads.p, d->arena.p, status, (uint32_t*)d->fstate.p,
+                                                   ++d->fused_epoch, d->max_block_h, d->kinds, d->cus, d->d_h_retry);
+    if (rc) return rc;
+    d->uncollected = true;
+    T.end(sp, s);
+    return OJPHGPU_OK;
+  }
+  const int rc = decode_chains(d, s);
+  return rc ? rc : decode_samples(d, s, 0, count);
+}
+
+// A run of a blocks-only decoder (the decoder half of a transcoder): the block decoder as ojphgpu_decoder_run_container
+// chooses it, and nothing behind it -- the sub-band planes stay in the arena.  The run's timer is left open for its owner
+// (who may have the band statistics follow) to close.
+static int decoder_run_blocks(ojphgpu_decoder* d)
+{
+  if (!d || !d->blocks_only) return OJPHGPU_E_INVALID;
+  d->timer.start(d->stream);
+  const bool fused = decoder_fuses(d);
+  d->last_fused = fused; d->last_image = nullptr; d->last_container = 0;
+  const int rc = decoder_block_launches(d, fused, d->nblocks);
+  if (rc) return rc;
+  d->ran = true;
+  return OJPHGPU_OK;
+}
+
 int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int container);
 static int decode_host(ojphgpu_decoder* d, const uint8_t* h_codestream, size_t len, void* h_image, int container);
 
@@ -1443,6 +1500,7 @@ extern "C" int ojphgpu_decoder_run_device8(ojphgpu_decoder* d, uint8_t* d_image)
 int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int container)
 {
   if (!d || (!d_image && !(d->region && d->P->frame_elems == 0))) return OJPHGPU_E_INVALID;   // (a region may hold no sample at a reduced resolution)
+  if (d->blocks_only) return OJPHGPU_E_INVALID;             // (a transcoder's half: decoder_run_blocks)
   const Plan& P = *d->P;
   if (container != 32 && container != 16 && container != 8) return OJPHGPU_E_INVALID;
   if (container != 32) for (const CompGeo& g : P.comps) if (g.bit_depth > (uint32_t)container) return OJPHGPU_E_INVALID;
@@ -1464,27 +1522,11 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
   // One launch for step 1 and step 2 (chains first, step-2 workers behind them slice by slice, kernels_ht_dec.hip) when
   // every block is at most 64 samples wide, of one wavelet and without refinement passes -- and where it pays: blocks
   // of 64 rows, few enough for resident workers (ht_decode_fused_pays); the synthesis levels follow on the same stream.  Otherwise: the separate launches, with the lower synthesis levels beside step 2 of the top resolution.
-  const bool fused = d->fstate.p && !d->force_separate && !d->fused_off && !d->any_refine && (d->kinds & (3 | 32)) == 1 && ((d->kinds & 12) == 4 || (d->kinds & 12) == 8) &&
-                     d->nblocks > 0 && ojphgpu::ht_decode_fused_pays(d->nblocks, d->max_block_h, d->cus);
+  const bool fused = decoder_fuses(d);
   d->last_fused = fused; d->last_image = d_image; d->last_container = container;
   const uint32_t n_low = fused ? 0u : d->n_low;
-  int rc;
-  if (fused) {
-    const ojphgpu_cb_desc* cbd = (const ojphgpu_cb_desc*)(d->o_cb_descs ? d->o_cb_descs : d->cb_descs.p);
-    uint8_t* status = (uint8_t*)(d->o_status ? d->o_status : d->status.p);
-    const uint8_t* data = (const uint8_t*)(d->o_data ? d->o_data : d->data.p);
-    const int sp = T.begin(SP_STEP2, s);
-    rc = ojphgpu::ht_decode_fused_launch(s, cbd, d->nblocks, data, (uint32_t*)d->quads.p, d->arena.p, status, (uint32_t*)d->fstate.p,
-                                         ++d->fused_epoch, d->max_block_h, d->kinds, d->cus, d->d_h_retry);
-    if (rc) return rc;
-    d->uncollected = true;
-    T.end(sp, s);
-  } else {
-    rc = decode_chains(d, s);
-    if (rc) return rc;
-    rc = decode_samples(d, s, 0, n_low ? n_low : d->nblocks);
-    if (rc) return rc;
-  }
+  int rc = decoder_block_launches(d, fused, n_low ? n_low : d->nblocks);
+  if (rc) return rc;
   if (n_low) {                                              // fork: the lower synthesis levels on the side stream
     HIPCHK(hipEventRecord(d->ev_fork, s));
     HIPCHK(hipStreamWaitEvent(d->side, d->ev_fork, 0));
@@ -1555,9 +1597,10 @@ extern "C" int ojphgpu_decoder_set_timing(ojphgpu_decoder* d, int per_launch)
 // the run that has just been enqueued again, through the separate step 1 / step 2 launches (a fused launch asked for it)
 int ojphgpu_decoder_repeat_separate(ojphgpu_decoder* d)
 {
-  if (!d || !d->last_image) return OJPHGPU_E_INVALID;
+  if (!d || (!d->last_image && !d->blocks_only)) return OJPHGPU_E_INVALID;
   d->force_separate = true;
-  const int rc = ojphgpu_decoder_run_container(d, d->last_image, d->last_container);
+  int rc = d->blocks_only ? decoder_run_blocks(d) : ojphgpu_decoder_run_container(d, d->last_image, d->last_container);
+  if (d->blocks_only && rc == OJPHGPU_OK) d->timer.finish(d->stream);
   d->force_separate = false;
   d->fused_retries++;
   return rc;
@@ -1672,5 +1715,184 @@ extern "C" int ojphgpu_decoder_level_timing(ojphgpu_decoder* d, float* out, uint
   int k = d->timer.read_each(SP_DWT, out, cap);
   if (k < 0) return OJPHGPU_E_HIP;
   *n = (uint32_t)k;
+  return OJPHGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// transcoding (include/ojphgpu.h section 5d): the decoder's first half and the encoder's second half on one arena
+// ---------------------------------------------------------------------------------------------
+extern "C" void ojphgpu_transcoder_destroy(ojphgpu_transcoder* t)
+{
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  (void)hipStreamSynchronize(t->stream);
+  if (t->enc) {
+    if (t->enc->side) (void)hipStreamSynchronize(t->enc->side);
+    t->enc->arena.p = nullptr;                              // the decoder's
+    ojphgpu_encoder_destroy(t->enc);
+  }
+  if (t->dec) ojphgpu_decoder_destroy(t->dec);
+  delete t;
+}
+
+extern "C" int ojphgpu_transcoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_transcoder** tout)
+{
+  if (!src || !out || !tout) return OJPHGPU_E_INVALID;
+  *tout = nullptr;
+  return no_throw([&]() -> int {
+    const Plan& S = src->plan; const Plan& O = out->plan;
+    if (!transcode_plans_fit(S, O)) return OJPHGPU_E_INVALID;
+    ojphgpu_transcoder* t = new ojphgpu_transcoder();
+    struct Owner { ojphgpu_transcoder* p; ~Owner() { if (p) ojphgpu_transcoder_destroy(p); } } owner{ t };
+    t->S = &S; t->O = &O; t->device = device; t->stream = (hipStream_t)stream;
+    const uint32_t ntiles = (uint32_t)S.tiles.size();
+    int rc = decoder_create(&src, 1, device, stream, 0, ntiles, &t->dec, true);
+    if (rc) return rc;
+    if ((rc = encoder_create(out, device, stream, 0, ntiles, 1, &t->enc, true)) != 0) return rc;
+    ojphgpu_decoder* d = t->dec;
+    t->enc->arena.p = d->arena.p;                           // one arena: the block decoder writes the planes the block coder reads
+    // the flat VLC / MEL strings of any later source fit: the worst case of every block (Lcup <= 4079 + slack)
+    const uint64_t worst = (uint64_t)d->block_ids.size() * ojphgpu_ht_decode_aux_words(4079) + 64;
+    d->aux.release();
+    if (d->aux.alloc((size_t)worst * 4 + 64)) return OJPHGPU_E_NOMEM;
+    t->h_descs.resize(d->block_ids.size());
+    owner.p = nullptr;
+    *tout = t;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_transcoder_set_budget(ojphgpu_transcoder* t, uint64_t max_bytes)
+{
+  if (!t) return OJPHGPU_E_INVALID;
+  HIPCHK(hipSetDevice(t->device));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const int rc = ojphgpu_encoder_set_budget(t->enc, max_bytes);
+  if (rc == OJPHGPU_OK) t->stage = 0;                       // (a source submitted under the other mode is dropped)
+  return rc;
+}
+
+// the band statistics of the planes the block decoder leaves: what the search's model starts from
+static int transcoder_stats(ojphgpu_transcoder* t)
+{
+  ojphgpu_decoder* d = t->dec; ojphgpu_encoder* e = t->enc;
+  EncoderRate& R = *e->rate;
+  hipStream_t s = t->stream;
+  HIPCHK(hipMemsetAsync(R.hist.p, 0, R.hist.n, s));
+  const int sp = d->timer.begin(SP_STATS, s);
+  const int rc = ojphgpu_band_stats(s, (const ojphgpu_stats_desc*)R.stats_descs.p, R.n_stats, R.stats_max_w, R.stats_max_h, e->arena.p, (uint32_t*)R.hist.p);
+  if (rc) return rc;
+  d->timer.end(sp, s);
+  R.searched = false;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_transcoder_submit(ojphgpu_transcoder* t, const uint8_t* h_codestream, size_t len, int resilient)
+{
+  if (!t || !h_codestream || len == 0) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    ojphgpu_decoder* d = t->dec; ojphgpu_encoder* e = t->enc;
+    const Plan& S = *t->S; const Plan& O = *t->O;
+    hipStream_t s = t->stream;
+    const bool budget = !e->budgets.empty();
+    if (!budget && !plan_all_reversible(O) && !(O.p.qstep > 0.0f)) return OJPHGPU_E_INVALID;   // no step and no budget
+    HIPCHK(hipSetDevice(t->device));
+    ojphgpu_plan* q = nullptr;
+    int rc = ojphgpu_t2_parse(h_codestream, len, resilient, &q);
+    if (rc) return rc;
+    struct Hold { ojphgpu_plan* q; ~Hold() { ojphgpu_plan_destroy(q); } } hold{ q };
+    const Plan& Q = q->plan;
+    if ((rc = ojphgpu_same_frame_geometry(S, Q, true)) != 0) return rc;
+    for (uint32_t c = 0; c < Q.p.num_comps; ++c) if (Q.style(c).causal) return OJPHGPU_E_INVALID;
+    for (size_t i = 0; i < Q.bands.size(); ++i)               // (K_max is this frame's own: transcode_plans_fit saw the first frame's)
+      if (Q.style(Q.bands[i].comp).rev && O.bands[i].K_max < Q.bands[i].K_max) return OJPHGPU_E_INVALID;
+    const size_t nb = d->block_ids.size();
+    ojphgpu_cb_desc* bd = t->h_descs.data();
+    // the launches of the last source have read what is replaced now (descriptors on the host and on the device, the bytes)
+    HIPCHK(hipStreamSynchronize(s));
+    if (e->side) HIPCHK(hipStreamSynchronize(e->side));
+    DecFrameInfo fi;
+    ojphgpu_decoder_fill_descs(S, Q, d->block_ids, 0, 0, bd, fi);
+    uint64_t nquads = 0, naux = 0;
+    if (ojphgpu_ht_decode_layout(bd, (uint32_t)nb, &nquads, &naux) != OJPHGPU_OK) return OJPHGPU_E_INVALID;
+    if ((naux + 16) * 4 > d->aux.n || (nquads + 16) * 4 > d->quads.n) return OJPHGPU_E_INVALID;     // sized for the worst case at create
+    if (fi.first + fi.len > len) return OJPHGPU_E_CODESTREAM;
+    t->stage = 0;
+    const size_t need = (size_t)fi.data_bytes() + 128;
+    if (need > d->data.n) {
+      d->data.release();
+      if (d->data.alloc(need + need / 4)) return OJPHGPU_E_NOMEM;
+    }
+    if (fi.len) HIPCHK(hipMemcpyAsync(d->data.p, h_codestream + fi.first, (size_t)fi.len, hipMemcpyHostToDevice, s));
+    if ((rc = ojphgpu_decoder_upload_pads(s, (uint8_t*)d->data.p, h_codestream, len, fi.pads)) != 0) return rc;
+    if (nb) HIPCHK(hipMemcpyAsync(d->cb_descs.p, bd, nb * sizeof(ojphgpu_cb_desc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));                        // the caller's codestream may go
+    d->any_refine = fi.any_refine; d->kinds = fi.kinds; d->max_len1 = fi.max_len1;
+    if ((rc = decoder_run_blocks(d)) != 0) return rc;
+    if (budget && (rc = transcoder_stats(t)) != 0) return rc;
+    d->timer.finish(s);
+    e->ran = false; e->fetched = false;
+    t->resilient = resilient != 0; t->failed = 0; t->code_ms = t->final_ms = 0;
+    t->stage = 1;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_transcoder_finish(ojphgpu_transcoder* t, uint8_t* h_out, size_t cap, size_t* out_len, uint32_t* failed_blocks)
+{
+  if (!t || !out_len || t->stage == 0) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    ojphgpu_decoder* d = t->dec; ojphgpu_encoder* e = t->enc;
+    hipStream_t s = t->stream;
+    HIPCHK(hipSetDevice(t->device));
+    const bool budget = !e->budgets.empty();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    int rc;
+    if (t->stage == 1) {
+      // the verdicts first (and the repeat of a one-launch run whose wait ran out): only then is a block coded
+      const uint32_t repeats = d->fused_retries;
+      if ((rc = ojphgpu_decoder_failed_blocks(d, &t->failed)) != 0) { t->stage = 0; return rc; }
+      if (failed_blocks) *failed_blocks = t->failed;
+      if (t->failed && !t->resilient) { t->stage = 0; return OJPHGPU_E_BLOCK; }
+      const auto t0 = now();
+      if (budget) {
+        // (the statistics of a repeated run were taken over planes the repeat has written again)
+        if (d->fused_retries != repeats && (rc = transcoder_stats(t)) != 0) { t->stage = 0; return rc; }
+      } else {
+        BlockCoderRun coder{ e, (uint8_t*)e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, (uint32_t)e->block_ids.size(), &e->timer };
+        e->timer.start(s);
+        if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) { t->stage = 0; return rc; }
+        e->timer.finish(s);
+        HIPCHK(hipStreamSynchronize(s));
+        t->code_ms = ms(t0, now());
+      }
+      e->ran = true; e->fetched = false;
+      t->stage = 2;
+    }
+    if (failed_blocks) *failed_blocks = t->failed;
+    const auto t1 = now();
+    rc = ojphgpu_encoder_finish(e, h_out, cap, out_len);
+    if (budget && e->rate->searched) { t->code_ms = e->rate->search_ms; t->final_ms = e->rate->final_ms; }
+    else t->final_ms = ms(t1, now());
+    if (rc != OJPHGPU_E_OVERFLOW) t->stage = 0;             // (too small a buffer: *out_len holds the need, the call may be repeated)
+    return rc;
+  });
+}
+
+extern "C" int ojphgpu_transcoder_rate_info(ojphgpu_transcoder* t, ojphgpu_rate_info* info)
+{
+  if (!t) return OJPHGPU_E_INVALID;
+  return ojphgpu_encoder_rate_info(t->enc, info);
+}
+
+extern "C" int ojphgpu_transcoder_timing(ojphgpu_transcoder* t, float out[4])
+{
+  if (!t || !out || !t->dec->ran) return OJPHGPU_E_INVALID;
+  HIPCHK(hipStreamSynchronize(t->stream));
+  Spans& T = t->dec->timer;
+  float a = 0, b = 0, c = 0, r = 0;
+  if (T.read(SP_PREP, &a) || T.read(SP_STEP1, &b) || T.read(SP_STEP2, &c) || T.read(SP_REFINE, &r) || T.read(SP_STATS, &out[1])) return OJPHGPU_E_HIP;
+  out[0] = a + b + c + r; out[2] = (float)t->code_ms; out[3] = (float)t->final_ms;
   return OJPHGPU_OK;
 }

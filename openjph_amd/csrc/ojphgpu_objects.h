@@ -640,6 +640,21 @@ struct ojphgpu_decoder {
   std::vector<uint32_t> block_ids;                 // plan-order index of each block descriptor (per frame)
   // what a run reads: the object's own buffers (null), or those of a frame pipeline's slot
   const void* o_cb_descs = nullptr; const void* o_data = nullptr; void* o_status = nullptr;
+  // the decoder half of a transcoder (section 5d): the block decoder alone -- no level batches, no conversion, no frame; a
+  // run ends with the sub-band planes in the arena
+  bool blocks_only = false;
+};
+// A transcoder: the block decoder of the source plan and the block coder of the output plan on the decoder's arena (the
+// encoder is created without one and borrows it: enc->arena.p is not the encoder's to free)
+struct ojphgpu_transcoder {
+  ojphgpu_decoder* dec = nullptr; ojphgpu_encoder* enc = nullptr;
+  const Plan* S = nullptr; const Plan* O = nullptr;
+  int device = 0; hipStream_t stream = nullptr;
+  std::vector<ojphgpu_cb_desc> h_descs;            // this frame's block descriptors
+  int stage = 0;                                   // 0 idle, 1 submitted, 2 collected and coded (a finish may be repeated)
+  bool resilient = false;                          // how the submitted source was parsed
+  uint32_t failed = 0;
+  double code_ms = 0, final_ms = 0;
 };
 struct DecFrameInfo {
   std::vector<DecRun> runs;                                  // region decoders: the runs; first = 0, len = the bytes staged

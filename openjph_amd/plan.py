@@ -423,6 +423,42 @@ def rate_predict(plan: Plan, hist):
     return out
 
 
+def transcode_params(src_plan: Plan, qstep=None, block=None, prog_order=None, precinct=None, precincts=None, tlm=None, tileparts=None):
+    """The parameters of a transcode's output: those of the parsed `src_plan` with only what may change changed -- qstep (an
+    irreversible output needs one, or a byte budget: a codestream does not carry its base step), block=(w, h),
+    prog_order, precinct=(w, h) or precincts=[(w, h), ...] from the lowest resolution up, tlm, tileparts ("", "R", "C",
+    "RC").  None keeps the source's."""
+    p = Params.from_buffer_copy(src_plan.params)
+    if qstep is not None:
+        p.qstep = float(qstep)
+    if block is not None:
+        p.block_w, p.block_h = block
+    if prog_order is not None:
+        p.prog_order = PROG_ORDERS[prog_order] if isinstance(prog_order, str) else int(prog_order)
+    if precinct is not None or precincts is not None:
+        p.precinct_w, p.precinct_h = precinct if precinct is not None else (0, 0)
+        for i in range(36):
+            p.precinct_exps[i] = 0
+        if precincts:
+            for i in range(int(p.num_decomps) + 1):
+                pw, ph = precincts[min(i, len(precincts) - 1)]
+                p.precinct_exps[i] = (int(pw).bit_length() - 1) | ((int(ph).bit_length() - 1) << 4)
+    if tlm is not None:
+        p.tlm = int(bool(tlm))
+    if tileparts is not None:
+        p.reserved[1] = (1 if "R" in tileparts else 0) | (2 if "C" in tileparts else 0)
+    return p
+
+
+def transcode_plan(src_plan: Plan, params) -> Plan:
+    """ojphgpu_plan_create_transcode: the plan of `params` (transcode_params) checked against the parsed source -- the same
+    frame, components, wavelet and decompositions, every band at the same place in the arena.  OjphError E_INVALID
+    otherwise."""
+    h = C.c_void_p()
+    check(capi.lib().ojphgpu_plan_create_transcode(src_plan.handle, C.byref(params), C.byref(h)), "plan_create_transcode")
+    return Plan(handle=h)
+
+
 def parse_codestream(data: bytes, resilient=False, skip=None) -> Plan:
     """skip = (skipped_res_for_data, skipped_res_for_recon): restrict_input_resolution BEFORE the tile-parts are read, as the
     reference orders it (ojphgpu_t2_parse_restricted) -- on undamaged codestreams the same as Plan.restrict_resolution afterwards"""
