@@ -456,6 +456,36 @@ int ojphgpu_ht_decode_step1(void* stream, const ojphgpu_cb_desc* d_blocks, uint3
 int ojphgpu_ht_decode_step2(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
                             const uint8_t* d_data, const uint32_t* d_quad_scratch, void* d_coef,
                             uint8_t* d_block_status);
+/* The separate launches as a stage: step 2 with the caller's knowledge of the blocks, and what will run (host only).
+ * `kinds` says what the blocks of a range are, OR-ed over the blocks; 0 = nothing is known, always valid:
+ *   bit 0 (1)    blocks of at most 64 columns occur          bit 1 (2)    blocks of more than 64 columns occur
+ *   bit 2 (4)    reversible blocks occur                     bit 3 (8)    irreversible blocks occur
+ *   bit 4 (16)   blocks with SigProp / MagRef passes occur (num_passes > 1 and len2 > 0)
+ *   bit 5 (32)   blocks on the 64-bit sample path occur (cb_desc.reversible bit 2; these launches skip them, the bit chooses nothing)
+ *   bit 6 (64)   blocks of more than 32 columns occur        bit 7 (128)  blocks of more than 16 columns occur
+ *   bit 8 (256)  bits 6 and 7 are filled in: only with it SET does a clear bit 6 / 7 mean "every block is at most 32 / 16 wide"
+ * ojphgpu_ht_decode_kinds: host only -- the kinds of h_blocks[0 .. n), the statement of the bits the decoder objects use too.
+ * The kernels are specialised by it (one transfer, narrow blocks, two or four blocks of at most 32 / 16 columns to a wavefront)
+ * and a specialised kernel leaves alone or mis-decodes a block it was told does not occur.  So a caller may know LESS than
+ * ojphgpu_ht_decode_kinds says, never more.  The valid coarsenings of a truthful value, in any combination:
+ *   - set bit 7, or bits 6 and 7: two blocks, or one, to a wavefront where the truth allows four, or two;
+ *   - clear bit 8: one block to a wavefront;
+ *   - set both bits 2 and 3: the kernel that reads each block's transfer from its descriptor (also what bit 4 selects);
+ *   - set bit 1: the kernel that also takes blocks of up to 128 columns.
+ * Clearing any of bits 0..4, 6, 7 that ojphgpu_ht_decode_kinds sets, or setting bit 8 where it was not computed, is invalid.
+ * ojphgpu_ht_decode_step2_kinds: ojphgpu_ht_decode_step2 (== kinds 0) with that knowledge.
+ * ojphgpu_ht_decode_launches: host only, no HIP call -- what ojphgpu_ht_decode_step1 and ojphgpu_ht_decode_step2_kinds launch
+ *   for n blocks of `kinds` under this process's OJPHGPU_S1_CH / OJPHGPU_DEC_PREP / OJPHGPU_DEC_DUAL (read once); both take
+ *   their choice from it.  out[0] step 1 reads prep's flat strings (1: ht_dec_step1_kernel) or the raw bytes (0:
+ *   ht_dec_step1_raw_kernel; ojphgpu_ht_decode_prep then launches nothing), [1] its CH (64 CH blocks per workgroup), [2] its
+ *   workgroups; [3] step 2 is ht_dec_step2_multi_kernel<TX, NB> (1) or ht_dec_step2_kernel<TX, WD> (0), [4] TX (0: per block,
+ *   1 reversible, 2 irreversible), [5] WD (1: no block wider than 64), [6] NB blocks per wavefront (1 for the single kernel),
+ *   [7] its workgroups, [8] blocks per workgroup.  `out` holds 9 values. */
+int ojphgpu_ht_decode_kinds(const ojphgpu_cb_desc* h_blocks, uint32_t n, int* kinds);
+int ojphgpu_ht_decode_step2_kinds(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
+                                  const uint8_t* d_data, const uint32_t* d_quad_scratch, void* d_coef,
+                                  uint8_t* d_block_status, int kinds);
+int ojphgpu_ht_decode_launches(uint32_t n, int kinds, uint32_t* out);
 /* Step 1 and step 2 in ONE launch (ht_dec_fused_kernel, what the decoder objects take for blocks of at most 64 columns
  * without refinement passes where it pays), as a stage of its own.
  * ojphgpu_ht_decode_fused_shape: host only -- how the launch deals n blocks out on `cus` compute units (0: 256) under the

@@ -261,7 +261,11 @@ SIGNATURES = {
                                           C.c_void_p]),
     "ojphgpu_ht_decode_step2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
-    "ojphgpu_ht_decode_fused_shape": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ojphgpu_ht_decode_kinds": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    "ojphgpu_ht_decode_step2_kinds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int]),
+    "ojphgpu_ht_decode_launches": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    "ojphgpu_ht_decode_fused_shape": (C.c_int,[C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ojphgpu_ht_decode_fused_slices": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
     "ojphgpu_ht_decode_fused_state_words": (C.c_uint64, [C.c_uint32]),
     "ojphgpu_ht_decode_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

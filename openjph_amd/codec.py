@@ -814,6 +814,65 @@ def ht_decode(descs: np.ndarray, data: np.ndarray, coef):
     return status.cpu().numpy()[:len(descs)]
 
 
+def ht_decode_kinds(descs: np.ndarray):
+    """what the blocks of `descs` are, as the `kinds` of ojphgpu_ht_decode_step2_kinds (host only; include/ojphgpu.h)"""
+    descs = np.ascontiguousarray(descs)
+    k = C.c_int()
+    check(capi.lib().ojphgpu_ht_decode_kinds(descs.ctypes.data if len(descs) else None, len(descs), C.byref(k)), "ht_decode_kinds")
+    return int(k.value)
+
+
+def ht_decode_launches(n, kinds=0):
+    """what the separate launches over n blocks of `kinds` are under this process's OJPHGPU_S1_CH / OJPHGPU_DEC_PREP /
+    OJPHGPU_DEC_DUAL (host only): dict of prep, ch, wgs1 (step 1: form, CH, workgroups), multi, tx, wd, nb, wgs2, per_wg
+    (step 2: multi or single kernel, its TX, WD, NB, workgroups, blocks per workgroup)"""
+    out = (C.c_uint32 * 9)()
+    check(capi.lib().ojphgpu_ht_decode_launches(int(n), int(kinds), out), "ht_decode_launches")
+    return dict(zip(("prep", "ch", "wgs1", "multi", "tx", "wd", "nb", "wgs2", "per_wg"), (int(v) for v in out)))
+
+
+class SeparateScratch:
+    """The scratch of the separate launches (prep, step 1, step 2) for up to max_blocks blocks, quad_elems record words and
+    aux_elems words of flat strings: allocated and zeroed once, here, never again -- a run finds what the runs before left."""
+
+    def __init__(self, max_blocks, quad_elems, aux_elems, device=0):
+        torch = _torch()
+        dev = torch.device("cuda", device)
+        self.max_blocks, self.quad_elems, self.aux_elems, self.device, self.runs = int(max_blocks), int(quad_elems), int(aux_elems), device, 0
+        self.quads = torch.zeros(self.quad_elems + 16, dtype=torch.int32, device=dev)
+        self.aux = torch.zeros(self.aux_elems + 16, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(self.max_blocks + 16, dtype=torch.uint8, device=dev)
+
+
+def ht_decode_separate(descs: np.ndarray, data: np.ndarray, coef, scratch: SeparateScratch, kinds=None):
+    """prep, step 1 and step 2 of `descs` (cleanup passes only: no refinement launch, no 64-bit path) on a scratch that
+    earlier runs have used, step 2 with `kinds` (None: what ht_decode_kinds says of these blocks; a caller may pass a valid
+    coarsening of that, include/ojphgpu.h); returns status[:n]"""
+    torch = _torch()
+    dev = coef.device.index
+    L = capi.lib()
+    n = len(descs)
+    descs = np.ascontiguousarray(descs.copy())
+    q, a = C.c_uint64(), C.c_uint64()
+    check(L.ojphgpu_ht_decode_layout(descs.ctypes.data, n, C.byref(q), C.byref(a)), "ht_decode_layout")
+    if n > scratch.max_blocks or int(q.value) > scratch.quad_elems or int(a.value) > scratch.aux_elems or dev != scratch.device:
+        raise ValueError("the SeparateScratch is too small for this launch or on another device")
+    if kinds is None:
+        kinds = ht_decode_kinds(descs)
+    d = to_device(descs, dev)
+    dd = to_device(np.concatenate([np.asarray(data, np.uint8), np.zeros(64, np.uint8)]), dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        s = _stream_ptr(torch, dev)
+        check(L.ojphgpu_ht_decode_prep(s, ptr(d), n, ptr(dd), ptr(scratch.aux)), "ht_decode_prep")
+        check(L.ojphgpu_ht_decode_step1(s, ptr(d), n, ptr(dd), ptr(scratch.aux), ptr(scratch.quads), ptr(scratch.status)), "ht_decode_step1")
+        check(L.ojphgpu_ht_decode_step2_kinds(s, ptr(d), n, ptr(dd), ptr(scratch.quads), ptr(coef), ptr(scratch.status), int(kinds)),
+              "ht_decode_step2_kinds")
+    scratch.runs += 1
+    torch.cuda.synchronize(dev)
+    return scratch.status.cpu().numpy()[:n].copy()
+
+
 def ht_decode_fused_shape(n, cus=0):
     """how the fused launch deals n blocks out on `cus` compute units under this process's OJPHGPU_FUSED_SHAPE / _RINGS
     (host only): dict of shape, ch, wgw, n1, per_wave, wwgs, nr, able (n1 <= cus), want (per_wave before the cap of 8)"""

@@ -53,6 +53,16 @@ int ht_decode64_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n
                        uint32_t* d_quad_scratch, void* d_coef, uint8_t* d_block_status, int refine);
 int ht_decode_step2_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const uint8_t* d_data,
                            const uint32_t* d_quad_scratch, void* d_coef, uint8_t* d_block_status, int kinds);
+// The `kinds` bits of ONE block, from its descriptor's w, reversible, num_passes and len2 (include/ojphgpu.h,
+// ojphgpu_ht_decode_step2_kinds, says what they mean); a range's kinds are its blocks' OR-ed.  The one statement of the bits:
+// the decoder objects (ojphgpu_decoder_fill_descs) and ojphgpu_ht_decode_kinds both come here.  Bit 5: the block is on the
+// 64-bit sample path and none of the launches above is for it (the callers take it out before they launch).
+inline int ht_decode_block_kinds(uint32_t w, uint32_t reversible, uint32_t num_passes, uint32_t len2)
+{
+  const int refine = (num_passes > 1u && len2 > 0u) ? 16 : 0;
+  if (reversible & 4u) return refine | 32;
+  return refine | (w > 64u ? 2 : 1) | ((reversible & 1u) ? 4 : 8) | (w > 32u ? 64 : 0) | (w > 16u ? 128 : 0) | 256;   // 256: the width bits 6 / 7 are filled in
+}
 
 }  // namespace ojphgpu
 #endif

@@ -2344,6 +2344,53 @@ extern "C" int ojphgpu_ht_decode_prep(void* stream, const ojphgpu_cb_desc* d_blo
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 
+namespace ojphgpu {
+// What the separate launches over n blocks are, under this process's OJPHGPU_S1_CH / OJPHGPU_DEC_PREP / OJPHGPU_DEC_DUAL and
+// with the caller's knowledge `kinds` of the blocks (ht_decode_block_kinds, ht_tables.h): the one place that chooses;
+// ojphgpu_ht_decode_step1, ht_decode_step2_launch and ojphgpu_ht_decode_launches all ask here.
+struct DecLaunches {
+  uint32_t prep, ch, wgs1;                  // step 1: ht_dec_step1_kernel<ch> on prep's strings (1) or ht_dec_step1_raw_kernel<ch> (0); workgroups
+  uint32_t multi, tx, wd, nb, wgs2, per_wg; // step 2: ht_dec_step2_multi_kernel<tx, nb> (1) or ht_dec_step2_kernel<tx, wd> (0, nb 1); workgroups; blocks each
+};
+static DecLaunches dec_launches(uint32_t n, int kinds)
+{
+  static const int ch = [] { const char* e = getenv("OJPHGPU_S1_CH"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 ? v : 4; }();
+  // two (four) blocks to a wavefront where every block of the range is at most 32 (16) columns wide (kinds bit 6 (7) clear;
+  // OJPHGPU_DEC_DUAL=0: never, =2: two at most)
+  static const int dual = [] { const char* e = getenv("OJPHGPU_DEC_DUAL"); return e ? atoi(e) : 4; }();
+  DecLaunches L;
+  L.prep = dec_uses_prep() ? 1u : 0u;
+  L.ch = (uint32_t)ch;
+  const uint32_t sets = (n + 63u) / 64u;
+  L.wgs1 = (sets + L.ch - 1u) / L.ch;
+  L.tx = (kinds & 16) ? 0u : (kinds & 12) == 4 ? 1u : (kinds & 12) == 8 ? 2u : 0u;
+  L.wd = (kinds & 3) == 1 ? 1u : 0u;
+  L.multi = (dual && (kinds & 256) && !(kinds & 64) && L.wd && (L.tx == 1u || L.tx == 2u)) ? 1u : 0u;
+  L.nb = !L.multi ? 1u : (!(kinds & 128) && dual >= 4) ? 4u : 2u;
+  L.per_wg = L.nb * (uint32_t)WAVES;
+  L.wgs2 = ((n + L.nb - 1u) / L.nb + (uint32_t)WAVES - 1u) / (uint32_t)WAVES;
+  return L;
+}
+}  // namespace ojphgpu
+
+extern "C" int ojphgpu_ht_decode_launches(uint32_t n, int kinds, uint32_t* out)
+{
+  if (!out) return OJPHGPU_E_INVALID;
+  const ojphgpu::DecLaunches L = ojphgpu::dec_launches(n, kinds);
+  out[0] = L.prep; out[1] = L.ch; out[2] = L.wgs1; out[3] = L.multi; out[4] = L.tx; out[5] = L.wd; out[6] = L.nb; out[7] = L.wgs2;
+  out[8] = L.per_wg;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_ht_decode_kinds(const ojphgpu_cb_desc* h_blocks, uint32_t n, int* kinds)
+{
+  if (!kinds || (!h_blocks && n)) return OJPHGPU_E_INVALID;
+  int k = 0;
+  for (uint32_t i = 0; i < n; ++i) k |= ojphgpu::ht_decode_block_kinds(h_blocks[i].w, h_blocks[i].reversible, h_blocks[i].num_passes, h_blocks[i].len2);
+  *kinds = k;
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_ht_decode_step1(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
                                         const uint8_t* d_data, const uint32_t* d_aux, uint32_t* d_quad_scratch,
                                         uint8_t* d_block_status)
@@ -2351,50 +2398,42 @@ extern "C" int ojphgpu_ht_decode_step1(void* stream, const ojphgpu_cb_desc* d_bl
   if (n == 0) return OJPHGPU_OK;
   if (ojphgpu::ensure_tables() != 0) return OJPHGPU_E_HIP;
   if (!d_blocks || !d_data || !d_aux || !d_quad_scratch || !d_block_status) return OJPHGPU_E_INVALID;
-  static const int ch = [] { const char* e = getenv("OJPHGPU_S1_CH"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 ? v : 4; }();
-  const uint32_t sets = (n + 63) / 64;
-  if (!ojphgpu::dec_uses_prep()) {
-    if (ch == 4) hipLaunchKernelGGL(ht_dec_step1_raw_kernel<4>, dim3((sets + 3) / 4), dim3(768), 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, d_block_status);
-    else if (ch == 2) hipLaunchKernelGGL(ht_dec_step1_raw_kernel<2>, dim3((sets + 1) / 2), dim3(384), 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, d_block_status);
-    else hipLaunchKernelGGL(ht_dec_step1_raw_kernel<1>, dim3(sets), dim3(192), 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, d_block_status);
+  const ojphgpu::DecLaunches L = ojphgpu::dec_launches(n, 0);
+  const dim3 grid(L.wgs1);
+  if (!L.prep) {
+    if (L.ch == 4) hipLaunchKernelGGL(ht_dec_step1_raw_kernel<4>, grid, dim3(768), 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, d_block_status);
+    else if (L.ch == 2) hipLaunchKernelGGL(ht_dec_step1_raw_kernel<2>, grid, dim3(384), 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, d_block_status);
+    else hipLaunchKernelGGL(ht_dec_step1_raw_kernel<1>, grid, dim3(192), 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, d_block_status);
     return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
   }
-  if (ch == 4) hipLaunchKernelGGL(ht_dec_step1_kernel<4>, dim3((sets + 3) / 4), dim3(512), 0, (hipStream_t)stream, d_blocks, n, d_data, d_aux, d_quad_scratch, d_block_status);
-  else if (ch == 2) hipLaunchKernelGGL(ht_dec_step1_kernel<2>, dim3((sets + 1) / 2), dim3(256), 0, (hipStream_t)stream, d_blocks, n, d_data, d_aux, d_quad_scratch, d_block_status);
-  else hipLaunchKernelGGL(ht_dec_step1_kernel<1>, dim3(sets), dim3(128), 0, (hipStream_t)stream, d_blocks, n, d_data, d_aux, d_quad_scratch, d_block_status);
+  if (L.ch == 4) hipLaunchKernelGGL(ht_dec_step1_kernel<4>, grid, dim3(512), 0, (hipStream_t)stream, d_blocks, n, d_data, d_aux, d_quad_scratch, d_block_status);
+  else if (L.ch == 2) hipLaunchKernelGGL(ht_dec_step1_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, d_blocks, n, d_data, d_aux, d_quad_scratch, d_block_status);
+  else hipLaunchKernelGGL(ht_dec_step1_kernel<1>, grid, dim3(128), 0, (hipStream_t)stream, d_blocks, n, d_data, d_aux, d_quad_scratch, d_block_status);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 
 namespace ojphgpu {
-// kinds: what the caller knows about the blocks of the range (0 = nothing): bit 0 blocks of at most 64 columns occur,
-// bit 1 wider ones, bit 2 reversible ones, bit 3 irreversible ones, bit 4 blocks with SigProp / MagRef passes, bit 6
-// blocks of more than 32 columns occur, bit 7 blocks of more than 16, bit 8 "bits 6 and 7 are filled in" -- only with bit 8
-// SET does a clear bit 6 / 7 mean that every block is at most 32 / 16 columns wide (opt-in: a caller that builds `kinds`
-// from bits 0..4 alone gets one block per wavefront, never the paired kernels, which leave wider blocks alone)
+// kinds: what the caller knows about the blocks of the range (include/ojphgpu.h, ojphgpu_ht_decode_step2_kinds; 0 = nothing);
+// which kernel that gives: dec_launches
 int ht_decode_step2_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const uint8_t* d_data,
                            const uint32_t* d_quad_scratch, void* d_coef, uint8_t* d_block_status, int kinds)
 {
   if (n == 0) return OJPHGPU_OK;
   if (!d_blocks || !d_data || !d_coef || !d_block_status || !d_quad_scratch) return OJPHGPU_E_INVALID;
-  const int tx = (kinds & 16) ? 0 : (kinds & 12) == 4 ? 1 : (kinds & 12) == 8 ? 2 : 0;
-  const int wd = (kinds & 3) == 1 ? 1 : 0;
-  // two (four) blocks to a wavefront where every block of the range is at most 32 (16) columns wide (kinds bit 6 (7) clear;
-  // OJPHGPU_DEC_DUAL=0: never, =2: two at most)
-  static const int multi = [] { const char* e = getenv("OJPHGPU_DEC_DUAL"); return e ? atoi(e) : 4; }();
-  if (multi && (kinds & 256) && !(kinds & 64) && wd && (tx == 1 || tx == 2)) {
-    const uint32_t nb = (!(kinds & 128) && multi >= 4) ? 4u : 2u;
-    const dim3 g2(((n + nb - 1) / nb + WAVES - 1) / WAVES), wg2(64 * WAVES);
-#define MULTI_LAUNCH(T, NB) hipLaunchKernelGGL((ht_dec_step2_multi_kernel<T, NB>), g2, wg2, 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, (uint32_t*)d_coef, d_block_status)
-    if (nb == 4) { if (tx == 1) MULTI_LAUNCH(1, 4); else MULTI_LAUNCH(2, 4); }
-    else         { if (tx == 1) MULTI_LAUNCH(1, 2); else MULTI_LAUNCH(2, 2); }
+  const DecLaunches L = dec_launches(n, kinds);
+  const uint32_t tx = L.tx;
+  const dim3 grid(L.wgs2), wg(64 * WAVES);
+  if (L.multi) {
+#define MULTI_LAUNCH(T, NB) hipLaunchKernelGGL((ht_dec_step2_multi_kernel<T, NB>), grid, wg, 0, (hipStream_t)stream, d_blocks, n, d_data, d_quad_scratch, (uint32_t*)d_coef, d_block_status)
+    if (L.nb == 4) { if (tx == 1) MULTI_LAUNCH(1, 4); else MULTI_LAUNCH(2, 4); }
+    else           { if (tx == 1) MULTI_LAUNCH(1, 2); else MULTI_LAUNCH(2, 2); }
 #undef MULTI_LAUNCH
     return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
   }
-  const dim3 grid((n + WAVES - 1) / WAVES), wg(64 * WAVES);
 #define STEP2_LAUNCH(T, W) hipLaunchKernelGGL((ht_dec_step2_kernel<T, W>), grid, wg, 0, (hipStream_t)stream, d_blocks, n, d_data, \
                                               d_quad_scratch, (uint32_t*)d_coef, d_block_status)
-  if (wd) { if (tx == 1) STEP2_LAUNCH(1, 1); else if (tx == 2) STEP2_LAUNCH(2, 1); else STEP2_LAUNCH(0, 1); }
-  else    { if (tx == 1) STEP2_LAUNCH(1, 0); else if (tx == 2) STEP2_LAUNCH(2, 0); else STEP2_LAUNCH(0, 0); }
+  if (L.wd) { if (tx == 1) STEP2_LAUNCH(1, 1); else if (tx == 2) STEP2_LAUNCH(2, 1); else STEP2_LAUNCH(0, 1); }
+  else      { if (tx == 1) STEP2_LAUNCH(1, 0); else if (tx == 2) STEP2_LAUNCH(2, 0); else STEP2_LAUNCH(0, 0); }
 #undef STEP2_LAUNCH
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
@@ -2530,6 +2569,13 @@ extern "C" int ojphgpu_ht_decode_step2(void* stream, const ojphgpu_cb_desc* d_bl
                                         uint8_t* d_block_status)
 {
   return ojphgpu::ht_decode_step2_launch(stream, d_blocks, n, d_data, d_quad_scratch, d_coef, d_block_status, 0);
+}
+
+extern "C" int ojphgpu_ht_decode_step2_kinds(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
+                                              const uint8_t* d_data, const uint32_t* d_quad_scratch, void* d_coef,
+                                              uint8_t* d_block_status, int kinds)
+{
+  return ojphgpu::ht_decode_step2_launch(stream, d_blocks, n, d_data, d_quad_scratch, d_coef, d_block_status, kinds);
 }
 
 // ---- the fused launch as a stage: its geometry (host only) and the launch itself -------------------------------------------

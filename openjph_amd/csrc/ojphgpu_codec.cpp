@@ -1104,9 +1104,9 @@ void ojphgpu_decoder_fill_descs(const Plan& P, const Plan& Q, const std::vector<
     o.w = (uint16_t)k.r.w; o.h = (uint16_t)k.r.h; o.K_max = (uint8_t)B.K_max;
     o.reversible = (uint8_t)((Q.style(B.comp).rev ? 1u : 0u) | (Q.style(B.comp).causal ? 2u : 0u) | (wide ? 4u : 0u));   // bit 1: vertically causal, bit 2: 64-bit samples
     o.missing_msbs = (uint8_t)std::min<uint32_t>(c.missing_msbs, 255); o.num_passes = (uint8_t)c.num_passes;
-    if (c.num_passes > 1 && c.len2 > 0) { fi.any_refine = true; fi.kinds |= 16; }
-    fi.kinds |= wide ? 32 : ((k.r.w > 64 ? 2 : 1) | ((o.reversible & 1u) ? 4 : 8) | (k.r.w > 32 ? 64 : 0) | (k.r.w > 16 ? 128 : 0) | 256);   // 256: the width bits 6 / 7 are filled in
     o.delta = B.delta; o.len1 = c.len1; o.len2 = c.len2; o.data_off = c.offset;
+    fi.kinds |= ojphgpu::ht_decode_block_kinds(k.r.w, o.reversible, c.num_passes, c.len2);   // (ht_tables.h)
+    if (fi.kinds & 16) fi.any_refine = true;
     fi.max_len1 = std::max(fi.max_len1, c.len1);
     if ((c.len1 + c.len2) && !pb) {
       max_off = std::max<uint64_t>(max_off, c.offset + c.len1 + c.len2);

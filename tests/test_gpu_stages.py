@@ -2,7 +2,11 @@
 (ojphgpu_dwt_forward/inverse, ojphgpu_ht_encode, ojphgpu_ht_decode).  Bit-exact for the integer
 5/3 path and the block coder; the 9/7 float path is compared bit-exactly too (same fp32
 add-mul-add order, no contraction) with the stated fallback tolerance of 1 ulp-level absolute
-error 2^-20 of full scale documented in DESIGN.md."""
+error 2^-20 of full scale documented in DESIGN.md.
+
+ojphgpu_ht_decode passes kinds = 0 to step 2: the block-decoder tests of this file run ht_dec_step2_kernel<0, 0> alone.  The
+other nine instantiations of step 2 and the forms of step 1 are in tests/test_gpu_separate_launches.py, the fused launch in
+tests/test_gpu_fused_geometry.py."""
 import numpy as np
 import pytest
 
