@@ -1219,6 +1219,16 @@ int  ojphgpu_unpack_video444(void* stream, int format, const void* d_video, uint
                              uint32_t height, uint32_t bit_depth, int container_bits);
 int  ojphgpu_pack_video444(void* stream, int format, const void* d_planes, void* d_video, uint32_t pitch, uint32_t width,
                            uint32_t height, int container_bits, uint32_t bit_depth);
+/* The rules of sections 7b - 7d for one OJPHGPU_VIDEO_* constant, as the stages and the pipes' _set_video apply them: family,
+ * chroma cell (a chroma sample covers sub_x x sub_y luma samples), depth column, narrowest container, what a video pointer and
+ * a pitch must be multiples of (pitch_align 0: no pitch, rows at row_bytes).  OJPHGPU_E_INVALID: an unknown format, a null out. */
+#define OJPHGPU_VIDEO_FAMILY_422 422
+#define OJPHGPU_VIDEO_FAMILY_420 420
+#define OJPHGPU_VIDEO_FAMILY_444 444
+typedef struct ojphgpu_video_info {                  /* family: OJPHGPU_VIDEO_FAMILY_* */
+  int family; uint32_t sub_x, sub_y, min_depth, max_depth, min_container_bits, pointer_align, pitch_align;
+} ojphgpu_video_info;
+int  ojphgpu_video_format_info(int format, ojphgpu_video_info* out);   /* host only */
 /* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
  * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
  * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a

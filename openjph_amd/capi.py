@@ -180,6 +180,11 @@ class Run(C.Structure):                   # ojphgpu_run
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("n", C.c_uint64)]
 
 
+class VideoInfo(C.Structure):             # ojphgpu_video_info
+    _fields_ = [("family", C.c_int), ("sub_x", C.c_uint32), ("sub_y", C.c_uint32), ("min_depth", C.c_uint32), ("max_depth", C.c_uint32),
+                ("min_container_bits", C.c_uint32), ("pointer_align", C.c_uint32), ("pitch_align", C.c_uint32)]
+
+
 _lib = None
 
 # name -> (restype, argtypes); also the list every test checks against include/ojphgpu.h
@@ -404,6 +409,7 @@ SIGNATURES = {
     "ojphgpu_video444_layout": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "ojphgpu_unpack_video444": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
     "ojphgpu_pack_video444": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]),
+    "ojphgpu_video_format_info": (C.c_int, [C.c_int, C.POINTER(VideoInfo)]),
     "ojphgpu_enc_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_dec_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_version": (C.c_char_p, []),

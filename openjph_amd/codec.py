@@ -958,20 +958,31 @@ def unpack_pixels(pixels, num_comps=None, big_endian=False, dtype=None):
     return out
 
 
+def _video_args(family, fmt, width, height, bit_depth):
+    """a video stage's format name (of its family), depth and frame -> (code, depth, w, h, row_bytes, chroma_offset, frame_bytes)"""
+    from .pipeline import _format, _layout
+    w, h = int(width), int(height)
+    return _format(family, fmt, bit_depth) + (w, h) + _layout(family, fmt, w, h)
+
+
+def _video_dtype(torch, fmt):
+    """an unpack stage's container when none is asked for: uint8 for the formats whose depth column ends at 8 bits"""
+    from .pipeline import _VIDEO_TABLE
+    return torch.uint8 if _VIDEO_TABLE[fmt][4] == 8 else torch.int16
+
+
 def unpack_video(d_buf, fmt, width, height, bit_depth=None, dtype=None, out=None):
     """a 4:2:2 video buffer on the device (uint8 tensor of the format's frame_bytes, 16-byte aligned; fmt = "uyvy" | "yuy2" |
     "v210" | "y210" | "y212" | "y216", pipeline.pack_video's layout) -> the frame's planes as ONE flat tensor, Y [H,W] then Cb
     and Cr [H,ceil(W/2)], in `dtype` (uint8 -- the 8-bit formats only -- / int16 / uint16 / int32; default: uint8 for the
     8-bit formats, else int16), or in `out` (contiguous, at least that many elements; its dtype is the container).
     ojphgpu_unpack_video."""
-    from .pipeline import video_format, video_layout
     torch = _torch()
-    code, b = video_format(fmt, bit_depth)
-    w, h = int(width), int(height)
+    code, b, w, h, row, _, total = _video_args(422, fmt, width, height, bit_depth)
     n = w * h + 2 * ((w + 1) // 2) * h
-    assert d_buf.is_cuda and d_buf.is_contiguous() and d_buf.numel() * d_buf.element_size() >= video_layout(fmt, w, h)[1]
+    assert d_buf.is_cuda and d_buf.is_contiguous() and d_buf.numel() * d_buf.element_size() >= total
     if out is None:
-        out = torch.empty(n, dtype=dtype if dtype is not None else (torch.uint8 if code in (1, 2) else torch.int16), device=d_buf.device)
+        out = torch.empty(n, dtype=dtype if dtype is not None else _video_dtype(torch, fmt), device=d_buf.device)
     assert out.is_cuda and out.is_contiguous() and out.numel() >= n
     check(capi.lib().ojphgpu_unpack_video(_stream_ptr(torch, d_buf.device.index or 0), code, C.c_void_p(d_buf.data_ptr()),
                                           C.c_void_p(out.data_ptr()), w, h, b, out.element_size() * 8), "unpack_video")
@@ -982,11 +993,8 @@ def pack_video(d_planes, fmt, width, height, bit_depth=None, out=None):
     """the way back: the planes as one flat tensor (the frame layout above; uint8 / int16 / uint16 / int32) -> uint8
     [H, row_bytes], clamped to [0, 2^bit_depth - 1], every padding position zero; `out`: a contiguous uint8 tensor of at
     least frame_bytes, 16-byte aligned.  ojphgpu_pack_video."""
-    from .pipeline import video_format, video_layout
     torch = _torch()
-    code, b = video_format(fmt, bit_depth)
-    w, h = int(width), int(height)
-    row, total = video_layout(fmt, w, h)
+    code, b, w, h, row, _, total = _video_args(422, fmt, width, height, bit_depth)
     assert d_planes.is_cuda and d_planes.is_contiguous() and d_planes.numel() >= w * h + 2 * ((w + 1) // 2) * h
     if out is None:
         out = torch.empty(total, dtype=torch.uint8, device=d_planes.device)
@@ -999,10 +1007,7 @@ def pack_video(d_planes, fmt, width, height, bit_depth=None, out=None):
 def _video420_args(torch, what, buf, fmt, width, height, bit_depth, luma_pitch, chroma, chroma_pitch):
     """the surface of the two 4:2:0 stages -> (code, depth, w, h, row_bytes, luma pointer, luma pitch, chroma pointer, chroma
     pitch).  The defaults are the tight layout inside `buf`; chroma=: a second tensor that holds the chroma plane"""
-    from .pipeline import video420_format, video420_layout
-    code, b = video420_format(fmt, bit_depth)
-    w, h = int(width), int(height)
-    row, off, total = video420_layout(fmt, w, h)
+    code, b, w, h, row, _, _ = _video_args(420, fmt, width, height, bit_depth)
     ch = (h + 1) // 2
     lp = row if luma_pitch is None else int(luma_pitch)
     cp = (lp if chroma is None else row) if chroma_pitch is None else int(chroma_pitch)
@@ -1030,7 +1035,7 @@ def unpack_video420(d_buf, fmt, width, height, bit_depth=None, dtype=None, out=N
     code, b, w, h, row, lptr, lp, cptr, cp = _video420_args(torch, "unpack_video420", d_buf, fmt, width, height, bit_depth, luma_pitch, chroma, chroma_pitch)
     n = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
     if out is None:
-        out = torch.empty(n, dtype=dtype if dtype is not None else (torch.uint8 if code != 0x13 else torch.int16), device=d_buf.device)
+        out = torch.empty(n, dtype=dtype if dtype is not None else _video_dtype(torch, fmt), device=d_buf.device)
     assert out.is_cuda and out.is_contiguous() and out.numel() >= n
     check(capi.lib().ojphgpu_unpack_video420(_stream_ptr(torch, d_buf.device.index or 0), code, C.c_void_p(lptr), lp, C.c_void_p(cptr), cp,
                                              C.c_void_p(out.data_ptr()), w, h, b, out.element_size() * 8), "unpack_video420")
@@ -1060,10 +1065,7 @@ def pack_video420(d_planes, fmt, width, height, bit_depth=None, out=None, luma_p
 
 def _video444_args(what, buf, fmt, width, height, bit_depth, pitch):
     """the surface of the two 4:4:4 stages -> (code, depth, w, h, row_bytes, pitch); the default is the tight layout"""
-    from .pipeline import video444_format, video444_layout
-    code, b = video444_format(fmt, bit_depth)
-    w, h = int(width), int(height)
-    row = video444_layout(fmt, w, h)[0]
+    code, b, w, h, row, _, _ = _video_args(444, fmt, width, height, bit_depth)
     p = row if pitch is None else int(pitch)
     assert buf.is_cuda and buf.is_contiguous(), what
     if p >= row:                                          # (a pitch below row_bytes: the library refuses it)
@@ -1082,7 +1084,7 @@ def unpack_video444(d_buf, fmt, width, height, bit_depth=None, dtype=None, out=N
     code, b, w, h, row, p = _video444_args("unpack_video444", d_buf, fmt, width, height, bit_depth, pitch)
     n = 3 * w * h
     if out is None:
-        out = torch.empty(n, dtype=dtype if dtype is not None else (torch.uint8 if code >= 0x26 else torch.int16), device=d_buf.device)
+        out = torch.empty(n, dtype=dtype if dtype is not None else _video_dtype(torch, fmt), device=d_buf.device)
     assert out.is_cuda and out.is_contiguous() and out.numel() >= n
     check(capi.lib().ojphgpu_unpack_video444(_stream_ptr(torch, d_buf.device.index or 0), code, C.c_void_p(d_buf.data_ptr()), p,
                                              C.c_void_p(out.data_ptr()), w, h, b, out.element_size() * 8), "unpack_video444")

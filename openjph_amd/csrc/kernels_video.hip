@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include "../../include/ojphgpu.h"
 #include "kernels_video_pieces.h"
+#include "video_formats.h"
 
 namespace {
 
@@ -190,24 +191,6 @@ __global__ __launch_bounds__(256) void pack_video_kernel(const D* __restrict__ s
   }
 }
 
-bool layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* frame_bytes)
-{
-  if (width == 0 || height == 0) return false;
-  const uint64_t cw = ((uint64_t)width + 1) / 2;
-  uint64_t rb;
-  switch (format) {
-    case UYVY: case YUY2: rb = 4 * cw; break;
-    case V210: rb = 128 * (((uint64_t)width + 47) / 48); break;
-    case Y2XX: rb = 8 * cw; break;
-    default: return false;
-  }
-  if (rb > 0xFFFFFFFFull) return false;
-  *row_bytes = (uint32_t)rb; *frame_bytes = rb * height;
-  return true;
-}
-
-bool depth_fits(int format, uint32_t b) { return format == Y2XX ? b >= 9 && b <= 16 : b >= 1 && b <= (format == V210 ? 10u : 8u); }
-
 template <int F, typename D>
 int launch(hipStream_t st, bool unpack, const void* src, void* dst, const Geo& g, uint32_t bit_depth)
 {
@@ -229,11 +212,10 @@ int run(void* stream, bool unpack, int format, const void* d_video, const void* 
         uint32_t bit_depth, int container_bits)
 {
   Geo g{};
-  uint64_t frame_bytes = 0;
-  if (!d_video || !d_planes || !layout(format, width, height, &g.row_bytes, &frame_bytes) || !depth_fits(format, bit_depth)) return OJPHGPU_E_INVALID;
-  if ((container_bits != 8 && container_bits != 16 && container_bits != 32) || (uint32_t)container_bits < bit_depth) return OJPHGPU_E_INVALID;
-  if (container_bits == 8 && format != UYVY && format != YUY2) return OJPHGPU_E_INVALID;   // (a v210 field is 10 bits whatever the depth says)
-  if ((uintptr_t)d_video & 15u) return OJPHGPU_E_INVALID;
+  uint64_t chroma_offset = 0, frame_bytes = 0;
+  const VideoDesc* v = video_desc(format, OJPHGPU_VIDEO_FAMILY_422);
+  if (!d_video || !d_planes || !video_check(v, width, height, bit_depth, container_bits)) return OJPHGPU_E_INVALID;
+  if (!video_layout(v, width, height, &g.row_bytes, &chroma_offset, &frame_bytes) || ((uintptr_t)d_video & (v->r.pointer_align - 1))) return OJPHGPU_E_INVALID;
   g.width = width; g.height = height; g.cw = (uint32_t)(((uint64_t)width + 1) / 2);
   g.shift = format == Y2XX ? 16u - bit_depth : 0u;
   const uint32_t np = format == V210 ? 24u : (format == Y2XX || container_bits != 8 ? 8u : 16u);
@@ -251,10 +233,18 @@ int run(void* stream, bool unpack, int format, const void* d_video, const void* 
 
 }  // namespace
 
+extern "C" int ojphgpu_video_format_info(int format, ojphgpu_video_info* out)
+{
+  const VideoDesc* v = video_desc(format);
+  if (v && out) *out = v->r;
+  return v && out ? OJPHGPU_OK : OJPHGPU_E_INVALID;
+}
+
 extern "C" int ojphgpu_video_layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* frame_bytes)
 {
+  uint64_t chroma_offset = 0;
   if (!row_bytes || !frame_bytes) return OJPHGPU_E_INVALID;
-  return layout(format, width, height, row_bytes, frame_bytes) ? OJPHGPU_OK : OJPHGPU_E_INVALID;
+  return video_layout(video_desc(format, OJPHGPU_VIDEO_FAMILY_422), width, height, row_bytes, &chroma_offset, frame_bytes) ? OJPHGPU_OK : OJPHGPU_E_INVALID;
 }
 
 extern "C" int ojphgpu_unpack_video(void* stream, int format, const void* d_video, void* d_planes, uint32_t width, uint32_t height,

@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include "../../include/ojphgpu.h"
 #include "kernels_video_pieces.h"
+#include "video_formats.h"
 
 namespace {
 
@@ -162,16 +163,6 @@ __global__ __launch_bounds__(256) void pack_video420_kernel(const D* __restrict_
 
 enum { NV12 = OJPHGPU_VIDEO_NV12, NV21 = OJPHGPU_VIDEO_NV21, P0XX = OJPHGPU_VIDEO_P0XX };
 
-bool layout420(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* chroma_offset, uint64_t* frame_bytes)
-{
-  if (width == 0 || height == 0 || (format != NV12 && format != NV21 && format != P0XX)) return false;
-  const uint64_t cw = ((uint64_t)width + 1) / 2, ch = ((uint64_t)height + 1) / 2;
-  const uint64_t rb = (format == P0XX ? 4 : 2) * cw;
-  if (rb > 0xFFFFFFFFull || (uint64_t)height + ch > 0xFFFFFFFFull) return false;
-  *row_bytes = (uint32_t)rb; *chroma_offset = rb * height; *frame_bytes = rb * (height + ch);
-  return true;
-}
-
 template <typename V, typename D>
 int launch420(hipStream_t st, bool unpack, const void* planes, const void* luma, const void* chroma, const Geo420& g, bool crcb, uint32_t bit_depth)
 {
@@ -187,15 +178,12 @@ int run420(void* stream, bool unpack, int format, const void* d_luma, uint32_t l
            const void* d_planes, uint32_t width, uint32_t height, uint32_t bit_depth, int container_bits)
 {
   Geo420 g{};
-  uint32_t row_bytes = 0;
-  uint64_t chroma_offset = 0, frame_bytes = 0;
-  if (!d_luma || !d_chroma || !d_planes || !layout420(format, width, height, &row_bytes, &chroma_offset, &frame_bytes)) return OJPHGPU_E_INVALID;
-  if (format == P0XX ? (bit_depth < 9 || bit_depth > 16) : (bit_depth < 1 || bit_depth > 8)) return OJPHGPU_E_INVALID;
-  if ((container_bits != 8 && container_bits != 16 && container_bits != 32) || (uint32_t)container_bits < bit_depth) return OJPHGPU_E_INVALID;
-  if (container_bits == 8 && format == P0XX) return OJPHGPU_E_INVALID;
-  if (luma_pitch < row_bytes || chroma_pitch < row_bytes) return OJPHGPU_E_INVALID;
-  const uintptr_t elem = format == P0XX ? 4u : 2u;     // a chroma pair: what every row of both planes must be aligned to
-  if (((uintptr_t)d_luma | (uintptr_t)d_chroma | luma_pitch | chroma_pitch) & (elem - 1)) return OJPHGPU_E_INVALID;
+  uint32_t row_bytes = 0; uint64_t chroma_offset = 0, frame_bytes = 0;
+  const VideoDesc* v = video_desc(format, OJPHGPU_VIDEO_FAMILY_420);
+  if (!d_luma || !d_chroma || !d_planes || !video_check(v, width, height, bit_depth, container_bits)) return OJPHGPU_E_INVALID;
+  if (!video_layout(v, width, height, &row_bytes, &chroma_offset, &frame_bytes) || luma_pitch < row_bytes || chroma_pitch < row_bytes) return OJPHGPU_E_INVALID;
+  // a chroma pair: what every row of both planes must be aligned to
+  if ((((uintptr_t)d_luma | (uintptr_t)d_chroma) & (v->r.pointer_align - 1)) || ((luma_pitch | chroma_pitch) & (v->r.pitch_align - 1))) return OJPHGPU_E_INVALID;
   g.width = width; g.height = height; g.cw = (uint32_t)(((uint64_t)width + 1) / 2); g.ch = (uint32_t)(((uint64_t)height + 1) / 2);
   g.shift = format == P0XX ? 16u - bit_depth : 0u;
   g.luma_pitch = luma_pitch; g.chroma_pitch = chroma_pitch;
@@ -216,7 +204,7 @@ int run420(void* stream, bool unpack, int format, const void* d_luma, uint32_t l
 extern "C" int ojphgpu_video420_layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* chroma_offset, uint64_t* frame_bytes)
 {
   if (!row_bytes || !chroma_offset || !frame_bytes) return OJPHGPU_E_INVALID;
-  return layout420(format, width, height, row_bytes, chroma_offset, frame_bytes) ? OJPHGPU_OK : OJPHGPU_E_INVALID;
+  return video_layout(video_desc(format, OJPHGPU_VIDEO_FAMILY_420), width, height, row_bytes, chroma_offset, frame_bytes) ? OJPHGPU_OK : OJPHGPU_E_INVALID;
 }
 
 extern "C" int ojphgpu_unpack_video420(void* stream, int format, const void* d_luma, uint32_t luma_pitch, const void* d_chroma, uint32_t chroma_pitch,

@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include "../../include/ojphgpu.h"
 #include "kernels_video_pieces.h"
+#include "video_formats.h"
 
 namespace {
 
@@ -148,33 +149,23 @@ __global__ __launch_bounds__(256) void pack_video444_kernel(const D* __restrict_
   }
 }
 
-// format -> field bits (0: not a format of this section), pixel bytes, the depths it holds, how it sits in its pixel
-struct Desc444 { int fb; uint32_t pixel_bytes, min_depth, max_depth; Fmt444 f; };
+// format (one of this section: video_formats.h has judged it) -> field bits, how it sits in its pixel
+struct Desc444 { int fb; Fmt444 f; };
 
 Desc444 describe444(int format)
 {
-  switch (format) {                                  //  fb  bytes depths   base  selector fill         low mid high
-  case OJPHGPU_VIDEO_V410: return Desc444{ 10, 4, 1, 10, { 2, SEL_LE, 0u, 1, 0, 2 } };            // Cb Y Cr
-  case OJPHGPU_VIDEO_Y410: return Desc444{ 10, 4, 1, 10, { 0, SEL_LE, 3u << 30, 1, 0, 2 } };
-  case OJPHGPU_VIDEO_R210: return Desc444{ 10, 4, 1, 10, { 0, SEL_BE, 0u, 2, 1, 0 } };            // B G R
-  case OJPHGPU_VIDEO_R10K: return Desc444{ 10, 4, 1, 10, { 2, SEL_BE, 0u, 2, 1, 0 } };
-  case OJPHGPU_VIDEO_Y4XX: return Desc444{ 16, 8, 9, 16, { 0, SEL_LE, 0u, 1, 0, 2 } };            // words Cb Y Cr; base, fill: by depth
-  case OJPHGPU_VIDEO_AYUV: return Desc444{ 8, 4, 1, 8, { 0, SEL_LE, 0xFFu << 24, 2, 1, 0 } };     // bytes Cr Cb Y A
-  case OJPHGPU_VIDEO_BGRA: return Desc444{ 8, 4, 1, 8, { 0, SEL_LE, 0xFFu << 24, 2, 1, 0 } };     // bytes B G R A
-  case OJPHGPU_VIDEO_RGBA: return Desc444{ 8, 4, 1, 8, { 0, SEL_LE, 0xFFu << 24, 0, 1, 2 } };     // bytes R G B A
-  case OJPHGPU_VIDEO_ARGB: return Desc444{ 8, 4, 1, 8, { 0, SEL_BE, 0xFFu << 24, 2, 1, 0 } };     // bytes A R G B: BGRA mirrored
+  switch (format) {                                  //  fb   base  selector fill         low mid high
+  case OJPHGPU_VIDEO_V410: return Desc444{ 10, { 2, SEL_LE, 0u, 1, 0, 2 } };            // Cb Y Cr
+  case OJPHGPU_VIDEO_Y410: return Desc444{ 10, { 0, SEL_LE, 3u << 30, 1, 0, 2 } };
+  case OJPHGPU_VIDEO_R210: return Desc444{ 10, { 0, SEL_BE, 0u, 2, 1, 0 } };            // B G R
+  case OJPHGPU_VIDEO_R10K: return Desc444{ 10, { 2, SEL_BE, 0u, 2, 1, 0 } };
+  case OJPHGPU_VIDEO_Y4XX: return Desc444{ 16, { 0, SEL_LE, 0u, 1, 0, 2 } };            // words Cb Y Cr; base, fill: by depth
+  case OJPHGPU_VIDEO_AYUV: return Desc444{ 8, { 0, SEL_LE, 0xFFu << 24, 2, 1, 0 } };     // bytes Cr Cb Y A
+  case OJPHGPU_VIDEO_BGRA: return Desc444{ 8, { 0, SEL_LE, 0xFFu << 24, 2, 1, 0 } };     // bytes B G R A
+  case OJPHGPU_VIDEO_RGBA: return Desc444{ 8, { 0, SEL_LE, 0xFFu << 24, 0, 1, 2 } };     // bytes R G B A
+  case OJPHGPU_VIDEO_ARGB: return Desc444{ 8, { 0, SEL_BE, 0xFFu << 24, 2, 1, 0 } };     // bytes A R G B: BGRA mirrored
   }
-  return Desc444{ 0, 0, 0, 0, { 0, 0, 0, 0, 0, 0 } };
-}
-
-bool layout444(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* frame_bytes)
-{
-  const Desc444 d = describe444(format);
-  if (width == 0 || height == 0 || d.fb == 0) return false;
-  const uint64_t rb = (uint64_t)d.pixel_bytes * width;
-  if (rb > 0xFFFFFFFFull) return false;
-  *row_bytes = (uint32_t)rb; *frame_bytes = rb * height;
-  return true;
+  return Desc444{ 0, { 0, 0, 0, 0, 0, 0 } };
 }
 
 template <int FB, typename D>
@@ -190,19 +181,16 @@ int launch444(hipStream_t st, bool unpack, const void* planes, const void* video
 int run444(void* stream, bool unpack, int format, const void* d_video, uint32_t pitch, const void* d_planes, uint32_t width, uint32_t height,
            uint32_t bit_depth, int container_bits)
 {
-  uint32_t row_bytes = 0;
-  uint64_t frame_bytes = 0;
-  if (!d_video || !d_planes || !layout444(format, width, height, &row_bytes, &frame_bytes)) return OJPHGPU_E_INVALID;
+  uint32_t row_bytes = 0; uint64_t chroma_offset = 0, frame_bytes = 0;
+  const VideoDesc* v = video_desc(format, OJPHGPU_VIDEO_FAMILY_444);
+  if (!d_video || !d_planes || !video_check(v, width, height, bit_depth, container_bits)) return OJPHGPU_E_INVALID;
+  if (!video_layout(v, width, height, &row_bytes, &chroma_offset, &frame_bytes) || pitch < row_bytes) return OJPHGPU_E_INVALID;
+  if (((uintptr_t)d_video & (v->r.pointer_align - 1)) || (pitch & (v->r.pitch_align - 1))) return OJPHGPU_E_INVALID;
   Desc444 d = describe444(format);
-  if (bit_depth < d.min_depth || bit_depth > d.max_depth) return OJPHGPU_E_INVALID;
-  if ((container_bits != 8 && container_bits != 16 && container_bits != 32) || (uint32_t)container_bits < bit_depth) return OJPHGPU_E_INVALID;
-  if (container_bits == 8 && d.fb != 8) return OJPHGPU_E_INVALID;
-  if (pitch < row_bytes) return OJPHGPU_E_INVALID;
-  if (((uintptr_t)d_video | pitch) & (uintptr_t)(d.pixel_bytes - 1)) return OJPHGPU_E_INVALID;
   if (d.fb == 16) { d.f.base = 16u - bit_depth; d.f.fill = (((1u << bit_depth) - 1u) << d.f.base) << 16; }
   Geo444 g{};
   g.width = width; g.height = height; g.pitch = pitch;
-  const uint32_t np = 16u / d.pixel_bytes;
+  const uint32_t np = 16u / v->unit_bytes;             // pixels of a piece
   g.pieces = (uint32_t)(((uint64_t)width + np - 1) / np);
   hipStream_t st = (hipStream_t)stream;
   if (d.fb == 16)
@@ -221,7 +209,8 @@ int run444(void* stream, bool unpack, int format, const void* d_video, uint32_t 
 extern "C" int ojphgpu_video444_layout(int format, uint32_t width, uint32_t height, uint32_t* row_bytes, uint64_t* frame_bytes)
 {
   if (!row_bytes || !frame_bytes) return OJPHGPU_E_INVALID;
-  return layout444(format, width, height, row_bytes, frame_bytes) ? OJPHGPU_OK : OJPHGPU_E_INVALID;
+  uint64_t chroma_offset = 0;
+  return video_layout(video_desc(format, OJPHGPU_VIDEO_FAMILY_444), width, height, row_bytes, &chroma_offset, frame_bytes) ? OJPHGPU_OK : OJPHGPU_E_INVALID;
 }
 
 extern "C" int ojphgpu_unpack_video444(void* stream, int format, const void* d_video, uint32_t pitch, void* d_planes, uint32_t width, uint32_t height,

@@ -23,7 +23,9 @@ template <typename D> __device__ __forceinline__ int32_t get(const uint32_t* w, 
 }
 
 // NW dwords (a multiple of four) <-> memory in the widest pieces the (wave-uniform) alignment `al` of the address allows;
-// MIN: what the element type guarantees anyway.  (The 4:2:2 kernels' pair, kept as it was.)
+// MIN: what the element type guarantees anyway.  The 4:2:2 kernels' pair, beside load_run / store_run on purpose: one pair for
+// both (the run generalised to any multiple of four dwords) changes all twenty 4:2:2 kernels, five take more VGPRs and
+// pack_video_kernel<V210, int> goes from 706 to 759 instructions and 63 to 84 global loads (profiles/video_pieces_fold_isa.txt).
 template <int NW, int MIN> __device__ __forceinline__ void store_words(uint8_t* p, const uint32_t* w, uint32_t al)
 {
   if ((al & 15u) == 0) {

@@ -35,6 +35,7 @@
 
 #include "ojphgpu_objects.h"
 #include "ojph_pool.h"
+#include "video_formats.h"
 
 namespace ojphgpu {
 int assemble_launch(void* stream, const T2Job* d_jobs, uint32_t njobs, const uint8_t* d_blob, const uint8_t* d_data, uint8_t* d_out);
@@ -129,16 +130,16 @@ bool pop_work(std::mutex& mu, std::condition_variable& cv, std::deque<uint32_t>&
 
 // ---- the hand-over: how a frame crosses PCIe -- the encoder's going in, the decoder's coming out.  PLANES: as the codec
 // holds it, straight into / out of the slot's image.  The other kinds go through the slot's staging buffer (`pixels`) and a
-// launch on the compute stream: PIXELS pixel-interleaved (_set_pixels), PACKED one bit string (_set_packed), VIDEO one 4:2:2
-// video buffer (_set_video, ojphgpu.h section 7b), one 4:2:0 video buffer in its tight layout (section 7c) or one 4:4:4
-// packed buffer, tight as well (section 7d).  A pipe has one; everything the launch needs is fixed when it is set.
+// launch on the compute stream: PIXELS pixel-interleaved (_set_pixels), PACKED one bit string (_set_packed), VIDEO one video
+// buffer in its format's tight layout (_set_video, ojphgpu.h sections 7b - 7d; the formats' rules: the one table of
+// video_formats.h).  A pipe has one; everything the launch needs is fixed when it is set.
 enum HandoverKind { PLANES = 0, PIXELS, PACKED, VIDEO };
 
 struct Handover {
   int kind = PLANES;
   int bits = 0, big_endian = 0;                      // PIXELS: 8 / 16 per sample; PACKED: 10 / 12 / 14
   int format = 0;                                    // VIDEO: OJPHGPU_VIDEO_*
-  uint32_t row_bytes = 0; uint64_t chroma_offset = 0; // VIDEO, 4:2:0 and 4:4:4: the tight layout inside the staging buffer
+  uint32_t row_bytes = 0; uint64_t chroma_offset = 0; // VIDEO: the tight layout inside the staging buffer (video_layout)
   uint32_t w = 0, h = 0, depth = 0;                  // PIXELS, VIDEO: the (luma) plane; the depth a decoder clamps to
   size_t bytes = 0;                                  // of a frame as handed over: what _acquire / _collect report and PCIe carries
 };
@@ -147,8 +148,6 @@ struct Handover {
 // decoding: the frame comes back, clamped to one range; odd_origin: the pipe decodes a window whose first column (ODD_X0) or
 // first row (ODD_Y0) is odd.
 enum { ODD_X0 = 1, ODD_Y0 = 2 };
-bool video_is_420(int format) { return format == OJPHGPU_VIDEO_NV12 || format == OJPHGPU_VIDEO_NV21 || format == OJPHGPU_VIDEO_P0XX; }
-bool video_is_444(int format) { return format >= OJPHGPU_VIDEO_V410 && format <= OJPHGPU_VIDEO_ARGB; }
 int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Handover& want)
 {
   const CompGeo& Y = P.comps[0];
@@ -175,48 +174,16 @@ int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Ha
     want.bytes = (size_t)((P.frame_elems + 31) / 32) * 4u * (size_t)want.bits;
     return OJPHGPU_OK;
   case VIDEO: {
-    // three unsigned components of one depth that fits the format, the chroma planes half as wide (rounded up) and as high
-    // as the luma plane (4:2:0: half as high, rounded up), tightly packed; -> the format's layout of that frame
-    const int format = want.format;
-    if (video_is_444(format)) {
-      // 4:4:4: three unsigned components of one depth that the format and the container hold, all of the size of component 0.
-      // There is no chroma cell, so a window passes at any origin
-      if (P.comps.size() != 3 || Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
-      const uint32_t b = Y.bit_depth;
-      for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != b || g.w != Y.w || g.h != Y.h) return OJPHGPU_E_INVALID;
-      if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != 2 * (uint64_t)Y.w * Y.h) return OJPHGPU_E_INVALID;
-      const bool bytes8 = format >= OJPHGPU_VIDEO_AYUV;
-      if (format == OJPHGPU_VIDEO_Y4XX ? (b < 9 || b > 16) : b > (bytes8 ? 8u : 10u)) return OJPHGPU_E_INVALID;
-      if ((uint32_t)container < b || (container == 8 && !bytes8)) return OJPHGPU_E_INVALID;
-      uint64_t bytes = 0;
-      const int rc = ojphgpu_video444_layout(format, Y.w, Y.h, &want.row_bytes, &bytes);
-      if (rc) return rc;
-      want.bytes = (size_t)bytes;
-      return OJPHGPU_OK;
-    }
-    const bool v420 = video_is_420(format);
-    if (((format < OJPHGPU_VIDEO_UYVY || format > OJPHGPU_VIDEO_Y2XX) && !v420) || P.comps.size() != 3) return OJPHGPU_E_INVALID;
-    if (Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
-    const uint32_t cw = (uint32_t)(((uint64_t)Y.w + 1) / 2), ch = v420 ? (uint32_t)(((uint64_t)Y.h + 1) / 2) : Y.h, b = Y.bit_depth;
-    for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != b) return OJPHGPU_E_INVALID;
+    // three unsigned components of one depth, the chroma planes the format's cell smaller than the luma plane (rounded up),
+    // tightly packed -> the format's tight layout of that frame.  A window's first column and row must open a chroma cell
+    const VideoDesc* v = video_desc(want.format); uint64_t bytes = 0;
+    if (!v || P.comps.size() != 3) return OJPHGPU_E_INVALID;
+    const uint32_t cw = (uint32_t)(((uint64_t)Y.w + v->r.sub_x - 1) / v->r.sub_x), ch = (uint32_t)(((uint64_t)Y.h + v->r.sub_y - 1) / v->r.sub_y);
+    for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != Y.bit_depth) return OJPHGPU_E_INVALID;
     for (size_t c = 1; c < 3; ++c) if (P.comps[c].w != cw || P.comps[c].h != ch) return OJPHGPU_E_INVALID;
     if (P.comps[1].frame_off != (uint64_t)Y.w * Y.h || P.comps[2].frame_off != (uint64_t)Y.w * Y.h + (uint64_t)cw * ch) return OJPHGPU_E_INVALID;
-    if (v420) {
-      if (format == OJPHGPU_VIDEO_P0XX ? (b < 9 || b > 16 || container == 8) : b > 8u) return OJPHGPU_E_INVALID;
-      if ((uint32_t)container < b) return OJPHGPU_E_INVALID;
-      uint64_t bytes = 0;
-      const int rc = ojphgpu_video420_layout(format, Y.w, Y.h, &want.row_bytes, &want.chroma_offset, &bytes);
-      if (rc) return rc;
-      if (odd_origin) return OJPHGPU_E_INVALID;       // (a window's first column and first row must open a 2 x 2 cell)
-      want.bytes = (size_t)bytes;
-      return OJPHGPU_OK;
-    }
-    if (format == OJPHGPU_VIDEO_Y2XX ? (b < 9 || b > 16) : b > (format == OJPHGPU_VIDEO_V210 ? 10u : 8u)) return OJPHGPU_E_INVALID;
-    if (container == 8 && format != OJPHGPU_VIDEO_UYVY && format != OJPHGPU_VIDEO_YUY2) return OJPHGPU_E_INVALID;
-    uint32_t row_bytes = 0; uint64_t bytes = 0;
-    const int rc = ojphgpu_video_layout(format, Y.w, Y.h, &row_bytes, &bytes);
-    if (rc) return rc;
-    if (odd_origin & ODD_X0) return OJPHGPU_E_INVALID;   // (a window's first column must open a pair)
+    if (!video_check(v, Y.w, Y.h, Y.bit_depth, container) || !video_layout(v, Y.w, Y.h, &want.row_bytes, &want.chroma_offset, &bytes)) return OJPHGPU_E_INVALID;
+    if (((odd_origin & ODD_X0) && v->r.sub_x == 2) || ((odd_origin & ODD_Y0) && v->r.sub_y == 2)) return OJPHGPU_E_INVALID;
     want.bytes = (size_t)bytes;
     return OJPHGPU_OK;
   }
@@ -235,17 +202,19 @@ int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int co
   case PACKED:
     return unpack ? ojphgpu_unpack_bits(stream, d_staged, d_planes, P.frame_elems, h.bits, container)
                   : ojphgpu_pack_bits(stream, d_planes, d_staged, P.frame_elems, container, h.bits);
-  case VIDEO:
-    if (video_is_444(h.format))                       // the tight layout: rows at row_bytes
+  case VIDEO: {                                       // 4:2:0 and 4:4:4: the tight layout, rows (of both planes) at row_bytes
+    uint8_t* const luma = (uint8_t*)d_staged;
+    switch (video_desc(h.format)->r.family) {
+    case OJPHGPU_VIDEO_FAMILY_444:
       return unpack ? ojphgpu_unpack_video444(stream, h.format, d_staged, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
                     : ojphgpu_pack_video444(stream, h.format, d_planes, d_staged, h.row_bytes, h.w, h.h, container, h.depth);
-    if (video_is_420(h.format)) {                     // the tight layout: both planes at row_bytes
-      uint8_t* const luma = (uint8_t*)d_staged;
+    case OJPHGPU_VIDEO_FAMILY_420:
       return unpack ? ojphgpu_unpack_video420(stream, h.format, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
                     : ojphgpu_pack_video420(stream, h.format, d_planes, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, h.w, h.h, container, h.depth);
     }
     return unpack ? ojphgpu_unpack_video(stream, h.format, d_staged, d_planes, h.w, h.h, h.depth, container)
                   : ojphgpu_pack_video(stream, h.format, d_planes, d_staged, h.w, h.h, container, h.depth);
+  }
   }
   return OJPHGPU_OK;
 }

@@ -88,20 +88,80 @@ def unpack_bits(packed, bits, n):
     return (b << np.arange(bits, dtype=np.uint32)[None, :]).sum(axis=1).astype(np.uint32)
 
 
-# 4:2:2 video buffers (ojphgpu.h section 7b): name -> (OJPHGPU_VIDEO_* constant, the depth the name fixes or None)
-VIDEO_FORMATS = {"uyvy": (1, None), "yuy2": (2, None), "v210": (3, None), "y2xx": (4, None), "y210": (4, 10), "y212": (4, 12), "y216": (4, 16)}
+# The video formats (ojphgpu.h sections 7b - 7d), the one table of this side (csrc/video_formats.h is the library's): name ->
+# (OJPHGPU_VIDEO_* constant, family, the depth the name fixes or None, lowest and highest depth of the column, the depth taken
+# when none is given or None: one must be, bytes per unit of pixels: row_bytes = unit_bytes * ceil(width / unit_pixels))
+_VIDEO_TABLE = {
+    "uyvy": (0x01, 422, None, 1, 8, None, 4, 2), "yuy2": (0x02, 422, None, 1, 8, None, 4, 2), "v210": (0x03, 422, None, 1, 10, None, 128, 48),
+    "y2xx": (0x04, 422, None, 9, 16, None, 8, 2), "y210": (0x04, 422, 10, 9, 16, 10, 8, 2), "y212": (0x04, 422, 12, 9, 16, 12, 8, 2),
+    "y216": (0x04, 422, 16, 9, 16, 16, 8, 2),
+    "nv12": (0x11, 420, None, 1, 8, 8, 2, 2), "nv21": (0x12, 420, None, 1, 8, 8, 2, 2), "p0xx": (0x13, 420, None, 9, 16, None, 4, 2),
+    "p010": (0x13, 420, 10, 9, 16, 10, 4, 2), "p012": (0x13, 420, 12, 9, 16, 12, 4, 2), "p016": (0x13, 420, 16, 9, 16, 16, 4, 2),
+    "v410": (0x21, 444, None, 1, 10, 10, 4, 1), "y410": (0x22, 444, None, 1, 10, 10, 4, 1), "r210": (0x23, 444, None, 1, 10, 10, 4, 1),
+    "r10k": (0x24, 444, None, 1, 10, 10, 4, 1), "y4xx": (0x25, 444, None, 9, 16, 16, 8, 1), "y412": (0x25, 444, 12, 9, 16, 12, 8, 1),
+    "y416": (0x25, 444, 16, 9, 16, 16, 8, 1), "ayuv": (0x26, 444, None, 1, 8, 8, 4, 1), "bgra": (0x27, 444, None, 1, 8, 8, 4, 1),
+    "rgba": (0x28, 444, None, 1, 8, 8, 4, 1), "argb": (0x29, 444, None, 1, 8, 8, 4, 1),
+}
+# a family's names -> (OJPHGPU_VIDEO_* constant, the depth the name fixes or None)
+VIDEO_FORMATS, VIDEO420_FORMATS, VIDEO444_FORMATS = ({n: (t[0], t[2]) for n, t in _VIDEO_TABLE.items() if t[1] == family} for family in (422, 420, 444))
 
 
-def video_format(fmt, bit_depth):
-    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a format name, refused when the depth is outside the format's column"""
-    if fmt not in VIDEO_FORMATS:
-        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS))))
-    code, fixed = VIDEO_FORMATS[fmt]
-    b = int(fixed if bit_depth is None else bit_depth)
-    lo, hi = {1: (1, 8), 2: (1, 8), 3: (1, 10), 4: (9, 16)}[code]
+def _entry(family, fmt):                              # a name's row of the table; family 0: any
+    t = _VIDEO_TABLE.get(fmt)
+    if t is None or family not in (0, t[1]):
+        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(n for n, u in _VIDEO_TABLE.items() if family in (0, u[1])))))
+    return t
+
+
+def _format(family, fmt, bit_depth):
+    """-> (OJPHGPU_VIDEO_* constant, bit depth); refused: a depth outside the format's column or not the one the name fixes"""
+    code, _, fixed, lo, hi, default, _, _ = _entry(family, fmt)
+    if bit_depth is None and default is None:
+        raise ValueError("video format %r needs a bit depth" % fmt)
+    b = int(default if bit_depth is None else bit_depth)
     if not lo <= b <= hi or (fixed is not None and b != fixed):
         raise ValueError("video format %r does not hold %d-bit samples" % (fmt, b))
     return code, b
+
+
+def _layout(family, fmt, width, height):
+    """-> (row_bytes, chroma_offset, frame_bytes) of the tight layout; chroma_offset 0 where there is no second plane"""
+    unit_bytes, unit_pixels = _entry(family, fmt)[6:]
+    if width < 1 or height < 1:
+        raise ValueError("video layout: a frame has at least one sample")
+    row = unit_bytes * (-(-int(width) // unit_pixels))
+    ch = (int(height) + 1) // 2 if family == 420 else 0
+    return row, row * int(height) if ch else 0, row * (int(height) + ch)
+
+
+def video_format(fmt, bit_depth):
+    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a 4:2:2 name and a depth of its column; a name that fixes no depth needs one"""
+    return _format(422, fmt, bit_depth)
+
+
+def video420_format(fmt, bit_depth):
+    """... of a 4:2:0 name; without a depth: the one the name fixes, nv12 / nv21: 8, p0xx needs one"""
+    return _format(420, fmt, bit_depth)
+
+
+def video444_format(fmt, bit_depth):
+    """... of a 4:4:4 name; without a depth: the one the name fixes, else the widest of the column"""
+    return _format(444, fmt, bit_depth)
+
+
+def video_layout(fmt, width, height):
+    """-> (row_bytes, frame_bytes) of a width x height frame, as ojphgpu_video_layout"""
+    return _layout(422, fmt, width, height)[::2]
+
+
+def video420_layout(fmt, width, height):
+    """-> (row_bytes, chroma_offset, frame_bytes), as ojphgpu_video420_layout: `height` luma rows, then ceil(height / 2) chroma rows"""
+    return _layout(420, fmt, width, height)
+
+
+def video444_layout(fmt, width, height):
+    """-> (row_bytes, frame_bytes) of the tight layout of a width x height frame, as ojphgpu_video444_layout"""
+    return _layout(444, fmt, width, height)[::2]
 
 
 def _video_code(plan, fmt, what):
@@ -109,22 +169,10 @@ def _video_code(plan, fmt, what):
     samples do not have is refused here as the library refuses the rest"""
     if fmt is None:
         return 0
-    tables = [t for t in (VIDEO_FORMATS, VIDEO420_FORMATS, VIDEO444_FORMATS) if fmt in t]
-    if not tables:
-        raise ValueError("video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO_FORMATS) + sorted(VIDEO420_FORMATS) + sorted(VIDEO444_FORMATS))))
-    code, fixed = tables[0][fmt]
+    code, _, fixed = _entry(0, fmt)[:3]
     if fixed is not None and plan.comp_format(0)[0] != fixed:
         raise capi.OjphError(capi.E_INVALID, "%s: %r on %d-bit samples" % (what, fmt, plan.comp_format(0)[0]))
     return code
-
-
-def video_layout(fmt, width, height):
-    """-> (row_bytes, frame_bytes) of a width x height frame, as ojphgpu_video_layout"""
-    code, cw = VIDEO_FORMATS[fmt][0], (int(width) + 1) // 2
-    if width < 1 or height < 1:
-        raise ValueError("video_layout: a frame has at least one sample")
-    row = {1: 4 * cw, 2: 4 * cw, 3: 128 * ((int(width) + 47) // 48), 4: 8 * cw}[code]
-    return row, row * int(height)
 
 
 def pack_video(planes, fmt, bit_depth=None):
@@ -174,39 +222,6 @@ def unpack_video(buf, fmt, width, height, bit_depth=None):
     return [np.ascontiguousarray(y), np.ascontiguousarray(f[:, :, 2]), np.ascontiguousarray(f[:, :, 3])]
 
 
-# 4:2:0 video buffers (ojphgpu.h section 7c), two planes: name -> (OJPHGPU_VIDEO_* constant, the depth the name fixes or None).
-# A table of its own: the 4:2:2 functions above keep refusing these names, as the 4:2:2 entry points refuse these codes.
-VIDEO420_FORMATS = {"nv12": (0x11, None), "nv21": (0x12, None), "p0xx": (0x13, None), "p010": (0x13, 10), "p012": (0x13, 12), "p016": (0x13, 16)}
-
-
-def video420_format(fmt, bit_depth):
-    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a 4:2:0 format name, refused when the depth is outside the format's column"""
-    if fmt not in VIDEO420_FORMATS:
-        raise ValueError("4:2:0 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO420_FORMATS))))
-    code, fixed = VIDEO420_FORMATS[fmt]
-    if fixed is None and bit_depth is None and code != 0x13:
-        bit_depth = 8
-    if fixed is None and bit_depth is None:
-        raise ValueError("video format %r needs a bit depth" % fmt)
-    b = int(fixed if bit_depth is None else bit_depth)
-    lo, hi = (9, 16) if code == 0x13 else (1, 8)
-    if not lo <= b <= hi or (fixed is not None and b != fixed):
-        raise ValueError("video format %r does not hold %d-bit samples" % (fmt, b))
-    return code, b
-
-
-def video420_layout(fmt, width, height):
-    """-> (row_bytes, chroma_offset, frame_bytes) of the tight layout of a width x height frame, as ojphgpu_video420_layout:
-    `height` luma rows, then ceil(height / 2) chroma rows, all at row_bytes"""
-    if fmt not in VIDEO420_FORMATS:
-        raise ValueError("4:2:0 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO420_FORMATS))))
-    if width < 1 or height < 1:
-        raise ValueError("video420_layout: a frame has at least one sample")
-    cw, ch = (int(width) + 1) // 2, (int(height) + 1) // 2
-    row = (4 if VIDEO420_FORMATS[fmt][0] == 0x13 else 2) * cw
-    return row, row * int(height), row * (int(height) + ch)
-
-
 def pack_video420(planes, fmt, bit_depth=None):
     """numpy: planes = [Y [H,W], Cb [ch,cw], Cr [ch,cw]] (cw = ceil(W / 2), ch = ceil(H / 2)) -> the frame as one 4:2:0 video
     buffer in the tight layout, uint8 [H + ch, row_bytes]: H luma rows, then ch rows of (Cb, Cr) pairs (nv21: (Cr, Cb)): the
@@ -246,41 +261,12 @@ def unpack_video420(buf, fmt, width, height, bit_depth=None):
     return [np.ascontiguousarray(f[:h, :w]), np.ascontiguousarray(cb), np.ascontiguousarray(cr)]
 
 
-# 4:4:4 packed video (ojphgpu.h section 7d), one interleaved word per pixel: name -> (OJPHGPU_VIDEO_* constant, the depth the
-# name fixes or None).  A table of its own again: pack_video and pack_video420 keep refusing these names.
-VIDEO444_FORMATS = {"v410": (0x21, None), "y410": (0x22, None), "r210": (0x23, None), "r10k": (0x24, None), "y4xx": (0x25, None), "y412": (0x25, 12),
-                    "y416": (0x25, 16), "ayuv": (0x26, None), "bgra": (0x27, None), "rgba": (0x28, None), "argb": (0x29, None)}
-# constant -> (bytes of a pixel, lowest and highest depth of the format's column)
-_VIDEO444_COLUMN = {0x21: (4, 1, 10), 0x22: (4, 1, 10), 0x23: (4, 1, 10), 0x24: (4, 1, 10), 0x25: (8, 9, 16), 0x26: (4, 1, 8), 0x27: (4, 1, 8),
-                    0x28: (4, 1, 8), 0x29: (4, 1, 8)}
-# the 10-bit dword formats: constant -> (dword byte order, first bit of component 0, 1, 2, the constant bits).  v410 and Y410
+# 4:4:4 packed video (ojphgpu.h section 7d), one interleaved word per pixel: the bit layouts of the numpy pair below.
+# The 10-bit dword formats: constant -> (dword byte order, first bit of component 0, 1, 2, the constant bits).  v410 and Y410
 # name Cb (component 1) first, R210 and R10k carry R (component 0) on top
 _VIDEO444_DWORD = {0x21: ("<u4", (12, 2, 22), 0), 0x22: ("<u4", (10, 0, 20), 3 << 30), 0x23: (">u4", (20, 10, 0), 0), 0x24: (">u4", (22, 12, 2), 0)}
 # the byte formats: constant -> the byte of component 0, 1, 2 and of alpha
 _VIDEO444_BYTES = {0x26: (2, 1, 0, 3), 0x27: (2, 1, 0, 3), 0x28: (0, 1, 2, 3), 0x29: (1, 2, 3, 0)}
-
-
-def video444_format(fmt, bit_depth):
-    """-> (OJPHGPU_VIDEO_* constant, bit depth) of a 4:4:4 format name, refused when the depth is outside the format's column;
-    without a depth: the one the name fixes, else the widest of the column"""
-    if fmt not in VIDEO444_FORMATS:
-        raise ValueError("4:4:4 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO444_FORMATS))))
-    code, fixed = VIDEO444_FORMATS[fmt]
-    _, lo, hi = _VIDEO444_COLUMN[code]
-    b = int((hi if fixed is None else fixed) if bit_depth is None else bit_depth)
-    if not lo <= b <= hi or (fixed is not None and b != fixed):
-        raise ValueError("video format %r does not hold %d-bit samples" % (fmt, b))
-    return code, b
-
-
-def video444_layout(fmt, width, height):
-    """-> (row_bytes, frame_bytes) of the tight layout of a width x height frame, as ojphgpu_video444_layout"""
-    if fmt not in VIDEO444_FORMATS:
-        raise ValueError("4:4:4 video format %r: one of %s" % (fmt, ", ".join(sorted(VIDEO444_FORMATS))))
-    if width < 1 or height < 1:
-        raise ValueError("video444_layout: a frame has at least one sample")
-    row = _VIDEO444_COLUMN[VIDEO444_FORMATS[fmt][0]][0] * int(width)
-    return row, row * int(height)
 
 
 def pack_video444(planes, fmt, bit_depth=None):

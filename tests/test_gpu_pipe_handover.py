@@ -7,7 +7,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_gpu_video import make_plan
+from tests.video_cases import C422, make_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ SEQUENCES = {
 
 def new_plan(depth, sub):
     from openjph_amd.plan import Plan, make_params
-    return make_plan(W, depth, True, h=H) if sub else Plan(make_params(W, H, 3, bit_depth=depth))
+    return make_plan(W, H, depth, True, C422) if sub else Plan(make_params(W, H, 3, bit_depth=depth))
 
 
 def setter(pipe, kind, arg):
@@ -194,3 +194,81 @@ def test_every_setter_is_refused_once_frames_flow(sub):
     ok = frame.nbytes == frame_bytes(pipe.plan, "planes", None) and same_planes(pipe.plan.unpack_frame(frame), frames[0])
     pipe.close()
     assert ok
+
+
+# ---- the refusal matrix of _set_video, against the literal table of tests/test_cpu_video_formats.py
+def set_video_answers(pipe, cell, depth, container):
+    """every name on a pipe that has no video hand-over on, planes again between names -> the names accepted; each answer
+    checked against the table, a refusal E_INVALID that leaves the pipe as it was"""
+    from openjph_amd import capi
+    from tests.test_cpu_video_formats import TABLE, accepts
+    taken = []
+    for name in TABLE:
+        want = accepts(name, cell, depth, container)
+        try:
+            pipe.set_video(name)
+            got = True
+        except capi.OjphError as e:
+            assert e.code == capi.E_INVALID, (name, e.code)
+            got = False
+        assert got == want, (name, cell, depth, container, got)
+        assert pipe.video == (name if got else None)
+        pipe.set_video(None)
+        assert pipe.video is None
+        if got:
+            taken.append(name)
+    return taken
+
+
+def replaced_and_refused(pipe, taken, cell, depth, container):
+    """the accepted names one after the other without planes between them, a refused name after each: what was accepted last
+    stays on -> it (None: nothing is accepted on this pipe)"""
+    from openjph_amd import capi
+    from tests.test_cpu_video_formats import TABLE, accepts
+    refused = [n for n in TABLE if not accepts(n, cell, depth, container)]
+    for i, name in enumerate(taken):
+        pipe.set_video(name)
+        with pytest.raises(capi.OjphError):
+            pipe.set_video(refused[i % len(refused)])
+        assert pipe.video == name
+    return taken[-1] if taken else None
+
+
+def test_set_video_accepts_exactly_what_the_format_table_says():
+    """Encoder pipes of 3 components of 6 x 4 luma (chroma 6 x 4, 3 x 4, 3 x 2; depths 8, 10, 12, 16; containers 8, 16, 32: the 27 of
+    the 36 whose container holds the depth exist) x every name, and two decoder pipes on a 4:4:4 stream, one of them a window
+    with odd x0 and odd y0: there is no chroma cell, so it takes what the full frame takes."""
+    from openjph_amd import capi, codec
+    from openjph_amd.pipeline import DecoderPipe, EncoderPipe, pack_video444
+    from openjph_amd.plan import Plan, make_params
+    from tests.test_cpu_video_formats import table_layout
+    pipes = 0
+    for cell in ((1, 1), (2, 1), (2, 2)):
+        for depth in (8, 10, 12, 16):
+            for container in (8, 16, 32):
+                plan = Plan(make_params(6, 4, 3, bit_depth=depth, downsampling=[(1, 1), cell, cell]))
+                assert [(plan.comp_info(c)["w"], plan.comp_info(c)["h"]) for c in (1, 2)] == [(-(-6 // cell[0]), -(-4 // cell[1]))] * 2
+                try:
+                    pipe = EncoderPipe(plan=plan, depth=2, container=container)
+                except capi.OjphError:
+                    assert container < depth, (cell, depth, container)
+                    continue
+                assert container >= depth
+                pipes += 1
+                last = replaced_and_refused(pipe, set_video_answers(pipe, cell, depth, container), cell, depth, container)
+                buf = pipe.acquire()                               # the frame is the one of what was accepted last
+                assert buf.nbytes == (table_layout(last, 6, 4)[2] if last else plan.frame_elems * container // 8), (cell, depth, container, last)
+                pipe.close()
+    assert pipes == 3 * (3 + 2 + 2 + 2)
+    w, h, depth, container = 22, 10, 8, 16
+    rng = np.random.default_rng(22)
+    cs = codec.Encoder(plan=Plan(make_params(w, h, 3, bit_depth=depth))).encode([rng.integers(0, 1 << depth, (h, w)).astype(np.int32) for _ in range(3)])
+    for view in ({}, dict(region=(3, 1, 9, 5))):
+        pipe = DecoderPipe(cs, depth=2, container=container, **view)
+        last = replaced_and_refused(pipe, set_video_answers(pipe, (1, 1), depth, container), (1, 1), depth, container)
+        assert last is not None
+        dec = codec.Decoder(cs, **view)
+        want = pack_video444(dec.plan.unpack_frame(dec.decode()), last, depth)
+        (got,) = list(pipe.decode_sequence([cs]))
+        pipe.close()
+        assert got.dtype == np.uint8 and got.shape == want.shape and got.tobytes() == want.tobytes(), (view, last)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests.test_cpu_video import garbage_in_padding, random_planes
+from tests.video_cases import C422, GUARD, decoded_planes, edged_planes, feed_planes, make_plan, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -17,14 +18,7 @@ WIDTHS = (1, 2, 3, 6, 7, 15, 16, 17, 31, 32, 33, 47, 48, 49, 97, 200)
 HEIGHTS = (1, 3)
 WIDE = (6149, 5)            # ... and rows of more than 64 units of every kernel: several workgroups share a row; five rows: two workgroups deep
 NP_DT = {8: np.uint8, 16: np.uint16, 32: np.int32}
-GUARD = 256                 # bytes of a fill pattern in front of and behind every destination
 DS422 = [(1, 1), (2, 1), (2, 1)]
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda()
 
 
 def guarded(nbytes, container):
@@ -120,27 +114,6 @@ def test_stage_refusals():
 
 
 # ---- the pipes
-def make_plan(w, depth, rev, h=34, **kw):
-    from openjph_amd.plan import Plan, make_params
-    return Plan(make_params(w, h, 3, bit_depth=depth, reversible=rev, **dict(dict(downsampling=DS422), **kw)))
-
-
-def edged_planes(seed, w, h, depth):
-    """blocks of 0 and 2^depth - 1: a lossy decode of them leaves the range"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for ww in (w, (w + 1) // 2, (w + 1) // 2):
-        a = np.where(rng.integers(0, 2, (h // 2 + 1, ww // 3 + 1)) == 1, (1 << depth) - 1, 0)
-        out.append(np.kron(a, np.ones((2, 3), int))[:h, :ww].astype(np.int32))
-    return out
-
-
-def feed_planes(pipe, planes):
-    buf = pipe.acquire()
-    buf[...] = pipe.plan.pack_frame(planes).reshape(buf.shape)
-    pipe.submit()
-
-
 @pytest.mark.parametrize("fmt,w,depth,rev,container", [("v210", 98, 10, True, 16), ("v210", 98, 10, False, 16), ("y210", 98, 10, True, 16),
                                                         ("y210", 98, 10, False, 32), ("uyvy", 97, 8, True, 8), ("yuy2", 97, 8, True, 16),
                                                         ("y212", 98, 12, True, 16), ("y216", 98, 16, True, 32)])
@@ -150,9 +123,9 @@ def test_encoder_pipe_fed_video_buffers(fmt, w, depth, rev, container):
     from oracle import refbind
     rng = np.random.default_rng(depth + w)
     frames = [random_planes(rng, w, 34, depth) for _ in range(3)]
-    enc = codec.Encoder(plan=make_plan(w, depth, rev))
+    enc = codec.Encoder(plan=make_plan(w, 34, depth, rev, C422))
     want = [enc.encode(enc.plan.pack_frame(p)) for p in frames]
-    pipe = EncoderPipe(plan=make_plan(w, depth, rev), depth=2, container=container, video=fmt)     # three frames: the slots are recycled
+    pipe = EncoderPipe(plan=make_plan(w, 34, depth, rev, C422), depth=2, container=container, video=fmt)     # three frames: the slots are recycled
     buf = pipe.acquire()
     assert buf.dtype == np.uint8 and buf.shape == (34, video_layout(fmt, w, 34)[0])
     got = list(pipe.encode_sequence(pack_video(p, fmt, depth) for p in frames))
@@ -163,19 +136,13 @@ def test_encoder_pipe_fed_video_buffers(fmt, w, depth, rev, container):
         assert got[0] == lib.encode(frames[0], depth, reversible=rev, downsampling=DS422, size=(w, 34))
 
 
-def decoded_planes(cs, **view):
-    from openjph_amd import codec
-    dec = codec.Decoder(cs, **view)
-    return dec.plan.unpack_frame(dec.decode())
-
-
 @pytest.mark.parametrize("fmt,w,depth", [("v210", 98, 10), ("y210", 98, 10), ("uyvy", 97, 8), ("yuy2", 97, 8)])
 def test_decoder_pipe_hands_back_video_buffers(fmt, w, depth):
     from openjph_amd import codec
     from openjph_amd.pipeline import DecoderPipe, pack_video
     rng = np.random.default_rng(w + depth)
-    lossless = codec.Encoder(plan=make_plan(w, depth, True)).encode(random_planes(rng, w, 34, depth))
-    lossy = codec.Encoder(plan=make_plan(w, depth, False, qstep=0.05)).encode(edged_planes(5, w, 34, depth))
+    lossless = codec.Encoder(plan=make_plan(w, 34, depth, True, C422)).encode(random_planes(rng, w, 34, depth))
+    lossy = codec.Encoder(plan=make_plan(w, 34, depth, False, C422, qstep=0.05)).encode(edged_planes(5, w, 34, depth, C422))
     assert max(int(p.max()) for p in decoded_planes(lossy)) > (1 << depth) - 1          # the clamp has something to do
     for cs, view in ((lossless, {}), (lossy, {}), (lossless, dict(skip_res=1)), (lossless, dict(region=(32, 5, 49, 20))),
                      (lossy, dict(skip_res=(1, 1), region=(16, 2, 21, 9)))):
@@ -194,12 +161,12 @@ def test_video_frames_through_the_searches():
     w, h, depth = 98, 34, 10
     img = synth_image(3, h, w, depth, seed=3)
     planes = [img[0], img[1][:, : (w + 1) // 2], img[2][:, : (w + 1) // 2]]
-    plain = len(codec.Encoder(plan=make_plan(w, depth, False)).encode(planes))
+    plain = len(codec.Encoder(plan=make_plan(w, 34, depth, False, C422)).encode(planes))
     for kw in (dict(max_bytes=plain * 2 // 3), dict(min_psnr=38.0)):
-        a = EncoderPipe(plan=make_plan(w, depth, False), depth=2, video="v210", **kw)
+        a = EncoderPipe(plan=make_plan(w, 34, depth, False, C422), depth=2, video="v210", **kw)
         got = list(a.encode_sequence([pack_video(planes, "v210", depth)]))
         a.close()
-        b = EncoderPipe(plan=make_plan(w, depth, False), depth=2, **kw)
+        b = EncoderPipe(plan=make_plan(w, 34, depth, False, C422), depth=2, **kw)
         feed_planes(b, planes)
         want = b.collect()
         b.close()
@@ -218,7 +185,7 @@ def test_pipe_refusals_leave_a_plane_pipe():
         return pipe.collect() == codec.Encoder(plan=pipe.plan).encode(planes)
 
     def enc_refuses(fmt, w=98, depth=10, **plan_kw):
-        pipe = EncoderPipe(plan=make_plan(w, depth, True, **plan_kw), depth=2, container=16)
+        pipe = EncoderPipe(plan=make_plan(w, 34, depth, True, C422, **plan_kw), depth=2, container=16)
         with pytest.raises(capi.OjphError) as e:
             pipe.set_video(fmt)
         ok = e.value.code == capi.E_INVALID and pipe.video is None and still_a_plane_pipe(pipe)
@@ -234,21 +201,21 @@ def test_pipe_refusals_leave_a_plane_pipe():
     assert enc_refuses("y210", depth=8)
     assert enc_refuses("uyvy", depth=10)
     # video together with pixels / packed, either order
-    pipe = EncoderPipe(plan=make_plan(98, 10, True), depth=2, packed=10)
+    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True, C422), depth=2, packed=10)
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("v210")
     assert e.value.code == capi.E_INVALID
     pipe.close()
-    pipe = EncoderPipe(plan=make_plan(98, 10, True), depth=2, video="v210")
+    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True, C422), depth=2, video="v210")
     assert pipe._lib.ojphgpu_enc_pipe_set_packed(pipe._h, 10) == capi.E_INVALID
     assert pipe._lib.ojphgpu_enc_pipe_set_pixels(pipe._h, 16, 0) == capi.E_INVALID
     pipe.set_video(None)                                                                   # 0 switches back to planes
     assert still_a_plane_pipe(pipe)
     pipe.close()
     with pytest.raises(capi.OjphError):
-        EncoderPipe(plan=make_plan(98, 8, True, downsampling=None), depth=2, container=8, pixels=(8, False), video="uyvy")
+        EncoderPipe(plan=make_plan(98, 34, 8, True, C422, downsampling=None), depth=2, container=8, pixels=(8, False), video="uyvy")
     # a call after the first acquire()
-    pipe = EncoderPipe(plan=make_plan(98, 10, True), depth=2)
+    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True, C422), depth=2)
     pipe.acquire()
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("v210")
@@ -256,7 +223,7 @@ def test_pipe_refusals_leave_a_plane_pipe():
     pipe.close()
     # the decoder: a window that starts on an odd column, packed frames, a call after the first submit()
     planes = random_planes(rng, 98, 34, 10)
-    cs = codec.Encoder(plan=make_plan(98, 10, True)).encode(planes)
+    cs = codec.Encoder(plan=make_plan(98, 34, 10, True, C422)).encode(planes)
     for region in ((33, 5, 49, 20), (33, 5, 50, 20)):
         pipe = DecoderPipe(cs, depth=2, region=region)
         with pytest.raises(capi.OjphError) as e:

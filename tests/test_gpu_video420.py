@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.test_cpu_video420 import garbage_in_padding420, random_planes420
+from tests.video_cases import C420, FILL, GUARD, decoded_planes, edged_planes, feed_planes, guarded_bytes, make_plan, pitched, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -20,16 +21,8 @@ WIDTHS += (4, 5, 511, 512, 1023, 1024, 1025)
 HEIGHTS = (1, 2, 3, 5)
 WIDE = (6149, 5)            # several workgroups share a row; 5 + 3 rows: two workgroups deep
 NP_DT = {8: np.uint8, 16: np.uint16, 32: np.int32}
-GUARD = 256                 # bytes of the fill pattern in front of and behind every destination
-FILL = 0x5A
 DS420 = [(1, 1), (2, 2), (2, 2)]
 DS422 = [(1, 1), (2, 1), (2, 1)]
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda()
 
 
 def shapes():
@@ -48,19 +41,6 @@ def layouts(fmt, w, h):
     return ((row, row, None),                                      # tight
             (row + 3 * elem(fmt), row + 3 * elem(fmt), elem(fmt)),   # row_bytes + 6 / + 12: the alignment changes row by row; chroma one element off 16 bytes
             (big, big + 256, 0))                                   # both pitches a multiple of 256
-
-
-def pitched(rows, pitch, rng=None):
-    """[n, row_bytes] -> the bytes of a plane of that pitch up to the end of its last row; the slack: FILL, or random bytes"""
-    n, row = rows.shape
-    out = np.full((n, pitch), FILL, np.uint8) if rng is None else rng.integers(0, 256, (n, pitch)).astype(np.uint8)
-    out[:, :row] = rows
-    return out.reshape(-1)[: pitch * (n - 1) + row]
-
-
-def guarded_bytes(content, front=GUARD):
-    """-> the bytes of a tensor that holds `content` between guards of FILL"""
-    return np.concatenate([np.full(front, FILL, np.uint8), content, np.full(GUARD, FILL, np.uint8)])
 
 
 def surface(buf, h, lp, cp, coff, rng=None):
@@ -187,27 +167,6 @@ def test_stage_refusals():
 
 
 # ---- the pipes
-def make_plan(w, h, depth, rev, **kw):
-    from openjph_amd.plan import Plan, make_params
-    return Plan(make_params(w, h, 3, bit_depth=depth, reversible=rev, **dict(dict(downsampling=DS420), **kw)))
-
-
-def edged_planes(seed, w, h, depth):
-    """blocks of 0 and 2^depth - 1: a lossy decode of them leaves the range"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for ww, hh in ((w, h), ((w + 1) // 2, (h + 1) // 2), ((w + 1) // 2, (h + 1) // 2)):
-        a = np.where(rng.integers(0, 2, (hh // 2 + 1, ww // 3 + 1)) == 1, (1 << depth) - 1, 0)
-        out.append(np.kron(a, np.ones((2, 3), int))[:hh, :ww].astype(np.int32))
-    return out
-
-
-def feed_planes(pipe, planes):
-    buf = pipe.acquire()
-    buf[...] = pipe.plan.pack_frame(planes).reshape(buf.shape)
-    pipe.submit()
-
-
 @pytest.mark.parametrize("fmt,w,h,depth,rev,container", [("nv12", 97, 33, 8, True, 8), ("nv21", 98, 34, 8, False, 16), ("p010", 98, 33, 10, True, 16),
                                                           ("p010", 97, 34, 10, False, 32), ("p012", 98, 34, 12, True, 16),
                                                           ("p016", 98, 34, 16, True, 32)])
@@ -217,9 +176,9 @@ def test_encoder_pipe_fed_420_buffers(fmt, w, h, depth, rev, container):
     from oracle import refbind
     rng = np.random.default_rng(depth + w + h)
     frames = [random_planes420(rng, w, h, depth) for _ in range(3)]
-    enc = codec.Encoder(plan=make_plan(w, h, depth, rev))
+    enc = codec.Encoder(plan=make_plan(w, h, depth, rev, C420))
     want = [enc.encode(enc.plan.pack_frame(p)) for p in frames]
-    pipe = EncoderPipe(plan=make_plan(w, h, depth, rev), depth=2, container=container, video=fmt)     # three frames: the slots are recycled
+    pipe = EncoderPipe(plan=make_plan(w, h, depth, rev, C420), depth=2, container=container, video=fmt)     # three frames: the slots are recycled
     buf = pipe.acquire()
     assert buf.dtype == np.uint8 and buf.shape == (h + (h + 1) // 2, video420_layout(fmt, w, h)[0])
     got = list(pipe.encode_sequence(pack_video420(p, fmt, depth) for p in frames))
@@ -230,19 +189,13 @@ def test_encoder_pipe_fed_420_buffers(fmt, w, h, depth, rev, container):
         assert got[0] == lib.encode(frames[0], depth, reversible=rev, downsampling=DS420, size=(w, h))
 
 
-def decoded_planes(cs, **view):
-    from openjph_amd import codec
-    dec = codec.Decoder(cs, **view)
-    return dec.plan.unpack_frame(dec.decode())
-
-
 @pytest.mark.parametrize("fmt,w,h,depth", [("nv12", 97, 33, 8), ("nv21", 98, 34, 8), ("p010", 98, 34, 10)])
 def test_decoder_pipe_hands_back_420_buffers(fmt, w, h, depth):
     from openjph_amd import codec
     from openjph_amd.pipeline import DecoderPipe, pack_video420
     rng = np.random.default_rng(w + depth)
-    lossless = codec.Encoder(plan=make_plan(w, h, depth, True)).encode(random_planes420(rng, w, h, depth))
-    lossy = codec.Encoder(plan=make_plan(w, h, depth, False, qstep=0.05)).encode(edged_planes(5, w, h, depth))
+    lossless = codec.Encoder(plan=make_plan(w, h, depth, True, C420)).encode(random_planes420(rng, w, h, depth))
+    lossy = codec.Encoder(plan=make_plan(w, h, depth, False, C420, qstep=0.05)).encode(edged_planes(5, w, h, depth, C420))
     assert max(int(p.max()) for p in decoded_planes(lossy)) > (1 << depth) - 1          # the clamp has something to do
     for cs, view in ((lossless, {}), (lossy, {}), (lossless, dict(skip_res=1)), (lossy, dict(skip_res=1)), (lossless, dict(region=(32, 6, 49, 20))),
                      (lossy, dict(region=(32, 6, 49, 20))), (lossy, dict(skip_res=(1, 1), region=(16, 4, 21, 9)))):
@@ -261,12 +214,12 @@ def test_p010_frames_through_the_searches():
     w, h, depth = 98, 34, 10
     img = synth_image(3, h, w, depth, seed=3)
     planes = [img[0], img[1][: (h + 1) // 2, : (w + 1) // 2], img[2][: (h + 1) // 2, : (w + 1) // 2]]
-    plain = len(codec.Encoder(plan=make_plan(w, h, depth, False)).encode(planes))
+    plain = len(codec.Encoder(plan=make_plan(w, h, depth, False, C420)).encode(planes))
     for kw in (dict(max_bytes=plain * 2 // 3), dict(min_psnr=38.0)):                      # one budget pipe, one quality pipe
-        a = EncoderPipe(plan=make_plan(w, h, depth, False), depth=2, video="p010", **kw)
+        a = EncoderPipe(plan=make_plan(w, h, depth, False, C420), depth=2, video="p010", **kw)
         got = list(a.encode_sequence([pack_video420(planes, "p010")]))
         a.close()
-        b = EncoderPipe(plan=make_plan(w, h, depth, False), depth=2, **kw)
+        b = EncoderPipe(plan=make_plan(w, h, depth, False, C420), depth=2, **kw)
         feed_planes(b, planes)
         want = b.collect()
         b.close()
@@ -285,7 +238,7 @@ def test_pipe_refusals_leave_a_plane_pipe():
         return pipe.collect() == codec.Encoder(plan=pipe.plan).encode(planes)
 
     def enc_refuses(fmt, w=98, h=34, depth=10, container=16, **plan_kw):
-        pipe = EncoderPipe(plan=make_plan(w, h, depth, True, **plan_kw), depth=2, container=container)
+        pipe = EncoderPipe(plan=make_plan(w, h, depth, True, C420, **plan_kw), depth=2, container=container)
         with pytest.raises(capi.OjphError) as e:
             pipe.set_video(fmt)
         ok = e.value.code == capi.E_INVALID and pipe.video is None and still_a_plane_pipe(pipe)
@@ -306,19 +259,19 @@ def test_pipe_refusals_leave_a_plane_pipe():
     assert enc_refuses("p012", depth=10)
     # p010 with container 8: such a pipe cannot exist on a 10-bit plan, so ask the library about 8-bit containers and P0XX on
     # the one plan that gets that far
-    pipe = EncoderPipe(plan=make_plan(98, 34, 8, True), depth=2, container=8)
+    pipe = EncoderPipe(plan=make_plan(98, 34, 8, True, C420), depth=2, container=8)
     assert pipe._lib.ojphgpu_enc_pipe_set_video(pipe._h, 0x13) == capi.E_INVALID
     with pytest.raises(capi.OjphError):
         pipe.set_video("p010")
     assert pipe.video is None and still_a_plane_pipe(pipe)
     pipe.close()
     # video together with pixels / packed, either order
-    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True), depth=2, packed=10)
+    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True, C420), depth=2, packed=10)
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("p010")
     assert e.value.code == capi.E_INVALID
     pipe.close()
-    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True), depth=2, video="p010")
+    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True, C420), depth=2, video="p010")
     assert pipe._lib.ojphgpu_enc_pipe_set_packed(pipe._h, 10) == capi.E_INVALID
     assert pipe._lib.ojphgpu_enc_pipe_set_pixels(pipe._h, 16, 0) == capi.E_INVALID
     pipe.set_video("p0xx")                                                                 # repeatable
@@ -326,9 +279,9 @@ def test_pipe_refusals_leave_a_plane_pipe():
     assert pipe.video is None and still_a_plane_pipe(pipe)
     pipe.close()
     with pytest.raises(capi.OjphError):
-        EncoderPipe(plan=make_plan(98, 34, 8, True, downsampling=None), depth=2, container=8, pixels=(8, False), video="nv12")
+        EncoderPipe(plan=make_plan(98, 34, 8, True, C420, downsampling=None), depth=2, container=8, pixels=(8, False), video="nv12")
     # a call after the first acquire()
-    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True), depth=2)
+    pipe = EncoderPipe(plan=make_plan(98, 34, 10, True, C420), depth=2)
     pipe.acquire()
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("p010")
@@ -336,7 +289,7 @@ def test_pipe_refusals_leave_a_plane_pipe():
     pipe.close()
     # the decoder: a window with odd x0; one with odd y0 and even height; packed frames; a call after the first submit()
     planes = random_planes420(rng, 98, 34, 10)
-    cs = codec.Encoder(plan=make_plan(98, 34, 10, True)).encode(planes)
+    cs = codec.Encoder(plan=make_plan(98, 34, 10, True, C420)).encode(planes)
     for region in ((33, 6, 49, 20), (33, 6, 50, 20), (32, 5, 49, 20), (32, 5, 50, 21)):
         pipe = DecoderPipe(cs, depth=2, region=region)
         with pytest.raises(capi.OjphError) as e:

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.test_cpu_video444 import garbage_in_padding444, random_planes444
+from tests.video_cases import FILL, GUARD, decoded_planes, edged_planes, feed_planes, guarded_bytes, make_plan, pitched, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -18,14 +19,6 @@ WIDTHS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1
 HEIGHTS = (1, 2, 3, 5)
 WIDE = (6149, 5)            # several workgroups share a row; 5 rows: two workgroups deep
 NP_DT = {8: np.uint8, 16: np.uint16, 32: np.int32}
-GUARD = 256                 # bytes of the fill pattern in front of and behind every destination
-FILL = 0x5A
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda()
 
 
 def shapes():
@@ -40,21 +33,6 @@ def layouts(fmt, w, h):
     return ((None, 0),                                             # tight
             (row + 3 * pixel, pixel),                              # one pixel off 16 bytes, and the alignment changes row by row
             (-(-row // 256) * 256, 0))                             # a multiple of 256
-
-
-def pitched(rows, pitch, rng=None):
-    """[n, row_bytes] -> the bytes of a buffer of that pitch up to the end of its last row; the slack: FILL, or random bytes"""
-    n, row = rows.shape
-    if pitch is None:
-        return rows.reshape(-1)
-    out = np.full((n, pitch), FILL, np.uint8) if rng is None else rng.integers(0, 256, (n, pitch)).astype(np.uint8)
-    out[:, :row] = rows
-    return out.reshape(-1)[: pitch * (n - 1) + row]
-
-
-def guarded_bytes(content, front=GUARD):
-    """-> the bytes of a tensor that holds `content` between guards of FILL"""
-    return np.concatenate([np.full(front, FILL, np.uint8), content, np.full(GUARD, FILL, np.uint8)])
 
 
 @pytest.mark.parametrize("fmt,depth,container", [(f, b, c) for f, b, cs in FORMATS for c in cs])
@@ -194,27 +172,6 @@ def test_stage_refusals():
 W, H = 98, 34
 
 
-def make_plan(depth, rev, w=W, h=H, **kw):
-    from openjph_amd.plan import Plan, make_params
-    return Plan(make_params(w, h, kw.pop("num_comps", 3), bit_depth=depth, reversible=rev, **kw))
-
-
-def edged_planes(seed, w, h, depth):
-    """blocks of 0 and 2^depth - 1: a lossy decode of them leaves the range"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(3):
-        a = np.where(rng.integers(0, 2, (h // 2 + 1, w // 3 + 1)) == 1, (1 << depth) - 1, 0)
-        out.append(np.kron(a, np.ones((2, 3), int))[:h, :w].astype(np.int32))
-    return out
-
-
-def feed_planes(pipe, planes):
-    buf = pipe.acquire()
-    buf[...] = pipe.plan.pack_frame(planes).reshape(buf.shape)
-    pipe.submit()
-
-
 # one format of each pixel kind (little-endian dword, big-endian dword, four words, bytes), an RGB format on a plan with the colour
 # transform on, reversible and irreversible
 @pytest.mark.parametrize("fmt,depth,rev,container,ct", [("v410", 10, True, 16, False), ("y410", 10, False, 32, False), ("r210", 10, True, 16, True),
@@ -226,9 +183,9 @@ def test_encoder_pipe_fed_444_buffers(fmt, depth, rev, container, ct):
     from openjph_amd.pipeline import EncoderPipe, pack_video444, video444_layout
     rng = np.random.default_rng(depth + container)
     frames = [random_planes444(rng, W, H, depth) for _ in range(3)]
-    enc = codec.Encoder(plan=make_plan(depth, rev, color_transform=ct))
+    enc = codec.Encoder(plan=make_plan(W, H, depth, rev, color_transform=ct))
     want = [enc.encode(enc.plan.pack_frame(p)) for p in frames]
-    pipe = EncoderPipe(plan=make_plan(depth, rev, color_transform=ct), depth=2, container=container, video=fmt)     # three frames: the slots are recycled
+    pipe = EncoderPipe(plan=make_plan(W, H, depth, rev, color_transform=ct), depth=2, container=container, video=fmt)     # three frames: the slots are recycled
     buf = pipe.acquire()
     assert buf.dtype == np.uint8 and buf.shape == (H, video444_layout(fmt, W, H)[0])
     got = list(pipe.encode_sequence(pack_video444(p, fmt, depth) for p in frames))
@@ -236,19 +193,13 @@ def test_encoder_pipe_fed_444_buffers(fmt, depth, rev, container, ct):
     assert got == want
 
 
-def decoded_planes(cs, **view):
-    from openjph_amd import codec
-    dec = codec.Decoder(cs, **view)
-    return dec.plan.unpack_frame(dec.decode())
-
-
 @pytest.mark.parametrize("fmt,depth,ct", [("v410", 10, False), ("r210", 10, True), ("y412", 12, False), ("bgra", 8, True)])
 def test_decoder_pipe_hands_back_444_buffers(fmt, depth, ct):
     from openjph_amd import codec
     from openjph_amd.pipeline import DecoderPipe, pack_video444
     rng = np.random.default_rng(depth)
-    lossless = codec.Encoder(plan=make_plan(depth, True, color_transform=ct)).encode(random_planes444(rng, W, H, depth))
-    lossy = codec.Encoder(plan=make_plan(depth, False, qstep=0.05)).encode(edged_planes(5, W, H, depth))
+    lossless = codec.Encoder(plan=make_plan(W, H, depth, True, color_transform=ct)).encode(random_planes444(rng, W, H, depth))
+    lossy = codec.Encoder(plan=make_plan(W, H, depth, False, qstep=0.05)).encode(edged_planes(5, W, H, depth))
     assert max(int(p.max()) for p in decoded_planes(lossy)) > (1 << depth) - 1          # the clamp has something to do
     # plain, a reduced resolution, a window with odd x0 and odd y0, both
     for cs, view in ((lossless, {}), (lossy, {}), (lossless, dict(skip_res=1)), (lossy, dict(skip_res=1)), (lossless, dict(region=(33, 7, 49, 20))),
@@ -268,12 +219,12 @@ def test_v410_frames_through_the_searches():
     depth = 10
     img = synth_image(3, H, W, depth, seed=3)
     planes = [img[0], img[1], img[2]]
-    plain = len(codec.Encoder(plan=make_plan(depth, False)).encode(planes))
+    plain = len(codec.Encoder(plan=make_plan(W, H, depth, False)).encode(planes))
     for kw in (dict(max_bytes=plain * 2 // 3), dict(min_psnr=38.0)):                      # one budget pipe, one quality pipe
-        a = EncoderPipe(plan=make_plan(depth, False), depth=2, video="v410", **kw)
+        a = EncoderPipe(plan=make_plan(W, H, depth, False), depth=2, video="v410", **kw)
         got = list(a.encode_sequence([pack_video444(planes, "v410")]))
         a.close()
-        want = codec.Encoder(plan=make_plan(depth, False), **kw).encode(planes)
+        want = codec.Encoder(plan=make_plan(W, H, depth, False), **kw).encode(planes)
         assert got == [want] and ("max_bytes" not in kw or len(want) <= plain * 2 // 3)
 
 
@@ -289,7 +240,7 @@ def test_pipe_refusals_leave_a_plane_pipe():
         return pipe.collect() == codec.Encoder(plan=pipe.plan).encode(planes)
 
     def enc_refuses(fmt, depth=10, container=16, **plan_kw):
-        pipe = EncoderPipe(plan=make_plan(depth, True, **plan_kw), depth=2, container=container)
+        pipe = EncoderPipe(plan=make_plan(W, H, depth, True, **plan_kw), depth=2, container=container)
         with pytest.raises(capi.OjphError) as e:
             pipe.set_video(fmt)
         ok = e.value.code == capi.E_INVALID and pipe.video is None and still_a_plane_pipe(pipe)
@@ -316,24 +267,24 @@ def test_pipe_refusals_leave_a_plane_pipe():
     assert enc_refuses("bgra", depth=10)
     assert enc_refuses("argb", depth=9)
     # v410 with 8-bit containers: the plan has 8-bit samples, which v410 holds, but not in that container
-    pipe = EncoderPipe(plan=make_plan(8, True), depth=2, container=8)
+    pipe = EncoderPipe(plan=make_plan(W, H, 8, True), depth=2, container=8)
     assert pipe._lib.ojphgpu_enc_pipe_set_video(pipe._h, 0x21) == capi.E_INVALID
     with pytest.raises(capi.OjphError):
         pipe.set_video("v410")
     assert pipe.video is None and still_a_plane_pipe(pipe)
     pipe.close()
     # video together with pixels / packed, either order
-    pipe = EncoderPipe(plan=make_plan(10, True), depth=2, packed=10)
+    pipe = EncoderPipe(plan=make_plan(W, H, 10, True), depth=2, packed=10)
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("v410")
     assert e.value.code == capi.E_INVALID
     pipe.close()
-    pipe = EncoderPipe(plan=make_plan(8, True), depth=2, pixels=(8, False))
+    pipe = EncoderPipe(plan=make_plan(W, H, 8, True), depth=2, pixels=(8, False))
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("bgra")
     assert e.value.code == capi.E_INVALID
     pipe.close()
-    pipe = EncoderPipe(plan=make_plan(10, True), depth=2, video="v410")
+    pipe = EncoderPipe(plan=make_plan(W, H, 10, True), depth=2, video="v410")
     assert pipe._lib.ojphgpu_enc_pipe_set_packed(pipe._h, 10) == capi.E_INVALID
     assert pipe._lib.ojphgpu_enc_pipe_set_pixels(pipe._h, 16, 0) == capi.E_INVALID
     pipe.set_video("y410")                                                                 # repeatable
@@ -341,9 +292,9 @@ def test_pipe_refusals_leave_a_plane_pipe():
     assert pipe.video is None and still_a_plane_pipe(pipe)
     pipe.close()
     with pytest.raises(capi.OjphError):
-        EncoderPipe(plan=make_plan(8, True), depth=2, container=8, pixels=(8, False), video="bgra")
+        EncoderPipe(plan=make_plan(W, H, 8, True), depth=2, container=8, pixels=(8, False), video="bgra")
     # a call after the first acquire()
-    pipe = EncoderPipe(plan=make_plan(10, True), depth=2)
+    pipe = EncoderPipe(plan=make_plan(W, H, 10, True), depth=2)
     pipe.acquire()
     with pytest.raises(capi.OjphError) as e:
         pipe.set_video("v410")
@@ -351,8 +302,8 @@ def test_pipe_refusals_leave_a_plane_pipe():
     pipe.close()
     # the decoder: a sub-sampled codestream, packed frames, a name of another depth, a call after the first submit()
     planes = random_planes444(rng, W, H, 10)
-    cs = codec.Encoder(plan=make_plan(10, True)).encode(planes)
-    sub = make_plan(10, True, downsampling=[(1, 1), (2, 1), (2, 1)])
+    cs = codec.Encoder(plan=make_plan(W, H, 10, True)).encode(planes)
+    sub = make_plan(W, H, 10, True, downsampling=[(1, 1), (2, 1), (2, 1)])
     cs422 = codec.Encoder(plan=sub).encode([planes[0], planes[1][:, : (W + 1) // 2], planes[2][:, : (W + 1) // 2]])
     pipe = DecoderPipe(cs422, depth=2)
     with pytest.raises(capi.OjphError) as e:
