@@ -949,6 +949,8 @@ void ojphgpu_transcoder_destroy(ojphgpu_transcoder* t);
  *    keeps `depth` (2..16) frames in flight.  One caller thread per pipe; results come back in
  *    submission order.  container_bits = 8 | 16 | 32 (see ojphgpu_encoder_run_device16 / 8); host_threads =
  *    threads that do a frame's host part (packet headers / parsing), 0 = 2.
+ *    Three pipes: the encoder's (frames in, codestreams out), the decoder's (codestreams in, frames out) and, at the end
+ *    of this section, the transcoder's (ojphgpu_tc_pipe: codestreams in, codestreams out, section 5d frame after frame).
  * ------------------------------------------------------------------------------------------ */
 typedef struct ojphgpu_enc_pipe ojphgpu_enc_pipe;
 typedef struct ojphgpu_dec_pipe ojphgpu_dec_pipe;
@@ -1096,6 +1098,50 @@ int  ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* pipe, int bits);     /* decod
  * with an odd y0 is refused whatever its height, as one with an odd x0 is.  The 4:4:4 formats of section 7d come back in
  * the tight layout too (ojphgpu_pack_video444, alpha opaque); there is no chroma cell, so a window passes at any x0, y0. */
 int  ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* pipe, int format);
+
+/* The transcode pipe: host codestream in, host codestream out -- section 5d's T(cs, out), source after source, with the
+ * parse, the upload, the download and Tier-2 of neighbouring frames overlapped with the device as the other two pipes do
+ * it.  Every collected codestream is, byte for byte, what ojphgpu_transcoder_submit + _finish give for its source.
+ * A frame passes three stages: host threads parse it, check it, fill its block descriptors into pinned memory and enqueue
+ * the uploads on the copy-in stream; ONE ordered thread per pipe owns the compute stream and runs, frame by frame in submit
+ * order, the block decoder, the collection of its verdicts (with the repeat a one-launch run may ask for; no block is coded
+ * before the verdicts are in) and the coding -- plain, or the budget's search; host threads lay the codestream out from
+ * the block lengths, and the assembly and the download run on the copy-out stream.  The pipe has one transcoder object and
+ * so one arena: frame n + 1's block decoder writes the planes frame n's coding reads, hence the frames are strictly serial
+ * on the compute stream and only the front and the finish of their neighbours overlap it.
+ * _create: the first source (parsed as ojphgpu_t2_parse parses it with `resilient`, as every later one is; it fixes the
+ *   geometry) and the output plan ojphgpu_plan_create_transcode made from that parse (it outlives the pipe); depth and
+ *   host_threads as above (that many threads for the front, and as many for the finish).  Refused: what
+ *   ojphgpu_transcoder_create refuses.  An irreversible output with qstep <= 0 is a pipe for a byte budget only: unless
+ *   _set_budget has switched one on, its first _acquire returns OJPHGPU_E_INVALID.
+ * _acquire: pinned host memory for the next source of `len` bytes, as ojphgpu_dec_pipe_acquire; OJPHGPU_E_AGAIN when all
+ *   slots are in flight.
+ * _submit: queues the acquired source and returns at once.
+ * _collect: the oldest submitted frame's output codestream, in pinned memory of the pipe that stays valid until its slot is
+ *   acquired again; *failed_blocks (may be NULL) = the source's blocks that failed to decode (zero blocks in the output of
+ *   a resilient pipe).  A frame fails from its own _collect only, its slot is free again, and the frames around it are byte
+ *   for byte what they are without it: a source that does not parse (the parser's code), one of another geometry
+ *   (OJPHGPU_E_INVALID), failed blocks in a pipe that is not resilient (OJPHGPU_E_BLOCK), a budget no step fits
+ *   (OJPHGPU_E_BUDGET).
+ * _set_budget: the rules of ojphgpu_enc_pipe_set_budget -- on from before the first _acquire or never, the value in force
+ *   at _submit is the frame's, it may move between frames but not back to 0 -- with the refusals of
+ *   ojphgpu_transcoder_set_budget.  The search of a frame starts from the j* of the last certified frame and alternates its
+ *   trials between the slot's output buffer and one spare: `passes` counts trials only and nothing is coded twice.
+ * _rate_info: of the frame collected last, as ojphgpu_enc_pipe_rate_info.
+ * _stats: out[0] frames completed, [1] mean host parse + descriptor time per frame (ms), [2] mean host Tier-2 time per frame
+ *   (ms), [3] mean submit -> codestream latency (ms).
+ * _fused_retries: frames whose block decoder ran twice because the one launch asked for it (ojphgpu_dec_pipe_fused_retries). */
+typedef struct ojphgpu_tc_pipe ojphgpu_tc_pipe;
+int  ojphgpu_tc_pipe_create(const uint8_t* h_codestream, size_t len, int resilient, const ojphgpu_plan* out_plan, int device,
+                            uint32_t depth, uint32_t host_threads, ojphgpu_tc_pipe** out);
+void ojphgpu_tc_pipe_destroy(ojphgpu_tc_pipe* pipe);
+int  ojphgpu_tc_pipe_acquire(ojphgpu_tc_pipe* pipe, size_t len, uint8_t** h_codestream);
+int  ojphgpu_tc_pipe_submit(ojphgpu_tc_pipe* pipe);
+int  ojphgpu_tc_pipe_collect(ojphgpu_tc_pipe* pipe, const uint8_t** h_out, size_t* len, uint32_t* failed_blocks);
+int  ojphgpu_tc_pipe_set_budget(ojphgpu_tc_pipe* pipe, uint64_t max_bytes);
+int  ojphgpu_tc_pipe_rate_info(ojphgpu_tc_pipe* pipe, ojphgpu_rate_info* info);
+int  ojphgpu_tc_pipe_stats(ojphgpu_tc_pipe* pipe, double out[4]);
+int  ojphgpu_tc_pipe_fused_retries(ojphgpu_tc_pipe* pipe, uint32_t* count);
 
 /* ---------------------------------------------------------------------------------------------
  * 7. Pixel-interleaved samples <-> planar containers on the device (kernels_pixels.hip)

@@ -412,6 +412,15 @@ SIGNATURES = {
     "ojphgpu_video_format_info": (C.c_int, [C.c_int, C.POINTER(VideoInfo)]),
     "ojphgpu_enc_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_dec_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
+    "ojphgpu_tc_pipe_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ojphgpu_tc_pipe_destroy": (None, [C.c_void_p]),
+    "ojphgpu_tc_pipe_acquire": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "ojphgpu_tc_pipe_submit": (C.c_int, [C.c_void_p]),
+    "ojphgpu_tc_pipe_collect": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "ojphgpu_tc_pipe_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_tc_pipe_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
+    "ojphgpu_tc_pipe_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "ojphgpu_tc_pipe_fused_retries": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ojphgpu_version": (C.c_char_p, []),
 }
 

@@ -1606,23 +1606,24 @@ int ojphgpu_decoder_repeat_separate(ojphgpu_decoder* d)
   return rc;
 }
 
-extern "C" int ojphgpu_decoder_failed_blocks(ojphgpu_decoder* d, uint32_t* count)
+// The verdicts of the run enqueued last, however its status bytes reach the host: fetch(user, &st) brings the status bytes + the
+// RETRY word behind them to the host once the launches enqueued so far have finished (ojphgpu_decoder_failed_blocks: a copy
+// into pageable memory and a wait for the stream; a frame pipeline: a copy kernel into pinned memory and an event).
+int ojphgpu_decoder_collect(ojphgpu_decoder* d, ojphgpu_status_fetch fetch, void* user, uint32_t* count)
 {
-  if (!d || !count || !d->ran) return OJPHGPU_E_INVALID;
-  const size_t tail = ((size_t)d->nblocks + 3u) & ~(size_t)3u;
-  std::vector<uint8_t> st(tail + 4);
+  if (!d || !fetch || !count) return OJPHGPU_E_INVALID;
   d->uncollected = false;
-  const uint8_t* status = (const uint8_t*)(d->o_status ? d->o_status : d->status.p);
+  const uint8_t* st = nullptr;
   for (int pass = 0; pass < 2; ++pass) {
-    HIPCHK(hipMemcpyAsync(st.data(), status, st.size(), hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
+    int rc = fetch(user, &st);
+    if (rc) return rc;
     // a fused launch whose workers gave up waiting for their chains (the chip was held up for seconds by other work): its
     // blocks have no verdict yet -- the frame is decoded again through the separate launches, into the same image
     if (pass == 0 && d->last_fused) {
-      const bool again = ojphgpu_fused_retry_wanted(st.data(), d->nblocks, d->fused_epoch);
+      const bool again = ojphgpu_fused_retry_wanted(st, d->nblocks, d->fused_epoch);
       d->fused_outcome(again);
       if (again) {
-        const int rc = ojphgpu_decoder_repeat_separate(d);
+        rc = ojphgpu_decoder_repeat_separate(d);
         if (rc) return rc;
         continue;
       }
@@ -1636,6 +1637,28 @@ extern "C" int ojphgpu_decoder_failed_blocks(ojphgpu_decoder* d, uint32_t* count
   for (uint32_t i = 0; i < d->nblocks; ++i) n += st[i] != 0;
   *count = n;
   return OJPHGPU_OK;
+}
+
+namespace {
+struct PageableStatus { ojphgpu_decoder* d; std::vector<uint8_t> st; };
+int fetch_pageable_status(void* user, const uint8_t** h_status)
+{
+  PageableStatus& f = *(PageableStatus*)user;
+  ojphgpu_decoder* d = f.d;
+  const uint8_t* status = (const uint8_t*)(d->o_status ? d->o_status : d->status.p);
+  HIPCHK(hipMemcpyAsync(f.st.data(), status, f.st.size(), hipMemcpyDeviceToHost, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  *h_status = f.st.data();
+  return OJPHGPU_OK;
+}
+}  // namespace
+
+extern "C" int ojphgpu_decoder_failed_blocks(ojphgpu_decoder* d, uint32_t* count)
+{
+  if (!d || !count || !d->ran) return OJPHGPU_E_INVALID;
+  const size_t tail = ((size_t)d->nblocks + 3u) & ~(size_t)3u;
+  PageableStatus f{ d, std::vector<uint8_t>(tail + 4) };
+  return ojphgpu_decoder_collect(d, fetch_pageable_status, &f, count);
 }
 
 extern "C" int ojphgpu_decoder_giveup_epoch(ojphgpu_decoder* d, uint32_t* last_giveup, uint32_t* current)
@@ -1772,8 +1795,12 @@ extern "C" int ojphgpu_transcoder_set_budget(ojphgpu_transcoder* t, uint64_t max
   return rc;
 }
 
+// ---- what one source needs of a transcoder, piece by piece: ojphgpu_transcoder_submit / _finish below put them together for
+// a single call, with the waits only a single call needs between them; the transcode pipe (ojphgpu_pipe.cpp) spreads them
+// over its stages.
+
 // the band statistics of the planes the block decoder leaves: what the search's model starts from
-static int transcoder_stats(ojphgpu_transcoder* t)
+int ojphgpu_transcoder_stats(ojphgpu_transcoder* t)
 {
   ojphgpu_decoder* d = t->dec; ojphgpu_encoder* e = t->enc;
   EncoderRate& R = *e->rate;
@@ -1787,12 +1814,76 @@ static int transcoder_stats(ojphgpu_transcoder* t)
   return OJPHGPU_OK;
 }
 
+// a later source against the first one and the output: the same geometry, no causal blocks, the reversible K_max rule
+int ojphgpu_transcoder_check_source(const ojphgpu_transcoder* t, const Plan& Q)
+{
+  const Plan& S = *t->S; const Plan& O = *t->O;
+  const int rc = ojphgpu_same_frame_geometry(S, Q, true);
+  if (rc) return rc;
+  for (uint32_t c = 0; c < Q.p.num_comps; ++c) if (Q.style(c).causal) return OJPHGPU_E_INVALID;
+  for (size_t i = 0; i < Q.bands.size(); ++i)               // (K_max is this frame's own: transcode_plans_fit saw the first frame's)
+    if (Q.style(Q.bands[i].comp).rev && O.bands[i].K_max < Q.bands[i].K_max) return OJPHGPU_E_INVALID;
+  return OJPHGPU_OK;
+}
+
+// its block descriptors into bd (one per block of the decoder half), with the layout and size checks; fi: what to upload
+int ojphgpu_transcoder_fill_descs(const ojphgpu_transcoder* t, const Plan& Q, size_t cs_len, ojphgpu_cb_desc* bd, DecFrameInfo& fi)
+{
+  const ojphgpu_decoder* d = t->dec;
+  const size_t nb = d->block_ids.size();
+  ojphgpu_decoder_fill_descs(*t->S, Q, d->block_ids, 0, 0, bd, fi);
+  uint64_t nquads = 0, naux = 0;
+  if (ojphgpu_ht_decode_layout(bd, (uint32_t)nb, &nquads, &naux) != OJPHGPU_OK) return OJPHGPU_E_INVALID;
+  if ((naux + 16) * 4 > d->aux.n || (nquads + 16) * 4 > d->quads.n) return OJPHGPU_E_INVALID;     // sized for the worst case at create
+  if (fi.first + fi.len > cs_len) return OJPHGPU_E_CODESTREAM;
+  return OJPHGPU_OK;
+}
+
+// "decode the blocks of these bytes": the block decoder over what the decoder half points at (its own buffers, or a pipe
+// slot's through o_cb_descs / o_data / o_status), with a budget the band statistics behind it
+int ojphgpu_transcoder_decode(ojphgpu_transcoder* t, bool any_refine, int kinds, uint32_t max_len1)
+{
+  ojphgpu_decoder* d = t->dec;
+  int rc;
+  d->any_refine = any_refine; d->kinds = kinds; d->max_len1 = max_len1;
+  if ((rc = decoder_run_blocks(d)) != 0) return rc;
+  if (!t->enc->budgets.empty() && (rc = ojphgpu_transcoder_stats(t)) != 0) return rc;
+  d->timer.finish(t->stream);
+  return OJPHGPU_OK;
+}
+
+// "collect verdicts and repeat": the verdicts first (and the repeat of a one-launch run whose wait ran out) -- only then is a
+// block coded.  OJPHGPU_E_BLOCK: a failed block of a source that was not parsed resiliently (*failed counts them).  The
+// statistics of a repeated run were taken over planes the repeat has written again: once more.
+int ojphgpu_transcoder_verdicts(ojphgpu_transcoder* t, ojphgpu_status_fetch fetch, void* user, bool resilient, uint32_t* failed)
+{
+  ojphgpu_decoder* d = t->dec;
+  const uint32_t repeats = d->fused_retries;
+  const int rc = ojphgpu_decoder_collect(d, fetch, user, failed);
+  if (rc) return rc;
+  if (*failed && !resilient) return OJPHGPU_E_BLOCK;
+  if (!t->enc->budgets.empty() && d->fused_retries != repeats) return ojphgpu_transcoder_stats(t);
+  return OJPHGPU_OK;
+}
+
+// "code, plain, into this output set": the encoder half's plain schedule over the arena
+int ojphgpu_transcoder_code(ojphgpu_transcoder* t, void* out, ojphgpu_cb_result* d_results, uint32_t* d_counters)
+{
+  ojphgpu_encoder* e = t->enc;
+  int rc;
+  BlockCoderRun coder{ e, (uint8_t*)out, d_results, d_counters, (uint32_t)e->block_ids.size(), &e->timer };
+  e->timer.start(t->stream);
+  if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) return rc;
+  e->timer.finish(t->stream);
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_transcoder_submit(ojphgpu_transcoder* t, const uint8_t* h_codestream, size_t len, int resilient)
 {
   if (!t || !h_codestream || len == 0) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     ojphgpu_decoder* d = t->dec; ojphgpu_encoder* e = t->enc;
-    const Plan& S = *t->S; const Plan& O = *t->O;
+    const Plan& O = *t->O;
     hipStream_t s = t->stream;
     const bool budget = !e->budgets.empty();
     if (!budget && !plan_all_reversible(O) && !(O.p.qstep > 0.0f)) return OJPHGPU_E_INVALID;   // no step and no budget
@@ -1802,21 +1893,14 @@ extern "C" int ojphgpu_transcoder_submit(ojphgpu_transcoder* t, const uint8_t* h
     if (rc) return rc;
     struct Hold { ojphgpu_plan* q; ~Hold() { ojphgpu_plan_destroy(q); } } hold{ q };
     const Plan& Q = q->plan;
-    if ((rc = ojphgpu_same_frame_geometry(S, Q, true)) != 0) return rc;
-    for (uint32_t c = 0; c < Q.p.num_comps; ++c) if (Q.style(c).causal) return OJPHGPU_E_INVALID;
-    for (size_t i = 0; i < Q.bands.size(); ++i)               // (K_max is this frame's own: transcode_plans_fit saw the first frame's)
-      if (Q.style(Q.bands[i].comp).rev && O.bands[i].K_max < Q.bands[i].K_max) return OJPHGPU_E_INVALID;
+    if ((rc = ojphgpu_transcoder_check_source(t, Q)) != 0) return rc;
     const size_t nb = d->block_ids.size();
     ojphgpu_cb_desc* bd = t->h_descs.data();
     // the launches of the last source have read what is replaced now (descriptors on the host and on the device, the bytes)
     HIPCHK(hipStreamSynchronize(s));
     if (e->side) HIPCHK(hipStreamSynchronize(e->side));
     DecFrameInfo fi;
-    ojphgpu_decoder_fill_descs(S, Q, d->block_ids, 0, 0, bd, fi);
-    uint64_t nquads = 0, naux = 0;
-    if (ojphgpu_ht_decode_layout(bd, (uint32_t)nb, &nquads, &naux) != OJPHGPU_OK) return OJPHGPU_E_INVALID;
-    if ((naux + 16) * 4 > d->aux.n || (nquads + 16) * 4 > d->quads.n) return OJPHGPU_E_INVALID;     // sized for the worst case at create
-    if (fi.first + fi.len > len) return OJPHGPU_E_CODESTREAM;
+    if ((rc = ojphgpu_transcoder_fill_descs(t, Q, len, bd, fi)) != 0) return rc;
     t->stage = 0;
     const size_t need = (size_t)fi.data_bytes() + 128;
     if (need > d->data.n) {
@@ -1827,10 +1911,7 @@ extern "C" int ojphgpu_transcoder_submit(ojphgpu_transcoder* t, const uint8_t* h
     if ((rc = ojphgpu_decoder_upload_pads(s, (uint8_t*)d->data.p, h_codestream, len, fi.pads)) != 0) return rc;
     if (nb) HIPCHK(hipMemcpyAsync(d->cb_descs.p, bd, nb * sizeof(ojphgpu_cb_desc), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));                        // the caller's codestream may go
-    d->any_refine = fi.any_refine; d->kinds = fi.kinds; d->max_len1 = fi.max_len1;
-    if ((rc = decoder_run_blocks(d)) != 0) return rc;
-    if (budget && (rc = transcoder_stats(t)) != 0) return rc;
-    d->timer.finish(s);
+    if ((rc = ojphgpu_transcoder_decode(t, fi.any_refine, fi.kinds, fi.max_len1)) != 0) return rc;
     e->ran = false; e->fetched = false;
     t->resilient = resilient != 0; t->failed = 0; t->code_ms = t->final_ms = 0;
     t->stage = 1;
@@ -1850,20 +1931,15 @@ extern "C" int ojphgpu_transcoder_finish(ojphgpu_transcoder* t, uint8_t* h_out, 
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     int rc;
     if (t->stage == 1) {
-      // the verdicts first (and the repeat of a one-launch run whose wait ran out): only then is a block coded
-      const uint32_t repeats = d->fused_retries;
-      if ((rc = ojphgpu_decoder_failed_blocks(d, &t->failed)) != 0) { t->stage = 0; return rc; }
-      if (failed_blocks) *failed_blocks = t->failed;
-      if (t->failed && !t->resilient) { t->stage = 0; return OJPHGPU_E_BLOCK; }
+      if (!d->ran) { t->stage = 0; return OJPHGPU_E_INVALID; }
+      const size_t tail = ((size_t)d->nblocks + 3u) & ~(size_t)3u;
+      PageableStatus f{ d, std::vector<uint8_t>(tail + 4) };
+      rc = ojphgpu_transcoder_verdicts(t, fetch_pageable_status, &f, t->resilient, &t->failed);
+      if (failed_blocks && (rc == OJPHGPU_OK || rc == OJPHGPU_E_BLOCK)) *failed_blocks = t->failed;
+      if (rc) { t->stage = 0; return rc; }
       const auto t0 = now();
-      if (budget) {
-        // (the statistics of a repeated run were taken over planes the repeat has written again)
-        if (d->fused_retries != repeats && (rc = transcoder_stats(t)) != 0) { t->stage = 0; return rc; }
-      } else {
-        BlockCoderRun coder{ e, (uint8_t*)e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, (uint32_t)e->block_ids.size(), &e->timer };
-        e->timer.start(s);
-        if ((rc = coder.clear()) != 0 || (rc = coder.rest_and_join()) != 0) { t->stage = 0; return rc; }
-        e->timer.finish(s);
+      if (!budget) {
+        if ((rc = ojphgpu_transcoder_code(t, e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p)) != 0) { t->stage = 0; return rc; }
         HIPCHK(hipStreamSynchronize(s));
         t->code_ms = ms(t0, now());
       }

@@ -656,6 +656,20 @@ struct ojphgpu_transcoder {
   uint32_t failed = 0;
   double code_ms = 0, final_ms = 0;
 };
+struct DecFrameInfo;
+// How the status bytes of a run (+ the RETRY word behind them) reach the host for whoever collects its verdicts: called once
+// the run is enqueued, returns with them readable at *h_status
+typedef int (*ojphgpu_status_fetch)(void* user, const uint8_t** h_status);
+// ojphgpu_decoder_failed_blocks with the fetch of the caller's choice (a frame pipeline's: a copy kernel into pinned memory)
+int ojphgpu_decoder_collect(ojphgpu_decoder* d, ojphgpu_status_fetch fetch, void* user, uint32_t* count);
+// What one source needs of a transcoder, piece by piece (ojphgpu_codec.cpp, above ojphgpu_transcoder_submit): shared by the
+// single transcoder's two calls and the transcode pipe
+int ojphgpu_transcoder_check_source(const ojphgpu_transcoder* t, const Plan& Q);
+int ojphgpu_transcoder_fill_descs(const ojphgpu_transcoder* t, const Plan& Q, size_t cs_len, ojphgpu_cb_desc* bd, DecFrameInfo& fi);
+int ojphgpu_transcoder_decode(ojphgpu_transcoder* t, bool any_refine, int kinds, uint32_t max_len1);
+int ojphgpu_transcoder_stats(ojphgpu_transcoder* t);
+int ojphgpu_transcoder_verdicts(ojphgpu_transcoder* t, ojphgpu_status_fetch fetch, void* user, bool resilient, uint32_t* failed);
+int ojphgpu_transcoder_code(ojphgpu_transcoder* t, void* out, ojphgpu_cb_result* d_results, uint32_t* d_counters);
 struct DecFrameInfo {
   std::vector<DecRun> runs;                                  // region decoders: the runs; first = 0, len = the bytes staged
   uint64_t first = 0, len = 0; bool any_refine = false; uint32_t max_len1 = 0; int kinds = 0;   // kinds: see ht_decode_step2_launch; bit 5: blocks on the 64-bit sample path

@@ -13,6 +13,9 @@
 //   a view    (ojphgpu_dec_pipe_create_view: reduced resolution, a window) the same, with the plan of every frame restricted
 //             as the first one's was and the H2D of the bytes done by a kernel that reads the runs of the view's blocks out
 //             of the pinned codestream (kernels_assemble.hip, gather_runs_kernel): only those bytes cross PCIe
+//   transcoder  host threads parse n+1's packet headers  |  H2D of n+1's bytes + descriptors  |  block decoder, verdicts and
+//             block coder (or the trials of a budget's search) of n  |  packet headers of n-1 on host threads -> placement
+//             kernel -> D2H of n-1's finished codestream (the end of this file)
 //
 // on separate HIP streams (copy-in, compute, copy-out) with events between them.  The coded bytes never
 // pass through a host memcpy: the encoder's codestream is assembled in HBM (kernels_assemble.hip) from the
@@ -325,44 +328,54 @@ struct ojphgpu_enc_pipe {
   std::thread search_worker;
 };
 
-static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
+// What a finisher does for a frame whose blocks are coded (its kernels have finished): the encoder pipe's frames and the
+// transcode pipe's alike.  P: the plan the blocks were quantised with; o: the output set they were coded into; the slot's
+// layout staging, codestream in HBM and pinned output, and the event behind its download.
+struct CodedFrame {
+  const Plan& P; const std::vector<uint32_t>& block_ids; const EncOut& o;
+  Pinned& h_lay; Grow& cs; Pinned& h_cs; hipEvent_t ev_done;
+};
+static int finish_coded_frame(const CodedFrame& f, hipStream_t s_d2h, int mode, size_t& cs_len, double& t_t2)
 {
-  const Plan& P = p->searching() ? s.rplan->plan : *p->P;    // (a budget, a target: the plan at the step the frame's search chose)
-  ojphgpu_encoder* e = p->enc;
-  auto fail = [&](int rc) { s.rc = rc; };
-  if (hipSetDevice(p->device) != hipSuccess) return fail(OJPHGPU_E_HIP);
-  if (hipEventSynchronize(s.ev_kern) != hipSuccess) return fail(OJPHGPU_E_HIP);
   const double t0 = now_ms();
-  const size_t nb = e->block_ids.size();
-  const RateTrialOut coded = s.o.trial(nb, nullptr);
+  const RateTrialOut coded = f.o.trial(f.block_ids.size(), nullptr);
   const ojphgpu_cb_result* res = coded.h_results;
-  if (coded.h_publish[1]) return fail(OJPHGPU_E_OVERFLOW);
-  int rc = no_throw([&]() -> int {
+  if (coded.h_publish[1]) return OJPHGPU_E_OVERFLOW;
+  return no_throw([&]() -> int {
     std::vector<ojphgpu_coded_block> cb;
-    ojphgpu_coded_blocks(P, e->block_ids, res, cb);
+    ojphgpu_coded_blocks(f.P, f.block_ids, res, cb);
     T2Layout L;
-    int r2 = t2_layout_codestream(P, cb.data(), L);
+    int r2 = t2_layout_codestream(f.P, cb.data(), L);
     if (r2) return r2;
-    s.t_t2 = now_ms() - t0;
+    t_t2 = now_ms() - t0;
     // the layout goes into the slot's pinned staging -- jobs, then the blob (64-byte aligned) -- where the
     // placement kernel reads it in place; the codestream is laid out in HBM and written to the slot's pinned
     // output by a copy kernel
     const size_t jbytes = L.jobs.size() * sizeof(T2Job), boff = (jbytes + 63) & ~(size_t)63;
     const size_t lbytes = boff + L.blob.size() + 16;
-    if (s.h_lay.reserve(lbytes + lbytes / 4)) return OJPHGPU_E_NOMEM;
-    if (s.cs.reserve((size_t)L.total + (size_t)L.total / 8 + 64) || s.h_cs.reserve((size_t)L.total + (size_t)L.total / 8 + 64)) return OJPHGPU_E_NOMEM;
-    memcpy(s.h_lay.p, L.jobs.data(), jbytes);
-    memcpy(s.h_lay.p + boff, L.blob.data(), L.blob.size());
-    r2 = assemble_launch(p->s_d2h, (const T2Job*)s.h_lay.d, (uint32_t)L.jobs.size(), s.h_lay.d + boff,
-                         (const uint8_t*)s.o.out.p, (uint8_t*)s.cs.b.p);
+    if (f.h_lay.reserve(lbytes + lbytes / 4)) return OJPHGPU_E_NOMEM;
+    if (f.cs.reserve((size_t)L.total + (size_t)L.total / 8 + 64) || f.h_cs.reserve((size_t)L.total + (size_t)L.total / 8 + 64)) return OJPHGPU_E_NOMEM;
+    memcpy(f.h_lay.p, L.jobs.data(), jbytes);
+    memcpy(f.h_lay.p + boff, L.blob.data(), L.blob.size());
+    r2 = assemble_launch(s_d2h, (const T2Job*)f.h_lay.d, (uint32_t)L.jobs.size(), f.h_lay.d + boff,
+                         (const uint8_t*)f.o.out.p, (uint8_t*)f.cs.b.p);
     if (r2) return r2;
-    r2 = download(p->mode, p->s_d2h, s.h_cs, s.cs.b.p, (size_t)L.total);
+    r2 = download(mode, s_d2h, f.h_cs, f.cs.b.p, (size_t)L.total);
     if (r2) return r2;
-    HIPCHK(hipEventRecord(s.ev_done, p->s_d2h));
-    HIPCHK(hipEventSynchronize(s.ev_done));
-    s.cs_len = (size_t)L.total;
+    HIPCHK(hipEventRecord(f.ev_done, s_d2h));
+    HIPCHK(hipEventSynchronize(f.ev_done));
+    cs_len = (size_t)L.total;
     return OJPHGPU_OK;
   });
+}
+
+static void enc_finish_frame(ojphgpu_enc_pipe* p, EncSlot& s)
+{
+  const Plan& P = p->searching() ? s.rplan->plan : *p->P;    // (a budget, a target: the plan at the step the frame's search chose)
+  auto fail = [&](int rc) { s.rc = rc; };
+  if (hipSetDevice(p->device) != hipSuccess) return fail(OJPHGPU_E_HIP);
+  if (hipEventSynchronize(s.ev_kern) != hipSuccess) return fail(OJPHGPU_E_HIP);
+  const int rc = finish_coded_frame(CodedFrame{ P, p->enc->block_ids, s.o, s.h_lay, s.cs, s.h_cs, s.ev_done }, p->s_d2h, p->mode, s.cs_len, s.t_t2);
   if (rc) {
     // uploads, kernels or the copy-out of this slot may already be enqueued: nothing of the slot may be rewritten or
     // re-reserved (hipHostFree / hipFree in reserve()) by the next _acquire while they are in flight
@@ -402,45 +415,60 @@ static void retire(ojphgpu_enc_pipe* p, EncSlot& s)
 // come back; the search, started from the last certified frame's answer, codes its trials into the slot's output set and
 // the spare in turn.  Afterwards the slot holds the set with j*, its plan copy stands at qstep(j*), and the finishers take
 // over as for any frame.
+// (the encoder pipe's frames, and the transcode pipe's: `e` is then the encoder half of its transcoder)
+struct RateFrame {
+  ojphgpu_encoder* e; Plan* Q;                       // Q: the slot's plan copy, left at qstep(j*)
+  uint64_t budget;
+  EncOut* slot; EncOut* spare;                       // the slot's output set and the pipe's spare
+  hipEvent_t ev_trial;
+};
 struct EncTrialCtx {
-  ojphgpu_enc_pipe* p; EncSlot* s;
+  const RateFrame* f;
   EncOut* best; EncOut* next;                        // best: holds the finest trial that fit so far (null: none); next: written next
-  int at;                                            // grid index s->rplan stands at
+  int at;                                            // grid index f->Q stands at
 };
 
 static int64_t enc_pipe_trial(void* user, uint32_t j)
 {
   EncTrialCtx& c = *(EncTrialCtx*)user;
-  ojphgpu_encoder* e = c.p->enc;
+  const RateFrame& f = *c.f;
   c.at = -1;
-  const int64_t size = ojphgpu_encoder_rate_trial(e, c.s->rplan->plan, c.next->trial(e->block_ids.size(), c.p->ev_trial), j);
+  const int64_t size = ojphgpu_encoder_rate_trial(f.e, *f.Q, c.next->trial(f.e->block_ids.size(), f.ev_trial), j);
   if (size < 0) return size;
   c.at = (int)j;
-  if ((uint64_t)size <= c.s->budget) {               // the finest that fits so far (the search never goes back below one): keep it
-    EncOut* other = c.best ? c.best : (c.next == &c.s->o ? &c.p->spare : &c.s->o);
+  if ((uint64_t)size <= f.budget) {                  // the finest that fits so far (the search never goes back below one): keep it
+    EncOut* other = c.best ? c.best : (c.next == f.slot ? f.spare : f.slot);
     c.best = c.next; c.next = other;
   }
   return size;
+}
+
+// The search of one frame, its histograms on the host: started from `hint` (moved to j* when the frame is certified), the
+// trials alternating between the two sets; *have: info holds something (OJPHGPU_OK, or OJPHGPU_E_BUDGET: passes, first_guess)
+static int rate_search_frame(const RateFrame& f, const uint32_t* h_hist, int& hint, ojphgpu_rate_info& info, bool& have)
+{
+  EncTrialCtx c{ &f, nullptr, f.slot, -1 };
+  const int rc = rate_search(f.e->rate->table, h_hist, f.budget, hint, enc_pipe_trial, &c, &info);
+  have = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
+  if (rc) return rc;
+  hint = (int)info.grid_index;
+  if (c.best != f.slot) std::swap(*f.slot, *f.spare);   // (pointers only) the slot keeps the set with j*, the other is the spare
+  if (c.at != (int)info.grid_index && !rate_apply_step(*f.Q, info.qstep)) return OJPHGPU_E_INVALID;
+  return OJPHGPU_OK;
 }
 
 static int enc_rate_frame(ojphgpu_enc_pipe* p, EncSlot& s)
 {
   ojphgpu_encoder* e = p->enc;
   EncoderRate& R = *e->rate;
-  ojphgpu_rate_info& info = s.found.rate;
   HIPCHK(hipSetDevice(p->device));
   int rc = enc_begin_frame(p, s);                    // transform + statistics (the encoder has a budget)
   if (rc) return rc;
   if ((rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
   HIPCHK(hipEventRecord(p->ev_trial, p->s_comp));
   HIPCHK(hipEventSynchronize(p->ev_trial));
-  EncTrialCtx c{ p, &s, nullptr, &s.o, -1 };
-  rc = rate_search(R.table, (const uint32_t*)p->h_hist.p, s.budget, p->hint, enc_pipe_trial, &c, &info);
-  s.found.have_rate = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
-  if (rc) return rc;
-  p->hint = (int)info.grid_index;
-  if (c.best != &s.o) std::swap(s.o, p->spare);      // (pointers only) the slot keeps the set with j*, the other is the spare
-  if (c.at != (int)info.grid_index && !rate_apply_step(s.rplan->plan, info.qstep)) return OJPHGPU_E_INVALID;
+  const RateFrame f{ e, &s.rplan->plan, s.budget, &s.o, &p->spare, p->ev_trial };
+  if ((rc = rate_search_frame(f, (const uint32_t*)p->h_hist.p, p->hint, s.found.rate, s.found.have_rate)) != 0) return rc;
   HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
   return OJPHGPU_OK;
 }
@@ -1134,5 +1162,409 @@ extern "C" int ojphgpu_dec_pipe_stats(ojphgpu_dec_pipe* p, double out[4])
   out[1] = p->n_done ? p->sum_parse / (double)p->n_done : 0.0;       // host parse + descriptor fill per frame, ms
   out[2] = p->n_done ? p->sum_latency / (double)p->n_done : 0.0;     // submit -> frame in pinned memory, ms
   out[3] = (double)p->workers.size();
+  return OJPHGPU_OK;
+}
+
+// =============================================================================================
+// transcode pipe
+// =============================================================================================
+// Host codestream in, host codestream out (section 5d's T, source after source).  A frame passes three stages, and the frames
+// of a sequence overlap each other across them:
+//   front     host threads: parse, the checks of a later source, the block descriptors into the slot's pinned memory, then
+//             the uploads of the block bytes and the descriptors on the copy-in stream
+//   device    ONE ordered thread, the owner of the compute stream (the encoder pipe's search worker, generalised): the block
+//             decoder over the slot's bytes, the verdicts (and the repeat a one-launch run may ask for), then the blocks coded
+//             into the slot's output set -- plainly, or by the budget's search with the spare set.  The transcoder has one
+//             arena: frame n + 1's block decoder writes the planes frame n's coding reads, so the frames are strictly serial
+//             here, in submit order; only the front and the finish of the neighbouring frames run beside them
+//   finish    host threads: Tier-2's layout from the block lengths, the assembly in HBM and the download on the copy-out
+//             stream (finish_coded_frame, the encoder pipe's)
+struct TcSlot {
+  SlotState state = FREE;
+  Pinned h_src, h_descs, h_status, h_lay, h_cs;
+  EncOut o;
+  Grow data, cs;
+  DeviceBuf cb_descs, status;
+  hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
+  size_t src_len = 0, cs_len = 0;
+  int rc = 0; uint32_t failed = 0;
+  bool front_done = false;                           // the front is through with the frame (s.rc says how): the device worker's turn
+  bool any_refine = false; int kinds = 0; uint32_t max_len1 = 0;   // of the frame's descriptors (DecFrameInfo)
+  double t_submit = 0, t_done = 0, t_parse = 0, t_t2 = 0;
+  uint64_t budget = 0;
+  ojphgpu_plan* rplan = nullptr;                     // a budget: the output plan at the step the frame's search chose
+  ojphgpu_rate_info rate{}; bool have_rate = false;
+};
+
+struct ojphgpu_tc_pipe {
+  ojphgpu_plan* first = nullptr;                     // parsed from the first source: the geometry of every source
+  const ojphgpu_plan* out = nullptr;                 // the caller's output plan
+  int device = 0, resilient = 0;
+  int mode_in = copy_mode("OJPHGPU_DEC_COPY_MODE", 0), mode_out = copy_mode("OJPHGPU_ENC_COPY_MODE", 0);
+  uint32_t depth = 0;
+  ojphgpu_transcoder* t = nullptr;                   // one object: one arena, one compute stream
+  hipStream_t s_h2d = nullptr, s_comp = nullptr, s_d2h = nullptr;
+  std::vector<TcSlot> slots;
+  size_t res_bytes = 0, st_bytes = 0;
+  uint64_t n_acq = 0, n_sub = 0, n_col = 0;
+  std::mutex mu; std::condition_variable cv_front, cv_dev, cv_fin, cv_done;
+  std::deque<uint32_t> front_work, fin_work;
+  bool stop_front = false, stop_dev = false, stop_fin = false;
+  std::vector<std::thread> fronts, finishers;
+  std::thread device_worker;
+  double sum_parse = 0, sum_t2 = 0, sum_latency = 0; uint64_t n_done = 0;
+  uint32_t fused_retries = 0;                        // (under mu) the decoder half's count after the frame the worker did last
+  hipEvent_t ev_host = nullptr;                      // the device worker's: behind what it waits for (verdicts, histograms, trials)
+  // byte budget (ojphgpu_tc_pipe_set_budget): the encoder pipe's rules
+  bool budget_on = false, dead = false;
+  uint64_t max_bytes = 0;
+  EncOut spare;
+  Pinned h_hist;
+  int hint = -1;                                     // j* of the last frame that was certified
+  ojphgpu_rate_info last{}; bool have_last = false;  // of the frame collected last
+};
+
+// the frame of a slot is over, whatever its outcome (s.rc): collectable, and counted
+static void retire(ojphgpu_tc_pipe* p, TcSlot& s)
+{
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    s.t_done = now_ms();
+    s.state = DONE;
+    p->sum_parse += s.t_parse; p->sum_t2 += s.t_t2; p->sum_latency += s.t_done - s.t_submit; p->n_done++;
+  }
+  p->cv_done.notify_all();
+}
+
+// ---- stage 1
+static void tc_front_frame(ojphgpu_tc_pipe* p, TcSlot& s)
+{
+  auto fail = [&](int rc) { s.rc = rc; };
+  if (hipSetDevice(p->device) != hipSuccess) return fail(OJPHGPU_E_HIP);
+  const double t0 = now_ms();
+  ojphgpu_plan* q = nullptr;
+  int rc = ojphgpu_t2_parse(s.h_src.p, s.src_len, p->resilient, &q);
+  if (rc) return fail(rc);
+  struct Hold { ojphgpu_plan* q; ~Hold() { ojphgpu_plan_destroy(q); } } hold{ q };
+  rc = no_throw([&]() -> int {
+    const Plan& Q = q->plan;
+    int r2 = ojphgpu_transcoder_check_source(p->t, Q);
+    if (r2) return r2;
+    const size_t nb = p->t->dec->block_ids.size();
+    DecFrameInfo fi;
+    if ((r2 = ojphgpu_transcoder_fill_descs(p->t, Q, s.src_len, (ojphgpu_cb_desc*)s.h_descs.p, fi)) != 0) return r2;
+    s.t_parse = now_ms() - t0;
+    if (s.data.reserve((size_t)fi.data_bytes() + (size_t)fi.len / 4 + 128)) return OJPHGPU_E_NOMEM;
+    if ((r2 = upload(p->mode_in, p->s_h2d, s.data.b.p, s.h_src, (size_t)fi.first, (size_t)fi.len)) != 0) return r2;
+    if ((r2 = ojphgpu_decoder_upload_pads(p->s_h2d, (uint8_t*)s.data.b.p, s.h_src.p, s.src_len, fi.pads)) != 0) return r2;   // (damaged codestreams only)
+    if ((r2 = upload(p->mode_in, p->s_h2d, s.cb_descs.p, s.h_descs, 0, nb * sizeof(ojphgpu_cb_desc))) != 0) return r2;
+    HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
+    s.any_refine = fi.any_refine; s.kinds = fi.kinds; s.max_len1 = fi.max_len1;
+    return OJPHGPU_OK;
+  });
+  if (rc) {                                          // (uploads of the slot may be enqueued: see enc_finish_frame)
+    hipStreamSynchronize(p->s_h2d);
+    fail(rc);
+  }
+}
+
+static void tc_front(ojphgpu_tc_pipe* p)
+{
+  for (uint32_t si; pop_work(p->mu, p->cv_front, p->front_work, p->stop_front, si);) {
+    tc_front_frame(p, p->slots[si]);
+    { std::lock_guard<std::mutex> lk(p->mu); p->slots[si].front_done = true; }
+    p->cv_dev.notify_all();
+  }
+}
+
+// ---- stage 2
+// the verdicts of the slot's run -- and, with a budget, the histograms taken behind it -- through the copy kernel into pinned memory
+struct TcFetch { ojphgpu_tc_pipe* p; TcSlot* s; };
+static int tc_fetch_status(void* user, const uint8_t** h_status)
+{
+  ojphgpu_tc_pipe* p = ((TcFetch*)user)->p; TcSlot& s = *((TcFetch*)user)->s;
+  int rc = copy_to_host_launch(p->s_comp, s.h_status.d, s.status.p, p->st_bytes);
+  if (rc) return rc;
+  if (p->budget_on) {
+    const EncoderRate& R = *p->t->enc->rate;
+    if ((rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
+  }
+  HIPCHK(hipEventRecord(p->ev_host, p->s_comp));
+  HIPCHK(hipEventSynchronize(p->ev_host));
+  *h_status = s.h_status.p;
+  return OJPHGPU_OK;
+}
+
+static int tc_device_frame(ojphgpu_tc_pipe* p, TcSlot& s)
+{
+  ojphgpu_transcoder* t = p->t;
+  ojphgpu_decoder* d = t->dec; ojphgpu_encoder* e = t->enc;
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
+  d->o_cb_descs = s.cb_descs.p; d->o_data = s.data.b.p; d->o_status = s.status.p;
+  int rc = ojphgpu_transcoder_decode(t, s.any_refine, s.kinds, s.max_len1);
+  if (rc) return rc;
+  const uint32_t repeats = d->fused_retries;
+  TcFetch fetch{ p, &s };
+  rc = ojphgpu_transcoder_verdicts(t, tc_fetch_status, &fetch, p->resilient != 0, &s.failed);   // no block is coded before the verdicts are in
+  { std::lock_guard<std::mutex> lk(p->mu); p->fused_retries = d->fused_retries; }
+  if (rc) return rc;
+  const size_t nb = e->block_ids.size();
+  if (!p->budget_on) {
+    const RateTrialOut coded = s.o.trial(nb, nullptr);
+    if ((rc = ojphgpu_transcoder_code(t, coded.out, coded.d_results, coded.d_counters)) != 0) return rc;
+    if ((rc = publish_words_launch(p->s_comp, coded.d_publish, coded.d_counters, 2)) != 0) return rc;
+  } else {
+    if (d->fused_retries != repeats) {               // the statistics were taken again over the repeated planes: fetch them again
+      const EncoderRate& R = *e->rate;
+      if ((rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
+      HIPCHK(hipEventRecord(p->ev_host, p->s_comp));
+      HIPCHK(hipEventSynchronize(p->ev_host));
+    }
+    const RateFrame f{ e, &s.rplan->plan, s.budget, &s.o, &p->spare, p->ev_host };
+    if ((rc = rate_search_frame(f, (const uint32_t*)p->h_hist.p, p->hint, s.rate, s.have_rate)) != 0) return rc;
+  }
+  HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
+  return OJPHGPU_OK;
+}
+
+// frames in submit order, whichever front thread finished first: the hint of a frame is its predecessor's answer
+static void tc_device_worker(ojphgpu_tc_pipe* p)
+{
+  for (uint64_t k = 0;; ++k) {
+    const uint32_t si = (uint32_t)(k % p->depth);
+    TcSlot& s = p->slots[si];
+    {
+      std::unique_lock<std::mutex> lk(p->mu);
+      auto ready = [&] { return k < p->n_sub && s.front_done; };
+      p->cv_dev.wait(lk, [&] { return p->stop_dev || ready(); });
+      if (!ready()) return;
+      s.front_done = false;
+    }
+    int rc = s.rc;                                   // (a frame the front refused: nothing of it reached the compute stream)
+    if (!rc && (rc = no_throw([&] { return tc_device_frame(p, s); })) != 0) {
+      // the frame ends here (OJPHGPU_E_BLOCK / _E_BUDGET among the reasons); see enc_finish_frame.  The arena keeps whatever
+      // its block decoder wrote: the next frame's writes every block's rectangle again, zeros where nothing is coded
+      hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp);
+      ojphgpu_decoder* d = p->t->dec;
+      d->o_cb_descs = nullptr; d->o_data = nullptr; d->o_status = nullptr;
+    }
+    if (rc) {
+      s.rc = rc;
+      retire(p, s);
+      continue;
+    }
+    { std::lock_guard<std::mutex> lk(p->mu); p->fin_work.push_back(si); }
+    p->cv_fin.notify_one();
+  }
+}
+
+// ---- stage 3
+static void tc_finisher(ojphgpu_tc_pipe* p)
+{
+  for (uint32_t si; pop_work(p->mu, p->cv_fin, p->fin_work, p->stop_fin, si);) {
+    TcSlot& s = p->slots[si];
+    int rc = OJPHGPU_E_HIP;
+    if (hipSetDevice(p->device) == hipSuccess && hipEventSynchronize(s.ev_kern) == hipSuccess) {
+      const Plan& P = p->budget_on ? s.rplan->plan : p->out->plan;   // (a budget: the plan at the step the frame's search chose)
+      rc = finish_coded_frame(CodedFrame{ P, p->t->enc->block_ids, s.o, s.h_lay, s.cs, s.h_cs, s.ev_done }, p->s_d2h, p->mode_out, s.cs_len, s.t_t2);
+    }
+    if (rc) {                                        // see enc_finish_frame
+      hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp); hipStreamSynchronize(p->s_d2h);
+      s.rc = rc;
+    }
+    retire(p, s);
+  }
+}
+
+extern "C" void ojphgpu_tc_pipe_destroy(ojphgpu_tc_pipe* p)
+{
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  // stage by stage: each hands its frames to the next
+  { std::lock_guard<std::mutex> lk(p->mu); p->stop_front = true; }
+  p->cv_front.notify_all();
+  for (std::thread& th : p->fronts) th.join();
+  if (p->device_worker.joinable()) {
+    { std::lock_guard<std::mutex> lk(p->mu); p->stop_dev = true; }
+    p->cv_dev.notify_all();
+    p->device_worker.join();
+  }
+  { std::lock_guard<std::mutex> lk(p->mu); p->stop_fin = true; }
+  p->cv_fin.notify_all();
+  for (std::thread& th : p->finishers) th.join();
+  for (hipStream_t s : { p->s_h2d, p->s_comp, p->s_d2h }) if (s) (void)hipStreamSynchronize(s);
+  if (p->t) ojphgpu_transcoder_destroy(p->t);
+  for (TcSlot& s : p->slots) {
+    for (Pinned* b : { &s.h_src, &s.h_descs, &s.h_status, &s.h_lay, &s.h_cs }) b->release();
+    s.o.release();
+    for (DeviceBuf* b : { &s.data.b, &s.cs.b, &s.cb_descs, &s.status }) b->release();
+    for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
+    delete s.rplan;
+  }
+  p->spare.release(); p->h_hist.release();
+  if (p->ev_host) (void)hipEventDestroy(p->ev_host);
+  for (hipStream_t s : { p->s_h2d, p->s_comp, p->s_d2h }) if (s) (void)hipStreamDestroy(s);
+  if (p->first) ojphgpu_plan_destroy(p->first);
+  delete p;
+}
+
+extern "C" int ojphgpu_tc_pipe_create(const uint8_t* h_codestream, size_t len, int resilient, const ojphgpu_plan* out_plan, int device,
+                                       uint32_t depth, uint32_t host_threads, ojphgpu_tc_pipe** out)
+{
+  if (!h_codestream || !len || !out_plan || !out || depth < 2 || depth > 16) return OJPHGPU_E_INVALID;
+  *out = nullptr;
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(device));
+    ojphgpu_tc_pipe* p = new (std::nothrow) ojphgpu_tc_pipe();
+    if (!p) return OJPHGPU_E_NOMEM;
+    struct Owner { ojphgpu_tc_pipe* p; ~Owner() { if (p) ojphgpu_tc_pipe_destroy(p); } } owner{ p };
+    int rc = ojphgpu_t2_parse(h_codestream, len, resilient, &p->first);
+    if (rc) return rc;
+    p->out = out_plan; p->device = device; p->depth = depth; p->resilient = resilient;
+    for (hipStream_t* s : { &p->s_h2d, &p->s_comp }) HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    HIPCHK(create_copy_out_stream(&p->s_d2h));
+    if ((rc = ojphgpu_transcoder_create(p->first, out_plan, device, p->s_comp, &p->t)) != 0) return rc;   // (the refusals)
+    ojphgpu_decoder* d = p->t->dec; ojphgpu_encoder* e = p->t->enc;
+    (void)ojphgpu_decoder_set_timing(d, 0); (void)ojphgpu_encoder_set_timing(e, 0);
+    const size_t nbs = d->block_ids.size(), nbo = e->block_ids.size();
+    p->res_bytes = nbo * sizeof(ojphgpu_cb_result) + 16;
+    p->st_bytes = ((nbs + 3) & ~(size_t)3) + 4;        // the status bytes + the RETRY word behind them
+    HIPCHK(hipEventCreateWithFlags(&p->ev_host, hipEventDisableTiming | hipEventReleaseToSystem));
+    const size_t cs_guess = std::min<size_t>((size_t)e->out_cap, len + len / 4 + (1u << 20));
+    p->slots.resize(depth);
+    for (TcSlot& s : p->slots) {
+      if (s.h_src.reserve(len + len / 4 + (1u << 16)) || s.h_descs.reserve(nbs * sizeof(ojphgpu_cb_desc) + 64) || s.h_status.reserve(nbs + 64) ||
+          s.o.h_res.reserve(p->res_bytes + 64) || s.h_cs.reserve(cs_guess) || s.h_lay.reserve(nbo * sizeof(T2Job) + nbo * 8 + (1u << 16))) return OJPHGPU_E_NOMEM;
+      if (s.data.reserve(len + len / 4 + 64) || s.cb_descs.alloc(nbs * sizeof(ojphgpu_cb_desc) + 64) || s.status.alloc(nbs + 64) ||
+          s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes) || s.cs.reserve(cs_guess)) return OJPHGPU_E_NOMEM;
+      HIPCHK(hipMemset(s.status.p, 0, nbs + 64));
+      for (hipEvent_t* ev : { &s.ev_in, &s.ev_kern, &s.ev_done }) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming | hipEventReleaseToSystem));
+    }
+    const uint32_t nthreads = host_threads ? std::min<uint32_t>(host_threads, 16) : 2;
+    for (uint32_t i = 0; i < nthreads; ++i) p->fronts.emplace_back(tc_front, p);
+    p->device_worker = std::thread(tc_device_worker, p);
+    for (uint32_t i = 0; i < nthreads; ++i) p->finishers.emplace_back(tc_finisher, p);
+    owner.p = nullptr;
+    *out = p;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_tc_pipe_acquire(ojphgpu_tc_pipe* p, size_t len, uint8_t** h_codestream)
+{
+  if (!p || !h_codestream || len == 0 || p->dead) return OJPHGPU_E_INVALID;
+  const Plan& O = p->out->plan;
+  if (!p->budget_on && !plan_all_reversible(O) && !(O.p.qstep > 0.0f)) return OJPHGPU_E_INVALID;   // no step and no budget
+  TcSlot& s = p->slots[p->n_acq % p->depth];
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (s.state != FREE && s.state != ACQUIRED) return OJPHGPU_E_AGAIN;     // every slot is in flight: collect a codestream first
+    s.state = ACQUIRED;
+  }
+  if (hipSetDevice(p->device) != hipSuccess) return OJPHGPU_E_HIP;
+  if (s.h_src.reserve(len + len / 4 + 64)) { std::lock_guard<std::mutex> lk(p->mu); s.state = FREE; return OJPHGPU_E_NOMEM; }
+  s.src_len = len;
+  *h_codestream = s.h_src.p;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_tc_pipe_submit(ojphgpu_tc_pipe* p)
+{
+  if (!p || p->dead) return OJPHGPU_E_INVALID;
+  const uint32_t si = (uint32_t)(p->n_acq % p->depth);
+  TcSlot& s = p->slots[si];
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (s.state != ACQUIRED) return OJPHGPU_E_INVALID;
+    s.rc = 0; s.failed = 0; s.cs_len = 0; s.t_parse = s.t_t2 = 0; s.t_submit = now_ms();
+    s.budget = p->max_bytes; s.have_rate = false; s.rate = ojphgpu_rate_info{};
+    s.front_done = false;
+    s.state = SUBMITTED;
+    p->front_work.push_back(si);
+    p->n_acq++; p->n_sub++;
+  }
+  p->cv_front.notify_one();
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_tc_pipe_collect(ojphgpu_tc_pipe* p, const uint8_t** h_out, size_t* len, uint32_t* failed_blocks)
+{
+  if (!p || !h_out || !len) return OJPHGPU_E_INVALID;
+  std::unique_lock<std::mutex> lk(p->mu);
+  if (p->n_col >= p->n_sub) return OJPHGPU_E_INVALID;            // nothing in flight
+  if (p->n_col > 0) {                                              // the codestream handed out last time is released now
+    TcSlot& prev = p->slots[(p->n_col - 1) % p->depth];
+    if (prev.state == HELD) prev.state = FREE;
+  }
+  TcSlot& s = p->slots[p->n_col % p->depth];
+  p->cv_done.wait(lk, [&] { return s.state == DONE; });
+  p->n_col++;
+  p->last = s.rate; p->have_last = s.have_rate;
+  if (failed_blocks) *failed_blocks = s.failed;
+  if (s.rc) { s.state = FREE; return s.rc; }
+  s.state = HELD;
+  *h_out = s.h_cs.p; *len = s.cs_len;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_tc_pipe_set_budget(ojphgpu_tc_pipe* p, uint64_t max_bytes)
+{
+  if (!p || p->dead) return OJPHGPU_E_INVALID;
+  if (p->n_acq != 0 || p->slots[0].state != FREE) {  // sources have been handed in: the mode stays, the budget may move
+    if (!p->budget_on || max_bytes == 0) return OJPHGPU_E_INVALID;
+    p->max_bytes = max_bytes;
+    return OJPHGPU_OK;
+  }
+  if (max_bytes == 0) return p->budget_on ? OJPHGPU_E_INVALID : OJPHGPU_OK;   // (once on, the buffers are there)
+  if (p->budget_on) { p->max_bytes = max_bytes; return OJPHGPU_OK; }
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(p->device));
+    ojphgpu_encoder* e = p->t->enc;
+    const int rc = ojphgpu_transcoder_set_budget(p->t, max_bytes);   // the refusals, the statistics, scratch and output bound of the finest step
+    if (rc) return rc;
+    // from here the encoder half runs in that mode and the buffers change hands (enc_search_on): every slot's output set at
+    // the bound of the finest step and its copy of the plan, the spare set -- the encoder half's own -- and the histograms
+    p->dead = true;
+    for (TcSlot& s : p->slots) {
+      s.o.out.release(); s.o.counters.release();
+      if (s.o.out.alloc((size_t)e->out_cap + 64) || s.o.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
+      if (!s.rplan) s.rplan = new ojphgpu_plan{ p->out->plan };
+    }
+    if (p->spare.h_res.reserve(p->res_bytes + 64)) return OJPHGPU_E_NOMEM;
+    p->spare.out = e->out; p->spare.counters = e->counters;
+    e->out = DeviceBuf(); e->counters = DeviceBuf();
+    if (p->h_hist.reserve(e->rate->h_hist.size() * 4 + 64)) return OJPHGPU_E_NOMEM;
+    p->hint = -1;
+    p->budget_on = true; p->max_bytes = max_bytes; p->dead = false;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_tc_pipe_rate_info(ojphgpu_tc_pipe* p, ojphgpu_rate_info* info)
+{
+  if (!p || !info) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->have_last) return OJPHGPU_E_INVALID;
+  *info = p->last;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_tc_pipe_fused_retries(ojphgpu_tc_pipe* p, uint32_t* count)
+{
+  if (!p || !count) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  *count = p->fused_retries;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_tc_pipe_stats(ojphgpu_tc_pipe* p, double out[4])
+{
+  if (!p || !out) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  out[0] = (double)p->n_done;
+  out[1] = p->n_done ? p->sum_parse / (double)p->n_done : 0.0;       // host parse + descriptor fill per frame, ms
+  out[2] = p->n_done ? p->sum_t2 / (double)p->n_done : 0.0;          // host Tier-2 (layout) per frame, ms
+  out[3] = p->n_done ? p->sum_latency / (double)p->n_done : 0.0;     // submit -> codestream in pinned memory, ms
   return OJPHGPU_OK;
 }

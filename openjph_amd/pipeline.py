@@ -556,3 +556,111 @@ class DecoderPipe(_Handover):
             self.submit()
         while self.in_flight:
             yield self.collect()
+
+
+class TranscoderPipe:
+    """A sequence of codestreams recoded to another packaging, quantisation step or byte budget (ojphgpu_tc_pipe): what
+    codec.Transcoder gives source by source, with the parse, the upload, the download and Tier-2 of neighbouring frames
+    overlapped with the device."""
+
+    def __init__(self, first_codestream: bytes, device=0, depth=4, host_threads=0, resilient=False, max_bytes=None, **kw):
+        """first_codestream: parsed for the geometry (every later source must have the same).  kw: what changes, as
+        plan.transcode_params takes it (qstep, block, prog_order, precinct, precincts, tlm, tileparts).  max_bytes=N: every
+        source is recoded to a byte budget (set_budget); an irreversible output needs qstep or a budget -- without either,
+        acquire() raises OjphError (capi.E_INVALID)."""
+        from .codec import _torch
+        from .plan import parse_codestream, transcode_params, transcode_plan
+        _torch()
+        self.depth = int(depth)
+        self.resilient = bool(resilient)
+        self.src_plan = parse_codestream(first_codestream, resilient)
+        self.params = transcode_params(self.src_plan, **kw)
+        self.plan = transcode_plan(self.src_plan, self.params)
+        self._lib = capi.lib()
+        self._h = C.c_void_p()
+        buf = np.frombuffer(first_codestream, dtype=np.uint8)
+        check(self._lib.ojphgpu_tc_pipe_create(buf.ctypes.data, len(first_codestream), int(self.resilient), self.plan.handle, device, self.depth,
+                                               host_threads, C.byref(self._h)), "tc_pipe_create")
+        self.failed_blocks = 0
+        self.in_flight = 0
+        if max_bytes:
+            self.set_budget(max_bytes)
+
+    def set_budget(self, max_bytes):
+        """Every source is recoded at the finest step of the rate grid whose codestream is at most max_bytes long, the search
+        started from the previous frame's answer (ojphgpu_tc_pipe_set_budget).  Switched on before the first acquire();
+        afterwards the budget may change between frames -- the value at submit() is the frame's -- but not go to 0.
+        Irreversible outputs only.  A frame no step fits raises OjphError (capi.E_BUDGET) from its collect()."""
+        check(self._lib.ojphgpu_tc_pipe_set_budget(self._h, int(max_bytes)), "tc_pipe_set_budget")
+
+    def rate_info(self):
+        """of the frame collected last: dict(grid_index, qstep, bytes, bytes_finer, passes, first_guess), as
+        codec.Transcoder.rate_info; after E_BUDGET passes and first_guess"""
+        info = capi.RateInfo()
+        check(self._lib.ojphgpu_tc_pipe_rate_info(self._h, C.byref(info)), "tc_pipe_rate_info")
+        return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
+
+    def close(self):
+        if self._h:
+            self._lib.ojphgpu_tc_pipe_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def acquire(self, nbytes):
+        """-> writable uint8 view of pinned memory for the next source, or None when every slot is in flight"""
+        ptr = C.c_void_p()
+        rc = self._lib.ojphgpu_tc_pipe_acquire(self._h, nbytes, C.byref(ptr))
+        if rc == capi.E_AGAIN:
+            return None
+        check(rc, "tc_pipe_acquire")
+        return _view(ptr.value, nbytes)
+
+    def submit(self):
+        check(self._lib.ojphgpu_tc_pipe_submit(self._h), "tc_pipe_submit")
+        self.in_flight += 1
+
+    def collect(self, copy=True):
+        """the oldest frame's output codestream; copy=False returns a view of pinned memory valid until its slot is acquired
+        again.  failed_blocks = the source's blocks that did not decode (zero blocks of a resilient pipe).  A frame that
+        failed -- it does not parse, has another geometry (capi.E_INVALID), failed blocks in a pipe that is not resilient
+        (capi.E_BLOCK), a budget no step fits (capi.E_BUDGET) -- raises OjphError from here, and the sequence goes on."""
+        ptr, n, failed = C.c_void_p(), C.c_size_t(), C.c_uint32()
+        if self.in_flight <= 0:              # nothing to collect: the counter stays where it is
+            raise capi.OjphError(capi.E_INVALID, "tc_pipe_collect: nothing in flight")
+        rc = self._lib.ojphgpu_tc_pipe_collect(self._h, C.byref(ptr), C.byref(n), C.byref(failed))
+        self.in_flight -= 1                  # the oldest frame is taken whatever its outcome
+        self.failed_blocks = int(failed.value)
+        check(rc, "tc_pipe_collect")
+        v = _view(ptr.value, n.value)
+        return v.tobytes() if copy else v
+
+    def stats(self):
+        out = (C.c_double * 4)()
+        check(self._lib.ojphgpu_tc_pipe_stats(self._h, out), "tc_pipe_stats")
+        n = C.c_uint32()
+        check(self._lib.ojphgpu_tc_pipe_fused_retries(self._h, C.byref(n)), "tc_pipe_fused_retries")
+        return dict(frames=int(out[0]), host_parse_ms=out[1], host_tier2_ms=out[2], latency_ms=out[3], fused_retries=int(n.value))
+
+    def transcode_sequence(self, codestreams, budgets=None):
+        """codestreams: iterable of sources -> generator of output codestreams, in order, `depth` frames in flight.  budgets (a
+        pipe with a byte budget): one int for every frame, or an iterable parallel to codestreams; a frame that fails raises
+        from here as from collect() (the generator ends with it: drive acquire / submit / collect to go on past one)"""
+        if budgets is not None and not hasattr(budgets, "__iter__"):
+            self.set_budget(budgets)
+            budgets = None
+        budgets = iter(budgets) if budgets is not None else None
+        for n, cs in enumerate(codestreams):
+            if budgets is not None:                       # (before the first acquire() this is what switches the mode on)
+                b = next(budgets, None)
+                if b is None:
+                    raise ValueError("transcode_sequence: budgets ended after %d values, codestreams go on" % n)
+                self.set_budget(b)
+            buf = self.acquire(len(cs))
+            while buf is None:
+                yield self.collect()
+                buf = self.acquire(len(cs))
+            buf[:] = np.frombuffer(cs, dtype=np.uint8)
+            self.submit()
+        while self.in_flight:
+            yield self.collect()

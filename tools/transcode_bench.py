@@ -18,7 +18,20 @@ target the contenders take turns, `--runs` rounds after `--warmup`, host clock f
 
 The two paths do not write the same bytes (the second rounds and clamps to samples in between); the lengths are reported.
 Prints one JSON line per target: medians, spread = (max - min) / median.
-  python tools/transcode_bench.py [--runs 10] [--warmup 2] [--rows 4320]"""
+  python tools/transcode_bench.py [--runs 10] [--warmup 2] [--rows 4320]
+
+--pipe: a SEQUENCE of sources instead, host memory to host memory: `--frames` identical C3 codestreams per round at the same
+three targets.  Per target three contenders take turns, `--rounds` rounds after one that warms every contender up:
+  pipe              pipeline.TranscoderPipe, depth 4: every slot's pinned source filled once, then acquire / submit / collect
+                    (copy=False) in steady state, as tools/e2e_pipeline.py drives the other two pipes
+  transcoder        codec.Transcoder.transcode called codestream by codestream on the bytes object (pageable memory in, a
+                    bytes object out): the same build's single call
+  dec_enc_pipes     a DecoderPipe (16-bit containers, slots filled once) feeding an EncoderPipe with the target's step or
+                    budget: the sample-domain route a caller has today; the frame goes from the decoder's pinned output into
+                    the encoder's pinned input by one host copy, which is part of the route
+Prints one JSON line per target: per contender the frames/s of every round, their median and spread (max - min) / median, and
+whether the pipe's median exceeds the single transcoder's by more than the larger of the two round-to-round spreads.
+  python tools/transcode_bench.py --pipe [--rounds 3] [--frames 24] [--rows 4320]"""
 import argparse
 import json
 import os
@@ -33,12 +46,127 @@ SRC_QSTEP = 0.001
 BPS = (0.2, 0.05)
 
 
+def run_tc_pipe(cs, n, kw, depth=4):
+    """every slot filled once, then n sources in steady state -> (seconds, the output, mean passes or None, stats)"""
+    from openjph_amd.pipeline import TranscoderPipe
+    pipe = TranscoderPipe(cs, depth=depth, **kw)
+    src = np.frombuffer(cs, dtype=np.uint8)
+    for _ in range(depth):
+        pipe.acquire(len(cs))[:] = src
+        pipe.submit()
+    first = None
+    while pipe.in_flight:
+        c = pipe.collect()
+        first = c if first is None else first
+    t0 = time.perf_counter()
+    sub = col = nbytes = passes = 0
+    while col < n:
+        while sub < n and pipe.acquire(len(cs)) is not None:
+            pipe.submit(); sub += 1
+        nbytes += len(pipe.collect(copy=False)); col += 1
+        if "max_bytes" in kw:
+            passes += pipe.rate_info()["passes"]
+    dt = time.perf_counter() - t0
+    st = pipe.stats()
+    pipe.close()
+    assert nbytes == n * len(first)
+    return dt, first, (passes / n if "max_bytes" in kw else None), st
+
+
+def run_dec_enc_pipes(cs, n, params, max_bytes, depth=4):
+    """a DecoderPipe feeding an EncoderPipe, n frames in steady state -> (seconds, the output)"""
+    from openjph_amd.pipeline import DecoderPipe, EncoderPipe
+    from openjph_amd.plan import Plan
+    dec = DecoderPipe(cs, depth=depth, container=16)
+    enc = EncoderPipe(plan=Plan(params), depth=depth, container=16, max_bytes=max_bytes or None)
+    src = np.frombuffer(cs, dtype=np.uint8)
+    out = [None]
+
+    def run(count, refill):
+        dsub = dcol = ecol = 0
+        while dcol < count:
+            while dsub < count:
+                buf = dec.acquire(len(cs))
+                if buf is None:
+                    break
+                if refill:
+                    buf[:] = src
+                dec.submit(); dsub += 1
+            frame = dec.collect(copy=False); dcol += 1
+            buf = enc.acquire()
+            while buf is None:
+                out[0] = enc.collect(copy=False); ecol += 1
+                buf = enc.acquire()
+            np.copyto(buf, frame.reshape(buf.shape))
+            enc.submit()
+        while enc.in_flight:
+            out[0] = enc.collect(copy=True); ecol += 1
+        assert ecol == count
+    run(depth, True)
+    t0 = time.perf_counter()
+    run(n, False)
+    dt = time.perf_counter() - t0
+    dec.close(); enc.close()
+    return dt, out[0]
+
+
+def pipe_bench(a):
+    from openjph_amd import codec
+    from openjph_amd.plan import make_params
+    from tests import synth
+    img = synth.survey_c3(rows=a.rows)
+    nc, h, w = img.shape
+    samples = img.size
+
+    def params(qstep):
+        return make_params(w, h, nc, bit_depth=12, reversible=False, qstep=qstep)
+    cs = codec.Encoder(params(SRC_QSTEP)).encode(img.astype(np.uint16))
+    del img
+    targets = [("budget %.2f B/sample" % b, dict(max_bytes=int(samples * b))) for b in BPS] + [("qstep %.3f" % (2 * SRC_QSTEP), dict(qstep=2 * SRC_QSTEP))]
+    for label, kw in targets:
+        single = codec.Transcoder(cs, **kw)
+        fps = {"pipe": [], "transcoder": [], "dec_enc_pipes": []}
+        passes = st = out_de = None
+        for r in range(a.rounds + 1):                           # round 0 warms every contender up and is not counted
+            dt_pipe, out_pipe, passes, st = run_tc_pipe(cs, a.frames, kw)
+            t0 = time.perf_counter()
+            for _ in range(a.frames):
+                out_single = single.transcode(cs)
+            dt_single = time.perf_counter() - t0
+            assert out_single == out_pipe
+            dt_de, out_de = run_dec_enc_pipes(cs, a.frames, params(kw.get("qstep", SRC_QSTEP)), kw.get("max_bytes", 0))
+            if r:
+                fps["pipe"].append(a.frames / dt_pipe); fps["transcoder"].append(a.frames / dt_single); fps["dec_enc_pipes"].append(a.frames / dt_de)
+        out = dict(frame="c3 %dx%dx%d 12-bit at qstep %g, %d bytes, host memory" % (w, h, nc, SRC_QSTEP, len(cs)), target=label, depth=4,
+                   frames_per_round=a.frames, bytes_pipe=len(out_pipe), bytes_dec_enc_pipes=len(out_de), mean_passes=passes,
+                   pipe_host_parse_ms=round(st["host_parse_ms"], 3), pipe_host_tier2_ms=round(st["host_tier2_ms"], 3),
+                   pipe_latency_ms=round(st["latency_ms"], 3))
+        if "max_bytes" in kw:
+            out.update(budget=kw["max_bytes"], grid_index=single.rate_info()["grid_index"], single_passes=single.rate_info()["passes"])
+        for k, v in fps.items():
+            med = float(np.median(v))
+            out[k] = dict(fps=[round(x, 1) for x in v], median_fps=round(med, 1), ms_per_frame=round(1e3 / med, 3),
+                          spread=round((max(v) - min(v)) / med, 3))
+        gap = float(np.median(fps["pipe"])) - float(np.median(fps["transcoder"]))
+        need = max(max(fps[k]) - min(fps[k]) for k in ("pipe", "transcoder"))
+        out["pipe_minus_transcoder_fps"] = round(gap, 1)
+        out["larger_spread_fps"] = round(need, 1)
+        out["margin_met"] = bool(gap > need)
+        print(json.dumps(out), flush=True)
+        del single
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=4320, help="top rows of the frame (rehearsals at a small size)")
+    ap.add_argument("--pipe", action="store_true", help="a sequence: the transcode pipe against the single transcoder and a DecoderPipe feeding an EncoderPipe")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=24)
     a = ap.parse_args()
+    if a.pipe:
+        return pipe_bench(a)
     import torch
     from openjph_amd import codec
     from openjph_amd.plan import make_params, parse_codestream
