@@ -315,10 +315,19 @@ public:
   // components of at most 16 bits, and not together with a byte budget: anything else is reported by write_headers, a
   // target beyond the finest step by flush().
   void set_max_sse(ui64 max_sse);
+  // ... under a byte cap (section 5c, "under a byte cap"): the step of the target where its codestream is at most cap_bytes
+  // long, else the finest step that fits -- the cap wins, flush() never fails for the target, and a cap below the coarsest
+  // step's codestream is flush()'s byte-budget error.  cap_bytes == 0: set_max_sse(max_sse).
+  void set_max_sse(ui64 max_sse, ui64 cap_bytes);
   void clear_max_sse();
   // after such a flush(): the step it chose, the squared error there and one step coarser (0 at index 0), the largest
   // absolute difference, the codestream's length and the number of trials the search made; false when there was none
   bool get_quality_info(ui32& grid_index, float& qstep, ui64& sse, ui64& sse_coarser, ui32& pae, ui64& bytes, ui32& passes);
+  // what the last flush() under a byte cap found: met = the target's own step fitted (quality_index == grid_index), else the
+  // finest step that fits was written and quality_index is the target's step (241: no step of the grid meets it); false
+  // without a cap or before the first flush()
+  bool get_capped_info(ui32& grid_index, float& qstep, bool& met, ui32& quality_index, ui64& sse, ui32& pae, ui64& bytes,
+                       ui32& quality_passes, ui32& rate_passes);
 
 private:
   codestream(const codestream&) = delete;

@@ -768,6 +768,15 @@ int  ojphgpu_rate_stepper_next(ojphgpu_rate_stepper* st, uint32_t* j);
 int  ojphgpu_rate_stepper_feed(ojphgpu_rate_stepper* st, int64_t size);
 int  ojphgpu_rate_stepper_info(const ojphgpu_rate_stepper* st, ojphgpu_rate_info* out);
 void ojphgpu_rate_stepper_destroy(ojphgpu_rate_stepper* st);
+/* The stepper under a ceiling (the capped mode of section 5c): ceil_index in 1 .. 240 is an index the caller has measured
+ * already, with size(ceil_index) = ceil_size > max_bytes.  The stepper starts with that as its upper end: it never hands
+ * out an index >= ceil_index, a hint >= ceil_index is moved to ceil_index - 1, ceil_size is reported as bytes_finer when
+ * j* == ceil_index - 1, and the model (if any) is scaled by ceil_size before its first proposal.  passes counts the
+ * stepper's own trials only; passes <= 16 and no index twice, as above.  ceil_index == OJPHGPU_RATE_GRID: no ceiling,
+ * exactly ojphgpu_rate_stepper_create (ceil_size is not read).  OJPHGPU_E_INVALID: ceil_index == 0 or beyond the grid's
+ * size, under a ceiling a ceil_size <= max_bytes or above INT64_MAX, and what _create refuses. */
+int  ojphgpu_rate_stepper_create_under(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
+                                       uint32_t ceil_index, uint64_t ceil_size, ojphgpu_rate_stepper** out);
 /* The searches of the `frames` frames of one encoder run, advanced together in ROUNDS over shared measurements, host only:
  * what ojphgpu_encoder_finish* drives for any frame count, for callers and tests that bring sizes of their own.  A stepper
  * per frame: hist = [frames][bands of the plan][OJPHGPU_STATS_BINS] (NULL: no model), max_bytes[frames], one hint for all.
@@ -891,6 +900,57 @@ int  ojphgpu_encoder_quality_comp(ojphgpu_encoder* enc, uint32_t comp, uint64_t*
 /* host clock of the last finish with a target, ms: out[0] the search (every trial), [1] the part of it spent waiting for
  * the device, [2] coding j*, its download and Tier-2 */
 int  ojphgpu_encoder_quality_timing(ojphgpu_encoder* enc, float out[3]);
+
+/* Under a byte cap: hold the quality target T = max_sse, but never exceed B = cap_bytes > 0.  A capped encode returns an
+ * index j*, an outcome and the codestream of j*, byte for byte the plain encode at qstep(j*); every figure below is measured
+ * for that frame.
+ *   OJPHGPU_CAPPED_MET:       SSE(j*) <= T and (j* == 0 or SSE(j* - 1) > T) -- the quality certificate -- and size(j*) <= B.
+ *   OJPHGPU_CAPPED_BY_BUDGET: size(j*) <= B and (j* == 240 or size(j* + 1) > B) -- the budget certificate of section 5b --
+ *                             and a witness that the target does not fit: an index q > j* that carries the quality
+ *                             certificate with size(q) > B (quality_index, quality_bytes), or a measured SSE(240) > T
+ *                             (quality_index == OJPHGPU_RATE_GRID: no step of the grid meets the target).  SSE(j*) and
+ *                             PAE(j*) are measured and reported whatever they are.
+ * The cap wins: OJPHGPU_E_QUALITY is never returned in this mode.  size(0) > B: OJPHGPU_E_BUDGET, nothing written (the
+ * passes are reported).  Neither SSE nor size is assumed monotone in j. */
+#define OJPHGPU_CAPPED_MET        0
+#define OJPHGPU_CAPPED_BY_BUDGET  1
+typedef struct ojphgpu_capped_info {
+  uint32_t grid_index; float qstep;                      /* j*, qstep(j*)                                                 */
+  uint32_t outcome;                                      /* OJPHGPU_CAPPED_*                                              */
+  uint32_t quality_index;                                /* q; OJPHGPU_RATE_GRID: none, SSE(240) > T was measured         */
+  uint64_t quality_bytes;                                /* size(q); 0 when q was never coded                             */
+  uint64_t bytes, bytes_finer;                           /* size(j*); BY_BUDGET: size(j* + 1), 0 when j* == 240; MET: 0   */
+  uint64_t sse, sse_coarser;                             /* SSE(j*); MET: SSE(j* - 1), 0 when j* == 0; BY_BUDGET: 0       */
+  uint32_t pae;                                          /* PAE(j*) (the encoder fills it)                                */
+  uint32_t quality_passes, rate_passes;                  /* calls of the sse_fn; of the size_fn (the encoder: codings)    */
+  uint32_t first_guess_q, first_guess_b;                 /* the first index each side tried (b: q when only q was coded)  */
+  uint32_t reserved;
+} ojphgpu_capped_info;
+typedef const uint32_t* (*ojphgpu_hist_fn)(void* user);  /* the frame's band statistics as ojphgpu_rate_search reads them, or NULL */
+/* The combined search, host only.  (1) ojphgpu_quality_search_hint(max_sse, hint_q): q, or "none" on a measured SSE(240) >
+ * T.  (2) With a q: size_fn(q); it fits: MET.  (3) Otherwise hist_fn is called ONCE (it may return NULL: plain halving)
+ * and the stepper of section 5b runs with hint_b -- under the ceiling q (ojphgpu_rate_stepper_create_under), or over the
+ * whole grid when there is no q; q == 0 that does not fit is OJPHGPU_E_BUDGET at once.  (4) OJPHGPU_E_BUDGET comes back as
+ * it is (info: the passes, the first guesses, quality_index / quality_bytes).  (5) SSE(j*) is the figure of the quality
+ * trial of j* where one was made, else one more sse_fn call, counted.  quality_passes <= 12 + 1, rate_passes <= 1 + 16, no
+ * index is asked twice by either callback; hist_fn is never called on MET.  hint_q / hint_b: -1 = none (the indices of
+ * ojphgpu_quality_search; the model's guess).  A negative value of a callback ends the search and comes back as it is.
+ * OJPHGPU_E_INVALID: cap_bytes == 0, a null callback, a hint outside -1 .. 240, a plan ojphgpu_rate_search refuses. */
+int  ojphgpu_capped_search(const ojphgpu_plan* plan, uint64_t max_sse, uint64_t cap_bytes, int32_t hint_q, int32_t hint_b,
+                           ojphgpu_sse_fn sse_fn, ojphgpu_size_fn size_fn, ojphgpu_hist_fn hist_fn, void* user,
+                           ojphgpu_capped_info* info);
+/* The encoder codes every following frame to max_sse under cap_bytes.  cap_bytes == 0: exactly ojphgpu_encoder_set_quality;
+ * ojphgpu_encoder_clear_quality switches the mode off.  Refused where set_quality is refused (batches, tile ranges,
+ * components deeper than 16 bits, a byte budget set, ojphgpu_encoder_finish_tiles*).  ojphgpu_encoder_run_device* enqueues
+ * conversion and DWT only, as with a target alone; ojphgpu_encoder_finish* runs ojphgpu_capped_search -- a quality trial as
+ * in section 5c, a size trial as in section 5b -- and launches the band statistics only when the cap binds (the
+ * unquantised planes are still in the arena).  When the last coding of the search was not j*, j* is coded once more and
+ * counted in rate_passes.  OJPHGPU_E_BUDGET leaves the encoder usable (capped_info: the passes).  While a cap is set,
+ * ojphgpu_encoder_quality_info and ojphgpu_encoder_rate_info return OJPHGPU_E_INVALID; ojphgpu_encoder_quality_comp answers
+ * for j*. */
+int  ojphgpu_encoder_set_quality_capped(ojphgpu_encoder* enc, uint64_t max_sse, uint64_t cap_bytes);
+/* what the last capped finish found (OJPHGPU_E_INVALID before one, or without a cap set) */
+int  ojphgpu_encoder_capped_info(ojphgpu_encoder* enc, ojphgpu_capped_info* info);
 
 /* ------------------------------------------------------------------------------------------ *
  * 5d. Transcoding: a codestream recoded to another packaging, step or byte budget without leaving the coefficient domain.
@@ -1029,7 +1089,7 @@ int  ojphgpu_enc_pipe_rate_info(ojphgpu_enc_pipe* pipe, ojphgpu_rate_info* info)
  * target, so the call itself is the switch, not its value -- and from then on the call may be repeated between frames; the
  * value in force at _submit is that frame's target; there is no way back.  OJPHGPU_E_INVALID: whatever
  * ojphgpu_encoder_set_quality refuses; switching on after the first _acquire; a pipe with a byte budget (and _set_budget on
- * a pipe with a target: the two do not combine yet).  The first call re-sizes every slot's output buffer for the finest
+ * a pipe with a target: a target under a byte cap is ojphgpu_enc_pipe_set_quality_capped below).  The first call re-sizes every slot's output buffer for the finest
  * step of the grid and allocates what ojphgpu_encoder_set_quality allocates; should it fail later than its refusals, the
  * pipe answers as ojphgpu_enc_pipe_set_budget describes.  The search of a frame starts from the j* of the last certified
  * frame (ojphgpu_quality_search_hint), runs on the pipe's compute stream in frame order and compares against the slot's own
@@ -1045,6 +1105,23 @@ int  ojphgpu_enc_pipe_set_quality(ojphgpu_enc_pipe* pipe, uint64_t max_sse);
 int  ojphgpu_enc_pipe_quality_info(ojphgpu_enc_pipe* pipe, ojphgpu_quality_info* info, uint32_t* first_guess);
 /* SSE and PAE of component `comp` of that frame at j* (OJPHGPU_E_INVALID when it was not certified) */
 int  ojphgpu_enc_pipe_quality_comp(ojphgpu_enc_pipe* pipe, uint32_t comp, uint64_t* sse, uint32_t* pae);
+/* Every frame of this pipe is coded to a quality target under a byte cap (section 5c, "under a byte cap"): each collected
+ * codestream is, byte for byte, what ojphgpu_encoder_set_quality_capped writes for that frame and pair.  Switched on by the
+ * first call with cap_bytes > 0 before the first _acquire, or never; from then on both values may move between frames (this
+ * call, or _set_quality for the target alone), the pair in force at _submit is the frame's, and the cap may not go back to
+ * 0.  cap_bytes == 0 on a pipe without a cap is exactly ojphgpu_enc_pipe_set_quality.  OJPHGPU_E_INVALID: what that call
+ * refuses; a quality pipe made without a cap (it has no spare output set and no pinned histograms: it cannot gain one);
+ * cap_bytes == 0 on a capped pipe.  _set_budget on such a pipe stays refused.  The ordered worker runs
+ * ojphgpu_capped_search per frame: the quality trials start from the q of the last certified frame, the size trials
+ * alternate between the slot's output set and the spare -- the set with the answer is never overwritten and nothing is
+ * coded twice -- and start from the j* of the last frame the cap bound; the band statistics are launched only when the
+ * cap binds.  Both hints stay where they are after a frame that fails.  A frame with size(0) > cap: its own _collect returns
+ * OJPHGPU_E_BUDGET and the sequence goes on.  On an unchanged frame: MET costs two quality trials and one coding,
+ * BY_BUDGET at most three and three. */
+int  ojphgpu_enc_pipe_set_quality_capped(ojphgpu_enc_pipe* pipe, uint64_t max_sse, uint64_t cap_bytes);
+/* what the capped search of the frame collected last found (after OJPHGPU_E_BUDGET: the passes); OJPHGPU_E_INVALID before the
+ * first _collect of such a pipe and after a frame that failed otherwise.  ojphgpu_enc_pipe_quality_comp answers for j*. */
+int  ojphgpu_enc_pipe_capped_info(ojphgpu_enc_pipe* pipe, ojphgpu_capped_info* info);
 
 /* the first codestream of the sequence fixes the frame geometry (it is only parsed, not decoded); every
  * submitted codestream must describe the same frame format and code-block grid (quantisation may differ) */

@@ -11,7 +11,7 @@
 #include "../../include/ojph_gpu_codestream.h"
 
 static void usage() {
-  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n | -min_psnr dB]\n"
+  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n | -min_psnr dB [-cap_bytes n]]\n"
          "  [-num_decomps n] [-block_size {w,h}] [-precincts {w,h}] [-prog_order LRCP|RLCP|RPCL|PCRL|CPRL]\n"
          "  [-colour_trans true|false] [-tile_size {w,h}] [-tlm_marker true|false] [-device n | -devices n,n,...]\n"
          "  [-image_offset {x,y}] [-tile_offset {x,y}] [-tileparts R|C|RC] [-profile IMF|BROADCAST] [-com \"text\"]\n"
@@ -107,10 +107,11 @@ int main(int argc, char** argv) {
       cs.set_byte_budget((size_t)mb);
     }
     unsigned long long max_sse = 0;
+    if (a.get("-cap_bytes") && !a.get("-min_psnr")) throw std::runtime_error("-cap_bytes caps a quality target: it needs -min_psnr (a byte budget alone is -max_bytes)");
     if (a.get("-min_psnr")) {                                   // GPU path only: the coarsest step of the rate grid found to reach the PSNR
       if (reversible) throw std::runtime_error("-min_psnr needs irreversible coding (-reversible false)");
       if (a.get("-qfactor") || a.get("-qstep")) throw std::runtime_error("-min_psnr chooses the quantisation step itself: it cannot be used together with -qstep or -qfactor");
-      if (a.get("-max_bytes")) throw std::runtime_error("-min_psnr and -max_bytes cannot be used together");
+      if (a.get("-max_bytes")) throw std::runtime_error("-min_psnr and -max_bytes cannot be used together: a quality target under a byte cap is -min_psnr with -cap_bytes");
       if (a.get("-devices")) throw std::runtime_error("-min_psnr codes on one device: it cannot be used together with -devices");
       unsigned long long n = 0;
       for (unsigned c = 0; c < img.num_comps; ++c) {
@@ -120,7 +121,12 @@ int main(int argc, char** argv) {
       if (img.bd(0) > 16) throw std::runtime_error("-min_psnr needs components of at most 16 bits");
       const unsigned long long peak = (1ull << img.bd(0)) - 1;
       max_sse = (unsigned long long)((double)(n * peak * peak) / pow(10.0, atof(a.get("-min_psnr")) / 10.0));   // (plan.psnr_to_sse)
-      cs.set_max_sse(max_sse);
+      if (a.get("-cap_bytes")) {                                // ... but never above this many bytes: the cap wins
+        const long long cb = atoll(a.get("-cap_bytes"));
+        if (cb <= 0) throw std::runtime_error("-cap_bytes must be a positive number of bytes");
+        cs.set_max_sse(max_sse, (unsigned long long)cb);
+      } else
+        cs.set_max_sse(max_sse);
     }
     if (a.get("-tlm_marker")) cs.request_tlm_marker(Args::to_bool(a.get("-tlm_marker")));
     if (a.get("-profile")) cs.set_profile(a.get("-profile"));
@@ -156,6 +162,11 @@ int main(int argc, char** argv) {
       if (a.get("-min_psnr") && cs.get_quality_info(gi, q, sse, coarser, pae, nbytes, passes))
         printf("Quality target %s dB: max_sse %llu, qstep = %.9g (grid index %u), sse %llu, one step coarser %llu, largest difference %u, %llu bytes, %u trials\n",
                a.get("-min_psnr"), max_sse, (double)q, gi, (unsigned long long)sse, (unsigned long long)coarser, pae, (unsigned long long)nbytes, passes);
+      bool met = false; ojph::ui32 qi = 0, qpasses = 0, rpasses = 0;
+      if (a.get("-cap_bytes") && cs.get_capped_info(gi, q, met, qi, sse, pae, nbytes, qpasses, rpasses))
+        printf("Quality target %s dB under %s bytes: max_sse %llu, outcome %s, qstep = %.9g (grid index %u, the target's %u), sse %llu, largest difference %u, %llu bytes, %u quality trials, %u codings\n",
+               a.get("-min_psnr"), a.get("-cap_bytes"), max_sse, met ? "MET" : "BY_BUDGET", (double)q, gi, qi, (unsigned long long)sse, pae,
+               (unsigned long long)nbytes, qpasses, rpasses);
     }
     cs.close();
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

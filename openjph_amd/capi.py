@@ -176,6 +176,17 @@ class QualityInfo(C.Structure):           # ojphgpu_quality_info
 SSE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64))      # ojphgpu_sse_fn
 
 
+class CappedInfo(C.Structure):            # ojphgpu_capped_info
+    _fields_ = [("grid_index", C.c_uint32), ("qstep", C.c_float), ("outcome", C.c_uint32), ("quality_index", C.c_uint32),
+                ("quality_bytes", C.c_uint64), ("bytes", C.c_uint64), ("bytes_finer", C.c_uint64), ("sse", C.c_uint64),
+                ("sse_coarser", C.c_uint64), ("pae", C.c_uint32), ("quality_passes", C.c_uint32), ("rate_passes", C.c_uint32),
+                ("first_guess_q", C.c_uint32), ("first_guess_b", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+HIST_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p)                                       # ojphgpu_hist_fn
+CAPPED_MET, CAPPED_BY_BUDGET = 0, 1
+
+
 class Run(C.Structure):                   # ojphgpu_run
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("n", C.c_uint64)]
 
@@ -385,6 +396,13 @@ SIGNATURES = {
     "ojphgpu_encoder_quality_info": (C.c_int, [C.c_void_p, C.POINTER(QualityInfo)]),
     "ojphgpu_encoder_quality_comp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ojphgpu_encoder_quality_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_rate_stepper_create_under": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "ojphgpu_capped_search": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, SSE_FN, SIZE_FN, HIST_FN, C.c_void_p,
+                                        C.POINTER(CappedInfo)]),
+    "ojphgpu_enc_pipe_set_quality_capped": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "ojphgpu_enc_pipe_capped_info": (C.c_int, [C.c_void_p, C.POINTER(CappedInfo)]),
+    "ojphgpu_encoder_set_quality_capped": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "ojphgpu_encoder_capped_info": (C.c_int, [C.c_void_p, C.POINTER(CappedInfo)]),
     "ojphgpu_plan_create_transcode": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_void_p)]),
     "ojphgpu_transcoder_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "ojphgpu_transcoder_set_budget": (C.c_int, [C.c_void_p, C.c_uint64]),

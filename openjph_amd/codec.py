@@ -43,13 +43,16 @@ class Encoder:
     """Whole-frame encoder for one frame shape / parameter set (ojphgpu_encoder)."""
 
     def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, max_bytes=0, max_sse=None, min_psnr=None,
-                 budgets=None, **kw):
+                 budgets=None, cap_bytes=0, **kw):
         """tiles=(first, count) restricts the encoder to a run of tiles (multi-GPU sharding);
         frames=B makes it code a batch of B independent frames per run ([B,C,H,W] input);
         max_bytes=N codes every frame to a byte budget (set_budget);
         budgets=[N0, N1, ...] codes frame f of every batch to N_f bytes (set_budgets);
-        max_sse=N / min_psnr=dB codes every frame to a quality target (set_quality)."""
+        max_sse=N / min_psnr=dB codes every frame to a quality target (set_quality);
+        cap_bytes=N with one of those two: to the target, but never above N bytes (set_quality(..., cap_bytes=N))."""
         torch = _torch()
+        if cap_bytes and max_sse is None and min_psnr is None:
+            raise ValueError("cap_bytes needs a quality target (max_sse or min_psnr); a byte budget alone is max_bytes")
         self.device = device
         self.plan = plan if plan is not None else Plan(params if params is not None else make_params(**kw))
         self.tiles = (0, self.plan.num_tiles) if tiles is None else (int(tiles[0]), int(tiles[1]))
@@ -70,13 +73,14 @@ class Encoder:
         self.max_bytes = 0
         self.budgets = None
         self.max_sse = None
+        self.cap_bytes = 0
         self._frame = None
         if max_bytes:
             self.set_budget(max_bytes)
         if budgets is not None:
             self.set_budgets(budgets)
         if max_sse is not None or min_psnr is not None:
-            self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
+            self.set_quality(max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes)
 
     def set_budget(self, max_bytes):
         """Every following frame is coded at the finest step of the rate grid (plan.rate_grid_qstep) whose codestream is at
@@ -104,26 +108,55 @@ class Encoder:
             self.max_bytes = seq[0] if any(seq) else 0
             self.budgets = seq if any(seq) else None
 
-    def set_quality(self, max_sse=None, min_psnr=None):
+    def set_quality(self, max_sse=None, min_psnr=None, cap_bytes=0):
         """Every following frame is coded at the coarsest step of the rate grid found to meet the target: the squared error
         between the frame and the decode of its codestream, summed over all components, is at most max_sse (an integer; 0 is
         a target) -- or min_psnr in dB, turned into one by plan.psnr_to_sse.  Both None switches the target off.  Where
         set_budget applies, and components of at most 16 bits; not together with a budget.  A target that not even the
         finest step meets raises OjphError with code E_QUALITY from finish() / encode().  The frame handed to run_device
-        is kept until finish() has returned: the search compares against it."""
+        is kept until finish() has returned: the search compares against it.
+
+        cap_bytes=N > 0: under a byte cap -- the step of the target where its codestream is at most N bytes long (outcome
+        MET), else the finest step that fits (outcome BY_BUDGET): the cap wins, E_QUALITY is never raised, and a cap below
+        the coarsest step's codestream raises E_BUDGET.  capped_info() tells which; quality_info() and rate_info() are
+        refused while a cap is set."""
         from .plan import psnr_to_sse
         if max_sse is not None and min_psnr is not None:
             raise ValueError("set_quality: max_sse or min_psnr, not both")
+        cap = int(cap_bytes)
+        if cap and max_sse is None and min_psnr is None:
+            raise ValueError("set_quality: cap_bytes needs a quality target (max_sse or min_psnr)")
+        if not 0 <= cap < 2 ** 64:
+            raise ValueError("set_quality: cap_bytes must fit 64 bits")
         with _torch().cuda.device(self.device):
             if max_sse is None and min_psnr is None:
                 check(self._lib.ojphgpu_encoder_clear_quality(self._h), "encoder_clear_quality")
-                self.max_sse = None
+                self.max_sse, self.cap_bytes = None, 0
                 return
             t = int(max_sse) if max_sse is not None else psnr_to_sse(self.plan, float(min_psnr))
             if not 0 <= t < 2 ** 64:
                 raise ValueError("set_quality: max_sse must fit 64 bits")
-            check(self._lib.ojphgpu_encoder_set_quality(self._h, t), "encoder_set_quality")
-        self.max_sse = t
+            if cap:
+                check(self._lib.ojphgpu_encoder_set_quality_capped(self._h, t, cap), "encoder_set_quality_capped")
+            else:
+                check(self._lib.ojphgpu_encoder_set_quality(self._h, t), "encoder_set_quality")
+        self.max_sse, self.cap_bytes = t, cap
+
+    def capped_info(self):
+        """what the last finish() under a byte cap found: dict(grid_index, qstep, outcome = capi.CAPPED_MET /
+        CAPPED_BY_BUDGET, quality_index = the target's own step (241: no step of the grid meets it), quality_bytes = its
+        codestream's length (0: never coded), bytes, bytes_finer, sse, sse_coarser, pae, quality_passes, rate_passes,
+        first_guess_q, first_guess_b, comps = [(sse, pae) per component]); after E_BUDGET the passes and comps == []"""
+        info = capi.CappedInfo()
+        check(self._lib.ojphgpu_encoder_capped_info(self._h, C.byref(info)), "encoder_capped_info")
+        out = {k: getattr(info, k) for k, _ in capi.CappedInfo._fields_ if k != "reserved"}
+        out["comps"] = []
+        for c in range(int(self.plan.params.num_comps)):
+            sse, pae = C.c_uint64(), C.c_uint32()
+            if self._lib.ojphgpu_encoder_quality_comp(self._h, c, C.byref(sse), C.byref(pae)) != capi.OK:
+                break
+            out["comps"].append((int(sse.value), int(pae.value)))
+        return out
 
     def quality_info(self):
         """what the last finish() with a quality target found: dict(grid_index, qstep, sse, sse_coarser = the error one step
@@ -590,11 +623,12 @@ def transcode(codestream: bytes, device=0, resilient=False, max_bytes=0, **kw) -
     return Transcoder(codestream, device=device, resilient=resilient, max_bytes=max_bytes, **kw).transcode(codestream)
 
 
-def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, **kw) -> bytes:
+def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0, **kw) -> bytes:
     """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes); max_bytes=N: coded to a byte
-    budget (Encoder.set_budget); max_sse=N / min_psnr=dB: coded to a quality target (Encoder.set_quality)."""
+    budget (Encoder.set_budget); max_sse=N / min_psnr=dB: coded to a quality target (Encoder.set_quality), with cap_bytes=N
+    under a byte cap."""
     nc, h, w = image.shape
-    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes, max_sse=max_sse, min_psnr=min_psnr).encode(image)
+    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes, max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes).encode(image)
 
 
 def gather_runs(src, runs, staged_len, out=None):

@@ -117,6 +117,7 @@ struct codestream_state {
   int device = 0;
   size_t byte_budget = 0;             // set_byte_budget: flush() codes the frame to at most this many bytes (0: off)
   bool quality_on = false; ui64 max_sse = 0;   // set_max_sse: flush() codes the frame to at most this squared error
+  ui64 cap_bytes = 0;                          // ... and to at most this many bytes (0: no cap)
   // more than one device: a tiled frame is coded by all of them, each a contiguous run of tiles (include/ojphgpu.h section 8)
   std::vector<int> devices;
   ojphgpu_multi_encoder* menc = nullptr; ojphgpu_multi_decoder* mdec = nullptr;
@@ -562,8 +563,18 @@ bool codestream::get_byte_budget_result(ui32& grid_index, float& qstep, ui64& by
   grid_index = info.grid_index; qstep = info.qstep; bytes = info.bytes; passes = info.passes;
   return true;
 }
-void codestream::set_max_sse(ui64 max_sse) { state->quality_on = true; state->max_sse = max_sse; }
-void codestream::clear_max_sse() { state->quality_on = false; }
+void codestream::set_max_sse(ui64 max_sse) { state->quality_on = true; state->max_sse = max_sse; state->cap_bytes = 0; }
+void codestream::set_max_sse(ui64 max_sse, ui64 cap_bytes) { state->quality_on = true; state->max_sse = max_sse; state->cap_bytes = cap_bytes; }
+void codestream::clear_max_sse() { state->quality_on = false; state->cap_bytes = 0; }
+bool codestream::get_capped_info(ui32& grid_index, float& qstep, bool& met, ui32& quality_index, ui64& sse, ui32& pae, ui64& bytes,
+                                 ui32& quality_passes, ui32& rate_passes)
+{
+  ojphgpu_capped_info info;
+  if (!state->enc || ojphgpu_encoder_capped_info(state->enc, &info) != OJPHGPU_OK) return false;
+  grid_index = info.grid_index; qstep = info.qstep; met = info.outcome == OJPHGPU_CAPPED_MET; quality_index = info.quality_index;
+  sse = info.sse; pae = info.pae; bytes = info.bytes; quality_passes = info.quality_passes; rate_passes = info.rate_passes;
+  return true;
+}
 bool codestream::get_quality_info(ui32& grid_index, float& qstep, ui64& sse, ui64& sse_coarser, ui32& pae, ui64& bytes, ui32& passes)
 {
   ojphgpu_quality_info info;
@@ -731,7 +742,7 @@ void codestream::write_headers(outfile_base* file, const comment_exchange* comme
     if (rc) ojph_error(0x00030F08, "cannot create the GPU encoder (status %d): no GPU?", rc);
     if (S.byte_budget && ojphgpu_encoder_set_budget(S.enc, S.byte_budget) != OJPHGPU_OK)
       ojph_error(0x00030F13, "a byte budget needs irreversible coding of every component with the Part-1 wavelet and no quality factor");
-    if (S.quality_on && ojphgpu_encoder_set_quality(S.enc, S.max_sse) != OJPHGPU_OK)
+    if (S.quality_on && ojphgpu_encoder_set_quality_capped(S.enc, S.max_sse, S.cap_bytes) != OJPHGPU_OK)
       ojph_error(0x00030F16, "a quality target needs irreversible coding of every component with the Part-1 wavelet, no quality factor, no byte budget and components of at most 16 bits");
     S.alloc_frame();
   }
@@ -791,7 +802,7 @@ void codestream::flush()
   }
   size_t len = 0;
   int rc = ojphgpu_encode(S.enc, S.frame, nullptr, 0, &len);            // runs the GPU path; reports the codestream size
-  if (rc == OJPHGPU_E_BUDGET) ojph_error(0x00030F15, "the byte budget of %zu bytes is below the codestream of the coarsest quantisation step (status %d)", S.byte_budget, rc);
+  if (rc == OJPHGPU_E_BUDGET) ojph_error(0x00030F15, "the byte budget of %zu bytes is below the codestream of the coarsest quantisation step (status %d)", S.quality_on ? (size_t)S.cap_bytes : S.byte_budget, rc);
   if (rc == OJPHGPU_E_QUALITY) ojph_error(0x00030F18, "the quality target of %llu is beyond the finest quantisation step (status %d)", (unsigned long long)S.max_sse, rc);
   if (rc != OJPHGPU_E_OVERFLOW && rc != OJPHGPU_OK) ojph_error(0x00030F0B, "GPU encode failed (status %d)", rc);
   std::unique_ptr<ui8[]> out(new ui8[len + 16]);

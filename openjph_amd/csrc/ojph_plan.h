@@ -241,6 +241,9 @@ int  rate_search(const RateTable& T, const uint32_t* hist, uint64_t max_bytes, i
 // encoder's; hist: [frames][hist_per] words
 int  rate_rounds_create(const RateTable& T, const uint32_t* hist, size_t hist_per, const uint64_t* max_bytes, uint32_t frames, int hint,
                         ojphgpu_rate_rounds** out);
+// ojphgpu_capped_search over a table the caller keeps (the encoder's, a pipe's)
+int  capped_search(const RateTable& T, uint64_t max_sse, uint64_t cap_bytes, int hint_q, int hint_b, ojphgpu_sse_fn sse_fn, ojphgpu_size_fn size_fn,
+                   ojphgpu_hist_fn hist_fn, void* user, ojphgpu_capped_info* info);
 // the blocks' delta / K_max / missing_msbs of another step into the block descriptors: block i of frame f (descriptor
 // f * nb + i) from d_quant[f * nclasses + d_class[i]]
 int  requant_frames_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, uint32_t frames, const uint32_t* d_class, const BandQuant* d_quant,

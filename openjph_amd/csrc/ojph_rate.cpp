@@ -138,11 +138,17 @@ struct ojphgpu_rate_stepper {
   int dir = 0, k = 0;                                        // of the hinted trials: the side they walk to, how far
   int pending = -1;                                          // the index handed out and not fed yet
   ojphgpu_rate_info info;
-  void start(const ojphgpu::RateTable& t, const uint32_t* hist, uint64_t budget, int h)
+  // c < N: size(c) = cs > budget was measured by the caller -- the search runs below c, and cs is the model's first scale
+  void start(const ojphgpu::RateTable& t, const uint32_t* hist, uint64_t budget, int h, int c = N, uint64_t cs = 0)
   {
     max_bytes = budget; hint = h;
     if (hist) model.reset(new ojphgpu::RateModel(t, hist));
-    phase = h >= 0 ? HINT : MAIN;
+    if (c < N) {
+      hi = c; size[(size_t)c] = (int64_t)cs;                  // (a ceiling is nothing but the first hi, measured by the caller)
+      if (hint >= c) hint = c - 1;
+      if (model) { const double p = model->bytes((uint32_t)c); if (p > 0) scale = (double)cs / p; }
+    }
+    phase = hint >= 0 ? HINT : MAIN;
     memset(&info, 0, sizeof(info));
   }
   int hand(int j, uint32_t* out)
@@ -321,13 +327,21 @@ extern "C" int ojphgpu_rate_search_hint(const ojphgpu_plan* plan, const uint32_t
 extern "C" int ojphgpu_rate_stepper_create(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
                                            ojphgpu_rate_stepper** out)
 {
+  return ojphgpu_rate_stepper_create_under(plan, hist, max_bytes, hint, OJPHGPU_RATE_GRID, 0, out);
+}
+
+extern "C" int ojphgpu_rate_stepper_create_under(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, int32_t hint,
+                                                 uint32_t ceil_index, uint64_t ceil_size, ojphgpu_rate_stepper** out)
+{
   if (!plan || !out || hint < -1 || hint >= (int32_t)OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  if (ceil_index == 0 || ceil_index > OJPHGPU_RATE_GRID) return OJPHGPU_E_INVALID;
+  if (ceil_index < OJPHGPU_RATE_GRID && (ceil_size <= max_bytes || ceil_size > (uint64_t)INT64_MAX)) return OJPHGPU_E_INVALID;   // (no ceiling: not read)
   *out = nullptr;
   return no_throw([&]() -> int {
     std::unique_ptr<ojphgpu_rate_stepper> st(new ojphgpu_rate_stepper());
     const int rc = rate_table_build(plan->plan, st->own);
     if (rc) return rc;
-    st->start(st->own, hist, max_bytes, hint);
+    st->start(st->own, hist, max_bytes, hint, (int)ceil_index, ceil_size);
     *out = st.release();
     return OJPHGPU_OK;
   });
@@ -483,6 +497,87 @@ extern "C" int ojphgpu_quality_search_hint(uint64_t max_sse, int32_t hint, ojphg
   out->grid_index = (uint32_t)hi; out->qstep = rate_grid_qstep((uint32_t)hi);
   out->sse = sse_hi; out->sse_coarser = hi ? sse_lo : 0;
   return OJPHGPU_OK;
+}
+
+// Encoding to a quality target under a byte cap (include/ojphgpu.h section 5c, "under a byte cap"): the quality search, one
+// size trial at its answer q and, only where that does not fit, the budget stepper below the ceiling q.  Every figure
+// reported was measured; neither callback is asked an index twice.
+namespace ojphgpu {
+int capped_search(const RateTable& T, uint64_t max_sse, uint64_t cap_bytes, int hint_q, int hint_b, ojphgpu_sse_fn sse_fn,
+                  ojphgpu_size_fn size_fn, ojphgpu_hist_fn hist_fn, void* user, ojphgpu_capped_info* info)
+{
+  const int N = OJPHGPU_RATE_GRID;
+  if (!sse_fn || !size_fn || !hist_fn || !info || cap_bytes == 0 || hint_q < -1 || hint_q >= N || hint_b < -1 || hint_b >= N) return OJPHGPU_E_INVALID;
+  memset(info, 0, sizeof(*info));
+  info->quality_index = (uint32_t)N;
+  struct Seen { ojphgpu_sse_fn fn; void* user; std::vector<int64_t> sse; } seen{ sse_fn, user, std::vector<int64_t>((size_t)N, -1) };
+  auto record = [](void* u, uint32_t j, uint64_t* sse) -> int64_t {
+    Seen& s = *(Seen*)u;
+    const int64_t rc = s.fn(s.user, j, sse);
+    if (rc >= 0 && j < (uint32_t)OJPHGPU_RATE_GRID) s.sse[j] = (int64_t)std::min<uint64_t>(*sse, (uint64_t)INT64_MAX);
+    return rc;
+  };
+  ojphgpu_quality_info qi;
+  int rc = ojphgpu_quality_search_hint(max_sse, hint_q, record, &seen, &qi, &info->first_guess_q);
+  info->quality_passes = qi.passes;
+  if (rc != OJPHGPU_OK && rc != OJPHGPU_E_QUALITY) return rc;
+  const bool have_q = rc == OJPHGPU_OK;
+  auto code = [](int64_t s) -> int { return s < INT32_MIN ? OJPHGPU_E_INVALID : (int)s; };
+  int ceil = N; uint64_t ceil_size = 0;
+  if (have_q) {
+    const uint32_t q = qi.grid_index;
+    info->quality_index = q;
+    info->first_guess_b = q;
+    const int64_t s = size_fn(user, q);
+    info->rate_passes = 1;
+    if (s < 0) return code(s);
+    info->quality_bytes = (uint64_t)s;
+    if ((uint64_t)s <= cap_bytes) {
+      info->outcome = OJPHGPU_CAPPED_MET;
+      info->grid_index = q; info->qstep = rate_grid_qstep(q);
+      info->bytes = (uint64_t)s;
+      info->sse = qi.sse; info->sse_coarser = qi.sse_coarser;
+      return OJPHGPU_OK;
+    }
+    if (q == 0) return OJPHGPU_E_BUDGET;                     // size(0) > B, measured
+    ceil = (int)q; ceil_size = (uint64_t)s;
+  }
+  info->outcome = OJPHGPU_CAPPED_BY_BUDGET;
+  const uint32_t* hist = hist_fn(user);                      // once; NULL: plain halving
+  ojphgpu_rate_stepper st;
+  st.start(T, hist, cap_bytes, hint_b, ceil, ceil_size);
+  for (;;) {
+    uint32_t j = 0;
+    rc = st.next(&j);
+    if (rc == 1) rc = st.feed(size_fn(user, j)); else break;
+    if (rc) break;
+  }
+  info->rate_passes += st.info.passes;
+  if (st.info.passes) info->first_guess_b = st.info.first_guess;
+  if (rc) return rc;                                         // OJPHGPU_E_BUDGET as it is
+  const uint32_t j = st.info.grid_index;
+  info->grid_index = j; info->qstep = st.info.qstep; info->bytes = st.info.bytes; info->bytes_finer = st.info.bytes_finer;
+  if (seen.sse[j] < 0) {                                     // not among the quality trials: measured now, and counted
+    uint64_t s = 0;
+    const int64_t e = record(&seen, j, &s);
+    info->quality_passes++;
+    if (e < 0) return code(e);
+    info->sse = s;
+  } else info->sse = (uint64_t)seen.sse[j];
+  return OJPHGPU_OK;
+}
+}  // namespace ojphgpu
+
+extern "C" int ojphgpu_capped_search(const ojphgpu_plan* plan, uint64_t max_sse, uint64_t cap_bytes, int32_t hint_q, int32_t hint_b,
+                                     ojphgpu_sse_fn sse_fn, ojphgpu_size_fn size_fn, ojphgpu_hist_fn hist_fn, void* user, ojphgpu_capped_info* info)
+{
+  if (!plan) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    RateTable T;
+    const int rc = rate_table_build(plan->plan, T);
+    if (rc) return rc;
+    return capped_search(T, max_sse, cap_bytes, hint_q, hint_b, sse_fn, size_fn, hist_fn, user, info);
+  });
 }
 
 extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hist, double* out)

@@ -437,6 +437,7 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
 
 static int encoder_rate_search(ojphgpu_encoder* e);
 static int encoder_quality_search(ojphgpu_encoder* e);
+static int encoder_capped_search(ojphgpu_encoder* e);
 
 extern "C" int ojphgpu_encoder_finish(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len)
 {
@@ -455,7 +456,7 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
   const bool budgets = !e->budgets.empty();
-  int rc = e->quality_on ? encoder_quality_search(e) : budgets ? encoder_rate_search(e) : OJPHGPU_OK;
+  int rc = e->quality_on ? (e->cap_bytes ? encoder_capped_search(e) : encoder_quality_search(e)) : budgets ? encoder_rate_search(e) : OJPHGPU_OK;
   if (rc) return rc;
   ojphgpu_rate_info info;
   if (budgets && (rc = ojphgpu_rate_rounds_frame(e->rate->rounds, frame, &info)) != 0) return rc;   // (OJPHGPU_E_BUDGET: this frame's alone)
@@ -798,7 +799,7 @@ extern "C" int ojphgpu_encoder_clear_quality(ojphgpu_encoder* e)
 {
   if (!e) return OJPHGPU_E_INVALID;
   if (e->quality_on && e->rate) { const int rc = encoder_restore_descs(e); if (rc) return rc; }
-  e->quality_on = false;
+  e->quality_on = false; e->cap_bytes = 0;
   return OJPHGPU_OK;
 }
 
@@ -808,7 +809,7 @@ extern "C" int ojphgpu_encoder_set_quality(ojphgpu_encoder* e, uint64_t max_sse)
   if (e->nframes > 1 || !encoder_may_search(e) || !e->budgets.empty()) return OJPHGPU_E_INVALID;
   const Plan& P = *e->P;
   for (const CompGeo& g : P.comps) if (g.bit_depth > 16) return OJPHGPU_E_INVALID;
-  if (e->quality) { e->max_sse = max_sse; e->quality_on = true; e->ran = false; return OJPHGPU_OK; }
+  if (e->quality) { e->max_sse = max_sse; e->cap_bytes = 0; e->quality_on = true; e->ran = false; return OJPHGPU_OK; }
   return no_throw([&]() -> int {
     HIPCHK(hipSetDevice(e->device));
     {                                                       // the half bit needs room below the coded bits at every step
@@ -839,9 +840,16 @@ extern "C" int ojphgpu_encoder_set_quality(ojphgpu_encoder* e, uint64_t max_sse)
       return OJPHGPU_E_NOMEM;
     if (!ec.empty()) HIPCHK(hipMemcpy(Q->comps.p, ec.data(), ec.size() * sizeof(ec[0]), hipMemcpyHostToDevice));
     e->quality = Q; owner.p = nullptr;
-    e->max_sse = max_sse; e->quality_on = true; e->ran = false;
+    e->max_sse = max_sse; e->cap_bytes = 0; e->quality_on = true; e->ran = false;
     return OJPHGPU_OK;
   });
+}
+
+extern "C" int ojphgpu_encoder_set_quality_capped(ojphgpu_encoder* e, uint64_t max_sse, uint64_t cap_bytes)
+{
+  const int rc = ojphgpu_encoder_set_quality(e, max_sse);
+  if (rc == OJPHGPU_OK) e->cap_bytes = cap_bytes;
+  return rc;
 }
 
 // One trial of the search: SSE(j) of the frame of the last run.  The planes of the arena, requantised with the band
@@ -908,7 +916,7 @@ static int encoder_quality_search(ojphgpu_encoder* e)
     if (!Q.frame) return OJPHGPU_E_INVALID;
     Q.by_index.assign(OJPHGPU_RATE_GRID, {});
     int rc = ojphgpu_quality_search(e->max_sse, encoder_quality_trial, e, &Q.info);
-    Q.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_QUALITY;
+    Q.have_info = rc == OJPHGPU_OK || rc == OJPHGPU_E_QUALITY; Q.have_capped = false;
     Q.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc) return rc;
     Q.best = Q.by_index[Q.info.grid_index];
@@ -929,16 +937,89 @@ static int encoder_quality_search(ojphgpu_encoder* e)
   return R.search_rc;
 }
 
+// One size trial of the capped search: the frame's blocks coded at j into the encoder's own output, as a round of the byte
+// budget's search codes them; R.frame_plan[0] is left at the step of j
+static int64_t encoder_size_trial(void* user, uint32_t j)
+{
+  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
+  EncoderRate& R = *e->rate;
+  const RateTrialOut own{ e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nullptr, nullptr, nullptr, nullptr };
+  const ojphgpu_cb_result* lengths = nullptr;
+  int rc;
+  if ((rc = encoder_plans_at(e, { j })) != 0 || (rc = encoder_code_round(e, own, &j, &lengths)) != 0) return rc;
+  e->quality->coded_at = (int)j;
+  return rate_layout_bytes(R.frame_plan[0]->plan, e->block_ids, lengths);
+}
+
+// The band statistics of the frame in the arena, for the model of the budget stepper: launched only when the cap binds.
+// A failure leaves the search without a model (plain halving) and is reported when the search has ended.
+static const uint32_t* encoder_capped_hist(void* user)
+{
+  ojphgpu_encoder* e = (ojphgpu_encoder*)user;
+  EncoderRate& R = *e->rate;
+  int& verdict = e->quality->hist_rc;
+  hipStream_t s = e->stream;
+  auto hip = [](hipError_t x) { return x == hipSuccess; };
+  verdict = OJPHGPU_E_HIP;
+  if (!hip(hipMemsetAsync(R.hist.p, 0, R.hist.n, s))) return nullptr;
+  if ((verdict = ojphgpu_band_stats(s, (const ojphgpu_stats_desc*)R.stats_descs.p, R.n_stats, R.stats_max_w, R.stats_max_h, e->arena.p, (uint32_t*)R.hist.p)) != 0) return nullptr;
+  verdict = OJPHGPU_E_HIP;
+  if (!hip(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, s)) || !hip(hipStreamSynchronize(s))) return nullptr;
+  verdict = OJPHGPU_OK;
+  return R.h_hist.data();
+}
+
+// the capped search of the last run, once: afterwards the device holds the coded blocks of j* and R.frame_plan[0] stands at its step
+static int encoder_capped_search(ojphgpu_encoder* e)
+{
+  EncoderRate& R = *e->rate; EncoderQuality& Q = *e->quality;
+  if (R.searched) return R.search_rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  Q.wait_ms = 0; Q.final_ms = 0; R.wait_ms = 0;
+  auto run = [&]() -> int {
+    if (!Q.frame) return OJPHGPU_E_INVALID;
+    Q.by_index.assign(OJPHGPU_RATE_GRID, {});
+    Q.coded_at = -1; Q.have_info = false; Q.hist_rc = OJPHGPU_OK;
+    int rc = capped_search(R.table, e->max_sse, e->cap_bytes, -1, -1, encoder_quality_trial, encoder_size_trial, encoder_capped_hist, e, &Q.capped);
+    Q.have_capped = !Q.hist_rc && (rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET);
+    if (Q.hist_rc) return Q.hist_rc;
+    if (rc) return rc;
+    ojphgpu_capped_info& I = Q.capped;
+    if (Q.coded_at != (int)I.grid_index) {                   // the last coding was another index: j* once more, counted and checked
+      const int64_t size = encoder_size_trial(e, I.grid_index);
+      I.rate_passes++;
+      if (size < 0) return size < INT32_MIN ? OJPHGPU_E_INVALID : (int)size;
+      if ((uint64_t)size != I.bytes) return OJPHGPU_E_HIP;   // the same blocks at the same step: anything else is a fault
+    }
+    Q.best = Q.by_index[I.grid_index];
+    if (Q.best.size() != Q.h_err.size()) return OJPHGPU_E_INVALID;
+    for (const ojphgpu_frame_err& c : Q.best) I.pae = std::max(I.pae, c.pae);
+    return OJPHGPU_OK;
+  };
+  R.search_rc = no_throw(run);
+  R.searched = true;
+  Q.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  Q.wait_ms += R.wait_ms;
+  return R.search_rc;
+}
+
+extern "C" int ojphgpu_encoder_capped_info(ojphgpu_encoder* e, ojphgpu_capped_info* info)
+{
+  if (!e || !info || !e->quality || !e->quality_on || !e->cap_bytes || !e->quality->have_capped || !e->rate->searched) return OJPHGPU_E_INVALID;
+  *info = e->quality->capped;
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_encoder_quality_info(ojphgpu_encoder* e, ojphgpu_quality_info* info)
 {
-  if (!e || !info || !e->quality || !e->quality->have_info) return OJPHGPU_E_INVALID;
+  if (!e || !info || !e->quality || e->cap_bytes || !e->quality->have_info) return OJPHGPU_E_INVALID;
   *info = e->quality->info;
   return OJPHGPU_OK;
 }
 
 extern "C" int ojphgpu_encoder_quality_comp(ojphgpu_encoder* e, uint32_t comp, uint64_t* sse, uint32_t* pae)
 {
-  if (!e || !sse || !pae || !e->quality || !e->quality->have_info || !e->rate->searched || e->rate->search_rc || comp >= e->quality->best.size())
+  if (!e || !sse || !pae || !e->quality || !(e->quality->have_info || e->quality->have_capped) || !e->rate->searched || e->rate->search_rc || comp >= e->quality->best.size())
     return OJPHGPU_E_INVALID;
   *sse = e->quality->best[comp].sse; *pae = e->quality->best[comp].pae;
   return OJPHGPU_OK;

@@ -491,6 +491,11 @@ struct EncoderQuality {
   std::vector<std::vector<ojphgpu_frame_err>> by_index;   // the figures of every index tried in this search
   bool have_info = false;
   ojphgpu_quality_info info;
+  // under a byte cap (ojphgpu_encoder_set_quality_capped): what the last capped finish found, and the index the device holds
+  bool have_capped = false;
+  ojphgpu_capped_info capped;
+  int coded_at = -1;
+  int hist_rc = 0;                                 // of the statistics pass of that search, when the cap bound (encoder_capped_hist)
   double search_ms = 0, wait_ms = 0, final_ms = 0;
   ~EncoderQuality();
 };
@@ -537,6 +542,7 @@ struct ojphgpu_encoder {
   std::vector<uint64_t> budgets;                   // one per frame: frame f of every run is coded to budgets[f]; empty: off
   EncoderRate* rate = nullptr;
   bool quality_on = false; uint64_t max_sse = 0;   // every frame is coded to this quality target (never together with a budget)
+  uint64_t cap_bytes = 0;                          // ... and under this byte cap (0: none; ojphgpu_encoder_set_quality_capped)
   EncoderQuality* quality = nullptr;
   // the blocks are coded by a search in ojphgpu_encoder_finish*, and Tier-2 writes from the search's plan
   bool searches() const { return !budgets.empty() || quality_on; }

@@ -273,6 +273,7 @@ struct EncOut {
 struct EncSearchResult {
   ojphgpu_rate_info rate{}; bool have_rate = false;
   ojphgpu_quality_info quality{}; uint32_t first_guess = 0; bool have_quality = false;
+  ojphgpu_capped_info capped{}; bool have_capped = false;   // a target under a byte cap: this instead of `quality`
   std::vector<ojphgpu_frame_err> comps;
 };
 
@@ -287,7 +288,7 @@ struct EncSlot {
   double t_submit = 0, t_done = 0, t_t2 = 0;
   // a pipe that searches: the frame's byte budget or quality target, what its search found, and the plan at the step it
   // chose (the finisher lays the codestream out from it while the worker re-quantises for the next frame)
-  uint64_t budget = 0, target = 0;
+  uint64_t budget = 0, target = 0, cap = 0;         // (cap: the byte cap of a frame with a target; 0 = none)
   ojphgpu_plan* rplan = nullptr;
   EncSearchResult found;
 };
@@ -321,6 +322,11 @@ struct ojphgpu_enc_pipe {
   uint64_t max_sse = 0;                             // the target the next _submit gives its frame
   Pinned h_qdescs, h_qerr;                          // a trial's requantise descriptors going out, its error words coming back
   std::vector<std::vector<ojphgpu_frame_err>> q_by_index;   // the figures of every index the search of the worker's frame tried
+  // a target under a byte cap (ojphgpu_enc_pipe_set_quality_capped): a quality pipe that has the spare set and the pinned
+  // histograms from the start.  `hint` is then the last certified frame's q, hint_b the last BY_BUDGET frame's j*
+  bool capped = false;
+  uint64_t cap_bytes = 0;                           // the cap the next _submit gives its frame
+  int hint_b = -1;
   // the ordered worker of a pipe that searches, whichever search it is: it owns the compute stream
   bool searching() const { return budget_on || quality_on; }
   std::deque<uint32_t> search_work; bool stop_search = false;
@@ -516,11 +522,64 @@ static int enc_quality_frame(ojphgpu_enc_pipe* p, EncSlot& s)
   return OJPHGPU_OK;
 }
 
+// ---- a target under a byte cap: the same worker, both kinds of trial.  Per frame, on the compute stream: unpack and
+// transform; ojphgpu_capped_search through the two trial callbacks above -- quality trials started from the last certified
+// frame's q, size trials alternating between the slot's output set and the spare, started from the last bound frame's j* --
+// and the band statistics only when the cap binds, while the unquantised planes are still in the arena.  Afterwards the
+// slot holds the set with j* and its plan copy stands at qstep(j*), as after a budget's search.
+struct EncCappedCtx { EncQualityCtx q; EncTrialCtx t; int hist_rc; };
+
+static int64_t enc_capped_sse(void* user, uint32_t j, uint64_t* sse) { return enc_pipe_quality_trial(&((EncCappedCtx*)user)->q, j, sse); }
+static int64_t enc_capped_size(void* user, uint32_t j) { return enc_pipe_trial(&((EncCappedCtx*)user)->t, j); }
+
+static const uint32_t* enc_capped_hist(void* user)
+{
+  EncCappedCtx& c = *(EncCappedCtx*)user;
+  ojphgpu_enc_pipe* p = c.q.p;
+  ojphgpu_encoder* e = p->enc;
+  EncoderRate& R = *e->rate;
+  c.hist_rc = no_throw([&]() -> int {
+    HIPCHK(hipMemsetAsync(R.hist.p, 0, R.hist.n, p->s_comp));
+    int rc = ojphgpu_band_stats(p->s_comp, (const ojphgpu_stats_desc*)R.stats_descs.p, R.n_stats, R.stats_max_w, R.stats_max_h, e->arena.p, (uint32_t*)R.hist.p);
+    if (rc || (rc = copy_to_host_launch(p->s_comp, p->h_hist.d, R.hist.p, R.h_hist.size() * 4)) != 0) return rc;
+    HIPCHK(hipEventRecord(p->ev_trial, p->s_comp));
+    HIPCHK(hipEventSynchronize(p->ev_trial));
+    return OJPHGPU_OK;
+  });
+  return c.hist_rc ? nullptr : (const uint32_t*)p->h_hist.p;   // (a failure: halving, and the frame ends with it below)
+}
+
+static int enc_capped_frame(ojphgpu_enc_pipe* p, EncSlot& s)
+{
+  ojphgpu_encoder* e = p->enc;
+  EncSearchResult& f = s.found;
+  HIPCHK(hipSetDevice(p->device));
+  int rc = enc_begin_frame(p, s);                    // conversion + DWT (e->quality_on)
+  if (rc) return rc;
+  const RateFrame rf{ e, &s.rplan->plan, s.cap, &s.o, &p->spare, p->ev_trial };
+  EncCappedCtx c{ EncQualityCtx{ p, &s }, EncTrialCtx{ &rf, nullptr, rf.slot, -1 }, OJPHGPU_OK };
+  for (std::vector<ojphgpu_frame_err>& v : p->q_by_index) v.clear();
+  rc = capped_search(e->rate->table, s.target, s.cap, p->hint, p->hint_b, enc_capped_sse, enc_capped_size, enc_capped_hist, &c, &f.capped);
+  f.have_capped = rc == OJPHGPU_OK || rc == OJPHGPU_E_BUDGET;
+  if (c.hist_rc) { f.have_capped = false; return c.hist_rc; }
+  if (rc) return rc;
+  const ojphgpu_capped_info& I = f.capped;
+  if (c.t.best != rf.slot) std::swap(*rf.slot, *rf.spare);   // (pointers only) the slot keeps the set with j*, the other is the spare
+  if (c.t.at != (int)I.grid_index && !rate_apply_step(*rf.Q, I.qstep)) { f.have_capped = false; return OJPHGPU_E_INVALID; }
+  f.comps = p->q_by_index[I.grid_index];
+  if (f.comps.size() != p->P->comps.size()) { f.have_capped = false; return OJPHGPU_E_INVALID; }
+  for (const ojphgpu_frame_err& k : f.comps) f.capped.pae = std::max(f.capped.pae, k.pae);
+  if (I.quality_index < OJPHGPU_RATE_GRID) p->hint = (int)I.quality_index;
+  if (I.outcome == OJPHGPU_CAPPED_BY_BUDGET) p->hint_b = (int)I.grid_index;
+  HIPCHK(hipEventRecord(s.ev_kern, p->s_comp));
+  return OJPHGPU_OK;
+}
+
 static void enc_search_worker(ojphgpu_enc_pipe* p)
 {
   for (uint32_t si; pop_work(p->mu, p->cv_search, p->search_work, p->stop_search, si);) {
     EncSlot& s = p->slots[si];
-    const int rc = no_throw([&] { return p->quality_on ? enc_quality_frame(p, s) : enc_rate_frame(p, s); });
+    const int rc = no_throw([&] { return p->capped ? enc_capped_frame(p, s) : p->quality_on ? enc_quality_frame(p, s) : enc_rate_frame(p, s); });
     if (rc) {                                        // the frame ends here (OJPHGPU_E_BUDGET / _E_QUALITY among the reasons); see enc_finish_frame
       hipStreamSynchronize(p->s_h2d); hipStreamSynchronize(p->s_comp);
       s.rc = rc;
@@ -646,7 +705,7 @@ extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
   HIPCHK(hipEventRecord(s.ev_in, p->s_h2d));
   if (p->searching()) {                              // everything on the compute stream is the search worker's, frame by frame
     std::lock_guard<std::mutex> lk(p->mu);
-    s.budget = p->max_bytes; s.target = p->max_sse; s.found = EncSearchResult{};
+    s.budget = p->max_bytes; s.target = p->max_sse; s.cap = p->capped ? p->cap_bytes : 0; s.found = EncSearchResult{};
     s.state = SUBMITTED;
     p->search_work.push_back(si);
     p->n_acq++; p->n_sub++;
@@ -768,6 +827,43 @@ extern "C" int ojphgpu_enc_pipe_set_quality(ojphgpu_enc_pipe* p, uint64_t max_ss
   });
 }
 
+// A target under a byte cap: a quality pipe that also takes what a budget pipe takes -- the encoder's own output set as the
+// spare, the pinned histograms -- so it is that from the first call, or never: a quality pipe made without a cap has
+// released the set and cannot gain one, and a capped pipe's cap cannot go back to 0.
+extern "C" int ojphgpu_enc_pipe_set_quality_capped(ojphgpu_enc_pipe* p, uint64_t max_sse, uint64_t cap_bytes)
+{
+  if (!p || p->dead || p->budget_on) return OJPHGPU_E_INVALID;
+  if (cap_bytes == 0) return p->capped ? OJPHGPU_E_INVALID : ojphgpu_enc_pipe_set_quality(p, max_sse);
+  if (p->quality_on || p->n_acq != 0 || p->slots[0].state != FREE) {   // the mode stays, both values may move
+    if (!p->capped) return OJPHGPU_E_INVALID;
+    p->max_sse = max_sse; p->cap_bytes = cap_bytes;
+    return OJPHGPU_OK;
+  }
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(p->device));
+    ojphgpu_encoder* e = p->enc;
+    int rc = ojphgpu_encoder_set_quality(e, max_sse);        // (the encoder's own cap stays 0: the pipe runs the search)
+    if (rc || (rc = enc_search_on(p, true)) != 0) return rc;
+    p->spare.out = e->out; p->spare.counters = e->counters;   // the encoder's own output set becomes the spare
+    e->out = DeviceBuf(); e->counters = DeviceBuf();
+    if (p->h_hist.reserve(e->rate->h_hist.size() * 4 + 64) ||
+        p->h_qdescs.reserve(e->quality->h_descs.size() * sizeof(ojphgpu_requant_desc) + 64) ||
+        p->h_qerr.reserve(p->P->comps.size() * sizeof(ojphgpu_frame_err) + 64)) return OJPHGPU_E_NOMEM;
+    p->q_by_index.assign(OJPHGPU_RATE_GRID, {});
+    p->quality_on = true; p->capped = true; p->max_sse = max_sse; p->cap_bytes = cap_bytes; p->hint_b = -1; p->dead = false;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_enc_pipe_capped_info(ojphgpu_enc_pipe* p, ojphgpu_capped_info* info)
+{
+  if (!p || !info) return OJPHGPU_E_INVALID;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->last.have_capped) return OJPHGPU_E_INVALID;
+  *info = p->last.capped;
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_enc_pipe_quality_info(ojphgpu_enc_pipe* p, ojphgpu_quality_info* info, uint32_t* first_guess)
 {
   if (!p || !info || !first_guess) return OJPHGPU_E_INVALID;
@@ -781,7 +877,7 @@ extern "C" int ojphgpu_enc_pipe_quality_comp(ojphgpu_enc_pipe* p, uint32_t comp,
 {
   if (!p || !sse || !pae) return OJPHGPU_E_INVALID;
   std::lock_guard<std::mutex> lk(p->mu);
-  if (!p->last.have_quality || comp >= p->last.comps.size()) return OJPHGPU_E_INVALID;
+  if (!(p->last.have_quality || p->last.have_capped) || comp >= p->last.comps.size()) return OJPHGPU_E_INVALID;
   *sse = p->last.comps[comp].sse; *pae = p->last.comps[comp].pae;
   return OJPHGPU_OK;
 }

@@ -318,7 +318,7 @@ class EncoderPipe(_Handover):
     _side = "enc"
 
     def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None,
-                 max_sse=None, min_psnr=None, video=None, **kw):
+                 max_sse=None, min_psnr=None, video=None, cap_bytes=0, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
         the device.  video="uyvy" | "yuy2" | "v210" | "y210" | "y212" | "y216": the frames are handed over as one 4:2:2 video
@@ -326,9 +326,12 @@ class EncoderPipe(_Handover):
         "p016": as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420's tight layout); video="v410" | "y410" |
         "r210" | "r10k" | "y412" | "y416" | "ayuv" | "bgra" | "rgba" | "argb": as one 4:4:4 packed buffer (uint8 [H, row_bytes],
         pack_video444's layout).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
-        quality target (set_quality) -- one or the other"""
+        quality target (set_quality) -- one or the other; cap_bytes=N with a target: to the target, but never above N bytes
+        (set_quality(..., cap_bytes=N); from the start, or never)"""
         from .codec import _torch
         _torch()
+        if cap_bytes and max_sse is None and min_psnr is None:
+            raise ValueError("cap_bytes needs a quality target (max_sse or min_psnr); a byte budget alone is max_bytes")
         self.plan = plan if plan is not None else Plan(params if params is not None else make_params(**kw))
         self.container = int(container)
         self.depth = int(depth)
@@ -345,7 +348,7 @@ class EncoderPipe(_Handover):
         if max_bytes:
             self.set_budget(max_bytes)
         if max_sse is not None or min_psnr is not None:
-            self.set_quality(max_sse=max_sse, min_psnr=min_psnr)
+            self.set_quality(max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes)
         self.in_flight = 0
 
     def set_budget(self, max_bytes):
@@ -362,20 +365,44 @@ class EncoderPipe(_Handover):
         check(self._lib.ojphgpu_enc_pipe_rate_info(self._h, C.byref(info)), "enc_pipe_rate_info")
         return {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
 
-    def set_quality(self, max_sse=None, min_psnr=None):
+    def set_quality(self, max_sse=None, min_psnr=None, cap_bytes=None):
         """Every frame is coded at the coarsest step of the rate grid found to meet the target -- the squared error between
         the frame and the decode of its codestream, over all components, is at most max_sse (an integer; 0 is a target), or
         min_psnr in dB turned into one by plan.psnr_to_sse -- the search started from the previous frame's answer
         (ojphgpu_enc_pipe_set_quality).  Switched on before the first acquire(); afterwards the target may change between
         frames -- the value at submit() is the frame's -- but not be switched off.  Not together with a byte budget.  A frame
-        whose target no step meets raises OjphError (capi.E_QUALITY) from its collect()."""
+        whose target no step meets raises OjphError (capi.E_QUALITY) from its collect().
+
+        cap_bytes=N > 0: under a byte cap (ojphgpu_enc_pipe_set_quality_capped) -- on from the first call or never; afterwards
+        both values may change between frames, the cap not back to 0; cap_bytes=None leaves the cap as it is.  Such a frame
+        never raises E_QUALITY: the finest step that fits is written instead (capped_info() tells), and a frame whose cap not
+        even the coarsest step fits raises OjphError (capi.E_BUDGET) from its collect()."""
         from .plan import psnr_to_sse
         if (max_sse is None) == (min_psnr is None):
             raise ValueError("set_quality: max_sse or min_psnr, one of them")
         t = int(max_sse) if max_sse is not None else psnr_to_sse(self.plan, float(min_psnr))
         if not 0 <= t < 2 ** 64:
             raise ValueError("set_quality: max_sse must fit 64 bits")
-        check(self._lib.ojphgpu_enc_pipe_set_quality(self._h, t), "enc_pipe_set_quality")
+        if cap_bytes is None:
+            check(self._lib.ojphgpu_enc_pipe_set_quality(self._h, t), "enc_pipe_set_quality")
+            return
+        if not 0 <= int(cap_bytes) < 2 ** 64:
+            raise ValueError("set_quality: cap_bytes must fit 64 bits")
+        check(self._lib.ojphgpu_enc_pipe_set_quality_capped(self._h, t, int(cap_bytes)), "enc_pipe_set_quality_capped")
+
+    def capped_info(self):
+        """of the frame collected last, on a pipe with a byte cap: the dict of codec.Encoder.capped_info; after E_BUDGET the
+        passes and comps == []"""
+        info = capi.CappedInfo()
+        check(self._lib.ojphgpu_enc_pipe_capped_info(self._h, C.byref(info)), "enc_pipe_capped_info")
+        out = {k: getattr(info, k) for k, _ in capi.CappedInfo._fields_ if k != "reserved"}
+        out["comps"] = []
+        for c in range(int(self.plan.params.num_comps)):
+            sse, pae = C.c_uint64(), C.c_uint32()
+            if self._lib.ojphgpu_enc_pipe_quality_comp(self._h, c, C.byref(sse), C.byref(pae)) != capi.OK:
+                break
+            out["comps"].append((int(sse.value), int(pae.value)))
+        return out
 
     def quality_info(self):
         """of the frame collected last: dict(grid_index, qstep, sse, sse_coarser, pae, passes, bytes, comps), as
@@ -430,15 +457,28 @@ class EncoderPipe(_Handover):
         check(self._lib.ojphgpu_enc_pipe_stats(self._h, out), "enc_pipe_stats")
         return dict(frames=int(out[0]), host_tier2_ms=out[1], latency_ms=out[2], tier2_threads=int(out[3]))
 
-    def encode_sequence(self, frames, budgets=None, targets=None):
+    def encode_sequence(self, frames, budgets=None, targets=None, caps=None):
         """frames: iterable of [C,H,W] arrays -> generator of codestreams, in order.  budgets (a pipe with a byte budget):
         one int for every frame, or an iterable parallel to frames; a frame no step fits raises from here as from collect().
-        targets (a pipe with a quality target): the same with max_sse values; not both"""
+        targets (a pipe with a quality target): the same with max_sse values; not both.  caps (with targets, on a pipe with a
+        byte cap): one cap for every frame, or an iterable parallel to frames"""
         if budgets is not None and targets is not None:
             raise ValueError("encode_sequence: budgets or targets, not both")
-        what, values = ("targets", targets) if targets is not None else ("budgets", budgets)
-        setter = (lambda v: self.set_quality(max_sse=v)) if targets is not None else self.set_budget
-        if values is not None and not hasattr(values, "__iter__"):
+        if caps is not None and targets is None:
+            raise ValueError("encode_sequence: caps need targets")
+        # one of three modes: what the values are called, the values (one for all frames, or one per frame), how one is set
+        if caps is not None:
+            import itertools
+            many = hasattr(targets, "__iter__") or hasattr(caps, "__iter__")
+            each = lambda v: iter(v) if hasattr(v, "__iter__") else itertools.repeat(v)
+            # (pairs; the shorter of two lists ends the values, as one list does)
+            what, values = "targets and caps", zip(each(targets), each(caps)) if many else (targets, caps)
+            setter = lambda v: self.set_quality(max_sse=v[0], cap_bytes=v[1])
+        elif targets is not None:
+            what, values, setter, many = "targets", targets, lambda v: self.set_quality(max_sse=v), hasattr(targets, "__iter__")
+        else:
+            what, values, setter, many = "budgets", budgets, self.set_budget, hasattr(budgets, "__iter__")
+        if values is not None and not many:
             setter(values)
             values = None
         values = iter(values) if values is not None else None

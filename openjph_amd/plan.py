@@ -403,6 +403,45 @@ def quality_search(max_sse, sse_fn, hint=None):
     return out
 
 
+def capped_search(plan: Plan, max_sse, cap_bytes, sse_fn, size_fn, hist_fn=None, hint_q=-1, hint_b=-1):
+    """ojphgpu_capped_search: a quality target under a byte cap over callbacks of the caller's -- sse_fn(j) -> SSE at grid
+    index j, size_fn(j) -> bytes of its codestream (negative values: error codes), hist_fn() -> uint32 [plan.num_bands, 80]
+    or None, called at most once and only when the cap binds.  -> dict of capi.CappedInfo's fields; capi.OjphError with
+    .code (capi.E_BUDGET when not even index 0 fits) and .info = the dict otherwise."""
+    info = capi.CappedInfo()
+    keep = []
+
+    def sse(user, j, out):
+        v = int(sse_fn(int(j)))
+        if v < 0:
+            return v
+        out[0] = v
+        return 0
+
+    def hist(user):
+        h = None if hist_fn is None else hist_fn()
+        if h is None:
+            return None
+        h = np.ascontiguousarray(h, dtype=np.uint32)
+        if h.size != plan.num_bands * capi.STATS_BINS:
+            raise ValueError("hist must hold 80 bins for every band of the plan")
+        keep.append(h)
+        return h.ctypes.data
+    if not 0 <= int(max_sse) < 2 ** 64 or not 0 <= int(cap_bytes) < 2 ** 64:
+        raise ValueError("max_sse and cap_bytes must fit 64 bits")
+    if not all(-2 ** 31 <= int(h) < 2 ** 31 for h in (hint_q, hint_b)):
+        rc = capi.E_INVALID
+    else:
+        rc = capi.lib().ojphgpu_capped_search(plan.handle, int(max_sse), int(cap_bytes), int(hint_q), int(hint_b), capi.SSE_FN(sse),
+                                              capi.SIZE_FN(lambda user, j: int(size_fn(int(j)))), capi.HIST_FN(hist), None, C.byref(info))
+    out = {k: getattr(info, k) for k, _ in capi.CappedInfo._fields_ if k != "reserved"}
+    if rc != capi.OK:
+        err = capi.OjphError(rc, "capped_search")
+        err.info = out
+        raise err
+    return out
+
+
 def psnr_to_sse(plan: Plan, db):
     """the max_sse of a PSNR over the whole frame: int(n peak^2 / 10^(dB / 10)) with n = the samples of all components and
     peak = 2^bit_depth - 1.  ValueError when the components differ in depth (a frame then has no one peak)."""

@@ -15,7 +15,10 @@ no search: the difference is what the search costs; (c) codec.Encoder(min_psnr) 
 there was before the pipe had a target, the full search on every frame; its frames are uploaded from pageable numpy memory
 (Encoder.encode), the pipes' from their pinned slots.  Prints one JSON line per target: j*, mean trials per frame, and per
 contender the frames/s of every round, their median and their spread (max - min) / median.
-  python tools/quality_bench.py --pipe [--rounds 3] [--frames 24] [--rows 4320]"""
+  python tools/quality_bench.py --pipe [--rounds 3] [--frames 24] [--rows 4320]
+
+--cap: a target under a byte cap (cap_bench below), single encoder or with --pipe the encoder pipe.
+  python tools/quality_bench.py --cap [--pipe] [--rounds 3] [--frames 24] [--rows 4320]"""
 import argparse
 import json
 import os
@@ -74,8 +77,78 @@ def pipe_bench(a):
         print(json.dumps(out), flush=True)
 
 
+def cap_bench(a):
+    """--cap: what a byte cap on the target costs, C3 at 45 dB under three caps -- one above size(q), one at 0.2 bytes per
+    sample, one at 3/4 of size(q), which binds.  Three contenders take turns, `--rounds` rounds after one that warms up: (a) the capped run; (b) the plain run at
+    qstep(j*); (c) the quality run without a cap.  Single encoder (device-resident frame, ms per frame), or with --pipe the
+    encoder pipe from host memory (`--frames` identical frames per round, frames/s).  One JSON line per cap: the outcome,
+    both indices, both pass counts (the pipe: of the last frame, its steady state), every round's figure, medians, spread."""
+    import torch
+    from openjph_amd import codec
+    from openjph_amd import plan as planmod
+    from openjph_amd.pipeline import EncoderPipe
+    from openjph_amd.plan import Plan, make_params
+    from tests import synth
+    img = synth.survey_c3(rows=a.rows)
+    nc, h, w = img.shape
+    img16 = img.astype(np.uint16)
+    d_img = torch.from_numpy(img16.view(np.int16)).cuda()
+
+    def params(qstep):
+        return make_params(w, h, nc, bit_depth=12, reversible=False, qstep=qstep)
+    pl = Plan(params(0.001))
+    T = planmod.psnr_to_sse(pl, 45)
+    quality = codec.Encoder(params(0.001), max_sse=T)
+    quality.run_device(d_img)
+    size_q = len(quality.finish())
+    capped = codec.Encoder(params(0.001))
+
+    def single(enc):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        enc.run_device(d_img)
+        cs = enc.finish()
+        return (time.perf_counter() - t0) * 1e3, cs
+
+    def piped(**kw):
+        pipe = EncoderPipe(Plan(params(kw.pop("qstep", 0.001))), depth=4, **kw)
+        t0 = time.perf_counter()
+        out = list(pipe.encode_sequence([img16] * a.frames))
+        dt = time.perf_counter() - t0
+        info = pipe.capped_info() if "cap_bytes" in kw else None
+        pipe.close()
+        return a.frames / dt, out[-1], info
+    # (0.2 bytes per sample lies above this frame's size(q) at 45 dB, 0.17: the third cap is one that binds)
+    for label, cap in (("above size(q)", size_q * 5 // 4), ("0.2 bytes per sample", int(0.2 * img.size)), ("3/4 of size(q)", size_q * 3 // 4)):
+        capped.set_quality(max_sse=T, cap_bytes=cap)
+        v = {"capped": [], "fixed_step": [], "quality": []}
+        info = fixed = None
+        for r in range(a.rounds + 1):
+            if a.pipe:
+                x, cs, info = piped(max_sse=T, cap_bytes=cap)
+                y, cs_fixed, _ = piped(qstep=planmod.rate_grid_qstep(info["grid_index"]))
+                z, _, _ = piped(max_sse=T)
+            else:
+                x, cs = single(capped)
+                info = capped.capped_info()
+                fixed = fixed or codec.Encoder(params(planmod.rate_grid_qstep(info["grid_index"])))
+                y, cs_fixed = single(fixed)
+                z, _ = single(quality)
+            assert cs == cs_fixed and len(cs) == info["bytes"] <= cap
+            if r:
+                v["capped"].append(x); v["fixed_step"].append(y); v["quality"].append(z)
+        out = dict(frame="c3 %dx%dx%d 12-bit, 16-bit containers" % (w, h, nc), mode="pipe, frames/s" if a.pipe else "single, ms per frame",
+                   min_psnr_db=45, max_sse=T, cap=label, cap_bytes=cap, size_q=size_q,
+                   **{k: info[k] for k in ("grid_index", "outcome", "quality_index", "bytes", "sse", "quality_passes", "rate_passes")})
+        for k, x in v.items():
+            med = float(np.median(x))
+            out[k] = dict(rounds=[round(t, 3) for t in x], median=round(med, 3), spread=round((max(x) - min(x)) / med, 3))
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cap", action="store_true", help="a target under a byte cap (with --pipe: in the encoder pipe)")
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=4320, help="top rows of the frame (rehearsals at a small size)")
@@ -84,6 +157,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=24)
     a = ap.parse_args()
+    if a.cap:
+        return cap_bench(a)
     if a.pipe:
         return pipe_bench(a)
     import torch
