@@ -634,8 +634,28 @@ int  ojphgpu_encoder_create_batch(const ojphgpu_plan* plan, int device, void* st
                                   uint32_t num_frames, ojphgpu_encoder** out);
 int  ojphgpu_encoder_finish_frame(ojphgpu_encoder* enc, uint32_t frame, uint8_t* h_out, size_t cap,
                                   size_t* out_len);
-/* device part only: d_image (int32 planes, resident in HBM) -> coded block bytes in HBM */
+/* device part only: d_image (int32 planes, resident in HBM) -> coded block bytes in HBM.
+ * What a run leaves (all ojphgpu_encoder_run_device*): on return, in the order of the encoder's stream, the frame HAS BEEN
+ * CONSUMED -- work enqueued on that stream afterwards may overwrite or free d_image -- and that is all the stream's order
+ * says.  The products of the run (coded bytes, block lengths, cursors, the coefficient planes) live in the object's own
+ * buffers and are reached only through the object's calls (_coded_bytes, _finish*, the timing getters, the next run,
+ * _destroy, the setters of section 5b / 5c), each of which waits for them.  A plain run of a single-frame encoder with at
+ * least two decompositions, into its own buffers and with per-launch timing off (ojphgpu_encoder_set_timing(enc, 0)), is
+ * RELEASED: everything behind the last launch that reads d_image -- the top resolution's blocks, the lower transform
+ * levels, the other blocks -- runs on two streams of the object's own and the caller's stream does not wait for it, so
+ * the caller's next job on that stream starts beside the block coder.  Every other run (per-launch timing on, which is
+ * the default; a byte budget or a quality target; a frame batch; the encoder of a frame pipe or a transcoder;
+ * OJPHGPU_NO_OVERLAP=1 or OJPHGPU_ENC_RELEASE=0 in the environment at creation) ends joined on the caller's stream.
+ * The bytes are the same either way.
+ * Stream capture: a joined run is a fork and a join on the caller's stream and can be captured as it is; a released run
+ * leaves two forked streams unjoined, so a capture that holds one must also hold one of the object's calls that wait
+ * (the next run of the same object does) before it ends -- or the object runs with per-launch timing on.
+ * Two caller streams: a caller that drives encodes and decodes on two streams of its own keeps a decode of its own
+ * priority waiting at all times and starves the low-priority branches of a released run; INTEGRATION.md section 5. */
 int  ojphgpu_encoder_run_device(ojphgpu_encoder* enc, const int32_t* d_image);
+/* diagnostic (tests, tools; not needed to use the object): *pending = 1 while a released run of the object has not been
+ * waited for by one of the calls above, else 0 */
+int  ojphgpu_encoder_is_pending(const ojphgpu_encoder* enc, int* pending);
 /* the frame in 16-bit containers (same plane layout, 2-byte elements; int16 for signed components,
  * uint16 otherwise; every component at most 16 bits deep) */
 int  ojphgpu_encoder_run_device16(ojphgpu_encoder* enc, const uint16_t* d_image);
@@ -699,7 +719,8 @@ int  ojphgpu_decode(ojphgpu_decoder* dec, const uint8_t* h_codestream, size_t le
  * stream: out[0]=convert+colour [1]=DWT [2]=HT block coder [3]=total */
 /* per_launch = 1 (default): every launch is bracketed by HIP events so that the per-stage sums below
  * are available; 0: only the wall time of the run is recorded (out[3]), the other entries read 0 --
- * the event pairs cost a few microseconds each, which shows at these kernel durations */
+ * the event pairs cost a few microseconds each, which shows at these kernel durations.  An encoder's run with 0 may be
+ * released (see ojphgpu_encoder_run_device); its total ends with the later of its two branches */
 int  ojphgpu_encoder_set_timing(ojphgpu_encoder* enc, int per_launch);
 int  ojphgpu_decoder_set_timing(ojphgpu_decoder* dec, int per_launch);
 int  ojphgpu_encoder_timing(ojphgpu_encoder* enc, float out[4]);

@@ -221,7 +221,9 @@ class Encoder:
 
     def run_device(self, d_image):
         """d_image: int32 torch tensor [C,H,W] (flat plan.frame_shape for sub-sampled components)
-        resident on the device. Asynchronous."""
+        resident on the device. Asynchronous.  In the order of the encoder's stream the frame has been consumed on return;
+        the products are reached through this object's calls, which wait for them (a run with set_timing(False) may be
+        released: include/ojphgpu.h, ojphgpu_encoder_run_device)."""
         torch = _torch()
         assert d_image.is_cuda and tuple(d_image.shape) == self.shape and d_image.is_contiguous()
         self._frame = d_image if self.max_sse is not None else None      # a quality target: finish() reads the frame again
@@ -236,6 +238,12 @@ class Encoder:
 
     def set_timing(self, per_launch: bool):
         check(self._lib.ojphgpu_encoder_set_timing(self._h, int(per_launch)), "encoder_set_timing")
+
+    def pending(self):
+        """a released run of this encoder has not been waited for yet (by coded_bytes, finish*, timing, the next run)"""
+        n = C.c_int()
+        check(self._lib.ojphgpu_encoder_is_pending(self._h, C.byref(n)), "encoder_is_pending")
+        return bool(n.value)
 
     def coded_bytes(self):
         n = C.c_uint64()

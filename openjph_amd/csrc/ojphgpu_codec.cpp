@@ -56,12 +56,18 @@ extern "C" void ojphgpu_encoder_destroy(ojphgpu_encoder* e)
 {
   if (!e) return;
   (void)hipSetDevice(e->device);
+  // a released run may still be coding on the object's own streams: nothing is freed under it
+  if (e->side) (void)hipStreamSynchronize(e->side);
+  if (e->low) (void)hipStreamSynchronize(e->low);
+  e->pending = false;
   for (DeviceBuf* b : { &e->arena, &e->image, &e->dwt_descs, &e->img_descs, &e->cb_descs, &e->conv_descs, &e->scratch, &e->out,
                         &e->results, &e->counters, &e->regions }) b->release();
   e->h_out.release(); e->h_res.release();
   if (e->side) (void)hipStreamDestroy(e->side);
+  if (e->low) (void)hipStreamDestroy(e->low);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+  if (e->ev_low) (void)hipEventDestroy(e->ev_low);
   e->timer.destroy();
   delete e->quality;
   delete e->rate;
@@ -77,12 +83,19 @@ extern "C" int ojphgpu_encoder_create(const ojphgpu_plan* plan, int device, void
 // blocks_only: the encoder half of a transcoder (section 5d) -- the block coder alone: no conversion or DWT descriptors and no
 // arena of its own (its owner lends it one)
 static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count,
-                          uint32_t nframes, ojphgpu_encoder** out, bool blocks_only = false);
+                          uint32_t nframes, ojphgpu_encoder** out, bool blocks_only = false, bool joined_only = false);
 
 extern "C" int ojphgpu_encoder_create_tiles(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first,
                                              uint32_t tile_count, ojphgpu_encoder** out)
 {
   return no_throw([&] { return encoder_create(plan, device, stream, tile_first, tile_count, 1, out); });
+}
+
+// the encoder of a frame pipe: every run writes into a slot and ends joined, so it gets no second stream (ojphgpu_objects.h)
+int ojphgpu_encoder_create_joined(const ojphgpu_plan* plan, int device, void* stream, ojphgpu_encoder** out)
+{
+  if (!plan) return OJPHGPU_E_INVALID;
+  return no_throw([&] { return encoder_create(plan, device, stream, 0, (uint32_t)plan->plan.tiles.size(), 1, out, false, true); });
 }
 
 extern "C" int ojphgpu_encoder_create_batch(const ojphgpu_plan* plan, int device, void* stream, uint32_t num_frames,
@@ -173,7 +186,7 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
 }
 
 static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count,
-                          uint32_t nframes, ojphgpu_encoder** out, bool blocks_only)
+                          uint32_t nframes, ojphgpu_encoder** out, bool blocks_only, bool joined_only)
 {
   if (!plan || !out || nframes == 0) return OJPHGPU_E_INVALID;
   *out = nullptr;
@@ -215,6 +228,8 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       // million samples of the top resolution and 1.6 x that below it (more bytes per sample, shorter launches), a lower
       // analysis level its bytes at 3 TB/s or a 12 us launch floor.  8K 4:4:4: 90 % (step 0.957 -> 0.938 ms); a 4K frame's
       // main branch is the longer one already: 100 %.  OJPHGPU_ENC_TOP_SHARE=<percent> overrides the model.
+      // The cut is the joined schedule's: a released run (ojphgpu_objects.h) measures best at 40-50 % (0.905 against
+      // 0.931 ms at 8K, profiles/enc_release_ab.txt), but one object runs both schedules and the cut is made once, here.
       static const int share_env = [] { const char* v = getenv("OJPHGPU_ENC_TOP_SHARE"); const int x = v ? atoi(v) : 0; return x < 10 ? 0 : x > 100 ? 100 : x; }();
       double s_top = 0, s_low = 0;                         // millions of samples
       for (size_t i = 0; i < e->block_ids.size(); ++i) {
@@ -226,22 +241,37 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       const double us_per_ms = 3.8, margin_us = 30.0;
       const double move = (s_top + margin_us / us_per_ms - 1.6 * s_low - dwt_us / us_per_ms) / 2.0;   // top samples the main branch should take
       int share = share_env;
-      if (!share) share = s_top > 0 && move > 0 ? (int)(100.0 * (1.0 - move / s_top)) : 100;
-      share = share < 50 ? 50 : share > 100 ? 100 : share;
+      if (!share) { share = s_top > 0 && move > 0 ? (int)(100.0 * (1.0 - move / s_top)) : 100; share = share < 50 ? 50 : share > 100 ? 100 : share; }
       e->n_top = (uint32_t)((uint64_t)e->n_top * (uint32_t)share / 100u);
     }
     if (e->n_top == 0 || e->n_top == e->block_ids.size()) e->n_top = 0;
     else {
       // the side stream carries the long launch of the pair (the top resolution's blocks); the main stream's branch -- four
       // small transform launches, then the other blocks -- is the one that ends last when both share the chip evenly:
-      // OJPHGPU_ENC_SIDE_PRIO=low lets the dispatcher prefer the main branch (high: the opposite; unset: equal)
+      // OJPHGPU_ENC_SIDE_PRIO=low lets the dispatcher prefer the main branch (high: the opposite; normal: equal; unset: below)
       int prio_lo = 0, prio_hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
       const char* pe = getenv("OJPHGPU_ENC_SIDE_PRIO");
       const int prio = pe && pe[0] == 'l' ? prio_lo : pe && pe[0] == 'h' ? prio_hi : (prio_lo + prio_hi) / 2;
-      if (hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, pe ? prio : 0) != hipSuccess ||
+      // Released runs (ojphgpu_objects.h) need a second stream -- the lower levels and their blocks -- and both own
+      // streams at the LOWEST priority: what runs beside them is the caller's next job, whose result the caller waits
+      // for, while theirs is not needed before the object's next run -- at equal priority the three launches that start
+      // behind level 1 share the chip evenly and a decode enqueued behind the encode takes as long as the time it saves
+      // (8K step 0.953 ms at equal priority, 0.931 with both low, 0.956 joined; profiles/enc_release_ab.txt).
+      // OJPHGPU_ENC_SIDE_PRIO overrides the priority of both.  An encoder whose runs always end joined -- a transcoder's
+      // block coder, a frame pipe's encoder (joined_only), OJPHGPU_ENC_RELEASE=0 -- keeps the one side stream at the
+      // caller's priority.  Both streams are made HERE, next to each other: made by the first released run instead
+      // (behind a decoder's streams) they measured 1.32 ms per 8K step against 0.93 (supposed, not shown: streams
+      // are dealt onto the runtime's four hardware queues in the order they are created, and the late ones share one).
+      const char* rel = getenv("OJPHGPU_ENC_RELEASE");
+      e->can_release = !blocks_only && !joined_only && !(rel && rel[0] == '0');
+      const int own_prio = pe ? prio : e->can_release ? prio_lo : 0;
+      if (hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, own_prio) != hipSuccess ||
           hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
+      if (e->can_release &&
+          (hipStreamCreateWithPriority(&e->low, hipStreamNonBlocking, own_prio) != hipSuccess ||
+           hipEventCreateWithFlags(&e->ev_low, hipEventDisableTiming) != hipSuccess)) return bail(OJPHGPU_E_HIP);
     }
   }
   std::vector<ojphgpu_cb_desc> bd;
@@ -291,16 +321,21 @@ struct BlockCoderRun {
     if (T) T->end(sh, st);
     return OJPHGPU_OK;
   }
-  int clear() { HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->stream)); return OJPHGPU_OK; }
-  int fork_top() {                                          // the top resolution's blocks are ready to be coded
+  // (every run of the block coder starts here: a released run of the object that is still coding is joined first)
+  int clear() { int rc = encoder_settle(e); if (rc) return rc; HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->stream)); return OJPHGPU_OK; }
+  // the top resolution's blocks are ready to be coded; release: the caller's stream is left here, the rest of the run goes to e->low
+  int fork_top(bool release = false) {
     forked = true;
     HIPCHK(hipEventRecord(e->ev_fork, e->stream));
     HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
     int rc = launch(e->side, 0, e->n_top, e->widths_top);
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev_join, e->side));
+    if (release) { e->pending = true; HIPCHK(hipStreamWaitEvent(e->low, e->ev_fork, 0)); }   // (pending from here: also a run that fails below)
     return OJPHGPU_OK;
   }
+  // the other blocks behind the lower levels on e->low; nobody waits yet (the caller records ev_low: ReleasedBranch)
+  int rest_released() { return launch(e->low, e->n_top, nblocks - e->n_top, e->widths_rest); }
   int rest_and_join() {                                     // (forks here if nobody has)
     int rc = e->n_top && !forked ? fork_top() : OJPHGPU_OK;
     if (rc) return rc;
@@ -309,6 +344,12 @@ struct BlockCoderRun {
     if (e->n_top) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
     return OJPHGPU_OK;
   }
+};
+// From the fork of a released run on, EVERY way out of the run records ev_low behind what has been queued on e->low -- a run
+// that fails half way has launches there too, and the settle of the next run must wait for them, not for an older record.
+struct ReleasedBranch {
+  ojphgpu_encoder* e; bool armed = false;
+  ~ReleasedBranch() { if (armed) (void)hipEventRecord(e->ev_low, e->low); }
 };
 }  // namespace
 
@@ -324,8 +365,10 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
   BlockCoderRun coder{ e, (uint8_t*)(e->o_out ? e->o_out : e->out.p),         // a pipeline slot's buffers, or the object's own
                        (ojphgpu_cb_result*)(e->o_results ? e->o_results : e->results.p),
                        (uint32_t*)(e->o_counters ? e->o_counters : e->counters.p), (uint32_t)e->block_ids.size() * e->nframes, &T };
-  int rc = coder.clear();
+  int rc = coder.clear();                                   // (joins a released run of this object first)
   if (rc) return rc;
+  const bool release = encoder_releases(e);                 // the caller's stream is left behind the last launch that reads the frame
+  ReleasedBranch branch{ e };
   T.start(s);
   if (e->need_convert) {
     const int sp = T.begin(SP_CONVERT, s);
@@ -351,7 +394,10 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     if (rc) return rc;
     T.end(sp, s);
     const bool top_done = b.depth == 0 && (i + 1 == e->batches.size() || e->batches[i + 1].depth != 0);
-    if (!budget && e->n_top && top_done && (rc = coder.fork_top()) != 0) return rc;
+    if (!budget && e->n_top && top_done) {
+      if ((rc = coder.fork_top(release)) != 0) return rc;
+      if (release) { s = e->low; branch.armed = true; }     // nothing behind this point touches the caller's memory
+    }
   }
   if (e->quality_on) {                                      // the search reads the planes in the arena and the caller's frame
     T.finish(s);
@@ -372,8 +418,13 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     e->ran = true; e->fetched = false;
     return OJPHGPU_OK;
   }
-  if ((rc = coder.rest_and_join()) != 0) return rc;
-  T.finish(s);
+  if (release && coder.forked) {
+    if ((rc = coder.rest_released()) != 0) return rc;
+    T.finish_two(s, e->side);
+  } else {
+    if ((rc = coder.rest_and_join()) != 0) return rc;
+    T.finish(s);
+  }
   e->ran = true; e->fetched = false;
   return OJPHGPU_OK;
 }
@@ -385,9 +436,18 @@ extern "C" int ojphgpu_encoder_set_timing(ojphgpu_encoder* e, int per_launch)
   return OJPHGPU_OK;
 }
 
+extern "C" int ojphgpu_encoder_is_pending(const ojphgpu_encoder* e, int* pending)
+{
+  if (!e || !pending) return OJPHGPU_E_INVALID;
+  *pending = e->pending ? 1 : 0;
+  return OJPHGPU_OK;
+}
+
 extern "C" int ojphgpu_encoder_coded_bytes(ojphgpu_encoder* e, uint64_t* bytes)
 {
   if (!e || !bytes || !e->ran) return OJPHGPU_E_INVALID;
+  int rc = encoder_settle(e);                               // (every finish comes through here before it reads a product)
+  if (rc) return rc;
   e->h_cursors.assign(e->counters_bytes / 4, 0);
   HIPCHK(hipMemcpyAsync(e->h_cursors.data(), e->counters.p, e->counters_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -537,6 +597,8 @@ extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* 
 static int encoder_restore_descs(ojphgpu_encoder* e)
 {
   HIPCHK(hipSetDevice(e->device));
+  int rc = encoder_settle(e);
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));
   const std::vector<ojphgpu_cb_desc>& bd = e->rate->bd;
   if (!bd.empty()) HIPCHK(hipMemcpy(e->cb_descs.p, bd.data(), bd.size() * sizeof(bd[0]), hipMemcpyHostToDevice));
@@ -624,6 +686,7 @@ static int encoder_rate_setup(ojphgpu_encoder* e)
         return OJPHGPU_E_INVALID;
       }
     }
+    { const int rc = encoder_settle(e); if (rc) return rc; }   // a released run still codes into the buffers replaced below
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->side) HIPCHK(hipStreamSynchronize(e->side));
     e->scratch.release(); e->out.release(); e->regions.release(); e->counters.release();
@@ -1057,6 +1120,7 @@ extern "C" int ojphgpu_encode16(ojphgpu_encoder* e, const uint16_t* h_image, uin
 extern "C" int ojphgpu_encoder_timing(ojphgpu_encoder* e, float out[4])
 {
   if (!e || !out || !e->ran) return OJPHGPU_E_INVALID;
+  if (encoder_settle(e)) return OJPHGPU_E_HIP;              // (a released run: its total ends with the later of its two branches)
   if (e->timer.read(SP_CONVERT, &out[0]) || e->timer.read(SP_DWT, &out[1]) || e->timer.read(SP_HT_ENC, &out[2]) ||
       e->timer.read(-1, &out[3])) return OJPHGPU_E_HIP;
   return OJPHGPU_OK;
@@ -1065,6 +1129,7 @@ extern "C" int ojphgpu_encoder_timing(ojphgpu_encoder* e, float out[4])
 extern "C" int ojphgpu_encoder_ht_timing(ojphgpu_encoder* e, float* out, uint32_t cap, uint32_t* n, uint32_t* n_top)
 {
   if (!e || !out || !n || !e->ran) return OJPHGPU_E_INVALID;
+  if (encoder_settle(e)) return OJPHGPU_E_HIP;
   int k = e->timer.read_each(SP_HT_ENC, out, cap);
   if (k < 0) return OJPHGPU_E_HIP;
   *n = (uint32_t)k;
@@ -1075,6 +1140,7 @@ extern "C" int ojphgpu_encoder_ht_timing(ojphgpu_encoder* e, float* out, uint32_
 extern "C" int ojphgpu_encoder_level_timing(ojphgpu_encoder* e, float* out, uint32_t cap, uint32_t* n)
 {
   if (!e || !out || !n || !e->ran) return OJPHGPU_E_INVALID;
+  if (encoder_settle(e)) return OJPHGPU_E_HIP;
   int k = e->timer.read_each(SP_DWT, out, cap);
   if (k < 0) return OJPHGPU_E_HIP;
   *n = (uint32_t)k;

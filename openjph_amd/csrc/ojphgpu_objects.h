@@ -406,18 +406,21 @@ struct Spans {
   struct Span { hipEvent_t a, b; int kind; };
   std::vector<Span> pool;            // events are created once and reused
   size_t used = 0;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
+  hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
   bool ok = false;
   bool detail = true;                // per-launch spans on; off = only the wall time of the run (two events)
-  int init() { ok = hipEventCreate(&t0) == hipSuccess && hipEventCreate(&t1) == hipSuccess; return ok ? 0 : -1; }
+  bool two = false;                  // the run ended on two streams (an encoder's released run): t1 and t2, the later one counts
+  int init() { ok = hipEventCreate(&t0) == hipSuccess && hipEventCreate(&t1) == hipSuccess && hipEventCreate(&t2) == hipSuccess; return ok ? 0 : -1; }
   void destroy() {
     for (Span& x : pool) { (void)hipEventDestroy(x.a); (void)hipEventDestroy(x.b); }
     if (t0) (void)hipEventDestroy(t0);
     if (t1) (void)hipEventDestroy(t1);
+    if (t2) (void)hipEventDestroy(t2);
     pool.clear();
   }
-  void start(hipStream_t s) { used = 0; if (ok) (void)hipEventRecord(t0, s); }
+  void start(hipStream_t s) { used = 0; two = false; if (ok) (void)hipEventRecord(t0, s); }
   void finish(hipStream_t s) { if (ok) (void)hipEventRecord(t1, s); }
+  void finish_two(hipStream_t s, hipStream_t other) { finish(s); two = ok; if (ok) (void)hipEventRecord(t2, other); }
   int begin(int kind, hipStream_t s) {
     if (!ok || !detail) return -1;
     if (used == pool.size()) {
@@ -433,7 +436,13 @@ struct Spans {
   // sum of the spans of `kind`; kind < 0: wall time of the run
   int read(int kind, float* out) {
     if (!ok || hipEventSynchronize(t1) != hipSuccess) return -1;
-    if (kind < 0) return hipEventElapsedTime(out, t0, t1) == hipSuccess ? 0 : -1;
+    if (kind < 0) {
+      if (hipEventElapsedTime(out, t0, t1) != hipSuccess) return -1;
+      float other = 0;
+      if (two && (hipEventSynchronize(t2) != hipSuccess || hipEventElapsedTime(&other, t0, t2) != hipSuccess)) return -1;
+      *out = std::max(*out, other);
+      return 0;
+    }
     float sum = 0;
     for (size_t i = 0; i < used; ++i)
       if (pool[i].kind == kind) { float ms = 0; if (hipEventElapsedTime(&ms, pool[i].a, pool[i].b) != hipSuccess) return -1; sum += ms; }
@@ -529,6 +538,17 @@ struct ojphgpu_encoder {
   int widths_top = 0, widths_rest = 0;             // which block encoder kernels each range needs (bit 0 narrow, bit 1 wide, bit 2 reversible, bit 3 irreversible)
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // A released run (include/ojphgpu.h section 5, "what a run leaves"): behind the last launch that reads the caller's frame
+  // nothing of an encode touches the caller's memory, so the rest is issued on streams of the object's own -- the top
+  // resolution's blocks on `side`, levels 2..L and the other blocks on `low` -- and the caller's stream is NOT made to wait
+  // for them at the end of the run: `pending` says that ev_join / ev_low are still to be waited for, and whatever reads or
+  // overwrites the products (out, results, counters, arena, scratch) calls encoder_settle() first.  Only a plain
+  // single-frame run into the object's own buffers with per-launch timing off is released (encoder_releases()).
+  // low / ev_low exist only where can_release holds (encoder_create): an object whose runs always end joined holds the one
+  // side stream it always had, at the caller's priority.
+  hipStream_t low = nullptr;
+  hipEvent_t ev_low = nullptr;
+  bool pending = false, can_release = false;
   // where a run writes its products: the object's own buffers (null), or -- for a frame pipeline that keeps
   // several frames in flight -- the buffers of the frame's slot (ojphgpu_pipe.cpp)
   void* o_out = nullptr; void* o_results = nullptr; void* o_counters = nullptr;
@@ -547,6 +567,24 @@ struct ojphgpu_encoder {
   // the blocks are coded by a search in ojphgpu_encoder_finish*, and Tier-2 writes from the search's plan
   bool searches() const { return !budgets.empty() || quality_on; }
 };
+// May the next run of e be released?  Not one that writes into a frame pipe's slot (the pipe records its own hand-over
+// events behind the run), not a searching one (the search goes on reading the arena on the caller's stream), and not with
+// per-launch timing on (the spans of a run are read as parts of one total).  Frame batches, tile ranges without a side
+// launch, blocks-only encoders, OJPHGPU_NO_OVERLAP=1 and OJPHGPU_ENC_RELEASE=0 never can (can_release).
+inline bool encoder_releases(const ojphgpu_encoder* e)
+{
+  return e->can_release && e->n_top && !e->o_out && !e->o_results && !e->o_counters && !e->searches() && !e->timer.detail;
+}
+// The stream-level join of a released run: e->stream waits for the branches' done events (no host synchronisation).
+// Called before anything is enqueued on e->stream -- or e->stream is synchronised -- to read or overwrite the products.
+inline int encoder_settle(ojphgpu_encoder* e)
+{
+  if (!e->pending) return OJPHGPU_OK;
+  HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+  HIPCHK(hipStreamWaitEvent(e->stream, e->ev_low, 0));
+  e->pending = false;
+  return OJPHGPU_OK;
+}
 // Where one trial of the budget search writes, and how its block lengths reach the host.  h_results != null: d_results is the
 // device address of that mapped pinned memory, the coder's records land in it, the two status words of d_counters are
 // published to d_publish (h_publish on the host) and `done` is recorded behind them and waited for.  Null: the records are
@@ -570,6 +608,8 @@ struct QualityTrialIo {
 int ojphgpu_encoder_quality_trial(ojphgpu_encoder* e, const QualityTrialIo& io, uint32_t j, ojphgpu_frame_err* comps);   // comps[component] = SSE / PAE at j
 // the device part of an encode: d_image holds the frame in `container`-bit elements (32 / 16)
 int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int container);
+// ojphgpu_encoder_create for an owner whose runs never release (a frame pipe): no second stream, the side stream as before
+int ojphgpu_encoder_create_joined(const ojphgpu_plan* plan, int device, void* stream, ojphgpu_encoder** out);
 
 // The plan-order coded-block table of one frame from the block coder's results: res[i] = the frame's block block_ids[i];
 // P = the plan the blocks were quantised with (its bands give K_max); blocks outside block_ids stay empty

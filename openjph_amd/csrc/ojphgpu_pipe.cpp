@@ -640,7 +640,7 @@ extern "C" int ojphgpu_enc_pipe_create(const ojphgpu_plan* plan, int device, uin
     if (container_bits != 32) for (const CompGeo& g : P.comps) if (g.bit_depth > (uint32_t)container_bits) return OJPHGPU_E_INVALID;
     for (hipStream_t* s : { &p->s_h2d, &p->s_comp }) HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
     HIPCHK(create_copy_out_stream(&p->s_d2h));
-    int rc = ojphgpu_encoder_create(plan, device, p->s_comp, &p->enc);
+    int rc = ojphgpu_encoder_create_joined(plan, device, p->s_comp, &p->enc);
     if (rc) return rc;
     (void)ojphgpu_encoder_set_timing(p->enc, 0);
     ojphgpu_encoder* e = p->enc;
