@@ -603,6 +603,18 @@ int ojphgpu_frame_error(void* stream, const void* d_a, const void* d_b, int cont
  * int32 hands over as it is and a narrower container saturates. */
 int ojphgpu_frame_error_ex(void* stream, const void* d_a, int bits_a, const void* d_b, int bits_b, const ojphgpu_error_comp* d_comps,
                            uint32_t n_comps, ojphgpu_frame_err* d_out);
+/* ojphgpu_frame_fit (section 5e builds on it; kernels_fit.hip): an int32 frame as ojphgpu_decoder_run_device leaves it -> the
+ * frame an encoder of another bit depth takes.  Component c = the elements [first_elem, first_elem + count) of both frames;
+ * per sample v' = (v + 2^(shift - 1)) >> shift for shift > 0 (an arithmetic shift, round half up, evaluated in 64 bits),
+ * v << -shift for shift < 0, v for shift == 0, then clamped to [lo, hi] -- what writing the decoded image to a file of the
+ * output's depth and reading it back does (the reference's image writers saturate: src/apps/others/ojph_img_io.cpp:106-230, :1208-1296).
+ * d_dst holds container_bits (8 | 16 | 32)-bit containers: int8 / int16 where lo < 0, else uint8 / uint16; 32-bit containers
+ * hold int32.  d_dst == d_src is allowed at 32 bits (and only there); otherwise the frames do not overlap.  Writes the count
+ * elements of every component and nothing else; a run may start at any element, count may be 0.  |shift| <= 31 and lo <=
+ * hi, or the component is left alone; n_comps at most 65535. */
+typedef struct ojphgpu_fit_comp { uint64_t first_elem, count; int32_t shift, lo, hi; uint32_t reserved; } ojphgpu_fit_comp;
+int ojphgpu_frame_fit(void* stream, const int32_t* d_src, void* d_dst, int container_bits, const ojphgpu_fit_comp* d_comps,
+                      uint32_t n_comps);
 
 /* ------------------------------------------------------------------------------------------ *
  * 5. Whole-frame codec objects: what an ojph::codestream-compatible facade calls from
@@ -644,7 +656,7 @@ int  ojphgpu_encoder_finish_frame(ojphgpu_encoder* enc, uint32_t frame, uint8_t*
  * RELEASED: everything behind the last launch that reads d_image -- the top resolution's blocks, the lower transform
  * levels, the other blocks -- runs on two streams of the object's own and the caller's stream does not wait for it, so
  * the caller's next job on that stream starts beside the block coder.  Every other run (per-launch timing on, which is
- * the default; a byte budget or a quality target; a frame batch; the encoder of a frame pipe or a transcoder;
+ * the default; a byte budget or a quality target; a frame batch; the encoder of a frame pipe, a transcoder or a recoder;
  * OJPHGPU_NO_OVERLAP=1 or OJPHGPU_ENC_RELEASE=0 in the environment at creation) ends joined on the caller's stream.
  * The bytes are the same either way.
  * Stream capture: a joined run is a fork and a join on the caller's stream and can be captured as it is; a released run
@@ -1018,6 +1030,56 @@ int  ojphgpu_transcoder_finish(ojphgpu_transcoder* t, uint8_t* h_out, size_t cap
 int  ojphgpu_transcoder_rate_info(ojphgpu_transcoder* t, ojphgpu_rate_info* info);
 int  ojphgpu_transcoder_timing(ojphgpu_transcoder* t, float out[4]);
 void ojphgpu_transcoder_destroy(ojphgpu_transcoder* t);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 5e. Recoding through the sample domain: what section 5d refuses -- another wavelet or number of decompositions, other
+ *    tiles, another bit depth, a source restricted in resolution or to a region.  It is what ojph_expand followed by
+ *    ojph_compress do through an image file (src/apps/ojph_expand/ojph_expand.cpp, src/apps/ojph_compress/ojph_compress.cpp),
+ *    with the frame staying in HBM.  For a source codestream cs, its view V (the restrictions `src` carries: none,
+ *    ojphgpu_plan_restrict_resolution, ojphgpu_plan_restrict_region, or both) and the output plan `out`:
+ *        F = what ojphgpu_decoder_run_device gives for cs under V (int32; a sample past its nominal range included)
+ *        G = fit(F): per component, with s = source depth - output depth, ojphgpu_frame_fit with shift = s and [lo, hi] =
+ *            the output's nominal range -- [0, 2^Bo - 1], or [-2^(Bo-1), 2^(Bo-1) - 1] for a signed component.  The clamp
+ *            always applies, also at s == 0: it is what the image file in between does (ojph_img_io.cpp:106-230).
+ *        R(cs, V, out) = what an encoder of `out` writes for G, in whatever mode it is in.
+ *    G sits in the narrowest container the encoder takes for `out`: 8-bit when every output depth is at most 8, 16-bit when
+ *    every one is at most 16 (int8 / int16 for signed components, uint8 / uint16 otherwise, as ojphgpu_encoder_run_device8 /
+ *    16 read them), else int32.
+ *
+ *    _create: `src` = a plan of ojphgpu_t2_parse*, restricted or not (it outlives the object, as `out` does).
+ *      OJPHGPU_E_INVALID: a source plan that is not a parsed one, an output plan that is; a component count, or a
+ *      component's width or height (ojphgpu_plan_comp_info of the restricted source against the output's), that differs --
+ *      nothing is resampled here; a component whose signedness changes; a component on the 64-bit sample path on either
+ *      side; a region whose absolute origin (image offset + x0, y0) is not a multiple of XRsiz * 2^skipped_res_for_recon
+ *      horizontally or YRsiz * 2^skipped_res_for_recon vertically for every component (the sizes may coincide, but the
+ *      chroma would be sited half a cell off); and what ojphgpu_decoder_create / ojphgpu_encoder_create refuse.
+ *    _encoder: the encoder half, BORROWED: it takes the setters and infos of sections 5b and 5c -- ojphgpu_encoder_set_budget,
+ *      _set_quality, _set_quality_capped, _clear_quality, _rate_info, _quality_info, _quality_comp, _capped_info, and the
+ *      timing calls -- so that the three modes stay in one place.  ojphgpu_encoder_run_device*, _finish*, _encode* and
+ *      _destroy on it are the recoder's alone.  A quality target is measured against G.  Its runs end joined (section 5).
+ *    _submit: parses the codestream (resilient as in ojphgpu_t2_parse) and restricts it as `src` is restricted, checks it
+ *      against `src` -- another geometry is OJPHGPU_E_INVALID and leaves the object usable --, uploads the bytes of the blocks
+ *      it decodes (the host buffer may go when the call returns) and enqueues the decoder's run into the int32 frame, the fit
+ *      and the encoder's run on G.  G stays the recoder's until _finish has returned.
+ *    _finish: collects the decoder's verdicts first (as ojphgpu_decoder_failed_blocks does; when that repeated the decode,
+ *      the fit and the encoder's run are enqueued again before anything is written); *failed_blocks (may be NULL) = the
+ *      blocks that failed.  A source that was not parsed resiliently with a failed block: OJPHGPU_E_BLOCK, nothing written; a
+ *      resilient one: those blocks are zero, as the decoder leaves them.  Then ojphgpu_encoder_finish (OJPHGPU_E_OVERFLOW:
+ *      *out_len holds the need, call again; OJPHGPU_E_BUDGET and OJPHGPU_E_QUALITY leave the object usable).
+ *    _frame: G of the last submit (device memory of the object's; valid until the next submit) and its container.
+ *    _timing (ms): out[0] the decoder's run, [1] the fit, [2] the encoder's run (device events of the last submit, read
+ *      after a wait for the stream); [3] ojphgpu_encoder_finish (host clock of the last finish: searches included).
+ *    Memory: the two objects' own, one int32 frame, and G where its container is narrower (at 32 bits the int32 frame is
+ *    fitted in place).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ojphgpu_recoder ojphgpu_recoder;
+int  ojphgpu_recoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_recoder** r);
+int  ojphgpu_recoder_encoder(ojphgpu_recoder* r, ojphgpu_encoder** enc);
+int  ojphgpu_recoder_submit(ojphgpu_recoder* r, const uint8_t* h_codestream, size_t len, int resilient);
+int  ojphgpu_recoder_finish(ojphgpu_recoder* r, uint8_t* h_out, size_t cap, size_t* out_len, uint32_t* failed_blocks);
+int  ojphgpu_recoder_frame(ojphgpu_recoder* r, const void** d_frame, int* container_bits);
+int  ojphgpu_recoder_timing(ojphgpu_recoder* r, float out[4]);
+void ojphgpu_recoder_destroy(ojphgpu_recoder* r);
 
 /* ------------------------------------------------------------------------------------------ *
  * 6. Frame pipelines: sequences of frames of one shape with PCIe copies, kernels and host Tier-2 of

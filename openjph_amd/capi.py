@@ -168,6 +168,11 @@ class FrameErr(C.Structure):              # ojphgpu_frame_err
     _fields_ = [("sse", C.c_uint64), ("pae", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FitComp(C.Structure):               # ojphgpu_fit_comp
+    _fields_ = [("first_elem", C.c_uint64), ("count", C.c_uint64), ("shift", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
 class QualityInfo(C.Structure):           # ojphgpu_quality_info
     _fields_ = [("grid_index", C.c_uint32), ("qstep", C.c_float), ("sse", C.c_uint64), ("sse_coarser", C.c_uint64),
                 ("pae", C.c_uint32), ("passes", C.c_uint32), ("bytes", C.c_uint64)]
@@ -440,6 +445,14 @@ SIGNATURES = {
     "ojphgpu_tc_pipe_rate_info": (C.c_int, [C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_tc_pipe_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "ojphgpu_tc_pipe_fused_retries": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ojphgpu_frame_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]),
+    "ojphgpu_recoder_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ojphgpu_recoder_encoder": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ojphgpu_recoder_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    "ojphgpu_recoder_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "ojphgpu_recoder_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "ojphgpu_recoder_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_recoder_destroy": (None, [C.c_void_p]),
     "ojphgpu_version": (C.c_char_p, []),
 }
 

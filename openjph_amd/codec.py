@@ -631,6 +631,157 @@ def transcode(codestream: bytes, device=0, resilient=False, max_bytes=0, **kw) -
     return Transcoder(codestream, device=device, resilient=resilient, max_bytes=max_bytes, **kw).transcode(codestream)
 
 
+class _BorrowedEncoder(Encoder):
+    """The encoder half of a Recoder (ojphgpu_recoder_encoder): the setters and infos of an Encoder over a handle that is
+    the recoder's -- nothing is created, run, finished or destroyed through it."""
+
+    def __init__(self, handle, plan, device):
+        self.device, self.plan, self.frames = device, plan, 1
+        self.tiles = (0, plan.num_tiles)
+        self._lib = capi.lib()
+        self._h = handle
+        self.shape = plan.frame_shape
+        self.max_bytes, self.budgets, self.max_sse, self.cap_bytes, self._frame = 0, None, None, 0, None
+
+    def __del__(self):
+        self._h = None
+
+    def _refuse(self, *a, **k):
+        raise RuntimeError("the encoder half of a Recoder runs and finishes through the Recoder")
+    run_device = finish = finish_tiles = finish_tiles_device = encode = set_budgets = _refuse
+
+
+class _DeviceMemory:
+    """device memory somebody else owns, as torch.as_tensor takes it"""
+
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = dict(shape=(int(nbytes),), typestr="|u1", data=(int(ptr), False), version=2)
+
+
+class Recoder:
+    """A codestream recoded through the sample domain (ojphgpu_recoder; include/ojphgpu.h section 5e): what Transcoder
+    refuses -- another wavelet, other decompositions or tiles, another bit depth, a source at a reduced resolution or
+    through a window.  One object owns a Decoder (under the view), one int32 frame in HBM, the fit to the output's depth
+    and range, and an Encoder with its three rate-control modes; the output is byte for byte what
+    Encoder(out).encode(fit(Decoder(cs, view).run_device())) writes."""
+
+    def __init__(self, codestream: bytes, device=0, resilient=False, skip_res=None, region=None, max_bytes=0, max_sse=None, min_psnr=None,
+                 cap_bytes=0, **kw):
+        """codestream: the first source (parsed for the geometry; every later one must have the same).  skip_res / region:
+        the view, as Decoder takes them.  kw: what changes, as plan.recode_params takes it (bit_depth, bit_depths and every
+        make_params keyword).  max_bytes / max_sse / min_psnr / cap_bytes: as Encoder takes them; a quality target is
+        measured against the fitted frame."""
+        from .plan import recode_params
+        torch = _torch()
+        if cap_bytes and max_sse is None and min_psnr is None:
+            raise ValueError("cap_bytes needs a quality target (max_sse or min_psnr); a byte budget alone is max_bytes")
+        self.device = device
+        self.resilient = bool(resilient)
+        self.src_plan = parse_codestream(codestream, resilient)
+        if skip_res:
+            a, b = (skip_res, skip_res) if isinstance(skip_res, int) else skip_res
+            self.src_plan.restrict_resolution(a, b)
+        if region is not None:
+            self.src_plan.restrict_region(*region)
+        self.params = recode_params(self.src_plan, **kw)
+        self.plan = Plan(self.params)
+        self._lib = capi.lib()
+        self._h = C.c_void_p()
+        with torch.cuda.device(device):
+            check(self._lib.ojphgpu_recoder_create(self.src_plan.handle, self.plan.handle, device, _stream_ptr(torch, device),
+                                                   C.byref(self._h)), "recoder_create")
+        eh = C.c_void_p()
+        check(self._lib.ojphgpu_recoder_encoder(self._h, C.byref(eh)), "recoder_encoder")
+        self.encoder = _BorrowedEncoder(eh, self.plan, device)
+        self.failed_blocks = 0
+        if max_bytes:
+            self.set_budget(max_bytes)
+        if max_sse is not None or min_psnr is not None:
+            self.set_quality(max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes)
+
+    def __del__(self):
+        try:
+            if self._h:
+                self.encoder._h = None
+                self._lib.ojphgpu_recoder_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def set_budget(self, max_bytes):
+        """Encoder.set_budget of the encoder half"""
+        self.encoder.set_budget(max_bytes)
+
+    def set_quality(self, max_sse=None, min_psnr=None, cap_bytes=0):
+        """Encoder.set_quality of the encoder half; the target is measured against the fitted frame"""
+        self.encoder.set_quality(max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes)
+
+    def rate_info(self):
+        return self.encoder.rate_info()
+
+    def quality_info(self):
+        return self.encoder.quality_info()
+
+    def capped_info(self):
+        return self.encoder.capped_info()
+
+    def submit(self, codestream: bytes):
+        """parses and uploads the source and enqueues its decode, the fit and the encoder's run"""
+        buf = np.frombuffer(codestream, dtype=np.uint8)
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_recoder_submit(self._h, buf.ctypes.data, len(codestream), int(self.resilient)), "recoder_submit")
+
+    def finish(self) -> bytes:
+        """the output codestream of the source submitted last; failed_blocks = the source's blocks that did not decode (zero
+        blocks of a resilient recoder; OjphError E_BLOCK otherwise)"""
+        e = self.encoder
+        cap = self.plan.frame_elems * 3 + 64 * self.plan.num_blocks + (1 << 20)
+        if e.max_bytes:
+            cap = min(e.max_bytes, self.plan.frame_elems * 4 + 64 * self.plan.num_blocks + (1 << 20))
+        out = np.empty(cap, np.uint8)
+        n, failed = C.c_size_t(), C.c_uint32()
+        with _torch().cuda.device(self.device):
+            rc = self._lib.ojphgpu_recoder_finish(self._h, out.ctypes.data, cap, C.byref(n), C.byref(failed))
+            if rc == capi.E_OVERFLOW and n.value > cap:
+                cap = int(n.value)
+                out = np.empty(cap, np.uint8)
+                rc = self._lib.ojphgpu_recoder_finish(self._h, out.ctypes.data, cap, C.byref(n), C.byref(failed))
+        self.failed_blocks = int(failed.value)
+        check(rc, "recoder_finish")
+        return out[:n.value].tobytes()
+
+    def recode(self, codestream: bytes) -> bytes:
+        self.submit(codestream)
+        return self.finish()
+
+    def frame(self):
+        """the fitted frame of the last submit, as the encoder half reads it: a torch tensor VIEW of the recoder's memory
+        (plan.frame_shape; int8 / int16 or uint8 / uint16 by the sign of component 0, or int32), valid until the next
+        submit; read it after finish(), which is where a repeated decode lands"""
+        torch = _torch()
+        p, bits = C.c_void_p(), C.c_int()
+        check(self._lib.ojphgpu_recoder_frame(self._h, C.byref(p), C.byref(bits)), "recoder_frame")
+        signed = self.plan.comp_format(0)[1]
+        dt = {8: torch.int8 if signed else torch.uint8, 16: torch.int16 if signed else torch.uint16, 32: torch.int32}[bits.value]
+        raw = torch.as_tensor(_DeviceMemory(p.value, self.plan.frame_elems * (bits.value // 8)), device="cuda:%d" % self.device)
+        return raw.view(dt).reshape(self.plan.frame_shape)
+
+    def timing(self):
+        """ms: dict(decode_ms, fit_ms, encode_ms = the three parts of the last submit (device events), finish_ms = the
+        encoder half's finish, searches included (host clock))"""
+        t = (C.c_float * 4)()
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_recoder_timing(self._h, t), "recoder_timing")
+        return dict(decode_ms=t[0], fit_ms=t[1], encode_ms=t[2], finish_ms=t[3])
+
+
+def recode(codestream: bytes, device=0, resilient=False, skip_res=None, region=None, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0,
+           **kw) -> bytes:
+    """One-shot helper: codestream -> codestream through the sample domain; arguments as Recoder takes them"""
+    return Recoder(codestream, device=device, resilient=resilient, skip_res=skip_res, region=region, max_bytes=max_bytes, max_sse=max_sse,
+                   min_psnr=min_psnr, cap_bytes=cap_bytes, **kw).recode(codestream)
+
+
 def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0, **kw) -> bytes:
     """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes); max_bytes=N: coded to a byte
     budget (Encoder.set_budget); max_sse=N / min_psnr=dB: coded to a quality target (Encoder.set_quality), with cap_bytes=N
@@ -766,6 +917,31 @@ def frame_error(a, b, comps):
     torch.cuda.synchronize(dev)
     r = out.cpu().numpy().view(frame_err_dtype)[:len(comps)]
     return [(int(x["sse"]), int(x["pae"])) for x in r]
+
+
+fit_comp_dtype = np.dtype(capi.FitComp)
+
+
+def frame_fit(src, comps, container_bits, out=None):
+    """ojphgpu_frame_fit: src an int32 device tensor holding a frame, comps = [(first_elem, count, shift, lo, hi), ...] ->
+    the fitted frame in container_bits (8 | 16 | 32)-bit containers, as a uint8 / uint16 / int32 device tensor of src's
+    element count (a signed component's elements are int8 / int16 behind that view).  out: a device tensor of that size to
+    write into -- elements outside the components' runs are left alone; src itself at 32 bits fits in place; None: zeros"""
+    torch = _torch()
+    assert src.is_cuda and src.is_contiguous() and src.dtype == torch.int32
+    dev = src.device.index
+    cd = np.zeros(len(comps), fit_comp_dtype)
+    for i, (first, count, shift, lo, hi) in enumerate(comps):
+        cd[i]["first_elem"], cd[i]["count"], cd[i]["shift"], cd[i]["lo"], cd[i]["hi"] = int(first), int(count), int(shift), int(lo), int(hi)
+    d = to_device(cd, dev)
+    if out is None:
+        out = torch.zeros(src.numel(), dtype={8: torch.uint8, 16: torch.uint16, 32: torch.int32}[int(container_bits)], device=src.device)
+    assert out.is_cuda and out.element_size() * 8 == int(container_bits)
+    with torch.cuda.device(dev):
+        check(capi.lib().ojphgpu_frame_fit(_stream_ptr(torch, dev), C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), int(container_bits),
+                                           C.c_void_p(d.data_ptr()), len(comps)), "frame_fit")
+        torch.cuda.synchronize(dev)
+    return out
 
 
 def dwt_general_image(direction, steps, elem, params: Params, descs: np.ndarray, image, arena, max_w, max_h, K=1.0, container=32):

@@ -2119,3 +2119,204 @@ extern "C" int ojphgpu_transcoder_timing(ojphgpu_transcoder* t, float out[4])
   out[0] = a + b + c + r; out[2] = (float)t->code_ms; out[3] = (float)t->final_ms;
   return OJPHGPU_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// recoding through the sample domain (include/ojphgpu.h section 5e): a decoder and an encoder with one frame between them
+// ---------------------------------------------------------------------------------------------
+extern "C" void ojphgpu_recoder_destroy(ojphgpu_recoder* r)
+{
+  if (!r) return;
+  (void)hipSetDevice(r->device);
+  (void)hipStreamSynchronize(r->stream);
+  if (r->enc) ojphgpu_encoder_destroy(r->enc);              // (both wait for their side streams)
+  if (r->dec) ojphgpu_decoder_destroy(r->dec);
+  for (DeviceBuf* b : { &r->frame, &r->fitted, &r->comps }) b->release();
+  for (hipEvent_t ev : { r->ev_fit0, r->ev_fit1 }) if (ev) (void)hipEventDestroy(ev);
+  delete r;
+}
+
+// may a decoder of S (parsed, under its view) feed an encoder of O through the fit?
+static bool recode_plans_fit(const Plan& S, const Plan& O)
+{
+  if (!S.parsed || S.coded.size() != S.blocks.size() || O.parsed || !O.coded.empty()) return false;
+  if (O.skip_read || O.skip_recon || O.has_region) return false;
+  if (S.any_wide || O.any_wide || S.comps.size() != O.comps.size() || S.comps.empty() || S.frame_elems == 0) return false;
+  for (size_t c = 0; c < S.comps.size(); ++c) {
+    const CompGeo& a = S.comps[c]; const CompGeo& b = O.comps[c];
+    if (a.w != b.w || a.h != b.h || a.is_signed != b.is_signed || a.frame_off != b.frame_off) return false;
+    if (a.bit_depth == 0 || a.bit_depth > 32 || b.bit_depth == 0 || b.bit_depth > 32) return false;
+    if (S.has_region) {                                     // the window starts on a sample of every component
+      const uint64_t fx = (uint64_t)a.dx << S.skip_recon, fy = (uint64_t)a.dy << S.skip_recon;
+      if (((uint64_t)S.p.image_x0 + S.region[0]) % fx != 0 || ((uint64_t)S.p.image_y0 + S.region[1]) % fy != 0) return false;
+    }
+  }
+  return S.frame_elems == O.frame_elems;
+}
+
+extern "C" int ojphgpu_recoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_recoder** rout)
+{
+  if (!src || !out || !rout) return OJPHGPU_E_INVALID;
+  *rout = nullptr;
+  return no_throw([&]() -> int {
+    const Plan& S = src->plan; const Plan& O = out->plan;
+    if (!recode_plans_fit(S, O)) return OJPHGPU_E_INVALID;
+    ojphgpu_recoder* r = new ojphgpu_recoder();
+    struct Owner { ojphgpu_recoder* p; ~Owner() { if (p) ojphgpu_recoder_destroy(p); } } owner{ r };
+    r->S = &S; r->O = &O; r->device = device; r->stream = (hipStream_t)stream;
+    int rc = decoder_create(&src, 1, device, stream, 0, (uint32_t)S.tiles.size(), &r->dec, false);
+    if (rc) return rc;
+    if ((rc = ojphgpu_encoder_create_joined(out, device, stream, &r->enc)) != 0) return rc;
+    ojphgpu_decoder* d = r->dec;
+    // the flat VLC / MEL strings of any later source fit: the worst case of every block (Lcup <= 4079 + slack)
+    const uint64_t worst = (uint64_t)d->block_ids.size() * ojphgpu_ht_decode_aux_words(4079) + 64;
+    d->aux.release();
+    if (d->aux.alloc((size_t)worst * 4 + 64)) return OJPHGPU_E_NOMEM;
+    r->h_descs.resize(d->block_ids.size());
+    uint32_t deepest = 0;
+    std::vector<ojphgpu_fit_comp> fc(S.comps.size());
+    for (size_t c = 0; c < S.comps.size(); ++c) {
+      const CompGeo& a = S.comps[c]; const CompGeo& b = O.comps[c];
+      deepest = std::max(deepest, b.bit_depth);
+      const int64_t lo = b.is_signed ? -((int64_t)1 << (b.bit_depth - 1)) : 0;
+      const int64_t hi = b.is_signed ? ((int64_t)1 << (b.bit_depth - 1)) - 1 : std::min<int64_t>(((int64_t)1 << b.bit_depth) - 1, INT32_MAX);
+      fc[c] = ojphgpu_fit_comp{ a.frame_off, (uint64_t)a.w * a.h, (int32_t)a.bit_depth - (int32_t)b.bit_depth, (int32_t)lo, (int32_t)hi, 0 };
+    }
+    r->container = deepest <= 8 ? 8 : deepest <= 16 ? 16 : 32;
+    r->ncomps = (uint32_t)fc.size();
+    HIPCHK(hipSetDevice(device));
+    if (r->frame.alloc((size_t)S.frame_elems * 4 + 64) || r->comps.alloc(fc.size() * sizeof(fc[0])) ||
+        (r->container != 32 && r->fitted.alloc((size_t)S.frame_elems * (size_t)(r->container / 8) + 64))) return OJPHGPU_E_NOMEM;
+    HIPCHK(hipMemcpy(r->comps.p, fc.data(), fc.size() * sizeof(fc[0]), hipMemcpyHostToDevice));
+    HIPCHK(hipEventCreate(&r->ev_fit0));
+    HIPCHK(hipEventCreate(&r->ev_fit1));
+    owner.p = nullptr;
+    *rout = r;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_recoder_encoder(ojphgpu_recoder* r, ojphgpu_encoder** enc)
+{
+  if (!r || !enc) return OJPHGPU_E_INVALID;
+  *enc = r->enc;
+  return OJPHGPU_OK;
+}
+
+// the fit of the frame the decoder has written, and the encoder's run on it
+static int recoder_fit_and_run(ojphgpu_recoder* r)
+{
+  hipStream_t s = r->stream;
+  HIPCHK(hipEventRecord(r->ev_fit0, s));
+  int rc = ojphgpu_frame_fit(s, (const int32_t*)r->frame.p, r->g(), r->container, (const ojphgpu_fit_comp*)r->comps.p, r->ncomps);
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(r->ev_fit1, s));
+  return ojphgpu_encoder_run_container(r->enc, r->g(), r->container);
+}
+
+extern "C" int ojphgpu_recoder_submit(ojphgpu_recoder* r, const uint8_t* h_codestream, size_t len, int resilient)
+{
+  if (!r || !h_codestream || len == 0) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    ojphgpu_decoder* d = r->dec; ojphgpu_encoder* e = r->enc;
+    const Plan& S = *r->S;
+    hipStream_t s = r->stream;
+    HIPCHK(hipSetDevice(r->device));
+    ojphgpu_plan* q = nullptr;
+    int rc = ojphgpu_t2_parse(h_codestream, len, resilient, &q);
+    if (rc) return rc;
+    struct Hold { ojphgpu_plan* q; ~Hold() { ojphgpu_plan_destroy(q); } } hold{ q };
+    // the view: restricted as `src` was (the refusals of the two calls are a geometry that differs)
+    if ((S.skip_read || S.skip_recon) && ojphgpu_plan_restrict_resolution(q, S.skip_read, S.skip_recon) != 0) return OJPHGPU_E_INVALID;
+    if (S.has_region && ojphgpu_plan_restrict_region(q, S.region[0], S.region[1], S.region[2], S.region[3]) != 0) return OJPHGPU_E_INVALID;
+    const Plan& Q = q->plan;
+    if ((rc = ojphgpu_same_frame_geometry(S, Q, true)) != 0) return rc;
+    // the launches of the last source have read what is replaced now (descriptors on the host and on the device, the bytes),
+    // and a search of the last finish may still hold the frame
+    HIPCHK(hipStreamSynchronize(s));
+    if (d->side) HIPCHK(hipStreamSynchronize(d->side));
+    if (e->side) HIPCHK(hipStreamSynchronize(e->side));
+    const size_t nb = d->block_ids.size();
+    ojphgpu_cb_desc* bd = r->h_descs.data();
+    DecFrameInfo fi;
+    ojphgpu_decoder_fill_descs(S, Q, d->block_ids, 0, 0, bd, fi);
+    uint64_t nquads = 0, naux = 0;
+    if (ojphgpu_ht_decode_layout(bd, (uint32_t)nb, &nquads, &naux) != OJPHGPU_OK) return OJPHGPU_E_INVALID;
+    if ((naux + 16) * 4 > d->aux.n || (nquads + 16) * 4 > d->quads.n) return OJPHGPU_E_INVALID;     // sized for the worst case at create
+    const bool runs = S.has_region;                         // (as the view decoder uploads: ojphgpu_decoder_upload_frame)
+    if (runs) { for (const DecRun& k : fi.runs) if (k.src > len || k.n > len - k.src) return OJPHGPU_E_CODESTREAM; }
+    else if (fi.first + fi.len > len) return OJPHGPU_E_CODESTREAM;
+    r->stage = 0;
+    const size_t need = (size_t)fi.data_bytes() + 128;
+    if (need > d->data.n) {
+      d->data.release();
+      if (d->data.alloc(need + need / 4)) return OJPHGPU_E_NOMEM;
+    }
+    if (runs && fi.len) {                                   // the runs at their places, zeros between them
+      r->h_stage.assign((size_t)fi.len, 0);
+      for (const DecRun& k : fi.runs) memcpy(r->h_stage.data() + k.dst, h_codestream + k.src, (size_t)k.n);
+      HIPCHK(hipMemcpyAsync(d->data.p, r->h_stage.data(), (size_t)fi.len, hipMemcpyHostToDevice, s));
+    } else if (fi.len) HIPCHK(hipMemcpyAsync(d->data.p, h_codestream + fi.first, (size_t)fi.len, hipMemcpyHostToDevice, s));
+    if ((rc = ojphgpu_decoder_upload_pads(s, (uint8_t*)d->data.p, h_codestream, len, fi.pads)) != 0) return rc;
+    if (nb) HIPCHK(hipMemcpyAsync(d->cb_descs.p, bd, nb * sizeof(ojphgpu_cb_desc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));                        // the caller's codestream may go
+    d->any_refine = fi.any_refine; d->kinds = fi.kinds; d->max_len1 = fi.max_len1;
+    rc = ojphgpu_decoder_run_container(d, r->frame.p, 32);
+    if (rc == OJPHGPU_E_UNCOLLECTED) rc = ojphgpu_decoder_run_container(d, r->frame.p, 32);   // (a source submitted and never finished: dropped)
+    if (rc) return rc;
+    if ((rc = recoder_fit_and_run(r)) != 0) return rc;
+    r->resilient = resilient != 0; r->failed = 0; r->final_ms = 0;
+    r->stage = 1;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_recoder_finish(ojphgpu_recoder* r, uint8_t* h_out, size_t cap, size_t* out_len, uint32_t* failed_blocks)
+{
+  if (!r || !out_len || r->stage == 0) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    ojphgpu_decoder* d = r->dec; ojphgpu_encoder* e = r->enc;
+    HIPCHK(hipSetDevice(r->device));
+    int rc;
+    if (r->stage == 1) {
+      // the verdicts first, and the repeat of a one-launch run whose wait ran out: it decodes into the int32 frame again, so
+      // the fit and the encoder's run follow it once more
+      const uint32_t repeats = d->fused_retries;
+      const size_t tail = ((size_t)d->nblocks + 3u) & ~(size_t)3u;
+      PageableStatus f{ d, std::vector<uint8_t>(tail + 4) };
+      rc = ojphgpu_decoder_collect(d, fetch_pageable_status, &f, &r->failed);
+      if (rc) { r->stage = 0; return rc; }
+      if (failed_blocks) *failed_blocks = r->failed;
+      if (r->failed && !r->resilient) { r->stage = 0; return OJPHGPU_E_BLOCK; }
+      if (d->fused_retries != repeats && (rc = recoder_fit_and_run(r)) != 0) { r->stage = 0; return rc; }
+      r->stage = 2;
+    }
+    if (failed_blocks) *failed_blocks = r->failed;
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = ojphgpu_encoder_finish(e, h_out, cap, out_len);
+    r->final_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != OJPHGPU_E_OVERFLOW) r->stage = 0;             // (too small a buffer: *out_len holds the need, the call may be repeated)
+    return rc;
+  });
+}
+
+extern "C" int ojphgpu_recoder_frame(ojphgpu_recoder* r, const void** d_frame, int* container_bits)
+{
+  if (!r || !d_frame || !container_bits || !r->dec->ran) return OJPHGPU_E_INVALID;
+  *d_frame = r->g(); *container_bits = r->container;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_recoder_timing(ojphgpu_recoder* r, float out[4])
+{
+  if (!r || !out || !r->dec->ran || !r->enc->ran) return OJPHGPU_E_INVALID;
+  HIPCHK(hipSetDevice(r->device));
+  HIPCHK(hipStreamSynchronize(r->stream));
+  float t[4];
+  int rc = ojphgpu_decoder_timing(r->dec, t);
+  if (rc) return rc;
+  out[0] = t[3];
+  HIPCHK(hipEventElapsedTime(&out[1], r->ev_fit0, r->ev_fit1));
+  if ((rc = ojphgpu_encoder_timing(r->enc, t)) != 0) return rc;
+  out[2] = t[3]; out[3] = (float)r->final_ms;
+  return OJPHGPU_OK;
+}

@@ -702,6 +702,24 @@ struct ojphgpu_transcoder {
   uint32_t failed = 0;
   double code_ms = 0, final_ms = 0;
 };
+// A recoder (section 5e): a whole decoder of the source plan -- under its view, if it has one -- and a whole encoder of the
+// output plan, with one int32 frame and the fit between them.  Both halves are the objects anybody else gets; what the
+// recoder adds is that a later source's descriptors replace the first one's in the decoder (as a decoder pipe's slots do).
+struct ojphgpu_recoder {
+  ojphgpu_decoder* dec = nullptr; ojphgpu_encoder* enc = nullptr;
+  const Plan* S = nullptr; const Plan* O = nullptr;
+  int device = 0; hipStream_t stream = nullptr;
+  DeviceBuf frame, fitted, comps;                  // F (int32; at 32 bits also G, fitted in place), G in a narrower container, the fit's components
+  int container = 32; uint32_t ncomps = 0;
+  std::vector<ojphgpu_cb_desc> h_descs;            // this source's block descriptors
+  std::vector<uint8_t> h_stage;                    // a view's runs, gathered for one copy
+  hipEvent_t ev_fit0 = nullptr, ev_fit1 = nullptr;
+  int stage = 0;                                   // 0 idle, 1 submitted, 2 collected (a finish may be repeated)
+  bool resilient = false;
+  uint32_t failed = 0;
+  double final_ms = 0;
+  void* g() const { return container == 32 ? frame.p : fitted.p; }
+};
 struct DecFrameInfo;
 // How the status bytes of a run (+ the RETRY word behind them) reach the host for whoever collects its verdicts: called once
 // the run is enqueued, returns with them readable at *h_status

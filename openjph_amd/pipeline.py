@@ -314,6 +314,33 @@ def unpack_video444(buf, fmt, width, height, bit_depth=None):
     return [np.ascontiguousarray(f[:, :, i].astype(np.uint16)) for i in _VIDEO444_BYTES[code][:3]]
 
 
+def fit_container(out_depths):
+    """the narrowest container an encoder takes for components of these depths: 8, 16 or 32 bits"""
+    deepest = max(int(b) for b in out_depths)
+    return 8 if deepest <= 8 else 16 if deepest <= 16 else 32
+
+
+def fit_frame(planes, src_depths, out_depths, signs):
+    """numpy statement of the recoder's fit (ojphgpu_frame_fit as codec.Recoder uses it; include/ojphgpu.h section 5e): the
+    decoded planes of a source (any integer arrays; a sample may lie past its nominal range) -> the planes an encoder of the
+    output depths takes.  Per component, s = source depth - output depth: (v + 2^(s - 1)) >> s for s > 0 (an arithmetic
+    shift, round half up, in 64 bits), v << -s for s < 0, then the clamp to the output's nominal range -- always, also at
+    s == 0.  Every plane comes back in the narrowest container the encoder takes for all of them (fit_container): int8 /
+    int16 for a signed component, uint8 / uint16 otherwise, or int32."""
+    bits = fit_container(out_depths)
+    out = []
+    for q, bs, bo, sg in zip(planes, src_depths, out_depths, signs):
+        v, s, bo = np.asarray(q).astype(np.int64), int(bs) - int(bo), int(bo)
+        if s > 0:
+            v = (v + (1 << (s - 1))) >> s
+        elif s < 0:
+            v = v << -s
+        lo, hi = (-(1 << (bo - 1)), (1 << (bo - 1)) - 1) if sg else (0, (1 << bo) - 1)
+        dt = np.int32 if bits == 32 else np.dtype("%s%d" % ("i" if sg else "u", bits // 8))
+        out.append(np.clip(v, lo, min(hi, 2 ** 31 - 1)).astype(dt))
+    return out
+
+
 class EncoderPipe(_Handover):
     _side = "enc"
 

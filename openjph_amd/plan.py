@@ -498,6 +498,66 @@ def transcode_plan(src_plan: Plan, params) -> Plan:
     return Plan(handle=h)
 
 
+# make_params keyword -> the fields of ojphgpu_params it fills ((name, index): one element of an array field)
+_PARAM_FIELDS = {
+    "bit_depth": ["bit_depth"], "bit_depths": ["comp_depth"], "is_signed": ["is_signed"], "signs": ["comp_sign"],
+    "reversible": ["reversible"], "num_decomps": ["num_decomps"], "block": ["block_w", "block_h"],
+    "color_transform": ["color_transform"], "tile": ["tile_w", "tile_h"], "prog_order": ["prog_order"], "qstep": ["qstep"],
+    "precinct": ["precinct_w", "precinct_h"], "precincts": ["precinct_exps"], "tlm": ["tlm"], "tileparts": [("reserved", 1)],
+    "qfactor": [("reserved", 2)], "image_offset": ["image_x0", "image_y0"], "tile_offset": ["tile_x0", "tile_y0"],
+    "downsampling": ["comp_dx", "comp_dy"], "coc": ["coc"], "nlt": ["nlt_default", "nlt_comp", "nlt_rank"],
+    "qfactors": ["qcc_qfactor", "qcc_ctype", "qcc_rank"], "atk": ["atk"], "dfs": ["dfs"], "wavelet": ["wavelet"],
+}
+
+
+def recode_params(src_plan: Plan, bit_depth=None, bit_depths=None, **kw):
+    """The parameters of a recode's output (codec.Recoder; include/ojphgpu.h section 5e): those of the parsed `src_plan`
+    -- under a view (restrict_resolution, restrict_region) the view's size on a grid of its own: image and tile offsets
+    zero, one tile, the source's decompositions minus the skipped resolutions -- with every make_params keyword given
+    overriding what it sets (reversible, qstep, num_decomps, tile, block, prog_order, ...).  bit_depth=N: every component
+    N bits deep; bit_depths=[...]: per component.  What only a parser sets (vertically causal blocks, BDnlt) is dropped:
+    the result is a writer's."""
+    p = Params.from_buffer_copy(src_plan.params)
+    p.reserved[0] = 0
+    p.nlt_bd_default = 0
+    for i in range(len(p.nlt_bd)):
+        p.nlt_bd[i] = 0
+    for i in range(len(p.nlt_reserved)):
+        p.nlt_reserved[i] = 0
+    skip = int(src_plan.skip[1])
+    if skip or src_plan.region is not None:
+        a0x, a0y = int(p.image_x0), int(p.image_y0)
+        a1x, a1y = a0x + int(p.width), a0y + int(p.height)
+        if src_plan.region is not None:
+            x0, y0, w, h = src_plan.region
+            a0x, a0y, a1x, a1y = a0x + x0, a0y + y0, a0x + x0 + w, a0y + y0 + h
+        up = lambda v: -((-v) >> skip)                      # ceil(v / 2^skip)
+        p.width, p.height = up(a1x) - up(a0x), up(a1y) - up(a0y)
+        p.image_x0 = p.image_y0 = p.tile_x0 = p.tile_y0 = 0
+        p.tile_w = p.tile_h = 0
+        p.num_decomps = int(p.num_decomps) - skip
+        for c in range(len(p.coc)):
+            if p.coc[c].rank and not p.coc[c].reserved[0] & 0x80:
+                p.coc[c].num_decomps = int(p.coc[c].num_decomps) - skip
+    if bit_depth is not None:
+        kw["bit_depth"] = int(bit_depth)
+        kw.setdefault("bit_depths", [0] * 16)
+    if bit_depths is not None:
+        kw["bit_depths"] = [int(b) for b in bit_depths]
+    unknown = set(kw) - set(_PARAM_FIELDS)
+    if unknown:
+        raise TypeError("recode_params: not a make_params keyword: %s" % ", ".join(sorted(unknown)))
+    kw.setdefault("num_decomps", int(p.num_decomps))        # (make_params sizes the precinct list by it)
+    o = make_params(int(p.width), int(p.height), int(p.num_comps), **kw)
+    for k in kw:
+        for f in _PARAM_FIELDS[k]:
+            if isinstance(f, tuple):
+                getattr(p, f[0])[f[1]] = getattr(o, f[0])[f[1]]
+            else:
+                setattr(p, f, getattr(o, f))
+    return p
+
+
 def parse_codestream(data: bytes, resilient=False, skip=None) -> Plan:
     """skip = (skipped_res_for_data, skipped_res_for_recon): restrict_input_resolution BEFORE the tile-parts are read, as the
     reference orders it (ojphgpu_t2_parse_restricted) -- on undamaged codestreams the same as Plan.restrict_resolution afterwards"""
