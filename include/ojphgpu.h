@@ -1445,6 +1445,20 @@ int  ojphgpu_video_format_info(int format, ojphgpu_video_info* out);   /* host o
  * run that reaches beyond it is the caller's mistake: those bytes come out unspecified).  staged_len == 0: no launch. */
 int  ojphgpu_gather_runs(void* stream, const void* d_src, size_t src_cap, const ojphgpu_run* d_runs, uint32_t n, void* d_dst,
                          uint64_t staged_len);
+/* Codestream assembly as a stage (kernels_assemble.hip, assemble_codestream): job i copies n bytes from d_blob + src (blob
+ * != 0) or d_data + src (blob == 0) to d_out + dst, one wavefront per job; source and destination are byte-aligned
+ * arbitrarily.  The n bytes at dst are written and nothing else.  The kernel reads whole aligned dwords: up to 3 bytes in
+ * front of a job's first byte and up to 3 behind its last, inside the dwords that hold them, so a source buffer ends on a
+ * dword boundary (hipMalloc's alignment with a size that is a multiple of 4).  d_jobs: the table in device memory.  n_jobs ==
+ * 0: no launch.  OJPHGPU_E_INVALID: a null d_jobs, d_blob or d_out.  Nothing is range-checked: the jobs are the caller's. */
+typedef struct ojphgpu_t2_job { uint64_t dst, src; uint32_t n, blob; } ojphgpu_t2_job;
+int  ojphgpu_assemble(void* stream, const ojphgpu_t2_job* d_jobs, uint32_t n_jobs, const uint8_t* d_blob, const uint8_t* d_data,
+                      uint8_t* d_out);
+/* The copy kernel of the pipes as a stage (copy_to_host_kernel): `bytes` bytes from d_src (device memory) to d_dst (the
+ * device address of pinned host memory, or device memory), both 16-byte aligned (otherwise OJPHGPU_E_INVALID).  Exactly
+ * [0, bytes) of d_dst is written.  bytes == 0: no launch.  OJPHGPU_COPY_WGS (read once per process) sets the workgroups of
+ * this kernel and of ojphgpu_gather_runs. */
+int  ojphgpu_copy_to_host(void* stream, void* d_dst, const void* d_src, size_t bytes);
 
 const char* ojphgpu_version(void);
 

@@ -196,7 +196,11 @@ class Run(C.Structure):                   # ojphgpu_run
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("n", C.c_uint64)]
 
 
-class VideoInfo(C.Structure):             # ojphgpu_video_info
+class T2Job(C.Structure):                 # ojphgpu_t2_job
+    _fields_ = [("dst", C.c_uint64), ("src", C.c_uint64), ("n", C.c_uint32), ("blob", C.c_uint32)]
+
+
+class VideoInfo(C.Structure):            # ojphgpu_video_info
     _fields_ = [("family", C.c_int), ("sub_x", C.c_uint32), ("sub_y", C.c_uint32), ("min_depth", C.c_uint32), ("max_depth", C.c_uint32),
                 ("min_container_bits", C.c_uint32), ("pointer_align", C.c_uint32), ("pitch_align", C.c_uint32)]
 
@@ -419,6 +423,8 @@ SIGNATURES = {
     "ojphgpu_transcoder_destroy": (None, [C.c_void_p]),
     "ojphgpu_plan_upload_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "ojphgpu_gather_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ojphgpu_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ojphgpu_copy_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ojphgpu_dec_pipe_create_view": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.c_uint32,
                                                C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ojphgpu_dec_pipe_view_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -1159,21 +1159,116 @@ def ht_decode_fused(descs: np.ndarray, data: np.ndarray, coef, scratch: FusedScr
     return st[:n].copy(), int(st[r:r + 4].view(np.uint32)[0]), epoch
 
 
-def unpack_pixels(pixels, num_comps=None, big_endian=False, dtype=None):
+def unpack_pixels(pixels, num_comps=None, big_endian=False, dtype=None, out=None):
     """pixel-interleaved samples on the device ([H,W,C] uint8 / uint16 tensor -- for big-endian 16-bit data the tensor
     holds the file's bytes as they are) -> planes [C,H,W] in `dtype` (uint8 / int16 / uint16 / int32; default: as the
-    input).  ojphgpu_unpack_pixels: what the reference's image readers do sample by sample on the host."""
+    input), or in `out` (contiguous, at least C * H * W elements, of which the first C * H * W are written; its dtype is the
+    container).  ojphgpu_unpack_pixels: what the reference's image readers do sample by sample on the host."""
     torch = _torch()
     assert pixels.is_cuda and pixels.is_contiguous() and pixels.dim() == 3
     h, w, c = pixels.shape
     bits = pixels.element_size() * 8
     assert bits in (8, 16)
-    out_dt = dtype if dtype is not None else (torch.uint8 if bits == 8 else torch.int16)
-    out = torch.empty((c, h, w), dtype=out_dt, device=pixels.device)
+    if out is None:
+        out = torch.empty((c, h, w), dtype=dtype if dtype is not None else (torch.uint8 if bits == 8 else torch.int16), device=pixels.device)
+    assert out.is_cuda and out.is_contiguous() and out.device == pixels.device and out.numel() >= c * h * w
     check(capi.lib().ojphgpu_unpack_pixels(_stream_ptr(torch, pixels.device.index or 0), C.c_void_p(pixels.data_ptr()),
                                            C.c_void_p(out.data_ptr()), w, h, c, bits, int(bool(big_endian)), out.element_size() * 8),
           "unpack_pixels")
+    return out.reshape(-1)[:c * h * w].reshape(c, h, w)
+
+
+def _bits_bytes(n, bits):
+    """the bytes of a bit string of n samples: whole groups of 32 samples"""
+    return (int(n) + 31) // 32 * 4 * int(bits)
+
+
+def unpack_bits(d_packed, bits, n, dtype=None, out=None):
+    """a bit string on the device (pipeline.pack_bits' layout: n samples of `bits` = 10 | 12 | 14 bits, padded to whole groups
+    of 32 samples; a contiguous tensor whose first byte is 4-byte aligned) -> the n samples in `dtype` (int16 / uint16 /
+    int32; default int16), or in `out` (contiguous, at least n elements, of which the first n are written; its dtype is the
+    container).  ojphgpu_unpack_bits."""
+    torch = _torch()
+    n, bits = int(n), int(bits)
+    assert d_packed.is_cuda and d_packed.is_contiguous()
+    if out is None:
+        out = torch.empty(max(n, 1), dtype=dtype if dtype is not None else torch.int16, device=d_packed.device)
+    assert out.is_cuda and out.is_contiguous() and out.device == d_packed.device and out.numel() >= n
+    if bits in (10, 12, 14):                              # (any other width: the library refuses it)
+        assert d_packed.numel() * d_packed.element_size() >= _bits_bytes(n, bits), "unpack_bits: the bit string is shorter than its groups"
+    check(capi.lib().ojphgpu_unpack_bits(_stream_ptr(torch, d_packed.device.index or 0), C.c_void_p(d_packed.data_ptr()),
+                                         C.c_void_p(out.data_ptr()), n, bits, out.element_size() * 8), "unpack_bits")
+    return out.reshape(-1)[:n]
+
+
+def pack_bits(d_samples, bits, out=None):
+    """the way back: samples on the device (a contiguous int16 / uint16 / int32 tensor, flattened) -> the bit string as a uint8
+    tensor of whole groups of 32 samples, every sample clamped to [0, 2^bits - 1], the padding samples of the last group zero;
+    `out`: a contiguous uint8 tensor of at least that many bytes, 4-byte aligned (bytes behind the groups are left alone).
+    ojphgpu_pack_bits."""
+    torch = _torch()
+    bits = int(bits)
+    assert d_samples.is_cuda and d_samples.is_contiguous()
+    n = d_samples.numel()
+    nbytes = _bits_bytes(n, bits)
+    if out is None:
+        out = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=d_samples.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.device == d_samples.device
+    if bits in (10, 12, 14):
+        assert out.numel() >= nbytes, "pack_bits: the destination is shorter than the groups"
+    check(capi.lib().ojphgpu_pack_bits(_stream_ptr(torch, d_samples.device.index or 0), C.c_void_p(d_samples.data_ptr()),
+                                       C.c_void_p(out.data_ptr()), n, d_samples.element_size() * 8, bits), "pack_bits")
+    return out.reshape(-1)[:nbytes]
+
+
+t2_job_dtype = np.dtype(capi.T2Job)
+
+
+def assemble(jobs, blob, data, out):
+    """codestream assembly as a stage (ojphgpu_assemble): jobs = t2_job_dtype array (host) -- job i copies n bytes from blob
+    (blob != 0) or data (blob == 0) at src to out at dst; blob, data, out: contiguous uint8 tensors on one device, blob and data
+    of a multiple of 4 bytes (the kernel reads the aligned dwords around a job's ends).  Every job is checked against the
+    tensors here, on the host: one that leaves them raises ValueError and nothing is launched.  Returns out."""
+    torch = _torch()
+    jobs = np.ascontiguousarray(jobs, dtype=t2_job_dtype)
+    for name, t in (("blob", blob), ("data", data), ("out", out)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8 and t.device == out.device):
+            raise ValueError("assemble: %s is not a contiguous uint8 tensor on the destination's device" % name)
+    for name, t in (("blob", blob), ("data", data)):
+        if t.numel() == 0 or t.numel() % 4 or t.data_ptr() % 4:
+            raise ValueError("assemble: %s is not a whole number of aligned dwords" % name)
+    if (jobs["src"] >= 1 << 62).any() or (jobs["dst"] >= 1 << 62).any():
+        raise ValueError("assemble: a job's offset is beyond any tensor")
+    n, src, dst = (jobs[k].astype(np.int64) for k in ("n", "src", "dst"))
+    if (src + n > np.where(jobs["blob"] != 0, blob.numel(), data.numel())).any():
+        raise ValueError("assemble: a job reads beyond its source")
+    if (dst + n > out.numel()).any():
+        raise ValueError("assemble: a job writes beyond the destination")
+    dev = out.device.index or 0
+    d_jobs = to_device(jobs, dev)
+    with torch.cuda.device(dev):
+        check(capi.lib().ojphgpu_assemble(_stream_ptr(torch, dev), C.c_void_p(d_jobs.data_ptr()), int(jobs.size), C.c_void_p(blob.data_ptr()),
+                                          C.c_void_p(data.data_ptr()), C.c_void_p(out.data_ptr())), "assemble")
+        torch.cuda.synchronize(dev)       # (d_jobs may go away after this call)
     return out
+
+
+def copy_to_host(dst, src, nbytes):
+    """the pipes' copy kernel as a stage (ojphgpu_copy_to_host): nbytes bytes from src to dst, contiguous tensors on one device
+    whose first bytes are 16-byte aligned (otherwise the library refuses: E_INVALID).  A byte count beyond either tensor raises
+    ValueError and nothing is launched.  Returns dst."""
+    torch = _torch()
+    nbytes = int(nbytes)
+    for name, t in (("dst", dst), ("src", src)):
+        if not (t.is_cuda and t.is_contiguous() and t.device == dst.device):
+            raise ValueError("copy_to_host: %s is not a contiguous tensor on the destination's device" % name)
+        if nbytes < 0 or nbytes > t.numel() * t.element_size():
+            raise ValueError("copy_to_host: %d bytes are more than %s holds" % (nbytes, name))
+    dev = dst.device.index or 0
+    with torch.cuda.device(dev):
+        check(capi.lib().ojphgpu_copy_to_host(_stream_ptr(torch, dev), C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), nbytes), "copy_to_host")
+        torch.cuda.synchronize(dev)
+    return dst
 
 
 def _video_args(family, fmt, width, height, bit_depth):
@@ -1327,16 +1422,20 @@ def pack_video444(d_planes, fmt, width, height, bit_depth=None, out=None, pitch=
     return out.reshape(-1)[:row * h].reshape(h, row) if pitch is None else out
 
 
-def pack_pixels(planes, bit_depth, pixel_bits=None, big_endian=False):
+def pack_pixels(planes, bit_depth, pixel_bits=None, big_endian=False, out=None):
     """planes [C,H,W] on the device -> pixel-interleaved [H,W,C] (uint8 for pixel_bits 8, else int16 holding the bytes
-    of uint16 samples, byte-swapped when big_endian), clamped to [0, 2^bit_depth - 1] as the reference's writers do."""
+    of uint16 samples, byte-swapped when big_endian), clamped to [0, 2^bit_depth - 1] as the reference's writers do.
+    `out`: a contiguous tensor of pixel_bits-bit elements, at least H * W * C of them, of which the first H * W * C are
+    written."""
     torch = _torch()
     assert planes.is_cuda and planes.is_contiguous() and planes.dim() == 3
     c, h, w = planes.shape
     pb = int(pixel_bits) if pixel_bits else (8 if bit_depth <= 8 else 16)
-    out = torch.empty((h, w, c), dtype=torch.uint8 if pb == 8 else torch.int16, device=planes.device)
+    if out is None:
+        out = torch.empty((h, w, c), dtype=torch.uint8 if pb == 8 else torch.int16, device=planes.device)
+    assert out.is_cuda and out.is_contiguous() and out.device == planes.device and out.element_size() * 8 == pb and out.numel() >= c * h * w
     check(capi.lib().ojphgpu_pack_pixels(_stream_ptr(torch, planes.device.index or 0), C.c_void_p(planes.data_ptr()),
                                          C.c_void_p(out.data_ptr()), w, h, c, planes.element_size() * 8, pb, int(bool(big_endian)),
                                          int(bit_depth)), "pack_pixels")
-    return out
+    return out.reshape(-1)[:c * h * w].reshape(h, w, c)
 

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 
 #include "ojph_plan.h"
@@ -252,4 +253,18 @@ static_assert(sizeof(ojphgpu_run) == sizeof(GatherRun), "ojphgpu_run is the kern
 extern "C" int ojphgpu_gather_runs(void* stream, const void* d_src, size_t src_cap, const ojphgpu_run* d_runs, uint32_t n, void* d_dst, uint64_t staged_len)
 {
   return ojphgpu::gather_runs_launch(stream, d_src, src_cap, d_runs, n, d_dst, staged_len);
+}
+
+static_assert(sizeof(ojphgpu_t2_job) == sizeof(ojphgpu::T2Job) && offsetof(ojphgpu_t2_job, dst) == offsetof(ojphgpu::T2Job, dst) &&
+              offsetof(ojphgpu_t2_job, src) == offsetof(ojphgpu::T2Job, src) && offsetof(ojphgpu_t2_job, n) == offsetof(ojphgpu::T2Job, n) &&
+              offsetof(ojphgpu_t2_job, blob) == offsetof(ojphgpu::T2Job, blob), "ojphgpu_t2_job is the kernel's placement job");
+
+extern "C" int ojphgpu_assemble(void* stream, const ojphgpu_t2_job* d_jobs, uint32_t n_jobs, const uint8_t* d_blob, const uint8_t* d_data, uint8_t* d_out)
+{
+  return ojphgpu::assemble_launch(stream, reinterpret_cast<const ojphgpu::T2Job*>(d_jobs), n_jobs, d_blob, d_data, d_out);
+}
+
+extern "C" int ojphgpu_copy_to_host(void* stream, void* d_dst, const void* d_src, size_t bytes)
+{
+  return ojphgpu::copy_to_host_launch(stream, d_dst, d_src, bytes);
 }

@@ -121,6 +121,141 @@ def test_convert_kernels_every_format(container):
             bd, sg, rev, nl, wide, container, int((g != wants[i]).sum()))
 
 
+GEOMETRY_TILES = [[(513, 5), (256, 2), (1, 1)], [(257, 2), (255, 5), (513, 1)]]          # (w, h) of the three tiles of a launch
+
+
+def _window(buf, off, pitch, h, w):
+    return np.lib.stride_tricks.as_strided(buf[off:], (h, w), (pitch * buf.itemsize, buf.itemsize))
+
+
+def _geometry_launch(container, colour, rev, tiles, rng):
+    """one forward and one inverse launch over three tiles of different sizes, each a window (src_x0, src_y0 > 0, img_pitch >
+    w) of a larger image, arena pitches wider than the planes.  Colour off: component 0 full size, component 1 half as wide,
+    component 2 with w = 0.  Colour on: a triple of one geometry with three formats (one signed) and a fourth, plain
+    component half as wide behind it.  The whole arena (forward) and the whole image (inverse) are compared: planes and
+    windows with the restatement, every other element with what it held."""
+    from openjph_amd import codec
+    deep = (8, 7, 6) if container == 8 else (8, 10, 12)
+    fmts = [(deep[0], False), (deep[1], True), (deep[2], False)] + ([(min(container, 11), False)] if colour else [])
+    nc, nt = len(fmts), len(tiles)
+
+    def width(c, w):
+        return (w if c < 3 else (w + 1) // 2) if colour else (w, (w + 1) // 2, 0)[c]
+    descs = np.zeros(nt * nc, codec.convert_desc_dtype)
+    rows = max(1 + t + h for t, (w, h) in enumerate(tiles)) + 1
+    img_len = 5
+    for c, (bd, sg) in enumerate(fmts):
+        pitch, x0 = 2 + sum(width(c, w) + 3 for w, h in tiles), 2
+        for t, (w, h) in enumerate(tiles):
+            d = descs[t * nc + c]
+            d["w"], d["h"], d["src_x0"], d["src_y0"], d["img_pitch"], d["img_off"] = width(c, w), h, x0, 1 + t, pitch, img_len
+            d["fmt"] = bd | (0x100 if sg else 0) | 0x200 | (0x400 if rev else 0)
+            x0 += width(c, w) + 3
+        img_len += pitch * rows + 7
+    arena_len = 9
+    for d in descs:
+        d["pitch"], d["plane_off"] = int(d["w"]) + 5, arena_len
+        arena_len += (int(d["w"]) + 5) * int(d["h"]) + 16
+    assert all(d["src_x0"] > 0 and d["src_y0"] > 0 and d["img_pitch"] > d["w"] and d["pitch"] > d["w"] for d in descs)
+    max_w, max_h = max(w for w, h in tiles), max(h for w, h in tiles)
+    params = _params(num_comps=nc, bit_depth=8, reversible=rev, color_transform=colour)
+    cdt = {32: np.int32, 16: np.int16, 8: np.int8}[container]
+    tdt = {32: torch.int32, 16: torch.int16, 8: torch.int8}[container]
+    tag = "container %d colour %s rev %s tiles %s" % (container, colour, rev, tiles)
+
+    def image_window(buf, d):
+        return _window(buf, int(d["img_off"]) + int(d["src_y0"]) * int(d["img_pitch"]) + int(d["src_x0"]), int(d["img_pitch"]), int(d["h"]), int(d["w"]))
+
+    def plane(buf, d):
+        return _window(buf, int(d["plane_off"]), int(d["pitch"]), int(d["h"]), int(d["w"]))
+
+    # forward: image -> arena
+    image = rng.integers(-128, 128, img_len).astype(cdt)
+    arena0 = rng.integers(0, 1 << 32, arena_len, dtype=np.uint64).astype(np.uint32)
+    want = arena0.copy()
+    for t in range(nt):
+        vals = []
+        for c, (bd, sg) in enumerate(fmts):
+            d = descs[t * nc + c]
+            n = int(d["w"]) * int(d["h"])
+            vals.append(rs.edge_samples(bd, sg, rng, n)[:n].reshape(int(d["h"]), int(d["w"])))
+            image_window(image, d)[...] = _to_container(vals[c], container)
+        first = 0
+        if colour:
+            first = 3
+            if rev:
+                out = [rs.wrap32(x).view(np.uint32) for x in rs.rct_forward(*[rs.rev_forward(vals[c], *fmts[c]) for c in range(3)])]
+            else:
+                out = [x.view(np.uint32) for x in rs.ict_forward(*[rs.irv_to_float(vals[c], *fmts[c]) for c in range(3)])]
+            for c in range(3):
+                plane(want, descs[t * nc + c])[...] = out[c]
+        for c in range(first, nc):
+            d = descs[t * nc + c]
+            if d["w"]:
+                plane(want, d)[...] = _conv_forward_want(vals[c].ravel(), fmts[c][0], fmts[c][1], rev, False, False).reshape(vals[c].shape)
+    arena = torch.from_numpy(arena0.view(np.int32)).cuda()
+    codec.convert("forward", params, descs, torch.from_numpy(image).cuda(), arena, max_w, max_h, container)
+    got = arena.cpu().numpy().view(np.uint32)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "forward %s: %d arena words differ, the first at %d" % (tag, bad.size, bad[0])
+    # inverse: arena -> image, from working samples in and beyond the range
+    words = rng.integers(0, 1 << 32, arena_len, dtype=np.uint64).astype(np.uint32)
+    image0 = rng.integers(-128, 128, img_len).astype(cdt)
+    want = image0.copy()
+    for t in range(nt):
+        src = []
+        for c, (bd, sg) in enumerate(fmts):
+            d = descs[t * nc + c]
+            n = int(d["w"]) * int(d["h"])
+            lo = -(1 << (bd - 1))
+            a = rs.wrap32(rng.integers(2 * lo - 5, -2 * lo + 5, n, dtype=np.int64)).view(np.uint32) if rev else rs.edge_floats(bd, rng, n)[:n].astype(np.float32).view(np.uint32)
+            src.append(a.reshape(int(d["h"]), int(d["w"])))
+            plane(words, d)[...] = src[c]
+        first = 0
+        if colour:
+            first = 3
+            if rev:
+                rgb = rs.rct_inverse(*[x.view(np.int32) for x in src[:3]])
+                out = [rs.wrap32(rgb[c] + rs.half(*fmts[c])).astype(np.int64) for c in range(3)]
+            else:
+                rgb = rs.ict_inverse(*[x.view(np.float32) for x in src[:3]])
+                out = [rs.irv_to_int(rgb[c], *fmts[c]).astype(np.int64) for c in range(3)]
+            for c in range(3):
+                image_window(want, descs[t * nc + c])[...] = _to_container(rs.saturate(out[c], container, fmts[c][1]), container)
+        for c in range(first, nc):
+            d = descs[t * nc + c]
+            if d["w"]:
+                v = _conv_inverse_want(src[c].ravel(), fmts[c][0], fmts[c][1], rev, False, False, container).reshape(src[c].shape)
+                image_window(want, d)[...] = _to_container(v, container)
+    out = torch.from_numpy(image0).cuda()
+    assert out.dtype == tdt
+    codec.convert("inverse", params, descs, out, torch.from_numpy(words.view(np.int32)).cuda(), max_w, max_h, container)
+    got = out.cpu().numpy()
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "inverse %s: %d image samples differ, the first at %d" % (tag, bad.size, bad[0])
+    return {(d["w"] > 0, int(d["w"]) < max_w) for d in descs}
+
+
+@pytest.mark.parametrize("container", [32, 16, 8])
+def test_convert_kernels_geometry(container):
+    """the stand-alone conversion kernels beyond one tile at the origin: blockIdx.z tiles of different sizes, window offsets,
+    components narrower than the launch and one that is empty, rows wider than one 256-thread workgroup, the colour branches
+    with mixed formats inside the triple and a component behind it -- both kinds, both directions.  (The 64-bit RCT stays with
+    the whole codestreams of tests/format_cases.py.)"""
+    rng = np.random.default_rng(40 + container)
+    ran, widths, heights, shapes = set(), set(), set(), set()
+    for i, (colour, rev) in enumerate([(False, True), (True, False), (True, True), (False, False)]):
+        for tiles in (GEOMETRY_TILES[i % 2], GEOMETRY_TILES[1 - i % 2][::-1]):
+            shapes |= _geometry_launch(container, colour, rev, tiles, rng)
+            ran.add((colour, rev))
+            widths |= {w for w, h in tiles}
+            heights |= {h for w, h in tiles}
+            assert len(set(tiles)) == 3
+    assert ran == {(c, r) for c in (False, True) for r in (False, True)}
+    assert widths == {1, 255, 256, 257, 513} and heights == {1, 2, 5}
+    assert (False, True) in shapes and (True, True) in shapes and (True, False) in shapes      # an empty, a narrower and a full-width component
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # the top DWT level with the conversion fused in (ojphgpu_dwt_{forward,inverse}_image_ex, _general_image)
 # ------------------------------------------------------------------------------------------------------------------------

@@ -272,3 +272,59 @@ def test_set_video_accepts_exactly_what_the_format_table_says():
         (got,) = list(pipe.decode_sequence([cs]))
         pipe.close()
         assert got.dtype == np.uint8 and got.shape == want.shape and got.tobytes() == want.tobytes(), (view, last)
+
+
+# ---- the clamp of the hand-over kernels inside decoder pipes: lossy frames whose plain decode leaves the range
+OVERSHOOT = {8: 0.05, 10: 0.05, 12: 0.03}                    # bit depth -> the 9/7 step at which samples decode to 2^depth
+
+
+@functools.lru_cache(maxsize=None)
+def overshooting(depth):
+    """80 x 48, 3 components, 3 decompositions, 9/7: a 4 x 4 checkerboard of 0 and 2^depth - 1, its inverse and a random plane of
+    those two values -> (codestream, the single decoder's frame [3, 48, 80], which holds 2^depth: one past the range)"""
+    from openjph_amd import codec
+    from tests import cpu_pipeline as cp
+    w, h, top = 80, 48, (1 << depth) - 1
+    board = ((np.arange(h)[:, None] // 4 + np.arange(w)[None, :] // 4) & 1) * top
+    rnd = np.random.default_rng(depth).integers(0, 2, (h, w)) * top
+    img = np.stack([board, top - board, rnd]).astype(np.int32)
+    cs = cp.encode(img, bit_depth=depth, reversible=False, qstep=OVERSHOOT[depth], num_decomps=3)[0]
+    frame = codec.Decoder(cs).decode().astype(np.int64).reshape(3, h, w)
+    assert (frame == top + 1).sum() >= 1, "depth %d: the plain decode stays in range, the test proves nothing" % depth
+    assert frame.max() == top + 1 and frame.min() >= 0
+    return cs, frame
+
+
+def one_frame(cs, **kw):
+    from openjph_amd.pipeline import DecoderPipe
+    pipe = DecoderPipe(cs, depth=2, **kw)
+    try:
+        (got,) = list(pipe.decode_sequence([cs]))
+        return np.array(got)
+    finally:
+        pipe.close()
+
+
+@pytest.mark.parametrize("container", [16, 32])
+@pytest.mark.parametrize("depth,bits", [(10, 10), (12, 12), (8, 10), (10, 12)])
+def test_decoder_pipe_packed_clamps_to_the_bit_string_not_to_the_depth(depth, bits, container):
+    """depth == bits: a decoded 2^bits must not wrap to 0 in the bit string; depth < bits: 2^depth comes through, as the header
+    says ("clamped to [0, 2^bits - 1]")"""
+    from openjph_amd.pipeline import pack_bits, unpack_bits
+    cs, frame = overshooting(depth)
+    got = one_frame(cs, packed=bits, container=container)
+    want = pack_bits(np.clip(frame, 0, (1 << bits) - 1), bits)
+    assert got.dtype == np.uint8 and got.size == want.size and np.array_equal(got.reshape(-1), want)
+    back = unpack_bits(got.reshape(-1), bits, frame.size).astype(np.int64)
+    if depth == bits:
+        assert back.max() == (1 << bits) - 1 and (back[frame.reshape(-1) == 1 << bits] == (1 << bits) - 1).all()
+    else:
+        assert back.max() == 1 << depth and np.array_equal(back, frame.reshape(-1))
+
+
+@pytest.mark.parametrize("pixels,depth", [((8, False), 8), ((16, True), 12)])
+def test_decoder_pipe_pixels_clamp_to_the_depth(pixels, depth):
+    cs, frame = overshooting(depth)
+    got = one_frame(cs, pixels=pixels)
+    want = np.transpose(np.clip(frame, 0, (1 << depth) - 1), (1, 2, 0)).astype(np.uint8 if pixels[0] == 8 else np.dtype(">u2" if pixels[1] else "<u2"))
+    assert got.shape == want.shape and got.dtype.itemsize == want.dtype.itemsize and got.tobytes() == want.tobytes()
