@@ -659,9 +659,22 @@ int  ojphgpu_encoder_finish_frame(ojphgpu_encoder* enc, uint32_t frame, uint8_t*
  * the default; a byte budget or a quality target; a frame batch; the encoder of a frame pipe, a transcoder or a recoder;
  * OJPHGPU_NO_OVERLAP=1 or OJPHGPU_ENC_RELEASE=0 in the environment at creation) ends joined on the caller's stream.
  * The bytes are the same either way.
+ * Consecutive released runs: an encoder that can release holds what a run produces -- coefficient planes, output buffer,
+ * block results, cursors -- TWICE, and every released run takes the set the run before it did not use.  The next run no
+ * longer waits for the previous one: its first transform level starts while the previous run's block coder is still
+ * running, and on the caller's stream it waits only for the run two back.  The object's other calls (_coded_bytes,
+ * _finish*, the timing getters, the setters of section 5b / 5c, a run that ends joined) wait for every run in flight and
+ * then read the products of the LAST run.  A released run cuts the top resolution's blocks between its two streams at
+ * OJPHGPU_ENC_TOP_SHARE_RELEASED percent (default 50), a joined one where OJPHGPU_ENC_TOP_SHARE or the model says;
+ * ojphgpu_encoder_ht_timing reports the cut of the last run.  Memory: the second set is one more arena, output buffer and
+ * results table per such encoder -- about 0.7 GB for an 8K 4:4:4 frame; OJPHGPU_ENC_SETS=1 in the environment at
+ * creation keeps one set (every run then waits for the one before it, as it did), and an encoder that can never release
+ * holds one.  OJPHGPU_ENC_SIDE_CLEAR=0 keeps the cursor clear of a released run on the caller's stream.
  * Stream capture: a joined run is a fork and a join on the caller's stream and can be captured as it is; a released run
- * leaves two forked streams unjoined, so a capture that holds one must also hold one of the object's calls that wait
- * (the next run of the same object does) before it ends -- or the object runs with per-launch timing on.
+ * leaves two forked streams unjoined, and the next released run of the same object no longer joins them (it waits for the
+ * run two back only).  A capture that holds released runs must therefore end with one of the calls that wait for every
+ * run in flight and stay on the stream -- a run with per-launch timing on is the one that neither synchronises the host
+ * nor is refused in a capture -- or the object runs with per-launch timing on (or OJPHGPU_ENC_RELEASE=0) throughout.
  * Two caller streams: a caller that drives encodes and decodes on two streams of its own keeps a decode of its own
  * priority waiting at all times and starves the low-priority branches of a released run; INTEGRATION.md section 5. */
 int  ojphgpu_encoder_run_device(ojphgpu_encoder* enc, const int32_t* d_image);

@@ -160,7 +160,8 @@ __device__ __forceinline__ void mel_one(MelState& m, uint8_t* buf, int lane)
 // atomics complete at ~55 M/s on this part (they are resolved at the memory side, the XCDs' L2s are not coherent
 // with each other), 18 000 of them are 0.33 ms -- the top resolution's launch could not get below 0.39 ms, a quarter of
 // it waiting in that queue (measured with the allocation taken out).  With `nreg` regions (a power of two) block bi
-// allocates in region bi % nreg: regions[2r] = first byte, regions[2r + 1] = bytes, its cursor in a cache line of its
+// allocates in region bi % nreg (bi: the launch's `first` + the index inside the launch, i.e. the block's index among all
+// blocks of the encoder, so that the region does not depend on how the blocks are cut into launches): regions[2r] = first byte, regions[2r + 1] = bytes, its cursor in a cache line of its
 // own at cursor[32 r].  nreg = 0: the single cursor of the C ABI entry point.
 // In two halves, so that a caller can work while the atomic is on its way: claim_request issues it and returns what it
 // came back with in lane 0's register, UNREAD; claim_offset reads that register -- the wait for the atomic lands there.
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
     const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint32_t* __restrict__ coef,
     uint8_t* __restrict__ scratch, uint8_t* __restrict__ out, uint32_t out_cap,
     ojphgpu_cb_result* __restrict__ results, uint32_t* __restrict__ cursor, uint32_t* __restrict__ status,
-    const uint32_t* __restrict__ regions, uint32_t nreg)
+    const uint32_t* __restrict__ regions, uint32_t nreg, uint32_t first)
 {
   using V = typename std::conditional<S64, uint64_t, uint32_t>::type;     // a sign-magnitude sample
   constexpr uint32_t VBITS = S64 ? 64u : 32u;
@@ -537,7 +538,7 @@ __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
   uint32_t off = 0;
   if (err) total = 0;
   if (total) {                                            // slots are 4-byte aligned (ht_encode_kernel stores dwords)
-    off = claim_output(cursor, regions, nreg, bi, (total + 3u) & ~3u, out_cap, lane);
+    off = claim_output(cursor, regions, nreg, first + bi, (total + 3u) & ~3u, out_cap, lane);
     if (off == 0xFFFFFFFFu) { err = 1; total = 0; off = 0; }
   }
   if (total) {
@@ -730,7 +731,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
     const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint32_t* __restrict__ coef,
     uint8_t* __restrict__ scratch, uint8_t* __restrict__ out, uint32_t out_cap,
     ojphgpu_cb_result* __restrict__ results, uint32_t* __restrict__ cursor, uint32_t* __restrict__ status,
-    const uint32_t* __restrict__ regions, uint32_t nreg)
+    const uint32_t* __restrict__ regions, uint32_t nreg, uint32_t first)
 {
   __shared__ __attribute__((aligned(16))) uint16_t s_vlc[2][2048];
   __shared__ uint32_t s_uvlc[64];                   // U-VLC codewords of u = 0..63 (u <= 31 here), see uvlc_word
@@ -1476,7 +1477,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   if (err) total = 0;
   const uint32_t slot = (total + 3u) & ~3u;
   Claim claim = { 0, 0, 0 };
-  if (total) claim = claim_request(cursor, regions, nreg, bi, slot, out_cap, lane);
+  if (total) claim = claim_request(cursor, regions, nreg, first + bi, slot, out_cap, lane);
   const uint32_t scup = mel.pos + v_pos;
   const uint32_t tail = mel.pos + v_pos;
   const uint32_t gpart = min(ms_out, ms_len), local = ms_len - gpart;   // MagSgn bytes in the scratch slot / still in the stage
@@ -1544,7 +1545,7 @@ namespace ojphgpu {
 // 3 | 32 (wavelet bits clear = both).
 int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const void* d_coef, uint8_t* d_scratch,
                      uint8_t* d_out, uint32_t out_cap, ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status,
-                     int widths, const uint32_t* d_regions, uint32_t nreg)
+                     int widths, const uint32_t* d_regions, uint32_t nreg, uint32_t first)
 {
   if (n == 0) return OJPHGPU_OK;
   if (ensure_tables() != 0) return OJPHGPU_E_HIP;
@@ -1557,29 +1558,29 @@ int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, 
   const dim3 ngrid((n + NWAVES - 1) / NWAVES);
   if ((widths & 1) && (widths & 4) && (widths & 16))
     hipLaunchKernelGGL((ht_encode_kernel<true, 3>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   else if ((widths & 1) && (widths & 4))
     hipLaunchKernelGGL((ht_encode_kernel<true, 4>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   if ((widths & 1) && (widths & 8) && (widths & 16))
     hipLaunchKernelGGL((ht_encode_kernel<false, 3>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   else if ((widths & 1) && (widths & 8))
     hipLaunchKernelGGL((ht_encode_kernel<false, 4>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   if ((widths & 2) && (widths & 64)) {                      // wider blocks, none of them wider than 128 samples: 32 pairs by 2 quad rows
     if (widths & 4)
       hipLaunchKernelGGL((ht_encode_kernel<true, 5>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                         (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                         (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
     if (widths & 8)
       hipLaunchKernelGGL((ht_encode_kernel<false, 5>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                         (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                         (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   } else if (widths & 2)
     hipLaunchKernelGGL(ht_encode_wide_kernel<false>, grid, dim3(64 * WAVES), 0, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   if (widths & 32)                                          // blocks of components on the 64-bit sample path
     hipLaunchKernelGGL(ht_encode_wide_kernel<true>, grid, dim3(64 * WAVES), 0, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg);
+                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 }  // namespace ojphgpu
@@ -1588,7 +1589,7 @@ extern "C" int ojphgpu_ht_encode(void* stream, const ojphgpu_cb_desc* d_blocks, 
                                   const void* d_coef, uint8_t* d_scratch, uint8_t* d_out, uint32_t out_cap,
                                   ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status)
 {
-  return ojphgpu::ht_encode_launch(stream, d_blocks, n, d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, 3 | 32, nullptr, 0);
+  return ojphgpu::ht_encode_launch(stream, d_blocks, n, d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, 3 | 32, nullptr, 0, 0);
 }
 
 namespace ojphgpu {

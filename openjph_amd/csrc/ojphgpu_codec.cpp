@@ -59,15 +59,19 @@ extern "C" void ojphgpu_encoder_destroy(ojphgpu_encoder* e)
   // a released run may still be coding on the object's own streams: nothing is freed under it
   if (e->side) (void)hipStreamSynchronize(e->side);
   if (e->low) (void)hipStreamSynchronize(e->low);
-  e->pending = false;
+  e->pending = e->other.pending = false;
   for (DeviceBuf* b : { &e->arena, &e->image, &e->dwt_descs, &e->img_descs, &e->cb_descs, &e->conv_descs, &e->scratch, &e->out,
-                        &e->results, &e->counters, &e->regions }) b->release();
+                        &e->results, &e->counters, &e->regions, &e->other.arena, &e->other.out, &e->other.results,
+                        &e->other.counters }) b->release();
   e->h_out.release(); e->h_res.release();
   if (e->side) (void)hipStreamDestroy(e->side);
   if (e->low) (void)hipStreamDestroy(e->low);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   if (e->ev_low) (void)hipEventDestroy(e->ev_low);
+  if (e->other.ev_join) (void)hipEventDestroy(e->other.ev_join);
+  if (e->other.ev_low) (void)hipEventDestroy(e->other.ev_low);
+  if (e->ev_clear) (void)hipEventDestroy(e->ev_clear);
   e->timer.destroy();
   delete e->quality;
   delete e->rate;
@@ -108,6 +112,31 @@ extern "C" int ojphgpu_encoder_create_batch(const ojphgpu_plan* plan, int device
 // The block descriptors of the encoder's blocks with their scratch slots, and the compacted output with its regions (e->
 // out_cap, nreg, h_regions, counters_bytes).  band_kmax: per band of the plan, the K_max the slots and the output are sized
 // for where it exceeds the plan's own (an encoder with a byte budget: the finest step its search may visit); null = the plan's.
+// Which block encoder kernels the two launches of a cut at n_top need (ht_encode_launch's `widths`)
+// percent of the top resolution's blocks on the side stream in a released run where OJPHGPU_ENC_TOP_SHARE_RELEASED is unset;
+// 0 = the joined cut
+#ifndef OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT
+#define OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT 50
+#endif
+static ojphgpu_encoder::EncoderCut encoder_cut(const ojphgpu_encoder* e, uint32_t n_top)
+{
+  const Plan& P = *e->P;
+  ojphgpu_encoder::EncoderCut c; c.n_top = n_top;
+  bool over32_top = false, over32_rest = false, over128_top = false, over128_rest = false;
+  for (size_t i = 0; i < e->block_ids.size(); ++i) {
+    const Block& k = P.blocks[e->block_ids[i]]; const Band& B = P.bands[k.band];
+    const bool wide = is_wide(P, B.comp), rev = P.style(B.comp).rev;
+    (i < n_top ? c.widths_top : c.widths_rest) |= wide ? 32 : ((k.r.w > 64 ? 2 : 1) | (rev ? 4 : 8));
+    if (!wide && k.r.w > 32 && k.r.w <= 64) (i < n_top ? over32_top : over32_rest) = true;
+    if (!wide && k.r.w > 128) (i < n_top ? over128_top : over128_rest) = true;
+  }
+  if (!over32_top) c.widths_top |= 16;                     // every block of the range at most 32 samples wide (e.g. the IMF profile's 32 x 32)
+  if (!over32_rest) c.widths_rest |= 16;
+  if (!over128_top) c.widths_top |= 64;                    // no block wider than 128 samples: 128 x 32 blocks take the narrow kernel, too
+  if (!over128_rest) c.widths_rest |= 64;
+  return c;
+}
+
 static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, std::vector<ojphgpu_cb_desc>& bd, uint64_t& scratch_total,
                                  bool* clamped = nullptr)
 {
@@ -116,7 +145,6 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
   const uint32_t nframes = e->nframes;
   bd.assign(e->block_ids.size(), ojphgpu_cb_desc());
   uint64_t scratch_bytes = 0, samples = 0;
-  bool over32_top = false, over32_rest = false, over128_top = false, over128_rest = false;
   for (size_t i = 0; i < bd.size(); ++i) {
     const Block& k = P.blocks[e->block_ids[i]]; const Band& B = P.bands[k.band];
     samples += (uint64_t)k.r.w * k.r.h;
@@ -127,14 +155,7 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
     d.missing_msbs = (uint8_t)(B.K_max - 1); d.num_passes = 1; d.delta = B.delta;
     d.data_off = scratch_bytes; d.scratch_cap = block_scratch_bytes(k.r.w, k.r.h, band_kmax ? std::max(B.K_max, band_kmax[k.band]) : B.K_max);
     scratch_bytes += d.scratch_cap;
-    (i < e->n_top ? e->widths_top : e->widths_rest) |= wide ? 32 : ((k.r.w > 64 ? 2 : 1) | ((d.reversible & 1) ? 4 : 8));   // which kernel variants the range needs
-    if (!wide && k.r.w > 32 && k.r.w <= 64) (i < e->n_top ? over32_top : over32_rest) = true;
-    if (!wide && k.r.w > 128) (i < e->n_top ? over128_top : over128_rest) = true;
   }
-  if (!over32_top) e->widths_top |= 16;                    // every block of the range at most 32 samples wide (e.g. the IMF profile's 32 x 32)
-  if (!over32_rest) e->widths_rest |= 16;
-  if (!over128_top) e->widths_top |= 64;                   // no block wider than 128 samples: 128 x 32 blocks take the narrow kernel, too
-  if (!over128_rest) e->widths_rest |= 64;
   if (nframes > 1) {                                      // replicate the block descriptors, frame-major
     const size_t nb = bd.size();
     bd.resize(nb * nframes);
@@ -164,7 +185,7 @@ static void encoder_block_layout(ojphgpu_encoder* e, const uint32_t* band_kmax, 
     std::vector<uint64_t> rc(R ? R : 1, 0);
     if (R) for (size_t i = 0; i < bd.size(); ++i) {
       const uint64_t own = kmax_all > 20 ? bd[i].scratch_cap : std::min<uint64_t>(bd[i].scratch_cap, (uint64_t)bd[i].w * bd[i].h * 3 + 64);
-      rc[(i < e->n_top ? i : i - e->n_top) & (R - 1)] += own;   // the kernel sees the index inside its launch
+      rc[i & (R - 1)] += own;                                // (the kernels: the launch's first index + the index inside the launch)
     }
     uint64_t total = 0;
     e->h_regions.assign(2 * (size_t)R, 0);
@@ -215,6 +236,7 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
     replicate_converts(cd, nframes, P.arena_elems, P.frame_elems);
   }
   e->block_ids = blocks_of_tiles(P, tr);
+  uint32_t n_top_released = 0;
   if (nframes == 1 && max_recon_decomps(P) >= 2 && getenv("OJPHGPU_NO_OVERLAP") == nullptr) {
     auto top = [&](uint32_t id) { const Band& B = P.bands[P.blocks[id].band]; return B.res == P.style(B.comp).L; };
     auto mid = std::stable_partition(e->block_ids.begin(), e->block_ids.end(), top);
@@ -228,8 +250,12 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       // million samples of the top resolution and 1.6 x that below it (more bytes per sample, shorter launches), a lower
       // analysis level its bytes at 3 TB/s or a 12 us launch floor.  8K 4:4:4: 90 % (step 0.957 -> 0.938 ms); a 4K frame's
       // main branch is the longer one already: 100 %.  OJPHGPU_ENC_TOP_SHARE=<percent> overrides the model.
-      // The cut is the joined schedule's: a released run (ojphgpu_objects.h) measures best at 40-50 % (0.905 against
-      // 0.931 ms at 8K, profiles/enc_release_ab.txt), but one object runs both schedules and the cut is made once, here.
+      // That is the joined schedule's cut.  A released run (ojphgpu_objects.h), whose branches nobody waits for, has a cut
+      // of its own: OJPHGPU_ENC_TOP_SHARE_RELEASED=<percent>, read at every creation; unset: 50 % -- blocks moved to the
+      // second stream's launch are coded beside the synthesis levels (HBM-bound) instead of beside the fused block decoder
+      // (issue-bound like the coder); 8K step 0.843 ms at 50 against 0.854 / 0.849 at 40 / 60 and 0.869 at 90
+      // (profiles/enc_sets_ab.txt has the sweep).  The run picks the pair (run_container); the blocks' output regions do
+      // not depend on it (encoder_block_layout).
       static const int share_env = [] { const char* v = getenv("OJPHGPU_ENC_TOP_SHARE"); const int x = v ? atoi(v) : 0; return x < 10 ? 0 : x > 100 ? 100 : x; }();
       double s_top = 0, s_low = 0;                         // millions of samples
       for (size_t i = 0; i < e->block_ids.size(); ++i) {
@@ -242,7 +268,12 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       const double move = (s_top + margin_us / us_per_ms - 1.6 * s_low - dwt_us / us_per_ms) / 2.0;   // top samples the main branch should take
       int share = share_env;
       if (!share) { share = s_top > 0 && move > 0 ? (int)(100.0 * (1.0 - move / s_top)) : 100; share = share < 50 ? 50 : share > 100 ? 100 : share; }
-      e->n_top = (uint32_t)((uint64_t)e->n_top * (uint32_t)share / 100u);
+      const uint32_t n_res_top = e->n_top;
+      e->n_top = (uint32_t)((uint64_t)n_res_top * (uint32_t)share / 100u);
+      const char* rv = getenv("OJPHGPU_ENC_TOP_SHARE_RELEASED");
+      const int rshare = rv ? std::min(100, std::max(10, atoi(rv))) : OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT;
+      n_top_released = rshare ? (uint32_t)((uint64_t)n_res_top * (uint32_t)rshare / 100u) : e->n_top;
+      if (n_top_released == 0 || n_top_released == e->block_ids.size()) n_top_released = e->n_top;
     }
     if (e->n_top == 0 || e->n_top == e->block_ids.size()) e->n_top = 0;
     else {
@@ -272,8 +303,21 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       if (e->can_release &&
           (hipStreamCreateWithPriority(&e->low, hipStreamNonBlocking, own_prio) != hipSuccess ||
            hipEventCreateWithFlags(&e->ev_low, hipEventDisableTiming) != hipSuccess)) return bail(OJPHGPU_E_HIP);
+      // A second product set for the object that can release (ojphgpu_objects.h) unless OJPHGPU_ENC_SETS=1 (for an A/B, and
+      // for a caller short of memory: the set is one more arena, output buffer and results table), and the event behind
+      // the counter clear on the side stream unless OJPHGPU_ENC_SIDE_CLEAR=0.  Both read at every creation.
+      const char* sets = getenv("OJPHGPU_ENC_SETS"); const char* sc = getenv("OJPHGPU_ENC_SIDE_CLEAR");
+      e->two_sets = e->can_release && !(sets && atoi(sets) == 1);
+      e->clear_on_side = e->can_release && !(sc && sc[0] == '0');
+      if (e->two_sets &&
+          (hipEventCreateWithFlags(&e->other.ev_join, hipEventDisableTiming) != hipSuccess ||
+           hipEventCreateWithFlags(&e->other.ev_low, hipEventDisableTiming) != hipSuccess)) return bail(OJPHGPU_E_HIP);
+      if (e->clear_on_side && hipEventCreateWithFlags(&e->ev_clear, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
     }
   }
+  e->cut_joined = encoder_cut(e, e->n_top);
+  e->cut_released = e->can_release ? encoder_cut(e, n_top_released) : e->cut_joined;
+  e->take_cut(e->cut_joined);
   std::vector<ojphgpu_cb_desc> bd;
   uint64_t scratch_bytes = 0;
   encoder_block_layout(e, nullptr, bd, scratch_bytes);
@@ -286,6 +330,12 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       e->results.alloc(bd.size() * sizeof(ojphgpu_cb_result)) || e->counters.alloc(e->counters_bytes) ||
       (e->nreg && e->regions.alloc(e->h_regions.size() * 4)))
     return bail(OJPHGPU_E_NOMEM);
+  if (e->two_sets) {                                        // the second set, exactly as the first
+    if (e->other.arena.alloc(P.arena_elems * 4) || e->other.out.alloc(cap) ||
+        e->other.results.alloc(bd.size() * sizeof(ojphgpu_cb_result)) || e->other.counters.alloc(e->counters_bytes))
+      return bail(OJPHGPU_E_NOMEM);
+    if (hipMemset(e->other.arena.p, 0, P.arena_elems * 4) != hipSuccess) return bail(OJPHGPU_E_HIP);
+  }
   if (e->nreg && hipMemcpy(e->regions.p, e->h_regions.data(), e->h_regions.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!blocks_only && hipMemset(e->arena.p, 0, P.arena_elems * 4 * nframes) != hipSuccess) return bail(OJPHGPU_E_HIP);
   if (!dd.empty() && hipMemcpy(e->dwt_descs.p, dd.data(), dd.size() * sizeof(dd[0]), hipMemcpyHostToDevice) != hipSuccess) return bail(OJPHGPU_E_HIP);
@@ -312,17 +362,41 @@ extern "C" int ojphgpu_encoder_run_device8(ojphgpu_encoder* e, const uint8_t* d_
 namespace {
 struct BlockCoderRun {
   ojphgpu_encoder* e; uint8_t* out; ojphgpu_cb_result* res; uint32_t* cnt; uint32_t nblocks; Spans* T;
-  bool forked = false;
+  bool forked = false, cleared_on_side = false;
   int launch(hipStream_t st, uint32_t first, uint32_t n, int widths) {
     const int sh = T ? T->begin(SP_HT_ENC, st) : -1;
     int rc = ojphgpu::ht_encode_launch(st, (const ojphgpu_cb_desc*)e->cb_descs.p + first, n, e->arena.p, (uint8_t*)e->scratch.p, out,
-                                       e->out_cap, res + first, cnt, cnt + 1, widths, (const uint32_t*)e->regions.p, e->nreg);
+                                       e->out_cap, res + first, cnt, cnt + 1, widths, (const uint32_t*)e->regions.p, e->nreg, first);
     if (rc) return rc;
     if (T) T->end(sh, st);
     return OJPHGPU_OK;
   }
   // (every run of the block coder starts here: a released run of the object that is still coding is joined first)
-  int clear() { int rc = encoder_settle(e); if (rc) return rc; HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->stream)); return OJPHGPU_OK; }
+  int clear() {
+    int rc = encoder_settle(e);
+    if (rc) return rc;
+    e->stream_wrote = true;                                 // (launches on the caller's stream will count in this set)
+    HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->stream));
+    return OJPHGPU_OK;
+  }
+  // ... but a released run: only the set it is about to reuse (the run two back, where the object has two) is joined on the
+  // caller's stream, whose next launch overwrites that set's arena.  The clear itself is off that stream (clear_on_side):
+  // `side` -- in order behind the set's last top launch -- waits for the set's low branch (whether or not the caller's
+  // stream has: that wait does not order `side`), clears, and ev_clear lets `low` follow (fork_top); the side launch of this
+  // run is behind the clear in stream order.  Not where the set's last run counted on the caller's stream (a joined or
+  // searching run: stream_wrote), which `side` is not ordered behind: there the clear stays on the caller's stream, behind
+  // that run and in front of this run's fork.
+  int clear_released() {
+    int rc = encoder_settle_last(e);
+    if (rc) return rc;
+    cleared_on_side = e->clear_on_side && !e->stream_wrote;
+    e->stream_wrote = false;
+    if (!cleared_on_side) { HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->stream)); return OJPHGPU_OK; }
+    HIPCHK(hipStreamWaitEvent(e->side, e->ev_low, 0));      // (never recorded, or long complete: no wait)
+    HIPCHK(hipMemsetAsync(cnt, 0, e->counters_bytes, e->side));
+    HIPCHK(hipEventRecord(e->ev_clear, e->side));
+    return OJPHGPU_OK;
+  }
   // the top resolution's blocks are ready to be coded; release: the caller's stream is left here, the rest of the run goes to e->low
   int fork_top(bool release = false) {
     forked = true;
@@ -331,7 +405,11 @@ struct BlockCoderRun {
     int rc = launch(e->side, 0, e->n_top, e->widths_top);
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev_join, e->side));
-    if (release) { e->pending = true; HIPCHK(hipStreamWaitEvent(e->low, e->ev_fork, 0)); }   // (pending from here: also a run that fails below)
+    if (release) {                                          // (pending from here: also a run that fails below)
+      e->pending = true;
+      HIPCHK(hipStreamWaitEvent(e->low, e->ev_fork, 0));
+      if (cleared_on_side) HIPCHK(hipStreamWaitEvent(e->low, e->ev_clear, 0));
+    }
     return OJPHGPU_OK;
   }
   // the other blocks behind the lower levels on e->low; nobody waits yet (the caller records ev_low: ReleasedBranch)
@@ -362,12 +440,14 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
   if (container != 32) for (const CompGeo& g : P.comps) if (g.bit_depth > (uint32_t)container) return OJPHGPU_E_INVALID;
   hipStream_t s = e->stream;
   Spans& T = e->timer;
+  const bool release = encoder_releases(e);                 // the caller's stream is left behind the last launch that reads the frame
+  if (release) encoder_next_set(e);                         // (from here on arena / out / results / counters are this run's)
+  e->take_cut(release ? e->cut_released : e->cut_joined);
   BlockCoderRun coder{ e, (uint8_t*)(e->o_out ? e->o_out : e->out.p),         // a pipeline slot's buffers, or the object's own
                        (ojphgpu_cb_result*)(e->o_results ? e->o_results : e->results.p),
                        (uint32_t*)(e->o_counters ? e->o_counters : e->counters.p), (uint32_t)e->block_ids.size() * e->nframes, &T };
-  int rc = coder.clear();                                   // (joins a released run of this object first)
+  int rc = release ? coder.clear_released() : coder.clear();   // (joins the released runs of this object that are in its way)
   if (rc) return rc;
-  const bool release = encoder_releases(e);                 // the caller's stream is left behind the last launch that reads the frame
   ReleasedBranch branch{ e };
   T.start(s);
   if (e->need_convert) {
@@ -486,7 +566,7 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
     if (rbytes) memcpy(e->h_results.data(), e->h_res.p, rbytes);
     if (e->nreg)
       for (size_t i = 0; i < e->h_results.size(); ++i) {
-        const uint32_t r = (uint32_t)(i < e->n_top ? i : i - e->n_top) & (e->nreg - 1);
+        const uint32_t r = (uint32_t)i & (e->nreg - 1);     // (by the index among all blocks: encoder_block_layout)
         if (e->h_results[i].length) e->h_results[i].offset = (uint32_t)(e->h_results[i].offset - e->h_regions[2 * r] + hpos[r]);
       }
     e->fetched = true;
@@ -636,6 +716,7 @@ extern "C" int ojphgpu_encoder_set_budgets(ojphgpu_encoder* e, const uint64_t* m
   if (!encoder_may_search(e) || e->quality_on) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     if (!e->rate) { const int rc = encoder_rate_setup(e); if (rc) return rc; }
+    { const int rc = encoder_settle(e); if (rc) return rc; }   // an object that gains a budget: no released run is left in flight
     e->budgets.assign(max_bytes, max_bytes + n);
     e->ran = false;
     return OJPHGPU_OK;
@@ -690,6 +771,10 @@ static int encoder_rate_setup(ojphgpu_encoder* e)
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->side) HIPCHK(hipStreamSynchronize(e->side));
     e->scratch.release(); e->out.release(); e->regions.release(); e->counters.release();
+    if (e->two_sets) {                                      // (the sets keep equal sizes: released runs come back with budget 0)
+      e->other.out.release(); e->other.counters.release();
+      if (e->other.out.alloc(e->out_cap) || e->other.counters.alloc(e->counters_bytes)) return OJPHGPU_E_NOMEM;
+    }
     if (e->scratch.alloc(scratch_bytes) || e->out.alloc(e->out_cap) || e->counters.alloc(e->counters_bytes) ||
         (e->nreg && e->regions.alloc(e->h_regions.size() * 4)) ||
         R->stats_descs.alloc(sd.size() * sizeof(sd[0])) || R->hist.alloc(P.bands.size() * OJPHGPU_STATS_BINS * 4 * nframes) ||
@@ -872,7 +957,11 @@ extern "C" int ojphgpu_encoder_set_quality(ojphgpu_encoder* e, uint64_t max_sse)
   if (e->nframes > 1 || !encoder_may_search(e) || !e->budgets.empty()) return OJPHGPU_E_INVALID;
   const Plan& P = *e->P;
   for (const CompGeo& g : P.comps) if (g.bit_depth > 16) return OJPHGPU_E_INVALID;
-  if (e->quality) { e->max_sse = max_sse; e->cap_bytes = 0; e->quality_on = true; e->ran = false; return OJPHGPU_OK; }
+  if (e->quality) {
+    if (encoder_settle(e)) return OJPHGPU_E_HIP;            // (as an object that gains a budget)
+    e->max_sse = max_sse; e->cap_bytes = 0; e->quality_on = true; e->ran = false;
+    return OJPHGPU_OK;
+  }
   return no_throw([&]() -> int {
     HIPCHK(hipSetDevice(e->device));
     {                                                       // the half bit needs room below the coded bits at every step

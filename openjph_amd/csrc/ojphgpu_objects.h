@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <utility>
 #include <vector>
 
 #include "dwt_region.h"
@@ -534,8 +535,15 @@ struct ojphgpu_encoder {
   // overlap of the block coder with the lower DWT levels: the blocks of the top resolution (3/4 of
   // the samples) only need the first DWT level, so they are coded on a second stream while the
   // small, latency-bound launches of levels 2..L run on the main one
-  uint32_t n_top = 0;                              // descriptors [0, n_top) = blocks of the top resolution
+  // The cut is a pair, one per schedule (EncoderCut): a joined run wants the side launch to end first, a released run -- whose
+  // branches nobody waits for -- measures best with about half of the top resolution on either stream.  A block's output
+  // region goes by its index among ALL blocks (encoder_block_layout), so the products do not depend on the cut and
+  // run_container takes the pair of the run it is about to make.  n_top / widths_*: the cut of the last run; before any run,
+  // of the schedule the next run would take.
+  uint32_t n_top = 0;                              // descriptors [0, n_top) = the side launch's blocks (all of the top resolution)
   int widths_top = 0, widths_rest = 0;             // which block encoder kernels each range needs (bit 0 narrow, bit 1 wide, bit 2 reversible, bit 3 irreversible)
+  struct EncoderCut { uint32_t n_top = 0; int widths_top = 0, widths_rest = 0; } cut_joined, cut_released;
+  void take_cut(const EncoderCut& c) { n_top = c.n_top; widths_top = c.widths_top; widths_rest = c.widths_rest; }
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // A released run (include/ojphgpu.h section 5, "what a run leaves"): behind the last launch that reads the caller's frame
@@ -549,6 +557,27 @@ struct ojphgpu_encoder {
   hipStream_t low = nullptr;
   hipEvent_t ev_low = nullptr;
   bool pending = false, can_release = false;
+  bool stream_wrote = false;                       // the set's counters were last counted in by launches on the caller's stream (a joined or searching run)
+  // Two product sets (two_sets; only where can_release holds, OJPHGPU_ENC_SETS=1 at creation: one).  What a run produces and
+  // the coder reads -- arena, out, results, counters -- with the set's own ev_join / ev_low / pending exists twice, so that
+  // the transform of run n + 1 need not wait for the block coder of run n.  arena / out / results / counters / ev_join /
+  // ev_low / pending above are ALWAYS the set of the last run (what every accessor reads); `other` is the set of the run
+  // before it.  A released run begins by exchanging the two (encoder_next_set) and waits, on the caller's stream, only for
+  // the set it then holds -- the run two back.  Every other run, and everything that reads or replaces products, waits for
+  // both (encoder_settle) and uses the set of the last run.  Both sets always have the same sizes (encoder_rate_setup).
+  // `scratch` stays single: a block's slot is touched only by the launch that codes the block; released runs all use
+  // cut_released, so in consecutive released runs that launch sits on the same in-order stream (side or low); any other run
+  // settles both sets first, and the next released run's launches sit on streams that wait for a fork event recorded on the
+  // caller's stream behind that run.
+  struct OtherSet {
+    DeviceBuf arena, out, results, counters;
+    hipEvent_t ev_join = nullptr, ev_low = nullptr;
+    bool pending = false, stream_wrote = false;
+  } other;
+  bool two_sets = false;
+  // the counter clear of a released run goes on `side` (BlockCoderRun::clear_released), `low` waits for ev_clear
+  hipEvent_t ev_clear = nullptr;
+  bool clear_on_side = false;
   // where a run writes its products: the object's own buffers (null), or -- for a frame pipeline that keeps
   // several frames in flight -- the buffers of the frame's slot (ojphgpu_pipe.cpp)
   void* o_out = nullptr; void* o_results = nullptr; void* o_counters = nullptr;
@@ -573,17 +602,36 @@ struct ojphgpu_encoder {
 // launch, blocks-only encoders, OJPHGPU_NO_OVERLAP=1 and OJPHGPU_ENC_RELEASE=0 never can (can_release).
 inline bool encoder_releases(const ojphgpu_encoder* e)
 {
-  return e->can_release && e->n_top && !e->o_out && !e->o_results && !e->o_counters && !e->searches() && !e->timer.detail;
+  return e->can_release && e->cut_released.n_top && !e->o_out && !e->o_results && !e->o_counters && !e->searches() && !e->timer.detail;
 }
 // The stream-level join of a released run: e->stream waits for the branches' done events (no host synchronisation).
 // Called before anything is enqueued on e->stream -- or e->stream is synchronised -- to read or overwrite the products.
-inline int encoder_settle(ojphgpu_encoder* e)
+inline int encoder_settle_last(ojphgpu_encoder* e)          // the set of the last run only
 {
   if (!e->pending) return OJPHGPU_OK;
   HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
   HIPCHK(hipStreamWaitEvent(e->stream, e->ev_low, 0));
   e->pending = false;
   return OJPHGPU_OK;
+}
+inline int encoder_settle(ojphgpu_encoder* e)               // every pending set
+{
+  if (e->other.pending) {
+    HIPCHK(hipStreamWaitEvent(e->stream, e->other.ev_join, 0));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->other.ev_low, 0));
+    e->other.pending = false;
+  }
+  return encoder_settle_last(e);
+}
+// A released run of an object with two sets takes the set the last run did not use: afterwards arena / out / ... are that
+// set -- still pending if the run two back has not been waited for -- and `other` is the last run's.
+inline void encoder_next_set(ojphgpu_encoder* e)
+{
+  if (!e->two_sets) return;
+  std::swap(e->arena, e->other.arena); std::swap(e->out, e->other.out);
+  std::swap(e->results, e->other.results); std::swap(e->counters, e->other.counters);
+  std::swap(e->ev_join, e->other.ev_join); std::swap(e->ev_low, e->other.ev_low);
+  std::swap(e->pending, e->other.pending); std::swap(e->stream_wrote, e->other.stream_wrote);
 }
 // Where one trial of the budget search writes, and how its block lengths reach the host.  h_results != null: d_results is the
 // device address of that mapped pinned memory, the coder's records land in it, the two status words of d_counters are
