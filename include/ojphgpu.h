@@ -615,6 +615,22 @@ int ojphgpu_frame_error_ex(void* stream, const void* d_a, int bits_a, const void
 typedef struct ojphgpu_fit_comp { uint64_t first_elem, count; int32_t shift, lo, hi; uint32_t reserved; } ojphgpu_fit_comp;
 int ojphgpu_frame_fit(void* stream, const int32_t* d_src, void* d_dst, int container_bits, const ojphgpu_fit_comp* d_comps,
                       uint32_t n_comps);
+/* ojphgpu_frame_resample (section 5e, "a resampling recode"; kernels_fit.hip): the fit with components halved on the way, in
+ * the same pass.  Component c = the src_w x src_h samples (rows src_w apart) from element src_first of the int32 frame ->
+ * the dst_w x dst_h samples (rows dst_w apart) from element dst_first of d_dst's containers.  fx, fy: 1 (kept) or 2 (halved)
+ * per direction; px, py: 0 or 1, the phase -- output sample i of a halved direction stands ON source sample 2 i + p, so
+ * dst_w == (src_w + 1 - px) / 2 where fx == 2 (src_w where fx == 1; rows alike; either may come to 0: nothing is written).
+ * Per output sample the taps (1, 2, 1) around that source sample in every halved direction, indices clamped into the
+ * plane, summed exactly in 64 bits and rounded once ((acc + 2^(k-1)) >> k, k = 2 per halved direction); then the fit of
+ * ojphgpu_frame_fit with shift, lo, hi, and its containers.  A component with fx == fy == 1 is that fit itself.  The frames
+ * never overlap.  Writes the dst_w * dst_h elements of every component and nothing else.  A factor other than 1 or 2, a
+ * phase above 1, |shift| > 31, lo > hi or sizes that contradict the rule: the component is left alone; n_comps at most
+ * 65535.  (pipeline.resample_plane states the filter in numpy.) */
+typedef struct ojphgpu_resample_comp {
+  uint64_t src_first, dst_first; uint32_t src_w, src_h, dst_w, dst_h; uint32_t fx, fy, px, py; int32_t shift, lo, hi; uint32_t reserved;
+} ojphgpu_resample_comp;
+int ojphgpu_frame_resample(void* stream, const int32_t* d_src, void* d_dst, int container_bits, const ojphgpu_resample_comp* d_comps,
+                           uint32_t n_comps);
 
 /* ------------------------------------------------------------------------------------------ *
  * 5. Whole-frame codec objects: what an ojph::codestream-compatible facade calls from
@@ -1084,9 +1100,32 @@ void ojphgpu_transcoder_destroy(ojphgpu_transcoder* t);
  *      after a wait for the stream); [3] ojphgpu_encoder_finish (host clock of the last finish: searches included).
  *    Memory: the two objects' own, one int32 frame, and G where its container is narrower (at 32 bits the int32 frame is
  *    fitted in place).
+ *
+ *    A resampling recode (4:4:4 -> 4:2:2 / 4:2:0, 4:2:2 -> 4:2:0, ...): _create_resampled with OJPHGPU_RESAMPLE_COSITED
+ *    accepts an output whose components are sub-sampled further than the view's: per component, with a the view's and b
+ *    the output's, b.dx == a.dx * fx and b.dy == a.dy * fy with fx, fy each 1 or 2, independently.  Then
+ *        G = fit(resample(F)): per component ojphgpu_frame_resample (section 4) with those factors -- taps (1, 2, 1) in a
+ *            halved direction, centred ON a source sample, because component sample i sits at reference-grid column
+ *            i * XRsiz: with the source component's origin xs0 = ceil(X0 / a.dx), output sample i stands on source index
+ *            2 i + px, px = xs0 & 1 (0 under any view, whose output has no image offset; rows alike) -- then the fit above.
+ *    F has the view's layout, G the output's; a component with fx == fy == 1 is exactly the fit.  Everything else (the
+ *    encoder's modes, a quality target measured against G, _finish, _frame, _timing with the stage as out[1]) is as above.
+ *    OJPHGPU_E_INVALID in addition to the list above (a component's size must now be what the output's canvas gives for
+ *    the halved grid, (a.w + 1 - px) / 2): a factor other than 1 or 2; upsampling; a view whose absolute origin is not a
+ *    multiple of the OUTPUT's XRsiz * 2^skipped_res_for_recon (YRsiz ...).  With OJPHGPU_RESAMPLE_NONE the call is
+ *    ojphgpu_recoder_create.  The output plan itself refuses a colour transform over sub-sampled chroma.
+ *    _resample_table: the plans judged as _create_resampled judges them, without a device: fills comps[0 .. *n) (cap at
+ *    least the component count, else OJPHGPU_E_INVALID) with what the recoder uploads for ojphgpu_frame_resample.
+ *    Memory: G gets a buffer of its own also in a 32-bit container whenever a component is resampled.
  * ------------------------------------------------------------------------------------------ */
+#define OJPHGPU_RESAMPLE_NONE    0
+#define OJPHGPU_RESAMPLE_COSITED 1
 typedef struct ojphgpu_recoder ojphgpu_recoder;
 int  ojphgpu_recoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_recoder** r);
+int  ojphgpu_recoder_create_resampled(const ojphgpu_plan* src, const ojphgpu_plan* out, int resample, int device, void* stream,
+                                      ojphgpu_recoder** r);
+int  ojphgpu_recoder_resample_table(const ojphgpu_plan* src, const ojphgpu_plan* out, int resample, ojphgpu_resample_comp* comps,
+                                    uint32_t cap, uint32_t* n);
 int  ojphgpu_recoder_encoder(ojphgpu_recoder* r, ojphgpu_encoder** enc);
 int  ojphgpu_recoder_submit(ojphgpu_recoder* r, const uint8_t* h_codestream, size_t len, int resilient);
 int  ojphgpu_recoder_finish(ojphgpu_recoder* r, uint8_t* h_out, size_t cap, size_t* out_len, uint32_t* failed_blocks);

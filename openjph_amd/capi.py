@@ -173,6 +173,16 @@ class FitComp(C.Structure):               # ojphgpu_fit_comp
                 ("reserved", C.c_uint32)]
 
 
+class ResampleComp(C.Structure):          # ojphgpu_resample_comp
+    _fields_ = [("src_first", C.c_uint64), ("dst_first", C.c_uint64), ("src_w", C.c_uint32), ("src_h", C.c_uint32), ("dst_w", C.c_uint32),
+                ("dst_h", C.c_uint32), ("fx", C.c_uint32), ("fy", C.c_uint32), ("px", C.c_uint32), ("py", C.c_uint32), ("shift", C.c_int32),
+                ("lo", C.c_int32), ("hi", C.c_int32), ("reserved", C.c_uint32)]
+
+
+RESAMPLE_NONE, RESAMPLE_COSITED = 0, 1
+RESAMPLE = {None: RESAMPLE_NONE, "none": RESAMPLE_NONE, "cosited": RESAMPLE_COSITED}
+
+
 class QualityInfo(C.Structure):           # ojphgpu_quality_info
     _fields_ = [("grid_index", C.c_uint32), ("qstep", C.c_float), ("sse", C.c_uint64), ("sse_coarser", C.c_uint64),
                 ("pae", C.c_uint32), ("passes", C.c_uint32), ("bytes", C.c_uint64)]
@@ -453,6 +463,9 @@ SIGNATURES = {
     "ojphgpu_tc_pipe_fused_retries": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ojphgpu_frame_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]),
     "ojphgpu_recoder_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ojphgpu_frame_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]),
+    "ojphgpu_recoder_create_resampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ojphgpu_recoder_resample_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ojphgpu_recoder_encoder": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "ojphgpu_recoder_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     "ojphgpu_recoder_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),

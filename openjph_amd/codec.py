@@ -661,16 +661,19 @@ class _DeviceMemory:
 class Recoder:
     """A codestream recoded through the sample domain (ojphgpu_recoder; include/ojphgpu.h section 5e): what Transcoder
     refuses -- another wavelet, other decompositions or tiles, another bit depth, a source at a reduced resolution or
-    through a window.  One object owns a Decoder (under the view), one int32 frame in HBM, the fit to the output's depth
-    and range, and an Encoder with its three rate-control modes; the output is byte for byte what
-    Encoder(out).encode(fit(Decoder(cs, view).run_device())) writes."""
+    through a window, and with resample= another chroma format.  One object owns a Decoder (under the view), one int32
+    frame in HBM, the fit to the output's depth and range, and an Encoder with its three rate-control modes; the output is
+    byte for byte what Encoder(out).encode(fit(Decoder(cs, view).run_device())) writes -- fit(resample(...)) with
+    resample="cosited" (pipeline.resample_frame)."""
 
     def __init__(self, codestream: bytes, device=0, resilient=False, skip_res=None, region=None, max_bytes=0, max_sse=None, min_psnr=None,
-                 cap_bytes=0, **kw):
+                 cap_bytes=0, resample=None, **kw):
         """codestream: the first source (parsed for the geometry; every later one must have the same).  skip_res / region:
         the view, as Decoder takes them.  kw: what changes, as plan.recode_params takes it (bit_depth, bit_depths and every
         make_params keyword).  max_bytes / max_sse / min_psnr / cap_bytes: as Encoder takes them; a quality target is
-        measured against the fitted frame."""
+        measured against the fitted frame.  resample="cosited": downsampling=[(dx, dy), ...] may then sub-sample a
+        component by 2 more than the source does, per direction (4:4:4 -> 4:2:2 / 4:2:0: ojphgpu_recoder_create_resampled);
+        without it such an output is refused as before."""
         from .plan import recode_params
         torch = _torch()
         if cap_bytes and max_sse is None and min_psnr is None:
@@ -687,9 +690,16 @@ class Recoder:
         self.plan = Plan(self.params)
         self._lib = capi.lib()
         self._h = C.c_void_p()
+        if resample not in capi.RESAMPLE:
+            raise ValueError("resample: None or one of %s" % ", ".join(sorted(k for k in capi.RESAMPLE if k)))
+        self.resample = resample
         with torch.cuda.device(device):
-            check(self._lib.ojphgpu_recoder_create(self.src_plan.handle, self.plan.handle, device, _stream_ptr(torch, device),
-                                                   C.byref(self._h)), "recoder_create")
+            if capi.RESAMPLE[resample] == capi.RESAMPLE_NONE:
+                check(self._lib.ojphgpu_recoder_create(self.src_plan.handle, self.plan.handle, device, _stream_ptr(torch, device),
+                                                       C.byref(self._h)), "recoder_create")
+            else:
+                check(self._lib.ojphgpu_recoder_create_resampled(self.src_plan.handle, self.plan.handle, capi.RESAMPLE[resample], device,
+                                                                 _stream_ptr(torch, device), C.byref(self._h)), "recoder_create_resampled")
         eh = C.c_void_p()
         check(self._lib.ojphgpu_recoder_encoder(self._h, C.byref(eh)), "recoder_encoder")
         self.encoder = _BorrowedEncoder(eh, self.plan, device)
@@ -756,7 +766,7 @@ class Recoder:
 
     def frame(self):
         """the fitted frame of the last submit, as the encoder half reads it: a torch tensor VIEW of the recoder's memory
-        (plan.frame_shape; int8 / int16 or uint8 / uint16 by the sign of component 0, or int32), valid until the next
+        (the output plan's frame_shape -- flat where its components differ in size; int8 / int16 or uint8 / uint16 by the sign of component 0, or int32), valid until the next
         submit; read it after finish(), which is where a repeated decode lands"""
         torch = _torch()
         p, bits = C.c_void_p(), C.c_int()
@@ -776,10 +786,10 @@ class Recoder:
 
 
 def recode(codestream: bytes, device=0, resilient=False, skip_res=None, region=None, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0,
-           **kw) -> bytes:
+           resample=None, **kw) -> bytes:
     """One-shot helper: codestream -> codestream through the sample domain; arguments as Recoder takes them"""
     return Recoder(codestream, device=device, resilient=resilient, skip_res=skip_res, region=region, max_bytes=max_bytes, max_sse=max_sse,
-                   min_psnr=min_psnr, cap_bytes=cap_bytes, **kw).recode(codestream)
+                   min_psnr=min_psnr, cap_bytes=cap_bytes, resample=resample, **kw).recode(codestream)
 
 
 def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0, **kw) -> bytes:
@@ -940,6 +950,48 @@ def frame_fit(src, comps, container_bits, out=None):
     with torch.cuda.device(dev):
         check(capi.lib().ojphgpu_frame_fit(_stream_ptr(torch, dev), C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), int(container_bits),
                                            C.c_void_p(d.data_ptr()), len(comps)), "frame_fit")
+        torch.cuda.synchronize(dev)
+    return out
+
+
+resample_comp_dtype = np.dtype(capi.ResampleComp)
+
+
+def resample_table(src_plan, out_plan, resample="cosited"):
+    """ojphgpu_recoder_resample_table: the plans judged as Recoder(resample=...) judges them, without a device -> the
+    components of ojphgpu_frame_resample as a resample_comp_dtype array (OjphError E_INVALID where creation would refuse)"""
+    nc = int(out_plan.params.num_comps)
+    tab = np.zeros(max(nc, 1), resample_comp_dtype)
+    n = C.c_uint32()
+    check(capi.lib().ojphgpu_recoder_resample_table(src_plan.handle, out_plan.handle, capi.RESAMPLE[resample], tab.ctypes.data, len(tab),
+                                                    C.byref(n)), "recoder_resample_table")
+    return tab[:n.value]
+
+
+def frame_resample(src, comps, container_bits, out=None):
+    """ojphgpu_frame_resample: src an int32 device tensor holding a frame, comps = a resample_comp_dtype array or [dict(src_first,
+    dst_first, src_w, src_h, dst_w, dst_h, fx, fy, px, py, shift, lo, hi), ...] -> the resampled and fitted frame in
+    container_bits (8 | 16 | 32)-bit containers, as a uint8 / uint16 / int32 device tensor (a signed component's elements are
+    int8 / int16 behind that view).  out: a device tensor to write into -- elements outside the components' outputs are left
+    alone; None: zeros up to the last output element"""
+    torch = _torch()
+    assert src.is_cuda and src.is_contiguous() and src.dtype == torch.int32
+    dev = src.device.index
+    if isinstance(comps, np.ndarray):
+        cd = np.ascontiguousarray(comps, resample_comp_dtype)
+    else:
+        cd = np.zeros(len(comps), resample_comp_dtype)
+        for i, c in enumerate(comps):
+            for k, v in c.items():
+                cd[i][k] = int(v)
+    d = to_device(cd, dev)
+    if out is None:
+        size = max([int(c["dst_first"]) + int(c["dst_w"]) * int(c["dst_h"]) for c in cd] + [1])
+        out = torch.zeros(size, dtype={8: torch.uint8, 16: torch.uint16, 32: torch.int32}[int(container_bits)], device=src.device)
+    assert out.is_cuda and out.element_size() * 8 == int(container_bits)
+    with torch.cuda.device(dev):
+        check(capi.lib().ojphgpu_frame_resample(_stream_ptr(torch, dev), C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), int(container_bits),
+                                                C.c_void_p(d.data_ptr()), len(cd)), "frame_resample")
         torch.cuda.synchronize(dev)
     return out
 

@@ -2242,13 +2242,89 @@ static bool recode_plans_fit(const Plan& S, const Plan& O)
   return S.frame_elems == O.frame_elems;
 }
 
-extern "C" int ojphgpu_recoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_recoder** rout)
+// the output's nominal range and the shift to its depth: what the fit of component a -> b takes
+static void recode_fit_range(const CompGeo& a, const CompGeo& b, int32_t& shift, int32_t& lo, int32_t& hi)
+{
+  shift = (int32_t)a.bit_depth - (int32_t)b.bit_depth;
+  lo = (int32_t)(b.is_signed ? -((int64_t)1 << (b.bit_depth - 1)) : 0);
+  hi = (int32_t)(b.is_signed ? ((int64_t)1 << (b.bit_depth - 1)) - 1 : std::min<int64_t>(((int64_t)1 << b.bit_depth) - 1, INT32_MAX));
+}
+
+// may a decoder of S (parsed, under its view) feed an encoder of O through the resampling fit?  Fills the table of
+// ojphgpu_frame_resample, one entry per component.  recode_plans_fit with the size rule replaced: b.dx == a.dx * fx (rows
+// alike), fx 1 or 2, and b's size what the halved grid gives
+static bool recode_plans_resample(const Plan& S, const Plan& O, std::vector<ojphgpu_resample_comp>& tab)
+{
+  if (!S.parsed || S.coded.size() != S.blocks.size() || O.parsed || !O.coded.empty()) return false;
+  if (O.skip_read || O.skip_recon || O.has_region) return false;
+  if (S.any_wide || O.any_wide || S.comps.size() != O.comps.size() || S.comps.empty() || S.frame_elems == 0) return false;
+  const bool view = S.skip_read || S.skip_recon || S.has_region;
+  const uint64_t ax0 = (uint64_t)S.p.image_x0 + (S.has_region ? S.region[0] : 0), ay0 = (uint64_t)S.p.image_y0 + (S.has_region ? S.region[1] : 0);
+  tab.assign(S.comps.size(), ojphgpu_resample_comp{});
+  for (size_t c = 0; c < S.comps.size(); ++c) {
+    const CompGeo& a = S.comps[c]; const CompGeo& b = O.comps[c];
+    if (a.is_signed != b.is_signed) return false;
+    if (a.bit_depth == 0 || a.bit_depth > 32 || b.bit_depth == 0 || b.bit_depth > 32) return false;
+    if (a.dx == 0 || a.dy == 0 || b.dx % a.dx != 0 || b.dy % a.dy != 0) return false;     // (upsampling, or no whole factor)
+    const uint32_t fx = b.dx / a.dx, fy = b.dy / a.dy;
+    if (fx < 1 || fx > 2 || fy < 1 || fy > 2) return false;
+    // a view starts on a sample of every OUTPUT component (a whole-frame view of a resampled component included: its
+    // output has no image offset, so the decimation starts at phase 0 and the view's first sample must be an even one)
+    if (S.has_region || (view && (fx == 2 || fy == 2))) {
+      const uint64_t gx = (uint64_t)b.dx << S.skip_recon, gy = (uint64_t)b.dy << S.skip_recon;
+      if (ax0 % gx != 0 || ay0 % gy != 0) return false;
+    }
+    const uint32_t px = view ? 0u : (a.x0 & 1u), py = view ? 0u : (a.y0 & 1u);
+    const uint32_t w = fx == 2 ? (uint32_t)(((uint64_t)a.w + 1u - px) / 2u) : a.w, h = fy == 2 ? (uint32_t)(((uint64_t)a.h + 1u - py) / 2u) : a.h;
+    if (b.w != w || b.h != h) return false;
+    ojphgpu_resample_comp& t = tab[c];
+    t.src_first = a.frame_off; t.dst_first = b.frame_off;
+    t.src_w = a.w; t.src_h = a.h; t.dst_w = b.w; t.dst_h = b.h;
+    t.fx = fx; t.fy = fy; t.px = fx == 2 ? px : 0u; t.py = fy == 2 ? py : 0u;
+    recode_fit_range(a, b, t.shift, t.lo, t.hi);
+  }
+  return O.frame_elems != 0;
+}
+
+extern "C" int ojphgpu_recoder_resample_table(const ojphgpu_plan* src, const ojphgpu_plan* out, int resample, ojphgpu_resample_comp* comps,
+                                              uint32_t cap, uint32_t* n)
+{
+  if (!src || !out || !comps || !n) return OJPHGPU_E_INVALID;
+  *n = 0;
+  if (resample != OJPHGPU_RESAMPLE_NONE && resample != OJPHGPU_RESAMPLE_COSITED) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    const Plan& S = src->plan; const Plan& O = out->plan;
+    std::vector<ojphgpu_resample_comp> tab;
+    if (resample == OJPHGPU_RESAMPLE_NONE) {                 // the fit's own judgement, its components as entries with both factors 1
+      if (!recode_plans_fit(S, O)) return OJPHGPU_E_INVALID;
+      tab.assign(S.comps.size(), ojphgpu_resample_comp{});
+      for (size_t c = 0; c < S.comps.size(); ++c) {
+        const CompGeo& a = S.comps[c]; const CompGeo& b = O.comps[c];
+        ojphgpu_resample_comp& t = tab[c];
+        t.src_first = a.frame_off; t.dst_first = b.frame_off;
+        t.src_w = t.dst_w = a.w; t.src_h = t.dst_h = a.h;
+        t.fx = t.fy = 1;
+        recode_fit_range(a, b, t.shift, t.lo, t.hi);
+      }
+    } else if (!recode_plans_resample(S, O, tab)) return OJPHGPU_E_INVALID;
+    if (tab.size() > cap) return OJPHGPU_E_INVALID;
+    std::copy(tab.begin(), tab.end(), comps);
+    *n = (uint32_t)tab.size();
+    return OJPHGPU_OK;
+  });
+}
+
+static int recoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int resample, int device, void* stream, ojphgpu_recoder** rout)
 {
   if (!src || !out || !rout) return OJPHGPU_E_INVALID;
   *rout = nullptr;
+  if (resample != OJPHGPU_RESAMPLE_NONE && resample != OJPHGPU_RESAMPLE_COSITED) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     const Plan& S = src->plan; const Plan& O = out->plan;
-    if (!recode_plans_fit(S, O)) return OJPHGPU_E_INVALID;
+    std::vector<ojphgpu_resample_comp> tab;
+    if (resample == OJPHGPU_RESAMPLE_NONE ? !recode_plans_fit(S, O) : !recode_plans_resample(S, O, tab)) return OJPHGPU_E_INVALID;
+    bool resampled = false;
+    for (const ojphgpu_resample_comp& t : tab) resampled = resampled || t.fx == 2 || t.fy == 2;
     ojphgpu_recoder* r = new ojphgpu_recoder();
     struct Owner { ojphgpu_recoder* p; ~Owner() { if (p) ojphgpu_recoder_destroy(p); } } owner{ r };
     r->S = &S; r->O = &O; r->device = device; r->stream = (hipStream_t)stream;
@@ -2266,22 +2342,38 @@ extern "C" int ojphgpu_recoder_create(const ojphgpu_plan* src, const ojphgpu_pla
     for (size_t c = 0; c < S.comps.size(); ++c) {
       const CompGeo& a = S.comps[c]; const CompGeo& b = O.comps[c];
       deepest = std::max(deepest, b.bit_depth);
-      const int64_t lo = b.is_signed ? -((int64_t)1 << (b.bit_depth - 1)) : 0;
-      const int64_t hi = b.is_signed ? ((int64_t)1 << (b.bit_depth - 1)) - 1 : std::min<int64_t>(((int64_t)1 << b.bit_depth) - 1, INT32_MAX);
-      fc[c] = ojphgpu_fit_comp{ a.frame_off, (uint64_t)a.w * a.h, (int32_t)a.bit_depth - (int32_t)b.bit_depth, (int32_t)lo, (int32_t)hi, 0 };
+      int32_t shift, lo, hi;
+      recode_fit_range(a, b, shift, lo, hi);
+      fc[c] = ojphgpu_fit_comp{ a.frame_off, (uint64_t)a.w * a.h, shift, lo, hi, 0 };
     }
     r->container = deepest <= 8 ? 8 : deepest <= 16 ? 16 : 32;
     r->ncomps = (uint32_t)fc.size();
+    r->resampled = resampled;
+    // (a resampled G has the output's layout: never the int32 frame itself)
+    const bool own_g = r->container != 32 || resampled;
+    const void* table = resampled ? (const void*)tab.data() : (const void*)fc.data();
+    const size_t table_bytes = resampled ? tab.size() * sizeof(tab[0]) : fc.size() * sizeof(fc[0]);
     HIPCHK(hipSetDevice(device));
-    if (r->frame.alloc((size_t)S.frame_elems * 4 + 64) || r->comps.alloc(fc.size() * sizeof(fc[0])) ||
-        (r->container != 32 && r->fitted.alloc((size_t)S.frame_elems * (size_t)(r->container / 8) + 64))) return OJPHGPU_E_NOMEM;
-    HIPCHK(hipMemcpy(r->comps.p, fc.data(), fc.size() * sizeof(fc[0]), hipMemcpyHostToDevice));
+    if (r->frame.alloc((size_t)S.frame_elems * 4 + 64) || r->comps.alloc(table_bytes) ||
+        (own_g && r->fitted.alloc((size_t)O.frame_elems * (size_t)(r->container / 8) + 64))) return OJPHGPU_E_NOMEM;
+    HIPCHK(hipMemcpy(r->comps.p, table, table_bytes, hipMemcpyHostToDevice));
     HIPCHK(hipEventCreate(&r->ev_fit0));
     HIPCHK(hipEventCreate(&r->ev_fit1));
     owner.p = nullptr;
     *rout = r;
     return OJPHGPU_OK;
   });
+}
+
+extern "C" int ojphgpu_recoder_create(const ojphgpu_plan* src, const ojphgpu_plan* out, int device, void* stream, ojphgpu_recoder** rout)
+{
+  return recoder_create(src, out, OJPHGPU_RESAMPLE_NONE, device, stream, rout);
+}
+
+extern "C" int ojphgpu_recoder_create_resampled(const ojphgpu_plan* src, const ojphgpu_plan* out, int resample, int device, void* stream,
+                                                ojphgpu_recoder** rout)
+{
+  return recoder_create(src, out, resample, device, stream, rout);
 }
 
 extern "C" int ojphgpu_recoder_encoder(ojphgpu_recoder* r, ojphgpu_encoder** enc)
@@ -2296,7 +2388,9 @@ static int recoder_fit_and_run(ojphgpu_recoder* r)
 {
   hipStream_t s = r->stream;
   HIPCHK(hipEventRecord(r->ev_fit0, s));
-  int rc = ojphgpu_frame_fit(s, (const int32_t*)r->frame.p, r->g(), r->container, (const ojphgpu_fit_comp*)r->comps.p, r->ncomps);
+  int rc = r->resampled
+             ? ojphgpu_frame_resample(s, (const int32_t*)r->frame.p, r->g(), r->container, (const ojphgpu_resample_comp*)r->comps.p, r->ncomps)
+             : ojphgpu_frame_fit(s, (const int32_t*)r->frame.p, r->g(), r->container, (const ojphgpu_fit_comp*)r->comps.p, r->ncomps);
   if (rc) return rc;
   HIPCHK(hipEventRecord(r->ev_fit1, s));
   return ojphgpu_encoder_run_container(r->enc, r->g(), r->container);

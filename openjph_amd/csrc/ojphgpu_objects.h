@@ -757,8 +757,9 @@ struct ojphgpu_recoder {
   ojphgpu_decoder* dec = nullptr; ojphgpu_encoder* enc = nullptr;
   const Plan* S = nullptr; const Plan* O = nullptr;
   int device = 0; hipStream_t stream = nullptr;
-  DeviceBuf frame, fitted, comps;                  // F (int32; at 32 bits also G, fitted in place), G in a narrower container, the fit's components
+  DeviceBuf frame, fitted, comps;                  // F (int32; at 32 bits also G, fitted in place), G in a narrower container or resampled, the stage's components
   int container = 32; uint32_t ncomps = 0;
+  bool resampled = false;                          // comps holds ojphgpu_resample_comp: the stage is ojphgpu_frame_resample, G the output's layout
   std::vector<ojphgpu_cb_desc> h_descs;            // this source's block descriptors
   std::vector<uint8_t> h_stage;                    // a view's runs, gathered for one copy
   hipEvent_t ev_fit0 = nullptr, ev_fit1 = nullptr;
@@ -766,7 +767,7 @@ struct ojphgpu_recoder {
   bool resilient = false;
   uint32_t failed = 0;
   double final_ms = 0;
-  void* g() const { return container == 32 ? frame.p : fitted.p; }
+  void* g() const { return container == 32 && !resampled ? frame.p : fitted.p; }
 };
 struct DecFrameInfo;
 // How the status bytes of a run (+ the RETRY word behind them) reach the host for whoever collects its verdicts: called once

@@ -341,6 +341,37 @@ def fit_frame(planes, src_depths, out_depths, signs):
     return out
 
 
+def resample_plane(q, fx, fy, px=0, py=0):
+    """numpy statement of the recoder's resampling (ojphgpu_frame_resample before its fit; include/ojphgpu.h section 5e): one
+    plane halved where fx / fy is 2.  Output sample i of a halved direction stands ON source sample 2 i + p (p = the parity
+    of the source component's origin on its own grid): taps (1, 2, 1) around it, indices clamped into the plane, summed
+    exactly in 64 bits and rounded once -- (acc + 2^(k-1)) >> k with k = 2 per halved direction.  -> int64"""
+    if fx not in (1, 2) or fy not in (1, 2) or px not in (0, 1) or py not in (0, 1):
+        raise ValueError("resample_plane: factors are 1 or 2, phases 0 or 1")
+    v = np.asarray(q).astype(np.int64)
+    hs, ws = v.shape
+    wo = (ws - px + 1) // 2 if fx == 2 else ws               # == ceil((xs0 + ws) / 2) - ceil(xs0 / 2); may be 0
+    ho = (hs - py + 1) // 2 if fy == 2 else hs
+
+    def taps(n, no, f, p):
+        if f == 1:
+            return [(np.arange(no), 1)]
+        c = 2 * np.arange(no) + p                            # always < n
+        return [(np.clip(c - 1, 0, n - 1), 1), (c, 2), (np.clip(c + 1, 0, n - 1), 1)]
+    acc = np.zeros((ho, wo), np.int64)
+    for iy, wy in taps(hs, ho, fy, py):
+        for ix, wx in taps(ws, wo, fx, px):
+            acc += wy * wx * v[np.ix_(iy, ix)]
+    k = 2 * ((fx == 2) + (fy == 2))                          # 0, 2 or 4
+    return (acc + (1 << (k - 1)) >> k) if k else acc
+
+
+def resample_frame(planes, factors, phases=None):
+    """resample_plane per component: factors = [(fx, fy), ...], phases = [(px, py), ...] (None: zeros)"""
+    phases = [(0, 0)] * len(planes) if phases is None else phases
+    return [resample_plane(q, fx, fy, px, py) for q, (fx, fy), (px, py) in zip(planes, factors, phases)]
+
+
 class EncoderPipe(_Handover):
     _side = "enc"
 

@@ -16,7 +16,8 @@ synchronise:
 All three write the same bytes (asserted).  Beside the table: the fit kernel's time (device events, Recoder.timing) and its
 share of the HBM peak from the bytes it moves, 4 read + 2 written per sample.  One JSON line per target: medians, spread =
 (max - min) / median.
-  python tools/recode_bench.py [--runs 10] [--warmup 2] [--rows 4320]"""
+  python tools/recode_bench.py [--runs 10] [--warmup 2] [--rows 4320]
+  python tools/recode_bench.py --resample [...]: the resampling stage beside the fit (resample_rounds below)"""
 import argparse
 import json
 import os
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=4320, help="top rows of the frame (rehearsals at a small size)")
+    ap.add_argument("--resample", action="store_true", help="the resampling stage beside the fit: 4:4:4 / 4:2:2 / 4:2:0 at 10 bits")
     a = ap.parse_args()
     import torch
     from openjph_amd import codec
@@ -55,6 +57,8 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3, out
 
+    if a.resample:
+        return resample_rounds(a, codec, cs, (nc, h, w))
     dec = codec.Decoder(cs)
     d32 = torch.empty(dec.shape, dtype=torch.int32, device="cuda")
     targets = [("budget %.2f B/sample" % BPS, dict(max_bytes=int(samples * BPS))), ("qstep %.3f" % OUT_QSTEP, dict(qstep=OUT_QSTEP))]
@@ -94,6 +98,40 @@ def main():
         out["recoder_timing_ms"] = {k: round(float(v), 3) for k, v in rec.timing().items()}
         print(json.dumps(out), flush=True)
         del rec, enc
+
+
+def resample_rounds(a, codec, cs, shape):
+    """--resample: the frame taken to 10 bits at the fixed step as 4:4:4 (the fit: ojphgpu_frame_fit), 4:2:2 and 4:2:0 (the
+    resampling stage: ojphgpu_frame_resample), the three recoders taking turns in every round; per format the stage's time
+    from the recoder's own device events (timing()["fit_ms"]), the bytes it moves -- 4 read per source sample, 2 written per
+    output sample -- and what that makes per second.  One JSON line with every round and the medians."""
+    nc, h, w = shape
+    formats = [("444", [(1, 1)] * 3, None), ("422", [(1, 1), (2, 1), (2, 1)], "cosited"), ("420", [(1, 1), (2, 2), (2, 2)], "cosited")]
+    recs, rounds, sizes = {}, {}, {}
+    for name, ds, rs in formats:
+        recs[name] = codec.Recoder(cs, resample=rs, reversible=False, qstep=OUT_QSTEP, bit_depth=10, color_transform=False, downsampling=ds)
+        rounds[name] = dict(stage_ms=[], recode_ms=[])
+    for i in range(a.warmup + a.runs):
+        for name, _, _ in formats:
+            t0 = time.perf_counter()
+            out = recs[name].recode(cs)
+            ms = (time.perf_counter() - t0) * 1e3
+            sizes[name] = len(out)
+            if i >= a.warmup:
+                rounds[name]["stage_ms"].append(round(float(recs[name].timing()["fit_ms"]), 4))
+                rounds[name]["recode_ms"].append(round(ms, 3))
+    out = dict(frame="c3 %dx%dx%d 12-bit reversible, %d bytes" % (w, h, nc, len(cs)), target="10 bits, qstep %.3f" % OUT_QSTEP, runs=a.runs)
+    for name, _, _ in formats:
+        moved = 4 * nc * h * w + 2 * recs[name].plan.frame_elems
+        st = rounds[name]["stage_ms"]
+        med = float(np.median(st))
+        out[name] = dict(stage="ojphgpu_frame_fit" if name == "444" else "ojphgpu_frame_resample", bytes_out=sizes[name], bytes_moved=moved,
+                         stage_median_ms=round(med, 4), stage_spread=round((max(st) - min(st)) / med, 3), TB_per_s=round(moved / (med * 1e-3) / 1e12, 3),
+                         share_of_hbm_peak=round(moved / (med * 1e-3) / HBM_PEAK, 3), recode_median_ms=round(float(np.median(rounds[name]["recode_ms"])), 3),
+                         rounds=rounds[name])
+    for name in ("422", "420"):
+        out[name]["stage_over_fit"] = round(out[name]["stage_median_ms"] / out["444"]["stage_median_ms"], 3)
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
