@@ -1199,6 +1199,24 @@ int  ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* pipe, int bits);
  * row_bytes, and the launch is ojphgpu_unpack_video444.  A 10-bit frame crosses the link in two thirds of the bytes of its
  * planes in 16-bit containers. */
 int  ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* pipe, int format);
+/* The frames are handed over as one RGB buffer and coded as Y, Cb, Cr 4:4:4, 4:2:2 or 4:2:0: an RGB member of the 4:4:4
+ * family (OJPHGPU_VIDEO_BGRA / _RGBA / _ARGB / _R210 / _R10K) and a colour spec (section 7e: OJPHGPU_COLOUR_* standard and
+ * ranges; rgb_depth: of the buffer's samples, 0 = the plan's depth).  Two launches per frame on the compute stream behind the
+ * upload: ojphgpu_unpack_video444 into a buffer of 3 w h containers of the slot, then ojphgpu_frame_rgb_to_ycc into the slot's
+ * image with the FORWARD table of (standard, rgb_depth, the plan's depth, the ranges) and the plan's chroma cell.  Every
+ * codestream is, byte for byte, the plain encode of those planes; a byte budget, a quality target and a cap combine with it
+ * as with _set_video (a target is measured against the Y, Cb, Cr planes).  The calling window of _set_video; excludes
+ * _set_pixels / _set_packed AND the plain _set_video (one or the other, for the life of the pipe or until set back to planes
+ * by format 0); _set_video itself is unchanged.
+ * OJPHGPU_E_INVALID, the pipe left as it was: a null spec; a format that is not one of the five (v410, Y410, AYUV, Y4XX hold
+ * Y, Cb, Cr already; the 4:2:2 and 4:2:0 formats); an unknown standard or range; a plan that has not exactly three unsigned
+ * components of one depth of 8 .. 16 bits that the container holds, component 0 on the reference grid (XRsiz = YRsiz = 1),
+ * components 1 and 2 sub-sampled alike by 1 or 2 each way with planes of (ceil(w / fx), ceil(h / fy)); an odd image offset in a
+ * halved direction (the chroma sample would stand on the cell's second luma sample: phase 1); an rgb_depth that the format
+ * does not hold (the byte formats: 8; R210 / R10K: 8 .. 10) or that is wider than the container.  (A colour transform over
+ * sub-sampled components is refused by the plan already; over a 4:4:4 plan it applies to Y, Cb, Cr as to any three planes.) */
+typedef struct ojphgpu_colour_spec { int standard, rgb_range, ycc_range; uint32_t rgb_depth; } ojphgpu_colour_spec;
+int  ojphgpu_enc_pipe_set_video_colour(ojphgpu_enc_pipe* pipe, int format, const ojphgpu_colour_spec* spec);
 
 /* Every frame of this pipe is coded to a byte budget (section 5b): each collected codestream is, byte for byte, the plain
  * encode of its frame at qstep(j*), with the certificate size(j*) <= budget < size(j* + 1) measured for that frame.
@@ -1310,6 +1328,15 @@ int  ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* pipe, int bits);     /* decod
  * with an odd y0 is refused whatever its height, as one with an odd x0 is.  The 4:4:4 formats of section 7d come back in
  * the tight layout too (ojphgpu_pack_video444, alpha opaque); there is no chroma cell, so a window passes at any x0, y0. */
 int  ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* pipe, int format);
+/* decoded Y, Cb, Cr frames come back as one RGB buffer: ojphgpu_frame_ycc_to_rgb with the INVERSE table from the slot's image
+ * into its buffer of 3 w h containers, then ojphgpu_pack_video444 -- the mirror of ojphgpu_enc_pipe_set_video_colour, with its
+ * conditions, judged on the view's plan when the pipe decodes a view: a reduced resolution always passes, a window when its
+ * x0 is even where fx == 2 and its y0 is even where fy == 2 (both together: a multiple of 2^(skip_recon + 1), even on the
+ * reduced grid).  The samples enter as the pipe's containers hold them (a decoded
+ * sample past its range is not clamped first; a 16-bit container saturates at 0 and 65535, an 8-bit one at 0 and 255).  A pipe
+ * with 32-bit containers is refused: its planes are int32 and may hold negative samples.  The calling window and the
+ * exclusions of _set_video. */
+int  ojphgpu_dec_pipe_set_video_colour(ojphgpu_dec_pipe* pipe, int format, const ojphgpu_colour_spec* spec);
 
 /* The transcode pipe: host codestream in, host codestream out -- section 5d's T(cs, out), source after source, with the
  * parse, the upload, the download and Tier-2 of neighbouring frames overlapped with the device as the other two pipes do
@@ -1487,6 +1514,60 @@ typedef struct ojphgpu_video_info {                  /* family: OJPHGPU_VIDEO_FA
   int family; uint32_t sub_x, sub_y, min_depth, max_depth, min_container_bits, pointer_align, pitch_align;
 } ojphgpu_video_info;
 int  ojphgpu_video_format_info(int format, ojphgpu_video_info* out);   /* host only */
+/* ---- 7e. RGB <-> YCbCr 4:4:4 / 4:2:2 / 4:2:0 (kernels_colour.hip): the matrix of a video standard, the range mapping, the
+ * change of depth and the halving / doubling of chroma in ONE integer pass over planar containers.  Exact integer arithmetic;
+ * pipeline.colour_table / rgb_to_ycc / ycc_to_rgb state the same in numpy, entry for entry and sample for sample.
+ *   The table.  (Kr, Kb) = (0.299, 0.114) BT601, (0.2126, 0.0722) BT709, (0.2627, 0.0593) BT2020 (non-constant luminance); Kg
+ *   = 1 - Kr - Kb.  A signal of depth B (8 .. 16, the RGB side's and the YCbCr side's chosen independently, as their ranges
+ *   are) has an offset and a span, s = 2^(B - 8): RGB or luma (0, 2^B - 1) full, (16 s, 219 s) narrow; chroma (2^(B-1), 2^B -
+ *   1) full, (128 s, 224 s) narrow.  k = 16 fraction bits.
+ *   FORWARD (RGB -> YCbCr): rows A = luma (Kr, Kg, Kb), Cb (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)), Cr (1 - Kr, -Kg, -Kb) / (2 (1 -
+ *   Kr)); m[c][0] and m[c][2] = llround(A[c][i] * span_ycc[c] / span_rgb * 65536.0); the GREEN coefficient m[c][1] = the row's
+ *   rounded total -- llround(span_ycc[0] / span_rgb * 65536.0) for luma, 0 for chroma -- minus the other two, so that every
+ *   grey gives exactly mid chroma and black and white exactly the ends of the luma range; off[c] = (offset_ycc[c] << 16) -
+ *   offset_rgb * (m[c][0] + m[c][1] + m[c][2]).
+ *   INVERSE (YCbCr -> RGB), from the closed form: R = Y + 2 (1 - Kr) Cr, B = Y + 2 (1 - Kb) Cb, G = Y - (2 Kb (1 - Kb) / Kg) Cb
+ *   - (2 Kr (1 - Kr) / Kg) Cr; each of the nine m[c][i] = llround(coef * span_rgb / span_ycc[i] * 65536.0) on its own (the two
+ *   structural zeros stay 0); off[c] = (offset_rgb << 16) - sum_i m[c][i] * offset_ycc[i].
+ *   lo = 0, hi = 2^(depth of the output side) - 1 both ways: super-white and sub-black survive, the container's range holds.
+ *   The stages.  frame: w x h the RGB and the luma planes; fx, fy (1 | 2 each) the chroma cell, chroma planes cw x ch with cw =
+ *   (w + 1) / 2 where fx == 2 (else w), ch alike; *_first: the first element of each plane in its buffer, rows tightly packed.
+ *   Containers: unsigned 8 / 16 / 32 bits, either side's on its own.  All sums in 64-bit two's complement.
+ *   _rgb_to_ycc: per pixel t_c = m[c] . (R, G, B).  Component c's sample (i, j) stands ON source sample (fx i, fy j) -- luma:
+ *   factors 1 --: in every halved direction the taps (1, 2, 1) over t_c, indices clamped into the plane (section 5e's filter
+ *   and siting, phase 0), kk = 2 per halved direction; out = clamp((acc + (off[c] << kk) + 2^(k + kk - 1)) >> (k + kk), lo[c],
+ *   hi[c]), an arithmetic shift, ONE rounding.
+ *   _ycc_to_rgb: chroma at luma column x of a halved direction = 2 C[x / 2] (x even), C[(x - 1) / 2] + C[min((x + 1) / 2, cw -
+ *   1)] (x odd); rows alike, the product in 2-D; kk = 1 per halved direction, luma enters as Y << kk; out = clamp((m[c] . (Y',
+ *   Cb', Cr') + (off[c] << kk) + 2^(k + kk - 1)) >> (k + kk), lo[c], hi[c]).  Samples are taken as they stand: one past its
+ *   nominal range is not clamped first.
+ *   A stage writes the samples of its three destination planes and NOTHING else.  [lo, hi] is narrowed to what the destination
+ *   container holds.  Table and frame travel as kernel arguments: nothing is uploaded, nothing allocated.  OJPHGPU_COLOUR_WGS
+ *   (read per call; 1 .. 65535) caps the workgroups of the launch.
+ * OJPHGPU_E_INVALID: a null pointer, a factor other than 1 or 2, k != 16, lo > hi, a container that is not 8 / 16 / 32 bits, a
+ * buffer not aligned to its container, w or h of 0, a source plane that overlaps a destination plane; _colour_table_make: an
+ * unknown standard, direction or range, a depth outside 8 .. 16. */
+#define OJPHGPU_COLOUR_BT601  601
+#define OJPHGPU_COLOUR_BT709  709
+#define OJPHGPU_COLOUR_BT2020 2020
+#define OJPHGPU_COLOUR_FORWARD 0                     /* RGB -> YCbCr */
+#define OJPHGPU_COLOUR_INVERSE 1                     /* YCbCr -> RGB */
+#define OJPHGPU_COLOUR_FULL   0
+#define OJPHGPU_COLOUR_NARROW 1
+typedef struct ojphgpu_colour_table { int32_t m[3][3]; int64_t off[3]; int32_t lo[3], hi[3]; uint32_t k; } ojphgpu_colour_table;
+typedef struct ojphgpu_colour_frame { uint32_t w, h, fx, fy; uint64_t rgb_first[3], ycc_first[3]; } ojphgpu_colour_frame;
+int  ojphgpu_colour_table_make(int standard, int direction, uint32_t rgb_depth, uint32_t ycc_depth, int rgb_range, int ycc_range,
+                               ojphgpu_colour_table* out);   /* host only */
+int  ojphgpu_frame_rgb_to_ycc(void* stream, const void* d_rgb, int rgb_container_bits, void* d_ycc, int ycc_container_bits,
+                              const ojphgpu_colour_frame* frame, const ojphgpu_colour_table* table);
+int  ojphgpu_frame_ycc_to_rgb(void* stream, const void* d_ycc, int ycc_container_bits, void* d_rgb, int rgb_container_bits,
+                              const ojphgpu_colour_frame* frame, const ojphgpu_colour_table* table);
+/* The plan judgement of ojphgpu_enc_pipe_set_video_colour (decoding == 0) / ojphgpu_dec_pipe_set_video_colour (decoding != 0)
+ * without a pipe or a device: OJPHGPU_OK or the setter's OJPHGPU_E_INVALID; a restricted plan is judged as the view it is (its
+ * window's origin included).  Any of table (the one the pipe would use), frame (where the six planes stand: R, G, B one after
+ * the other, Y, Cb, Cr as in the plan's frame) and frame_bytes (of the RGB buffer) may be null. */
+int  ojphgpu_video_colour_fit(const ojphgpu_plan* plan, int container_bits, int decoding, int format, const ojphgpu_colour_spec* spec,
+                              ojphgpu_colour_table* table, ojphgpu_colour_frame* frame, uint64_t* frame_bytes);   /* host only */
 /* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
  * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
  * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a

@@ -179,6 +179,22 @@ class ResampleComp(C.Structure):          # ojphgpu_resample_comp
                 ("lo", C.c_int32), ("hi", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class ColourTable(C.Structure):           # ojphgpu_colour_table
+    _fields_ = [("m", (C.c_int32 * 3) * 3), ("off", C.c_int64 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("k", C.c_uint32)]
+
+
+class ColourFrame(C.Structure):           # ojphgpu_colour_frame
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("fx", C.c_uint32), ("fy", C.c_uint32), ("rgb_first", C.c_uint64 * 3),
+                ("ycc_first", C.c_uint64 * 3)]
+
+
+class ColourSpec(C.Structure):            # ojphgpu_colour_spec
+    _fields_ = [("standard", C.c_int), ("rgb_range", C.c_int), ("ycc_range", C.c_int), ("rgb_depth", C.c_uint32)]
+
+
+COLOUR_STANDARD = {"bt601": 601, "bt709": 709, "bt2020": 2020}
+COLOUR_DIRECTION = {"forward": 0, "inverse": 1}
+COLOUR_RANGE = {"full": 0, "narrow": 1}
 RESAMPLE_NONE, RESAMPLE_COSITED = 0, 1
 RESAMPLE = {None: RESAMPLE_NONE, "none": RESAMPLE_NONE, "cosited": RESAMPLE_COSITED}
 
@@ -450,6 +466,13 @@ SIGNATURES = {
     "ojphgpu_unpack_video444": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
     "ojphgpu_pack_video444": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]),
     "ojphgpu_video_format_info": (C.c_int, [C.c_int, C.POINTER(VideoInfo)]),
+    "ojphgpu_colour_table_make": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(ColourTable)]),
+    "ojphgpu_frame_rgb_to_ycc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(ColourFrame), C.POINTER(ColourTable)]),
+    "ojphgpu_frame_ycc_to_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(ColourFrame), C.POINTER(ColourTable)]),
+    "ojphgpu_video_colour_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ColourSpec), C.POINTER(ColourTable), C.POINTER(ColourFrame),
+                                           C.POINTER(C.c_uint64)]),
+    "ojphgpu_enc_pipe_set_video_colour": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ColourSpec)]),
+    "ojphgpu_dec_pipe_set_video_colour": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ColourSpec)]),
     "ojphgpu_enc_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_dec_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_tc_pipe_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -996,6 +996,61 @@ def frame_resample(src, comps, container_bits, out=None):
     return out
 
 
+def colour_table(standard, direction, rgb_depth, ycc_depth, rgb_range="full", ycc_range="narrow"):
+    """ojphgpu_colour_table_make (host only): -> pipeline.ColourTable, entry for entry what pipeline.colour_table states"""
+    from .pipeline import ColourTable
+    t = capi.ColourTable()
+    try:
+        args = (capi.COLOUR_STANDARD[standard], capi.COLOUR_DIRECTION[direction], int(rgb_depth), int(ycc_depth), capi.COLOUR_RANGE[rgb_range],
+                capi.COLOUR_RANGE[ycc_range])
+    except KeyError as e:
+        raise ValueError("colour_table: %s" % e)
+    check(capi.lib().ojphgpu_colour_table_make(*args, C.byref(t)), "colour_table_make")
+    return ColourTable(tuple(tuple(int(x) for x in r) for r in t.m), tuple(int(x) for x in t.off), tuple(int(x) for x in t.lo),
+                       tuple(int(x) for x in t.hi), int(t.k))
+
+
+def _colour_stage(name, src, dst_count, table, width, height, fx, fy, rgb_first, ycc_first, dtype, out):
+    torch = _torch()
+    w, h, fx, fy = int(width), int(height), int(fx), int(fy)
+    assert src.is_cuda and src.is_contiguous() and src.element_size() in (1, 2, 4)
+    dev = src.device.index or 0
+    cw, ch = -(-w // max(fx, 1)), -(-h // max(fy, 1))
+    t = capi.ColourTable()
+    for c in range(3):
+        for i in range(3):
+            t.m[c][i] = int(table.m[c][i])
+        t.off[c], t.lo[c], t.hi[c] = int(table.off[c]), int(table.lo[c]), int(table.hi[c])
+    t.k = int(table.k)
+    f = capi.ColourFrame(w, h, fx, fy)
+    f.rgb_first[:] = [0, w * h, 2 * w * h] if rgb_first is None else [int(x) for x in rgb_first]
+    f.ycc_first[:] = [0, w * h, w * h + cw * ch] if ycc_first is None else [int(x) for x in ycc_first]
+    if out is None:
+        assert rgb_first is None and ycc_first is None, "%s: planes placed by hand need out=" % name
+        out = torch.zeros(dst_count(w, h, cw, ch), dtype=dtype if dtype is not None else src.dtype, device=src.device)
+    assert out.is_cuda and out.is_contiguous() and out.element_size() in (1, 2, 4)
+    with torch.cuda.device(dev):
+        check(getattr(capi.lib(), "ojphgpu_frame_" + name)(_stream_ptr(torch, dev), C.c_void_p(src.data_ptr()), src.element_size() * 8,
+                                                           C.c_void_p(out.data_ptr()), out.element_size() * 8, C.byref(f), C.byref(t)), name)
+        torch.cuda.synchronize(dev)
+    return out
+
+
+def rgb_to_ycc(d_rgb, table, width, height, fx=1, fy=1, dtype=None, out=None, rgb_first=None, ycc_first=None):
+    """ojphgpu_frame_rgb_to_ycc: d_rgb a device tensor of unsigned 8-, 16- or 32-bit containers (whatever the dtype's sign)
+    holding the planes R, G, B [H, W], tightly packed one after the other or each from its element of rgb_first; table: a
+    pipeline.ColourTable; fx, fy: the chroma cell (1 | 2 each) -> Y [H, W], Cb, Cr [ch, cw] as ONE flat tensor in `dtype`
+    (default: d_rgb's), or in `out` (its dtype is the container; only the planes' samples are written), each plane from its
+    element of ycc_first (default: one after the other).  pipeline.rgb_to_ycc states the arithmetic."""
+    return _colour_stage("rgb_to_ycc", d_rgb, lambda w, h, cw, ch: w * h + 2 * cw * ch, table, width, height, fx, fy, rgb_first, ycc_first, dtype, out)
+
+
+def ycc_to_rgb(d_ycc, table, width, height, fx=1, fy=1, dtype=None, out=None, rgb_first=None, ycc_first=None):
+    """ojphgpu_frame_ycc_to_rgb, the mirror: Y [H, W], Cb, Cr [ch, cw] in d_ycc -> R, G, B [H, W].  pipeline.ycc_to_rgb states
+    the arithmetic."""
+    return _colour_stage("ycc_to_rgb", d_ycc, lambda w, h, cw, ch: 3 * w * h, table, width, height, fx, fy, rgb_first, ycc_first, dtype, out)
+
+
 def dwt_general_image(direction, steps, elem, params: Params, descs: np.ndarray, image, arena, max_w, max_h, K=1.0, container=32):
     """ojphgpu_dwt_forward_general_image / _inverse_general_image: the general lifting kernels' top level with the conversion
     fused in (steps as for dwt_general; elem 0 = int32, 2 = float); descs as for dwt_image"""

@@ -145,14 +145,64 @@ struct Handover {
   uint32_t row_bytes = 0; uint64_t chroma_offset = 0; // VIDEO: the tight layout inside the staging buffer (video_layout)
   uint32_t w = 0, h = 0, depth = 0;                  // PIXELS, VIDEO: the (luma) plane; the depth a decoder clamps to
   size_t bytes = 0;                                  // of a frame as handed over: what _acquire / _collect report and PCIe carries
+  // VIDEO with a colour spec (_set_video_colour, ojphgpu.h section 7e): the buffer holds R, G, B, the plan Y, Cb, Cr.  depth:
+  // the RGB side's; table: forward for an encoder pipe, inverse for a decoder pipe; frame: where the six planes stand -- R, G,
+  // B w x h one after the other in the slot's `rgb` buffer, the plan's in its image
+  bool colour = false;
+  ojphgpu_colour_spec spec{};
+  ojphgpu_colour_table table{};
+  ojphgpu_colour_frame frame{};
+  size_t rgb_bytes = 0;                              // of the slot's `rgb` buffer: 3 w h containers
 };
+
+enum { ODD_X0 = 1, ODD_Y0 = 2 };                    // a decoder pipe's window begins on an odd column / row
+
+// The plan judgement of the two _set_video_colour setters (every refusal that needs no device): `want` (format, spec) -> the
+// rest of it.
+int handover_fit_colour(const Plan& P, int container, bool decoding, int odd_origin, Handover& want)
+{
+  const VideoDesc* v = video_desc(want.format, OJPHGPU_VIDEO_FAMILY_444); uint64_t bytes = 0;
+  if (!v || P.comps.size() != 3) return OJPHGPU_E_INVALID;
+  // the RGB members of the family; the others hold Y, Cb, Cr already
+  if (want.format != OJPHGPU_VIDEO_BGRA && want.format != OJPHGPU_VIDEO_RGBA && want.format != OJPHGPU_VIDEO_ARGB &&
+      want.format != OJPHGPU_VIDEO_R210 && want.format != OJPHGPU_VIDEO_R10K) return OJPHGPU_E_INVALID;
+  const CompGeo& Y = P.comps[0]; const CompGeo& Cb = P.comps[1]; const CompGeo& Cr = P.comps[2];
+  // three unsigned components of one depth of 8 .. 16 bits, the chroma planes (fx, fy) smaller, each factor 1 or 2
+  for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != Y.bit_depth) return OJPHGPU_E_INVALID;
+  if (Y.bit_depth < 8 || Y.bit_depth > 16 || Y.bit_depth > (uint32_t)container || Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
+  if (Y.dx != 1 || Y.dy != 1 || Cb.dx != Cr.dx || Cb.dy != Cr.dy || (Cb.dx != 1 && Cb.dx != 2) || (Cb.dy != 1 && Cb.dy != 2)) return OJPHGPU_E_INVALID;
+  const uint32_t fx = Cb.dx, fy = Cb.dy;
+  const uint32_t cw = (uint32_t)(((uint64_t)Y.w + fx - 1) / fx), ch = (uint32_t)(((uint64_t)Y.h + fy - 1) / fy);
+  if (Cb.w != cw || Cb.h != ch || Cr.w != cw || Cr.h != ch) return OJPHGPU_E_INVALID;
+  // a chroma sample stands ON the first luma sample of its cell (phase 0): no odd image offset, no window from an odd column
+  // or row, in a halved direction
+  if ((fx == 2 && ((P.p.image_x0 & 1u) || (odd_origin & ODD_X0))) || (fy == 2 && ((P.p.image_y0 & 1u) || (odd_origin & ODD_Y0)))) return OJPHGPU_E_INVALID;
+  if (P.has_region && P.skip_recon) {                 // a window at a reduced resolution: its origin is even on THAT grid
+    if (P.skip_recon > 30) return OJPHGPU_E_INVALID;
+    const uint32_t cell = 2u << P.skip_recon;
+    if ((fx == 2 && P.region[0] % cell) || (fy == 2 && P.region[1] % cell)) return OJPHGPU_E_INVALID;
+  }
+  // a decoder's 32-bit planes are int32 and may hold negative samples, which the stage's unsigned containers cannot say
+  if (decoding && container == 32) return OJPHGPU_E_INVALID;
+  const uint32_t rgb_depth = want.spec.rgb_depth ? want.spec.rgb_depth : Y.bit_depth;
+  if (!video_check(v, Y.w, Y.h, rgb_depth, container) || !video_layout(v, Y.w, Y.h, &want.row_bytes, &want.chroma_offset, &bytes)) return OJPHGPU_E_INVALID;
+  const int rc = ojphgpu_colour_table_make(want.spec.standard, decoding ? OJPHGPU_COLOUR_INVERSE : OJPHGPU_COLOUR_FORWARD, rgb_depth, Y.bit_depth,
+                                           want.spec.rgb_range, want.spec.ycc_range, &want.table);
+  if (rc) return rc;
+  const uint64_t wh = (uint64_t)Y.w * Y.h;
+  want.w = Y.w; want.h = Y.h; want.depth = rgb_depth;
+  want.frame = ojphgpu_colour_frame{ Y.w, Y.h, fx, fy, { 0, wh, 2 * wh }, { Y.frame_off, Cb.frame_off, Cr.frame_off } };
+  want.rgb_bytes = (size_t)(3 * wh) * (size_t)(container / 8);
+  want.bytes = (size_t)bytes;
+  return OJPHGPU_OK;
+}
 
 // Every refusal of the three setters, and the size of the frame: `want` (kind, bits, big_endian, format) -> the rest of it.
 // decoding: the frame comes back, clamped to one range; odd_origin: the pipe decodes a window whose first column (ODD_X0) or
 // first row (ODD_Y0) is odd.
-enum { ODD_X0 = 1, ODD_Y0 = 2 };
 int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Handover& want)
 {
+  if (want.kind == VIDEO && want.colour) return handover_fit_colour(P, container, decoding, odd_origin, want);
   const CompGeo& Y = P.comps[0];
   want.w = Y.w; want.h = Y.h; want.depth = 0;
   for (const CompGeo& g : P.comps) want.depth = std::max(want.depth, g.bit_depth);
@@ -196,8 +246,17 @@ int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Ha
 
 // The launch of a hand-over on `stream`: staged frame -> planes (unpack: the encoder) or planes -> staged frame, clamped
 // (the decoder).  Nothing for PLANES.
-int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int container, bool unpack, void* d_staged, void* d_planes)
+int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int container, bool unpack, void* d_staged, void* d_planes, void* d_rgb)
 {
+  if (h.kind == VIDEO && h.colour) {                  // two launches: the buffer <-> R, G, B planes <-> the plan's Y, Cb, Cr
+    int rc;
+    if (unpack) {
+      if ((rc = ojphgpu_unpack_video444(stream, h.format, d_staged, h.row_bytes, d_rgb, h.w, h.h, h.depth, container)) != 0) return rc;
+      return ojphgpu_frame_rgb_to_ycc(stream, d_rgb, container, d_planes, container, &h.frame, &h.table);
+    }
+    if ((rc = ojphgpu_frame_ycc_to_rgb(stream, d_planes, container, d_rgb, container, &h.frame, &h.table)) != 0) return rc;
+    return ojphgpu_pack_video444(stream, h.format, d_rgb, d_staged, h.row_bytes, h.w, h.h, container, h.depth);
+  }
   switch (h.kind) {
   case PIXELS:                                        // the file's / capture buffer's / display buffer's pixel order
     return unpack ? ojphgpu_unpack_pixels(stream, d_staged, d_planes, h.w, h.h, P.p.num_comps, h.bits, h.big_endian, container)
@@ -230,18 +289,19 @@ template <class Slot> void* handover_device_side(const Handover& h, Slot& s) { r
 // frame and staging buffer hold the new size -- both only grow, so the call may be repeated -- and the pipe takes the
 // hand-over.  A refusal changes nothing.
 template <class Pipe, class Slot>
-int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, int odd_origin, int kind, int arg, int big_endian)
+int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, int odd_origin, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr)
 {
-  if (p->ho.kind != PLANES && p->ho.kind != kind) return OJPHGPU_E_INVALID;
+  if (p->ho.kind != PLANES && (p->ho.kind != kind || p->ho.colour != (spec != nullptr))) return OJPHGPU_E_INVALID;   // (_set_video and _set_video_colour exclude each other too)
   return no_throw([&]() -> int {
     Handover h;
     h.kind = arg ? kind : PLANES; h.big_endian = big_endian ? 1 : 0;
     (kind == VIDEO ? h.format : h.bits) = arg;
+    if (spec && arg) { h.colour = true; h.spec = *spec; }
     const int rc = handover_fit(*p->P, p->container, decoding, odd_origin, h);
     if (rc) return rc;
     if (h.kind != PLANES) {
       HIPCHK(hipSetDevice(p->device));
-      for (Slot& s : p->slots) if ((s.*frame).reserve(h.bytes + 64) || s.pixels.reserve(h.bytes)) return OJPHGPU_E_NOMEM;
+      for (Slot& s : p->slots) if ((s.*frame).reserve(h.bytes + 64) || s.pixels.reserve(h.bytes) || s.rgb.reserve(h.rgb_bytes)) return OJPHGPU_E_NOMEM;
     }
     p->ho = h;
     return OJPHGPU_OK;
@@ -283,6 +343,7 @@ struct EncSlot {
   EncOut o;
   DeviceBuf image;
   Grow cs, pixels;                                  // pixels: the frame as it was handed over, unless that is as planes
+  Grow rgb;                                         // a hand-over with a colour spec: the R, G, B planes between its two launches
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   int rc = 0; size_t cs_len = 0;
   double t_submit = 0, t_done = 0, t_t2 = 0;
@@ -399,7 +460,7 @@ static int enc_begin_frame(ojphgpu_enc_pipe* p, EncSlot& s)
 {
   ojphgpu_encoder* e = p->enc;
   HIPCHK(hipStreamWaitEvent(p->s_comp, s.ev_in, 0));
-  const int rc = handover_launch(p->s_comp, p->ho, *p->P, p->container, true, s.pixels.b.p, s.image.p);
+  const int rc = handover_launch(p->s_comp, p->ho, *p->P, p->container, true, s.pixels.b.p, s.image.p, s.rgb.b.p);
   if (rc) return rc;
   e->o_out = s.o.out.p; e->o_results = s.o.h_res.d; e->o_counters = s.o.counters.p;
   return ojphgpu_encoder_run_container(e, s.image.p, p->container);
@@ -615,7 +676,7 @@ extern "C" void ojphgpu_enc_pipe_destroy(ojphgpu_enc_pipe* p)
   if (p->enc) ojphgpu_encoder_destroy(p->enc);
   for (EncSlot& s : p->slots) {
     s.h_in.release(); s.o.release(); s.h_lay.release(); s.h_cs.release();
-    for (DeviceBuf* b : { &s.image, &s.cs.b, &s.pixels.b }) b->release();
+    for (DeviceBuf* b : { &s.image, &s.cs.b, &s.pixels.b, &s.rgb.b }) b->release();
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
     delete s.rplan;
   }
@@ -683,15 +744,19 @@ extern "C" int ojphgpu_enc_pipe_acquire(ojphgpu_enc_pipe* p, void** h_frame, siz
 }
 
 // before the first _acquire: the hand-over may still be set (and set again)
-static int enc_set_handover(ojphgpu_enc_pipe* p, int kind, int arg, int big_endian)
+static int enc_set_handover(ojphgpu_enc_pipe* p, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr)
 {
   if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE) return OJPHGPU_E_INVALID;
-  return handover_set(p, &EncSlot::h_in, false, 0, kind, arg, big_endian);
+  return handover_set(p, &EncSlot::h_in, false, 0, kind, arg, big_endian, spec);
 }
 
 extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian) { return enc_set_handover(p, PIXELS, pixel_bits, big_endian); }
 extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits) { return enc_set_handover(p, PACKED, bits, 0); }
 extern "C" int ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* p, int format) { return enc_set_handover(p, VIDEO, format, 0); }
+extern "C" int ojphgpu_enc_pipe_set_video_colour(ojphgpu_enc_pipe* p, int format, const ojphgpu_colour_spec* spec)
+{
+  return spec ? enc_set_handover(p, VIDEO, format, 0, spec) : OJPHGPU_E_INVALID;
+}
 
 extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
 {
@@ -900,6 +965,7 @@ struct DecSlot {
   SlotState state = FREE;
   Pinned h_cs, h_descs, h_img, h_status;
   Grow data, pixels;                                // pixels: the frame as it is handed back, unless that is as planes
+  Grow rgb;                                         // a hand-over with a colour spec: the R, G, B planes between its two launches
   DeviceBuf image, cb_descs, status, runs;          // runs: a view's run table, copied there for the gather kernel
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   size_t cs_len = 0;
@@ -1007,7 +1073,7 @@ static void dec_process_frame(ojphgpu_dec_pipe* p, DecSlot& s)
         if (r3) return r3;
         epoch = d->fused_epoch; was_fused = d->last_fused;
         if (separate) d->fused_retries++;
-        if ((r3 = handover_launch(s_comp, p->ho, P, p->container, false, s.pixels.b.p, s.image.p)) != 0) return r3;   // planes -> the frame as it is handed back
+        if ((r3 = handover_launch(s_comp, p->ho, P, p->container, false, s.pixels.b.p, s.image.p, s.rgb.b.p)) != 0) return r3;   // planes -> the frame as it is handed back
         HIPCHK(hipEventRecord(s.ev_kern, s_comp));
       }
       HIPCHK(hipStreamWaitEvent(p->s_d2h, s.ev_kern, 0));
@@ -1071,7 +1137,7 @@ extern "C" void ojphgpu_dec_pipe_destroy(ojphgpu_dec_pipe* p)
   for (ojphgpu_decoder* d : p->decs) if (d) ojphgpu_decoder_destroy(d);
   for (DecSlot& s : p->slots) {
     s.h_cs.release(); s.h_descs.release(); s.h_img.release(); s.h_status.release();
-    for (DeviceBuf* b : { &s.data.b, &s.image, &s.cb_descs, &s.status, &s.pixels.b, &s.runs }) b->release();
+    for (DeviceBuf* b : { &s.data.b, &s.image, &s.cb_descs, &s.status, &s.pixels.b, &s.rgb.b, &s.runs }) b->release();
     for (hipEvent_t ev : { s.ev_in, s.ev_kern, s.ev_done }) if (ev) (void)hipEventDestroy(ev);
   }
   for (hipStream_t s : { p->s_h2d, p->s_comps[0], p->s_comps[1], p->s_comps[2], p->s_comps[3], p->s_d2h }) if (s) (void)hipStreamDestroy(s);
@@ -1211,16 +1277,39 @@ extern "C" int ojphgpu_dec_pipe_collect(ojphgpu_dec_pipe* p, const void** h_fram
 }
 
 // before the first _submit: the hand-over may still be set (and set again)
-static int dec_set_handover(ojphgpu_dec_pipe* p, int kind, int arg, int big_endian)
+static int dec_set_handover(ojphgpu_dec_pipe* p, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr)
 {
   if (!p || p->n_sub != 0) return OJPHGPU_E_INVALID;
   const int odd_origin = !p->has_region ? 0 : ((p->region[0] & 1u) ? ODD_X0 : 0) | ((p->region[1] & 1u) ? ODD_Y0 : 0);
-  return handover_set(p, &DecSlot::h_img, true, odd_origin, kind, arg, big_endian);
+  return handover_set(p, &DecSlot::h_img, true, odd_origin, kind, arg, big_endian, spec);
 }
 
 extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, int big_endian) { return dec_set_handover(p, PIXELS, pixel_bits, big_endian); }
 extern "C" int ojphgpu_dec_pipe_set_packed(ojphgpu_dec_pipe* p, int bits) { return dec_set_handover(p, PACKED, bits, 0); }
 extern "C" int ojphgpu_dec_pipe_set_video(ojphgpu_dec_pipe* p, int format) { return dec_set_handover(p, VIDEO, format, 0); }
+extern "C" int ojphgpu_dec_pipe_set_video_colour(ojphgpu_dec_pipe* p, int format, const ojphgpu_colour_spec* spec)
+{
+  return spec ? dec_set_handover(p, VIDEO, format, 0, spec) : OJPHGPU_E_INVALID;
+}
+
+// the judgement of the two setters above on a plan alone, without a pipe or a device
+extern "C" int ojphgpu_video_colour_fit(const ojphgpu_plan* plan, int container_bits, int decoding, int format, const ojphgpu_colour_spec* spec,
+                                        ojphgpu_colour_table* table, ojphgpu_colour_frame* frame, uint64_t* frame_bytes)
+{
+  if (!plan || !spec || (container_bits != 8 && container_bits != 16 && container_bits != 32)) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    const Plan& P = plan->plan;
+    Handover h;
+    h.kind = VIDEO; h.format = format; h.colour = true; h.spec = *spec;
+    const int odd_origin = !P.has_region ? 0 : ((P.region[0] & 1u) ? ODD_X0 : 0) | ((P.region[1] & 1u) ? ODD_Y0 : 0);
+    const int rc = handover_fit(P, container_bits, decoding != 0, odd_origin, h);
+    if (rc) return rc;
+    if (table) *table = h.table;
+    if (frame) *frame = h.frame;
+    if (frame_bytes) *frame_bytes = h.bytes;
+    return OJPHGPU_OK;
+  });
+}
 
 extern "C" int ojphgpu_dec_pipe_plan(ojphgpu_dec_pipe* p, const ojphgpu_plan** plan)
 {

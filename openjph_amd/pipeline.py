@@ -4,7 +4,9 @@ through restart() for the frames of a sequence (ojph_codestream.h:204): the call
 memory the library hands out and receives finished codestreams -- or the other way round -- `depth`
 frames in flight.  Plumbing only: ctypes views of the pipe's pinned host memory, no arithmetic here.
 """
+import collections
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -40,7 +42,7 @@ class _Handover:
     """The hand-over setters of both pipes (ojphgpu_{enc,dec}_pipe_set_pixels / _set_packed / _set_video; None or 0: planes
     again): before the first acquire() of an encoder pipe / submit() of a decoder pipe, repeatable until then, one kind at a
     time.  A refusal raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
-    pixels = packed = video = None
+    pixels = packed = video = colour = None
 
     def _set(self, kind, *args):
         name = "%s_pipe_set_%s" % (self._side, kind)
@@ -61,6 +63,16 @@ class _Handover:
         origin"""
         self._set("video", _video_code(self.plan, fmt, "%s_pipe_set_video" % self._side))
         self.video = fmt
+
+    def set_video_colour(self, fmt, colour):
+        """the buffer holds R, G, B (fmt = "bgra" | "rgba" | "argb" | "r210" | "r10k"), the plan Y, Cb, Cr 4:4:4, 4:2:2 or 4:2:0:
+        colour = a standard's name ("bt601" | "bt709" | "bt2020": full-range RGB of the plan's depth, narrow-range YCbCr) or a
+        Colour; the matrix, the ranges, the change of depth and the chroma filter run on the device between the buffer and the
+        planes (ojphgpu_{enc,dec}_pipe_set_video_colour; ojphgpu.h section 7e).  Excludes set_video; fmt None: planes again"""
+        spec = _colour_spec(colour)
+        self._set("video_colour", _video_code(self.plan, fmt, "%s_pipe_set_video_colour" % self._side), C.byref(spec))
+        self.video = fmt
+        self.colour = (colour if isinstance(colour, Colour) else Colour(colour)) if fmt else None
 
 
 def pack_bits(samples, bits):
@@ -372,18 +384,175 @@ def resample_frame(planes, factors, phases=None):
     return [resample_plane(q, fx, fy, px, py) for q, (fx, fy), (px, py) in zip(planes, factors, phases)]
 
 
+# RGB <-> YCbCr (ojphgpu.h section 7e): the numpy statement of ojphgpu_colour_table_make and of the two stages
+COLOUR_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}      # name -> (Kr, Kb)
+ColourTable = collections.namedtuple("ColourTable", "m off lo hi k")     # m: 3 x 3 ints, off / lo / hi: 3 ints, k: fraction bits
+
+
+class Colour(collections.namedtuple("Colour", "standard rgb_range ycc_range rgb_depth")):
+    """what a pipe's colour= takes beside a standard's name: the ranges, and the depth of the RGB side (0: the plan's)"""
+    def __new__(cls, standard, rgb_range="full", ycc_range="narrow", rgb_depth=0):
+        if standard not in COLOUR_STANDARDS or rgb_range not in ("full", "narrow") or ycc_range not in ("full", "narrow"):
+            raise ValueError("Colour: a standard of %s, ranges full or narrow" % ", ".join(sorted(COLOUR_STANDARDS)))
+        return super().__new__(cls, standard, rgb_range, ycc_range, int(rgb_depth))
+
+
+def _llround(x):                                      # C's llround: to nearest, halves away from zero
+    a = abs(x)
+    f = math.floor(a)
+    f += (a - f) >= 0.5                               # (a - f is exact)
+    return int(f) if x >= 0 else -int(f)
+
+
+def colour_range(depth, rng):
+    """-> (offset of RGB or luma, its span, offset of chroma, its span) of a depth-bit signal, full or narrow range"""
+    depth = int(depth)
+    if not 8 <= depth <= 16 or rng not in ("full", "narrow"):
+        raise ValueError("colour_range: depths 8 .. 16, full or narrow")
+    s = 1 << (depth - 8)
+    return (0, (1 << depth) - 1, 128 * s, (1 << depth) - 1) if rng == "full" else (16 * s, 219 * s, 128 * s, 224 * s)
+
+
+def colour_table(standard, direction, rgb_depth, ycc_depth, rgb_range="full", ycc_range="narrow"):
+    """numpy statement of ojphgpu_colour_table_make (include/ojphgpu.h section 7e): every double expression in the order the
+    library writes it -> ColourTable"""
+    if standard not in COLOUR_STANDARDS or direction not in ("forward", "inverse"):
+        raise ValueError("colour_table: a standard of %s, forward or inverse" % ", ".join(sorted(COLOUR_STANDARDS)))
+    Kr, Kb = COLOUR_STANDARDS[standard]
+    Kg = 1.0 - Kr - Kb
+    off_rgb, span_rgb_i, _, _ = colour_range(rgb_depth, rgb_range)
+    off_y, span_y, off_c, span_c = colour_range(ycc_depth, ycc_range)
+    off_ycc, span_rgb, span_ycc = (off_y, off_c, off_c), float(span_rgb_i), (float(span_y), float(span_c), float(span_c))
+    m = [[0] * 3 for _ in range(3)]
+    off = [0] * 3
+    if direction == "forward":
+        A = ((Kr, Kg, Kb),
+             (-Kr / (2.0 * (1.0 - Kb)), -Kg / (2.0 * (1.0 - Kb)), (1.0 - Kb) / (2.0 * (1.0 - Kb))),
+             ((1.0 - Kr) / (2.0 * (1.0 - Kr)), -Kg / (2.0 * (1.0 - Kr)), -Kb / (2.0 * (1.0 - Kr))))
+        for c in range(3):
+            m[c][0] = _llround(A[c][0] * span_ycc[c] / span_rgb * 65536.0)
+            m[c][2] = _llround(A[c][2] * span_ycc[c] / span_rgb * 65536.0)
+            total = _llround(span_ycc[0] / span_rgb * 65536.0) if c == 0 else 0
+            m[c][1] = total - m[c][0] - m[c][2]                  # green: the row's rounded total minus the other two
+            off[c] = (off_ycc[c] << 16) - off_rgb * sum(m[c])
+        top = (1 << int(ycc_depth)) - 1
+    else:
+        Ci = ((1.0, 0.0, 2.0 * (1.0 - Kr)),
+              (1.0, -(2.0 * Kb * (1.0 - Kb) / Kg), -(2.0 * Kr * (1.0 - Kr) / Kg)),
+              (1.0, 2.0 * (1.0 - Kb), 0.0))
+        for c in range(3):
+            for i in range(3):
+                m[c][i] = 0 if Ci[c][i] == 0.0 else _llround(Ci[c][i] * span_rgb / span_ycc[i] * 65536.0)
+            off[c] = (off_rgb << 16) - sum(m[c][i] * off_ycc[i] for i in range(3))
+        top = (1 << int(rgb_depth)) - 1
+    return ColourTable(tuple(tuple(r) for r in m), tuple(off), (0, 0, 0), (top, top, top), 16)
+
+
+def _wrap64(x):                                       # a Python int as the int64 of the same 64 bits
+    x = int(x) & 0xFFFFFFFFFFFFFFFF
+    return np.int64(x - (1 << 64) if x >> 63 else x)
+
+
+def _colour_spec(colour):
+    col = colour if isinstance(colour, Colour) else Colour(colour)
+    return capi.ColourSpec(capi.COLOUR_STANDARD[col.standard], capi.COLOUR_RANGE[col.rgb_range], capi.COLOUR_RANGE[col.ycc_range], col.rgb_depth)
+
+
+def video_colour_fit(plan, fmt, colour, container=16, decoding=False):
+    """ojphgpu_video_colour_fit: the judgement of set_video_colour on a plan alone, without a pipe or a device (OjphError
+    E_INVALID where the setter would refuse) -> dict(table = the ColourTable the pipe would use, fx, fy, bytes = of the RGB
+    buffer)"""
+    spec, t, f, n = _colour_spec(colour), capi.ColourTable(), capi.ColourFrame(), C.c_uint64()
+    check(capi.lib().ojphgpu_video_colour_fit(plan.handle, int(container), int(bool(decoding)), _video_code(plan, fmt, "video_colour_fit"), C.byref(spec),
+                                              C.byref(t), C.byref(f), C.byref(n)), "video_colour_fit")
+    table = ColourTable(tuple(tuple(int(x) for x in r) for r in t.m), tuple(int(x) for x in t.off), tuple(int(x) for x in t.lo),
+                        tuple(int(x) for x in t.hi), int(t.k))
+    return dict(table=table, fx=int(f.fx), fy=int(f.fy), bytes=int(n.value))
+
+
+def _colour_finish(acc, table, c, kk):
+    k = int(table.k)
+    with np.errstate(over="ignore"):
+        v = (acc + _wrap64(int(table.off[c]) << kk) + np.int64(1 << (k + kk - 1))) >> np.int64(k + kk)
+    return np.clip(v, int(table.lo[c]), int(table.hi[c]))
+
+
+def _colour_check(table, fx, fy):
+    if fx not in (1, 2) or fy not in (1, 2) or int(table.k) != 16:
+        raise ValueError("colour stage: factors are 1 or 2, k is 16")
+
+
+def rgb_to_ycc(planes, table, fx=1, fy=1):
+    """numpy statement of ojphgpu_frame_rgb_to_ycc (include/ojphgpu.h section 7e): planes = R, G, B [H, W] (unsigned samples as
+    they stand) -> [Y [H, W], Cb [ch, cw], Cr [ch, cw]] (int64), cw = ceil(W / 2) where fx == 2, ch alike.  Per pixel t_c = m[c]
+    . (R, G, B); a chroma sample stands ON source sample (fx i, fy j): taps (1, 2, 1) over t_c in every halved direction,
+    indices clamped into the plane (resample_plane's filter and siting at phase 0), one rounding, the clamp to [lo, hi].  All
+    sums in 64-bit two's complement."""
+    _colour_check(table, fx, fy)
+    a = [np.asarray(p).astype(np.int64) for p in planes]
+    if len(a) != 3 or a[0].ndim != 2 or a[0].size == 0 or a[1].shape != a[0].shape or a[2].shape != a[0].shape:
+        raise ValueError("rgb_to_ycc: three planes [H, W] of one size")
+    h, w = a[0].shape
+
+    def taps(n, f):
+        if f == 1:
+            return [(np.arange(n), 1)]
+        c = 2 * np.arange((n + 1) // 2)
+        return [(np.clip(c - 1, 0, n - 1), 1), (c, 2), (np.clip(c + 1, 0, n - 1), 1)]
+    out = []
+    with np.errstate(over="ignore"):
+        for c in range(3):
+            t = sum(_wrap64(table.m[c][i]) * a[i] for i in range(3))
+            gx, gy = (fx, fy) if c else (1, 1)
+            acc = 0
+            for iy, wy in taps(h, gy):
+                for ix, wx in taps(w, gx):
+                    acc = acc + np.int64(wy * wx) * t[np.ix_(iy, ix)]
+            out.append(_colour_finish(acc, table, c, 2 * ((gx == 2) + (gy == 2))))
+    return out
+
+
+def ycc_to_rgb(planes, table, fx=1, fy=1):
+    """numpy statement of ojphgpu_frame_ycc_to_rgb: planes = Y [H, W], Cb, Cr [ch, cw] (samples as they stand, not clamped
+    first) -> [R, G, B] [H, W] (int64).  Chroma at luma column x of a halved direction: 2 C[x / 2] for even x, C[(x - 1) / 2] +
+    C[min((x + 1) / 2, cw - 1)] for odd x; rows alike, the product in 2-D; luma enters as Y << kk, kk = 1 per halved direction;
+    the matrix, one rounding, the clamp to [lo, hi]."""
+    _colour_check(table, fx, fy)
+    y, cb, cr = [np.asarray(p).astype(np.int64) for p in planes]
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError("ycc_to_rgb: the luma plane is [H, W]")
+    h, w = y.shape
+    cw, ch = (w + 1) // 2 if fx == 2 else w, (h + 1) // 2 if fy == 2 else h
+    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
+        raise ValueError("ycc_to_rgb: chroma planes of %s and %s, not %s" % (cb.shape, cr.shape, (ch, cw)))
+
+    def pair(n, nc, f):                               # the two chroma samples under each of n luma positions (weights 1, 1)
+        x = np.arange(n)
+        if f == 1:
+            return [x]
+        return [x // 2, np.where(x & 1, np.minimum((x + 1) // 2, nc - 1), x // 2)]
+    kk = (fx == 2) + (fy == 2)
+    v = [y << np.int64(kk)]
+    for q in (cb, cr):
+        v.append(sum(q[np.ix_(iy, ix)] for iy in pair(h, ch, fy) for ix in pair(w, cw, fx)))
+    with np.errstate(over="ignore"):
+        return [_colour_finish(sum(_wrap64(table.m[c][i]) * v[i] for i in range(3)), table, c, kk) for c in range(3)]
+
+
 class EncoderPipe(_Handover):
     _side = "enc"
 
     def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None,
-                 max_sse=None, min_psnr=None, video=None, cap_bytes=0, **kw):
+                 max_sse=None, min_psnr=None, video=None, cap_bytes=0, colour=None, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
         the device.  video="uyvy" | "yuy2" | "v210" | "y210" | "y212" | "y216": the frames are handed over as one 4:2:2 video
         buffer (uint8 [H, row_bytes], pack_video's layout) and unpacked on the device; video="nv12" | "nv21" | "p010" | "p012" |
         "p016": as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420's tight layout); video="v410" | "y410" |
         "r210" | "r10k" | "y412" | "y416" | "ayuv" | "bgra" | "rgba" | "argb": as one 4:4:4 packed buffer (uint8 [H, row_bytes],
-        pack_video444's layout).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
+        pack_video444's layout).  colour="bt601" | "bt709" | "bt2020" or a Colour, with one of the RGB names among them ("bgra" |
+        "rgba" | "argb" | "r210" | "r10k"): the buffer holds R, G, B and is coded as the plan's Y, Cb, Cr -- 4:4:4, 4:2:2 or 4:2:0
+        -- converted on the device (set_video_colour).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
         quality target (set_quality) -- one or the other; cap_bytes=N with a target: to the target, but never above N bytes
         (set_quality(..., cap_bytes=N); from the start, or never)"""
         from .codec import _torch
@@ -401,7 +570,11 @@ class EncoderPipe(_Handover):
             self.set_pixels(*pixels)
         if packed:
             self.set_packed(packed)
-        if video is not None:
+        if colour is not None and video is None:
+            raise ValueError("colour= goes with video= (an RGB format)")
+        if colour is not None:
+            self.set_video_colour(video, colour)
+        elif video is not None:
             self.set_video(video)
         if max_bytes:
             self.set_budget(max_bytes)
@@ -560,12 +733,14 @@ class DecoderPipe(_Handover):
     _side = "dec"
 
     def __init__(self, first_codestream: bytes, device=0, depth=4, container=16, host_threads=0, resilient=False, pixels=None, packed=None,
-                 skip_res=None, region=None, video=None):
+                 skip_res=None, region=None, video=None, colour=None):
         """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
         skip_res=n or (for_data, for_recon), region=(x0, y0, w, h): the pipe decodes that view of every frame, as
         video="uyvy" | ...: they come back as one 4:2:2 video buffer (uint8 [H, row_bytes], pack_video of the planes);
         video="nv12" | "nv21" | "p010" | ...: as one 4:2:0 video buffer (uint8 [H + ceil(H / 2), row_bytes], pack_video420 of them);
         video="v410" | "bgra" | ...: as one 4:4:4 packed buffer (uint8 [H, row_bytes], pack_video444 of them).
+        colour="bt709" | ... or a Colour, with video="bgra" | "rgba" | "argb" | "r210" | "r10k": the decoded Y, Cb, Cr planes (4:4:4,
+        4:2:2 or 4:2:0) come back as that RGB buffer, converted on the device (set_video_colour).
         codec.Decoder takes them (ojphgpu_dec_pipe_create_view); .plan, the frames and pixels / packed are the view's"""
         from .codec import _torch
         _torch()
@@ -586,7 +761,11 @@ class DecoderPipe(_Handover):
             self.set_pixels(*pixels)
         if packed:
             self.set_packed(packed)
-        if video is not None:
+        if colour is not None and video is None:
+            raise ValueError("colour= goes with video= (an RGB format)")
+        if colour is not None:
+            self.set_video_colour(video, colour)
+        elif video is not None:
             self.set_video(video)
         self.in_flight = 0
 

@@ -15,6 +15,11 @@ holds each against the kernel of those with the nearest bytes per launch in its 
 against the same pipe fed planes in 16-bit containers and fed the 10-bit string of packed=10; its default --out is
 profiles/video444_bench.txt.
 
+--colour measures the two stages of kernels_colour.hip instead (ojphgpu_frame_rgb_to_ycc / _ycc_to_rgb, 16-bit containers, to and
+from 4:2:2 and 4:2:0) beside ojphgpu_frame_resample (the same taps: a 4:4:4 int32 frame to 4:2:2 / 4:2:0 in 16-bit containers) and
+ojphgpu_unpack_video444 (r210 into 16-bit containers) on the same frame in the same rounds, and runs EncoderPipe(video="r210",
+colour="bt709") against EncoderPipe(video="v410") on the same 4:4:4 10-bit plan; its default --out is profiles/colour_bench.txt.
+
 1. Every instantiation of ojphgpu_unpack_video / _pack_video (format x container), bytes read plus written per second, beside
    the yardstick: ojphgpu_unpack_pixels / _pack_pixels with 3 components, 16-bit samples into 16-bit containers, on the same
    number of pixels -- the same kind of copy.  All of them alternate inside every round; a kernel runs `reps` launches per
@@ -129,6 +134,91 @@ def kernel_rates_444(torch, rounds, reps, emit):
             note = "   %s %s (%.1f)" % ("reaches" if o["reaches_peer"] else "BELOW", peer, out[peer]["median"])
         emit("  %-40s %s  median %7.1f  spread %4.1f %%  %5.1f MB, %5.1f us per launch%s" %
              (name, " ".join("%7.1f" % x for x in o["GBps"]), o["median"], o["spread"] * 100, o["bytes"] / 1e6, o["us_per_launch"], note))
+    return out
+
+
+def kernel_rates_colour(torch, rounds, reps, emit):
+    """both colour stages to and from 4:2:2 and 4:2:0 in 16-bit containers, the resample stage with the same factors and the
+    r210 unpack, alternating inside every round; launches go straight to the C ABI, nothing waits between them"""
+    import ctypes as C
+    from openjph_amd import capi, codec
+    from openjph_amd.pipeline import colour_table, video444_layout
+    L, st = capi.lib(), codec._stream_ptr(torch, 0)
+    work = {}
+
+    def c_table(t):
+        ct = capi.ColourTable()
+        for c in range(3):
+            for i in range(3):
+                ct.m[c][i] = t.m[c][i]
+            ct.off[c], ct.lo[c], ct.hi[c] = t.off[c], t.lo[c], t.hi[c]
+        ct.k = t.k
+        return ct
+    fwd, inv = c_table(colour_table("bt709", "forward", DEPTH, DEPTH)), c_table(colour_table("bt709", "inverse", DEPTH, DEPTH))
+    rgb = [torch.randint(0, 1 << DEPTH, (3 * W * H,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(NSETS)]
+    ycc = [torch.randint(0, 1 << DEPTH, (3 * W * H,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(NSETS)]
+    src32 = [torch.randint(0, 1 << DEPTH, (3 * W * H,), dtype=torch.int32, device="cuda") for _ in range(NSETS)]
+    for name, fx, fy in (("4:2:2", 2, 1), ("4:2:0", 2, 2)):
+        cw, ch = (W + fx - 1) // fx, (H + fy - 1) // fy
+        f = capi.ColourFrame(W, H, fx, fy)
+        f.rgb_first[:] = [0, W * H, 2 * W * H]
+        f.ycc_first[:] = [0, W * H, W * H + cw * ch]
+        moved = (3 * W * H + W * H + 2 * cw * ch) * 2
+        work["rgb_to_ycc 16 -> 16 %s" % name] = (lambda i, f=f: codec.check(L.ojphgpu_frame_rgb_to_ycc(st, C.c_void_p(rgb[i].data_ptr()), 16, C.c_void_p(ycc[i].data_ptr()), 16, C.byref(f), C.byref(fwd)), "rgb_to_ycc"), moved)
+        work["ycc_to_rgb 16 -> 16 %s" % name] = (lambda i, f=f: codec.check(L.ojphgpu_frame_ycc_to_rgb(st, C.c_void_p(ycc[i].data_ptr()), 16, C.c_void_p(rgb[i].data_ptr()), 16, C.byref(f), C.byref(inv)), "ycc_to_rgb"), moved)
+        comps = np.zeros(3, codec.resample_comp_dtype)
+        at = 0
+        for c, (gx, gy) in enumerate(((1, 1), (fx, fy), (fx, fy))):
+            dw, dh = (W + gx - 1) // gx, (H + gy - 1) // gy
+            comps[c] = (c * W * H, at, W, H, dw, dh, gx, gy, 0, 0, 0, 0, (1 << DEPTH) - 1, 0)
+            at += dw * dh
+        d_comps = codec.to_device(comps, 0)
+        work["frame_resample 32 -> 16 %s (the same taps)" % name] = (lambda i, d=d_comps: codec.check(L.ojphgpu_frame_resample(st, C.c_void_p(src32[i].data_ptr()), C.c_void_p(ycc[i].data_ptr()), 16, C.c_void_p(d.data_ptr()), 3), "frame_resample"),
+                                                                    3 * W * H * 4 + at * 2)
+    total = video444_layout("r210", W, H)[1]
+    vid = [torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda") for _ in range(NSETS)]
+    work["unpack r210 -> 16"] = (lambda i: codec.check(L.ojphgpu_unpack_video444(st, 0x23, C.c_void_p(vid[i].data_ptr()), 4 * W, C.c_void_p(rgb[i].data_ptr()), W, H, DEPTH, 16), "unpack_video444"),
+                                 total + 3 * W * H * 2)
+    rates = timed_rounds(torch, work, rounds, reps)
+    emit("1. kernels, %d x %d, TB/s read + written; %d rounds of %d launches" % (W, H, rounds, reps))
+    out = {}
+    for name, v in rates.items():
+        med, spread = median_spread(v)
+        out[name] = {"GBps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "bytes": work[name][1],
+                     "us_per_launch": round(work[name][1] / med / 1e3, 2)}
+        emit("  %-46s %s  median %6.3f TB/s  spread %4.1f %%  %5.1f MB, %6.1f us per launch" %
+             (name, " ".join("%6.3f" % (x / 1e3) for x in v), med / 1e3, spread * 100, work[name][1] / 1e6, out[name]["us_per_launch"]))
+    return out
+
+
+def pipe_rates_colour(rounds, frames, depth, emit):
+    """EncoderPipe on the 8K 10-bit 4:4:4 plan fed one v410 buffer (no colour stage) against the same plan fed one r210 buffer
+    with colour="bt709" (unpack + the forward stage), alternating rounds: the difference is the stage's cost in the overlap"""
+    from bench import workload_image
+    from openjph_amd.pipeline import EncoderPipe, pack_video444
+    from openjph_amd.plan import Plan, make_params
+    img = workload_image("c3_8k_444_12b_irv97")
+    assert img.shape == (3, H, W), img.shape
+    planes = [np.ascontiguousarray(img[c] >> 2) for c in range(3)]
+    mk = lambda: Plan(make_params(W, H, 3, bit_depth=DEPTH, reversible=False))
+    pipes = {"v410": EncoderPipe(plan=mk(), depth=depth, container=16, video="v410"),
+             "r210+bt709": EncoderPipe(plan=mk(), depth=depth, container=16, video="r210", colour="bt709")}
+    frame = {"v410": pack_video444(planes, "v410", DEPTH), "r210+bt709": pack_video444(planes, "r210", DEPTH)}
+    first = {way: fill_and_drain(p, frame[way]) for way, p in pipes.items()}
+    fps = {way: [] for way in pipes}
+    for _ in range(rounds):
+        for way, p in pipes.items():
+            fps[way].append(frames / steady(p, frames))
+    for p in pipes.values():
+        p.close()
+    out = {}
+    emit("2. EncoderPipe, %d x %d 4:4:4 %d-bit 9/7, depth %d, %d frames per round, codestreams %s bytes" %
+         (W, H, DEPTH, depth, frames, " / ".join(str(len(first[w])) for w in pipes)))
+    for way, v in fps.items():
+        med, spread = median_spread(v)
+        out[way] = {"fps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "ms_per_frame": round(1e3 / med, 3)}
+        emit("  %-11s frames/s per round %s  median %7.1f  spread %4.1f %%  %6.3f ms per frame" %
+             (way, " ".join("%7.1f" % x for x in v), med, spread * 100, 1e3 / med))
     return out
 
 
@@ -307,12 +397,13 @@ def main():
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--v420", action="store_true", help="the 4:2:0 kernels and a p010 pipe beside the yardstick and their 4:2:2 peers")
     ap.add_argument("--v444", action="store_true", help="the 4:4:4 kernels and a v410 pipe beside the yardstick, the P010 kernels, planes and packed=10")
+    ap.add_argument("--colour", action="store_true", help="the RGB <-> YCbCr stages beside the resample stage and the r210 unpack; an r210 + colour pipe against a v410 pipe")
     ap.add_argument("--frame", default=None, metavar="WxH", help="another frame size for the kernels (the pipes are then left out): what a rate owes to the bytes of a launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                "video444_bench.txt" if args.v444 else "video420_bench.txt" if args.v420 else "video_bench.txt")
+                                "colour_bench.txt" if args.colour else "video444_bench.txt" if args.v444 else "video420_bench.txt" if args.v420 else "video_bench.txt")
     global W, H
     if args.frame:
         W, H = (int(v) for v in args.frame.lower().split("x"))
@@ -325,14 +416,14 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --v444" if args.v444 else " --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
+    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --colour" if args.colour else " --v444" if args.v444 else " --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
                                                                                      args.depth, torch.cuda.get_device_name(0)))
-    kernels = kernel_rates_444(torch, args.rounds, args.reps, emit) if args.v444 else kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
+    kernels = kernel_rates_colour(torch, args.rounds, args.reps, emit) if args.colour else kernel_rates_444(torch, args.rounds, args.reps, emit) if args.v444 else kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
     torch.cuda.empty_cache()
     if args.frame:
         pipes = {}
     else:
-        pipes = pipe_rates_444(args.rounds, args.frames, args.depth, emit) if args.v444 else pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420)
+        pipes = pipe_rates_colour(args.rounds, args.frames, args.depth, emit) if args.colour else pipe_rates_444(args.rounds, args.frames, args.depth, emit) if args.v444 else pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print(json.dumps({"kernels": kernels, "pipes": pipes}))
