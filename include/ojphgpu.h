@@ -727,8 +727,37 @@ int  ojphgpu_decoder_upload_frame(ojphgpu_decoder* dec, uint32_t frame, const ui
 void ojphgpu_decoder_destroy(ojphgpu_decoder* dec);
 /* H2D of the codestream bytes */
 int  ojphgpu_decoder_upload(ojphgpu_decoder* dec, const uint8_t* h_codestream, size_t len);
-/* device part only: coded bytes in HBM -> d_image (int32 planes) */
+/* device part only: coded bytes in HBM -> d_image (int32 planes).
+ * What a run orders (all ojphgpu_decoder_run_device*): d_image is WRITTEN IN THE ORDER OF THE DECODER'S STREAM -- only the
+ * top synthesis level (and a stand-alone conversion) touches it, and they are enqueued on that stream; work enqueued there
+ * before the call is complete before the first sample lands, work enqueued behind it sees the whole frame.  A plain run of
+ * a single-frame decoder made by ojphgpu_decoder_create (or _create_tiles over all tiles) whose block decoder is the one
+ * launch (blocks at most 64 wide and 64 rows tall, no refinement passes, at least two decompositions), whole frames, with
+ * per-launch timing off (ojphgpu_decoder_set_timing(dec, 0)), is RELEASED: the block decoder -- which reads the object's
+ * codestream bytes and descriptors and writes its own coefficient planes, records and status, nothing of the caller's --
+ * runs on a stream of the object's own.  There it is ordered behind the object's last upload and behind the last
+ * synthesis that read the planes it writes, NOT behind the caller's stream: it starts beside whatever that stream still
+ * holds (the synthesis of the run before, an encode's first transform level).  The caller's stream waits for it in front
+ * of the synthesis levels, which stay on the caller's stream (OJPHGPU_DEC_AHEAD_LEVELS=1 at creation: levels L..2 follow
+ * the block decoder on the own stream and the caller's stream waits in front of the top level; measured slower).  An
+ * object that can release takes its uploads (ojphgpu_decoder_upload*) on the same own stream and makes the caller's stream
+ * wait for them: a caller that synchronises its stream may reuse the host buffer as before, and a fresh decoder on a busy
+ * stream gets its upload and block decoder beside the work already queued.  It holds its coefficient planes TWICE
+ * (released runs alternate; the block decoder of run n + 1 waits for the synthesis of run n - 1 only: + 0.4 GB at 8K
+ * 4:4:4); OJPHGPU_DEC_SETS=1 in the environment at creation keeps one (it then waits for run n).
+ * Every other run (per-launch timing on, which is the default; a batch; a region; a tile range; a frame with one
+ * decomposition; the separate launches; the decoders of pipes, transcoders, recoders and multi-device decoders;
+ * OJPHGPU_NO_OVERLAP=1 or OJPHGPU_DEC_RELEASE=0 at creation) is enqueued on the caller's stream as before, behind every
+ * released run of the object.  What settles a released run (makes the caller's stream wait for everything the own stream
+ * holds, without a host synchronisation, before it reads status or planes): ojphgpu_decoder_failed_blocks, the timing
+ * getters, ojphgpu_decoder_set_timing, ojphgpu_decoder_giveup_epoch (which also drains the own stream), a run of the other
+ * schedule; ojphgpu_decoder_destroy drains the own stream.  The samples are the same either way.
+ * OJPHGPU_DEC_AHEAD_PRIO=high|normal|low: priority of the own stream (default high, as the side stream always was); read
+ * at creation.  Stream capture: a released run forks to the own stream and joins it again inside the call, but waits there
+ * for events of earlier runs and uploads; capture runs with per-launch timing on or under OJPHGPU_DEC_RELEASE=0. */
 int  ojphgpu_decoder_run_device(ojphgpu_decoder* dec, int32_t* d_image);
+/* diagnostic (tests, tools): *pending = 1 while a released run of the object has not been settled by one of the calls above */
+int  ojphgpu_decoder_pending(const ojphgpu_decoder* dec, int* pending);
 int  ojphgpu_decoder_run_device16(ojphgpu_decoder* dec, uint16_t* d_image);     /* 16-bit containers */
 int  ojphgpu_decoder_run_device8(ojphgpu_decoder* dec, uint8_t* d_image);       /* 8-bit containers */
 int  ojphgpu_decode16(ojphgpu_decoder* dec, const uint8_t* h_codestream, size_t len, uint16_t* h_image);

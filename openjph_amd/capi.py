@@ -355,6 +355,7 @@ SIGNATURES = {
     "ojphgpu_encoder_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_encoder_is_pending": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "ojphgpu_decoder_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    "ojphgpu_decoder_pending": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "ojphgpu_encoder_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "ojphgpu_decoder_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "ojphgpu_encoder_level_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -412,6 +412,13 @@ class Decoder:
     def set_timing(self, per_launch: bool):
         check(self._lib.ojphgpu_decoder_set_timing(self._h, int(per_launch)), "decoder_set_timing")
 
+    def pending(self):
+        """a released run of this decoder has not been settled yet (by failed_blocks, timing, set_timing, giveup_epoch, a run
+        of the other schedule); include/ojphgpu.h, ojphgpu_decoder_run_device"""
+        n = C.c_int()
+        check(self._lib.ojphgpu_decoder_pending(self._h, C.byref(n)), "decoder_pending")
+        return bool(n.value)
+
     def failed_blocks(self):
         n = C.c_uint32()
         check(self._lib.ojphgpu_decoder_failed_blocks(self._h, C.byref(n)), "decoder_failed_blocks")

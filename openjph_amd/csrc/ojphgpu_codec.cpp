@@ -1241,9 +1241,13 @@ extern "C" void ojphgpu_decoder_destroy(ojphgpu_decoder* d)
 {
   if (!d) return;
   (void)hipSetDevice(d->device);
-  for (DeviceBuf* b : { &d->arena, &d->image, &d->dwt_descs, &d->img_descs, &d->cb_descs, &d->conv_descs, &d->data, &d->status, &d->quads, &d->aux,
-                       &d->fstate, &d->dwt_regs, &d->img_regs })
+  // a released run may still be decoding, an upload still copying, on the object's own stream: nothing is freed under them
+  if (d->can_release && d->side) (void)hipStreamSynchronize(d->side);
+  d->pending = false;
+  for (DeviceBuf* b : { &d->arena, &d->arena2, &d->image, &d->dwt_descs, &d->img_descs, &d->cb_descs, &d->conv_descs, &d->data, &d->status, &d->quads,
+                       &d->aux, &d->fstate, &d->dwt_regs, &d->img_regs })
     b->release();
+  for (hipEvent_t ev : { d->ev_done, d->ev_up, d->ev_read, d->ev_read2 }) if (ev) (void)hipEventDestroy(ev);
   if (d->h_retry) (void)hipHostFree(d->h_retry);
   if (d->h_stage) (void)hipHostFree(d->h_stage);
   if (d->ev_stage) (void)hipEventDestroy(d->ev_stage);
@@ -1262,11 +1266,18 @@ extern "C" int ojphgpu_decoder_create(const ojphgpu_plan* plan, int device, void
 
 // blocks_only: the decoder half of a transcoder (section 5d) -- the block decoder alone: no level batches, no conversion
 static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, int device, void* stream, uint32_t tile_first,
-                          uint32_t tile_count, ojphgpu_decoder** out, bool blocks_only = false);
+                          uint32_t tile_count, ojphgpu_decoder** out, bool blocks_only = false, bool may_release = false);
 
 extern "C" int ojphgpu_decoder_create_tiles(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first,
                                              uint32_t tile_count, ojphgpu_decoder** out)
 {
+  return no_throw([&] { return decoder_create(&plan, 1, device, stream, tile_first, tile_count, out, false, true); });
+}
+
+// the decoder of a frame pipe or of a multi-device decoder: its runs never release (ojphgpu_objects.h)
+int ojphgpu_decoder_create_joined(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count, ojphgpu_decoder** out)
+{
+  if (!plan) return OJPHGPU_E_INVALID;
   return no_throw([&] { return decoder_create(&plan, 1, device, stream, tile_first, tile_count, out); });
 }
 
@@ -1431,7 +1442,7 @@ int ojphgpu_decoder_upload_pads(hipStream_t s, uint8_t* d_frame_data, const uint
 }
 
 static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, int device, void* stream, uint32_t tile_first,
-                          uint32_t tile_count, ojphgpu_decoder** out, bool blocks_only)
+                          uint32_t tile_count, ojphgpu_decoder** out, bool blocks_only, bool may_release)
 {
   if (!plans || !plans[0] || !out || nframes == 0) return OJPHGPU_E_INVALID;
   *out = nullptr;
@@ -1493,8 +1504,13 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
     d->n_low = (uint32_t)(mid - ids.begin());
     int prio_lo = 0, prio_hi = 0;                         // the short launches of the side stream go first at the dispatcher
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    int prio = prio_hi;
+    // (a decoder that may release runs its block launch there too: OJPHGPU_DEC_AHEAD_PRIO, read once, here)
+    const char* ahead_prio = may_release && !blocks_only && !P.has_region ? getenv("OJPHGPU_DEC_AHEAD_PRIO") : nullptr;
+    if (ahead_prio && !strcmp(ahead_prio, "low")) prio = prio_lo;
+    else if (ahead_prio && !strcmp(ahead_prio, "normal")) prio = (prio_lo + prio_hi) / 2;
     if (d->n_low == 0 || d->n_low == ids.size()) d->n_low = 0;
-    else if (hipStreamCreateWithPriority(&d->side, hipStreamNonBlocking, prio_hi) != hipSuccess ||
+    else if (hipStreamCreateWithPriority(&d->side, hipStreamNonBlocking, prio) != hipSuccess ||
              hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming) != hipSuccess ||
              hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
   }
@@ -1552,6 +1568,24 @@ static int decoder_create(const ojphgpu_plan* const* plans, uint32_t nframes, in
     if (hipEventCreateWithFlags(&d->ev_stage, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
   }
   if (d->timer.init() != 0) return bail(OJPHGPU_E_HIP);
+  // Released runs (ojphgpu_objects.h): only an object that would release its next run as it stands -- the switches are read
+  // once, here -- holds the events, takes its uploads on its own stream and, unless OJPHGPU_DEC_SETS=1, a second arena
+  const char* rel = getenv("OJPHGPU_DEC_RELEASE"); const char* sets = getenv("OJPHGPU_DEC_SETS"); const char* lv = getenv("OJPHGPU_DEC_AHEAD_LEVELS");
+  d->can_release = may_release && !(rel && !strcmp(rel, "0")) && getenv("OJPHGPU_NO_OVERLAP") == nullptr &&
+                   tile_first == 0 && tile_count == P.tiles.size();   // (a tile range is one worker's share of a frame: collected on the spot)
+  d->timer.detail = false;
+  d->can_release = d->can_release && decoder_releases(d);
+  d->timer.detail = true;
+  if (d->can_release) {
+    d->ahead_levels = lv && !strcmp(lv, "1");               // (measured: the block launch alone wins)
+    d->two_arenas = !(sets && !strcmp(sets, "1"));
+    for (hipEvent_t* ev : { &d->ev_done, &d->ev_up, &d->ev_read, &d->ev_read2 })
+      if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return bail(OJPHGPU_E_HIP);
+    if (d->two_arenas) {                                    // the second arena, exactly as the first
+      if (d->arena2.alloc(P.arena_elems * 4)) return bail(OJPHGPU_E_NOMEM);
+      if (hipMemset(d->arena2.p, 0, P.arena_elems * 4) != hipSuccess) return bail(OJPHGPU_E_HIP);
+    }
+  }
   owner.p = nullptr;
   *out = d;
   return OJPHGPU_OK;
@@ -1584,10 +1618,25 @@ extern "C" int ojphgpu_decoder_upload_frame(ojphgpu_decoder* d, uint32_t frame, 
     return ojphgpu_decoder_upload_pads(d->stream, (uint8_t*)d->data.p + d->f_base[frame], h_codestream, len, d->f_pads[frame]);
   }
   if (len < d->f_first[frame] + d->f_len[frame]) return OJPHGPU_E_INVALID;
+  // A decoder that can release copies on its own stream: in order behind the last block launch that read `data` (a joined
+  // run's sits on the caller's stream: decoder_own_follows_joined) and in front of the next one, beside whatever the
+  // caller's stream still holds.  The caller's stream follows (ev_up), so a caller that synchronises it may reuse the
+  // host buffer, and a joined run reads the new bytes.
+  hipStream_t us = d->stream;
+  if (d->can_release) {
+    int rc = decoder_own_follows_joined(d);
+    if (rc) return rc;
+    us = d->side;
+  }
   if (d->f_len[frame])
     HIPCHK(hipMemcpyAsync((uint8_t*)d->data.p + d->f_base[frame], h_codestream + d->f_first[frame], d->f_len[frame],
-                          hipMemcpyHostToDevice, d->stream));
-  return ojphgpu_decoder_upload_pads(d->stream, (uint8_t*)d->data.p + d->f_base[frame], h_codestream, len, d->f_pads[frame]);
+                          hipMemcpyHostToDevice, us));
+  const int rc = ojphgpu_decoder_upload_pads(us, (uint8_t*)d->data.p + d->f_base[frame], h_codestream, len, d->f_pads[frame]);
+  if (d->can_release) {                                     // (also behind a copy that failed half way)
+    HIPCHK(hipEventRecord(d->ev_up, d->side));
+    HIPCHK(hipStreamWaitEvent(d->stream, d->ev_up, 0));
+  }
+  return rc;
 }
 
 // prep + step 1 of every block (one launch each: step 1 costs one serial chain however few blocks it gets)
@@ -1635,12 +1684,13 @@ static int decode_samples(ojphgpu_decoder* d, hipStream_t s, uint32_t first, uin
 }
 
 // The synthesis of a run, from the level batches through the conversion: the sub-band planes in the decoder's arena ->
-// d_image.  n_low != 0: the levels below the top run on the side stream (forked by the caller) and finish_blocks -- the
-// rest of the block decoder on the main stream, then the join; it sets `joined` -- is called before the top level.  What
+// d_image.  low != null: the levels below the top run on that stream (forked by the caller) and finish_blocks -- the
+// rest of the block decoder on the main stream (a released run: nothing), then the join; it sets `joined` -- is called
+// before the top level.  What
 // ojphgpu_decoder_run_container issues behind its block decoder, and all that the synthesis-only decoder of an encoder
 // with a quality target (section 5c) ever issues: one schedule, so a trial of that search sees the decoder's own samples.
 template <typename F>
-static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, uint32_t n_low, bool& joined, F finish_blocks)
+static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, hipStream_t low, bool& joined, F finish_blocks)
 {
   const Plan& P = *d->P;
   hipStream_t s = d->stream;
@@ -1648,8 +1698,8 @@ static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, u
   int rc = OJPHGPU_OK;
   for (const LevelBatch& b : d->batches) {
     const bool top = b.depth == 0;                          // the last level of its components (there may be two such launches)
-    hipStream_t ls = (n_low && !top) ? d->side : s;
-    if (top && n_low && !joined && (rc = finish_blocks()) != 0) return rc;
+    hipStream_t ls = (low && !top) ? low : s;
+    if (top && low && !joined && (rc = finish_blocks()) != 0) return rc;
     const int sp = T.begin(SP_DWT, ls);
     if (d->region) {                                        // region synthesis (the Part-1 wavelets only: plan_restrict_region)
       const ojphgpu_dwt_region* regs = (const ojphgpu_dwt_region*)(b.img_first >= 0 ? d->img_regs.p : d->dwt_regs.p) + (b.img_first >= 0 ? b.img_first : (int)b.first);
@@ -1669,7 +1719,7 @@ static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, u
     if (rc) return rc;
     T.end(sp, ls);
   }
-  if (n_low && !joined && (rc = finish_blocks()) != 0) return rc;
+  if (low && !joined && (rc = finish_blocks()) != 0) return rc;
   if (d->need_convert) {
     const int sp = T.begin(SP_CONVERT, s);
     rc = ojphgpu_convert_inverse_ex(s, &P.p, (const ojphgpu_convert_desc*)d->conv_descs.p, d->conv_tiles * d->nframes,
@@ -1683,17 +1733,16 @@ static int decoder_synthesis(ojphgpu_decoder* d, void* d_image, int container, u
 // The block decoder of a run takes the one launch for step 1 and step 2 (chains first, step-2 workers behind them slice by
 // slice, kernels_ht_dec.hip) when every block is at most 64 samples wide, of one wavelet and without refinement passes -- and
 // where it pays: blocks of 64 rows, few enough for resident workers (ht_decode_fused_pays).  Otherwise: the separate launches.
-static bool decoder_fuses(const ojphgpu_decoder* d)
+bool decoder_fuses(const ojphgpu_decoder* d)
 {
   return d->fstate.p && !d->force_separate && !d->fused_off && !d->any_refine && (d->kinds & (3 | 32)) == 1 && ((d->kinds & 12) == 4 || (d->kinds & 12) == 8) &&
          d->nblocks > 0 && ojphgpu::ht_decode_fused_pays(d->nblocks, d->max_block_h, d->cus);
 }
 
-// ... and its launches on the main stream: the one launch over all blocks, or prep + step 1 of all blocks and step 2 of the
+// ... and its launches on stream s (the caller's; a released run: the object's own): the one launch over all blocks, or prep + step 1 of all blocks and step 2 of the
 // first `count` descriptors (the rest is the caller's: decode_samples beside the lower synthesis levels)
-static int decoder_block_launches(ojphgpu_decoder* d, bool fused, uint32_t count)
+static int decoder_block_launches(ojphgpu_decoder* d, bool fused, uint32_t count, hipStream_t s)
 {
-  hipStream_t s = d->stream;
   Spans& T = d->timer;
   if (fused) {
     const ojphgpu_cb_desc* cbd = (const ojphgpu_cb_desc*)(d->o_cb_descs ? d->o_cb_descs : d->cb_descs.p);
@@ -1720,8 +1769,53 @@ static int decoder_run_blocks(ojphgpu_decoder* d)
   d->timer.start(d->stream);
   const bool fused = decoder_fuses(d);
   d->last_fused = fused; d->last_image = nullptr; d->last_container = 0;
-  const int rc = decoder_block_launches(d, fused, d->nblocks);
+  const int rc = decoder_block_launches(d, fused, d->nblocks, d->stream);
   if (rc) return rc;
+  d->ran = true;
+  return OJPHGPU_OK;
+}
+
+// A released run (ojphgpu_objects.h; decoder_releases() has admitted it): the one block launch -- under
+// OJPHGPU_DEC_AHEAD_LEVELS=1 synthesis levels L..2 too -- on the object's own stream, behind the object's last upload and
+// the last reader of the arena it writes and NOT behind the caller's stream; the caller's stream waits for it (ev_done)
+// and runs the synthesis; only the top level and the conversion write the image.  T.start / T.finish stay on the caller's stream.
+namespace {
+// From the first launch on the own stream on, EVERY way out of the run records ev_done behind what has been queued there -- a
+// run that fails half way has launches there too, and whoever settles must wait for them, not for an older record.
+struct ReleasedDecode {
+  ojphgpu_decoder* d; bool armed = false;
+  void done() { if (armed) (void)hipEventRecord(d->ev_done, d->side); armed = false; }
+  ~ReleasedDecode() { done(); }
+};
+}  // namespace
+static int decoder_run_released(ojphgpu_decoder* d, void* d_image, int container)
+{
+  hipStream_t s = d->stream, own = d->side;
+  Spans& T = d->timer;
+  if (d->two_arenas) { std::swap(d->arena, d->arena2); std::swap(d->ev_read, d->ev_read2); }   // (from here on `arena` is this run's)
+  if (d->last_joined) {                                     // quads / fstate / data were last used on the caller's stream
+    HIPCHK(hipStreamWaitEvent(own, d->two_arenas ? d->ev_read2 : d->ev_read, 0));
+    d->last_joined = false;
+  }
+  HIPCHK(hipStreamWaitEvent(own, d->ev_read, 0));           // the last synthesis that read this arena (never recorded: no wait)
+  T.start(s);
+  d->last_fused = true; d->last_image = d_image; d->last_container = container;
+  ReleasedDecode branch{ d, true };
+  d->pending = true;                                        // (from here: also a run that fails below)
+  int rc = decoder_block_launches(d, true, d->nblocks, own);
+  if (rc) return rc;
+  bool joined = false;
+  auto join = [&]() -> int {                                // the caller's stream gets behind the own stream's part of the run
+    joined = true;
+    branch.done();
+    HIPCHK(hipStreamWaitEvent(s, d->ev_done, 0));
+    return OJPHGPU_OK;
+  };
+  if (!d->ahead_levels && (rc = join()) != 0) return rc;
+  rc = decoder_synthesis(d, d_image, container, d->ahead_levels ? own : nullptr, joined, join);
+  (void)hipEventRecord(d->ev_read, s);                      // behind the last launch of this run that reads the arena
+  if (rc) return rc;
+  T.finish(s);
   d->ran = true;
   return OJPHGPU_OK;
 }
@@ -1754,14 +1848,21 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
       return OJPHGPU_E_UNCOLLECTED;
     }
   }
-  T.start(s);
   // One launch for step 1 and step 2 (chains first, step-2 workers behind them slice by slice, kernels_ht_dec.hip) when
   // every block is at most 64 samples wide, of one wavelet and without refinement passes -- and where it pays: blocks
   // of 64 rows, few enough for resident workers (ht_decode_fused_pays); the synthesis levels follow on the same stream.  Otherwise: the separate launches, with the lower synthesis levels beside step 2 of the top resolution.
   const bool fused = decoder_fuses(d);
+  if (decoder_releases(d)) return decoder_run_released(d, d_image, container);
+  int rc = decoder_settle(d);                               // a joined run behind released ones: the last run's arena, behind all of them
+  if (rc) return rc;
+  struct JoinedRun {                                        // every way out: the own stream's next job can be put behind this run
+    ojphgpu_decoder* d;
+    ~JoinedRun() { if (d->can_release) { (void)hipEventRecord(d->ev_read, d->stream); d->last_joined = true; } }
+  } joined_run{ d };
+  T.start(s);
   d->last_fused = fused; d->last_image = d_image; d->last_container = container;
   const uint32_t n_low = fused ? 0u : d->n_low;
-  int rc = decoder_block_launches(d, fused, n_low ? n_low : d->nblocks);
+  rc = decoder_block_launches(d, fused, n_low ? n_low : d->nblocks, s);
   if (rc) return rc;
   if (n_low) {                                              // fork: the lower synthesis levels on the side stream
     HIPCHK(hipEventRecord(d->ev_fork, s));
@@ -1776,7 +1877,7 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
     HIPCHK(hipStreamWaitEvent(s, d->ev_join, 0));           // join before the top synthesis level
     return OJPHGPU_OK;
   };
-  if ((rc = decoder_synthesis(d, d_image, container, n_low, joined, finish_blocks)) != 0) return rc;
+  if ((rc = decoder_synthesis(d, d_image, container, n_low ? d->side : nullptr, joined, finish_blocks)) != 0) return rc;
   T.finish(s);
   d->ran = true;
   return OJPHGPU_OK;
@@ -1785,7 +1886,7 @@ int ojphgpu_decoder_run_container(ojphgpu_decoder* d, void* d_image, int contain
 static int decoder_synthesis_only(ojphgpu_decoder* d, void* d_image, int container)
 {
   bool joined = true;
-  return decoder_synthesis(d, d_image, container, 0, joined, [] { return OJPHGPU_OK; });
+  return decoder_synthesis(d, d_image, container, nullptr, joined, [] { return OJPHGPU_OK; });
 }
 
 // A decoder object that only synthesises: the level batches, the conversion and an arena (zeroed, as a decoder's is) of a
@@ -1826,6 +1927,8 @@ static int decoder_create_synthesis(const ojphgpu_plan* plan, int device, void* 
 extern "C" int ojphgpu_decoder_set_timing(ojphgpu_decoder* d, int per_launch)
 {
   if (!d) return OJPHGPU_E_INVALID;
+  const int rc = decoder_settle(d);                         // (the next run may be of the other schedule)
+  if (rc) return rc;
   d->timer.detail = per_launch != 0;
   return OJPHGPU_OK;
 }
@@ -1851,7 +1954,9 @@ int ojphgpu_decoder_collect(ojphgpu_decoder* d, ojphgpu_status_fetch fetch, void
   d->uncollected = false;
   const uint8_t* st = nullptr;
   for (int pass = 0; pass < 2; ++pass) {
-    int rc = fetch(user, &st);
+    int rc = decoder_settle(d);                             // a released run: the fetch reads its status on the caller's stream
+    if (rc) return rc;
+    rc = fetch(user, &st);
     if (rc) return rc;
     // a fused launch whose workers gave up waiting for their chains (the chip was held up for seconds by other work): its
     // blocks have no verdict yet -- the frame is decoded again through the separate launches, into the same image
@@ -1900,7 +2005,10 @@ extern "C" int ojphgpu_decoder_failed_blocks(ojphgpu_decoder* d, uint32_t* count
 extern "C" int ojphgpu_decoder_giveup_epoch(ojphgpu_decoder* d, uint32_t* last_giveup, uint32_t* current)
 {
   if (!d || !last_giveup || !current) return OJPHGPU_E_INVALID;
+  const int rc = decoder_settle(d);
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(d->stream));
+  if (d->can_release) HIPCHK(hipStreamSynchronize(d->side));   // (a released run that failed half way; an upload)
   *last_giveup = d->h_retry ? *(volatile uint32_t*)d->h_retry : 0u;
   *current = d->fused_epoch;
   return OJPHGPU_OK;
@@ -1912,6 +2020,13 @@ extern "C" int ojphgpu_decoder_region_info(ojphgpu_decoder* d, uint64_t out[4])
   uint64_t bytes = d->f_len.empty() ? 0 : d->f_len[0];
   if (!d->f_pads.empty()) for (const PadCopy& c : d->f_pads[0]) bytes += c.got;
   out[0] = d->block_ids.size(); out[1] = d->P->blocks.size(); out[2] = bytes; out[3] = d->tiles_touched;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_decoder_pending(const ojphgpu_decoder* d, int* pending)
+{
+  if (!d || !pending) return OJPHGPU_E_INVALID;
+  *pending = d->pending ? 1 : 0;
   return OJPHGPU_OK;
 }
 
@@ -1954,6 +2069,7 @@ static int decode_host(ojphgpu_decoder* d, const uint8_t* h_codestream, size_t l
 extern "C" int ojphgpu_decoder_timing(ojphgpu_decoder* d, float out[4])
 {
   if (!d || !out || !d->ran) return OJPHGPU_E_INVALID;
+  if (decoder_settle(d)) return OJPHGPU_E_HIP;
   float a = 0, b = 0, c = 0, r = 0;
   if (d->timer.read(SP_PREP, &a) || d->timer.read(SP_STEP1, &b) || d->timer.read(SP_STEP2, &c) || d->timer.read(SP_REFINE, &r) ||
       d->timer.read(SP_DWT, &out[1]) || d->timer.read(SP_CONVERT, &out[2]) || d->timer.read(-1, &out[3])) return OJPHGPU_E_HIP;
@@ -1964,6 +2080,7 @@ extern "C" int ojphgpu_decoder_timing(ojphgpu_decoder* d, float out[4])
 extern "C" int ojphgpu_decoder_ht_timing(ojphgpu_decoder* d, float out[3])
 {
   if (!d || !out || !d->ran) return OJPHGPU_E_INVALID;
+  if (decoder_settle(d)) return OJPHGPU_E_HIP;
   if (d->timer.read(SP_PREP, &out[0]) || d->timer.read(SP_STEP1, &out[1]) || d->timer.read(SP_STEP2, &out[2])) return OJPHGPU_E_HIP;
   return OJPHGPU_OK;
 }
@@ -1971,6 +2088,7 @@ extern "C" int ojphgpu_decoder_ht_timing(ojphgpu_decoder* d, float out[3])
 extern "C" int ojphgpu_decoder_level_timing(ojphgpu_decoder* d, float* out, uint32_t cap, uint32_t* n)
 {
   if (!d || !out || !n || !d->ran) return OJPHGPU_E_INVALID;
+  if (decoder_settle(d)) return OJPHGPU_E_HIP;
   int k = d->timer.read_each(SP_DWT, out, cap);
   if (k < 0) return OJPHGPU_E_HIP;
   *n = (uint32_t)k;

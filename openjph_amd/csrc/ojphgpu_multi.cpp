@@ -29,6 +29,9 @@
 
 #include "ojph_plan.h"
 
+// (ojphgpu_codec.cpp: a decoder whose runs never release -- every worker's run is collected on the spot)
+int ojphgpu_decoder_create_joined(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count, ojphgpu_decoder** out);
+
 using namespace ojphgpu;
 
 namespace {
@@ -300,7 +303,7 @@ extern "C" int ojphgpu_multi_decoder_create(const uint8_t* h_codestream, size_t 
       W.device = devices[k]; W.tiles = run_of(nt, k, n);
       HIPCHK(hipSetDevice(W.device));
       HIPCHK(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
-      rc = ojphgpu_decoder_create_tiles(m->plan, W.device, W.stream, W.tiles.first, W.tiles.count, &W.dec);
+      rc = ojphgpu_decoder_create_joined(m->plan, W.device, W.stream, W.tiles.first, W.tiles.count, &W.dec);
       if (rc) return rc;
       HIPCHK(hipMalloc(&W.d_image, (size_t)P.frame_elems * 4 + 64));
     }

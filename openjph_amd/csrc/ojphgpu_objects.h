@@ -737,7 +737,53 @@ struct ojphgpu_decoder {
   // the decoder half of a transcoder (section 5d): the block decoder alone -- no level batches, no conversion, no frame; a
   // run ends with the sub-band planes in the arena
   bool blocks_only = false;
+  // A released run (include/ojphgpu.h, ojphgpu_decoder_run_device): nothing in the block decoder and in synthesis levels
+  // L..2 touches the caller's memory -- they read the object's codestream bytes and descriptors and read and write its
+  // arena, records and status -- so a run that decoder_releases() admits issues the block launch (with ahead_levels:
+  // levels L..2 as well) on `side`, the object's own stream, and the caller's stream waits for ev_done, recorded behind
+  // them, in front of the first level it runs itself.  The uploads of
+  // such an object go on `side` too (ev_up lets the caller's stream follow), in order with the block launches that read
+  // `data`.  pending: ev_done has been recorded and nothing but the run itself has waited for it; whatever reads the status
+  // or the arena on the caller's stream, or frees anything, calls decoder_settle() first.
+  // Two arenas (two_arenas; OJPHGPU_DEC_SETS=1 at creation: one): released runs alternate, `arena` is ALWAYS the last
+  // run's, `arena2` the one before it.  ev_read / ev_read2: recorded on the caller's stream behind the last synthesis
+  // that read arena / arena2; `side` waits for the event of the arena it is about to write -- the run two back -- and,
+  // behind a joined run (last_joined: its block launches used quads / fstate / data on the caller's stream), for that run's
+  // as well.  quads, fstate, status and aux stay single: the block launches of released runs sit on one in-order stream.
+  bool can_release = false, pending = false, two_arenas = false, last_joined = false;
+  bool ahead_levels = false;                       // OJPHGPU_DEC_AHEAD_LEVELS=1: levels L..2 of a released run go with the block launch (default: they stay on the caller's stream)
+  DeviceBuf arena2;
+  hipEvent_t ev_done = nullptr, ev_up = nullptr, ev_read = nullptr, ev_read2 = nullptr;
 };
+// May the next run of d be released?  A single-frame decoder with a side stream whose block decoder is the one launch,
+// into its own buffers (not a pipe's slot), whole frames (no region, not a transcoder's half), with per-launch timing off
+// (the spans of a run are read as parts of one total).  can_release: what was settled at creation -- made through the
+// public single-frame create, fusing then, not under OJPHGPU_NO_OVERLAP=1 / OJPHGPU_DEC_RELEASE=0.
+bool decoder_fuses(const ojphgpu_decoder* d);
+inline bool decoder_releases(const ojphgpu_decoder* d)
+{
+  return d->can_release && d->nframes == 1 && d->n_low != 0 && d->side && decoder_fuses(d) && !d->o_cb_descs && !d->o_data && !d->o_status &&
+         !d->blocks_only && !d->region && !d->force_separate && !d->timer.detail;
+}
+// The stream-level join of a released run: d->stream waits for what the own stream holds (no host synchronisation).
+inline int decoder_settle(ojphgpu_decoder* d)
+{
+  if (!d->pending) return OJPHGPU_OK;
+  HIPCHK(hipStreamWaitEvent(d->stream, d->ev_done, 0));
+  d->pending = false;
+  return OJPHGPU_OK;
+}
+// the own stream gets behind a joined run of the object (its block launches and synthesis on the caller's stream)
+inline int decoder_own_follows_joined(ojphgpu_decoder* d)
+{
+  if (!d->last_joined) return OJPHGPU_OK;
+  HIPCHK(hipStreamWaitEvent(d->side, d->ev_read, 0));
+  d->last_joined = false;
+  return OJPHGPU_OK;
+}
+// ojphgpu_decoder_create for an owner whose runs never release (a frame pipe, a multi-device decoder): one arena, the
+// uploads on the caller's stream
+int ojphgpu_decoder_create_joined(const ojphgpu_plan* plan, int device, void* stream, uint32_t tile_first, uint32_t tile_count, ojphgpu_decoder** out);
 // A transcoder: the block decoder of the source plan and the block coder of the output plan on the decoder's arena (the
 // encoder is created without one and borrows it: enc->arena.p is not the encoder's to free)
 struct ojphgpu_transcoder {

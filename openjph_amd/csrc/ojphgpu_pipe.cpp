@@ -1183,7 +1183,7 @@ extern "C" int ojphgpu_dec_pipe_create_view(const uint8_t* h_codestream, size_t 
     }
     for (uint32_t k = 0; k < p->nobj; ++k) {
       HIPCHK(hipStreamCreateWithFlags(&p->s_comps[k], hipStreamNonBlocking));
-      rc = ojphgpu_decoder_create(p->first, device, p->s_comps[k], &p->decs[k]);
+      rc = ojphgpu_decoder_create_joined(p->first, device, p->s_comps[k], 0, (uint32_t)p->first->plan.tiles.size(), &p->decs[k]);
       if (rc) return rc;
       ojphgpu_decoder* dk = p->decs[k];
       (void)ojphgpu_decoder_set_timing(dk, 0);

@@ -20,7 +20,7 @@ sel = codec[mid:mid + n]
 t0 = sel[0][0]
 busy_until = sel[0][0]
 for s, e, k, q in sel:
-    name = k.split("(")[0].replace("(anonymous namespace)::", "").replace("void ", "")[:58]
+    name = k.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].split("<")[0][:58]
     gap = (s - busy_until) / 1e3
     print("%9.1f .. %9.1f  %7.1f us  q%-3s idle-before %6.1f  %s" % ((s - t0) / 1e3, (e - t0) / 1e3, (e - s) / 1e3, q, gap if gap > 0 else 0.0, name))
     busy_until = max(busy_until, e)
