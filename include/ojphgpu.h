@@ -681,7 +681,7 @@ int  ojphgpu_encoder_finish_frame(ojphgpu_encoder* enc, uint32_t frame, uint8_t*
  * running, and on the caller's stream it waits only for the run two back.  The object's other calls (_coded_bytes,
  * _finish*, the timing getters, the setters of section 5b / 5c, a run that ends joined) wait for every run in flight and
  * then read the products of the LAST run.  A released run cuts the top resolution's blocks between its two streams at
- * OJPHGPU_ENC_TOP_SHARE_RELEASED percent (default 50), a joined one where OJPHGPU_ENC_TOP_SHARE or the model says;
+ * OJPHGPU_ENC_TOP_SHARE_RELEASED percent (default 10 where the top resolution has more than 8192 blocks, else 50), a joined one where OJPHGPU_ENC_TOP_SHARE or the model says;
  * ojphgpu_encoder_ht_timing reports the cut of the last run.  Memory: the second set is one more arena, output buffer and
  * results table per such encoder -- about 0.7 GB for an 8K 4:4:4 frame; OJPHGPU_ENC_SETS=1 in the environment at
  * creation keeps one set (every run then waits for the one before it, as it did), and an encoder that can never release

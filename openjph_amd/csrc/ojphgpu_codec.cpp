@@ -116,7 +116,13 @@ extern "C" int ojphgpu_encoder_create_batch(const ojphgpu_plan* plan, int device
 // percent of the top resolution's blocks on the side stream in a released run where OJPHGPU_ENC_TOP_SHARE_RELEASED is unset;
 // 0 = the joined cut
 #ifndef OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT
-#define OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT 50
+#define OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT 10
+#endif
+#ifndef OJPHGPU_ENC_TOP_SHARE_RELEASED_LARGE
+#define OJPHGPU_ENC_TOP_SHARE_RELEASED_LARGE 8192    // blocks in the top resolution above which the default above holds (two rounds of
+#endif                                               // the 4 096 wavefront slots the narrow block encoder has on 256 CUs); up to it:
+#ifndef OJPHGPU_ENC_TOP_SHARE_RELEASED_SMALL
+#define OJPHGPU_ENC_TOP_SHARE_RELEASED_SMALL 50
 #endif
 static ojphgpu_encoder::EncoderCut encoder_cut(const ojphgpu_encoder* e, uint32_t n_top)
 {
@@ -251,11 +257,13 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       // analysis level its bytes at 3 TB/s or a 12 us launch floor.  8K 4:4:4: 90 % (step 0.957 -> 0.938 ms); a 4K frame's
       // main branch is the longer one already: 100 %.  OJPHGPU_ENC_TOP_SHARE=<percent> overrides the model.
       // That is the joined schedule's cut.  A released run (ojphgpu_objects.h), whose branches nobody waits for, has a cut
-      // of its own: OJPHGPU_ENC_TOP_SHARE_RELEASED=<percent>, read at every creation; unset: 50 % -- blocks moved to the
+      // of its own: OJPHGPU_ENC_TOP_SHARE_RELEASED=<percent>, read at every creation; unset: 10 % -- blocks moved to the
       // second stream's launch are coded beside the synthesis levels (HBM-bound) instead of beside the fused block decoder
-      // (issue-bound like the coder); 8K step 0.843 ms at 50 against 0.854 / 0.849 at 40 / 60 and 0.869 at 90
-      // (profiles/enc_sets_ab.txt has the sweep).  The run picks the pair (run_container); the blocks' output regions do
-      // not depend on it (encoder_block_layout).
+      // (issue-bound like the coder).  With the decoder's fused launch on the caller's stream the 8K step was 0.843 ms at 50
+      // against 0.854 / 0.849 at 40 / 60 and 0.869 at 90 (profiles/enc_sets_ab.txt); since that launch runs on a stream of
+      // its own the optimum is at the other end: 0.7952 at 10, 0.7994 at 20, 0.8051 at 30, 0.8159 at 50, five alternating
+      // rounds, every round in this order (profiles/enc_block_runs_ab.txt).  The run picks the pair (run_container); the
+      // blocks' output regions do not depend on it (encoder_block_layout).
       static const int share_env = [] { const char* v = getenv("OJPHGPU_ENC_TOP_SHARE"); const int x = v ? atoi(v) : 0; return x < 10 ? 0 : x > 100 ? 100 : x; }();
       double s_top = 0, s_low = 0;                         // millions of samples
       for (size_t i = 0; i < e->block_ids.size(); ++i) {
@@ -271,7 +279,11 @@ static int encoder_create(const ojphgpu_plan* plan, int device, void* stream, ui
       const uint32_t n_res_top = e->n_top;
       e->n_top = (uint32_t)((uint64_t)n_res_top * (uint32_t)share / 100u);
       const char* rv = getenv("OJPHGPU_ENC_TOP_SHARE_RELEASED");
-      const int rshare = rv ? std::min(100, std::max(10, atoi(rv))) : OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT;
+      // (unset: 10 where the top resolution has more blocks than OJPHGPU_ENC_TOP_SHARE_RELEASED_LARGE -- the 8K frame's
+      // 18 360; 50, as before, below that: a 4K frame's 4 590 blocks are one round of the chip's coder slots, and its step
+      // is 1.6 % LONGER at 10, 0.3026 against 0.2977 ms in five alternating pairs.  Not swept between the two sizes.)
+      const int rshare = rv ? std::min(100, std::max(10, atoi(rv)))
+                            : n_res_top > (uint32_t)OJPHGPU_ENC_TOP_SHARE_RELEASED_LARGE ? OJPHGPU_ENC_TOP_SHARE_RELEASED_DEFAULT : OJPHGPU_ENC_TOP_SHARE_RELEASED_SMALL;
       n_top_released = rshare ? (uint32_t)((uint64_t)n_res_top * (uint32_t)rshare / 100u) : e->n_top;
       if (n_top_released == 0 || n_top_released == e->block_ids.size()) n_top_released = e->n_top;
     }
