@@ -423,6 +423,44 @@ typedef struct ojphgpu_cb_result {   /* encode result per block */
 int ojphgpu_ht_encode(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
                       const void* d_coef, uint8_t* d_scratch, uint8_t* d_out, uint32_t out_cap,
                       ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status);
+/* The block encoder as a stage with what the encoder objects know and use: the kinds of the blocks, and output regions.
+ * ojphgpu_ht_encode_ex: ojphgpu_ht_encode (== widths 3 | 32, nreg 0, first 0) with that knowledge.  d_blocks and d_results
+ *   point at the FIRST block of the range that is coded; `first` is that block's index among all blocks of the caller (a
+ *   caller that codes one array in several launches passes the same regions, cursor and output to each) and only chooses
+ *   regions.  Regions: nreg = 0, the single cursor d_cursor[0] over d_out[0 .. out_cap); else nreg (a power of two) regions,
+ *   d_regions[2 r] = first byte of region r in d_out, d_regions[2 r + 1] = its bytes, its cursor (zeroed by the caller) at
+ *   d_cursor[32 r]; block i of the launch takes a 4-byte aligned slot in region (first + i) & (nreg - 1).  A block whose
+ *   slot does not fit what is left of its region, or whose scratch slot is too small, reports offset 0, length 0, writes
+ *   nothing to d_out and sets *d_status (d_cursor + 1 in the objects); a cursor counts every request, also a refused one.
+ * `widths` says what the blocks of the range are; every launched kernel skips the blocks that are not its own:
+ *   bit 0 (1)    blocks of at most 64 columns occur           bit 1 (2)    blocks of more than 64 columns occur
+ *   bit 2 (4)    reversible blocks occur                      bit 3 (8)    irreversible blocks occur  (neither: both)
+ *   bit 4 (16)   NO block of 33..64 columns occurs: the blocks of bit 0 take the layout of 8 quad pairs by 8 quad rows
+ *   bit 5 (32)   blocks on the 64-bit sample path occur (cb_desc.reversible bit 2; bits 0..4 and 6 say nothing of them)
+ *   bit 6 (64)   NO block of more than 128 columns occurs: the blocks of bit 1 take the narrow kernel, 32 pairs by 2 rows
+ * ojphgpu_ht_encode_kinds: host only -- the truthful widths of h_blocks[0 .. n), the statement the encoder objects use too
+ *   (a descriptor without samples, w or h 0, counts with its w and reversible like any other: a kernel must report it).
+ * A caller may know LESS than ojphgpu_ht_encode_kinds says, never more.  The valid coarsenings of a truthful value, in any
+ * combination:
+ *   - clear bit 4: the blocks of at most 32 columns take the 16-pairs-by-4-rows layout of the 64-column blocks;
+ *   - clear bit 6: the blocks of 65..128 columns take the raster-order wide kernel;
+ *   - set both or neither of bits 2 and 3: both wavelets' instantiations run;
+ *   - set bits 0, 1 or 5 that the truth lacks: a kernel is launched that finds no block of its own.
+ * Everything else is invalid: clearing bit 0, 1 or 5 that the truth sets, stating one wavelet where the other occurs, or
+ * setting bit 4 or 6 that the truth lacks.  Then no launched instantiation owns some block (e.g. bit 4 set with a 40-column
+ * block present: the 8-by-8 layout takes blocks of at most 32 columns only) and that block's result is NEVER WRITTEN -- no
+ * error is reported, d_results keeps what the caller left there.
+ * ojphgpu_ht_encode_launches: host only, no HIP call -- what ojphgpu_ht_encode_ex launches for n blocks under `widths`, in
+ *   issue order; it takes its launches from the same table.  *count launches (at most 5), five values each in `out`:
+ *   [0] 0 = ht_encode_kernel<REV, LOGP>, 1 = ht_encode_wide_kernel<S64>; [1] REV, or S64; [2] LOGP (3: 8 pairs by 8 quad
+ *   rows, 4: 16 by 4, 5: 32 by 2; 0 for the wide kernel); [3] workgroups; [4] blocks (wavefronts) per workgroup.  `cap` =
+ *   the launches `out` has room for; E_INVALID (with *count set) where cap < *count. */
+int ojphgpu_ht_encode_ex(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
+                         const void* d_coef, uint8_t* d_scratch, uint8_t* d_out, uint32_t out_cap,
+                         ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status,
+                         int widths, const uint32_t* d_regions, uint32_t nreg, uint32_t first);
+int ojphgpu_ht_encode_kinds(const ojphgpu_cb_desc* h_blocks, uint32_t n, int* widths);
+int ojphgpu_ht_encode_launches(uint32_t n, int widths, uint32_t* out, uint32_t cap, uint32_t* count);
 
 /* K9 + K7: HT decoder (ojph_block_decoder32.cpp:742-1613) with the dequantise transfer
  * (ojph_codestream_gen.cpp:124-168) fused.  Three launches: prep (one wavefront per block:

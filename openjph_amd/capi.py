@@ -304,6 +304,11 @@ SIGNATURES = {
                                             C.c_uint32, C.c_void_p, C.c_void_p]),
     "ojphgpu_ht_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ojphgpu_ht_encode_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "ojphgpu_ht_encode_kinds": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    "ojphgpu_ht_encode_launches": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
     "ojphgpu_ht_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "ojphgpu_ht_decode_aux_words": (C.c_uint32, [C.c_uint32]),

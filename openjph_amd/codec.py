@@ -1104,8 +1104,94 @@ def dwt_general(direction, steps, elem, descs: np.ndarray, arena, max_w, max_h, 
     torch.cuda.synchronize(dev)
 
 
-def ht_encode(descs: np.ndarray, coef, scratch_bytes, out_cap):
-    """Returns (results array, out bytes tensor (host numpy), status)."""
+def ht_encode_kinds(descs: np.ndarray):
+    """what the blocks of `descs` are, as the truthful `widths` of ojphgpu_ht_encode_ex (host only; include/ojphgpu.h)"""
+    descs = np.ascontiguousarray(descs)
+    k = C.c_int()
+    check(capi.lib().ojphgpu_ht_encode_kinds(descs.ctypes.data if len(descs) else None, len(descs), C.byref(k)), "ht_encode_kinds")
+    return int(k.value)
+
+
+def ht_encode_launches(n, widths):
+    """the launches of ojphgpu_ht_encode_ex over n blocks under `widths`, in issue order (host only, no HIP call): a list of
+    dicts of wide (1: ht_encode_wide_kernel<S64 = flag>, 0: ht_encode_kernel<REV = flag, logp>), flag, logp, wgs, per_wg"""
+    L = capi.lib()
+    cnt = C.c_uint32()
+    L.ojphgpu_ht_encode_launches(int(n), int(widths), None, 0, C.byref(cnt))
+    out = (C.c_uint32 * (5 * max(cnt.value, 1)))()
+    check(L.ojphgpu_ht_encode_launches(int(n), int(widths), out, cnt.value, C.byref(cnt)), "ht_encode_launches")
+    return [dict(zip(("wide", "flag", "logp", "wgs", "per_wg"), (int(v) for v in out[5 * i:5 * i + 5]))) for i in range(cnt.value)]
+
+
+class EncodeStage:
+    """ojphgpu_ht_encode_ex as the encoder objects use it: one descriptor array, one scratch, one compacted output with
+    `regions` ((nreg, 2) uint32 rows of first byte, bytes; None = the single cursor over out_cap) and the cursor words, all
+    made once; launch() codes a range of the descriptors into them.  Out and scratch start filled with SENTINEL, results
+    with 0xFFFFFFFF words (a block no launched kernel owns keeps them).  scratch_caps_as_given=False: the slots (data_off,
+    scratch_cap) are laid out here, roomy enough for any content, instead of taken from `descs`."""
+    SENTINEL = 0xA5
+
+    def __init__(self, descs: np.ndarray, coef, scratch_bytes, out_cap, regions=None, scratch_caps_as_given=True):
+        torch = _torch()
+        self.torch, self.dev, self.coef = torch, coef.device.index, coef
+        descs = np.ascontiguousarray(descs.copy())
+        if not scratch_caps_as_given:
+            from .csrc_consts import block_scratch_bytes
+            off = 0
+            for d in descs:
+                d["data_off"], d["scratch_cap"] = off, block_scratch_bytes(int(d["w"]), int(d["h"]), 30)
+                off += int(d["scratch_cap"])
+            scratch_bytes = off
+        self.descs, self.n, self.out_cap = descs, len(descs), int(out_cap)
+        self.d = to_device(descs, self.dev) if len(descs) else torch.zeros(64, dtype=torch.uint8, device=coef.device)
+        self.scratch = torch.full((max(int(scratch_bytes), 16),), self.SENTINEL, dtype=torch.uint8, device=coef.device)
+        self.out = torch.full((max(int(out_cap), 16),), self.SENTINEL, dtype=torch.uint8, device=coef.device)
+        self.results = torch.full((len(descs) * 2 + 2,), -1, dtype=torch.int32, device=coef.device)
+        reg = np.zeros((0, 2), np.uint32) if regions is None else np.ascontiguousarray(np.asarray(regions, np.uint32).reshape(-1, 2))
+        self.nreg = len(reg)
+        self.regions = to_device(reg, self.dev) if self.nreg else None
+        self.counters = torch.zeros(32 * max(self.nreg, 1) + 32, dtype=torch.int32, device=coef.device)
+
+    def launch(self, lo=0, n=None, widths=None, first=None):
+        """codes descriptors [lo, lo + n) under `widths` (None: what ht_encode_kinds says of that range); `first` (None: lo) is
+        the index of descriptor lo among all blocks and only chooses regions"""
+        n = self.n - lo if n is None else int(n)
+        if lo < 0 or n < 0 or lo + n > self.n:
+            raise ValueError("the range is not inside the descriptor array")
+        if widths is None:
+            widths = ht_encode_kinds(self.descs[lo:lo + n])
+        ptr = lambda t, o=0: C.c_void_p(t.data_ptr() + o)
+        with self.torch.cuda.device(self.dev):
+            check(capi.lib().ojphgpu_ht_encode_ex(_stream_ptr(self.torch, self.dev), ptr(self.d, lo * self.descs.dtype.itemsize), n,
+                                                  ptr(self.coef), ptr(self.scratch), ptr(self.out), self.out_cap, ptr(self.results, 8 * lo),
+                                                  ptr(self.counters), ptr(self.counters, 4), int(widths),
+                                                  ptr(self.regions) if self.nreg else None, self.nreg, int(lo if first is None else first)),
+                  "ht_encode_ex")
+
+    def read(self):
+        """(results (n, 2) uint32, the whole out buffer, status, the whole scratch buffer, cursor word per region (one for none))"""
+        self.torch.cuda.synchronize(self.dev)
+        res = self.results.cpu().numpy()[:self.n * 2].view(np.uint32).reshape(-1, 2).copy()
+        cnt = self.counters.cpu().numpy().view(np.uint32)
+        return res, self.out.cpu().numpy()[:self.out_cap].copy(), int(cnt[1]), self.scratch.cpu().numpy().copy(), cnt[0:32 * max(self.nreg, 1):32].copy()
+
+
+_ENC_KW = dict(widths=None, regions=None, first=0, scratch_caps_as_given=True)
+
+
+def ht_encode(descs: np.ndarray, coef, scratch_bytes, out_cap, **kw):
+    """Returns (results array, out bytes tensor (host numpy), status).
+
+    With any of the keyword arguments widths=None, regions=None, first=0, scratch_caps_as_given=True: one launch of
+    ojphgpu_ht_encode_ex through an EncodeStage (which see), returning its read(): (results, the whole out buffer, status,
+    the whole scratch buffer, the regions' cursor words), untouched bytes of out and scratch holding EncodeStage.SENTINEL."""
+    if kw:
+        if set(kw) - set(_ENC_KW):
+            raise TypeError("ht_encode: unknown keyword argument(s) %s" % sorted(set(kw) - set(_ENC_KW)))
+        a = dict(_ENC_KW, **kw)
+        st = EncodeStage(descs, coef, scratch_bytes, out_cap, a["regions"], a["scratch_caps_as_given"])
+        st.launch(0, len(descs), a["widths"], a["first"])
+        return st.read()
     torch = _torch()
     dev = coef.device.index
     d = to_device(descs, dev)

@@ -37,6 +37,16 @@ namespace ojphgpu {
 int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const void* d_coef, uint8_t* d_scratch,
                      uint8_t* d_out, uint32_t out_cap, ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status,
                      int widths, const uint32_t* d_regions, uint32_t nreg, uint32_t first);   // regions: see claim_output (kernels_ht_enc.hip)
+// What ONE block states about the range it is in, from its descriptor's w and reversible: bits 0..3 and 5 as in `widths`
+// (include/ojphgpu.h, ojphgpu_ht_encode_ex); 256 = a block of 33..64 columns, 512 = one of more than 128 -- the two facts whose
+// ABSENCE from a range is `widths` bit 4 / bit 6.  A range's `widths` = ht_encode_range_widths(its blocks' values OR-ed).  The
+// one statement of the bits: the encoder objects (encoder_cut) and ojphgpu_ht_encode_kinds both come here.
+inline int ht_encode_block_widths(uint32_t w, uint32_t reversible)
+{
+  if (reversible & 4u) return 32;                         // on the 64-bit sample path, whatever its width
+  return (w > 64u ? 2 : 1) | ((reversible & 1u) ? 4 : 8) | ((w > 32u && w <= 64u) ? 256 : 0) | (w > 128u ? 512 : 0);
+}
+inline int ht_encode_range_widths(int ored) { return (ored & 47) | ((ored & 256) ? 0 : 16) | ((ored & 512) ? 0 : 64); }
 // ojphgpu_ht_decode_step2 with the caller's knowledge of the blocks of the range (kernels_ht_dec.hip)
 // step 1 + step 2 in one launch (kernels_ht_dec.hip, ht_dec_fused_kernel): chains first, step-2 workers behind them
 bool dec_fuses();

@@ -1543,6 +1543,32 @@ namespace ojphgpu {
 // (cb_desc.reversible bit 2); bit 6 = none of its wider blocks is wider than 128 samples (they take the narrow kernel's
 // 32-pairs-by-2-rows layout instead of the raster-order wide kernel).  Every kernel skips the blocks of the other kind, so a caller that does not know passes
 // 3 | 32 (wavelet bits clear = both).
+//
+// The launches over n blocks under `widths`, in issue order: the one place that chooses; ht_encode_launch and
+// ojphgpu_ht_encode_launches both ask here.
+struct EncLaunch { uint32_t wide, flag, logp, wgs, per_wg; };   // ht_encode_wide_kernel<flag = S64> (1, logp 0) or ht_encode_kernel<flag = REV, logp> (0)
+constexpr uint32_t ENC_MAX_LAUNCHES = 5;
+static uint32_t enc_launches(uint32_t n, int widths, EncLaunch* L)
+{
+  if (n == 0) return 0;
+  uint32_t c = 0;
+  if ((widths & 12) == 0) widths |= 12;                   // the caller does not know the wavelets: both instantiations
+  const uint32_t grid = (n + WAVES - 1) / WAVES, ngrid = (n + NWAVES - 1) / NWAVES;
+  if (widths & 1) {                                         // blocks of up to 64 samples: 8 pairs by 8 quad rows where none is wider than 32
+    const uint32_t logp = (widths & 16) ? 3u : 4u;
+    if (widths & 4) L[c++] = { 0u, 1u, logp, ngrid, (uint32_t)NWAVES };
+    if (widths & 8) L[c++] = { 0u, 0u, logp, ngrid, (uint32_t)NWAVES };
+  }
+  if ((widths & 2) && (widths & 64)) {                      // wider blocks, none of them wider than 128 samples: 32 pairs by 2 quad rows
+    if (widths & 4) L[c++] = { 0u, 1u, 5u, ngrid, (uint32_t)NWAVES };
+    if (widths & 8) L[c++] = { 0u, 0u, 5u, ngrid, (uint32_t)NWAVES };
+  } else if (widths & 2)
+    L[c++] = { 1u, 0u, 0u, grid, (uint32_t)WAVES };
+  if (widths & 32)                                          // blocks of components on the 64-bit sample path
+    L[c++] = { 1u, 1u, 0u, grid, (uint32_t)WAVES };
+  return c;
+}
+
 int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, const void* d_coef, uint8_t* d_scratch,
                      uint8_t* d_out, uint32_t out_cap, ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status,
                      int widths, const uint32_t* d_regions, uint32_t nreg, uint32_t first)
@@ -1551,45 +1577,60 @@ int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, 
   if (ensure_tables() != 0) return OJPHGPU_E_HIP;
   if (!d_blocks || !d_coef || !d_scratch || !d_out || !d_results || !d_cursor || !d_status) return OJPHGPU_E_INVALID;
   if (nreg && (!d_regions || (nreg & (nreg - 1u)))) return OJPHGPU_E_INVALID;
-  dim3 grid((n + WAVES - 1) / WAVES);
-  if ((widths & 12) == 0) widths |= 12;                   // the caller does not know the wavelets: both instantiations
   // timing experiment: dynamic LDS nobody uses lowers the workgroups per CU (OJPHGPU_ENC_LDS_BALLAST bytes)
   static const unsigned ballast = [] { const char* e = getenv("OJPHGPU_ENC_LDS_BALLAST"); const long v = e ? atol(e) : 0; return v > 0 && v < 100000 ? (unsigned)v : 0u; }();
-  const dim3 ngrid((n + NWAVES - 1) / NWAVES);
-  if ((widths & 1) && (widths & 4) && (widths & 16))
-    hipLaunchKernelGGL((ht_encode_kernel<true, 3>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
+  using Kernel = void (*)(const ojphgpu_cb_desc*, uint32_t, const uint32_t*, uint8_t*, uint8_t*, uint32_t, ojphgpu_cb_result*, uint32_t*,
+                          uint32_t*, const uint32_t*, uint32_t, uint32_t);
+  EncLaunch L[ENC_MAX_LAUNCHES];
+  const uint32_t count = enc_launches(n, widths, L);
+  for (uint32_t i = 0; i < count; ++i) {
+    const EncLaunch& l = L[i];
+    Kernel k;
+    if (l.wide) k = l.flag ? ht_encode_wide_kernel<true> : ht_encode_wide_kernel<false>;
+    else if (l.logp == 3) k = l.flag ? ht_encode_kernel<true, 3> : ht_encode_kernel<false, 3>;
+    else if (l.logp == 4) k = l.flag ? ht_encode_kernel<true, 4> : ht_encode_kernel<false, 4>;
+    else k = l.flag ? ht_encode_kernel<true, 5> : ht_encode_kernel<false, 5>;
+    hipLaunchKernelGGL(k, dim3(l.wgs), dim3(64 * l.per_wg), l.wide ? 0u : ballast, (hipStream_t)stream, d_blocks, n,
                        (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-  else if ((widths & 1) && (widths & 4))
-    hipLaunchKernelGGL((ht_encode_kernel<true, 4>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-  if ((widths & 1) && (widths & 8) && (widths & 16))
-    hipLaunchKernelGGL((ht_encode_kernel<false, 3>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-  else if ((widths & 1) && (widths & 8))
-    hipLaunchKernelGGL((ht_encode_kernel<false, 4>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-  if ((widths & 2) && (widths & 64)) {                      // wider blocks, none of them wider than 128 samples: 32 pairs by 2 quad rows
-    if (widths & 4)
-      hipLaunchKernelGGL((ht_encode_kernel<true, 5>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                         (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-    if (widths & 8)
-      hipLaunchKernelGGL((ht_encode_kernel<false, 5>), ngrid, dim3(64 * NWAVES), ballast, (hipStream_t)stream, d_blocks, n,
-                         (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-  } else if (widths & 2)
-    hipLaunchKernelGGL(ht_encode_wide_kernel<false>, grid, dim3(64 * WAVES), 0, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
-  if (widths & 32)                                          // blocks of components on the 64-bit sample path
-    hipLaunchKernelGGL(ht_encode_wide_kernel<true>, grid, dim3(64 * WAVES), 0, (hipStream_t)stream, d_blocks, n,
-                       (const uint32_t*)d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, d_regions, nreg, first);
+  }
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 }  // namespace ojphgpu
+
+extern "C" int ojphgpu_ht_encode_ex(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
+                                     const void* d_coef, uint8_t* d_scratch, uint8_t* d_out, uint32_t out_cap,
+                                     ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status,
+                                     int widths, const uint32_t* d_regions, uint32_t nreg, uint32_t first)
+{
+  return ojphgpu::ht_encode_launch(stream, d_blocks, n, d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, widths, d_regions, nreg, first);
+}
 
 extern "C" int ojphgpu_ht_encode(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
                                   const void* d_coef, uint8_t* d_scratch, uint8_t* d_out, uint32_t out_cap,
                                   ojphgpu_cb_result* d_results, uint32_t* d_cursor, uint32_t* d_status)
 {
-  return ojphgpu::ht_encode_launch(stream, d_blocks, n, d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, 3 | 32, nullptr, 0, 0);
+  return ojphgpu_ht_encode_ex(stream, d_blocks, n, d_coef, d_scratch, d_out, out_cap, d_results, d_cursor, d_status, 3 | 32, nullptr, 0, 0);
+}
+
+extern "C" int ojphgpu_ht_encode_kinds(const ojphgpu_cb_desc* h_blocks, uint32_t n, int* widths)
+{
+  if (!widths || (!h_blocks && n)) return OJPHGPU_E_INVALID;
+  int k = 0;
+  for (uint32_t i = 0; i < n; ++i) k |= ojphgpu::ht_encode_block_widths(h_blocks[i].w, h_blocks[i].reversible);
+  *widths = ojphgpu::ht_encode_range_widths(k);
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_ht_encode_launches(uint32_t n, int widths, uint32_t* out, uint32_t cap, uint32_t* count)
+{
+  if (!count || (!out && cap)) return OJPHGPU_E_INVALID;
+  ojphgpu::EncLaunch L[ojphgpu::ENC_MAX_LAUNCHES];
+  *count = ojphgpu::enc_launches(n, widths, L);
+  if (cap < *count) return OJPHGPU_E_INVALID;
+  for (uint32_t i = 0; i < *count; ++i) {
+    out[5 * i] = L[i].wide; out[5 * i + 1] = L[i].flag; out[5 * i + 2] = L[i].logp; out[5 * i + 3] = L[i].wgs; out[5 * i + 4] = L[i].per_wg;
+  }
+  return OJPHGPU_OK;
 }
 
 namespace ojphgpu {

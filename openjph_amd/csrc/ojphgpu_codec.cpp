@@ -128,18 +128,16 @@ static ojphgpu_encoder::EncoderCut encoder_cut(const ojphgpu_encoder* e, uint32_
 {
   const Plan& P = *e->P;
   ojphgpu_encoder::EncoderCut c; c.n_top = n_top;
-  bool over32_top = false, over32_rest = false, over128_top = false, over128_rest = false;
+  int top = 0, rest = 0;                                   // the blocks' own statements, OR-ed (ht_encode_block_widths, ht_tables.h)
   for (size_t i = 0; i < e->block_ids.size(); ++i) {
     const Block& k = P.blocks[e->block_ids[i]]; const Band& B = P.bands[k.band];
-    const bool wide = is_wide(P, B.comp), rev = P.style(B.comp).rev;
-    (i < n_top ? c.widths_top : c.widths_rest) |= wide ? 32 : ((k.r.w > 64 ? 2 : 1) | (rev ? 4 : 8));
-    if (!wide && k.r.w > 32 && k.r.w <= 64) (i < n_top ? over32_top : over32_rest) = true;
-    if (!wide && k.r.w > 128) (i < n_top ? over128_top : over128_rest) = true;
+    // (the descriptor's `reversible` as encoder_block_layout writes it)
+    (i < n_top ? top : rest) |= ojphgpu::ht_encode_block_widths(k.r.w, (P.style(B.comp).rev ? 1u : 0u) | (is_wide(P, B.comp) ? 4u : 0u));
   }
-  if (!over32_top) c.widths_top |= 16;                     // every block of the range at most 32 samples wide (e.g. the IMF profile's 32 x 32)
-  if (!over32_rest) c.widths_rest |= 16;
-  if (!over128_top) c.widths_top |= 64;                    // no block wider than 128 samples: 128 x 32 blocks take the narrow kernel, too
-  if (!over128_rest) c.widths_rest |= 64;
+  // bit 4: every block of the range at most 32 samples wide (e.g. the IMF profile's 32 x 32); bit 6: none wider than 128
+  // samples (128 x 32 blocks take the narrow kernel, too)
+  c.widths_top = ojphgpu::ht_encode_range_widths(top);
+  c.widths_rest = ojphgpu::ht_encode_range_widths(rest);
   return c;
 }
 
