@@ -1635,6 +1635,57 @@ int  ojphgpu_frame_ycc_to_rgb(void* stream, const void* d_ycc, int ycc_container
  * the other, Y, Cb, Cr as in the plan's frame) and frame_bytes (of the RGB buffer) may be null. */
 int  ojphgpu_video_colour_fit(const ojphgpu_plan* plan, int container_bits, int decoding, int format, const ojphgpu_colour_spec* spec,
                               ojphgpu_colour_table* table, ojphgpu_colour_frame* frame, uint64_t* frame_bytes);   /* host only */
+
+/* ---- 7f. A Y, Cb, Cr frame of one chroma format -> another (kernels_chroma.hip): 4:4:4, 4:2:2, 4:2:0 and 4:4:0 into each other
+ * over planar containers, so that a pipe takes or hands back a video buffer whose chroma cell is not its plan's.  Exact integer
+ * arithmetic; pipeline.rechroma_plane / rechroma_frame state the same in numpy, sample for sample.
+ *   frame: w x h the luma plane; (sfx, sfy) the source's chroma cell, (dfx, dfy) the destination's, each factor 1 | 2; a chroma
+ *   plane of cell (cx, cy) is ceil(w / cx) x ceil(h / cy); *_off: the first element of each plane in its buffer, rows tightly
+ *   packed.  One container for both sides: 8 / 16 bits unsigned, 32 bits int32 (a decoder's planes may hold negative samples).
+ *   Luma is copied.  A chroma plane, per direction with source factor s and destination factor d: s == d: the index as it is,
+ *   weight 1.  d == 2 s (halved): output i stands ON source sample 2 i -- the taps (1, 2, 1) around it, indices clamped into
+ *   the plane (section 5e's filter and siting, phase 0), 2 bits.  s == 2 d (doubled): _ycc_to_rgb's rule, 2 C[x / 2] (x even),
+ *   C[(x - 1) / 2] + C[min((x + 1) / 2, n - 1)] (x odd), n the source length, 1 bit.  The directions are independent (one may
+ *   halve while the other doubles: 4:2:2 <-> 4:4:0); the sum is the 2-D product of their taps, exact, rounded ONCE: (acc + 2^(k -
+ *   1)) >> k, an arithmetic shift, k the bits of both directions; k == 0 is a copy.  No clamp: every weight is positive and they
+ *   sum to 2^k, so an output lies between the smallest and the largest input.
+ *   One launch for the three planes.  It writes the samples of the three destination planes and NOTHING else.  The frame
+ *   travels as a kernel argument: nothing is uploaded, nothing allocated.  OJPHGPU_CHROMA_WGS (read per call; 1 .. 65535) caps
+ *   the workgroups of the launch (default 2048, of 256 threads).
+ * OJPHGPU_E_INVALID: a null pointer, a factor other than 1 or 2, w or h of 0, a container that is not 8 / 16 / 32 bits, a buffer
+ * not aligned to its container, a source plane that overlaps a destination plane. */
+#define OJPHGPU_CHROMA_COSITED 1
+typedef struct ojphgpu_chroma_frame { uint32_t w, h, sfx, sfy, dfx, dfy; uint64_t src_off[3], dst_off[3]; } ojphgpu_chroma_frame;
+int  ojphgpu_frame_rechroma(void* stream, const void* d_src, void* d_dst, int container_bits, const ojphgpu_chroma_frame* frame);
+/* The frames of an encoder pipe are handed over as one video buffer whose chroma cell need not be the plan's: any format of
+ * sections 7b - 7d except the five RGB names (BGRA / RGBA / ARGB / R210 / R10K hold R, G, B: _set_video_colour is their way), mode
+ * = OJPHGPU_CHROMA_COSITED.  Two launches per frame on the compute stream behind the upload: the family's unpack into a buffer of
+ * the slot sized to the FORMAT's planes, then ojphgpu_frame_rechroma into the slot's image.  Every codestream is, byte for byte,
+ * the plain encode of pipeline.rechroma_frame(unpacked planes, the format's cell, the plan's cell); a byte budget, a quality
+ * target and a cap combine with it as with _set_video (a target is measured against the planes in the plan's chroma format).
+ * _acquire hands out the format's tight layout for the luma size.  A format whose cell IS the plan's is accepted and is exactly
+ * the _set_video hand-over: one launch, no intermediate buffer.  The calling window of _set_video; excludes _set_pixels /
+ * _set_packed, the plain _set_video and _set_video_colour (for the life of the pipe or until set back to planes by format 0 with
+ * mode 0 or OJPHGPU_CHROMA_COSITED); those setters are unchanged.
+ * OJPHGPU_E_INVALID, the pipe left as it was: an unknown format or one of the five RGB names; a mode other than
+ * OJPHGPU_CHROMA_COSITED (0 only with format 0); a plan that has not exactly three unsigned components of one depth that the
+ * format and the container hold, component 0 on the reference grid, components 1 and 2 sub-sampled alike by 1 or 2 each way with
+ * planes of (ceil(w / fx), ceil(h / fy)), in the tight frame layout; an odd image offset in a direction where EITHER side's cell
+ * is 2 (the chroma sample would stand on the cell's second luma sample: phase 1). */
+int  ojphgpu_enc_pipe_set_video_chroma(ojphgpu_enc_pipe* pipe, int format, int mode);
+/* The mirror: decoded frames come back as that video buffer -- ojphgpu_frame_rechroma from the slot's image into its buffer of
+ * the format's planes, then the family's pack (which clamps to [0, 2^depth - 1], negative int32 samples included: a pipe with
+ * 32-bit containers is accepted).  The samples enter the stage as the pipe's containers hold them.  Judged on the view's plan
+ * when the pipe decodes a view: a reduced resolution always passes; a window when its x0 is even where either side's fx == 2 and
+ * its y0 is even where either side's fy == 2 (with a reduced resolution too: a multiple of 2^(skip_recon + 1) there). */
+int  ojphgpu_dec_pipe_set_video_chroma(ojphgpu_dec_pipe* pipe, int format, int mode);
+/* The plan judgement of the two setters (decoding == 0 / != 0) without a pipe or a device: OJPHGPU_OK or the setter's
+ * OJPHGPU_E_INVALID; a restricted plan is judged as the view it is.  frame (may be null): the stage's descriptor -- source and
+ * destination as the pipe would launch it, the format's planes w h, then the two chroma planes, one after the other, the
+ * plan's as in its frame; equal cells: both sides the plan's, which no launch uses.  buffer_bytes (may be null): of the video
+ * buffer. */
+int  ojphgpu_video_chroma_fit(const ojphgpu_plan* plan, int container_bits, int decoding, int format, int mode, ojphgpu_chroma_frame* frame,
+                              uint64_t* buffer_bytes);   /* host only */
 /* Runs of bytes scattered over a source -> the staged layout a view decoder reads (kernels_assemble.hip).  d_src: the
  * device address of the source -- mapped pinned host memory (hipHostGetDevicePointer; the kernel then reads across PCIe
  * exactly the dwords that hold the runs) or device memory -- 16-byte aligned; src_cap: the bytes of it that may be read, a

@@ -188,6 +188,11 @@ class ColourFrame(C.Structure):           # ojphgpu_colour_frame
                 ("ycc_first", C.c_uint64 * 3)]
 
 
+class ChromaFrame(C.Structure):           # ojphgpu_chroma_frame
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("sfx", C.c_uint32), ("sfy", C.c_uint32), ("dfx", C.c_uint32), ("dfy", C.c_uint32),
+                ("src_off", C.c_uint64 * 3), ("dst_off", C.c_uint64 * 3)]
+
+
 class ColourSpec(C.Structure):            # ojphgpu_colour_spec
     _fields_ = [("standard", C.c_int), ("rgb_range", C.c_int), ("ycc_range", C.c_int), ("rgb_depth", C.c_uint32)]
 
@@ -195,6 +200,8 @@ class ColourSpec(C.Structure):            # ojphgpu_colour_spec
 COLOUR_STANDARD = {"bt601": 601, "bt709": 709, "bt2020": 2020}
 COLOUR_DIRECTION = {"forward": 0, "inverse": 1}
 COLOUR_RANGE = {"full": 0, "narrow": 1}
+CHROMA_COSITED = 1
+CHROMA = {"cosited": CHROMA_COSITED}
 RESAMPLE_NONE, RESAMPLE_COSITED = 0, 1
 RESAMPLE = {None: RESAMPLE_NONE, "none": RESAMPLE_NONE, "cosited": RESAMPLE_COSITED}
 
@@ -479,6 +486,10 @@ SIGNATURES = {
                                            C.POINTER(C.c_uint64)]),
     "ojphgpu_enc_pipe_set_video_colour": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ColourSpec)]),
     "ojphgpu_dec_pipe_set_video_colour": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ColourSpec)]),
+    "ojphgpu_frame_rechroma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ChromaFrame)]),
+    "ojphgpu_video_chroma_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ChromaFrame), C.POINTER(C.c_uint64)]),
+    "ojphgpu_enc_pipe_set_video_chroma": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ojphgpu_dec_pipe_set_video_chroma": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ojphgpu_enc_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_dec_pipe_set_video": (C.c_int, [C.c_void_p, C.c_int]),
     "ojphgpu_tc_pipe_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

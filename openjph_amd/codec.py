@@ -1058,6 +1058,32 @@ def ycc_to_rgb(d_ycc, table, width, height, fx=1, fy=1, dtype=None, out=None, rg
     return _colour_stage("ycc_to_rgb", d_ycc, lambda w, h, cw, ch: 3 * w * h, table, width, height, fx, fy, rgb_first, ycc_first, dtype, out)
 
 
+def frame_rechroma(src, dst, width, height, src_cell, dst_cell, src_off=None, dst_off=None):
+    """ojphgpu_frame_rechroma: src a device tensor of 8-, 16- (unsigned, whatever the dtype's sign) or 32-bit (int32) containers
+    holding Y [H, W] and Cb, Cr of src_cell = (sub_x, sub_y), tightly packed one after the other or each from its element of
+    src_off -> the frame with chroma planes of dst_cell in dst, a device tensor of the same container (None: zeros of the
+    planes' size; only the planes' samples are written), each plane from its element of dst_off.  pipeline.rechroma_frame
+    states the arithmetic.  -> dst"""
+    torch = _torch()
+    w, h = int(width), int(height)
+    assert src.is_cuda and src.element_size() in (1, 2, 4)
+    dev = src.device.index or 0
+    f = capi.ChromaFrame(w, h, int(src_cell[0]), int(src_cell[1]), int(dst_cell[0]), int(dst_cell[1]))
+    sc = -(-w // max(f.sfx, 1)) * -(-h // max(f.sfy, 1))
+    dc = -(-w // max(f.dfx, 1)) * -(-h // max(f.dfy, 1))
+    f.src_off[:] = [0, w * h, w * h + sc] if src_off is None else [int(x) for x in src_off]
+    f.dst_off[:] = [0, w * h, w * h + dc] if dst_off is None else [int(x) for x in dst_off]
+    if dst is None:
+        assert dst_off is None, "frame_rechroma: planes placed by hand need dst="
+        dst = torch.zeros(w * h + 2 * dc, dtype=src.dtype, device=src.device)
+    assert dst.is_cuda and dst.element_size() == src.element_size()
+    with torch.cuda.device(dev):
+        check(capi.lib().ojphgpu_frame_rechroma(_stream_ptr(torch, dev), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), src.element_size() * 8,
+                                                C.byref(f)), "frame_rechroma")
+        torch.cuda.synchronize(dev)
+    return dst
+
+
 def dwt_general_image(direction, steps, elem, params: Params, descs: np.ndarray, image, arena, max_w, max_h, K=1.0, container=32):
     """ojphgpu_dwt_forward_general_image / _inverse_general_image: the general lifting kernels' top level with the conversion
     fused in (steps as for dwt_general; elem 0 = int32, 2 = float); descs as for dwt_image"""

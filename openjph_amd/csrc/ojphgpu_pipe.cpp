@@ -152,7 +152,13 @@ struct Handover {
   ojphgpu_colour_spec spec{};
   ojphgpu_colour_table table{};
   ojphgpu_colour_frame frame{};
-  size_t rgb_bytes = 0;                              // of the slot's `rgb` buffer: 3 w h containers
+  size_t rgb_bytes = 0;                              // of the slot's `rgb` buffer: 3 w h containers (chroma: the format's planes)
+  // VIDEO through _set_video_chroma (section 7f): the buffer holds Y, Cb, Cr in the FORMAT's chroma cell, the plan in its own.
+  // chroma: the setter's mode (0: another setter's); stage: the cells differ, so two launches -- the format's planes stand one
+  // after the other in the slot's `rgb` buffer, cframe says where (source: the buffer's side for an encoder pipe, the plan's
+  // for a decoder pipe).  Equal cells: the plain VIDEO hand-over
+  int chroma = 0; bool stage = false;
+  ojphgpu_chroma_frame cframe{};
 };
 
 enum { ODD_X0 = 1, ODD_Y0 = 2 };                    // a decoder pipe's window begins on an odd column / row
@@ -197,12 +203,63 @@ int handover_fit_colour(const Plan& P, int container, bool decoding, int odd_ori
   return OJPHGPU_OK;
 }
 
+int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Handover& want);
+
+// The plan judgement of the two _set_video_chroma setters (every refusal that needs no device): `want` (format, chroma) -> the
+// rest of it.  A format of the plan's own cell is judged as the plain VIDEO hand-over, behind the origin rule of this one.
+int handover_fit_chroma(const Plan& P, int container, bool decoding, int odd_origin, Handover& want)
+{
+  const VideoDesc* v = video_desc(want.format); uint64_t bytes = 0;
+  if (!v || P.comps.size() != 3 || want.chroma != OJPHGPU_CHROMA_COSITED) return OJPHGPU_E_INVALID;
+  // the RGB members of the 4:4:4 family hold R, G, B: _set_video_colour is their way
+  if (want.format == OJPHGPU_VIDEO_BGRA || want.format == OJPHGPU_VIDEO_RGBA || want.format == OJPHGPU_VIDEO_ARGB ||
+      want.format == OJPHGPU_VIDEO_R210 || want.format == OJPHGPU_VIDEO_R10K) return OJPHGPU_E_INVALID;
+  const CompGeo& Y = P.comps[0]; const CompGeo& Cb = P.comps[1]; const CompGeo& Cr = P.comps[2];
+  for (const CompGeo& g : P.comps) if (g.is_signed || g.bit_depth != Y.bit_depth) return OJPHGPU_E_INVALID;
+  if (Y.w == 0 || Y.h == 0) return OJPHGPU_E_INVALID;
+  if (Y.dx != 1 || Y.dy != 1 || Cb.dx != Cr.dx || Cb.dy != Cr.dy || (Cb.dx != 1 && Cb.dx != 2) || (Cb.dy != 1 && Cb.dy != 2)) return OJPHGPU_E_INVALID;
+  const uint32_t pfx = Cb.dx, pfy = Cb.dy, ffx = v->r.sub_x, ffy = v->r.sub_y;   // the plan's cell, the format's
+  const uint32_t cw = (uint32_t)(((uint64_t)Y.w + pfx - 1) / pfx), ch = (uint32_t)(((uint64_t)Y.h + pfy - 1) / pfy);
+  const uint64_t wh = (uint64_t)Y.w * Y.h;
+  if (Cb.w != cw || Cb.h != ch || Cr.w != cw || Cr.h != ch) return OJPHGPU_E_INVALID;
+  if (Y.frame_off != 0 || Cb.frame_off != wh || Cr.frame_off != wh + (uint64_t)cw * ch) return OJPHGPU_E_INVALID;   // the tight frame layout
+  // a chroma sample stands ON the first luma sample of its cell (phase 0) on BOTH sides: no odd image offset, no window from
+  // an odd column or row, in a direction where either cell is 2
+  const bool cx = pfx == 2 || ffx == 2, cy = pfy == 2 || ffy == 2;
+  if ((cx && ((P.p.image_x0 & 1u) || (odd_origin & ODD_X0))) || (cy && ((P.p.image_y0 & 1u) || (odd_origin & ODD_Y0)))) return OJPHGPU_E_INVALID;
+  if (P.has_region && P.skip_recon) {                 // a window at a reduced resolution: its origin is even on THAT grid
+    if (P.skip_recon > 30) return OJPHGPU_E_INVALID;
+    const uint32_t cell = 2u << P.skip_recon;
+    if ((cx && P.region[0] % cell) || (cy && P.region[1] % cell)) return OJPHGPU_E_INVALID;
+  }
+  if (pfx == ffx && pfy == ffy) {                     // the plain hand-over: one launch, no intermediate buffer
+    Handover plain = want;
+    plain.chroma = 0;
+    const int rc = handover_fit(P, container, decoding, odd_origin, plain);
+    if (rc) return rc;
+    plain.chroma = want.chroma; plain.stage = false;
+    plain.cframe = ojphgpu_chroma_frame{ Y.w, Y.h, pfx, pfy, pfx, pfy, { 0, wh, wh + (uint64_t)cw * ch }, { 0, wh, wh + (uint64_t)cw * ch } };
+    want = plain;
+    return OJPHGPU_OK;
+  }
+  if (!video_check(v, Y.w, Y.h, Y.bit_depth, container) || !video_layout(v, Y.w, Y.h, &want.row_bytes, &want.chroma_offset, &bytes)) return OJPHGPU_E_INVALID;
+  const uint64_t fc = (((uint64_t)Y.w + ffx - 1) / ffx) * (((uint64_t)Y.h + ffy - 1) / ffy);   // samples of a chroma plane of the format
+  want.w = Y.w; want.h = Y.h; want.depth = Y.bit_depth;
+  want.stage = true;
+  if (decoding) want.cframe = ojphgpu_chroma_frame{ Y.w, Y.h, pfx, pfy, ffx, ffy, { Y.frame_off, Cb.frame_off, Cr.frame_off }, { 0, wh, wh + fc } };
+  else want.cframe = ojphgpu_chroma_frame{ Y.w, Y.h, ffx, ffy, pfx, pfy, { 0, wh, wh + fc }, { Y.frame_off, Cb.frame_off, Cr.frame_off } };
+  want.rgb_bytes = (size_t)(wh + 2 * fc) * (size_t)(container / 8);
+  want.bytes = (size_t)bytes;
+  return OJPHGPU_OK;
+}
+
 // Every refusal of the three setters, and the size of the frame: `want` (kind, bits, big_endian, format) -> the rest of it.
 // decoding: the frame comes back, clamped to one range; odd_origin: the pipe decodes a window whose first column (ODD_X0) or
 // first row (ODD_Y0) is odd.
 int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Handover& want)
 {
   if (want.kind == VIDEO && want.colour) return handover_fit_colour(P, container, decoding, odd_origin, want);
+  if (want.kind == VIDEO && want.chroma) return handover_fit_chroma(P, container, decoding, odd_origin, want);
   const CompGeo& Y = P.comps[0];
   want.w = Y.w; want.h = Y.h; want.depth = 0;
   for (const CompGeo& g : P.comps) want.depth = std::max(want.depth, g.bit_depth);
@@ -244,6 +301,22 @@ int handover_fit(const Plan& P, int container, bool decoding, int odd_origin, Ha
   return OJPHGPU_E_INVALID;
 }
 
+// a video buffer in its tight layout <-> tightly packed planes of the format's cell (4:2:0 and 4:4:4: rows, of both planes, at row_bytes)
+int video_launch(hipStream_t stream, const Handover& h, int container, bool unpack, void* d_staged, void* d_planes)
+{
+  uint8_t* const luma = (uint8_t*)d_staged;
+  switch (video_desc(h.format)->r.family) {
+  case OJPHGPU_VIDEO_FAMILY_444:
+    return unpack ? ojphgpu_unpack_video444(stream, h.format, d_staged, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
+                  : ojphgpu_pack_video444(stream, h.format, d_planes, d_staged, h.row_bytes, h.w, h.h, container, h.depth);
+  case OJPHGPU_VIDEO_FAMILY_420:
+    return unpack ? ojphgpu_unpack_video420(stream, h.format, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
+                  : ojphgpu_pack_video420(stream, h.format, d_planes, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, h.w, h.h, container, h.depth);
+  }
+  return unpack ? ojphgpu_unpack_video(stream, h.format, d_staged, d_planes, h.w, h.h, h.depth, container)
+                : ojphgpu_pack_video(stream, h.format, d_planes, d_staged, h.w, h.h, container, h.depth);
+}
+
 // The launch of a hand-over on `stream`: staged frame -> planes (unpack: the encoder) or planes -> staged frame, clamped
 // (the decoder).  Nothing for PLANES.
 int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int container, bool unpack, void* d_staged, void* d_planes, void* d_rgb)
@@ -257,6 +330,15 @@ int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int co
     if ((rc = ojphgpu_frame_ycc_to_rgb(stream, d_planes, container, d_rgb, container, &h.frame, &h.table)) != 0) return rc;
     return ojphgpu_pack_video444(stream, h.format, d_rgb, d_staged, h.row_bytes, h.w, h.h, container, h.depth);
   }
+  if (h.kind == VIDEO && h.stage) {                   // two launches: the buffer <-> planes of the format's cell <-> the plan's planes
+    int rc;
+    if (unpack) {
+      if ((rc = video_launch(stream, h, container, true, d_staged, d_rgb)) != 0) return rc;
+      return ojphgpu_frame_rechroma(stream, d_rgb, d_planes, container, &h.cframe);
+    }
+    if ((rc = ojphgpu_frame_rechroma(stream, d_planes, d_rgb, container, &h.cframe)) != 0) return rc;
+    return video_launch(stream, h, container, false, d_staged, d_rgb);
+  }
   switch (h.kind) {
   case PIXELS:                                        // the file's / capture buffer's / display buffer's pixel order
     return unpack ? ojphgpu_unpack_pixels(stream, d_staged, d_planes, h.w, h.h, P.p.num_comps, h.bits, h.big_endian, container)
@@ -264,19 +346,8 @@ int handover_launch(hipStream_t stream, const Handover& h, const Plan& P, int co
   case PACKED:
     return unpack ? ojphgpu_unpack_bits(stream, d_staged, d_planes, P.frame_elems, h.bits, container)
                   : ojphgpu_pack_bits(stream, d_planes, d_staged, P.frame_elems, container, h.bits);
-  case VIDEO: {                                       // 4:2:0 and 4:4:4: the tight layout, rows (of both planes) at row_bytes
-    uint8_t* const luma = (uint8_t*)d_staged;
-    switch (video_desc(h.format)->r.family) {
-    case OJPHGPU_VIDEO_FAMILY_444:
-      return unpack ? ojphgpu_unpack_video444(stream, h.format, d_staged, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
-                    : ojphgpu_pack_video444(stream, h.format, d_planes, d_staged, h.row_bytes, h.w, h.h, container, h.depth);
-    case OJPHGPU_VIDEO_FAMILY_420:
-      return unpack ? ojphgpu_unpack_video420(stream, h.format, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, d_planes, h.w, h.h, h.depth, container)
-                    : ojphgpu_pack_video420(stream, h.format, d_planes, luma, h.row_bytes, luma + h.chroma_offset, h.row_bytes, h.w, h.h, container, h.depth);
-    }
-    return unpack ? ojphgpu_unpack_video(stream, h.format, d_staged, d_planes, h.w, h.h, h.depth, container)
-                  : ojphgpu_pack_video(stream, h.format, d_planes, d_staged, h.w, h.h, container, h.depth);
-  }
+  case VIDEO:
+    return video_launch(stream, h, container, unpack, d_staged, d_planes);
   }
   return OJPHGPU_OK;
 }
@@ -289,14 +360,17 @@ template <class Slot> void* handover_device_side(const Handover& h, Slot& s) { r
 // frame and staging buffer hold the new size -- both only grow, so the call may be repeated -- and the pipe takes the
 // hand-over.  A refusal changes nothing.
 template <class Pipe, class Slot>
-int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, int odd_origin, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr)
+int handover_set(Pipe* p, Pinned Slot::*frame, bool decoding, int odd_origin, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr,
+                 int chroma = 0)
 {
-  if (p->ho.kind != PLANES && (p->ho.kind != kind || p->ho.colour != (spec != nullptr))) return OJPHGPU_E_INVALID;   // (_set_video and _set_video_colour exclude each other too)
+  // (_set_video, _set_video_colour and _set_video_chroma -- chroma != 0 -- exclude each other too)
+  if (p->ho.kind != PLANES && (p->ho.kind != kind || p->ho.colour != (spec != nullptr) || (p->ho.chroma != 0) != (chroma != 0))) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     Handover h;
     h.kind = arg ? kind : PLANES; h.big_endian = big_endian ? 1 : 0;
     (kind == VIDEO ? h.format : h.bits) = arg;
     if (spec && arg) { h.colour = true; h.spec = *spec; }
+    if (chroma && arg) h.chroma = chroma;
     const int rc = handover_fit(*p->P, p->container, decoding, odd_origin, h);
     if (rc) return rc;
     if (h.kind != PLANES) {
@@ -343,7 +417,7 @@ struct EncSlot {
   EncOut o;
   DeviceBuf image;
   Grow cs, pixels;                                  // pixels: the frame as it was handed over, unless that is as planes
-  Grow rgb;                                         // a hand-over with a colour spec: the R, G, B planes between its two launches
+  Grow rgb;                                         // a hand-over of two launches (a colour spec: R, G, B; a chroma stage: the format's planes): what stands between them
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   int rc = 0; size_t cs_len = 0;
   double t_submit = 0, t_done = 0, t_t2 = 0;
@@ -744,11 +818,14 @@ extern "C" int ojphgpu_enc_pipe_acquire(ojphgpu_enc_pipe* p, void** h_frame, siz
 }
 
 // before the first _acquire: the hand-over may still be set (and set again)
-static int enc_set_handover(ojphgpu_enc_pipe* p, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr)
+static int enc_set_handover(ojphgpu_enc_pipe* p, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr, int chroma = 0)
 {
   if (!p || p->dead || p->n_acq != 0 || p->slots[0].state != FREE) return OJPHGPU_E_INVALID;
-  return handover_set(p, &EncSlot::h_in, false, 0, kind, arg, big_endian, spec);
+  return handover_set(p, &EncSlot::h_in, false, 0, kind, arg, big_endian, spec, chroma);
 }
+
+// mode of a _set_video_chroma call: COSITED, or 0 together with format 0 (planes again)
+static bool chroma_mode_ok(int format, int mode) { return mode == OJPHGPU_CHROMA_COSITED || (mode == 0 && format == 0); }
 
 extern "C" int ojphgpu_enc_pipe_set_pixels(ojphgpu_enc_pipe* p, int pixel_bits, int big_endian) { return enc_set_handover(p, PIXELS, pixel_bits, big_endian); }
 extern "C" int ojphgpu_enc_pipe_set_packed(ojphgpu_enc_pipe* p, int bits) { return enc_set_handover(p, PACKED, bits, 0); }
@@ -756,6 +833,11 @@ extern "C" int ojphgpu_enc_pipe_set_video(ojphgpu_enc_pipe* p, int format) { ret
 extern "C" int ojphgpu_enc_pipe_set_video_colour(ojphgpu_enc_pipe* p, int format, const ojphgpu_colour_spec* spec)
 {
   return spec ? enc_set_handover(p, VIDEO, format, 0, spec) : OJPHGPU_E_INVALID;
+}
+
+extern "C" int ojphgpu_enc_pipe_set_video_chroma(ojphgpu_enc_pipe* p, int format, int mode)
+{
+  return chroma_mode_ok(format, mode) ? enc_set_handover(p, VIDEO, format, 0, nullptr, OJPHGPU_CHROMA_COSITED) : OJPHGPU_E_INVALID;
 }
 
 extern "C" int ojphgpu_enc_pipe_submit(ojphgpu_enc_pipe* p)
@@ -965,7 +1047,7 @@ struct DecSlot {
   SlotState state = FREE;
   Pinned h_cs, h_descs, h_img, h_status;
   Grow data, pixels;                                // pixels: the frame as it is handed back, unless that is as planes
-  Grow rgb;                                         // a hand-over with a colour spec: the R, G, B planes between its two launches
+  Grow rgb;                                         // a hand-over of two launches (a colour spec: R, G, B; a chroma stage: the format's planes): what stands between them
   DeviceBuf image, cb_descs, status, runs;          // runs: a view's run table, copied there for the gather kernel
   hipEvent_t ev_in = nullptr, ev_kern = nullptr, ev_done = nullptr;
   size_t cs_len = 0;
@@ -1277,11 +1359,11 @@ extern "C" int ojphgpu_dec_pipe_collect(ojphgpu_dec_pipe* p, const void** h_fram
 }
 
 // before the first _submit: the hand-over may still be set (and set again)
-static int dec_set_handover(ojphgpu_dec_pipe* p, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr)
+static int dec_set_handover(ojphgpu_dec_pipe* p, int kind, int arg, int big_endian, const ojphgpu_colour_spec* spec = nullptr, int chroma = 0)
 {
   if (!p || p->n_sub != 0) return OJPHGPU_E_INVALID;
   const int odd_origin = !p->has_region ? 0 : ((p->region[0] & 1u) ? ODD_X0 : 0) | ((p->region[1] & 1u) ? ODD_Y0 : 0);
-  return handover_set(p, &DecSlot::h_img, true, odd_origin, kind, arg, big_endian, spec);
+  return handover_set(p, &DecSlot::h_img, true, odd_origin, kind, arg, big_endian, spec, chroma);
 }
 
 extern "C" int ojphgpu_dec_pipe_set_pixels(ojphgpu_dec_pipe* p, int pixel_bits, int big_endian) { return dec_set_handover(p, PIXELS, pixel_bits, big_endian); }
@@ -1292,7 +1374,30 @@ extern "C" int ojphgpu_dec_pipe_set_video_colour(ojphgpu_dec_pipe* p, int format
   return spec ? dec_set_handover(p, VIDEO, format, 0, spec) : OJPHGPU_E_INVALID;
 }
 
-// the judgement of the two setters above on a plan alone, without a pipe or a device
+extern "C" int ojphgpu_dec_pipe_set_video_chroma(ojphgpu_dec_pipe* p, int format, int mode)
+{
+  return chroma_mode_ok(format, mode) ? dec_set_handover(p, VIDEO, format, 0, nullptr, OJPHGPU_CHROMA_COSITED) : OJPHGPU_E_INVALID;
+}
+
+// the judgement of the two _set_video_chroma setters on a plan alone, without a pipe or a device
+extern "C" int ojphgpu_video_chroma_fit(const ojphgpu_plan* plan, int container_bits, int decoding, int format, int mode, ojphgpu_chroma_frame* frame,
+                                        uint64_t* buffer_bytes)
+{
+  if (!plan || (container_bits != 8 && container_bits != 16 && container_bits != 32) || mode != OJPHGPU_CHROMA_COSITED) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    const Plan& P = plan->plan;
+    Handover h;
+    h.kind = VIDEO; h.format = format; h.chroma = mode;
+    const int odd_origin = !P.has_region ? 0 : ((P.region[0] & 1u) ? ODD_X0 : 0) | ((P.region[1] & 1u) ? ODD_Y0 : 0);
+    const int rc = handover_fit(P, container_bits, decoding != 0, odd_origin, h);
+    if (rc) return rc;
+    if (frame) *frame = h.cframe;
+    if (buffer_bytes) *buffer_bytes = h.bytes;
+    return OJPHGPU_OK;
+  });
+}
+
+// the judgement of the two _set_video_colour setters on a plan alone, without a pipe or a device
 extern "C" int ojphgpu_video_colour_fit(const ojphgpu_plan* plan, int container_bits, int decoding, int format, const ojphgpu_colour_spec* spec,
                                         ojphgpu_colour_table* table, ojphgpu_colour_frame* frame, uint64_t* frame_bytes)
 {

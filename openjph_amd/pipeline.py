@@ -42,7 +42,7 @@ class _Handover:
     """The hand-over setters of both pipes (ojphgpu_{enc,dec}_pipe_set_pixels / _set_packed / _set_video; None or 0: planes
     again): before the first acquire() of an encoder pipe / submit() of a decoder pipe, repeatable until then, one kind at a
     time.  A refusal raises OjphError (capi.E_INVALID) and leaves the pipe as it was."""
-    pixels = packed = video = colour = None
+    pixels = packed = video = colour = chroma = None
 
     def _set(self, kind, *args):
         name = "%s_pipe_set_%s" % (self._side, kind)
@@ -73,6 +73,17 @@ class _Handover:
         self._set("video_colour", _video_code(self.plan, fmt, "%s_pipe_set_video_colour" % self._side), C.byref(spec))
         self.video = fmt
         self.colour = (colour if isinstance(colour, Colour) else Colour(colour)) if fmt else None
+
+    def set_video_chroma(self, fmt, mode="cosited"):
+        """the buffer holds Y, Cb, Cr in the chroma format of fmt (any name of the three families but the five RGB ones), the plan
+        in its own -- 4:4:4, 4:2:2, 4:2:0 or 4:4:0: chroma is halved (taps (1, 2, 1), cosited) or doubled (linear) on the device
+        between the buffer and the planes, as rechroma_frame states it (ojphgpu_{enc,dec}_pipe_set_video_chroma; ojphgpu.h section
+        7f).  Equal cells: exactly set_video.  Excludes set_video and set_video_colour; fmt None: planes again"""
+        if mode not in capi.CHROMA:
+            raise ValueError("chroma mode %r: one of %s" % (mode, ", ".join(sorted(capi.CHROMA))))
+        self._set("video_chroma", _video_code(self.plan, fmt, "%s_pipe_set_video_chroma" % self._side), capi.CHROMA[mode])
+        self.video = fmt
+        self.chroma = mode if fmt else None
 
 
 def pack_bits(samples, bits):
@@ -384,6 +395,74 @@ def resample_frame(planes, factors, phases=None):
     return [resample_plane(q, fx, fy, px, py) for q, (fx, fy), (px, py) in zip(planes, factors, phases)]
 
 
+def _rechroma_taps(n, no, s, d):
+    """one direction of rechroma_plane: n source samples of factor s -> no outputs of factor d, as [(indices, weight), ...] and
+    the bits the weights sum to"""
+    x = np.arange(no)
+    if s == d:
+        return [(x, 1)], 0
+    if d == 2 * s:                                    # resample_plane's taps at phase 0
+        return [(np.clip(2 * x - 1, 0, n - 1), 1), (2 * x, 2), (np.clip(2 * x + 1, 0, n - 1), 1)], 2
+    return [(x // 2, 1), (np.where(x & 1, np.minimum((x + 1) // 2, n - 1), x // 2), 1)], 1      # ycc_to_rgb's pair
+
+
+def rechroma_plane(q, s, d, size=None):
+    """numpy statement of ojphgpu_frame_rechroma on one chroma plane (include/ojphgpu.h section 7f): q [hs, ws] of the cell s =
+    (sub_x, sub_y) -> the plane of the cell d, each factor 1 or 2.  Per direction: equal factors: the index as it is; d == 2 s
+    (halved): output i stands ON source sample 2 i, taps (1, 2, 1), indices clamped into the plane, 2 bits -- resample_plane at
+    phase 0; s == 2 d (doubled): 2 C[x / 2] for even x, C[(x - 1) / 2] + C[min((x + 1) / 2, n - 1)] for odd x, 1 bit -- ycc_to_rgb's
+    rule.  The 2-D product of the two directions' taps, exact in 64 bits, rounded once: (acc + 2^(k-1)) >> k; k == 0 is a copy.
+    No clamp: the weights are positive and sum to 2^k.  size = (w, h) of the luma plane: a plane of a cell (cx, cy) is ceil(w /
+    cx) x ceil(h / cy) (None: a doubled direction gives twice the source's length).  -> int64"""
+    (sx, sy), (dx, dy) = s, d
+    if any(f not in (1, 2) for f in (sx, sy, dx, dy)):
+        raise ValueError("rechroma_plane: cell factors are 1 or 2")
+    v = np.asarray(q).astype(np.int64)
+    if v.ndim != 2 or v.size == 0:
+        raise ValueError("rechroma_plane: a plane is [H, W]")
+    hs, ws = v.shape
+    if size is None:
+        size = (ws * sx, hs * sy)
+    w, h = int(size[0]), int(size[1])
+    if (-(-w // sx), -(-h // sy)) != (ws, hs):
+        raise ValueError("rechroma_plane: a plane of %s, the cell %s of a %d x %d frame has %s" % ((hs, ws), (sx, sy), w, h, (-(-h // sy), -(-w // sx))))
+    wo, ho = -(-w // dx), -(-h // dy)
+    tx, kx = _rechroma_taps(ws, wo, sx, dx)
+    ty, ky = _rechroma_taps(hs, ho, sy, dy)
+    acc = np.zeros((ho, wo), np.int64)
+    for iy, wy in ty:
+        for ix, wx in tx:
+            acc += wy * wx * v[np.ix_(iy, ix)]
+    k = kx + ky
+    return (acc + (1 << (k - 1)) >> k) if k else acc
+
+
+def rechroma_frame(planes, src_cell, dst_cell):
+    """planes = [Y [H, W], Cb, Cr of src_cell] -> [Y as it is, Cb, Cr of dst_cell] (int64): rechroma_plane per chroma plane"""
+    y = np.asarray(planes[0]).astype(np.int64)
+    if len(planes) != 3 or y.ndim != 2 or y.size == 0:
+        raise ValueError("rechroma_frame: three planes, the luma plane [H, W]")
+    size = (y.shape[1], y.shape[0])
+    return [y] + [rechroma_plane(q, src_cell, dst_cell, size) for q in planes[1:]]
+
+
+def video_cell(fmt):
+    """-> the chroma cell (sub_x, sub_y) of a video format's name"""
+    return {422: (2, 1), 420: (2, 2), 444: (1, 1)}[_entry(0, fmt)[1]]
+
+
+def video_chroma_fit(plan, fmt, container=16, decoding=False, mode="cosited"):
+    """ojphgpu_video_chroma_fit: the judgement of set_video_chroma on a plan alone, without a pipe or a device (OjphError
+    E_INVALID where the setter would refuse) -> dict(src_cell, dst_cell = the stage's two cells (equal: the plain set_video
+    hand-over), src_off, dst_off = where its planes stand, w, h, bytes = of the video buffer)"""
+    f, n = capi.ChromaFrame(), C.c_uint64()
+    m = capi.CHROMA.get(mode, mode)
+    check(capi.lib().ojphgpu_video_chroma_fit(plan.handle, int(container), int(bool(decoding)), _video_code(plan, fmt, "video_chroma_fit"), int(m),
+                                              C.byref(f), C.byref(n)), "video_chroma_fit")
+    return dict(w=int(f.w), h=int(f.h), src_cell=(int(f.sfx), int(f.sfy)), dst_cell=(int(f.dfx), int(f.dfy)), src_off=tuple(int(x) for x in f.src_off),
+                dst_off=tuple(int(x) for x in f.dst_off), bytes=int(n.value))
+
+
 # RGB <-> YCbCr (ojphgpu.h section 7e): the numpy statement of ojphgpu_colour_table_make and of the two stages
 COLOUR_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}      # name -> (Kr, Kb)
 ColourTable = collections.namedtuple("ColourTable", "m off lo hi k")     # m: 3 x 3 ints, off / lo / hi: 3 ints, k: fraction bits
@@ -543,7 +622,7 @@ class EncoderPipe(_Handover):
     _side = "enc"
 
     def __init__(self, plan: Plan = None, params=None, device=0, depth=4, container=16, host_threads=0, pixels=None, packed=None, max_bytes=None,
-                 max_sse=None, min_psnr=None, video=None, cap_bytes=0, colour=None, **kw):
+                 max_sse=None, min_psnr=None, video=None, cap_bytes=0, colour=None, chroma=None, **kw):
         """pixels=(bits, big_endian): the frames are handed over pixel-interleaved ([H,W,C] of 8- or 16-bit samples, the
         order of .ppm files / capture buffers; 16-bit samples byte-swapped when big_endian) and turned into planes on
         the device.  video="uyvy" | "yuy2" | "v210" | "y210" | "y212" | "y216": the frames are handed over as one 4:2:2 video
@@ -552,7 +631,9 @@ class EncoderPipe(_Handover):
         "r210" | "r10k" | "y412" | "y416" | "ayuv" | "bgra" | "rgba" | "argb": as one 4:4:4 packed buffer (uint8 [H, row_bytes],
         pack_video444's layout).  colour="bt601" | "bt709" | "bt2020" or a Colour, with one of the RGB names among them ("bgra" |
         "rgba" | "argb" | "r210" | "r10k"): the buffer holds R, G, B and is coded as the plan's Y, Cb, Cr -- 4:4:4, 4:2:2 or 4:2:0
-        -- converted on the device (set_video_colour).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
+        -- converted on the device (set_video_colour).  chroma="cosited", with any other video name: the buffer's chroma format
+        need not be the plan's (v210 into a 4:2:0 plan, nv12 into a 4:2:2 one, ...): halved or doubled on the device
+        (set_video_chroma).  max_bytes: every frame is coded to that byte budget (set_budget); max_sse / min_psnr: ... to that
         quality target (set_quality) -- one or the other; cap_bytes=N with a target: to the target, but never above N bytes
         (set_quality(..., cap_bytes=N); from the start, or never)"""
         from .codec import _torch
@@ -572,8 +653,12 @@ class EncoderPipe(_Handover):
             self.set_packed(packed)
         if colour is not None and video is None:
             raise ValueError("colour= goes with video= (an RGB format)")
+        if chroma is not None and (video is None or colour is not None):
+            raise ValueError("chroma= goes with video= (a Y, Cb, Cr format), not with colour=")
         if colour is not None:
             self.set_video_colour(video, colour)
+        elif chroma is not None:
+            self.set_video_chroma(video, chroma)
         elif video is not None:
             self.set_video(video)
         if max_bytes:
@@ -733,7 +818,7 @@ class DecoderPipe(_Handover):
     _side = "dec"
 
     def __init__(self, first_codestream: bytes, device=0, depth=4, container=16, host_threads=0, resilient=False, pixels=None, packed=None,
-                 skip_res=None, region=None, video=None, colour=None):
+                 skip_res=None, region=None, video=None, colour=None, chroma=None):
         """pixels=(bits, big_endian): decoded frames come back pixel-interleaved ([H,W,C]), clamped to the bit depth.
         skip_res=n or (for_data, for_recon), region=(x0, y0, w, h): the pipe decodes that view of every frame, as
         video="uyvy" | ...: they come back as one 4:2:2 video buffer (uint8 [H, row_bytes], pack_video of the planes);
@@ -741,6 +826,8 @@ class DecoderPipe(_Handover):
         video="v410" | "bgra" | ...: as one 4:4:4 packed buffer (uint8 [H, row_bytes], pack_video444 of them).
         colour="bt709" | ... or a Colour, with video="bgra" | "rgba" | "argb" | "r210" | "r10k": the decoded Y, Cb, Cr planes (4:4:4,
         4:2:2 or 4:2:0) come back as that RGB buffer, converted on the device (set_video_colour).
+        chroma="cosited", with any other video name: the buffer's chroma format need not be the codestream's (a 4:2:0 feed out as
+        uyvy, a 4:4:4 master as nv12, ...): halved or doubled on the device (set_video_chroma).
         codec.Decoder takes them (ojphgpu_dec_pipe_create_view); .plan, the frames and pixels / packed are the view's"""
         from .codec import _torch
         _torch()
@@ -763,8 +850,12 @@ class DecoderPipe(_Handover):
             self.set_packed(packed)
         if colour is not None and video is None:
             raise ValueError("colour= goes with video= (an RGB format)")
+        if chroma is not None and (video is None or colour is not None):
+            raise ValueError("chroma= goes with video= (a Y, Cb, Cr format), not with colour=")
         if colour is not None:
             self.set_video_colour(video, colour)
+        elif chroma is not None:
+            self.set_video_chroma(video, chroma)
         elif video is not None:
             self.set_video(video)
         self.in_flight = 0

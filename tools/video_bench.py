@@ -20,6 +20,11 @@ from 4:2:2 and 4:2:0) beside ojphgpu_frame_resample (the same taps: a 4:4:4 int3
 ojphgpu_unpack_video444 (r210 into 16-bit containers) on the same frame in the same rounds, and runs EncoderPipe(video="r210",
 colour="bt709") against EncoderPipe(video="v410") on the same 4:4:4 10-bit plan; its default --out is profiles/colour_bench.txt.
 
+--chroma measures the stage of kernels_chroma.hip instead (ojphgpu_frame_rechroma, 16-bit containers: 4:2:2 -> 4:2:0, 4:2:0 ->
+4:2:2, 4:4:4 -> 4:2:2, 4:2:2 -> 4:4:4) beside ojphgpu_frame_resample and the two colour stages with the same factors on the same
+frame in the same rounds, and runs EncoderPipe(video="v210", chroma="cosited") on a 4:2:0 plan against EncoderPipe(video="v210") on
+a 4:2:2 plan; its default --out is profiles/chroma_bench.txt.
+
 1. Every instantiation of ojphgpu_unpack_video / _pack_video (format x container), bytes read plus written per second, beside
    the yardstick: ojphgpu_unpack_pixels / _pack_pixels with 3 components, 16-bit samples into 16-bit containers, on the same
    number of pixels -- the same kind of copy.  All of them alternate inside every round; a kernel runs `reps` launches per
@@ -188,6 +193,91 @@ def kernel_rates_colour(torch, rounds, reps, emit):
                      "us_per_launch": round(work[name][1] / med / 1e3, 2)}
         emit("  %-46s %s  median %6.3f TB/s  spread %4.1f %%  %5.1f MB, %6.1f us per launch" %
              (name, " ".join("%6.3f" % (x / 1e3) for x in v), med / 1e3, spread * 100, work[name][1] / 1e6, out[name]["us_per_launch"]))
+    return out
+
+
+def kernel_rates_chroma(torch, rounds, reps, emit):
+    """the chroma stage between 4:4:4, 4:2:2 and 4:2:0 in 16-bit containers, the resample stage and both colour stages with the
+    same factors, alternating inside every round; launches go straight to the C ABI, nothing waits between them"""
+    import ctypes as C
+    from openjph_amd import capi, codec
+    from openjph_amd.pipeline import colour_table
+    L, st = capi.lib(), codec._stream_ptr(torch, 0)
+    work = {}
+
+    def c_table(t):
+        ct = capi.ColourTable()
+        for c in range(3):
+            for i in range(3):
+                ct.m[c][i] = t.m[c][i]
+            ct.off[c], ct.lo[c], ct.hi[c] = t.off[c], t.lo[c], t.hi[c]
+        ct.k = t.k
+        return ct
+    fwd, inv = c_table(colour_table("bt709", "forward", DEPTH, DEPTH)), c_table(colour_table("bt709", "inverse", DEPTH, DEPTH))
+    a16 = [torch.randint(0, 1 << DEPTH, (3 * W * H,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(NSETS)]
+    b16 = [torch.randint(0, 1 << DEPTH, (3 * W * H,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(NSETS)]
+    src32 = [torch.randint(0, 1 << DEPTH, (3 * W * H,), dtype=torch.int32, device="cuda") for _ in range(NSETS)]
+    size = lambda c: ((W + c[0] - 1) // c[0]) * ((H + c[1] - 1) // c[1])
+    for name, s, d in (("4:2:2 -> 4:2:0", (2, 1), (2, 2)), ("4:2:0 -> 4:2:2", (2, 2), (2, 1)), ("4:4:4 -> 4:2:2", (1, 1), (2, 1)), ("4:2:2 -> 4:4:4", (2, 1), (1, 1))):
+        f = capi.ChromaFrame(W, H, s[0], s[1], d[0], d[1])
+        f.src_off[:] = [0, W * H, W * H + size(s)]
+        f.dst_off[:] = [0, W * H, W * H + size(d)]
+        work["rechroma 16 %s" % name] = (lambda i, f=f: codec.check(L.ojphgpu_frame_rechroma(st, C.c_void_p(a16[i].data_ptr()), C.c_void_p(b16[i].data_ptr()), 16, C.byref(f)), "frame_rechroma"),
+                                         (2 * W * H + 2 * size(s) + 2 * size(d)) * 2)
+    for name, fx, fy in (("across", 2, 1), ("down", 1, 2)):   # the factors of the four above: chroma halved / doubled in one direction
+        cw, ch = (W + fx - 1) // fx, (H + fy - 1) // fy
+        f = capi.ColourFrame(W, H, fx, fy)
+        f.rgb_first[:] = [0, W * H, 2 * W * H]
+        f.ycc_first[:] = [0, W * H, W * H + cw * ch]
+        moved = (3 * W * H + W * H + 2 * cw * ch) * 2
+        work["rgb_to_ycc 16 -> 16 halved %s" % name] = (lambda i, f=f: codec.check(L.ojphgpu_frame_rgb_to_ycc(st, C.c_void_p(a16[i].data_ptr()), 16, C.c_void_p(b16[i].data_ptr()), 16, C.byref(f), C.byref(fwd)), "rgb_to_ycc"), moved)
+        work["ycc_to_rgb 16 -> 16 doubled %s" % name] = (lambda i, f=f: codec.check(L.ojphgpu_frame_ycc_to_rgb(st, C.c_void_p(b16[i].data_ptr()), 16, C.c_void_p(a16[i].data_ptr()), 16, C.byref(f), C.byref(inv)), "ycc_to_rgb"), moved)
+        comps = np.zeros(3, codec.resample_comp_dtype)
+        at = 0
+        for c, (gx, gy) in enumerate(((1, 1), (fx, fy), (fx, fy))):
+            dw, dh = (W + gx - 1) // gx, (H + gy - 1) // gy
+            comps[c] = (c * W * H, at, W, H, dw, dh, gx, gy, 0, 0, 0, 0, (1 << DEPTH) - 1, 0)
+            at += dw * dh
+        d_comps = codec.to_device(comps, 0)
+        work["frame_resample 32 -> 16 halved %s" % name] = (lambda i, d=d_comps: codec.check(L.ojphgpu_frame_resample(st, C.c_void_p(src32[i].data_ptr()), C.c_void_p(b16[i].data_ptr()), 16, C.c_void_p(d.data_ptr()), 3), "frame_resample"),
+                                                            3 * W * H * 4 + at * 2)
+    rates = timed_rounds(torch, work, rounds, reps)
+    emit("1. kernels, %d x %d, TB/s read + written; %d rounds of %d launches" % (W, H, rounds, reps))
+    out = {}
+    for name, v in rates.items():
+        med, spread = median_spread(v)
+        out[name] = {"GBps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "bytes": work[name][1],
+                     "us_per_launch": round(work[name][1] / med / 1e3, 2)}
+        emit("  %-46s %s  median %6.3f TB/s  spread %4.1f %%  %5.1f MB, %6.1f us per launch" %
+             (name, " ".join("%6.3f" % (x / 1e3) for x in v), med / 1e3, spread * 100, work[name][1] / 1e6, out[name]["us_per_launch"]))
+    return out
+
+
+def pipe_rates_chroma(rounds, frames, depth, emit):
+    """EncoderPipe fed one v210 buffer two ways, alternating rounds: chroma="cosited" on the 8K 10-bit 4:2:0 plan (unpack + the stage
+    that halves chroma down) against the plain video="v210" pipe on the 4:2:2 plan (unpack alone; it codes half as many chroma
+    samples more)"""
+    from openjph_amd.pipeline import EncoderPipe, pack_video
+    from openjph_amd.plan import Plan, make_params
+    frame = pack_video(workload_planes(), "v210", DEPTH)
+    mk = lambda fy: Plan(make_params(W, H, 3, bit_depth=DEPTH, reversible=False, downsampling=[(1, 1), (2, fy), (2, fy)]))
+    pipes = {"v210 -> 4:2:0 (chroma)": EncoderPipe(plan=mk(2), depth=depth, container=16, video="v210", chroma="cosited"),
+             "v210 -> 4:2:2 (plain)": EncoderPipe(plan=mk(1), depth=depth, container=16, video="v210")}
+    first = {way: fill_and_drain(p, frame) for way, p in pipes.items()}
+    fps = {way: [] for way in pipes}
+    for _ in range(rounds):
+        for way, p in pipes.items():
+            fps[way].append(frames / steady(p, frames))
+    for p in pipes.values():
+        p.close()
+    out = {}
+    emit("2. EncoderPipe, %d x %d %d-bit 9/7, one v210 buffer per frame, depth %d, %d frames per round, codestreams %s bytes" %
+         (W, H, DEPTH, depth, frames, " / ".join(str(len(first[w])) for w in pipes)))
+    for way, v in fps.items():
+        med, spread = median_spread(v)
+        out[way] = {"fps": [round(x, 1) for x in v], "median": round(med, 1), "spread": round(spread, 4), "ms_per_frame": round(1e3 / med, 3)}
+        emit("  %-23s frames/s per round %s  median %7.1f  spread %4.1f %%  %6.3f ms per frame" %
+             (way, " ".join("%7.1f" % x for x in v), med, spread * 100, 1e3 / med))
     return out
 
 
@@ -398,12 +488,13 @@ def main():
     ap.add_argument("--v420", action="store_true", help="the 4:2:0 kernels and a p010 pipe beside the yardstick and their 4:2:2 peers")
     ap.add_argument("--v444", action="store_true", help="the 4:4:4 kernels and a v410 pipe beside the yardstick, the P010 kernels, planes and packed=10")
     ap.add_argument("--colour", action="store_true", help="the RGB <-> YCbCr stages beside the resample stage and the r210 unpack; an r210 + colour pipe against a v410 pipe")
+    ap.add_argument("--chroma", action="store_true", help="the chroma stage beside the resample stage and the colour stages of the same factors; a v210 + chroma pipe on a 4:2:0 plan against the plain v210 pipe")
     ap.add_argument("--frame", default=None, metavar="WxH", help="another frame size for the kernels (the pipes are then left out): what a rate owes to the bytes of a launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                "colour_bench.txt" if args.colour else "video444_bench.txt" if args.v444 else "video420_bench.txt" if args.v420 else "video_bench.txt")
+                                "chroma_bench.txt" if args.chroma else "colour_bench.txt" if args.colour else "video444_bench.txt" if args.v444 else "video420_bench.txt" if args.v420 else "video_bench.txt")
     global W, H
     if args.frame:
         W, H = (int(v) for v in args.frame.lower().split("x"))
@@ -416,14 +507,14 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --colour" if args.colour else " --v444" if args.v444 else " --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
+    emit("tools/video_bench.py%s%s --rounds %d --reps %d --frames %d --depth %d on %s" % (" --chroma" if args.chroma else " --colour" if args.colour else " --v444" if args.v444 else " --v420" if args.v420 else "", " --frame " + args.frame if args.frame else "", args.rounds, args.reps, args.frames,
                                                                                      args.depth, torch.cuda.get_device_name(0)))
-    kernels = kernel_rates_colour(torch, args.rounds, args.reps, emit) if args.colour else kernel_rates_444(torch, args.rounds, args.reps, emit) if args.v444 else kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
+    kernels = kernel_rates_chroma(torch, args.rounds, args.reps, emit) if args.chroma else kernel_rates_colour(torch, args.rounds, args.reps, emit) if args.colour else kernel_rates_444(torch, args.rounds, args.reps, emit) if args.v444 else kernel_rates(torch, args.rounds, args.reps, emit, args.v420)
     torch.cuda.empty_cache()
     if args.frame:
         pipes = {}
     else:
-        pipes = pipe_rates_colour(args.rounds, args.frames, args.depth, emit) if args.colour else pipe_rates_444(args.rounds, args.frames, args.depth, emit) if args.v444 else pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420)
+        pipes = pipe_rates_chroma(args.rounds, args.frames, args.depth, emit) if args.chroma else pipe_rates_colour(args.rounds, args.frames, args.depth, emit) if args.colour else pipe_rates_444(args.rounds, args.frames, args.depth, emit) if args.v444 else pipe_rates(args.rounds, args.frames, args.depth, emit, args.v420)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print(json.dumps({"kernels": kernels, "pipes": pipes}))
