@@ -309,6 +309,14 @@ public:
   // after such a flush(): the step it chose (its index in the grid and its value), the codestream's length and the number
   // of block-coder runs the search made; false when there was none
   bool get_byte_budget_result(ui32& grid_index, float& qstep, ui64& bytes, ui32& passes);
+  // GPU-side addition: flush() codes a REVERSIBLE frame under a byte cap (include/ojphgpu.h section 5f): lossless, byte
+  // for byte the plain codestream, where that is at most max_bytes long; else at the first level of the truncation ladder
+  // that fits -- sub-bands drop low bit-planes, every 5/3 decoder reads the result.  Call it before write_headers; 0
+  // switches it off.  Reversible Part-1 coding of every component with one number of decompositions, one frame on one
+  // device: anything else is reported by write_headers, a cap below the last level's codestream by flush().
+  void set_truncation_budget(size_t max_bytes);
+  // after such a flush(): the level it chose (0: lossless), the codestream's length and the block-coder runs the search made
+  bool get_truncation_result(ui32& level, ui64& bytes, ui32& passes);
   // GPU-side addition: flush() codes the frame to a quality target (include/ojphgpu.h section 5c: the coarsest base step of
   // that grid found whose decoded frame differs from the frame by a squared error, summed over all components, of at most
   // max_sse; 0 is a target).  Call it before write_headers; clear_max_sse switches it off.  Where set_byte_budget applies,

@@ -400,7 +400,11 @@ typedef struct ojphgpu_cb_desc {     /* one code-block */
   uint16_t w, h;
   uint8_t  K_max, reversible, missing_msbs, num_passes;   /* last two: decode only; reversible bit 1
                                         (decode): vertically causal code-block style; bit 2: the block is on the
-                                        64-bit sample path (int64 samples at coef_off, the 64-bit block coder) */
+                                        64-bit sample path (int64 samples at coef_off, the 64-bit block coder);
+                                        bit 3 (encode, 32-bit reversible blocks only): code the block at
+                                        p = 30 - missing_msbs, i.e. without its K_max - 1 - missing_msbs lowest
+                                        magnitude planes (section 5f); without the bit missing_msbs is not read
+                                        on encode */
   float    delta;                    /* irreversible: encode uses 1/delta, decode uses delta */
   uint32_t len1, len2;               /* decode: pass lengths */
   uint64_t data_off;                 /* decode: byte offset of the coded bytes in `d_data`;
@@ -438,8 +442,13 @@ int ojphgpu_ht_encode(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
  *   bit 4 (16)   NO block of 33..64 columns occurs: the blocks of bit 0 take the layout of 8 quad pairs by 8 quad rows
  *   bit 5 (32)   blocks on the 64-bit sample path occur (cb_desc.reversible bit 2; bits 0..4 and 6 say nothing of them)
  *   bit 6 (64)   NO block of more than 128 columns occurs: the blocks of bit 1 take the narrow kernel, 32 pairs by 2 rows
+ *   bit 7 (128)  reversible blocks that drop low bit-planes occur (cb_desc.reversible bit 3): instantiations of their own,
+ *                launched behind the others in the layouts bits 0, 1, 4 and 6 name (such a block says nothing of bit 2).  A
+ *                caller that does not know CANNOT coarsen this one in: without bit 7 no kernel owns a flagged block.
  * ojphgpu_ht_encode_kinds: host only -- the truthful widths of h_blocks[0 .. n), the statement the encoder objects use too
  *   (a descriptor without samples, w or h 0, counts with its w and reversible like any other: a kernel must report it).
+ *   It is also where flagged descriptors are validated: one with missing_msbs >= K_max, on the 64-bit path (bit 2) or
+ *   irreversible is OJPHGPU_E_INVALID -- a caller launches nothing then.
  * A caller may know LESS than ojphgpu_ht_encode_kinds says, never more.  The valid coarsenings of a truthful value, in any
  * combination:
  *   - clear bit 4: the blocks of at most 32 columns take the 16-pairs-by-4-rows layout of the 64-column blocks;
@@ -451,8 +460,9 @@ int ojphgpu_ht_encode(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
  * block present: the 8-by-8 layout takes blocks of at most 32 columns only) and that block's result is NEVER WRITTEN -- no
  * error is reported, d_results keeps what the caller left there.
  * ojphgpu_ht_encode_launches: host only, no HIP call -- what ojphgpu_ht_encode_ex launches for n blocks under `widths`, in
- *   issue order; it takes its launches from the same table.  *count launches (at most 5), five values each in `out`:
- *   [0] 0 = ht_encode_kernel<REV, LOGP>, 1 = ht_encode_wide_kernel<S64>; [1] REV, or S64; [2] LOGP (3: 8 pairs by 8 quad
+ *   issue order; it takes its launches from the same table.  *count launches (at most 7; 5 without bit 7), five values each in `out`:
+ *   [0] 0 = ht_encode_kernel<REV, LOGP>, 1 = ht_encode_wide_kernel<S64>; [1] REV, or S64 (+ 2: the instantiation of the
+ *   blocks that drop bit-planes -- 3 narrow, 2 wide); [2] LOGP (3: 8 pairs by 8 quad
  *   rows, 4: 16 by 4, 5: 32 by 2; 0 for the wide kernel); [3] workgroups; [4] blocks (wavefronts) per workgroup.  `cap` =
  *   the launches `out` has room for; E_INVALID (with *count set) where cap < *count. */
 int ojphgpu_ht_encode_ex(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n,
@@ -610,6 +620,11 @@ int ojphgpu_convert_inverse16(void* stream, const ojphgpu_params* params,
 typedef struct ojphgpu_stats_desc { uint64_t plane_off; uint32_t pitch, w, h, slot; } ojphgpu_stats_desc;
 int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
                        const void* d_coef, uint32_t* d_hist);
+/* The integer form (section 5f builds on it): the same pass over planes of int32 coefficients (the reversible path), the
+ * same kernel with another counting function.  bin = the bit length of |v| -- 0 for 0, 1 for +-1, 31 for INT_MAX, 32 for
+ * INT_MIN; bins 33 .. 79 of a slot stay zero.  Descriptors, slots, exact uint32 counts and the limits are those above. */
+int ojphgpu_band_stats_int(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
+                           const void* d_coef, uint32_t* d_hist);
 
 /* The two passes of a trial of the quality search (section 5c builds on them; kernels_quality.hip).
  *
@@ -967,6 +982,71 @@ int  ojphgpu_encoder_rate_rounds(ojphgpu_encoder* enc, uint32_t* rounds);
  * device and the copies of the block lengths, [2] the download and Tier-2 of j*; out[3] the band statistics kernel of the
  * run before it (device events; needs ojphgpu_encoder_set_timing's per-launch spans, the default) */
 int  ojphgpu_encoder_rate_timing(ojphgpu_encoder* enc, float out[4]);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 5f. A reversible frame under a byte cap: lossless where the frame fits, the nearest thing to it where it does not, in a
+ *    codestream every 5/3 decoder reads.  Section 5b refuses reversible components -- there is no step to search.  What is
+ *    searched here is how many of its lowest magnitude bit-planes each sub-band drops: a block of band b that drops t_b
+ *    planes is coded at p = 30 - missing_msbs with missing_msbs = K_max(b) - 1 - t_b, the packet header says so, and a
+ *    decoder puts the half bit below the kept planes (the reference's decoder reads such blocks; its encoder never writes
+ *    them).  QCD / SIZ / COD are those of the plain encode.
+ *
+ *    The ladder.  A TABLE gives every band of the plan its t_b, 0 <= t_b <= K_max(b) - 1; a LEVEL j = 0 .. J - 1 names one:
+ *      w_b    = log2(g_h g_v g_c), g_h / g_v the L2 norms of the 1-D 5/3 synthesis basis vector of the band's branch (low
+ *               or high) at its decomposition depth -- a unit impulse taken through the linear inverse lifting, in double,
+ *               away from the borders -- and g_c the L2 norm of the component's column of the inverse colour transform:
+ *               with the RCT sqrt(3) for component 0, sqrt(11/16) for components 1 and 2, else 1;
+ *      q_b    = floor(4 (w_b - min_b w_b) + 0.5), quarter planes;
+ *      t_b(j) = clamp(floor((j + 3 - q_b) / 4), 0, K_max(b) - 1);      J = max_b(4 (K_max(b) - 1) + q_b) - 3 + 1.
+ *    Level 0 is lossless and byte for byte the plain encode, level 1 drops one plane of the band(s) of lowest weight, level
+ *    J - 1 leaves every band its top plane only.  Neighbouring levels may share a table (and then a size).  A block none of
+ *    whose samples reaches 2^t_b is not coded (length 0).  size(j) = the length, SOC to EOC, of the codestream at level j.
+ *    A capped encode with max_bytes = B returns the level j* with size(j*) <= B and (j* == 0 or size(j* - 1) > B), both
+ *    measured; size(J - 1) > B: OJPHGPU_E_BUDGET.  Whole planes are coarse: neighbouring distinct sizes differ by tens of
+ *    per cent, not by the 1-2 % of the grid of section 5b.
+ *    Plans: reversible Part-1 5/3 in every component (COC included) with one number of decompositions, no ATK / DFS, no
+ *    component on the 64-bit sample path; anything else is OJPHGPU_E_INVALID from every call of this section.
+ * ------------------------------------------------------------------------------------------ */
+int  ojphgpu_plan_trunc_levels(const ojphgpu_plan* plan, uint32_t* levels);           /* J */
+int  ojphgpu_plan_trunc_weights(const ojphgpu_plan* plan, int32_t* q);                /* q[bands of the plan] */
+int  ojphgpu_plan_trunc_table(const ojphgpu_plan* plan, uint32_t j, uint8_t* t);      /* t[bands]; j >= J: OJPHGPU_E_INVALID */
+typedef struct ojphgpu_trunc_info {
+  uint32_t level;                                        /* j*                                                  */
+  uint32_t passes, first_guess;                          /* calls of size_fn; the level of the second of them -- the
+                                                            model's guess -- or 0 when level 0 was the only one  */
+  uint32_t max_dropped;                                  /* the largest t_b of level j*                         */
+  uint32_t lossless;                                     /* j* == 0: the codestream is the plain encode's       */
+  uint32_t reserved;
+  uint64_t bytes, bytes_finer;                           /* size(j*); size(j* - 1), 0 when j* == 0              */
+} ojphgpu_trunc_info;
+/* The search, host only: hist = the integer band statistics of the frame (ojphgpu_band_stats_int), [bands of the plan]
+ * [OJPHGPU_STATS_BINS] in band order, or NULL.  fn(user, j) = size(j).  Levels that share a table are one measurement:
+ * only the first level of such a run is ever asked, and j* is one of those.  The first trial is level 0: the frame that
+ * fits -- what the mode is for -- takes one pass.  With hist a model (a coefficient of bit length L > t_b costs about
+ * L - t_b + 3 bits, the constants of section 5b's model, rescaled by observed / predicted after every trial, the first of
+ * them included) leads the second trial.  Then the interval between a level measured not to fit and one measured to fit is
+ * halved.  Correctness never rests on the
+ * model or on fn being monotone: the certificate is two measurements.  passes <= 2 + ceil(log2 J) for every fn.
+ * OJPHGPU_E_BUDGET (info: passes, first_guess) when the last level does not fit; a negative value of fn as it is. */
+int  ojphgpu_trunc_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
+                          ojphgpu_trunc_info* info);
+/* max_bytes > 0: the encoder codes every following frame under that cap; 0 switches the mode off.  ojphgpu_encoder_run_device*
+ * then enqueues conversion, DWT and the integer band statistics; ojphgpu_encoder_finish runs the search -- per trial the
+ * table goes into the block descriptors, the block coder runs, the block lengths come to the host and the Tier-2 layout
+ * gives size(j) -- and writes the codestream of j*.  OJPHGPU_E_BUDGET leaves the encoder usable.  The scratch slots and
+ * the output of the plain plan hold every level.  _set_trunc_level: a fixed level instead (no search, no statistics);
+ * j < 0 switches it off, j >= J is OJPHGPU_E_INVALID.  The two replace each other.  Tiled frames: the cap is the whole
+ * codestream's.  OJPHGPU_E_INVALID, encoder unchanged: a plan this section refuses (above); a batch encoder; an encoder of
+ * a tile range that does not cover the frame; together with ojphgpu_encoder_set_budget(s) / _set_quality*.  In this mode
+ * ojphgpu_encoder_finish_tiles* are refused.  _trunc_info: what the last finish found (a fixed level: that level, passes 1,
+ * bytes_finer 0); OJPHGPU_E_INVALID before the first finish of the mode. */
+int  ojphgpu_encoder_set_truncation(ojphgpu_encoder* enc, uint64_t max_bytes);
+int  ojphgpu_encoder_set_trunc_level(ojphgpu_encoder* enc, int32_t j);
+int  ojphgpu_encoder_trunc_info(ojphgpu_encoder* enc, ojphgpu_trunc_info* info);
+/* after such a finish, ms: out[0] host clock of the coding inside it (every trial, and j* once more when the last trial was
+ * another level); out[1] the integer statistics kernel of the run before it (device events; needs
+ * ojphgpu_encoder_set_timing's per-launch spans), 0 at a fixed level */
+int  ojphgpu_encoder_trunc_timing(ojphgpu_encoder* enc, float out[2]);
 
 /* ------------------------------------------------------------------------------------------ *
  * 5c. Encoding to a quality target: the other half of rate control.  Over the grid of section 5b, SSE(j) = the sum, over

@@ -11,7 +11,7 @@
 #include "../../include/ojph_gpu_codestream.h"
 
 static void usage() {
-  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n | -min_psnr dB [-cap_bytes n]]\n"
+  printf("ojph_compress (GPU path) -i in.{pgm,ppm,yuv,raw} -o out.j2c [-reversible true|false] [-qstep f | -qfactor 1..100 | -max_bytes n | -min_psnr dB [-cap_bytes n] | -truncate_to n]\n"
          "  [-num_decomps n] [-block_size {w,h}] [-precincts {w,h}] [-prog_order LRCP|RLCP|RPCL|PCRL|CPRL]\n"
          "  [-colour_trans true|false] [-tile_size {w,h}] [-tlm_marker true|false] [-device n | -devices n,n,...]\n"
          "  [-image_offset {x,y}] [-tile_offset {x,y}] [-tileparts R|C|RC] [-profile IMF|BROADCAST] [-com \"text\"]\n"
@@ -106,6 +106,13 @@ int main(int argc, char** argv) {
       if (mb <= 0) throw std::runtime_error("-max_bytes must be a positive number of bytes");
       cs.set_byte_budget((size_t)mb);
     }
+    if (a.get("-truncate_to")) {                                // GPU path only: lossless where it fits, else the first truncation level that does
+      if (!reversible) throw std::runtime_error("-truncate_to needs reversible coding (-reversible true); an irreversible byte budget is -max_bytes");
+      if (a.get("-devices")) throw std::runtime_error("-truncate_to codes on one device: it cannot be used together with -devices");
+      const long long tb = atoll(a.get("-truncate_to"));
+      if (tb <= 0) throw std::runtime_error("-truncate_to must be a positive number of bytes");
+      cs.set_truncation_budget((size_t)tb);
+    }
     unsigned long long max_sse = 0;
     if (a.get("-cap_bytes") && !a.get("-min_psnr")) throw std::runtime_error("-cap_bytes caps a quality target: it needs -min_psnr (a byte budget alone is -max_bytes)");
     if (a.get("-min_psnr")) {                                   // GPU path only: the coarsest step of the rate grid found to reach the PSNR
@@ -156,6 +163,11 @@ int main(int argc, char** argv) {
       ojph::ui32 gi = 0, passes = 0; float q = 0; ojph::ui64 nbytes = 0;
       if (a.get("-max_bytes") && cs.get_byte_budget_result(gi, q, nbytes, passes))
         printf("Byte budget %s: qstep = %.9g (grid index %u), %llu bytes, %u passes\n", a.get("-max_bytes"), (double)q, gi, (unsigned long long)nbytes, passes);
+    }
+    {
+      ojph::ui32 level = 0, passes = 0; ojph::ui64 nbytes = 0;
+      if (a.get("-truncate_to") && cs.get_truncation_result(level, nbytes, passes))
+        printf("Truncation budget %s: level %u%s, %llu bytes, %u passes\n", a.get("-truncate_to"), level, level ? "" : " (lossless)", (unsigned long long)nbytes, passes);
     }
     {
       ojph::ui32 gi = 0, passes = 0, pae = 0; float q = 0; ojph::ui64 nbytes = 0, sse = 0, coarser = 0;

@@ -155,6 +155,11 @@ class RateInfo(C.Structure):              # ojphgpu_rate_info
 SIZE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint32)      # ojphgpu_size_fn
 
 
+class TruncInfo(C.Structure):             # ojphgpu_trunc_info
+    _fields_ = [("level", C.c_uint32), ("passes", C.c_uint32), ("first_guess", C.c_uint32), ("max_dropped", C.c_uint32),
+                ("lossless", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("bytes_finer", C.c_uint64)]
+
+
 class RequantDesc(C.Structure):           # ojphgpu_requant_desc
     _fields_ = [("plane_off", C.c_uint64), ("pitch", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("delta_inv", C.c_float),
                 ("delta", C.c_float), ("K_max", C.c_uint32)]
@@ -411,6 +416,15 @@ SIGNATURES = {
     "ojphgpu_unpack_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "ojphgpu_pack_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "ojphgpu_band_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ojphgpu_band_stats_int": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ojphgpu_plan_trunc_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ojphgpu_plan_trunc_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ojphgpu_plan_trunc_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ojphgpu_trunc_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, SIZE_FN, C.c_void_p, C.POINTER(TruncInfo)]),
+    "ojphgpu_encoder_set_truncation": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ojphgpu_encoder_set_trunc_level": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ojphgpu_encoder_trunc_info": (C.c_int, [C.c_void_p, C.POINTER(TruncInfo)]),
+    "ojphgpu_encoder_trunc_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "ojphgpu_rate_grid_qstep": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
     "ojphgpu_rate_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_rate_search_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),
@@ -550,7 +564,7 @@ class OjphError(RuntimeError):
                  E_OVERFLOW: "output buffer too small", E_BLOCK: "error decoding a codeblock",
                  E_AGAIN: "no free pipeline slot",
                  E_UNCOLLECTED: "the previous run of this decoder asked for a repeat and was never collected",
-                 E_BUDGET: "the byte budget is below the codestream of the coarsest quantisation step",
+                 E_BUDGET: "the byte budget is below the codestream of the coarsest quantisation step / the last truncation level",
                  E_QUALITY: "the quality target is beyond the finest quantisation step"}
         super().__init__("ojph error: %s (%d) %s" % (names.get(code, "?"), code, what))
         self.code = code

@@ -43,13 +43,15 @@ class Encoder:
     """Whole-frame encoder for one frame shape / parameter set (ojphgpu_encoder)."""
 
     def __init__(self, params: Params = None, device=0, plan: Plan = None, tiles=None, frames=1, max_bytes=0, max_sse=None, min_psnr=None,
-                 budgets=None, cap_bytes=0, **kw):
+                 budgets=None, cap_bytes=0, truncate_to=0, truncate_level=None, **kw):
         """tiles=(first, count) restricts the encoder to a run of tiles (multi-GPU sharding);
         frames=B makes it code a batch of B independent frames per run ([B,C,H,W] input);
         max_bytes=N codes every frame to a byte budget (set_budget);
         budgets=[N0, N1, ...] codes frame f of every batch to N_f bytes (set_budgets);
         max_sse=N / min_psnr=dB codes every frame to a quality target (set_quality);
-        cap_bytes=N with one of those two: to the target, but never above N bytes (set_quality(..., cap_bytes=N))."""
+        cap_bytes=N with one of those two: to the target, but never above N bytes (set_quality(..., cap_bytes=N));
+        truncate_to=N codes every reversible frame under a byte cap (set_truncation), truncate_level=j at a fixed level of
+        the truncation ladder (set_trunc_level)."""
         torch = _torch()
         if cap_bytes and max_sse is None and min_psnr is None:
             raise ValueError("cap_bytes needs a quality target (max_sse or min_psnr); a byte budget alone is max_bytes")
@@ -75,8 +77,13 @@ class Encoder:
         self.max_sse = None
         self.cap_bytes = 0
         self._frame = None
+        self.truncating = False
         if max_bytes:
             self.set_budget(max_bytes)
+        if truncate_to:
+            self.set_truncation(truncate_to)
+        if truncate_level is not None:
+            self.set_trunc_level(truncate_level)
         if budgets is not None:
             self.set_budgets(budgets)
         if max_sse is not None or min_psnr is not None:
@@ -91,6 +98,40 @@ class Encoder:
             check(self._lib.ojphgpu_encoder_set_budget(self._h, int(max_bytes)), "encoder_set_budget")
         self.max_bytes = int(max_bytes)
         self.budgets = None
+
+    def set_truncation(self, max_bytes):
+        """Every following frame of a reversible encoder is coded under a byte cap (include/ojphgpu.h section 5f): lossless,
+        byte for byte the plain encode, where that fits max_bytes; else at the first level of the truncation ladder
+        (plan.trunc_table) whose codestream fits -- its sub-bands drop low bit-planes, any 5/3 decoder reads it.  0 switches
+        the mode off.  A cap not even the last level fits raises OjphError with code E_BUDGET from finish() / encode()."""
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_encoder_set_truncation(self._h, int(max_bytes)), "encoder_set_truncation")
+        self.truncating = int(max_bytes) > 0
+
+    def set_trunc_level(self, j):
+        """Every following frame is coded at level j of the truncation ladder (0: lossless): no search, no statistics.
+        None or a negative j switches the mode off."""
+        j = -1 if j is None else int(j)
+        if not -2 ** 31 <= j < 2 ** 31:
+            check(capi.E_INVALID, "encoder_set_trunc_level")
+        with _torch().cuda.device(self.device):
+            check(self._lib.ojphgpu_encoder_set_trunc_level(self._h, j), "encoder_set_trunc_level")
+        self.truncating = j >= 0
+
+    def trunc_info(self):
+        """what the last finish() of a truncating encoder found: dict(level, passes = block-coder runs the search measured,
+        first_guess, max_dropped = the most planes a band drops, lossless, bytes, bytes_finer = the length one level finer, 0
+        at level 0); after E_BUDGET: passes and first_guess"""
+        info = capi.TruncInfo()
+        check(self._lib.ojphgpu_encoder_trunc_info(self._h, C.byref(info)), "encoder_trunc_info")
+        return {k: int(getattr(info, k)) for k, _ in capi.TruncInfo._fields_ if k != "reserved"}
+
+    def trunc_timing(self):
+        """of the last finish() of a truncating encoder, ms: dict(search_ms = host clock of the coding inside it, stats_ms = the
+        integer statistics kernel of the run before it (device events; 0 at a fixed level))"""
+        t = (C.c_float * 2)()
+        check(self._lib.ojphgpu_encoder_trunc_timing(self._h, t), "encoder_trunc_timing")
+        return dict(search_ms=t[0], stats_ms=t[1])
 
     def set_budgets(self, budgets):
         """A batch encoder codes frame f of every following batch to budgets[f] bytes (len(budgets) == frames): each
@@ -255,7 +296,7 @@ class Encoder:
         if self.max_bytes:                 # (a budget far above what the frame can need: the second round below)
             budget = self.budgets[frame] if self.budgets and 0 <= frame < self.frames else self.max_bytes
             cap = min(budget, self.plan.frame_elems * 4 + 64 * self.plan.num_blocks + (1 << 20))
-        elif self.max_sse is not None:     # (the blocks are coded inside finish: nothing to size the buffer by yet)
+        elif self.max_sse is not None or self.truncating:     # (the blocks are coded inside finish: nothing to size the buffer by yet)
             cap = self.plan.frame_elems * 3 + 64 * self.plan.num_blocks + (1 << 20)
         else:
             cap = self.coded_bytes() // self.frames * 2 + 64 * self.plan.num_blocks + (1 << 20)
@@ -799,12 +840,14 @@ def recode(codestream: bytes, device=0, resilient=False, skip_res=None, region=N
                    min_psnr=min_psnr, cap_bytes=cap_bytes, resample=resample, **kw).recode(codestream)
 
 
-def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0, **kw) -> bytes:
+def encode(image: np.ndarray, device=0, max_bytes=0, max_sse=None, min_psnr=None, cap_bytes=0, truncate_to=0, truncate_level=None, **kw) -> bytes:
     """One-shot helper: image int32 [C,H,W]; keyword args as in plan.make_params (minus sizes); max_bytes=N: coded to a byte
     budget (Encoder.set_budget); max_sse=N / min_psnr=dB: coded to a quality target (Encoder.set_quality), with cap_bytes=N
-    under a byte cap."""
+    under a byte cap; truncate_to=N: a reversible frame under a byte cap (Encoder.set_truncation), truncate_level=j: at a
+    fixed level of the truncation ladder."""
     nc, h, w = image.shape
-    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes, max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes).encode(image)
+    return Encoder(make_params(w, h, nc, **kw), device=device, max_bytes=max_bytes, max_sse=max_sse, min_psnr=min_psnr, cap_bytes=cap_bytes,
+                   truncate_to=truncate_to, truncate_level=truncate_level).encode(image)
 
 
 def gather_runs(src, runs, staged_len, out=None):
@@ -884,17 +927,19 @@ def dwt_image(direction, params: Params, descs: np.ndarray, image, arena, max_w,
 stats_desc_dtype = np.dtype(capi.StatsDesc)
 
 
-def band_stats(descs: np.ndarray, arena, slots):
+def band_stats(descs: np.ndarray, arena, slots, integer=False):
     """ojphgpu_band_stats: descs stats_desc_dtype (host), arena a device tensor of 32-bit elements -> uint32 [slots, 80]
-    half-octave histograms of the magnitudes of the planes' fp32 coefficients"""
+    half-octave histograms of the magnitudes of the planes' fp32 coefficients.  integer=True: ojphgpu_band_stats_int, the
+    planes hold int32 coefficients and bin = the bit length of |v|."""
     torch = _torch()
     dev = arena.device.index
     d = to_device(descs, dev)
     hist = torch.zeros((int(slots), capi.STATS_BINS), dtype=torch.int32, device=arena.device)
     max_w = int(descs["w"].max()) if len(descs) else 0
     max_h = int(descs["h"].max()) if len(descs) else 0
-    check(capi.lib().ojphgpu_band_stats(_stream_ptr(torch, dev), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
-                                        C.c_void_p(arena.data_ptr()), C.c_void_p(hist.data_ptr())), "band_stats")
+    f = capi.lib().ojphgpu_band_stats_int if integer else capi.lib().ojphgpu_band_stats
+    check(f(_stream_ptr(torch, dev), C.c_void_p(d.data_ptr()), len(descs), max_w, max_h,
+            C.c_void_p(arena.data_ptr()), C.c_void_p(hist.data_ptr())), "band_stats_int" if integer else "band_stats")
     torch.cuda.synchronize(dev)
     return hist.cpu().numpy().view(np.uint32)
 

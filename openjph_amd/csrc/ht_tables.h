@@ -44,9 +44,10 @@ int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, 
 inline int ht_encode_block_widths(uint32_t w, uint32_t reversible)
 {
   if (reversible & 4u) return 32;                         // on the 64-bit sample path, whatever its width
-  return (w > 64u ? 2 : 1) | ((reversible & 1u) ? 4 : 8) | ((w > 32u && w <= 64u) ? 256 : 0) | (w > 128u ? 512 : 0);
+  // (bit 3: a reversible block that drops low bit-planes -- `widths` bit 7, the TRUNC instantiations, instead of bit 2)
+  return (w > 64u ? 2 : 1) | ((reversible & 8u) ? 128 : (reversible & 1u) ? 4 : 8) | ((w > 32u && w <= 64u) ? 256 : 0) | (w > 128u ? 512 : 0);
 }
-inline int ht_encode_range_widths(int ored) { return (ored & 47) | ((ored & 256) ? 0 : 16) | ((ored & 512) ? 0 : 64); }
+inline int ht_encode_range_widths(int ored) { return (ored & (47 | 128)) | ((ored & 256) ? 0 : 16) | ((ored & 512) ? 0 : 64); }
 // ojphgpu_ht_decode_step2 with the caller's knowledge of the blocks of the range (kernels_ht_dec.hip)
 // step 1 + step 2 in one launch (kernels_ht_dec.hip, ht_dec_fused_kernel): chains first, step-2 workers behind them
 bool dec_fuses();

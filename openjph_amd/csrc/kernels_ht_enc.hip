@@ -199,7 +199,9 @@ __device__ __forceinline__ uint32_t claim_output(uint32_t* cursor, const uint32_
 // S64: the blocks of components on the 64-bit sample path (ojph_encode_codeblock64, ojph_block_encoder.cpp:1026-1520; the
 // transfer gen_rev_tx_to_cb64, ojph_codestream_gen.cpp:81-100): int64 samples, exponents up to 63, MagSgn values of up to
 // 63 bits and the U-VLC extension for u > 32 (:245-253, :1269-1293, :1487-1492) -- the same symbols otherwise.
-template <bool S64>
+// TRUNC: the blocks whose descriptor asks for fewer bit-planes (cb_desc.reversible bit 3, include/ojphgpu.h): coded at
+// p = 30 - missing_msbs instead of 30 - (K_max - 1); 32-bit reversible blocks only, an instantiation of its own.
+template <bool S64, bool TRUNC = false>
 __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
     const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint32_t* __restrict__ coef,
     uint8_t* __restrict__ scratch, uint8_t* __restrict__ out, uint32_t out_cap,
@@ -215,7 +217,9 @@ __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform, and the compiler knows it
   const uint32_t bi = blockIdx.x * WAVES + wave;
   // narrow blocks of 32-bit samples belong to ht_encode_kernel; blocks of 64-bit samples, of any width, to the S64 instantiation
-  const bool mine = bi < n && (S64 ? (blocks[bi].reversible & 4u) != 0 : (blocks[bi].w > NARROW_MAX_W && (blocks[bi].reversible & 4u) == 0));
+  static_assert(!(S64 && TRUNC), "dropped bit-planes: 32-bit samples only");
+  const bool mine = bi < n && (S64 ? (blocks[bi].reversible & 4u) != 0
+                                   : (blocks[bi].w > NARROW_MAX_W && (blocks[bi].reversible & 12u) == (TRUNC ? 8u : 0u) && (!TRUNC || (blocks[bi].reversible & 1u))));
   if (!__syncthreads_or(mine ? 1 : 0)) return;
   // (16 bytes per lane and turn.  A workgroup lives for 12-40 us and meets at the barrier below before anything else: with
   // 2-byte turns, sixteen of them, the 8K frame's encode was 0.458 ms instead of 0.440, 32 x 32 blocks 0.603 instead of 0.562)
@@ -228,6 +232,9 @@ __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
   const uint32_t W = d.w, H = d.h;
   if (W == 0 || H == 0) { if (lane == 0) { results[bi].offset = 0; results[bi].length = 0; } return; }
   const uint32_t K = d.K_max, p = VBITS - 1u - K;   // missing_msbs = K_max - 1, p = 30 (62) - missing_msbs
+  // TRUNC: the samples stay aligned by K_max (p), the coder looks at them from plane pc = 30 - missing_msbs upwards
+  // (the host has checked missing_msbs < K_max; the min keeps the shift defined whatever a descriptor holds)
+  const uint32_t pc = TRUNC ? 30u - min((uint32_t)d.missing_msbs, 30u) : p;
   const bool rev = (d.reversible & 1u) != 0;
   const float delta_inv = rev ? 0.0f : __fdiv_rn(1.0f, d.delta);         // ojph_codeblock.cpp:98
   const uint32_t* src = coef + d.coef_off;
@@ -278,7 +285,7 @@ __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
     for (int i = 0; i < 8; ++i) {
       const int q = i >> 2, nn = i & 3;
       V t = active ? sample(x0 + 2 * q + (nn >> 1), y0 + (nn & 1)) : (V)0;
-      val[i] = ((V)(t + t) >> p) & ~(V)1;               // 2*mu_p        (:592-595)
+      val[i] = ((V)(t + t) >> pc) & ~(V)1;              // 2*mu_p        (:592-595)
       sgn[i] = (uint32_t)(t >> (VBITS - 1u));
     }
     // ---- bottom sample row of the quad row above: columns x0-1 .. x0+4 ----
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(64 * WAVES) void ht_encode_wide_kernel(
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       V t = (active && !first_row) ? sample(x0 - 1 + i, y0 - 1) : (V)0;
-      V v = ((V)(t + t) >> p) & ~(V)1;
+      V v = ((V)(t + t) >> pc) & ~(V)1;
       Eab[i] = expo(v); Sab[i] = v != 0;
     }
 
@@ -726,7 +733,10 @@ __device__ __forceinline__ void mel_stuff(const uint32_t* raw, uint32_t total_bi
 // LOGP: a step covers 2^LOGP quad pairs across (lane & (2^LOGP - 1)) by 64 / 2^LOGP quad rows down.  4 = the layout
 // described above (blocks up to 64 columns, 4 quad rows per step); 3 = blocks up to 32 columns (the 32 x 32 blocks of
 // the IMF profile), 8 quad rows per step -- with the 16-pair layout half of the lanes of such a block would idle.
-template <bool REV, int LOGP>
+// TRUNC (REV only): the instantiation of the blocks whose descriptor drops low bit-planes (cb_desc.reversible bit 3): they
+// are coded at p = 30 - missing_msbs, i.e. without their t = K_max - 1 - missing_msbs lowest magnitude planes -- the coder's
+// mu is the magnitude shifted right by t, everything behind it is the same code.  The other instantiations skip such blocks.
+template <bool REV, int LOGP, bool TRUNC = false>
 __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWAVES_PER_EU, 8))) void ht_encode_kernel(
     const ojphgpu_cb_desc* __restrict__ blocks, uint32_t n, const uint32_t* __restrict__ coef,
     uint8_t* __restrict__ scratch, uint8_t* __restrict__ out, uint32_t out_cap,
@@ -753,6 +763,8 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   ojphgpu_cb_desc d;
   __builtin_memcpy(&d, &dw, sizeof d);
   static_assert(offsetof(ojphgpu_cb_desc, K_max) == 16 && offsetof(ojphgpu_cb_desc, reversible) == 17, "K_max, reversible: bytes 0, 1 of dword 4");
+  static_assert(offsetof(ojphgpu_cb_desc, missing_msbs) == 18, "missing_msbs: byte 2 of dword 4");
+  static_assert(REV || !TRUNC, "dropped bit-planes: reversible blocks only");
   uint32_t kr = dw.v[4];
   asm volatile("" : "+s"(kr));                                            // (the dword as a whole, in a scalar register)
   const uint32_t d_K_max = kr & 0xFFu, d_reversible = (kr >> 8) & 0xFFu;
@@ -761,11 +773,15 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
   // LOGP 5 (32 pairs by 2 quad rows): the blocks of 65..128 columns of a launch none of whose blocks is wider (128 x 32)
   const bool my_width = LOGP == 5 ? (W > NARROW_MAX_W && W <= 4u * PPR) : (W <= NARROW_MAX_W && W <= 4u * PPR);
   // (false: ht_encode_wide_kernel's, or another instantiation's)
-  const bool my_kind = bi < n && my_width && ((d_reversible & 1u) != 0) == REV && (d_reversible & 4u) == 0;
+  const bool my_kind = bi < n && my_width && ((d_reversible & 1u) != 0) == REV && (d_reversible & 12u) == (TRUNC ? 8u : 0u);
   const bool mine = my_kind && W != 0 && H != 0;
   NarrowLds& L = s_wave[wave];
   uint8_t* outb = reinterpret_cast<uint8_t*>(L.out);
   const uint32_t K = d_K_max, p = 31u - K;      // missing_msbs = K_max - 1, p = 30 - missing_msbs
+  // TRUNC: t = K_max - 1 - missing_msbs planes dropped (the host has checked missing_msbs < K_max; the and keeps the shift
+  // defined whatever a descriptor holds).  Fewer planes need no more room than all of them: scratch slots and output sized
+  // for K_max planes -- (K_max + 2) / 7 bytes per sample -- hold every t.
+  const uint32_t tdrop = TRUNC ? (K - 1u - ((kr >> 16) & 0xFFu)) & 31u : 0u;
   constexpr bool rev = REV;
   const float delta_inv = rev ? 0.0f : __fdiv_rn(1.0f, d.delta);         // ojph_codeblock.cpp:98
   const uint32_t* src = coef + d.coef_off;
@@ -1106,7 +1122,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
           if (rev) {
             const int v = (int)raw;
             const uint32_t a = (uint32_t)(v >= 0 ? v : -v);
-            mu[2 * k + j] = a & colm[k];                                        // :70-76, with the same wrap-around when |v| >= 2^K_max:
+            mu[2 * k + j] = TRUNC ? (a & colm[k]) >> tdrop : a & colm[k];       // :70-76, with the same wrap-around when |v| >= 2^K_max:
             sx[2 * k + j] = raw | (a << p);                                     // its top bit lands on the sign
             nz |= a;                                                            // (clamped loads: every lane holds samples of the block's own rows)
           } else {
@@ -1129,6 +1145,7 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NWA
         }
       }
       if (rev) nz &= (1u << K) - 1u;                      // = the OR of the mu of the block's samples
+      if (TRUNC) nz >>= tdrop;
       // request the rows of the step that takes this set next.  One set: not behind the last step.  Two sets: unconditional,
       // rows past the block's last clamped into it like every other row (a request skipped at the block's end would be a
       // branch that joins "set requested" with "set not requested", and the wait of the NEXT step could no longer leave
@@ -1541,18 +1558,19 @@ namespace ojphgpu {
 // blocks of reversibly transformed components, bit 3 = of irreversibly transformed ones; bit 4 = none of its blocks of
 // up to 64 samples is wider than 32 (they take the 8-pairs-by-8-rows layout); bit 5 = it holds blocks of 64-bit samples
 // (cb_desc.reversible bit 2); bit 6 = none of its wider blocks is wider than 128 samples (they take the narrow kernel's
-// 32-pairs-by-2-rows layout instead of the raster-order wide kernel).  Every kernel skips the blocks of the other kind, so a caller that does not know passes
+// 32-pairs-by-2-rows layout instead of the raster-order wide kernel); bit 7 = it holds reversible blocks that drop low
+// bit-planes (cb_desc.reversible bit 3): the TRUNC instantiations, in the layouts bits 0, 1, 4 and 6 name.  Every kernel skips the blocks of the other kind, so a caller that does not know passes
 // 3 | 32 (wavelet bits clear = both).
 //
 // The launches over n blocks under `widths`, in issue order: the one place that chooses; ht_encode_launch and
 // ojphgpu_ht_encode_launches both ask here.
-struct EncLaunch { uint32_t wide, flag, logp, wgs, per_wg; };   // ht_encode_wide_kernel<flag = S64> (1, logp 0) or ht_encode_kernel<flag = REV, logp> (0)
-constexpr uint32_t ENC_MAX_LAUNCHES = 5;
+struct EncLaunch { uint32_t wide, flag, logp, wgs, per_wg; };   // ht_encode_wide_kernel<flag = S64> (1, logp 0) or ht_encode_kernel<flag = REV, logp> (0); flag bit 1: TRUNC
+constexpr uint32_t ENC_MAX_LAUNCHES = 7;
 static uint32_t enc_launches(uint32_t n, int widths, EncLaunch* L)
 {
   if (n == 0) return 0;
   uint32_t c = 0;
-  if ((widths & 12) == 0) widths |= 12;                   // the caller does not know the wavelets: both instantiations
+  if ((widths & (12 | 128)) == 0) widths |= 12;           // the caller does not know the wavelets: both instantiations
   const uint32_t grid = (n + WAVES - 1) / WAVES, ngrid = (n + NWAVES - 1) / NWAVES;
   if (widths & 1) {                                         // blocks of up to 64 samples: 8 pairs by 8 quad rows where none is wider than 32
     const uint32_t logp = (widths & 16) ? 3u : 4u;
@@ -1566,6 +1584,11 @@ static uint32_t enc_launches(uint32_t n, int widths, EncLaunch* L)
     L[c++] = { 1u, 0u, 0u, grid, (uint32_t)WAVES };
   if (widths & 32)                                          // blocks of components on the 64-bit sample path
     L[c++] = { 1u, 1u, 0u, grid, (uint32_t)WAVES };
+  if (widths & 128) {                                       // reversible blocks that drop low bit-planes, behind everything else
+    if (widths & 1) L[c++] = { 0u, 3u, (widths & 16) ? 3u : 4u, ngrid, (uint32_t)NWAVES };
+    if ((widths & 2) && (widths & 64)) L[c++] = { 0u, 3u, 5u, ngrid, (uint32_t)NWAVES };
+    else if (widths & 2) L[c++] = { 1u, 2u, 0u, grid, (uint32_t)WAVES };
+  }
   return c;
 }
 
@@ -1586,7 +1609,8 @@ int ht_encode_launch(void* stream, const ojphgpu_cb_desc* d_blocks, uint32_t n, 
   for (uint32_t i = 0; i < count; ++i) {
     const EncLaunch& l = L[i];
     Kernel k;
-    if (l.wide) k = l.flag ? ht_encode_wide_kernel<true> : ht_encode_wide_kernel<false>;
+    if (l.wide) k = l.flag == 2u ? ht_encode_wide_kernel<false, true> : l.flag ? ht_encode_wide_kernel<true> : ht_encode_wide_kernel<false>;
+    else if (l.flag == 3u) k = l.logp == 3 ? ht_encode_kernel<true, 3, true> : l.logp == 4 ? ht_encode_kernel<true, 4, true> : ht_encode_kernel<true, 5, true>;
     else if (l.logp == 3) k = l.flag ? ht_encode_kernel<true, 3> : ht_encode_kernel<false, 3>;
     else if (l.logp == 4) k = l.flag ? ht_encode_kernel<true, 4> : ht_encode_kernel<false, 4>;
     else k = l.flag ? ht_encode_kernel<true, 5> : ht_encode_kernel<false, 5>;
@@ -1616,7 +1640,12 @@ extern "C" int ojphgpu_ht_encode_kinds(const ojphgpu_cb_desc* h_blocks, uint32_t
 {
   if (!widths || (!h_blocks && n)) return OJPHGPU_E_INVALID;
   int k = 0;
-  for (uint32_t i = 0; i < n; ++i) k |= ojphgpu::ht_encode_block_widths(h_blocks[i].w, h_blocks[i].reversible);
+  for (uint32_t i = 0; i < n; ++i) {
+    // a block that drops bit-planes (bit 3): 32-bit reversible, and at least its top plane stays -- nothing ill-formed is launched
+    const ojphgpu_cb_desc& d = h_blocks[i];
+    if ((d.reversible & 8u) && ((d.reversible & 5u) != 1u || d.missing_msbs >= d.K_max)) return OJPHGPU_E_INVALID;
+    k |= ojphgpu::ht_encode_block_widths(d.w, d.reversible);
+  }
   *widths = ojphgpu::ht_encode_range_widths(k);
   return OJPHGPU_OK;
 }

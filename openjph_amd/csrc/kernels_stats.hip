@@ -26,10 +26,21 @@ constexpr uint32_t WG = 256, UNIT_ROWS = 8, WIDE = 32768, MAX_W = 1u << 21;
 // a half holds 65535; what a unit can add to one is bounded by the samples its four threads of one lane take (unit_cost)
 constexpr uint32_t FLUSH_AT = 60000;
 
+// INT false: u is an fp32 coefficient, the bin its exponent field and top mantissa bit (include/ojphgpu.h, ojphgpu_band_stats);
+// INT true: u is an int32 coefficient of a reversible plane, the bin the bit length of |u| -- 0 for 0, 32 for INT_MIN
+// (ojphgpu_band_stats_int; section 5f builds on it)
+template <bool INT>
 __device__ __forceinline__ void count(uint32_t* tab, uint32_t lane, uint32_t u, bool valid)
 {
-  int e = (int)((u >> 22) & 0x1FFu) - 191;
-  e = e < 0 ? 0 : e > (int)BINS - 1 ? (int)BINS - 1 : e;
+  int e;
+  if (INT) {
+    const int v = (int)u;
+    const uint32_t a = v < 0 ? 0u - u : u;                   // |INT_MIN| = 2^31 as unsigned
+    e = 32 - (int)__clz((int)a);                             // (__clz(0) = 32)
+  } else {
+    e = (int)((u >> 22) & 0x1FFu) - 191;
+    e = e < 0 ? 0 : e > (int)BINS - 1 ? (int)BINS - 1 : e;
+  }
   // no branch around the add: a sample that does not count adds nothing to the (valid) place its bits name
   atomicAdd(&tab[((uint32_t)e >> 1) * COLS + lane], valid ? 1u << (((uint32_t)e & 1u) * 16u) : 0u);
 }
@@ -55,6 +66,7 @@ __device__ void flush(uint32_t* tab, uint32_t t, uint32_t* __restrict__ hist, ui
 
 // unit u = (descriptor u / row_units, rows [unit_rows (u % row_units), + unit_rows) of its plane); workgroup b takes units
 // b, b + grid, ...  Everything that decides a branch around a barrier is uniform over the workgroup.
+template <bool INT>
 __global__ __launch_bounds__(WG) void band_stats_kernel(const ojphgpu_stats_desc* __restrict__ descs, uint32_t max_w, uint32_t row_units, uint32_t unit_rows,
                                                         uint32_t units, const uint32_t* __restrict__ coef,
                                                         uint32_t* __restrict__ hist)
@@ -97,8 +109,8 @@ __global__ __launch_bounds__(WG) void band_stats_kernel(const ojphgpu_stats_desc
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          count(tab, lane, v[k].x, nv[k] > 0); count(tab, lane, v[k].y, nv[k] > 1);
-          count(tab, lane, v[k].z, nv[k] > 2); count(tab, lane, v[k].w, nv[k] > 3);
+          count<INT>(tab, lane, v[k].x, nv[k] > 0); count<INT>(tab, lane, v[k].y, nv[k] > 1);
+          count<INT>(tab, lane, v[k].z, nv[k] > 2); count<INT>(tab, lane, v[k].w, nv[k] > 3);
         }
       }
     } else {
@@ -113,7 +125,7 @@ __global__ __launch_bounds__(WG) void band_stats_kernel(const ojphgpu_stats_desc
           ok[k] = it < items;
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) count(tab, lane, v[k], ok[k]);
+        for (int k = 0; k < 4; ++k) count<INT>(tab, lane, v[k], ok[k]);
       }
     }
   }
@@ -133,10 +145,24 @@ __global__ void requant_frames_kernel(ojphgpu_cb_desc* __restrict__ descs, uint3
   d.delta = b.delta;
 }
 
+// a truncation table into the block descriptors (section 5f): block i drops drop[cls[i]] planes.  0 planes: the plan's own
+// descriptor (bit 3 clear, missing_msbs = K_max - 1), so level 0 puts back what the encoder was made with.
+__global__ void trunc_descs_kernel(ojphgpu_cb_desc* __restrict__ descs, uint32_t nb, const uint32_t* __restrict__ cls,
+                                   const uint8_t* __restrict__ drop)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb) return;
+  ojphgpu_cb_desc& d = descs[i];
+  const uint32_t top = d.K_max ? d.K_max - 1u : 0u, t = min((uint32_t)drop[cls[i]], top);   // (a flagged block keeps its top plane)
+  d.missing_msbs = (uint8_t)(top - t);
+  d.reversible = (uint8_t)(t ? d.reversible | 8u : d.reversible & ~8u);
+}
+
 }  // namespace
 
-extern "C" int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
-                                  const void* d_coef, uint32_t* d_hist)
+template <bool INT>
+static int band_stats_launch(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
+                             const void* d_coef, uint32_t* d_hist)
 {
   if (!d_descs || !d_coef || !d_hist) return OJPHGPU_E_INVALID;
   if (n == 0 || max_w == 0 || max_h == 0) return OJPHGPU_OK;
@@ -147,9 +173,21 @@ extern "C" int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_desc
   if (units > 0xFFFFFFFFull) return OJPHGPU_E_INVALID;
   // a bounded grid that strides over the units: eight workgroups per compute unit of the largest part
   const uint32_t grid = (uint32_t)std::min<uint64_t>(units, 2048);
-  hipLaunchKernelGGL(band_stats_kernel, dim3(grid), dim3(WG), 0, (hipStream_t)stream, d_descs,
+  hipLaunchKernelGGL(band_stats_kernel<INT>, dim3(grid), dim3(WG), 0, (hipStream_t)stream, d_descs,
                      max_w, (uint32_t)row_units, unit_rows, (uint32_t)units, (const uint32_t*)d_coef, d_hist);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
+}
+
+extern "C" int ojphgpu_band_stats(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
+                                  const void* d_coef, uint32_t* d_hist)
+{
+  return band_stats_launch<false>(stream, d_descs, n, max_w, max_h, d_coef, d_hist);
+}
+
+extern "C" int ojphgpu_band_stats_int(void* stream, const ojphgpu_stats_desc* d_descs, uint32_t n, uint32_t max_w, uint32_t max_h,
+                                      const void* d_coef, uint32_t* d_hist)
+{
+  return band_stats_launch<true>(stream, d_descs, n, max_w, max_h, d_coef, d_hist);
 }
 
 namespace ojphgpu {
@@ -161,6 +199,13 @@ int requant_frames_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, u
   if (frames > 65535u) return OJPHGPU_E_INVALID;           // (the grid's y extent)
   hipLaunchKernelGGL(requant_frames_kernel, dim3((nb + 255u) / 256u, frames), dim3(256), 0, (hipStream_t)stream, d_descs, nb, frames, d_class,
                      d_quant, nclasses);
+  return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
+}
+
+int trunc_descs_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, const uint32_t* d_class, const uint8_t* d_drop)
+{
+  if (nb == 0) return OJPHGPU_OK;
+  hipLaunchKernelGGL(trunc_descs_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d_descs, nb, d_class, d_drop);
   return hipGetLastError() == hipSuccess ? OJPHGPU_OK : OJPHGPU_E_HIP;
 }
 

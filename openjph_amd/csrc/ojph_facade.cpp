@@ -115,6 +115,7 @@ struct codestream_state {
   bool headers_written = false, headers_read = false, decoded = false;
   std::string profile;
   int device = 0;
+  size_t trunc_budget = 0;            // set_truncation_budget: flush() codes the reversible frame under this cap (0: off)
   size_t byte_budget = 0;             // set_byte_budget: flush() codes the frame to at most this many bytes (0: off)
   bool quality_on = false; ui64 max_sse = 0;   // set_max_sse: flush() codes the frame to at most this squared error
   ui64 cap_bytes = 0;                          // ... and to at most this many bytes (0: no cap)
@@ -563,6 +564,14 @@ bool codestream::get_byte_budget_result(ui32& grid_index, float& qstep, ui64& by
   grid_index = info.grid_index; qstep = info.qstep; bytes = info.bytes; passes = info.passes;
   return true;
 }
+void codestream::set_truncation_budget(size_t max_bytes) { state->trunc_budget = max_bytes; }
+bool codestream::get_truncation_result(ui32& level, ui64& bytes, ui32& passes)
+{
+  ojphgpu_trunc_info info;
+  if (!state->enc || ojphgpu_encoder_trunc_info(state->enc, &info) != OJPHGPU_OK) return false;
+  level = info.level; bytes = info.bytes; passes = info.passes;
+  return true;
+}
 void codestream::set_max_sse(ui64 max_sse) { state->quality_on = true; state->max_sse = max_sse; state->cap_bytes = 0; }
 void codestream::set_max_sse(ui64 max_sse, ui64 cap_bytes) { state->quality_on = true; state->max_sse = max_sse; state->cap_bytes = cap_bytes; }
 void codestream::clear_max_sse() { state->quality_on = false; state->cap_bytes = 0; }
@@ -744,8 +753,11 @@ void codestream::write_headers(outfile_base* file, const comment_exchange* comme
       ojph_error(0x00030F13, "a byte budget needs irreversible coding of every component with the Part-1 wavelet and no quality factor");
     if (S.quality_on && ojphgpu_encoder_set_quality_capped(S.enc, S.max_sse, S.cap_bytes) != OJPHGPU_OK)
       ojph_error(0x00030F16, "a quality target needs irreversible coding of every component with the Part-1 wavelet, no quality factor, no byte budget and components of at most 16 bits");
+    if (S.trunc_budget && ojphgpu_encoder_set_truncation(S.enc, S.trunc_budget) != OJPHGPU_OK)
+      ojph_error(0x00030F19, "a truncation budget needs reversible coding of every component with the Part-1 wavelet and one number of decompositions, 32-bit samples, and no byte budget or quality target");
     S.alloc_frame();
   }
+  if (S.trunc_budget && !S.enc) ojph_error(0x00030F1A, "a truncation budget is available for single frames on one device (no restart()ed sequence, no set_devices)");
   if (S.quality_on && !S.enc) ojph_error(0x00030F17, "a quality target is available for single frames on one device (no restart()ed sequence, no set_devices)");
   if (S.byte_budget && !S.enc) ojph_error(0x00030F14, "a byte budget is available for single frames on one device (no restart()ed sequence, no set_devices)");
   // a frame still queued for this very file object (enable_frame_pipelining, and the application re-opened the object for
@@ -802,6 +814,7 @@ void codestream::flush()
   }
   size_t len = 0;
   int rc = ojphgpu_encode(S.enc, S.frame, nullptr, 0, &len);            // runs the GPU path; reports the codestream size
+  if (rc == OJPHGPU_E_BUDGET && S.trunc_budget) ojph_error(0x00030F1B, "the truncation budget of %zu bytes is below the codestream that keeps only every sub-band's top bit-plane (status %d)", S.trunc_budget, rc);
   if (rc == OJPHGPU_E_BUDGET) ojph_error(0x00030F15, "the byte budget of %zu bytes is below the codestream of the coarsest quantisation step (status %d)", S.quality_on ? (size_t)S.cap_bytes : S.byte_budget, rc);
   if (rc == OJPHGPU_E_QUALITY) ojph_error(0x00030F18, "the quality target of %llu is beyond the finest quantisation step (status %d)", (unsigned long long)S.max_sse, rc);
   if (rc != OJPHGPU_E_OVERFLOW && rc != OJPHGPU_OK) ojph_error(0x00030F0B, "GPU encode failed (status %d)", rc);

@@ -249,6 +249,27 @@ int  capped_search(const RateTable& T, uint64_t max_sse, uint64_t cap_bytes, int
 int  requant_frames_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, uint32_t frames, const uint32_t* d_class, const BandQuant* d_quant,
                            uint32_t nclasses);
 
+// A reversible frame under a byte cap (include/ojphgpu.h section 5f; ojph_rate.cpp): the ladder of truncation tables.  q =
+// a band's weight in quarter planes, top = K_max - 1, the most planes its blocks can drop; t_b(j) = drop(j, b).
+struct TruncLadder {
+  uint32_t levels = 0;                                       // J
+  std::vector<int32_t> q;                                    // per band of the plan
+  std::vector<uint8_t> top;
+  std::vector<uint32_t> band_class, class_band;              // band -> class (component, resolution, orientation); class -> one of its bands
+  uint8_t drop(uint32_t j, size_t b) const {
+    const int64_t a = (int64_t)j + 3 - q[b];
+    const int64_t t = a >= 0 ? a / 4 : -((3 - a) / 4);       // floor division
+    return (uint8_t)std::min<int64_t>(std::max<int64_t>(t, 0), top[b]);
+  }
+};
+bool trunc_plan_ok(const Plan& P);                           // reversible Part-1 throughout, one wavelet and depth, 32-bit samples
+int  trunc_ladder_build(const Plan& P, TruncLadder& T);
+int  trunc_search(const TruncLadder& T, uint64_t num_blocks, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
+                  ojphgpu_trunc_info* out);
+// missing_msbs = K_max - 1 - t[class] and bit 3 of `reversible` (set where t > 0) into the block descriptors: block i from
+// d_drop[d_class[i]] (kernels_stats.hip)
+int  trunc_descs_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, const uint32_t* d_class, const uint8_t* d_drop);
+
 // Transcoding (include/ojphgpu.h section 5d; ojph_transcode.cpp): a block decoder of S and a block coder of O can share one
 // arena -- both plans unrestricted, Part-1 wavelets and 32-bit samples throughout, the same arena size, and every band with the
 // same rectangle at the same place; a reversible band of O holds the magnitudes of S's (K_max).  S is a parsed plan.

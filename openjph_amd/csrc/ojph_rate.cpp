@@ -592,3 +592,186 @@ extern "C" int ojphgpu_rate_predict(const ojphgpu_plan* plan, const uint32_t* hi
     return OJPHGPU_OK;
   });
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A reversible frame under a byte cap (include/ojphgpu.h section 5f): the ladder of truncation tables and the search.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace ojphgpu {
+
+bool trunc_plan_ok(const Plan& P)
+{
+  if (P.parsed || !P.atks.empty() || !P.dfss.empty() || P.p.wavelet != 0 || P.any_wide || P.p.num_comps == 0) return false;
+  const CodStyle& s0 = P.style(0);
+  for (uint32_t c = 0; c < P.p.num_comps; ++c) {
+    const CodStyle& st = P.style(c);
+    if (!st.rev || st.wavelet >= 2 || st.dfs >= 0 || st.L != s0.L) return false;
+    if (c < P.wide.size() && P.wide[c]) return false;
+  }
+  return true;
+}
+
+// L2 norm of the 1-D 5/3 synthesis basis vector of the low (high) branch at decomposition depth d: a unit impulse in that
+// band taken through the linear inverse lifting, d levels, in double, in the middle of a line of 64 coefficients at depth d
+// (the vector spans fewer than 8 of them, so the borders play no part).  Beyond depth 12 the line would get long for
+// nothing: every further level of low-pass synthesis multiplies the norm by sqrt(2) to within 4^-d.
+static double trunc_synth_norm(uint32_t d, bool high)
+{
+  if (d == 0) return 1.0;
+  const uint32_t dd = std::min(d, 12u);
+  size_t n = 64;
+  std::vector<double> s(n, 0.0), h(n, 0.0), x;
+  (high ? h : s)[n / 2] = 1.0;
+  for (uint32_t lev = dd; lev >= 1; --lev) {
+    x.assign(2 * n, 0.0);
+    for (size_t i = 0; i < n; ++i) x[2 * i] = s[i] - (h[i ? i - 1 : 0] + h[i]) / 4.0;
+    for (size_t i = 0; i < n; ++i) x[2 * i + 1] = h[i] + (x[2 * i] + x[i + 1 < n ? 2 * i + 2 : 2 * i]) / 2.0;
+    s = x; n *= 2; h.assign(n, 0.0);
+  }
+  double e = 0;
+  for (double v : x) e += v * v;
+  return std::sqrt(e) * std::exp2(0.5 * (double)(d - dd));
+}
+
+int trunc_ladder_build(const Plan& P, TruncLadder& T)
+{
+  if (!trunc_plan_ok(P) || P.bands.empty()) return OJPHGPU_E_INVALID;
+  const size_t nb = P.bands.size();
+  std::vector<double> w(nb);
+  std::map<uint32_t, double> lo, hi;                         // by depth
+  auto norm = [&](uint32_t d, bool high) { auto& m = high ? hi : lo; auto it = m.find(d); if (it == m.end()) it = m.emplace(d, trunc_synth_norm(d, high)).first; return it->second; };
+  const bool rct = P.p.color_transform != 0 && P.p.num_comps >= 3;
+  double wmin = 0;
+  for (size_t i = 0; i < nb; ++i) {
+    const Band& B = P.bands[i];
+    const uint32_t L = P.style(B.comp).L, d = B.res == 0 ? L : L - B.res + 1;
+    const bool hh = B.band == 1 || B.band == 3, vh = B.band == 2 || B.band == 3;   // HL, HH: high horizontally; LH, HH: vertically
+    const double gc = rct && B.comp < 3 ? (B.comp == 0 ? std::sqrt(3.0) : std::sqrt(11.0 / 16.0)) : 1.0;
+    w[i] = std::log2(norm(d, hh) * norm(d, vh) * gc);
+    if (i == 0 || w[i] < wmin) wmin = w[i];
+  }
+  T.q.resize(nb); T.top.resize(nb);
+  int64_t last = 0;
+  for (size_t i = 0; i < nb; ++i) {
+    T.q[i] = (int32_t)std::floor(4.0 * (w[i] - wmin) + 0.5);
+    T.top[i] = (uint8_t)(P.bands[i].K_max ? std::min(P.bands[i].K_max, 32u) - 1u : 0u);
+    last = std::max<int64_t>(last, 4 * (int64_t)T.top[i] + T.q[i]);
+  }
+  T.levels = (uint32_t)std::max<int64_t>(last - 3 + 1, 1);
+  // the classes of bands (component, resolution, orientation): a table has one entry per class on the device
+  std::map<uint64_t, uint32_t> ids;
+  T.band_class.resize(nb); T.class_band.clear();
+  for (size_t i = 0; i < nb; ++i) {
+    const Band& B = P.bands[i];
+    const uint64_t key = ((uint64_t)B.comp << 16) | ((uint64_t)B.res << 8) | B.band;
+    auto it = ids.find(key);
+    if (it == ids.end()) { it = ids.emplace(key, (uint32_t)T.class_band.size()).first; T.class_band.push_back((uint32_t)i); }
+    T.band_class[i] = it->second;
+  }
+  return OJPHGPU_OK;
+}
+
+// The model of the search: a coefficient of bit length len > t costs about len - t + 3 bits, the constants are those of
+// RateModel.  Only its shape matters: it is rescaled by what a trial measures.
+static double trunc_predict(const TruncLadder& T, const uint32_t* hist, uint64_t num_blocks, uint32_t j)
+{
+  double bits = 0;
+  for (size_t b = 0; b < T.q.size(); ++b) {
+    const uint32_t t = T.drop(j, b);
+    for (uint32_t len = t + 1; len <= 32; ++len) bits += (double)hist[b * OJPHGPU_STATS_BINS + len] * (double)(len - t + 3);
+  }
+  return bits / 8.0 + 300.0 + 6.0 * (double)num_blocks;
+}
+
+int trunc_search(const TruncLadder& T, uint64_t num_blocks, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_trunc_info* out)
+{
+  memset(out, 0, sizeof(*out));
+  // the levels whose table differs from the level before: only they are measured
+  std::vector<uint32_t> u;
+  for (uint32_t j = 0; j < T.levels; ++j) {
+    bool differs = j == 0;
+    for (size_t b = 0; b < T.q.size() && !differs; ++b) differs = T.drop(j, b) != T.drop(j - 1, b);
+    if (differs) u.push_back(j);
+  }
+  const int64_t U = (int64_t)u.size();
+  // lo: the largest index measured NOT to fit (-1: none), hi: the smallest measured to fit (U: none); hi - lo == 1 ends it
+  int64_t lo = -1, hi = U; uint64_t size_lo = 0, size_hi = 0;
+  double scale = 1.0;
+  bool guided = false;                                      // the model has led its trial: level 0, the model's level, then halving (the pass cap)
+  auto measure = [&](int64_t k) -> int {
+    const int64_t sz = fn(user, u[(size_t)k]);
+    if (sz < 0) return (int)sz;
+    out->passes++;
+    if (hist) { const double pr = trunc_predict(T, hist, num_blocks, u[(size_t)k]); if (pr > 0) scale = (double)sz / pr; }
+    if ((uint64_t)sz <= max_bytes) { hi = k; size_hi = (uint64_t)sz; } else { lo = k; size_lo = (uint64_t)sz; }
+    return 0;
+  };
+  auto propose = [&]() -> int64_t {                         // the first index the (rescaled) model says fits, inside (lo, hi)
+    for (int64_t k = lo + 1; k < hi; ++k) if (scale * trunc_predict(T, hist, num_blocks, u[(size_t)k]) <= (double)max_bytes) return k;
+    return hi - 1;
+  };
+  while (hi - lo > 1) {
+    int64_t k;
+    if (out->passes == 0) k = 0;                             // lossless first: a frame that fits takes one pass, and its size scales the model
+    else if (hist && !guided) { guided = true; k = propose(); }
+    else k = lo + (hi - lo) / 2;
+    if (out->passes <= 1) out->first_guess = u[(size_t)k];
+    const int rc = measure(k);
+    if (rc) return rc;
+  }
+  if (hi == U) return OJPHGPU_E_BUDGET;
+  out->level = u[(size_t)hi]; out->bytes = size_hi; out->bytes_finer = lo >= 0 ? size_lo : 0;
+  out->lossless = hi == 0;
+  for (size_t b = 0; b < T.q.size(); ++b) out->max_dropped = std::max<uint32_t>(out->max_dropped, T.drop(out->level, b));
+  return OJPHGPU_OK;
+}
+
+}  // namespace ojphgpu
+
+extern "C" int ojphgpu_plan_trunc_levels(const ojphgpu_plan* plan, uint32_t* levels)
+{
+  if (!plan || !levels) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    TruncLadder T;
+    const int rc = trunc_ladder_build(plan->plan, T);
+    if (rc) return rc;
+    *levels = T.levels;
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_plan_trunc_weights(const ojphgpu_plan* plan, int32_t* q)
+{
+  if (!plan || !q) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    TruncLadder T;
+    const int rc = trunc_ladder_build(plan->plan, T);
+    if (rc) return rc;
+    std::copy(T.q.begin(), T.q.end(), q);
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_plan_trunc_table(const ojphgpu_plan* plan, uint32_t j, uint8_t* t)
+{
+  if (!plan || !t) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    TruncLadder T;
+    const int rc = trunc_ladder_build(plan->plan, T);
+    if (rc) return rc;
+    if (j >= T.levels) return OJPHGPU_E_INVALID;
+    for (size_t b = 0; b < T.q.size(); ++b) t[b] = T.drop(j, b);
+    return OJPHGPU_OK;
+  });
+}
+
+extern "C" int ojphgpu_trunc_search(const ojphgpu_plan* plan, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
+                                    ojphgpu_trunc_info* info)
+{
+  if (!plan || !fn || !info) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    TruncLadder T;
+    const int rc = trunc_ladder_build(plan->plan, T);
+    if (rc) return rc;
+    return trunc_search(T, plan->plan.blocks.size(), hist, max_bytes, fn, user, info);
+  });
+}

@@ -75,6 +75,7 @@ extern "C" void ojphgpu_encoder_destroy(ojphgpu_encoder* e)
   e->timer.destroy();
   delete e->quality;
   delete e->rate;
+  delete e->trunc;
   delete e;
 }
 
@@ -373,10 +374,11 @@ namespace {
 struct BlockCoderRun {
   ojphgpu_encoder* e; uint8_t* out; ojphgpu_cb_result* res; uint32_t* cnt; uint32_t nblocks; Spans* T;
   bool forked = false, cleared_on_side = false;
+  int more_widths = 0;                                      // `widths` bits this run adds to the cut's (section 5f: bit 7)
   int launch(hipStream_t st, uint32_t first, uint32_t n, int widths) {
     const int sh = T ? T->begin(SP_HT_ENC, st) : -1;
     int rc = ojphgpu::ht_encode_launch(st, (const ojphgpu_cb_desc*)e->cb_descs.p + first, n, e->arena.p, (uint8_t*)e->scratch.p, out,
-                                       e->out_cap, res + first, cnt, cnt + 1, widths, (const uint32_t*)e->regions.p, e->nreg, first);
+                                       e->out_cap, res + first, cnt, cnt + 1, widths | more_widths, (const uint32_t*)e->regions.p, e->nreg, first);
     if (rc) return rc;
     if (T) T->end(sh, st);
     return OJPHGPU_OK;
@@ -467,7 +469,7 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
     T.end(sp, s);
   }
   if (rc) return rc;
-  const bool budget = e->searches();                        // the blocks are coded by the search, in ojphgpu_encoder_finish*
+  const bool budget = e->searches() || e->trunc_on;         // the blocks are coded by the search, in ojphgpu_encoder_finish*
   for (size_t i = 0; i < e->batches.size(); ++i) {
     const LevelBatch& b = e->batches[i];
     const int sp = T.begin(SP_DWT, s);
@@ -488,6 +490,20 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
       if ((rc = coder.fork_top(release)) != 0) return rc;
       if (release) { s = e->low; branch.armed = true; }     // nothing behind this point touches the caller's memory
     }
+  }
+  if (e->trunc_on) {                                        // section 5f: under a cap the search wants the integer statistics
+    EncoderTrunc& R = *e->trunc;
+    if (e->trunc_level < 0) {
+      HIPCHK(hipMemsetAsync(R.hist.p, 0, R.hist.n, s));
+      const int sp = T.begin(SP_STATS, s);
+      rc = ojphgpu_band_stats_int(s, (const ojphgpu_stats_desc*)R.stats_descs.p, R.n_stats, R.stats_max_w, R.stats_max_h, e->arena.p, (uint32_t*)R.hist.p);
+      if (rc) return rc;
+      T.end(sp, s);
+    }
+    T.finish(s);
+    R.searched = false;
+    e->ran = true; e->fetched = false;
+    return OJPHGPU_OK;
   }
   if (e->quality_on) {                                      // the search reads the planes in the arena and the caller's frame
     T.finish(s);
@@ -581,11 +597,13 @@ static int encoder_fetch(ojphgpu_encoder* e, uint32_t frame, std::vector<ojphgpu
       }
     e->fetched = true;
   }
-  ojphgpu_coded_blocks(P, e->block_ids, e->h_results.data() + (size_t)frame * e->block_ids.size(), cb);
+  ojphgpu_coded_blocks(P, e->block_ids, e->h_results.data() + (size_t)frame * e->block_ids.size(), cb,
+                       e->trunc_on ? e->trunc->band_drop.data() : nullptr);
   return OJPHGPU_OK;
 }
 
 static int encoder_rate_search(ojphgpu_encoder* e);
+static int encoder_trunc_code(ojphgpu_encoder* e);
 static int encoder_quality_search(ojphgpu_encoder* e);
 static int encoder_capped_search(ojphgpu_encoder* e);
 
@@ -606,7 +624,8 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
   const bool budgets = !e->budgets.empty();
-  int rc = e->quality_on ? (e->cap_bytes ? encoder_capped_search(e) : encoder_quality_search(e)) : budgets ? encoder_rate_search(e) : OJPHGPU_OK;
+  int rc = e->trunc_on ? encoder_trunc_code(e)
+         : e->quality_on ? (e->cap_bytes ? encoder_capped_search(e) : encoder_quality_search(e)) : budgets ? encoder_rate_search(e) : OJPHGPU_OK;
   if (rc) return rc;
   ojphgpu_rate_info info;
   if (budgets && (rc = ojphgpu_rate_rounds_frame(e->rate->rounds, frame, &info)) != 0) return rc;   // (OJPHGPU_E_BUDGET: this frame's alone)
@@ -616,6 +635,7 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
   auto t1 = now();
   rc = ojphgpu_t2_write(e->searches() ? e->rate->frame_plan[frame] : e->handle, e->h_out.p, cb.data(), h_out, cap, out_len);
   if (budgets) e->rate->final_ms = std::chrono::duration<double, std::milli>(now() - t0).count();
+  if (e->trunc_on && e->trunc_level >= 0 && (rc == OJPHGPU_OK || rc == OJPHGPU_E_OVERFLOW)) e->trunc->info.bytes = *out_len;   // (a fixed level: nothing measured it)
   if (e->quality_on) e->quality->final_ms += std::chrono::duration<double, std::milli>(now() - t0).count();
   if (tm) fprintf(stderr, "ojphgpu: finish frame %u: D2H %.2f ms, Tier-2 %.2f ms\n", frame,
                   std::chrono::duration<double, std::milli>(t1 - t0).count(),
@@ -627,7 +647,7 @@ extern "C" int ojphgpu_encoder_finish_frame(ojphgpu_encoder* e, uint32_t frame, 
 extern "C" int ojphgpu_encoder_finish_tiles(ojphgpu_encoder* e, uint8_t* h_out, size_t cap, size_t* out_len,
                                              uint32_t* tile_part_len)
 {
-  if (!e || !out_len || !e->ran || e->searches()) return OJPHGPU_E_INVALID;
+  if (!e || !out_len || !e->ran || e->searches() || e->trunc_on) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     std::vector<ojphgpu_coded_block> cb;
     int rc = encoder_fetch(e, 0, cb);
@@ -649,7 +669,7 @@ int copy_to_host_launch(void* stream, void* d_dst, const void* src, size_t bytes
 extern "C" int ojphgpu_encoder_finish_tiles_device(ojphgpu_encoder* e, uint8_t* d_out, size_t cap, size_t* out_len,
                                                     uint32_t* tile_part_len)
 {
-  if (!e || !out_len || !e->ran || e->searches()) return OJPHGPU_E_INVALID;
+  if (!e || !out_len || !e->ran || e->searches() || e->trunc_on) return OJPHGPU_E_INVALID;
   return no_throw([&]() -> int {
     const Plan& P = *e->P;
     uint64_t nbytes = 0;
@@ -945,6 +965,179 @@ extern "C" int ojphgpu_encoder_rate_timing(ojphgpu_encoder* e, float out[4])
   out[0] = (float)e->rate->search_ms; out[1] = (float)e->rate->wait_ms; out[2] = (float)e->rate->final_ms;
   if (e->timer.read(SP_STATS, &out[3])) return OJPHGPU_E_HIP;
   return OJPHGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// a reversible frame under a byte cap (include/ojphgpu.h section 5f)
+// ---------------------------------------------------------------------------------------------
+static int encoder_trunc_setup(ojphgpu_encoder* e)
+{
+  const Plan& P = *e->P;
+  return no_throw([&]() -> int {
+    HIPCHK(hipSetDevice(e->device));
+    std::unique_ptr<EncoderTrunc> R(new EncoderTrunc());
+    for (const Band& B : P.bands) if ((uint64_t)B.r.w * B.r.h > 0xFFFFFFFFull) return OJPHGPU_E_INVALID;   // the counts are 32 bits wide
+    int rc = trunc_ladder_build(P, R->ladder);
+    if (rc) return rc;
+    std::vector<ojphgpu_stats_desc> sd;
+    for (size_t i = 0; i < P.bands.size(); ++i) {
+      const Band& B = P.bands[i];
+      if (B.empty) continue;
+      sd.push_back(ojphgpu_stats_desc{ B.plane_off, B.pitch, B.r.w, B.r.h, (uint32_t)i });
+      R->stats_max_w = std::max(R->stats_max_w, B.r.w); R->stats_max_h = std::max(R->stats_max_h, B.r.h);
+    }
+    R->n_stats = (uint32_t)sd.size();
+    std::vector<uint32_t> cls(e->block_ids.size());
+    for (size_t i = 0; i < cls.size(); ++i) cls[i] = R->ladder.band_class[P.blocks[e->block_ids[i]].band];
+    const size_t nc = R->ladder.class_band.size();
+    if (R->stats_descs.alloc(std::max<size_t>(sd.size(), 1) * sizeof(sd[0])) || R->hist.alloc(P.bands.size() * OJPHGPU_STATS_BINS * 4) ||
+        R->block_class.alloc(std::max<size_t>(cls.size(), 1) * 4) || R->drop.alloc(std::max<size_t>(nc, 4)))
+      return OJPHGPU_E_NOMEM;
+    if (!sd.empty()) HIPCHK(hipMemcpy(R->stats_descs.p, sd.data(), sd.size() * sizeof(sd[0]), hipMemcpyHostToDevice));
+    if (!cls.empty()) HIPCHK(hipMemcpy(R->block_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
+    R->h_hist.assign(P.bands.size() * OJPHGPU_STATS_BINS, 0);
+    R->h_drop.assign(nc, 0); R->band_drop.assign(P.bands.size(), 0);
+    e->trunc = R.release();
+    return OJPHGPU_OK;
+  });
+}
+
+// the table of `level` into the block descriptors, on the encoder's stream
+static int encoder_trunc_descs(ojphgpu_encoder* e, uint32_t level)
+{
+  EncoderTrunc& R = *e->trunc;
+  for (size_t c = 0; c < R.h_drop.size(); ++c) R.h_drop[c] = R.ladder.drop(level, R.ladder.class_band[c]);
+  HIPCHK(hipMemcpyAsync(R.drop.p, R.h_drop.data(), R.h_drop.size(), hipMemcpyHostToDevice, e->stream));
+  return trunc_descs_launch(e->stream, (ojphgpu_cb_desc*)e->cb_descs.p, (uint32_t)e->block_ids.size(), (const uint32_t*)R.block_class.p,
+                            (const uint8_t*)R.drop.p);
+}
+
+static bool encoder_may_truncate(const ojphgpu_encoder* e)
+{
+  const Plan& P = *e->P;
+  return e->nframes == 1 && e->tiles.first == 0 && e->tiles.count == P.tiles.size() && !e->o_out && !e->o_results && !e->o_counters &&
+         !e->searches() && trunc_plan_ok(P);
+}
+
+// switches the mode on (cap > 0, or level >= 0) or off; off puts the plan's own descriptors back
+static int encoder_trunc_mode(ojphgpu_encoder* e, uint64_t cap, int32_t level)
+{
+  const bool on = cap > 0 || level >= 0;
+  if (!on) {
+    if (!e->trunc_on) return OJPHGPU_OK;
+    HIPCHK(hipSetDevice(e->device));
+    int rc = encoder_settle(e);
+    if (rc || (rc = encoder_trunc_descs(e, 0)) != 0) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->trunc_on = false; e->trunc_bytes = 0; e->trunc_level = -1; e->ran = false;
+    return OJPHGPU_OK;
+  }
+  if (!encoder_may_truncate(e)) return OJPHGPU_E_INVALID;
+  if (!e->trunc) { const int rc = encoder_trunc_setup(e); if (rc) return rc; }
+  if (level >= 0 && (uint32_t)level >= e->trunc->ladder.levels) return OJPHGPU_E_INVALID;
+  { const int rc = encoder_settle(e); if (rc) return rc; }    // an object that gains the mode: no released run is left in flight
+  e->trunc_on = true; e->trunc_bytes = cap; e->trunc_level = level;
+  e->trunc->have_info = false; e->trunc->searched = false;
+  e->ran = false;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_set_truncation(ojphgpu_encoder* e, uint64_t max_bytes)
+{
+  if (!e) return OJPHGPU_E_INVALID;
+  return encoder_trunc_mode(e, max_bytes, -1);
+}
+
+extern "C" int ojphgpu_encoder_set_trunc_level(ojphgpu_encoder* e, int32_t j)
+{
+  if (!e) return OJPHGPU_E_INVALID;
+  return encoder_trunc_mode(e, 0, j < 0 ? -1 : j);
+}
+
+extern "C" int ojphgpu_encoder_trunc_timing(ojphgpu_encoder* e, float out[2])
+{
+  if (!e || !out || !e->trunc_on || !e->trunc || !e->trunc->searched || !e->ran) return OJPHGPU_E_INVALID;
+  out[0] = (float)e->trunc->search_ms;
+  out[1] = 0.0f;
+  if (e->trunc_level < 0 && e->timer.read(SP_STATS, &out[1])) return OJPHGPU_E_HIP;
+  return OJPHGPU_OK;
+}
+
+extern "C" int ojphgpu_encoder_trunc_info(ojphgpu_encoder* e, ojphgpu_trunc_info* info)
+{
+  if (!e || !info || !e->trunc_on || !e->trunc || !e->trunc->have_info || !e->trunc->searched) return OJPHGPU_E_INVALID;
+  *info = e->trunc->info;
+  return OJPHGPU_OK;
+}
+
+// The blocks of the last run coded at `level` in the schedule of a plain run (so level 0 leaves what a plain run leaves); the
+// block lengths come to the host and Tier-2 lays the codestream out: size(level), or an error (< 0).  R.band_drop then
+// stands at that level.
+static int64_t encoder_trunc_trial(ojphgpu_encoder* e, uint32_t level)
+{
+  EncoderTrunc& R = *e->trunc;
+  const Plan& P = *e->P;
+  hipStream_t s = e->stream;
+  const uint32_t nb = (uint32_t)e->block_ids.size();
+  BlockCoderRun coder{ e, (uint8_t*)e->out.p, (ojphgpu_cb_result*)e->results.p, (uint32_t*)e->counters.p, nb, nullptr };
+  int rc = coder.clear();                                   // (settles; the descriptors are rewritten behind every earlier launch)
+  if (rc || (rc = encoder_trunc_descs(e, level)) != 0) return rc;
+  bool any = false;
+  for (size_t b = 0; b < R.band_drop.size(); ++b) { R.band_drop[b] = R.ladder.drop(level, b); any = any || R.band_drop[b]; }
+  // the blocks that drop planes take the instantiations of their own (`widths` bit 7) behind the plain ones of the cut: above
+  // level 0 both kinds run over all blocks, each skipping the other's
+  coder.more_widths = any ? 128 : 0;
+  if ((rc = coder.rest_and_join()) != 0) return rc;
+  uint32_t status = 0;
+  const size_t rbytes = e->h_results.size() * sizeof(ojphgpu_cb_result);
+  if (rbytes) HIPCHK(hipMemcpyAsync(e->h_results.data(), e->results.p, rbytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&status, (uint32_t*)e->counters.p + 1, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  e->fetched = false;
+  if (status) return OJPHGPU_E_OVERFLOW;                    // (cannot happen: fewer planes need no more room than all of them)
+  std::vector<ojphgpu_coded_block> cb;
+  ojphgpu_coded_blocks(P, e->block_ids, e->h_results.data(), cb, R.band_drop.data());
+  T2Layout L;
+  rc = t2_layout_codestream(P, cb.data(), L);
+  return rc ? (int64_t)rc : (int64_t)L.total;
+}
+
+// What ojphgpu_encoder_finish does first in this mode, once per run: the search under the cap, or the fixed level.  When it
+// returns OJPHGPU_OK the device holds the frame as finish writes it.
+static int encoder_trunc_code(ojphgpu_encoder* e)
+{
+  EncoderTrunc& R = *e->trunc;
+  if (R.searched) return R.search_rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  auto run = [&]() -> int {
+    HIPCHK(hipSetDevice(e->device));
+    R.have_info = true;
+    memset(&R.info, 0, sizeof(R.info));
+    if (e->trunc_level >= 0) {
+      const int64_t size = encoder_trunc_trial(e, (uint32_t)e->trunc_level);
+      if (size < 0) return (int)size;
+      R.info.level = R.info.first_guess = (uint32_t)e->trunc_level; R.info.passes = 1; R.info.bytes = (uint64_t)size;
+      R.info.lossless = e->trunc_level == 0;
+      for (uint8_t t : R.band_drop) R.info.max_dropped = std::max<uint32_t>(R.info.max_dropped, t);
+      return OJPHGPU_OK;
+    }
+    HIPCHK(hipMemcpyAsync(R.h_hist.data(), R.hist.p, R.h_hist.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    struct Ctx { ojphgpu_encoder* e; int64_t last; } ctx{ e, -1 };
+    auto fn = [](void* u, uint32_t j) -> int64_t { Ctx* c = (Ctx*)u; c->last = (int64_t)j; return encoder_trunc_trial(c->e, j); };
+    int rc = trunc_search(R.ladder, e->P->blocks.size(), R.h_hist.data(), e->trunc_bytes, fn, &ctx, &R.info);
+    if (rc) return rc;
+    if (ctx.last != (int64_t)R.info.level) {                // the last trial was not j*: coded once more, the size must be the one measured
+      const int64_t size = encoder_trunc_trial(e, R.info.level);
+      if (size < 0) return (int)size;
+      if ((uint64_t)size != R.info.bytes) return OJPHGPU_E_HIP;
+    }
+    return OJPHGPU_OK;
+  };
+  R.search_rc = no_throw(run);
+  R.searched = true;
+  R.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return R.search_rc;
 }
 
 // ---------------------------------------------------------------------------------------------

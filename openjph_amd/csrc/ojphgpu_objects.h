@@ -510,6 +510,21 @@ struct EncoderQuality {
   ~EncoderQuality();
 };
 
+// What an encoder that codes reversible frames under a byte cap keeps (include/ojphgpu.h section 5f; made by the first
+// ojphgpu_encoder_set_truncation / _set_trunc_level)
+struct EncoderTrunc {
+  TruncLadder ladder;
+  DeviceBuf block_class, drop, stats_descs, hist;  // the blocks' classes, a table (a byte per class), the integer statistics
+  uint32_t n_stats = 0, stats_max_w = 0, stats_max_h = 0;
+  std::vector<uint32_t> h_hist;
+  std::vector<uint8_t> h_drop, band_drop;          // per class: the table being uploaded; per band: the table the device results stand at
+  bool searched = false; int search_rc = 0;        // the last run has been coded, with this verdict
+  bool have_info = false;
+  ojphgpu_trunc_info info;
+  double search_ms = 0;                            // host clock of the last finish's coding: every trial, and j* once more
+  ~EncoderTrunc() { for (DeviceBuf* b : { &block_class, &drop, &stats_descs, &hist }) b->release(); }
+};
+
 struct ojphgpu_encoder {
   const ojphgpu_plan* handle = nullptr;
   const Plan* P = nullptr;
@@ -595,6 +610,10 @@ struct ojphgpu_encoder {
   EncoderQuality* quality = nullptr;
   // the blocks are coded by a search in ojphgpu_encoder_finish*, and Tier-2 writes from the search's plan
   bool searches() const { return !budgets.empty() || quality_on; }
+  // section 5f: reversible frames under a byte cap (trunc_bytes) or at a fixed level of the ladder (trunc_level >= 0); the
+  // blocks are coded in ojphgpu_encoder_finish, Tier-2 writes from the encoder's own plan with the table's missing_msbs
+  bool trunc_on = false; uint64_t trunc_bytes = 0; int32_t trunc_level = -1;
+  EncoderTrunc* trunc = nullptr;
 };
 // May the next run of e be released?  Not one that writes into a frame pipe's slot (the pipe records its own hand-over
 // events behind the run), not a searching one (the search goes on reading the arena on the caller's stream), and not with
@@ -602,7 +621,7 @@ struct ojphgpu_encoder {
 // launch, blocks-only encoders, OJPHGPU_NO_OVERLAP=1 and OJPHGPU_ENC_RELEASE=0 never can (can_release).
 inline bool encoder_releases(const ojphgpu_encoder* e)
 {
-  return e->can_release && e->cut_released.n_top && !e->o_out && !e->o_results && !e->o_counters && !e->searches() && !e->timer.detail;
+  return e->can_release && e->cut_released.n_top && !e->o_out && !e->o_results && !e->o_counters && !e->searches() && !e->trunc_on && !e->timer.detail;
 }
 // The stream-level join of a released run: e->stream waits for the branches' done events (no host synchronisation).
 // Called before anything is enqueued on e->stream -- or e->stream is synchronised -- to read or overwrite the products.
@@ -660,16 +679,18 @@ int ojphgpu_encoder_run_container(ojphgpu_encoder* e, const void* d_image, int c
 int ojphgpu_encoder_create_joined(const ojphgpu_plan* plan, int device, void* stream, ojphgpu_encoder** out);
 
 // The plan-order coded-block table of one frame from the block coder's results: res[i] = the frame's block block_ids[i];
-// P = the plan the blocks were quantised with (its bands give K_max); blocks outside block_ids stay empty
+// P = the plan the blocks were quantised with (its bands give K_max); blocks outside block_ids stay empty.  band_drop
+// (section 5f; null: none): the bit-planes the blocks of every band of the plan were coded without
 inline void ojphgpu_coded_blocks(const Plan& P, const std::vector<uint32_t>& block_ids, const ojphgpu_cb_result* res,
-                                 std::vector<ojphgpu_coded_block>& cb)
+                                 std::vector<ojphgpu_coded_block>& cb, const uint8_t* band_drop = nullptr)
 {
   cb.assign(P.blocks.size(), ojphgpu_coded_block{ 0, 0, 0, 0, 0 });
   for (size_t i = 0; i < block_ids.size(); ++i) {
     const ojphgpu_cb_result& r = res[i];
     ojphgpu_coded_block& c = cb[block_ids[i]];
     c.offset = r.offset; c.len1 = r.length; c.len2 = 0;
-    c.missing_msbs = r.length ? P.bands[P.blocks[block_ids[i]].band].K_max - 1 : 0;      // ojph_codeblock.cpp:148
+    const uint32_t band = P.blocks[block_ids[i]].band;
+    c.missing_msbs = r.length ? P.bands[band].K_max - 1 - (band_drop ? band_drop[band] : 0u) : 0;   // ojph_codeblock.cpp:148
     c.num_passes = r.length ? 1 : 0;
   }
 }

@@ -287,6 +287,28 @@ class Plan:
             check(self._lib.ojphgpu_plan_padded_blocks(self.handle, out.ctypes.data, int(n.value), C.byref(n)))
         return out
 
+    @property
+    def trunc_levels(self):
+        """J, the number of levels of the truncation ladder (include/ojphgpu.h section 5f); OjphError E_INVALID for a plan the
+        section refuses"""
+        n = C.c_uint32()
+        check(self._lib.ojphgpu_plan_trunc_levels(self.handle, C.byref(n)), "plan_trunc_levels")
+        return int(n.value)
+
+    def trunc_weights(self):
+        """q_b, the weight of every band of the plan in quarter planes (int32 [num_bands])"""
+        q = np.zeros(self.num_bands, np.int32)
+        check(self._lib.ojphgpu_plan_trunc_weights(self.handle, q.ctypes.data), "plan_trunc_weights")
+        return q
+
+    def trunc_table(self, j):
+        """t_b(j), the bit-planes every band of the plan drops at level j (uint8 [num_bands])"""
+        t = np.zeros(self.num_bands, np.uint8)
+        if not 0 <= int(j) < 2 ** 32:
+            check(capi.E_INVALID, "plan_trunc_table")
+        check(self._lib.ojphgpu_plan_trunc_table(self.handle, int(j), t.ctypes.data), "plan_trunc_table")
+        return t
+
     def t2_write(self, block_data: np.ndarray, coded: np.ndarray) -> bytes:
         """block_data: uint8 array; coded: coded_dtype array (offset/len1/...) in plan order."""
         block_data = np.ascontiguousarray(block_data, dtype=np.uint8)
@@ -364,6 +386,67 @@ def rate_search(plan: Plan, hist, max_bytes, size_fn, hint=None):
     out = {k: getattr(info, k) for k, _ in capi.RateInfo._fields_}
     if rc != capi.OK:
         err = capi.OjphError(rc, "rate_search")
+        err.info = out
+        raise err
+    return out
+
+
+def trunc_synth_norm(depth, high):
+    """L2 norm of the 1-D 5/3 synthesis basis vector of the low / high branch at decomposition depth `depth`: a unit impulse
+    through the linear inverse lifting, in float64, in the middle of a line of 64 coefficients at that depth (beyond depth
+    12: times sqrt(2) per further level, as the C code)"""
+    if depth == 0:
+        return 1.0
+    dd = min(int(depth), 12)
+    s, h = np.zeros(64), np.zeros(64)
+    (h if high else s)[32] = 1.0
+    for _ in range(dd):
+        n = len(s)
+        x = np.zeros(2 * n)
+        x[0::2] = s - (np.concatenate([h[:1], h[:-1]]) + h) / 4.0
+        x[1::2] = h + (x[0::2] + np.concatenate([x[2::2], x[-2:-1]])) / 2.0
+        s, h = x, np.zeros(2 * n)
+    return float(np.sqrt((s * s).sum()) * 2.0 ** (0.5 * (depth - dd)))
+
+
+def trunc_table_np(bands, num_decomps, rct, j=None):
+    """The ladder of include/ojphgpu.h section 5f restated in numpy from the band list alone: bands = plan.bands (fields comp,
+    res, band, K_max), num_decomps = the decompositions of every component, rct = the reversible colour transform is on.
+    -> (q int32 [bands], J, tie) with tie = the smallest distance of a 4 w_b from a rounding tie; with j also t_b(j) uint8
+    as a fourth value."""
+    comp, res, ori = (np.asarray(bands[k]).astype(np.int64) for k in ("comp", "res", "band"))
+    top = np.maximum(np.asarray(bands["K_max"]).astype(np.int64), 1) - 1
+    depth = np.where(res == 0, num_decomps, num_decomps - res + 1)
+    norms = {(d, hi): trunc_synth_norm(d, hi) for d in set(depth.tolist()) for hi in (False, True)}
+    gh = np.array([norms[(d, o in (1, 3))] for d, o in zip(depth.tolist(), ori.tolist())])
+    gv = np.array([norms[(d, o in (2, 3))] for d, o in zip(depth.tolist(), ori.tolist())])
+    gc = np.ones(len(comp))
+    if rct:
+        gc = np.where(comp == 0, np.sqrt(3.0), np.where(comp < 3, np.sqrt(11.0 / 16.0), 1.0))
+    w = np.log2(gh * gv * gc)
+    x = 4.0 * (w - w.min())
+    q = np.floor(x + 0.5).astype(np.int64)
+    tie = float(np.abs(x - np.floor(x) - 0.5).min())
+    J = int((4 * top + q).max() - 3 + 1)
+    out = (q.astype(np.int32), max(J, 1), tie)
+    if j is not None:
+        out += (np.clip((int(j) + 3 - q) // 4, 0, top).astype(np.uint8),)
+    return out
+
+
+def trunc_search(plan: Plan, hist, max_bytes, size_fn):
+    """ojphgpu_trunc_search: hist uint32 [plan.num_bands, 80] of ojphgpu_band_stats_int (None: no model), size_fn(j) -> bytes
+    of the codestream at level j.  -> dict(level, passes, first_guess, max_dropped, lossless, bytes, bytes_finer);
+    capi.OjphError with .code == capi.E_BUDGET (and .info = the dict) when not even the last level fits."""
+    info = capi.TruncInfo()
+    cb = capi.SIZE_FN(lambda user, j: int(size_fn(int(j))))
+    h = None if hist is None else np.ascontiguousarray(hist, dtype=np.uint32)
+    if h is not None and h.size != plan.num_bands * capi.STATS_BINS:
+        raise ValueError("hist must hold 80 bins for every band of the plan")
+    rc = capi.lib().ojphgpu_trunc_search(plan.handle, None if h is None else h.ctypes.data, int(max_bytes), cb, None, C.byref(info))
+    out = {k: int(getattr(info, k)) for k, _ in capi.TruncInfo._fields_ if k != "reserved"}
+    if rc != capi.OK:
+        err = capi.OjphError(rc, "trunc_search")
         err.info = out
         raise err
     return out

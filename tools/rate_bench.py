@@ -29,7 +29,16 @@ the batch's search and the sum of the frames' passes, median ms of (a) (b) (c), 
 --first N: the first budgeted frame of a fresh encoder -- what a one-shot caller (ojph_compress with a byte budget) pays, with
 no plan copy of any grid index made yet: per budget N encoders in turn, each made, run once on the C3 frame and timed on
 the host clock around finish() alone.  Prints one JSON line per budget: every time and the median.
-  python tools/rate_bench.py --first 7 [--rows 4320]"""
+  python tools/rate_bench.py --first 7 [--rows 4320]
+
+--trunc: a reversible frame under a byte cap (include/ojphgpu.h section 5f): a 4K 4:4:4 16-bit frame (the C7 family scaled
+to 16 bits; 16-bit containers in HBM), 5/3 with the RCT, at caps of 0.9, 0.6 and 0.3 of its lossless size.  Per cap two
+encoders take turns, `--runs` rounds after `--warmup`: (a) the capped encode, run_device + finish; (b) the plain lossless
+encode, which runs none of the new code -- what it costs at the parent commit is bench.py's comparison, not this tool's.
+Prints one JSON line per cap: level, passes (trials per search), first guess, the largest number of planes a band drops,
+median ms of (a) and (b), the coding inside finish, and the integer statistics kernel's time (device events) with its
+fraction of the 8 TB/s HBM peak beside the level-1 DWT launch of the same run.
+  python tools/rate_bench.py --trunc [--runs 10] [--warmup 3] [--rows 2160]"""
 import argparse
 import json
 import os
@@ -159,6 +168,57 @@ def batch_bench(a):
             flush=True)
 
 
+def trunc_bench(a):
+    import torch
+    from openjph_amd import codec
+    from openjph_amd.plan import make_params
+    from tests import synth
+    rows = min(a.rows, 2160)
+    rng = np.random.default_rng(1234)
+    img = synth._noisy(synth._family(2160, 3840, 32768, 14400, 12800, 4800, 197, 161, 23), rng.normal(0, 640, (3, 2160, 3840)), 65535)[:, :rows]
+    nc, h, w = img.shape
+    d_img = torch.from_numpy(np.ascontiguousarray(img).astype(np.uint16).view(np.int16)).cuda()
+    samples = img.size
+    del img
+    params = make_params(w, h, nc, bit_depth=16, reversible=True, color_transform=True)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def run(enc):
+        enc.run_device(d_img)
+        return enc.finish()
+    plain = codec.Encoder(params)
+    capped = codec.Encoder(params)
+    lossless = len(run(plain))
+    for share in (0.9, 0.6, 0.3):
+        cap = int(lossless * share)
+        capped.set_truncation(cap)
+        t = {"capped": [], "plain": []}
+        info = timing = stats = None
+        for i in range(a.warmup + a.runs):
+            ms, cs = timed(lambda: run(capped))
+            info, timing, stats = capped.trunc_info(), capped.trunc_timing(), capped.timing()
+            assert len(cs) == info["bytes"] <= cap < info["bytes_finer"]
+            ms_plain, cs_plain = timed(lambda: run(plain))
+            assert len(cs_plain) == lossless
+            if i >= a.warmup:
+                t["capped"].append(ms); t["plain"].append(ms_plain)
+        med = {k: round(float(np.median(v)), 3) for k, v in t.items()}
+        print(json.dumps(dict(
+            frame="c7 family x 16, %dx%dx%d 16-bit, 16-bit containers, 5/3 + RCT" % (w, h, nc), lossless_bytes=lossless, share=share, cap=cap,
+            level=info["level"], levels=capped.plan.trunc_levels, bytes=info["bytes"], bytes_finer=info["bytes_finer"], passes=info["passes"],
+            first_guess=info["first_guess"], max_dropped=info["max_dropped"], ms_capped=med["capped"], ms_plain_lossless=med["plain"],
+            capped_over_plain=round(med["capped"] / med["plain"], 3), coding_in_finish_ms=round(timing["search_ms"], 3),
+            run_device_ms=round(stats["total_ms"], 3), stats_int_kernel_ms=round(timing["stats_ms"], 4),
+            stats_hbm_fraction=round(4.0 * samples / (timing["stats_ms"] * 1e-3) / HBM_PEAK, 3) if timing["stats_ms"] > 0 else None,
+            dwt_level1_ms=round(stats["dwt_levels_ms"][0], 4))), flush=True)
+
+
 def first_frame_bench(a):
     import torch
     from openjph_amd import codec
@@ -199,7 +259,10 @@ def main():
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--batch", type=int, default=0, help="B: the budgets of a batch encoder of B 4K frames against B single encodes")
     ap.add_argument("--first", type=int, default=0, help="N: finish() of the first budgeted frame of N fresh encoders per budget")
+    ap.add_argument("--trunc", action="store_true", help="a reversible 4K 16-bit frame under caps of 0.9, 0.6 and 0.3 of its lossless size")
     a = ap.parse_args()
+    if a.trunc:
+        return trunc_bench(a)
     if a.first:
         return first_frame_bench(a)
     if a.pipe:
