@@ -1049,6 +1049,45 @@ int  ojphgpu_encoder_trunc_info(ojphgpu_encoder* enc, ojphgpu_trunc_info* info);
 int  ojphgpu_encoder_trunc_timing(ojphgpu_encoder* enc, float out[2]);
 
 /* ------------------------------------------------------------------------------------------ *
+ * 5g. Near-lossless coding of a reversible frame, the host side: the other half of section 5f's rate control -- the
+ *    smallest codestream of the ladder whose decode stays within an error bound.  What is here is the contract and the
+ *    search; the encoder mode that would measure the levels on the device is not built yet.
+ *
+ *    u[0] = 0 < u[1] < ... < u[U - 1]: the levels of section 5f whose table differs from the level before.  SSE(j) / PAE(j):
+ *    the exact sum of squared differences / the largest absolute difference between the caller's frame and the int32 frame
+ *    ojphgpu_decoder_run_device returns for the codestream of level j (ojphgpu_encoder_set_trunc_level(j)), over every
+ *    component on its own grid.  A target is max_sse = T and / or max_pae = E; UINT64_MAX / UINT32_MAX: no bound; both
+ *    unbounded: OJPHGPU_E_INVALID.  A level MEETS when SSE(j) <= T and PAE(j) <= E.  The result is an index k*, u[k*] the
+ *    level to code -- at k* = 0 the plain lossless encode.  The certificate: u[k*] meets (measured; level 0 meets by the
+ *    reversible path's own contract and is never measured), and k* == U - 1 or u[k* + 1] is measured not to meet.  Neither
+ *    figure is monotone over the ladder: any index with the certificate is an answer, and nothing is assumed between two
+ *    measured levels.  There is no failure code: level 0 always meets, and T = 0 or E = 0 gives it without a trial (then no
+ *    coarser neighbour is measured either).
+ *
+ *    No block needs coding to measure a level: the planes truncated per band -- magnitude m -> 0 where m >> t == 0, else
+ *    (m >> t << t) | 1 << (t - 1), sign kept -- and taken through the decoder's synthesis ARE the decode of the codestream
+ *    of that table, sample for sample (tests/test_cpu_near_lossless.py, against the reference's decode).
+ *    Plans: those of section 5f, and no component deeper than 16 bits (ojphgpu_frame_error's sum bound).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ojphgpu_near_lossless_info {
+  uint32_t level;                                        /* u[k*]                                               */
+  uint32_t passes;                                       /* calls of err_fn                                     */
+  uint32_t lossless;                                     /* k* == 0: the codestream is the plain encode's       */
+  uint32_t max_dropped;                                  /* the largest t_b of that level                       */
+  uint32_t pae, level_coarser, pae_coarser, reserved;    /* PAE(u[k*]) (0 at level 0); u[k* + 1] and its PAE --  */
+  uint64_t sse, sse_coarser;                             /* SSE likewise -- the neighbour measured not to meet,
+                                                            zeros when k* == U - 1 or nothing was measured       */
+  uint64_t bytes;                                        /* the codestream's length: for the caller that codes
+                                                            the level to fill; the search leaves 0               */
+} ojphgpu_near_lossless_info;
+typedef int (*ojphgpu_err_fn)(void* user, uint32_t level, uint64_t* sse, uint32_t* pae);   /* 0, or an error (returned as it is) */
+/* The search, host only (no HIP call): lo = 0 (meets, unmeasured), hi = U (virtual, does not meet); u[lo + (hi - lo) / 2] is
+ * measured and the end its verdict names moves there, until hi - lo == 1: k* = lo.  passes <= ceil(log2 U) for every
+ * err_fn, no level is asked twice.  (A first guess led by the integer band statistics, as section 5f has one, is not made.) */
+int  ojphgpu_near_lossless_search(const ojphgpu_plan* plan, uint64_t max_sse, uint32_t max_pae, ojphgpu_err_fn err_fn, void* user,
+                                  ojphgpu_near_lossless_info* info);
+
+/* ------------------------------------------------------------------------------------------ *
  * 5c. Encoding to a quality target: the other half of rate control.  Over the grid of section 5b, SSE(j) = the sum, over
  *    every component and every sample of it on its own grid, of (original - decoded)^2, where `decoded` is what
  *    ojphgpu_decoder_run_device returns (int32 samples: a sample the reference leaves one past its range stays there, where a

@@ -160,6 +160,15 @@ class TruncInfo(C.Structure):             # ojphgpu_trunc_info
                 ("lossless", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("bytes_finer", C.c_uint64)]
 
 
+class NearLosslessInfo(C.Structure):      # ojphgpu_near_lossless_info
+    _fields_ = [("level", C.c_uint32), ("passes", C.c_uint32), ("lossless", C.c_uint32), ("max_dropped", C.c_uint32),
+                ("pae", C.c_uint32), ("level_coarser", C.c_uint32), ("pae_coarser", C.c_uint32), ("reserved", C.c_uint32),
+                ("sse", C.c_uint64), ("sse_coarser", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+ERR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))      # ojphgpu_err_fn
+
+
 class RequantDesc(C.Structure):           # ojphgpu_requant_desc
     _fields_ = [("plane_off", C.c_uint64), ("pitch", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("delta_inv", C.c_float),
                 ("delta", C.c_float), ("K_max", C.c_uint32)]
@@ -425,6 +434,7 @@ SIGNATURES = {
     "ojphgpu_encoder_set_trunc_level": (C.c_int, [C.c_void_p, C.c_int32]),
     "ojphgpu_encoder_trunc_info": (C.c_int, [C.c_void_p, C.POINTER(TruncInfo)]),
     "ojphgpu_encoder_trunc_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ojphgpu_near_lossless_search": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, ERR_FN, C.c_void_p, C.POINTER(NearLosslessInfo)]),
     "ojphgpu_rate_grid_qstep": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
     "ojphgpu_rate_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),
     "ojphgpu_rate_search_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, SIZE_FN, C.c_void_p, C.POINTER(RateInfo)]),

@@ -266,6 +266,9 @@ bool trunc_plan_ok(const Plan& P);                           // reversible Part-
 int  trunc_ladder_build(const Plan& P, TruncLadder& T);
 int  trunc_search(const TruncLadder& T, uint64_t num_blocks, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user,
                   ojphgpu_trunc_info* out);
+std::vector<uint32_t> trunc_distinct_levels(const TruncLadder& T);   // the levels whose table differs from the level before
+// near-lossless coding (section 5g): the coarsest distinct level found that meets max_sse and max_pae, by halving
+int  near_lossless_search(const TruncLadder& T, uint64_t max_sse, uint32_t max_pae, ojphgpu_err_fn fn, void* user, ojphgpu_near_lossless_info* out);
 // missing_msbs = K_max - 1 - t[class] and bit 3 of `reversible` (set where t > 0) into the block descriptors: block i from
 // d_drop[d_class[i]] (kernels_stats.hip)
 int  trunc_descs_launch(void* stream, ojphgpu_cb_desc* d_descs, uint32_t nb, const uint32_t* d_class, const uint8_t* d_drop);

@@ -682,16 +682,22 @@ static double trunc_predict(const TruncLadder& T, const uint32_t* hist, uint64_t
   return bits / 8.0 + 300.0 + 6.0 * (double)num_blocks;
 }
 
-int trunc_search(const TruncLadder& T, uint64_t num_blocks, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_trunc_info* out)
+// the levels whose table differs from the level before (level 0 first)
+std::vector<uint32_t> trunc_distinct_levels(const TruncLadder& T)
 {
-  memset(out, 0, sizeof(*out));
-  // the levels whose table differs from the level before: only they are measured
   std::vector<uint32_t> u;
   for (uint32_t j = 0; j < T.levels; ++j) {
     bool differs = j == 0;
     for (size_t b = 0; b < T.q.size() && !differs; ++b) differs = T.drop(j, b) != T.drop(j - 1, b);
     if (differs) u.push_back(j);
   }
+  return u;
+}
+
+int trunc_search(const TruncLadder& T, uint64_t num_blocks, const uint32_t* hist, uint64_t max_bytes, ojphgpu_size_fn fn, void* user, ojphgpu_trunc_info* out)
+{
+  memset(out, 0, sizeof(*out));
+  const std::vector<uint32_t> u = trunc_distinct_levels(T);   // only they are measured
   const int64_t U = (int64_t)u.size();
   // lo: the largest index measured NOT to fit (-1: none), hi: the smallest measured to fit (U: none); hi - lo == 1 ends it
   int64_t lo = -1, hi = U; uint64_t size_lo = 0, size_hi = 0;
@@ -721,6 +727,29 @@ int trunc_search(const TruncLadder& T, uint64_t num_blocks, const uint32_t* hist
   if (hi == U) return OJPHGPU_E_BUDGET;
   out->level = u[(size_t)hi]; out->bytes = size_hi; out->bytes_finer = lo >= 0 ? size_lo : 0;
   out->lossless = hi == 0;
+  for (size_t b = 0; b < T.q.size(); ++b) out->max_dropped = std::max<uint32_t>(out->max_dropped, T.drop(out->level, b));
+  return OJPHGPU_OK;
+}
+
+// Near-lossless coding (include/ojphgpu.h section 5g): the coarsest distinct level found that meets both bounds, by halving
+// between level 0 (meets by contract, never measured) and a virtual level behind the last (does not meet).  Nothing is
+// assumed of fn between two measured levels: the certificate is the measurement of u[k*] and that of u[k* + 1].
+int near_lossless_search(const TruncLadder& T, uint64_t max_sse, uint32_t max_pae, ojphgpu_err_fn fn, void* user, ojphgpu_near_lossless_info* out)
+{
+  memset(out, 0, sizeof(*out));
+  if (max_sse == UINT64_MAX && max_pae == UINT32_MAX) return OJPHGPU_E_INVALID;
+  const std::vector<uint32_t> u = trunc_distinct_levels(T);
+  size_t lo = 0, hi = max_sse == 0 || max_pae == 0 ? 1 : u.size();   // (a bound of 0: level 0, the only level known to meet it)
+  while (hi - lo > 1) {
+    const size_t k = lo + (hi - lo) / 2;
+    uint64_t sse = 0; uint32_t pae = 0;
+    const int rc = fn(user, u[k], &sse, &pae);
+    if (rc) return rc;
+    out->passes++;
+    if (sse <= max_sse && pae <= max_pae) { lo = k; out->sse = sse; out->pae = pae; }
+    else { hi = k; out->level_coarser = u[k]; out->sse_coarser = sse; out->pae_coarser = pae; }
+  }
+  out->level = u[lo]; out->lossless = lo == 0;
   for (size_t b = 0; b < T.q.size(); ++b) out->max_dropped = std::max<uint32_t>(out->max_dropped, T.drop(out->level, b));
   return OJPHGPU_OK;
 }
@@ -773,5 +802,18 @@ extern "C" int ojphgpu_trunc_search(const ojphgpu_plan* plan, const uint32_t* hi
     const int rc = trunc_ladder_build(plan->plan, T);
     if (rc) return rc;
     return trunc_search(T, plan->plan.blocks.size(), hist, max_bytes, fn, user, info);
+  });
+}
+
+extern "C" int ojphgpu_near_lossless_search(const ojphgpu_plan* plan, uint64_t max_sse, uint32_t max_pae, ojphgpu_err_fn err_fn, void* user,
+                                            ojphgpu_near_lossless_info* info)
+{
+  if (!plan || !err_fn || !info) return OJPHGPU_E_INVALID;
+  return no_throw([&]() -> int {
+    TruncLadder T;
+    const int rc = trunc_ladder_build(plan->plan, T);
+    if (rc) return rc;
+    for (const CompGeo& g : plan->plan.comps) if (g.bit_depth > 16) return OJPHGPU_E_INVALID;
+    return near_lossless_search(T, max_sse, max_pae, err_fn, user, info);
   });
 }

@@ -452,6 +452,23 @@ def trunc_search(plan: Plan, hist, max_bytes, size_fn):
     return out
 
 
+def near_lossless_search(plan: Plan, max_sse, max_pae, err_fn):
+    """ojphgpu_near_lossless_search: max_sse / max_pae None = no bound; err_fn(level) -> (sse, pae) of the decode of the
+    codestream at that level.  -> dict(level, passes, lossless, max_dropped, sse, pae, level_coarser, sse_coarser, pae_coarser,
+    bytes = 0)"""
+    info = capi.NearLosslessInfo()
+
+    def trial(user, level, sse, pae):
+        a, b = err_fn(int(level))
+        sse[0], pae[0] = int(a), int(b)
+        return 0
+
+    t = 2 ** 64 - 1 if max_sse is None else int(max_sse)
+    e = 2 ** 32 - 1 if max_pae is None else int(max_pae)
+    check(capi.lib().ojphgpu_near_lossless_search(plan.handle, t, e, capi.ERR_FN(trial), None, C.byref(info)), "near_lossless_search")
+    return {k: int(getattr(info, k)) for k, _ in capi.NearLosslessInfo._fields_ if k != "reserved"}
+
+
 def quality_search(max_sse, sse_fn, hint=None):
     """ojphgpu_quality_search, or with hint = a grid index (-1: none) ojphgpu_quality_search_hint (the first trial is `hint`,
     then its neighbours on the side the result points to; in a sequence: the previous frame's answer): sse_fn(j) -> SSE of
